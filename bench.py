@@ -20,6 +20,11 @@ algorithmic 6*T*r*(d_in+d_out) count per second.  At N = 
 keys measured in the same process after the headline: `dense` (the steady state after the first accumulate(): dense
 frozen accumulator, MFMA-bound), `fp32` (the exact-fp32 parity path against the 157 TF fp32 matrix peak) and `train`
 (a full llama_60m training step through the module-swap surface) -- skip them with --only-headline.
+
+`--dump-outputs DIR` writes what the timed path handed its caller in the last timed step as DIR/<name>.npy (float32),
+so that two builds can be compared output for output on the same seeded inputs: per layer `b<block>_<name>_y`,
+`b<block>_<name>_dx` (a fixed, seeded sample of the token rows, the same rows for every layer) and `..._dA`, `..._dB`
+(whole); `--mode train` writes the last step's `loss`.  At most DUMP_BYTES in all.
 """
 import argparse
 import gc
@@ -35,7 +40,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0     # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
+HBM_PEAK_GBS = 8000.0     # MI355X HBM3E spec peak
 MFMA_BF16_TFLOPS = 2500.0  # dense bf16 MFMA peak
 MFMA_F32_TFLOPS = 157.0    # fp32 matrix peak
 # HBM bytes per launch of the roofline kernel, from the rocprofv3 PMC passes made at the commit named inside the file
@@ -46,6 +51,8 @@ DENSE_KERNEL = "sow::gemm4_kernel<false, true, false> = gemm4h (projection pass 
 LLAMA_60M = dict(hidden=512, inter=1376, layers=8)
 BLOCK_NAMES = ["q", "k", "v", "o", "gate", "up", "down"]
 BLOCK_GROUPS = [[0, 1, 2], [3], [4, 5], [6]]   # model-independent layers inside one decoder block
+DUMP_BYTES = 64 * 10**6    # --dump-outputs: everything one run writes, .npy headers (128 bytes each) included
+DUMP_ROWS = 128            # --dump-outputs: sampled token rows of y / dX per layer (fewer when the budget needs it)
 
 
 def layer_shapes():
@@ -94,7 +101,12 @@ def parse():
     ap.add_argument("--dry-run", action="store_true",
                     help="stop after torch.distributed is up: print {n_gpus, rccl} and exit (launcher / rendezvous rehearsal; with "
                          "SOW_BENCH_BACKEND=gloo it needs no GPU)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (see the module docstring)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def launch_ranks(args):
@@ -230,6 +242,36 @@ class Stack:
         return offs[lo], (offs[hi] if hi < len(offs) else self.bucket.padded_numel)
 
 
+def stack_outputs(stack):
+    """name -> tensor: what one step of the stack hands its caller.  y and dX of every layer on a seeded sample of the token
+    rows (the same rows for every layer; as many as DUMP_BYTES leaves after the factor gradients, at most DUMP_ROWS), dA and
+    dB whole."""
+    width = sum(di + do for di, do in stack.shapes)          # float32 elements per sampled row, and per unit of rank
+    n_rows = min(stack.T, DUMP_ROWS, (DUMP_BYTES - 4 * 128 * len(stack.calls)) // 4 // width - stack.r)
+    if n_rows < 1:
+        sys.exit(f"bench.py: --dump-outputs: the factor gradients at rank {stack.r} alone exceed {DUMP_BYTES // 10**6} MB")
+    rows = torch.randperm(stack.T, generator=torch.Generator().manual_seed(0))[:n_rows].sort().values
+    rows = rows.to(stack.x[0].device)
+    nb = len(BLOCK_NAMES)
+    out = {}
+    for li, c in enumerate(stack.calls):
+        tag = f"b{li // nb}_{BLOCK_NAMES[li % nb]}"
+        out[tag + "_y"] = c.y.index_select(0, rows)
+        out[tag + "_dx"] = c.dx.index_select(0, rows)
+        out[tag + "_dA"] = stack.A[li].grad
+        out[tag + "_dB"] = stack.B[li].grad
+    return out
+
+
+def write_outputs(out_dir, arrays):
+    """arrays (name -> tensor) as out_dir/<name>.npy in float32 (float64 stays float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        np.save(os.path.join(out_dir, name + ".npy"), (t.double() if t.dtype == torch.float64 else t.float()).numpy())
+
+
 def algorithmic(shapes, T, r, es, acc):
     flops = sum(6 * T * r * (di + do) + (4 * T * di * do if acc == "dense" else 0) for di, do in shapes)
     nbytes = sum(T * (3 * di + 2 * do) * es + 2 * T * r * es for di, do in shapes)
@@ -310,7 +352,7 @@ def cpu_baseline(shapes, T, r):
     return out
 
 
-def train_mode(args, world, rank, device, steps=None, warmup=None, quiet=False):
+def train_mode(args, world, rank, device, steps=None, warmup=None, quiet=False, dump=None):
     """Caller protocol of the reference's scripts/simple_train.py:316-333, 389-405, 425-428, 502-506, 566-572,
     596-650 with synthetic tokens: llama_60m from the JSON's numbers, prepare_sow(rank 50, normal_QR),
     bf16 cast after the swap, AdamW with two groups, accumulate + reset_optimizer between backward and step.
@@ -402,6 +444,8 @@ def train_mode(args, world, rank, device, steps=None, warmup=None, quiet=False):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     ms = elapsed / steps * 1e3
+    if dump and rank == 0:
+        write_outputs(dump, {"loss": loss.detach().double()})
     out = {
         "metric": "llama_60m --architecture sow rank=50 training tokens/s (full step, synthetic tokens)",
         "value": batch * seq * world / (ms * 1e-3), "unit": "tokens/s", "n_gpus": world, "steps": steps,
@@ -467,10 +511,11 @@ def _stats(ms_list):
     return {"median": med, "min": v[0], "max": v[-1], "mean": sum(v) / n, "per_replay_ms": [round(x, 4) for x in ms_list]}
 
 
-def measure_stack(args, dtype_name, acc, world, rank, device, steps, warmup, detail, warm_replays=5):
+def measure_stack(args, dtype_name, acc, world, rank, device, steps, warmup, detail, warm_replays=5, dump=None):
     """Build the stack, capture the step, time `steps` replays (barrier + synchronize on both sides, max over ranks).
     Every replay is also bracketed by HIP events on the launch stream (`replays`: median / min / max / per-replay list), so a
-    record shows whether a slow figure was one stall or a uniform slowdown.
+    record shows whether a slow figure was one stall or a uniform slowdown.  `dump`: rank 0 writes stack_outputs() of the
+    last timed step there, before any further launch.
 
     N > 1: the step is cut into a forward graph and one backward graph per decoder block (last block first); after each
     block's graph the all-reduce of THAT block's slice of the flat factor-gradient bucket is issued on the bucket's side
@@ -561,6 +606,8 @@ def measure_stack(args, dtype_name, acc, world, rank, device, steps, warmup, det
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             elapsed = float(tmax.item())
         ms = elapsed / steps * 1e3
+        if dump and rank == 0:
+            write_outputs(dump, stack_outputs(stack))
         flops, nbytes = algorithmic(shapes, T, args.rank, es, acc)
         res.update(ms_per_step=ms, flops=flops, nbytes=nbytes, graph=graphs is not None, T=T, shapes=shapes, es=es,
                    replays=_stats([ev[i].elapsed_time(ev[i + 1]) for i in range(steps)]), overlap=overlap)
@@ -714,12 +761,13 @@ def main():
     from sow_amd import _lib
     _lib.load()  # fail loudly when the HIP library is missing
     if args.mode == "train":
-        train_mode(args, world, rank, device)
+        train_mode(args, world, rank, device, dump=args.dump_outputs)
         if world > 1:
             dist.destroy_process_group()
         return
 
-    head = measure_stack(args, args.dtype, args.acc, world, rank, device, args.steps, args.warmup, detail=True)
+    head = measure_stack(args, args.dtype, args.acc, world, rank, device, args.steps, args.warmup, detail=True,
+                         dump=args.dump_outputs)
     ms, T, shapes, es = head["ms_per_step"], head["T"], head["shapes"], head["es"]
     if rank == 0:
         n_layers = len(shapes)

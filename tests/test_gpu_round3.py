@@ -285,6 +285,43 @@ def test_bench_launch_sequence_vs_oracle():
         assert rel_err(stack.B[li].grad.float().cpu(), dB_ref[0]) < 2e-2, ("dB", li)
 
 
+def test_bench_dump_outputs_holds_the_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR` in a child process: the line times exactly --steps replays; DIR holds one float32 .npy
+    per output of the 56 layers (y / dX on the sampled rows, dA / dB whole), within DUMP_BYTES in all, and each equals what
+    the same stack computes from the same seeded inputs in this process (tolerance as above)."""
+    import importlib.util
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    from conftest import ROOT
+    T, out_dir = 8192, tmp_path / "dump"
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--tokens", str(T),
+                          "--only-headline", "--no-cpu-baseline", "--dump-outputs", str(out_dir)],
+                         capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+    assert run.returncode == 0, run.stderr[-2000:]
+    rec = json.loads([ln for ln in run.stdout.splitlines() if ln.startswith("{")][-1])
+    assert rec["steps"] == 3 and len(rec["replays"]["per_replay_ms"]) == 3
+    spec = importlib.util.spec_from_file_location("bench_dump", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    files = sorted(os.listdir(out_dir))
+    assert len(files) == 4 * 56
+    assert sum(os.path.getsize(out_dir / f) for f in files) <= bench.DUMP_BYTES
+    stack = bench.Stack(bench.layer_shapes(), T, 50, torch.bfloat16, torch.device(DEV), "none")
+    stack.step()
+    torch.cuda.synchronize()
+    want = bench.stack_outputs(stack)
+    assert sorted(name + ".npy" for name in want) == files
+    for name, t in want.items():
+        got = np.load(out_dir / (name + ".npy"))
+        assert got.dtype == np.float32 and got.shape == tuple(t.shape), name
+        assert rel_err(torch.from_numpy(got), t.float().cpu()) < 2e-2, name
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # SURVEY 8 f4: tensor-train optimizer state through the batched entry points
 # ---------------------------------------------------------------------------------------------------------------

@@ -235,7 +235,7 @@ from tn_gradient.utils import closest_factorization, pad_matrix, unpad_matrix
 
 
 @pytest.mark.parametrize("where", list(DRIVER_IMPORTS))
-def test_driver_import_lines_resolve_to_sow_amd(where):
+def test_driver_import_lines_resolve_to_sow_amd(where, tmp_path):
     """`simple_train.py` / `finetune.py` unchanged: their tn_gradient imports, executed verbatim in a fresh interpreter with
     the repo first on sys.path, bind the sow_amd implementation."""
     code = ("import sys; sys.path.insert(0, %r)\n" % ROOT) + DRIVER_IMPORTS[where] + """
@@ -246,7 +246,7 @@ for name, obj in list(globals().items()):
         assert obj is getattr(sow_amd, name), name
 print('ok')
 """ % ROOT
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd="/tmp")
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=str(tmp_path))
     assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stderr
 
 
