@@ -130,7 +130,8 @@ def sow_forward(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, ac
                 save_h: bool = True):
     """y, h_save = forward of the SoW contraction on a flattened [T, d_in] input.  save_h = False (no-grad / eval callers,
     e.g. the reload + generate loop of commonsense_evaluate.py:268-287): the projection is not written to HBM and None
-    is returned in its place (r <= 64; wider ranks compose two GEMMs and need the buffer as their intermediate)."""
+    is returned in its place (r <= 64 without a dense accumulator; wider ranks compose two GEMMs and need the buffer as
+    their intermediate, a dense accumulator's fused kernels write it as scratch)."""
     lib = _lib.load()
     dev = _need_gpu(x2, A, B, acc_down if acc_down is not None and acc_down.numel() else None,
                     acc_up if acc_up is not None and acc_up.numel() else None, bias)
@@ -150,7 +151,9 @@ def sow_forward(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, ac
     bias = bias.contiguous() if bias is not None else None
     y = torch.empty((T, d_out), dtype=x2.dtype, device=dev)
     h = None
-    if save_h or r > 64:
+    # a dense accumulator at r <= 64 takes the saved projection as scratch even when it is not kept: without it
+    # sow_forward composes the product from two launches and rounds y twice (the training forward rounds it once)
+    if save_h or r > 64 or kind == _lib.ACC_DENSE:
         h = torch.empty(T * (64 if r <= 64 else r), dtype=x2.dtype, device=dev)   # == sow_h_save_elems(T, r)
     # the forward touches a workspace only for some shapes (include/sow_amd.h: sow_forward_workspace_bytes)
     nws = _forward_workspace_bytes(lib, T, d_in, d_out, r, r_acc, kind, dt)
@@ -224,9 +227,10 @@ class LayerCall:
             raise ValueError("sow_amd.LayerCall: factor shapes do not match the input")
         self.device, self.kind = dev, kind
         self.y = y if y is not None else torch.empty((T, d_out), dtype=x2.dtype, device=dev)
-        # save_h = False (forward_only calls that no backward follows): h_save = NULL, the projection stays on chip
+        # save_h = False (forward_only calls that no backward follows): h_save = NULL, the projection stays on chip --
+        # except with a dense accumulator, whose single-launch kernels need the buffer (as in sow_forward)
         self.h = h if h is not None else (torch.empty(T * (64 if r <= 64 else r), dtype=x2.dtype, device=dev)
-                                          if (save_h or r > 64 or not forward_only) else None)
+                                          if (save_h or r > 64 or not forward_only or kind == _lib.ACC_DENSE) else None)
         self.dx = dx
         r_acc = acc_down.shape[1] if kind == _lib.ACC_LOWRANK else 0
         # a forward-only call needs scratch for a few shapes only (sow_forward_workspace_bytes), often none at all

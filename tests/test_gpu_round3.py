@@ -42,9 +42,8 @@ def test_forward_without_saved_projection_is_bit_identical(shape, dtype, dense):
         y_eval = m(x)
     assert not y_eval.requires_grad
     if dense and r <= 64:
-        # with a dense accumulator and no h_save the low-rank term is added by a second kernel (one more rounding in bf16)
-        tol = 2e-2 if dtype == torch.bfloat16 else 1e-5
-        assert rel_err(y_eval.float().cpu(), y_train.float().cpu()) < tol
+        # a dense accumulator takes a scratch projection buffer without grad too: the same launches as training
+        assert torch.equal(y_eval, y_train)
     elif T > 8192 or T < 128:
         assert torch.equal(y_eval, y_train)
     else:
