@@ -15,7 +15,12 @@
  *     the caller passes a workspace sized by the matching *_workspace_bytes query;
  *   - all tensors are dense row-major device buffers, 16-byte aligned for the
  *     fast paths (unaligned / odd shapes take slower element-wise paths);
- *   - dtype: SOW_DTYPE_F32 (exact f32 MFMA) or SOW_DTYPE_BF16 (bf16 MFMA, f32 accumulate);
+ *   - dtype: SOW_DTYPE_F32 (fp32 tensors; products on the bf16 matrix pipe as 3 x bf16 splits by default, the exact
+ *     f32 MFMA under the F32_EXACT switch), SOW_DTYPE_BF16 (bf16 MFMA, f32 accumulate) or SOW_DTYPE_F16 (f16 MFMA, f32
+ *     accumulate); the tensor-train entry points (sow_tt_*, sow_ttadam_dense) are fp32 only;
+ *   - f16 numerics: every product accumulates in fp32 and each output element is rounded once, to nearest even, to f16;
+ *     a result beyond +-65504 becomes +-inf (IEEE rounding, as torch's f16 matmul; no saturation); subnormal outputs are
+ *     kept, not flushed; h_save has the bf16 layout (scale * x . A, 64 columns, column 63 = 1.0 when free);
  *   - `stream` is a hipStream_t passed as void* (0 = default stream); kernels are
  *     enqueued on it, so the calls are capturable into a hipGraph;
  *   - n_iter > 1 is presented as concatenated factors A = [A_1 .. A_n] ([d_in, n*r]),
@@ -33,6 +38,7 @@ extern "C" {
 
 #define SOW_DTYPE_F32 0
 #define SOW_DTYPE_BF16 1
+#define SOW_DTYPE_F16 2
 
 #define SOW_OK 0
 #define SOW_ERR_NULL (-1)

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SOW_AMD_LIB: an alternative build of the same library (the `make STAMPS=1` timeline build used by tools/chain_stamps.py)
 LIB_PATH = os.environ.get("SOW_AMD_LIB") or os.path.join(_HERE, "lib", "libsow_amd.so")
 
-F32, BF16 = 0, 1
+F32, BF16, F16 = 0, 1, 2
 ACC_NONE, ACC_LOWRANK, ACC_DENSE = 0, 1, 2
 H_COLS = 64
 BWD_DATA, BWD_WEIGHTS, BWD_WEIGHTS_PARTIAL, BWD_WEIGHTS_REDUCE = 1, 2, 4, 8

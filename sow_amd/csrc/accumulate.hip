@@ -162,15 +162,23 @@ int launch_accumulate_batch(const AccItem* items, int n, int dtype, hipStream_t 
     const int gx = max_tiles < 64 ? max_tiles : 64;   // tile loop inside: keeps the grid at <= 64 x n workgroups
     if (dtype == SOW_F32)
       hipLaunchKernelGGL(rank_update_batch_kernel<float>, dim3(gx, b.n), dim3(256), 0, stream, b);
-    else
+    else if (dtype == SOW_BF16)
       hipLaunchKernelGGL(rank_update_batch_kernel<bf16_t>, dim3(gx, b.n), dim3(256), 0, stream, b);
+    else if (dtype == SOW_F16)
+      hipLaunchKernelGGL(rank_update_batch_kernel<f16_t>, dim3(gx, b.n), dim3(256), 0, stream, b);
+    else
+      return SOW_ERR_DTYPE;
     SOW_CHECK_LAUNCH();
     if (!any_qr) continue;
     const int gc = (max_m * 64 + 255) / 256 < 64 ? (max_m * 64 + 255) / 256 : 64;
     if (dtype == SOW_F32)
       hipLaunchKernelGGL(qr_copy_in_batch_kernel<float>, dim3(gc, b.n), dim3(256), 0, stream, b);
-    else
+    else if (dtype == SOW_BF16)
       hipLaunchKernelGGL(qr_copy_in_batch_kernel<bf16_t>, dim3(gc, b.n), dim3(256), 0, stream, b);
+    else if (dtype == SOW_F16)
+      hipLaunchKernelGGL(qr_copy_in_batch_kernel<f16_t>, dim3(gc, b.n), dim3(256), 0, stream, b);
+    else
+      return SOW_ERR_DTYPE;
     SOW_CHECK_LAUNCH();
   }
   {
@@ -189,8 +197,12 @@ int launch_accumulate_batch(const AccItem* items, int n, int dtype, hipStream_t 
     const int gc = (max_m * 64 + 255) / 256 < 64 ? (max_m * 64 + 255) / 256 : 64;
     if (dtype == SOW_F32)
       hipLaunchKernelGGL(qr_copy_out_batch_kernel<float>, dim3(gc, b.n), dim3(256), 0, stream, b);
-    else
+    else if (dtype == SOW_BF16)
       hipLaunchKernelGGL(qr_copy_out_batch_kernel<bf16_t>, dim3(gc, b.n), dim3(256), 0, stream, b);
+    else if (dtype == SOW_F16)
+      hipLaunchKernelGGL(qr_copy_out_batch_kernel<f16_t>, dim3(gc, b.n), dim3(256), 0, stream, b);
+    else
+      return SOW_ERR_DTYPE;
     SOW_CHECK_LAUNCH();
   }
   return SOW_OK;

@@ -26,6 +26,19 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* M, int64_t ld, int
     out[c] = from_f32<T>(v);
   }
 }
+static int launch_colsum(const void* dy, int64_t T, int d_out, void* dbias, float beta, int dtype, hipStream_t stream) {
+  const dim3 grid((d_out + 63) / 64);
+  if (dtype == SOW_F32)
+    hipLaunchKernelGGL(colsum_kernel<float>, grid, dim3(256), 0, stream, (const float*)dy, (int64_t)d_out, T, d_out, (float*)dbias, beta);
+  else if (dtype == SOW_BF16)
+    hipLaunchKernelGGL(colsum_kernel<bf16_t>, grid, dim3(256), 0, stream, (const bf16_t*)dy, (int64_t)d_out, T, d_out, (bf16_t*)dbias, beta);
+  else if (dtype == SOW_F16)
+    hipLaunchKernelGGL(colsum_kernel<f16_t>, grid, dim3(256), 0, stream, (const f16_t*)dy, (int64_t)d_out, T, d_out, (f16_t*)dbias, beta);
+  else
+    return SOW_ERR_DTYPE;
+  SOW_CHECK_LAUNCH();
+  return SOW_OK;
+}
 }  // namespace sow
 
 // ---- kernel-selection switches (common.hpp: enum Switch) ----------------------------------------------
@@ -55,7 +68,7 @@ using namespace sow;
 
 static inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 static inline size_t esize(int dtype) { return dtype == SOW_F32 ? 4 : 2; }
-static inline bool ok_dtype(int d) { return d == SOW_F32 || d == SOW_BF16; }
+static inline bool ok_dtype(int d) { return d == SOW_F32 || d == SOW_BF16 || d == SOW_F16; }
 static inline bool al4p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 static inline bool al16p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
@@ -76,7 +89,7 @@ static size_t short_hp_bytes(int64_t T, int d_in, int d_out, int r_live, int dty
 // the live-factor chain of one direction (Hsave required); returns SOW_ERR_UNSUPPORTED when the split does not apply
 static int launch_chain_short(const ChainParams& p, int dtype, bool bwd, float* hpartial, hipStream_t stream) {
   const int ntb = ceil_div(p.M, 64);
-  const bool f32 = dtype == SOW_F32;
+  const bool f32 = dtype == SOW_F32;   // else bf16 / f16: chain2 (launch_chain2 dispatches on the dtype)
   if (!hpartial || !p.Hsave || ntb > SHORT_NTB || !(f32 ? chain2f_supported(p, dtype) : chain2_supported(p, dtype)) ||
       sw_on(SW_FORCE_CHAIN_V1) || sw_on(SW_NO_SHORT_SPLIT))
     return SOW_ERR_UNSUPPORTED;
@@ -90,14 +103,14 @@ static int launch_chain_short(const ChainParams& p, int dtype, bool bwd, float* 
     ChainParams a = p;
     a.ntb = ntb, a.st_per = ceil_div(nst, ks), a.sl_per = 0, a.Hpartial = hpartial, a.Hload = nullptr;
     ks = ceil_div(nst, a.st_per);
-    rc = f32 ? launch_chain2f(a, bwd, stream) : launch_chain2(a, bwd, stream);
+    rc = f32 ? launch_chain2f(a, bwd, stream) : launch_chain2(a, bwd, dtype, stream);
     if (rc) return rc == SOW_ERR_ALIGN ? SOW_ERR_UNSUPPORTED : rc;
     rc = launch_h_reduce(hpartial, ks, p.Hsave, p.M, p.rb, p.scale, dtype, stream);
     if (rc) return rc;
   } else {
     ChainParams a = p;
     a.Y = nullptr, a.D2 = 0, a.bias = nullptr;   // H-only mode
-    rc = f32 ? launch_chain2f(a, bwd, stream) : launch_chain2(a, bwd, stream);
+    rc = f32 ? launch_chain2f(a, bwd, stream) : launch_chain2(a, bwd, dtype, stream);
     if (rc) return rc == SOW_ERR_ALIGN ? SOW_ERR_UNSUPPORTED : rc;
   }
   if (nsl == 0) return SOW_OK;
@@ -105,13 +118,24 @@ static int launch_chain_short(const ChainParams& p, int dtype, bool bwd, float* 
   ChainParams b = p;
   const int kn = want < nsl ? want : nsl;
   b.ntb = ntb, b.st_per = 0, b.sl_per = ceil_div(nsl, kn), b.Hpartial = nullptr, b.Hload = p.Hsave, b.Hsave = nullptr;
-  return f32 ? launch_chain2f(b, bwd, stream) : launch_chain2(b, bwd, stream);
+  return f32 ? launch_chain2f(b, bwd, stream) : launch_chain2(b, bwd, dtype, stream);
 }
 
 // row-major A, plain product: the streaming kernel when it fills the chip, else the 128x128 kernel
 static int gemm_auto(const void* A, int64_t lda, const void* B, int64_t ldb, bool transB, void* C, int64_t ldc,
                      const void* bias, int64_t M, int N, int K, float alpha, float beta, int dtype, hipStream_t stream,
                      void* ws = nullptr, size_t ws_bytes = 0) {
+  if (dtype == SOW_F16) {
+    // f16 has gemm4 (and its split-K form) only: taken where its 256 x 256 tiles fill at least half of the chip, as for bf16
+    // (launch_gemm2); shorter products and the FORCE_GEMM_V1 / GEMM4 = 0 switches take the generic kernel
+    const int g4 = sw(SW_GEMM4);
+    const int64_t work = (int64_t)ceil_div(M, 256) * ceil_div(N, 256) * gemm4_splits(M, N, K, false, ws, ws_bytes);
+    if (!sw_on(SW_FORCE_GEMM_V1) && (g4 > 0 || (g4 < 0 && work >= 120)) &&
+        gemm4_supported(A, lda, B, ldb, transB, nullptr, 0, nullptr, 0, C, ldc, bias, M, N, K, dtype))
+      return launch_gemm4(A, lda, B, ldb, transB, nullptr, 0, nullptr, 0, 0, C, ldc, bias, M, N, K, alpha, beta, stream, ws,
+                          ws_bytes, dtype);
+    return launch_gemm(A, lda, false, B, ldb, transB, C, ldc, bias, M, N, K, alpha, beta, dtype, stream);
+  }
   if (gemm2_supported(A, lda, B, ldb, transB, nullptr, 0, nullptr, 0, C, ldc, bias, M, N, K, dtype))
     return launch_gemm2(A, lda, B, ldb, transB, nullptr, 0, nullptr, 0, 0, C, ldc, bias, M, N, K, alpha, beta, stream, ws, ws_bytes);
   return launch_gemm(A, lda, false, B, ldb, transB, C, ldc, bias, M, N, K, alpha, beta, dtype, stream);
@@ -119,7 +143,7 @@ static int gemm_auto(const void* A, int64_t lda, const void* B, int64_t ldb, boo
 
 extern "C" {
 
-int sow_version(void) { return 111; }
+int sow_version(void) { return 112; }
 
 int sow_set_switch(const char* name, int value) {
   if (!name) return SOW_ERR_NULL;
@@ -302,7 +326,7 @@ int sow_forward(const void* x, const void* A, const void* B, const void* acc_dow
       if (gemm4h_supported(x, d_in, acc_down, d_out, false, A, r_live, B, d_out, y, d_out, bias, h_save, T, d_out, d_in, r_live,
                            dtype))
         return launch_gemm4h(x, d_in, acc_down, d_out, false, A, r_live, B, d_out, y, d_out, bias, h_save, T, d_out, d_in,
-                             r_live, scale, stream);
+                             r_live, scale, dtype, stream);
       if (gemm2h_supported(x, d_in, acc_down, d_out, false, A, r_live, B, d_out, y, d_out, bias, h_save, T, d_out, d_in,
                            r_live, dtype))
         return launch_gemm2h(x, d_in, acc_down, d_out, false, A, r_live, B, d_out, y, d_out, bias, h_save, T, d_out, d_in,
@@ -318,7 +342,7 @@ int sow_forward(const void* x, const void* A, const void* B, const void* acc_dow
         // short T: the H-only pass split over K (T / 64 workgroups cannot fill the chip: 29 us on 16 workgroups at 1024 x 4096)
         rc = SOW_ERR_UNSUPPORTED;
         if (ws && workspace_bytes >= w.total) rc = launch_chain_short(ph, dtype, false, (float*)(ws + w.off_hp), stream);
-        if (rc == SOW_ERR_UNSUPPORTED) rc = launch_chain2(ph, false, stream);
+        if (rc == SOW_ERR_UNSUPPORTED) rc = launch_chain2(ph, false, dtype, stream);
         if (rc) return rc;
         const bool sk = ws && w.sk_bytes && workspace_bytes >= w.total;
         return launch_gemm2(x, d_in, acc_down, d_out, false, h_save, 64, B, d_out, r_live, y, d_out, bias, T, d_out, d_in,
@@ -419,7 +443,7 @@ int sow_backward_ex(const void* dy, const void* x, const void* h_save, const voi
                            dtype)) {
         // one launch: dh projected by the kernel's own pass over dY, A^T read from A's own 2r-byte rows
         rc = launch_gemm4h(dy, d_out, acc_down, d_out, true, B, d_out, A, r_live, dx, d_in, nullptr, dh, T, d_in, d_out, r_live,
-                           scale, stream);
+                           scale, dtype, stream);
         if (rc) return rc;
         data_done = true;
       } else if (gemm2h_supported(dy, d_out, acc_down, d_out, true, B, d_out, A, r_live, dx, d_in, nullptr, dh, T, d_in, d_out,
@@ -436,7 +460,7 @@ int sow_backward_ex(const void* dy, const void* x, const void* h_save, const voi
         if (pad_fused) pd.pad_src = A, pd.pad_dst = apad, pd.pad_rows = d_in, pd.pad_r = r_live;
         rc = SOW_ERR_UNSUPPORTED;
         if (short_hp_bytes(T, d_in, d_out, r_live, dtype)) rc = launch_chain_short(pd, dtype, true, (float*)(ws + w.off_hp), stream);
-        if (rc == SOW_ERR_UNSUPPORTED) rc = launch_chain2(pd, true, stream);
+        if (rc == SOW_ERR_UNSUPPORTED) rc = launch_chain2(pd, true, dtype, stream);
         if (rc) return rc;
         if (!pad_fused) {
           rc = launch_pad64(A, apad, d_in, r_live, stream);
@@ -507,11 +531,8 @@ int sow_backward_ex(const void* dy, const void* x, const void* h_save, const voi
     rc = launch_tn_reduce(rp, dtype, stream);
     if (rc) return rc;
     if (dbias && !ones_ok) {
-      if (dtype == SOW_F32)
-        hipLaunchKernelGGL(colsum_kernel<float>, dim3((d_out + 63) / 64), dim3(256), 0, stream, (const float*)dy, (int64_t)d_out, T, d_out, (float*)dbias, grad_beta);
-      else
-        hipLaunchKernelGGL(colsum_kernel<bf16_t>, dim3((d_out + 63) / 64), dim3(256), 0, stream, (const bf16_t*)dy, (int64_t)d_out, T, d_out, (bf16_t*)dbias, grad_beta);
-      SOW_CHECK_LAUNCH();
+      rc = launch_colsum(dy, T, d_out, dbias, grad_beta, dtype, stream);
+      if (rc) return rc;
     }
     return SOW_OK;
   }
@@ -528,11 +549,8 @@ int sow_backward_ex(const void* dy, const void* x, const void* h_save, const voi
   rc = launch_gemm(h_save, r_live, true, dy, d_out, false, dB, d_out, nullptr, r_live, d_out, (int)T, scale, grad_beta, dtype, stream);
   if (rc) return rc;
   if (dbias) {
-    if (dtype == SOW_F32)
-      hipLaunchKernelGGL(colsum_kernel<float>, dim3((d_out + 63) / 64), dim3(256), 0, stream, (const float*)dy, (int64_t)d_out, T, d_out, (float*)dbias, grad_beta);
-    else
-      hipLaunchKernelGGL(colsum_kernel<bf16_t>, dim3((d_out + 63) / 64), dim3(256), 0, stream, (const bf16_t*)dy, (int64_t)d_out, T, d_out, (bf16_t*)dbias, grad_beta);
-    SOW_CHECK_LAUNCH();
+    rc = launch_colsum(dy, T, d_out, dbias, grad_beta, dtype, stream);
+    if (rc) return rc;
   }
   return SOW_OK;
 }
@@ -547,11 +565,11 @@ int sow_backward(const void* dy, const void* x, const void* h_save, const void* 
 
 // ---- grouped entry points ------------------------------------------------------------------------------------
 // A group is n INDEPENDENT SoWLinear calls (e.g. q / k / v of one attention block, gate / up of one MLP).  Layers that
-// take the plain bf16 streaming kernels (no accumulator, r <= 64, T / 64 > SHORT_NTB) share launches, C2_MAXG /
+// take the plain bf16 / f16 streaming kernels (no accumulator, r <= 64, T / 64 > SHORT_NTB) share launches, C2_MAXG /
 // TN_MAXG at a time; every other layer is forwarded to the single-layer entry point.  Results are bit-identical to n
 // separate calls: the shared grid runs each layer's own workgroups unchanged.
 static bool group_chain_params(const sow_layer_args& L, bool bwd, int dtype, const WsPlan& w, ChainParams* out) {
-  if (dtype != SOW_BF16 || L.acc_kind != SOW_ACC_NONE || L.r_live > 64 || sw_on(SW_NO_GROUPED) || sw_on(SW_FORCE_CHAIN_V1))
+  if ((dtype != SOW_BF16 && dtype != SOW_F16) || L.acc_kind != SOW_ACC_NONE || L.r_live > 64 || sw_on(SW_NO_GROUPED) || sw_on(SW_FORCE_CHAIN_V1))
     return false;
   if (ceil_div(L.T, 64) <= SHORT_NTB) return false;   // short inputs: K / column split, single-layer path
   ChainParams p{};
@@ -621,7 +639,7 @@ int sow_forward_group(const sow_layer_args* layers, int n, int dtype, void* stre
     const WsPlan w{};
     if (group_chain_params(L, false, dtype, w, &batch[nb])) {   // h_save may be NULL (no backward follows)
       if (++nb == C2_MAXG) {
-        if ((rc = launch_chain2_group(batch, nb, false, stream))) return rc;
+        if ((rc = launch_chain2_group(batch, nb, false, dtype, stream))) return rc;
         nb = 0;
       }
       continue;
@@ -631,7 +649,7 @@ int sow_forward_group(const sow_layer_args* layers, int n, int dtype, void* stre
         gemm4h_supported(L.x, L.d_in, L.acc_down, L.d_out, false, L.A, L.r_live, L.B, L.d_out, L.y, L.d_out, L.bias, L.h_save, L.T,
                          L.d_out, L.d_in, L.r_live, dtype)) {
       if ((rc = launch_gemm4h(L.x, L.d_in, L.acc_down, L.d_out, false, L.A, L.r_live, L.B, L.d_out, L.y, L.d_out, L.bias, L.h_save,
-                              L.T, L.d_out, L.d_in, L.r_live, L.scale, stream)))
+                              L.T, L.d_out, L.d_in, L.r_live, L.scale, dtype, stream)))
         return rc;
       continue;
     }
@@ -652,7 +670,7 @@ int sow_forward_group(const sow_layer_args* layers, int n, int dtype, void* stre
     if (rc) return rc;
   }
   if (ng && (rc = launch_gemm2h_group(gbatch, ng, false, stream))) return rc;
-  return nb ? launch_chain2_group(batch, nb, false, stream) : SOW_OK;
+  return nb ? launch_chain2_group(batch, nb, false, dtype, stream) : SOW_OK;
 }
 
 int sow_backward_group(const sow_layer_args* layers, int n, int dtype, int phases, void* stream_) {
@@ -691,14 +709,14 @@ int sow_backward_group(const sow_layer_args* layers, int n, int dtype, int phase
       void* dh = ws_base(L.workspace) + w.off_dh;
       if (group_chain_params(L, true, dtype, w, &batch[nb])) {
         if (++nb == C2_MAXG) {
-          if ((rc = launch_chain2_group(batch, nb, true, stream))) return rc;
+          if ((rc = launch_chain2_group(batch, nb, true, dtype, stream))) return rc;
           nb = 0;
         }
       } else if (L.acc_kind == SOW_ACC_DENSE && L.r_live <= 64 &&
                  gemm4h_supported(L.dy, L.d_out, L.acc_down, L.d_out, true, L.B, L.d_out, L.A, L.r_live, L.dx, L.d_in, nullptr, dh,
                                   L.T, L.d_in, L.d_out, L.r_live, dtype)) {
         if ((rc = launch_gemm4h(L.dy, L.d_out, L.acc_down, L.d_out, true, L.B, L.d_out, L.A, L.r_live, L.dx, L.d_in, nullptr, dh,
-                                L.T, L.d_in, L.d_out, L.r_live, L.scale, stream)))
+                                L.T, L.d_in, L.d_out, L.r_live, L.scale, dtype, stream)))
           return rc;
       } else if (L.acc_kind == SOW_ACC_DENSE && L.r_live <= 64 && !sw_on(SW_NO_GROUPED) &&
                  gemm2h_supported(L.dy, L.d_out, L.acc_down, L.d_out, true, L.B, L.d_out, L.A, L.r_live, L.dx, L.d_in, nullptr, dh,
@@ -713,7 +731,7 @@ int sow_backward_group(const sow_layer_args* layers, int n, int dtype, int phase
         return rc;
     }
     if (ng && (rc = launch_gemm2h_group(gbatch, ng, true, stream))) return rc;
-    if (nb && (rc = launch_chain2_group(batch, nb, true, stream))) return rc;
+    if (nb && (rc = launch_chain2_group(batch, nb, true, dtype, stream))) return rc;
   }
   // row-owner weight-gradient kernel with slab counts planned over the group: when the caller asks for it (and then builds
   // the deferred reduction from sow_backward_group_reduce_desc), or when this call runs the reduction itself
@@ -837,7 +855,7 @@ int sow_gemm(const void* A, int64_t lda, int trans_a, const void* B, int64_t ldb
 }
 
 size_t sow_gemm_workspace_bytes(int64_t M, int N, int K, int trans_a, int dtype) {
-  if (trans_a || dtype != SOW_BF16 || M <= 0 || N <= 0 || K <= 0) return 0;
+  if (trans_a || (dtype != SOW_BF16 && dtype != SOW_F16) || M <= 0 || N <= 0 || K <= 0) return 0;
   return gemm4_splitk_bytes(M, N, K, false);
 }
 
@@ -900,7 +918,7 @@ int sow_qr_thin(const void* W, int64_t ldw, int m, int n, int in_dtype, int k, v
       Bp = (const float*)W + q.kc, ldb = ldw;
     } else {
       float* wf = (float*)(ws + q.off_w);
-      rc = launch_cast_copy((const bf16_t*)W + q.kc, ldw, SOW_BF16, wf, nt, SOW_F32, m, nt, stream);
+      rc = launch_cast_copy((const char*)W + q.kc * esize(in_dtype), ldw, in_dtype, wf, nt, SOW_F32, m, nt, stream);
       if (rc) return rc;
       Bp = wf, ldb = nt;
     }
@@ -911,7 +929,7 @@ int sow_qr_thin(const void* W, int64_t ldw, int m, int n, int in_dtype, int k, v
       float* rt = (float*)(ws + q.off_r);
       rc = launch_gemm(Qt, m, false, Bp, ldb, false, rt, nt, nullptr, k, nt, m, 1.f, 0.f, SOW_F32, stream);
       if (rc) return rc;
-      rc = launch_cast_copy(rt, nt, SOW_F32, (bf16_t*)R_out + q.kc, ldr, SOW_BF16, k, nt, stream);
+      rc = launch_cast_copy(rt, nt, SOW_F32, (char*)R_out + q.kc * esize(out_dtype), ldr, out_dtype, k, nt, stream);
       if (rc) return rc;
     }
   }

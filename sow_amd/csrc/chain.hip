@@ -28,6 +28,7 @@ template <typename T> struct ChainCfg;
 template <> struct ChainCfg<bf16_t> {
   static constexpr int BK = 64, BN = 128, NT = 2;
 };
+template <> struct ChainCfg<f16_t> : ChainCfg<bf16_t> {};
 template <> struct ChainCfg<float> {
   static constexpr int BK = 32, BN = 64, NT = 1;
 };
@@ -67,7 +68,8 @@ template <typename T, bool BWD> __device__ __forceinline__ T f2_fetch(const Chai
   const T* base = (const T*)p.F2b;
   return BWD ? base[(int64_t)ng * p.ldf2b + r] : base[(int64_t)r * p.ldf2b + ng];
 }
-// dword (2 x bf16) fetches for the fast paths (rb, leading dims, D1, D2 even; 4-byte aligned bases)
+// dword (2 x 16-bit) fetches for the fast paths (rb, leading dims, D1, D2 even; 4-byte aligned bases); a bit copy, so the
+// bf16 form serves f16 too
 template <bool BWD> __device__ __forceinline__ uint32_t f1_fetch2(const ChainParams& p, int kg, int r) {
   // !BWD: elements (kg, r), (kg, r+1) ; BWD: elements (r, kg), (r, kg+1)
   if (kg >= p.D1 || r >= p.rb) return 0u;
@@ -102,7 +104,8 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainParams p) {
   const int64_t m0 = (int64_t)blockIdx.x * CH_BM;
   const T* X = (const T*)p.X;
   const int rtot = p.rb;
-  static_assert(!(F32 && FASTF), "dword factor loaders are bf16 only");
+  static_assert(!(F32 && FASTF), "dword factor loaders are 16-bit only");
+  using V8 = typename DT<T>::v8;
 
   // ------------------------------------------------------------------ phase 1 staging registers
   constexpr int XV = CH_BM * BK / VE / 256;       // 16-byte vectors of X per thread (2)
@@ -154,7 +157,7 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainParams p) {
         if constexpr (F32)
           ((float*)Xs)[row * (BK + 1) + k] = xe[i];
         else
-          *(bf16_t*)(Xs + bf16_img_off<BK>(row, k >> 3) + (k & 7) * 2) = xe[i];
+          *(T*)(Xs + bf16_img_off<BK>(row, k >> 3) + (k & 7) * 2) = xe[i];
       }
     }
   };
@@ -207,7 +210,7 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainParams p) {
           else
             ((float*)F1s)[k * CH_RP + r] = fe[i];
         } else {
-          *(bf16_t*)(F1s + bf16_img_off<BK>(r, k >> 3) + (k & 7) * 2) = fe[i];
+          *(T*)(F1s + bf16_img_off<BK>(r, k >> 3) + (k & 7) * 2) = fe[i];
         }
       }
     }
@@ -242,8 +245,8 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainParams p) {
     } else {
 #pragma unroll
       for (int ks = 0; ks < BK / 16; ++ks) {
-        const bf16x8 a = *(const bf16x8*)(Xs + bf16_img_off<BK>(wm * 32 + li, 2 * ks + lh));
-        const bf16x8 b = *(const bf16x8*)(F1s + bf16_img_off<BK>(wn * 32 + li, 2 * ks + lh));
+        const V8 a = *(const V8*)(Xs + bf16_img_off<BK>(wm * 32 + li, 2 * ks + lh));
+        const V8 b = *(const V8*)(F1s + bf16_img_off<BK>(wn * 32 + li, 2 * ks + lh));
         hacc = mfma32(a, b, hacc);
       }
     }
@@ -265,7 +268,7 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainParams p) {
       if constexpr (F32)
         ((float*)Hs)[row * (CH_RP + 1) + c] = hsc;
       else
-        *(bf16_t*)(Hs + bf16_img_off<CH_RP>(row, c >> 3) + (c & 7) * 2) = (bf16_t)hsc;
+        *(T*)(Hs + bf16_img_off<CH_RP>(row, c >> 3) + (c & 7) * 2) = from_f32<T>(hsc);
       if (Hsave && m0 + row < p.M) {
         // live columns, zero padding, and 1.0 in column 63 (when free): the skinny-TN kernel turns that
         // column into the column sums of its other operand (dbias) at no cost
@@ -338,7 +341,7 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainParams p) {
           else
             ((float*)F2s)[r * BN + n] = f2e[i];
         } else {
-          *(bf16_t*)(F2s + bf16_img_off<CH_RP>(n, r >> 3) + (r & 7) * 2) = f2e[i];
+          *(T*)(F2s + bf16_img_off<CH_RP>(n, r >> 3) + (r & 7) * 2) = f2e[i];
         }
       }
     }
@@ -371,10 +374,10 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainParams p) {
       }
     } else {
       for (int ks = 0; ks < ksteps; ++ks) {
-        const bf16x8 a = *(const bf16x8*)(Hs + bf16_img_off<CH_RP>(wm * 32 + li, 2 * ks + lh));
+        const V8 a = *(const V8*)(Hs + bf16_img_off<CH_RP>(wm * 32 + li, 2 * ks + lh));
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-          const bf16x8 b = *(const bf16x8*)(F2s + bf16_img_off<CH_RP>(ncol + nt * 32 + li, 2 * ks + lh));
+          const V8 b = *(const V8*)(F2s + bf16_img_off<CH_RP>(ncol + nt * 32 + li, 2 * ks + lh));
           yacc[nt] = mfma32(a, b, yacc[nt]);
         }
       }
@@ -407,13 +410,13 @@ template <typename T, bool BWD> static int launch_chain_t(const ChainParams& p, 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 
-// Host entry used by api.hip.  dtype: SOW_F32 / SOW_BF16.
+// Host entry used by api.hip.  dtype: SOW_F32 / SOW_BF16 / SOW_F16.
 int launch_chain(ChainParams p, int dtype, bool bwd, hipStream_t stream) {
   if (!p.X || !p.Y) return SOW_ERR_NULL;
   if (p.ra != 0 || p.rb <= 0 || p.rb > CH_RP) return SOW_ERR_SHAPE;
   if (!p.F1b || !p.F2b) return SOW_ERR_NULL;
   if (chain2_supported(p, dtype) && !sw_on(SW_FORCE_CHAIN_V1)) {
-    const int rc = launch_chain2(p, bwd, stream);
+    const int rc = launch_chain2(p, bwd, dtype, stream);
     if (rc != SOW_ERR_ALIGN) return rc;  // factor alignment not met: fall through to the generic kernel
   }
   if (chain3f_supported(p, dtype)) {
@@ -427,13 +430,15 @@ int launch_chain(ChainParams p, int dtype, bool bwd, hipStream_t stream) {
   const int ve = dtype == SOW_F32 ? 4 : 8;
   const bool vec = p.D1 % ve == 0 && p.D2 % ve == 0 && p.ldx % ve == 0 && p.ldy % ve == 0 && aligned16(p.X) &&
                    aligned16(p.Y) && (!p.bias || aligned16(p.bias));
-  if (dtype == SOW_BF16) {
-    // dword factor loaders: pairs of bf16 must not straddle a segment or a row
+  if (dtype == SOW_BF16 || dtype == SOW_F16) {
+    // dword factor loaders: pairs of 16-bit elements must not straddle a segment or a row
     bool f = p.rb % 2 == 0 && p.ldf1b % 2 == 0 && p.ldf2b % 2 == 0 && aligned4(p.F1b) && aligned4(p.F2b);
     // the dword reads pair elements along the STORAGE-contiguous axis: fwd F1 pairs ranks, F2 pairs n;
     // bwd F1 pairs k (= D1), F2 pairs ranks.  Even extents keep the pairs inside the matrix.
     f = f && p.D1 % 2 == 0 && p.D2 % 2 == 0;
     p.fast_factors = f ? 1 : 0;
+    if (dtype == SOW_F16)
+      return bwd ? launch_chain_t<f16_t, true>(p, vec, stream) : launch_chain_t<f16_t, false>(p, vec, stream);
     return bwd ? launch_chain_t<bf16_t, true>(p, vec, stream) : launch_chain_t<bf16_t, false>(p, vec, stream);
   } else if (dtype == SOW_F32) {
     p.fast_factors = 0;

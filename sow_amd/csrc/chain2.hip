@@ -117,7 +117,7 @@ template <bool TR> __device__ __forceinline__ int img_chunk(int row, int c) {
 // 5.1 TB/s), so three 512-workgroup layers in one 1536-workgroup grid pay it once; later rounds start while earlier
 // workgroups drain.  Every workgroup runs exactly the single-layer code on its own layer's parameter block, so the
 // results are bit-identical to separate launches.
-template <bool BWD, bool P16>
+template <typename T, bool BWD, bool P16>
 __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid, char* smem, const int t, const int lane, const int w,
                                              uint64_t* stamps) {
   constexpr bool TR = !BWD;
@@ -134,8 +134,8 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
   const int nst = p.sl_per > 0 ? 0 : (p.st_per > 0 ? (nst_all - st0 < p.st_per ? nst_all - st0 : p.st_per) : nst_all);
   const int nsl = p.st_per > 0 ? 0 : (p.sl_per > 0 ? (nsl_all - sl0 < p.sl_per ? nsl_all - sl0 : p.sl_per) : nsl_all);
   const int total = nst + nsl;
-  const bf16_t* Amat = (const bf16_t*)(BWD ? p.F2b : p.F1b);   // [rows_a, rb] contiguous
-  const bf16_t* Bmat = (const bf16_t*)(BWD ? p.F1b : p.F2b);   // [rb, cols_b], ld = ldb
+  const T* Amat = (const T*)(BWD ? p.F2b : p.F1b);   // [rows_a, rb] contiguous
+  const T* Bmat = (const T*)(BWD ? p.F1b : p.F2b);   // [rb, cols_b], ld = ldb
   const int64_t ldb = BWD ? p.ldf1b : p.ldf2b;
   const int rows_a = BWD ? D2 : D1, cols_b = BWD ? D1 : D2;
   const char* zp = zero_page_for(lane);
@@ -238,16 +238,16 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
   // -------------------------------------------------------------------- compute waves
   if (p.pad_dst && bid * 64 < p.pad_rows) {
     // side job (first ceil(rows / 64) workgroups): two 8-column groups per thread, plain guarded loads
-    const bf16_t* src = (const bf16_t*)p.pad_src;
-    bf16_t* dst = (bf16_t*)p.pad_dst;
+    const T* src = (const T*)p.pad_src;
+    T* dst = (T*)p.pad_dst;
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
       const int idx = t + 256 * it, row = bid * 64 + (idx >> 3), c0 = (idx & 7) * 8;
       if (row < p.pad_rows) {
         u32x4 v;
-        bf16_t* e = (bf16_t*)&v;
+        T* e = (T*)&v;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) e[j] = (c0 + j < p.pad_r) ? src[(int64_t)row * p.pad_r + c0 + j] : (bf16_t)0.f;
+        for (int j = 0; j < 8; ++j) e[j] = (c0 + j < p.pad_r) ? src[(int64_t)row * p.pad_r + c0 + j] : (T)0.f;
         *(u32x4*)(dst + (int64_t)row * 64 + c0) = v;
       }
     }
@@ -259,7 +259,7 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
   char* ring = smem + C2_RING0 + tg * C2_RING;
   const uint32_t ring_a = lds_addr(ring);
   const uint32_t slot_a = lds_addr(smem);
-  const bf16_t* X = (const bf16_t*)p.X;
+  const T* X = (const T*)p.X;
   const int64_t tok0 = m0 + 32 * tg;
 
   // X DMA: this wave issues instructions i = 2*hh, 2*hh+1 (token rows 16*hh .. 16*hh+15) of every stage
@@ -358,7 +358,7 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
       LGKM_WAIT0();
     }
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) hacc = mfma32(as_bf16x8(ff[ks]), as_bf16x8(xf[ks]), hacc);
+    for (int ks = 0; ks < 4; ++ks) hacc = mfma32(as_v8<T>(ff[ks]), as_v8<T>(xf[ks]), hacc);
     __builtin_amdgcn_sched_barrier(0);
   }
 
@@ -373,7 +373,7 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
     // phase-2-only workgroup: H comes from memory.  hf[s] of lane (li, lh) = ranks 16s + 4lh + (0..3) and
     // 16s + 8 + 4lh + (0..3) of token li; the 1.0 of column 63 (dbias trick) must not reach the product.
     raw_barrier();
-    const bf16_t* Hl = (const bf16_t*)p.Hload + tok * 64 + 4 * lh;
+    const T* Hl = (const T*)p.Hload + tok * 64 + 4 * lh;
 #pragma unroll
     for (int s4 = 0; s4 < 4; ++s4) {
       u32x2 lo = {0u, 0u}, hi = {0u, 0u};
@@ -405,14 +405,14 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
       }
 #pragma unroll
       for (int a = 0; a < 2; ++a)
-        own[a] = (u32x4){pack_bf16x2(hv[8 * a + 0], hv[8 * a + 1]), pack_bf16x2(hv[8 * a + 2], hv[8 * a + 3]),
-                         pack_bf16x2(hv[8 * a + 4], hv[8 * a + 5]), pack_bf16x2(hv[8 * a + 6], hv[8 * a + 7])};
+        own[a] = (u32x4){pack16x2<T>(hv[8 * a + 0], hv[8 * a + 1]), pack16x2<T>(hv[8 * a + 2], hv[8 * a + 3]),
+                         pack16x2<T>(hv[8 * a + 4], hv[8 * a + 5]), pack16x2<T>(hv[8 * a + 6], hv[8 * a + 7])};
       if (p.Hsave && tok < p.M) {
-        bf16_t* Hs = (bf16_t*)p.Hsave + tok * 64 + hh * 32 + 4 * lh;
+        T* Hs = (T*)p.Hsave + tok * 64 + hh * 32 + 4 * lh;
 #pragma unroll
         for (int rq = 0; rq < 4; ++rq) {
-          u32x2 v = {pack_bf16x2(hv[4 * rq + 0], hv[4 * rq + 1]), pack_bf16x2(hv[4 * rq + 2], hv[4 * rq + 3])};
-          if (hh == 1 && rq == 3 && lh == 1 && rb < 64) v[1] = (v[1] & 0xffffu) | 0x3F800000u;  // column 63 <- 1.0
+          u32x2 v = {pack16x2<T>(hv[4 * rq + 0], hv[4 * rq + 1]), pack16x2<T>(hv[4 * rq + 2], hv[4 * rq + 3])};
+          if (hh == 1 && rq == 3 && lh == 1 && rb < 64) v[1] = (v[1] & 0xffffu) | (DT<T>::one_bits << 16);  // column 63 <- 1.0
           *(u32x2*)(Hs + 8 * rq) = v;
         }
       }
@@ -435,8 +435,8 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
   // rows (measured: 2x the time of full-row stores).  Each slice is transposed through a per-token-group
   // fp32 LDS tile ([32 tok][64 col], 16-byte chunks XOR-swizzled by the row; this wave fills its 32
   // columns) and written one step later as 16-byte row segments (this wave stores rows 16*hh..+15).
-  bf16_t* Y = (bf16_t*)p.Y;
-  const bf16_t* bias = (const bf16_t*)p.bias;
+  T* Y = (T*)p.Y;
+  const T* bias = (const T*)p.bias;
   const int ksteps = (rb + 15) / 16;
   auto tile_addr = [&](int buf, int row, int chunk) {   // chunk = 16-byte (4 fp32) index 0..15
     return ring_a + (uint32_t)(buf * 8192 + row * 256 + ((chunk ^ (row & 15)) * 16));
@@ -463,16 +463,16 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
         const float* f1 = (const float*)&v1[pass];
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = f0[e], v[4 + e] = f1[e];
-        bf16_t* dst = Y + tk * p.ldy + col;
+        T* dst = Y + tk * p.ldy + col;
         if (p.beta != 0.f) {
           const u32x4 old = *(const u32x4*)dst;
-          const bf16_t* o = (const bf16_t*)&old;
+          const T* o = (const T*)&old;
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] += p.beta * (float)o[e];
         }
         if (bias) {
           const u32x4 bv = *(const u32x4*)(bias + col);
-          const bf16_t* bb = (const bf16_t*)&bv;
+          const T* bb = (const T*)&bv;
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] += (float)bb[e];
         }
@@ -480,7 +480,7 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
         // in the eight L2s when the last workgroup ends and are written back before the next kernel may start (the XCDs'
         // L2s are not coherent with each other): 512 -> 512 forward 23.0 -> 19.7 us per launch, step 4.48 -> 4.23 ms.
         // ("sc0 sc1" write-through: 22.3 us; "sc0 sc1 nt": 19.2 us -- no better than nt alone.)
-        const u32x4 ov = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
+        const u32x4 ov = {pack16x2<T>(v[0], v[1]), pack16x2<T>(v[2], v[3]), pack16x2<T>(v[4], v[5]), pack16x2<T>(v[6], v[7])};
         if (p.nt_store) asm volatile("global_store_dwordx4 %0, %1, off nt" ::"v"(dst), "v"(ov) : "memory");
         else *(u32x4*)dst = ov;
       }
@@ -512,20 +512,20 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
           const float* f1 = (const float*)&v1[ps];
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = f0[e], v[4 + e] = f1[e];
-          bf16_t* dst = Y + tk * p.ldy + col;
+          T* dst = Y + tk * p.ldy + col;
           if (p.beta != 0.f) {
             const u32x4 old = *(const u32x4*)dst;
-            const bf16_t* o = (const bf16_t*)&old;
+            const T* o = (const T*)&old;
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] += p.beta * (float)o[e];
           }
           if (bias) {
             const u32x4 bv = *(const u32x4*)(bias + col);
-            const bf16_t* bb = (const bf16_t*)&bv;
+            const T* bb = (const T*)&bv;
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] += (float)bb[e];
           }
-          const u32x4 ov = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
+          const u32x4 ov = {pack16x2<T>(v[0], v[1]), pack16x2<T>(v[2], v[3]), pack16x2<T>(v[4], v[5]), pack16x2<T>(v[6], v[7])};
           if (p.nt_store) asm volatile("global_store_dwordx4 %0, %1, off nt" ::"v"(dst), "v"(ov) : "memory");
           else *(u32x4*)dst = ov;
         }
@@ -542,7 +542,7 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
   auto store16 = [&](int r, int col, u32x4 ov) {
     const int64_t tk = tok0 + r;
     if (tk < p.M && col < D2) {
-      bf16_t* dst = Y + tk * p.ldy + col;
+      T* dst = Y + tk * p.ldy + col;
       if (p.nt_store) asm volatile("global_store_dwordx4 %0, %1, off nt" ::"v"(dst), "v"(ov) : "memory");
       else *(u32x4*)dst = ov;
     }
@@ -595,14 +595,14 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
     for (int i = 0; i < 16; ++i) yacc[i] = 0.f;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks)
-      if (ks < ksteps) yacc = mfma32(as_bf16x8(join2(bl[ks], bh[ks])), as_bf16x8(hf[ks]), yacc);
+      if (ks < ksteps) yacc = mfma32(as_v8<T>(join2(bl[ks], bh[ks])), as_v8<T>(hf[ks]), yacc);
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (park16) {
       if (sl >= 2 && !(sl & 1)) flush_pair16(sl - 2);
       // park: register quad rq = columns hh*32 + 8*rq + 4*lh .. +3 of token li = half lh of 16-byte chunk hh*4 + rq
 #pragma unroll
       for (int rq = 0; rq < 4; ++rq) {
-        const u32x2 v = {pack_bf16x2(yacc[4 * rq + 0], yacc[4 * rq + 1]), pack_bf16x2(yacc[4 * rq + 2], yacc[4 * rq + 3])};
+        const u32x2 v = {pack16x2<T>(yacc[4 * rq + 0], yacc[4 * rq + 1]), pack16x2<T>(yacc[4 * rq + 2], yacc[4 * rq + 3])};
         *(u32x2*)(ring + (C2_DEPTH - 3) * C2_STAGE + (sl % 3) * 4096 + li * 128 + (((hh * 4 + rq) ^ ((li >> 1) & 7)) * 16) + lh * 8) = v;
       }
     } else {
@@ -662,7 +662,25 @@ template <bool BWD, bool P16> __global__ __launch_bounds__(C2_THREADS, 4) void c
     // loop by LICM it stays live across the whole block (168 VGPRs instead of ~100; above 128 a CU holds one workgroup)
     int tt = t;
     asm volatile("" : "+v"(tt));
-    chain2_block<BWD, P16>(grp.p[layer], blk - grp.start[layer], smem, tt, tt & 63, w, grp.stamps ? grp.stamps + (int64_t)blk * 16 : nullptr);
+    chain2_block<bf16_t, BWD, P16>(grp.p[layer], blk - grp.start[layer], smem, tt, tt & 63, w, grp.stamps ? grp.stamps + (int64_t)blk * 16 : nullptr);
+  }
+}
+// the f16 form of the same loop
+template <bool BWD, bool P16> __global__ __launch_bounds__(C2_THREADS, 4) void chain2_f16_kernel(const ChainGroup grp) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int t = threadIdx.x;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int total = grp.start[C2_MAXG];
+  for (int blk = (int)blockIdx.x; blk < total; blk += (int)gridDim.x) {
+    int layer = 0;
+#pragma unroll
+    for (int i = 1; i < C2_MAXG; ++i)
+      if (i < grp.n && blk >= grp.start[i]) layer = i;
+    // opaque per iteration: keeps the per-lane address arithmetic of a block inside its iteration -- hoisted out of the
+    // loop by LICM it stays live across the whole block (168 VGPRs instead of ~100; above 128 a CU holds one workgroup)
+    int tt = t;
+    asm volatile("" : "+v"(tt));
+    chain2_block<f16_t, BWD, P16>(grp.p[layer], blk - grp.start[layer], smem, tt, tt & 63, w, grp.stamps ? grp.stamps + (int64_t)blk * 16 : nullptr);
   }
 }
 
@@ -671,14 +689,14 @@ bool chain2_supported(const ChainParams& p, int dtype) {
   auto a16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   // rb >= 4: the overlap trick zero-fills every 16-byte piece that would cross the end of A and repairs only
   // the LAST row; with 4-byte rows (rb = 2) the last three rows lose their data (found by tests/test_gpu_fuzz.py)
-  if (dtype != SOW_BF16 || p.ra != 0 || p.rb < 4 || p.rb > 64 || (p.rb & 1)) return false;
+  if ((dtype != SOW_BF16 && dtype != SOW_F16) || p.ra != 0 || p.rb < 4 || p.rb > 64 || (p.rb & 1)) return false;
   if (p.D1 % 8 || p.D2 % 8 || p.ldx % 8 || p.ldy % 8) return false;
   if (!a16(p.X) || !a16(p.Y) || (p.bias && !a16(p.bias)) || (p.Hsave && !a16(p.Hsave))) return false;
   if (p.M < 64) return false;   // (short inputs run T/64 workgroups either way; measured 1.4x faster than the generic kernel at T = 1024)
   return true;
 }
 
-// Hsave[t][c] = bf16(scale * sum_s Hpartial[s][t][c]) for c < rb, 0 above, 1.0 in column 63 when rb < 64
+// Hsave[t][c] = T(scale * sum_s Hpartial[s][t][c]) for c < rb, 0 above, 1.0 in column 63 when rb < 64
 template <typename T>
 __global__ __launch_bounds__(256) void h_reduce_kernel(const float* __restrict__ Hp, int nsplit, T* __restrict__ Hs, int64_t M,
                                                        int rb, float scale) {
@@ -699,7 +717,7 @@ __global__ __launch_bounds__(256) void h_reduce_kernel(const float* __restrict__
     v[j] = c < rb ? v[j] * scale : ((c == 63 && rb < 64) ? 1.0f : 0.f);
   }
   if constexpr (sizeof(T) == 2) {
-    *(u32x4*)(Hs + tok * 64 + c0) = (u32x4){pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
+    *(u32x4*)(Hs + tok * 64 + c0) = (u32x4){pack16x2<T>(v[0], v[1]), pack16x2<T>(v[2], v[3]), pack16x2<T>(v[4], v[5]), pack16x2<T>(v[6], v[7])};
   } else {
     *(f32x4*)(Hs + tok * 64 + c0) = (f32x4){v[0], v[1], v[2], v[3]};
     *(f32x4*)(Hs + tok * 64 + c0 + 4) = (f32x4){v[4], v[5], v[6], v[7]};
@@ -712,8 +730,12 @@ int launch_h_reduce(const float* Hpartial, int nsplit, void* Hsave, int64_t M, i
   const dim3 grid((unsigned)((M * 8 + 255) / 256));
   if (dtype == SOW_BF16)
     hipLaunchKernelGGL(h_reduce_kernel<bf16_t>, grid, dim3(256), 0, stream, Hpartial, nsplit, (bf16_t*)Hsave, M, rb, scale);
-  else
+  else if (dtype == SOW_F16)
+    hipLaunchKernelGGL(h_reduce_kernel<f16_t>, grid, dim3(256), 0, stream, Hpartial, nsplit, (f16_t*)Hsave, M, rb, scale);
+  else if (dtype == SOW_F32)
     hipLaunchKernelGGL(h_reduce_kernel<float>, grid, dim3(256), 0, stream, Hpartial, nsplit, (float*)Hsave, M, rb, scale);
+  else
+    return SOW_ERR_DTYPE;
   SOW_CHECK_LAUNCH();
   return SOW_OK;
 }
@@ -729,8 +751,9 @@ static int chain2_grid(const ChainParams& p) {
   return ceil_div(p.M, C2_BM);
 }
 
-int launch_chain2_group(const ChainParams* ps, int n, bool bwd, hipStream_t stream) {
+int launch_chain2_group(const ChainParams* ps, int n, bool bwd, int dtype, hipStream_t stream) {
   if (n <= 0) return SOW_OK;
+  if (dtype != SOW_BF16 && dtype != SOW_F16) return SOW_ERR_DTYPE;
   if (n > C2_MAXG) return SOW_ERR_SHAPE;
   ChainGroup g{};
   g.n = n;
@@ -760,8 +783,13 @@ int launch_chain2_group(const ChainParams* ps, int n, bool bwd, hipStream_t stre
   for (int i = 0; i < n; ++i) p16 = p16 && g.p[i].pair_flush && g.p[i].beta == 0.f && !g.p[i].bias;
 #define C2_LAUNCH(B, P)                                                                                              \
   do {                                                                                                               \
-    SOW_SET_MAX_LDS_ONCE(C2_LDS, (chain2_kernel<B, P>));                                                             \
-    hipLaunchKernelGGL((chain2_kernel<B, P>), dim3((unsigned)grid), dim3(C2_THREADS), C2_LDS, stream, g);            \
+    if (dtype == SOW_F16) {                                                                                          \
+      SOW_SET_MAX_LDS_ONCE(C2_LDS, (chain2_f16_kernel<B, P>));                                                       \
+      hipLaunchKernelGGL((chain2_f16_kernel<B, P>), dim3((unsigned)grid), dim3(C2_THREADS), C2_LDS, stream, g);      \
+    } else {                                                                                                         \
+      SOW_SET_MAX_LDS_ONCE(C2_LDS, (chain2_kernel<B, P>));                                                           \
+      hipLaunchKernelGGL((chain2_kernel<B, P>), dim3((unsigned)grid), dim3(C2_THREADS), C2_LDS, stream, g);          \
+    }                                                                                                                \
   } while (0)
   if (bwd) {
     if (p16) C2_LAUNCH(true, true);
@@ -775,6 +803,6 @@ int launch_chain2_group(const ChainParams* ps, int n, bool bwd, hipStream_t stre
   return SOW_OK;
 }
 
-int launch_chain2(const ChainParams& p, bool bwd, hipStream_t stream) { return launch_chain2_group(&p, 1, bwd, stream); }
+int launch_chain2(const ChainParams& p, bool bwd, int dtype, hipStream_t stream) { return launch_chain2_group(&p, 1, bwd, dtype, stream); }
 
 }  // namespace sow

@@ -2,7 +2,7 @@
 //
 // Conventions used by every kernel in this directory:
 //   * wavefront = 64 lanes, workgroups of 256 threads (4 waves) unless stated;
-//   * MFMA shapes: v_mfma_f32_32x32x16_bf16 (bf16 in, f32 acc) and
+//   * MFMA shapes: v_mfma_f32_32x32x16_bf16 / _f16 (16-bit in, f32 acc) and
 //     v_mfma_f32_32x32x2_f32 (exact f32).  Both share the C/D map
 //       col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5), reg in [0,16);
 //     A operand: lane holds A[row = lane & 31][k-group lane >> 5]; B operand: B[k-group][col = lane & 31];
@@ -25,33 +25,51 @@ typedef __bf16 bf16_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+typedef _Float16 f16_t;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 
-enum : int { SOW_F32 = 0, SOW_BF16 = 1 };
+enum : int { SOW_F32 = 0, SOW_BF16 = 1, SOW_F16 = 2 };
 
 
 template <typename T> struct DT;
 template <> struct DT<float> {
   static constexpr int id = SOW_F32;
   static constexpr int VE = 4;  // elements per 16-byte vector
+  using v8 = float;             // MFMA fragment (v_mfma_f32_32x32x2_f32: one k per lane)
 };
 template <> struct DT<bf16_t> {
   static constexpr int id = SOW_BF16;
   static constexpr int VE = 8;
+  using v8 = bf16x8;   // MFMA fragment of 8 k
+  static constexpr uint32_t one_bits = 0x3F80u;   // 1.0
+};
+template <> struct DT<f16_t> {
+  static constexpr int id = SOW_F16;
+  static constexpr int VE = 8;
+  using v8 = f16x8;
+  static constexpr uint32_t one_bits = 0x3C00u;
 };
 
 __device__ __forceinline__ float to_f32(float v) { return v; }
 __device__ __forceinline__ float to_f32(bf16_t v) { return (float)v; }
+__device__ __forceinline__ float to_f32(f16_t v) { return (float)v; }
 template <typename T> __device__ __forceinline__ T from_f32(float v);
 template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }
 template <> __device__ __forceinline__ bf16_t from_f32<bf16_t>(float v) { return (bf16_t)v; }  // RNE, NaN-preserving
+// RNE (v_cvt_f16_f32): |v| past 65504 + half an ulp becomes +-inf, subnormals are kept.  Never the pkrtz forms: they truncate.
+template <> __device__ __forceinline__ f16_t from_f32<f16_t>(float v) { return (f16_t)v; }
 
 __device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x16 mfma32(f16x8 a, f16x8 b, f32x16 c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
 }
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
@@ -92,6 +110,20 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
   v[0] = (bf16_t)lo;
   v[1] = (bf16_t)hi;
   return __builtin_bit_cast(uint32_t, v);
+}
+__device__ __forceinline__ uint32_t pack_f16x2(float lo, float hi) {
+  f16x2 v;
+  v[0] = (f16_t)lo;   // RNE each (v_cvt_f16_f32), not v_cvt_pkrtz_f16_f32
+  v[1] = (f16_t)hi;
+  return __builtin_bit_cast(uint32_t, v);
+}
+// two 16-bit elements of type T (bf16_t / f16_t) from fp32, RNE
+template <typename T> __device__ __forceinline__ uint32_t pack16x2(float lo, float hi);
+template <> __device__ __forceinline__ uint32_t pack16x2<bf16_t>(float lo, float hi) { return pack_bf16x2(lo, hi); }
+template <> __device__ __forceinline__ uint32_t pack16x2<f16_t>(float lo, float hi) { return pack_f16x2(lo, hi); }
+// 16-byte register image -> the MFMA fragment type of T
+template <typename T> __device__ __forceinline__ typename DT<T>::v8 as_v8(u32x4 v) {
+  return __builtin_bit_cast(typename DT<T>::v8, v);
 }
 
 // XCD-aware bijective block remap (cdna guide T1): consecutive logical ids land on the same XCD.

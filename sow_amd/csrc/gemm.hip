@@ -30,6 +30,7 @@ template <typename T> struct GemmCfg;
 template <> struct GemmCfg<bf16_t> {
   static constexpr int BK = 64;
 };
+template <> struct GemmCfg<f16_t> : GemmCfg<bf16_t> {};
 template <> struct GemmCfg<float> {
   static constexpr int BK = 32;
 };
@@ -132,7 +133,7 @@ template <typename T, bool KC, bool FAST> struct OperandTile {
           else
             ((float*)img)[k * 128 + row] = e[i];
         } else {
-          *(bf16_t*)(img + bf16_img_off<BK>(row, k >> 3) + (k & 7) * 2) = e[i];
+          *(T*)(img + bf16_img_off<BK>(row, k >> 3) + (k & 7) * 2) = e[i];
         }
       }
     }
@@ -145,7 +146,7 @@ template <typename T, bool KC> __device__ __forceinline__ auto frag(const char* 
     const float* f = (const float*)img;
     return KC ? f[row * (BK + 1) + 2 * ks + lh] : f[(2 * ks + lh) * 128 + row];
   } else {
-    return *(const bf16x8*)(img + bf16_img_off<BK>(row, 2 * ks + lh));
+    return *(const typename DT<T>::v8*)(img + bf16_img_off<BK>(row, 2 * ks + lh));
   }
 }
 
@@ -258,6 +259,8 @@ int launch_gemm(const void* A, int64_t lda, bool transA, const void* B, int64_t 
     return transB ? launch_gemm_tt<T, false, true>(p, stream) : launch_gemm_tt<T, false, false>(p, stream);
   if (dtype == SOW_BF16) {
     SOW_GEMM_DISPATCH(bf16_t)
+  } else if (dtype == SOW_F16) {
+    SOW_GEMM_DISPATCH(f16_t)
   } else if (dtype == SOW_F32) {
     // vector-aligned fp32 products run on the bf16 matrix pipe as 3 x bf16 splits (gemm_x3.hip; F32_EXACT switch: fp32 MFMA)
     if (p.vecA && p.vecB && p.vecC && K >= 16 && !sw_on(SW_F32_EXACT))

@@ -36,7 +36,7 @@ struct ChainParams {
   size_t planes_bytes;
 };
 int launch_chain(ChainParams p, int dtype, bool bwd, hipStream_t stream);
-// chain2.hip (bf16 streaming version)
+// chain2.hip (bf16 / f16 streaming version; dtype SOW_BF16 or SOW_F16)
 constexpr int C2_MAXG = 4;   // layers per grouped launch
 struct ChainGroup {
   ChainParams p[C2_MAXG];
@@ -46,9 +46,9 @@ struct ChainGroup {
 };
 extern void* g_chain2_stamps;
 bool chain2_supported(const ChainParams& p, int dtype);
-int launch_chain2(const ChainParams& p, bool bwd, hipStream_t stream);
+int launch_chain2(const ChainParams& p, bool bwd, int dtype, hipStream_t stream);
 // one grid for n <= C2_MAXG independent layers of the same direction (each one chain2_supported)
-int launch_chain2_group(const ChainParams* ps, int n, bool bwd, hipStream_t stream);
+int launch_chain2_group(const ChainParams* ps, int n, bool bwd, int dtype, hipStream_t stream);
 int launch_h_reduce(const float* Hpartial, int nsplit, void* Hsave, int64_t M, int rb, float scale, int dtype,
                     hipStream_t stream);
 // chain2f.hip (fp32 streaming version)
@@ -156,13 +156,14 @@ int launch_pad64(const void* in, void* out, int rows, int r, hipStream_t stream)
 int launch_gemm3(const void* A, int64_t lda, const void* B, int64_t ldb, bool nt, const void* A2, int64_t lda2,
                  const void* B2, int64_t ldb2, int k2, void* C, int64_t ldc, const void* bias, int64_t M, int N, int K,
                  float alpha, float beta, hipStream_t stream);
-// gemm4.hip (same contract as launch_gemm2; 256x256x64 tiles, two wave groups in anti-phase, v_mfma_f32_16x16x32_bf16)
+// gemm4.hip (same contract as launch_gemm2; 256x256x64 tiles, two wave groups in anti-phase, v_mfma_f32_16x16x32_bf16 / _f16)
 bool gemm4_supported(const void* A, int64_t lda, const void* B, int64_t ldb, bool nt, const void* A2, int64_t lda2,
                      const void* B2, int64_t ldb2, const void* C, int64_t ldc, const void* bias, int64_t M, int N, int K,
                      int dtype);
+// dtype: SOW_BF16 or SOW_F16 (gemm4_f16_kernel)
 int launch_gemm4(const void* A, int64_t lda, const void* B, int64_t ldb, bool nt, const void* A2, int64_t lda2,
                  const void* B2, int64_t ldb2, int k2, void* C, int64_t ldc, const void* bias, int64_t M, int N, int K,
-                 float alpha, float beta, hipStream_t stream, void* ws = nullptr, size_t ws_bytes = 0);
+                 float alpha, float beta, hipStream_t stream, void* ws = nullptr, size_t ws_bytes = 0, int dtype = SOW_BF16);
 // split-K of gemm4 for short M (<= 128 output tiles): scratch bytes (0 = the shape does not split), and the split count a
 // launch with this scratch takes (1 = none)
 size_t gemm4_splitk_bytes(int64_t M, int N, int K, bool has_ext);
@@ -174,7 +175,7 @@ bool gemm4h_supported(const void* X, int64_t ldx, const void* W, int64_t ldw, bo
                       int N, int K, int r, int dtype);
 int launch_gemm4h(const void* X, int64_t ldx, const void* W, int64_t ldw, bool nt, const void* F, int64_t ldf,
                   const void* G, int64_t ldg, void* C, int64_t ldc, const void* bias, void* H, int64_t M, int N, int K,
-                  int r, float hscale, hipStream_t stream);
+                  int r, float hscale, int dtype, hipStream_t stream);
 // gemm2h.hip (the same product with the projection h = hscale * X . op(F) computed in the kernel: one launch per pass)
 bool gemm2h_supported(const void* X, int64_t ldx, const void* W, int64_t ldw, bool nt, const void* F, int64_t ldf,
                       const void* G, int64_t ldg, const void* C, int64_t ldc, const void* bias, const void* H, int64_t M,

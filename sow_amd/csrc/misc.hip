@@ -94,6 +94,8 @@ int launch_adamw_flat(void* p, const void* g, void* m, void* v, int64_t n, float
   if (dtype == SOW_F32 && state_dtype == SOW_F32) SOW_ADAMW(float, float);
   else if (dtype == SOW_BF16 && state_dtype == SOW_BF16) SOW_ADAMW(bf16_t, bf16_t);
   else if (dtype == SOW_BF16 && state_dtype == SOW_F32) SOW_ADAMW(bf16_t, float);
+  else if (dtype == SOW_F16 && state_dtype == SOW_F16) SOW_ADAMW(f16_t, f16_t);
+  else if (dtype == SOW_F16 && state_dtype == SOW_F32) SOW_ADAMW(f16_t, float);
   else return SOW_ERR_DTYPE;
 #undef SOW_ADAMW
   SOW_CHECK_LAUNCH();
@@ -237,7 +239,7 @@ int launch_small_inverse(const float* A, float* out, int batch, int r, hipStream
   return SOW_OK;
 }
 
-// y = a*x + b*y   (fp32 or bf16)
+// y = a*x + b*y   (fp32, bf16 or f16)
 template <typename T>
 __global__ __launch_bounds__(256) void axpby_kernel(const T* x, T* y, int64_t n, float a, float b) {
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
@@ -256,6 +258,8 @@ int launch_axpby(const void* x, void* y, int64_t n, float a, float b, int dtype,
     hipLaunchKernelGGL(axpby_kernel<float>, dim3(grid), dim3(256), 0, stream, (const float*)x, (float*)y, n, a, b);
   else if (dtype == SOW_BF16)
     hipLaunchKernelGGL(axpby_kernel<bf16_t>, dim3(grid), dim3(256), 0, stream, (const bf16_t*)x, (bf16_t*)y, n, a, b);
+  else if (dtype == SOW_F16)
+    hipLaunchKernelGGL(axpby_kernel<f16_t>, dim3(grid), dim3(256), 0, stream, (const f16_t*)x, (f16_t*)y, n, a, b);
   else
     return SOW_ERR_DTYPE;
   SOW_CHECK_LAUNCH();

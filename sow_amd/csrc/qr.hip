@@ -65,16 +65,23 @@ int launch_cast_copy(const void* src, int64_t lds, int src_dtype, void* dst, int
                      int cols, hipStream_t stream) {
   if (rows <= 0 || cols <= 0) return SOW_OK;
   const int g = grid_for(rows * cols);
-  if (src_dtype == SOW_F32 && dst_dtype == SOW_F32)
-    hipLaunchKernelGGL((cast_copy_kernel<float, float>), dim3(g), dim3(256), 0, stream, (const float*)src, lds, (float*)dst, ldd, rows, cols);
-  else if (src_dtype == SOW_F32 && dst_dtype == SOW_BF16)
-    hipLaunchKernelGGL((cast_copy_kernel<float, bf16_t>), dim3(g), dim3(256), 0, stream, (const float*)src, lds, (bf16_t*)dst, ldd, rows, cols);
-  else if (src_dtype == SOW_BF16 && dst_dtype == SOW_F32)
-    hipLaunchKernelGGL((cast_copy_kernel<bf16_t, float>), dim3(g), dim3(256), 0, stream, (const bf16_t*)src, lds, (float*)dst, ldd, rows, cols);
-  else if (src_dtype == SOW_BF16 && dst_dtype == SOW_BF16)
-    hipLaunchKernelGGL((cast_copy_kernel<bf16_t, bf16_t>), dim3(g), dim3(256), 0, stream, (const bf16_t*)src, lds, (bf16_t*)dst, ldd, rows, cols);
-  else
+#define SOW_CAST(Tin, Tout) \
+  hipLaunchKernelGGL((cast_copy_kernel<Tin, Tout>), dim3(g), dim3(256), 0, stream, (const Tin*)src, lds, (Tout*)dst, ldd, rows, cols)
+#define SOW_CAST_TO(Tin)                                     \
+  if (dst_dtype == SOW_F32) SOW_CAST(Tin, float);            \
+  else if (dst_dtype == SOW_BF16) SOW_CAST(Tin, bf16_t);     \
+  else if (dst_dtype == SOW_F16) SOW_CAST(Tin, f16_t);       \
+  else return SOW_ERR_DTYPE;
+  if (src_dtype == SOW_F32) {
+    SOW_CAST_TO(float)
+  } else if (src_dtype == SOW_BF16) {
+    SOW_CAST_TO(bf16_t)
+  } else if (src_dtype == SOW_F16) {
+    SOW_CAST_TO(f16_t)
+  } else
     return SOW_ERR_DTYPE;
+#undef SOW_CAST_TO
+#undef SOW_CAST
   SOW_CHECK_LAUNCH();
   return SOW_OK;
 }
@@ -92,6 +99,8 @@ int launch_qr_panel(const void* W, int64_t ldw, int in_dtype, int m, int kc, int
     hipLaunchKernelGGL(qr_copy_in_kernel<float>, dim3(g), dim3(256), 0, stream, (const float*)W, ldw, Pt, m, kc);
   else if (in_dtype == SOW_BF16)
     hipLaunchKernelGGL(qr_copy_in_kernel<bf16_t>, dim3(g), dim3(256), 0, stream, (const bf16_t*)W, ldw, Pt, m, kc);
+  else if (in_dtype == SOW_F16)
+    hipLaunchKernelGGL(qr_copy_in_kernel<f16_t>, dim3(g), dim3(256), 0, stream, (const f16_t*)W, ldw, Pt, m, kc);
   else
     return SOW_ERR_DTYPE;
   SOW_CHECK_LAUNCH();
@@ -108,6 +117,8 @@ int launch_qr_copy_out(const float* Qt, const float* Pt, void* Q, int64_t ldq, v
     hipLaunchKernelGGL(qr_copy_out_kernel<float>, dim3(g), dim3(256), 0, stream, Qt, Pt, (float*)Q, ldq, (float*)R, ldr, m, kc, r, k_rows);
   else if (out_dtype == SOW_BF16)
     hipLaunchKernelGGL(qr_copy_out_kernel<bf16_t>, dim3(g), dim3(256), 0, stream, Qt, Pt, (bf16_t*)Q, ldq, (bf16_t*)R, ldr, m, kc, r, k_rows);
+  else if (out_dtype == SOW_F16)
+    hipLaunchKernelGGL(qr_copy_out_kernel<f16_t>, dim3(g), dim3(256), 0, stream, Qt, Pt, (f16_t*)Q, ldq, (f16_t*)R, ldr, m, kc, r, k_rows);
   else
     return SOW_ERR_DTYPE;
   SOW_CHECK_LAUNCH();

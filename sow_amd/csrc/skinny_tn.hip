@@ -28,6 +28,7 @@ template <typename T> struct TnCfg;
 template <> struct TnCfg<bf16_t> {
   static constexpr int BT = 64;  // tokens per staged chunk
 };
+template <> struct TnCfg<f16_t> : TnCfg<bf16_t> {};
 template <> struct TnCfg<float> {
   static constexpr int BT = 32;
 };
@@ -77,8 +78,9 @@ template <typename T> __global__ __launch_bounds__(256, 2) void tn_partial_kerne
         const bool tv = tt < t_end;
         sd[j] = tv ? *(const uint32_t*)(Sg + tt * 64 + 2 * dp) : 0u;
         if (J.ones_col >= 0 && (J.ones_col >> 1) == dp && tv) {
-          // replace element ones_col of the pair by bf16(1.0) = 0x3F80
-          sd[j] = (J.ones_col & 1) ? ((sd[j] & 0xffffu) | 0x3F800000u) : ((sd[j] & 0xffff0000u) | 0x3F80u);
+          // replace element ones_col of the pair by 1.0 (bf16 0x3F80, f16 0x3C00)
+          constexpr uint32_t one = DT<T>::one_bits;
+          sd[j] = (J.ones_col & 1) ? ((sd[j] & 0xffffu) | (one << 16)) : ((sd[j] & 0xffff0000u) | one);
         }
       }
       if (J.vec) {
@@ -93,7 +95,7 @@ template <typename T> __global__ __launch_bounds__(256, 2) void tn_partial_kerne
         for (int i = 0; i < 16; ++i) {
           const int e = t + 256 * i, d = e & 63, tl = e >> 6;
           const int64_t tt = tt0 + tl;
-          me[i] = (tt < t_end && d0 + d < J.D) ? Mg[tt * J.ldm + d0 + d] : (bf16_t)0.f;
+          me[i] = (tt < t_end && d0 + d < J.D) ? Mg[tt * J.ldm + d0 + d] : from_f32<T>(0.f);
         }
       }
     } else {
@@ -139,7 +141,7 @@ template <typename T> __global__ __launch_bounds__(256, 2) void tn_partial_kerne
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           const int e = t + 256 * i, d = e & 63, tl = e >> 6;
-          *(bf16_t*)(Mi + bf16_img_off<BT>(d, tl >> 3) + (tl & 7) * 2) = me[i];
+          *(T*)(Mi + bf16_img_off<BT>(d, tl >> 3) + (tl & 7) * 2) = me[i];
         }
       }
     } else {
@@ -177,8 +179,9 @@ template <typename T> __global__ __launch_bounds__(256, 2) void tn_partial_kerne
     } else {
 #pragma unroll
       for (int ks = 0; ks < BT / 16; ++ks) {
-        const bf16x8 a = *(const bf16x8*)(Mi + bf16_img_off<BT>(dm * 32 + li, 2 * ks + lh));
-        const bf16x8 bb = *(const bf16x8*)(Si + bf16_img_off<BT>(rn * 32 + li, 2 * ks + lh));
+        using V8 = typename DT<T>::v8;
+        const V8 a = *(const V8*)(Mi + bf16_img_off<BT>(dm * 32 + li, 2 * ks + lh));
+        const V8 bb = *(const V8*)(Si + bf16_img_off<BT>(rn * 32 + li, 2 * ks + lh));
         acc = mfma32(a, bb, acc);
       }
     }
@@ -1383,6 +1386,9 @@ int launch_tn(const TnParams& p, int dtype, hipStream_t stream) {
     } else {
       hipLaunchKernelGGL(tn_partial_kernel<bf16_t>, dim3(blocks), dim3(256), 0, stream, p);
     }
+  } else if (dtype == SOW_F16) {
+    // no f16 LDS-DMA / row-owner kernels: the generic one for every shape
+    hipLaunchKernelGGL(tn_partial_kernel<f16_t>, dim3(blocks), dim3(256), 0, stream, p);
   } else if (dtype == SOW_F32) {
     bool dma = p.slab_len % 8 == 0;
     for (int j = 0; j < p.njobs; ++j) {
@@ -1419,6 +1425,8 @@ int launch_tn_reduce_batch(const ReduceParams* descs, const int* starts, int n, 
   if (n <= 0 || total_blocks <= 0) return SOW_OK;
   if (dtype == SOW_BF16)
     hipLaunchKernelGGL(tn_reduce_batch_kernel<bf16_t>, dim3(total_blocks), dim3(256), 0, stream, descs, starts, n);
+  else if (dtype == SOW_F16)
+    hipLaunchKernelGGL(tn_reduce_batch_kernel<f16_t>, dim3(total_blocks), dim3(256), 0, stream, descs, starts, n);
   else if (dtype == SOW_F32)
     hipLaunchKernelGGL(tn_reduce_batch_kernel<float>, dim3(total_blocks), dim3(256), 0, stream, descs, starts, n);
   else
@@ -1434,6 +1442,8 @@ int launch_tn_reduce(ReduceParams p, int dtype, hipStream_t stream) {
   if (blocks == 0) return SOW_OK;
   if (dtype == SOW_BF16)
     hipLaunchKernelGGL(tn_reduce_kernel<bf16_t>, dim3(blocks), dim3(256), 0, stream, p);
+  else if (dtype == SOW_F16)
+    hipLaunchKernelGGL(tn_reduce_kernel<f16_t>, dim3(blocks), dim3(256), 0, stream, p);
   else if (dtype == SOW_F32)
     hipLaunchKernelGGL(tn_reduce_kernel<float>, dim3(blocks), dim3(256), 0, stream, p);
   else

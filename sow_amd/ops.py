@@ -13,14 +13,14 @@ import torch
 
 from . import _lib
 
-_DT = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16}
+_DT = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
 
 
 def _dt(t: torch.Tensor) -> int:
     try:
         return _DT[t.dtype]
     except KeyError:
-        raise TypeError(f"sow_amd supports float32 and bfloat16 tensors, got {t.dtype}") from None
+        raise TypeError(f"sow_amd supports float32, bfloat16 and float16 tensors, got {t.dtype}") from None
 
 
 def _need_gpu(*ts: Optional[torch.Tensor]) -> torch.device:

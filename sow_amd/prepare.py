@@ -198,7 +198,7 @@ def _accumulate_batched(mods):
         A0 = m.downscale_weights._parameters["0"]
         by_key.setdefault((A0.device, A0.dtype), []).append(m)
     for (dev, dtype), group in by_key.items():
-        es = 2 if dtype == torch.bfloat16 else 4
+        es = torch.empty((), dtype=dtype).element_size()
         hooked = [("_fresh_gaussian" in m.__dict__) or (type(m)._fresh_gaussian is not SoWLinear._fresh_gaussian_default)
                   for m in group]
         qr = [m.init_method == "normal_QR" for m in group]
