@@ -61,7 +61,8 @@ const char* sow_error_string(int code);
 /* Kernel-selection switches -- for A/B measurements and for the tests that pin every kernel variant; production code
  * never touches them.  They are the library's ONLY process-wide state: a table of atomics initialised from the
  * environment (SOW_AMD_<NAME>) once, at first use; no launch path calls getenv.  Names: FORCE_CHAIN_V1, NO_SHORT_SPLIT,
- * NO_FUSED_H, FORCE_GEMM_V1, TN_NARROW, NO_GEMM3S, NO_GROUPED, NO_PERSIST, NO_NT_STORE, NT_LOAD, NO_PAIR_FLUSH, F32_EXACT, NO_PARK16, TN_NO_NT_LOAD, NO_TN_ROWS, NO_GEMM4H, NO_CHAIN3F, NO_TN_F32Q, NO_SPLITK
+ * NO_FUSED_H, FORCE_GEMM_V1, TN_NARROW, NO_GEMM3S, NO_GROUPED, NO_PERSIST, NO_NT_STORE, NT_LOAD, NO_PAIR_FLUSH, F32_EXACT, NO_PARK16, TN_NO_NT_LOAD, NO_TN_ROWS, NO_GEMM4H, NO_CHAIN3F, NO_TN_F32Q, NO_SPLITK,
+ * NO_WIDE_CHAIN
  * (value 1 = on, -1 / 0 = off) and GEMM3S, GEMM3, GEMM4
  * (1 = force, 0 = forbid, -1 = automatic).  sow_set_switch returns SOW_ERR_UNSUPPORTED for an unknown name;
  * sow_get_switch returns the value (-1 / 0 / 1).  Changing a switch while other threads launch is safe (atomic) but
@@ -72,7 +73,8 @@ int sow_get_switch(const char* name);
 /* Bytes of workspace needed by sow_forward / sow_backward for this shape. */
 size_t sow_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, int dtype);
 /* Bytes of workspace sow_forward itself touches: 0 for most bf16 shapes (the caller may then pass NULL / 0), else the
- * same figure as sow_workspace_bytes (a low-rank accumulator wider than 64; short inputs, whose chain is split over K
+ * same figure as sow_workspace_bytes (r_live > 64: the packed factors of the fused wide chain, or the projection when the
+ * caller passes h_save = NULL to the generic composition; a low-rank accumulator wider than 64; short inputs, whose chain is split over K
  * and over the output columns to fill the chip; fp32 inputs with T >= 8192, whose factors are pre-split into bf16 planes
  * there; a bf16 dense accumulator at short T and long K, whose product is split over K).  A caller that passes NULL / 0
  * where the query is non-zero still gets the right result from a slower kernel, except for the wide low-rank accumulator
@@ -83,7 +85,13 @@ size_t sow_h_save_elems(int64_t T, int r_live);
 
 /* SoWLinear.forward -- replaces sow.py:107-126:
  *   y = acc_term + scale * (x @ A) @ B + bias,   h_save = scale * (x @ A) for r_live <= 64 (padded to 64
- *   columns, column 63 = 1.0 when free) or x @ A for r_live > 64; opaque to the caller, kept for backward.
+ *   columns, column 63 = 1.0 when free) or x @ A for r_live > 64 ([T, r_live] row-major, rounded once; y is computed from
+ *   the rounded h); opaque to the caller, kept for backward.  h_save may be NULL when no backward follows (the projection
+ *   then stays on chip, or goes to the workspace).
+ * bf16 / f16 layers with even r_live in (64, 256], d_in and d_out multiples of 8 and 16-byte-aligned x / y / bias run the
+ * fused wide chain (one pass over x; the NO_WIDE_CHAIN switch forces the generic GEMM composition), as does a low-rank
+ * accumulator with even r_acc in (64, 256]; their backward runs the same chain for dX and a token-slab weight-gradient
+ * kernel (dA, dB and dbias in one pass over x and dY, partial sums added in a fixed order).
  * x [T,d_in], A [d_in,r_live], B [r_live,d_out], y [T,d_out]; acc_down/acc_up per acc_kind
  * (r_acc = vr for SOW_ACC_LOWRANK, ignored otherwise); bias [d_out] or NULL.
  * The accumulator term is NOT scaled (sow.py:110-112). */
@@ -131,8 +139,9 @@ int sow_backward_ex(const void* dy, const void* x, const void* h_save, const voi
  *   sow_reduce_desc_bytes()    size of one opaque descriptor
  *   sow_backward_reduce_desc() writes the descriptor of one layer to HOST memory `desc_out` and its block count to
  *                              `blocks_out` (same shape / pointer arguments as the sow_backward_ex call it completes;
- *                              SOW_ERR_UNSUPPORTED for r_live > 64, or r_live = 64 with dbias: those have no separate
- *                              reduction -- use SOW_BWD_WEIGHTS)
+ *                              r_live > 64: an empty descriptor with 0 blocks, PARTIAL already finished the gradients;
+ *                              SOW_ERR_UNSUPPORTED for r_live = 64 with dbias: no separate reduction -- use
+ *                              SOW_BWD_WEIGHTS); sow_reduce_batch skips 0-block entries
  *   sow_reduce_batch()         `descs`: n descriptors back to back in DEVICE memory; `starts`: n ints in device memory,
  *                              starts[i] = sum of the block counts of layers < i; total_blocks = their total. */
 size_t sow_reduce_desc_bytes(void);

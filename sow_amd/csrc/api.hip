@@ -45,7 +45,8 @@ static int launch_colsum(const void* dy, int64_t T, int d_out, void* dbias, floa
 namespace sow {
 static const char* const kSwitchNames[SW_COUNT] = {"FORCE_CHAIN_V1", "NO_SHORT_SPLIT", "NO_FUSED_H", "FORCE_GEMM_V1", "TN_NARROW",
                                                    "NO_GEMM3S",      "GEMM3S",         "GEMM3",      "NO_GROUPED",     "NO_PERSIST",     "NO_NT_STORE",    "NT_LOAD",        "NO_PAIR_FLUSH",  "F32_EXACT",
-                                                   "NO_PARK16",      "TN_NO_NT_LOAD",  "NO_TN_ROWS",     "GEMM4",          "NO_GEMM4H",      "NO_CHAIN3F",     "NO_TN_F32Q",     "NO_SPLITK"};
+                                                   "NO_PARK16",      "TN_NO_NT_LOAD",  "NO_TN_ROWS",     "GEMM4",          "NO_GEMM4H",      "NO_CHAIN3F",     "NO_TN_F32Q",     "NO_SPLITK",
+                                                   "NO_WIDE_CHAIN"};
 static std::atomic<int> g_switch[SW_COUNT];
 static std::once_flag g_switch_once;
 static void switches_from_env() {
@@ -143,7 +144,7 @@ static int gemm_auto(const void* A, int64_t lda, const void* B, int64_t ldb, boo
 
 extern "C" {
 
-int sow_version(void) { return 112; }
+int sow_version(void) { return 113; }
 
 int sow_set_switch(const char* name, int value) {
   if (!name) return SOW_ERR_NULL;
@@ -188,7 +189,8 @@ size_t sow_h_save_elems(int64_t T, int r_live) { return (size_t)T * (size_t)(r_l
 
 // workspace carve (identical in the query and in the calls)
 struct WsPlan {
-  size_t off_dh, off_t, off_apad, off_hp, off_p0, off_p1, off_planes, planes_bytes, off_sk, sk_bytes, total;
+  size_t off_dh, off_t, off_apad, off_hp, off_p0, off_p1, off_planes, planes_bytes, off_sk, sk_bytes, off_wide, wide_bytes,
+      off_pw, pw_bytes, total;
   int ns, slab_len;
   int ns_cap;   // slabs the partial regions can hold (group-planned slab counts may exceed the single-layer choice)
 };
@@ -236,6 +238,25 @@ static WsPlan plan_ws(int64_t T, int d_in, int d_out, int r_live, int r_acc, int
     w.sk_bytes = f > b ? f : b;
     off += al256(w.sk_bytes);
   }
+  // fused wide-rank chain (chain_wide.hip): the packed factors of one launch -- the live factors or those of a wide low-rank
+  // accumulator (same stream, launch after launch: they share the region)
+  w.off_wide = off;
+  w.wide_bytes = 0;
+  {
+    int rw = chain_wide_shape_ok(r_live, d_in, d_out, dtype) ? r_live : 0;
+    if (acc_kind == SOW_ACC_LOWRANK && chain_wide_shape_ok(r_acc, d_in, d_out, dtype) && r_acc > rw) rw = r_acc;
+    if (rw) {
+      w.wide_bytes = chain_wide_pack_bytes(rw, d_in, d_out);
+      off += al256(w.wide_bytes);
+    }
+  }
+  // token-slab partials of the wide weight-gradient kernel (skinny_tn_wide.hip)
+  w.off_pw = off;
+  w.pw_bytes = 0;
+  if (tnw_shape_ok(r_live, d_in, d_out, dtype)) {
+    w.pw_bytes = tnw_partial_bytes(T, d_in, d_out, r_live);
+    off += al256(w.pw_bytes);
+  }
   w.total = off;
   return w;
 }
@@ -248,6 +269,22 @@ static char* ws_base(void* workspace) {
 // takes chain2f
 static void set_planes(ChainParams& p, char* ws, const WsPlan& w, size_t workspace_bytes) {
   if (ws && w.planes_bytes && workspace_bytes >= w.total) p.planes = ws + w.off_planes, p.planes_bytes = w.planes_bytes;
+}
+
+// One term of a wide-rank layer on the fused chain (chain_wide.hip), the factors packed into the workspace's wide region;
+// SOW_ERR_UNSUPPORTED: nothing launched, the caller composes generic GEMMs.  Forward (bwd = false): F1 = A-like [D1][r],
+// F2 = B-like [r][D2]; data gradient: F1 = B-like [r][D1], F2 = A-like [D2][r].
+static int wide_chain(const void* X, void* Y, const void* F1, int64_t ldf1, const void* F2, int64_t ldf2, void* Hsave,
+                      const void* bias, int64_t T, int D1, int D2, int r, float hscale, float yscale, float beta, bool bwd,
+                      int dtype, char* ws, const WsPlan& w, size_t workspace_bytes, hipStream_t stream) {
+  if (sw_on(SW_NO_WIDE_CHAIN) || !ws || !w.wide_bytes || workspace_bytes < w.total + 255 ||
+      chain_wide_pack_bytes(r, D1, D2) > w.wide_bytes)
+    return SOW_ERR_UNSUPPORTED;
+  WideArgs a{};
+  a.X = X, a.Y = Y, a.F1 = F1, a.F2 = F2, a.ldf1 = ldf1, a.ldf2 = ldf2, a.Hsave = Hsave, a.bias = bias;
+  a.M = T, a.D1 = D1, a.D2 = D2, a.r = r, a.hscale = hscale, a.yscale = yscale, a.beta = beta, a.bwd = bwd ? 1 : 0;
+  a.pack = ws + w.off_wide, a.pack_bytes = w.wide_bytes;
+  return launch_chain_wide(a, dtype, stream);
 }
 
 // the reduction of the slab partials of one layer (shared by sow_backward_ex and the deferred, batched form)
@@ -271,7 +308,13 @@ int sow_backward_reduce_desc(void* dA, void* dB, void* dbias, int64_t T, int d_i
   if (!ok_dtype(dtype)) return SOW_ERR_DTYPE;
   if (T <= 0 || d_in <= 0 || d_out <= 0 || r_live <= 0) return SOW_ERR_SHAPE;
   if (!dA || !dB || !workspace || !desc_out || !blocks_out) return SOW_ERR_NULL;
-  if (r_live > 64 || (dbias && r_live > 63)) return SOW_ERR_UNSUPPORTED;   // those paths have no separate reduction
+  if (r_live > 64) {
+    // the PARTIAL phase of a wide layer leaves finished gradients: an empty descriptor, no blocks in sow_reduce_batch
+    memset(desc_out, 0, sizeof(ReduceParams));
+    *blocks_out = 0;
+    return SOW_OK;
+  }
+  if (dbias && r_live > 63) return SOW_ERR_UNSUPPORTED;   // no separate reduction: use SOW_BWD_WEIGHTS
   if (acc_kind != SOW_ACC_LOWRANK) r_acc = 0;
   const WsPlan w = plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, dtype);
   if (workspace_bytes < w.total + 255) return SOW_ERR_WORKSPACE;
@@ -293,7 +336,8 @@ size_t sow_forward_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, i
   if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0 || !ok_dtype(dtype)) return 0;
   const bool wide_acc = acc_kind == SOW_ACC_LOWRANK && r_acc > 64;
   const WsPlan w = plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, dtype);
-  if (!wide_acc && short_hp_bytes(T, d_in, d_out, r_live, dtype) == 0 && w.planes_bytes == 0 && w.sk_bytes == 0) return 0;   // the forward does not touch it
+  if (!wide_acc && r_live <= 64 && short_hp_bytes(T, d_in, d_out, r_live, dtype) == 0 && w.planes_bytes == 0 && w.sk_bytes == 0)
+    return 0;   // the forward does not touch it
   return w.total + 256;
 }
 
@@ -365,10 +409,14 @@ int sow_forward(const void* x, const void* A, const void* B, const void* acc_dow
       beta = 1.f;
     } else {
       if (!ws || workspace_bytes < w.total) return SOW_ERR_WORKSPACE;
-      void* t = ws + w.off_t;
-      rc = launch_gemm(x, d_in, false, acc_down, r_acc, false, t, r_acc, nullptr, T, r_acc, d_in, 1.f, 0.f, dtype, stream);
-      if (rc) return rc;
-      rc = launch_gemm(t, r_acc, false, acc_up, d_out, false, y, d_out, nullptr, T, d_out, r_acc, 1.f, 0.f, dtype, stream);
+      rc = wide_chain(x, y, acc_down, r_acc, acc_up, d_out, nullptr, nullptr, T, d_in, d_out, r_acc, 1.f, 1.f, 0.f, false, dtype,
+                      ws, w, workspace_bytes, stream);
+      if (rc == SOW_ERR_UNSUPPORTED) {
+        void* t = ws + w.off_t;
+        rc = launch_gemm(x, d_in, false, acc_down, r_acc, false, t, r_acc, nullptr, T, r_acc, d_in, 1.f, 0.f, dtype, stream);
+        if (rc) return rc;
+        rc = launch_gemm(t, r_acc, false, acc_up, d_out, false, y, d_out, nullptr, T, d_out, r_acc, 1.f, 0.f, dtype, stream);
+      }
       if (rc) return rc;
       beta = 1.f;
     }
@@ -386,11 +434,20 @@ int sow_forward(const void* x, const void* A, const void* B, const void* acc_dow
     }
     return launch_chain(p, dtype, false, stream);
   }
-  // generic rank: h = x A ; y = beta*y + scale * h B + bias
-  if (!h_save) return SOW_ERR_NULL;
-  rc = launch_gemm(x, d_in, false, A, r_live, false, h_save, r_live, nullptr, T, r_live, d_in, 1.f, 0.f, dtype, stream);
+  // wide rank: the fused chain (h = x A kept on chip, copied to h_save when given), else the generic composition
+  //   h = x A ; y = beta*y + scale * h B + bias   with h in h_save or, without it, in the workspace
+  const bool ws_ok = ws && workspace_bytes >= w.total + 255;
+  rc = wide_chain(x, y, A, r_live, B, d_out, h_save, bias, T, d_in, d_out, r_live, 1.f, scale, beta, false, dtype, ws, w,
+                  workspace_bytes, stream);
+  if (rc != SOW_ERR_UNSUPPORTED) return rc;
+  void* h = h_save;
+  if (!h) {
+    if (!ws_ok) return SOW_ERR_WORKSPACE;
+    h = ws + w.off_dh;
+  }
+  rc = launch_gemm(x, d_in, false, A, r_live, false, h, r_live, nullptr, T, r_live, d_in, 1.f, 0.f, dtype, stream);
   if (rc) return rc;
-  return launch_gemm(h_save, r_live, false, B, d_out, false, y, d_out, bias, T, d_out, r_live, scale, beta, dtype, stream);
+  return launch_gemm(h, r_live, false, B, d_out, false, y, d_out, bias, T, d_out, r_live, scale, beta, dtype, stream);
 }
 
 int sow_backward_ex(const void* dy, const void* x, const void* h_save, const void* A, const void* B, const void* acc_down,
@@ -489,10 +546,14 @@ int sow_backward_ex(const void* dy, const void* x, const void* h_save, const voi
       if (rc) return rc;
       beta = 1.f;
     } else {
-      void* t = ws + w.off_t;
-      rc = launch_gemm(dy, d_out, false, acc_up, d_out, true, t, r_acc, nullptr, T, r_acc, d_out, 1.f, 0.f, dtype, stream);
-      if (rc) return rc;
-      rc = launch_gemm(t, r_acc, false, acc_down, r_acc, true, dx, d_in, nullptr, T, d_in, r_acc, 1.f, 0.f, dtype, stream);
+      rc = wide_chain(dy, dx, acc_up, d_out, acc_down, r_acc, nullptr, nullptr, T, d_out, d_in, r_acc, 1.f, 1.f, 0.f, true, dtype,
+                      ws, w, workspace_bytes, stream);
+      if (rc == SOW_ERR_UNSUPPORTED) {
+        void* t = ws + w.off_t;
+        rc = launch_gemm(dy, d_out, false, acc_up, d_out, true, t, r_acc, nullptr, T, r_acc, d_out, 1.f, 0.f, dtype, stream);
+        if (rc) return rc;
+        rc = launch_gemm(t, r_acc, false, acc_down, r_acc, true, dx, d_in, nullptr, T, d_in, r_acc, 1.f, 0.f, dtype, stream);
+      }
       if (rc) return rc;
       beta = 1.f;
     }
@@ -536,14 +597,24 @@ int sow_backward_ex(const void* dy, const void* x, const void* h_save, const voi
     }
     return SOW_OK;
   }
-  // generic rank (GEMM composition)
+  // wide rank: the fused chain (dh = scale dY B^T to the workspace, dX = beta dX + dh A^T) and the token-slab weight-gradient
+  // kernel, else the generic GEMM composition
   if (do_data) {
-    rc = launch_gemm(dy, d_out, false, B, d_out, true, dh, r_live, nullptr, T, r_live, d_out, scale, 0.f, dtype, stream);
-    if (rc) return rc;
-    rc = launch_gemm(dh, r_live, false, A, r_live, true, dx, d_in, nullptr, T, d_in, r_live, 1.f, beta, dtype, stream);
+    rc = wide_chain(dy, dx, B, d_out, A, r_live, dh, nullptr, T, d_out, d_in, r_live, scale, 1.f, beta, true, dtype, ws, w,
+                    workspace_bytes, stream);
+    if (rc == SOW_ERR_UNSUPPORTED) {
+      rc = launch_gemm(dy, d_out, false, B, d_out, true, dh, r_live, nullptr, T, r_live, d_out, scale, 0.f, dtype, stream);
+      if (rc) return rc;
+      rc = launch_gemm(dh, r_live, false, A, r_live, true, dx, d_in, nullptr, T, d_in, r_live, 1.f, beta, dtype, stream);
+    }
     if (rc) return rc;
   }
   if (!do_partial) return SOW_OK;   // wide ranks: the PARTIAL phase does all of the weight gradients
+  if (w.pw_bytes && !sw_on(SW_NO_WIDE_CHAIN)) {
+    rc = launch_tn_wide(x, dh, dy, h_save, dA, dB, dbias, T, d_in, d_out, r_live, scale, grad_beta, dtype, ws + w.off_pw,
+                        w.pw_bytes, stream);
+    if (rc != SOW_ERR_UNSUPPORTED) return rc;
+  }
   rc = launch_gemm(x, d_in, true, dh, r_live, false, dA, r_live, nullptr, d_in, r_live, (int)T, 1.f, grad_beta, dtype, stream);
   if (rc) return rc;
   rc = launch_gemm(h_save, r_live, true, dy, d_out, false, dB, d_out, nullptr, r_live, d_out, (int)T, scale, grad_beta, dtype, stream);

@@ -137,6 +137,51 @@ int launch_tn_rows(TnRowsItem* items, int n, hipStream_t stream);
 int launch_tn_group(const TnParams* ps, int n, hipStream_t stream);
 int launch_tn_reduce(ReduceParams p, int dtype, hipStream_t stream);
 int launch_tn_reduce_batch(const ReduceParams* descs, const int* starts, int n, int total_blocks, int dtype, hipStream_t stream);
+// chain_wide.hip (bf16 / f16, even r in (64, 256], D1 and D2 multiples of 8; X, Y, bias 16-byte aligned): the fused
+// wide-rank chain  H = rn(hscale * X . F1) (to Hsave [M, r] when non-null),  Y = beta * Y + yscale * H . F2 + bias.
+// Forward (bwd = 0): F1 = A [D1][r] (ldf1 = r), F2 = B [r][D2] (ldf2 = D2).  Data gradient (bwd = 1): F1 = B [r][D1]
+// (ldf1 = D1), F2 = A [D2][r] (ldf2 = r).  `pack` (16-byte aligned, chain_wide_pack_bytes) receives the packed factors.
+struct WideArgs {
+  const void* X;
+  void* Y;
+  const void *F1, *F2;
+  int64_t ldf1, ldf2;
+  void* Hsave;
+  const void* bias;
+  int64_t M;
+  int D1, D2, r;
+  float hscale, yscale, beta;
+  int bwd;
+  void* pack;
+  size_t pack_bytes;
+};
+bool chain_wide_shape_ok(int r, int d1, int d2, int dtype);
+size_t chain_wide_pack_bytes(int r, int d_in, int d_out);
+// SOW_ERR_UNSUPPORTED when the shape, the alignment or the scratch does not suit the kernel (nothing launched)
+int launch_chain_wide(const WideArgs& a, int dtype, hipStream_t stream);
+// skinny_tn_wide.hip: weight gradients of a wide-rank layer, token-slab partials + fixed-order reduction
+struct TnwParams {
+  const void* M[2];     // x [T, d_in], dY [T, d_out]
+  const void* S[2];     // dh [T, r], h [T, r]
+  float* partial[2];    // [ns][Dpad][r_pad] fp32
+  float* colsum;        // [ns][Dpad of dY] fp32 (dbias), or nullptr
+  int D[2], ncg[2];
+  int64_t T;
+  int r, r_pad, ns, slab_len;
+};
+struct TnwReduce {
+  const float *P0, *P1, *CS;
+  void *dA, *dB, *dbias;
+  int D0, D1, r, r_pad, ns;
+  float scale, beta;
+};
+bool tnw_shape_ok(int r, int d_in, int d_out, int dtype);
+int tnw_pick_slabs(int64_t T, int d_in, int d_out, int* slab_len);
+size_t tnw_partial_bytes(int64_t T, int d_in, int d_out, int r);
+// dA = x^T dh, dB = scale h^T dY, dbias = colsum(dY), each g = beta g + new; `ws` 256-byte aligned (tnw_partial_bytes)
+int launch_tn_wide(const void* x, const void* dh, const void* dy, const void* h, void* dA, void* dB, void* dbias, int64_t T,
+                   int d_in, int d_out, int r, float scale, float beta, int dtype, void* ws, size_t ws_bytes,
+                   hipStream_t stream);
 // gemm.hip
 int launch_gemm(const void* A, int64_t lda, bool transA, const void* B, int64_t ldb, bool transB, void* C, int64_t ldc,
                 const void* bias, int64_t M, int N, int K, float alpha, float beta, int dtype, hipStream_t stream);

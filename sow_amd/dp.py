@@ -61,9 +61,10 @@ class _GradSink:
         self.queued = False       # data gradient done, waiting for the rest of the block
 
     def usable(self, A, B) -> bool:
-        # n_iter == 1 layers only (A, B ARE the bucket's parameters), gradients bound to the flat buffer, r <= 64
+        # n_iter == 1 layers only (A, B ARE the bucket's parameters), gradients bound to the flat buffer, r <= 256 (a wide
+        # layer's PARTIAL phase finishes its gradients; its deferred reduction is an empty descriptor)
         pA, pB = self.pA, self.pB
-        return (A.data_ptr() == pA.data_ptr() and B.data_ptr() == pB.data_ptr() and B.shape[0] <= 64
+        return (A.data_ptr() == pA.data_ptr() and B.data_ptr() == pB.data_ptr() and B.shape[0] <= 256
                 and pA.grad is not None and pB.grad is not None
                 and pA.grad.data_ptr() == self.bucket.grad_ptr(pA) and pB.grad.data_ptr() == self.bucket.grad_ptr(pB))
 

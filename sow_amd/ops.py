@@ -130,8 +130,8 @@ def sow_forward(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, ac
                 save_h: bool = True):
     """y, h_save = forward of the SoW contraction on a flattened [T, d_in] input.  save_h = False (no-grad / eval callers,
     e.g. the reload + generate loop of commonsense_evaluate.py:268-287): the projection is not written to HBM and None
-    is returned in its place (r <= 64 without a dense accumulator; wider ranks compose two GEMMs and need the buffer as
-    their intermediate, a dense accumulator's fused kernels write it as scratch)."""
+    is returned in its place (every rank except r <= 64 with a dense accumulator, whose fused kernels write it as scratch;
+    a wide layer off the fused chain keeps its intermediate in the forward workspace)."""
     lib = _lib.load()
     dev = _need_gpu(x2, A, B, acc_down if acc_down is not None and acc_down.numel() else None,
                     acc_up if acc_up is not None and acc_up.numel() else None, bias)
@@ -153,7 +153,7 @@ def sow_forward(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, ac
     h = None
     # a dense accumulator at r <= 64 takes the saved projection as scratch even when it is not kept: without it
     # sow_forward composes the product from two launches and rounds y twice (the training forward rounds it once)
-    if save_h or r > 64 or kind == _lib.ACC_DENSE:
+    if save_h or (r <= 64 and kind == _lib.ACC_DENSE):
         h = torch.empty(T * (64 if r <= 64 else r), dtype=x2.dtype, device=dev)   # == sow_h_save_elems(T, r)
     # the forward touches a workspace only for some shapes (include/sow_amd.h: sow_forward_workspace_bytes)
     nws = _forward_workspace_bytes(lib, T, d_in, d_out, r, r_acc, kind, dt)
@@ -230,7 +230,7 @@ class LayerCall:
         # save_h = False (forward_only calls that no backward follows): h_save = NULL, the projection stays on chip --
         # except with a dense accumulator, whose single-launch kernels need the buffer (as in sow_forward)
         self.h = h if h is not None else (torch.empty(T * (64 if r <= 64 else r), dtype=x2.dtype, device=dev)
-                                          if (save_h or r > 64 or not forward_only or kind == _lib.ACC_DENSE) else None)
+                                          if (save_h or not forward_only or (r <= 64 and kind == _lib.ACC_DENSE)) else None)
         self.dx = dx
         r_acc = acc_down.shape[1] if kind == _lib.ACC_LOWRANK else 0
         # a forward-only call needs scratch for a few shapes only (sow_forward_workspace_bytes), often none at all
