@@ -40,6 +40,24 @@ extern "C" {
 #define SOW_DTYPE_BF16 1
 #define SOW_DTYPE_F16 2
 
+/* Parameters in fp32 (mixed precision, as under torch.autocast): OR-ed into SOW_DTYPE_BF16 or SOW_DTYPE_F16 (the compute
+ * dtype).  Accepted by sow_workspace_bytes, sow_forward_workspace_bytes, sow_forward, sow_backward, sow_backward_ex,
+ * sow_backward_reduce_desc, sow_reduce_batch, sow_forward_group, sow_backward_group, sow_backward_group_reduce_desc and
+ * sow_backward_group_plan; every other entry point, and SOW_DTYPE_F32 | SOW_PARAM_F32 anywhere, returns SOW_ERR_DTYPE
+ * (checked on the host before anything is launched or dereferenced).  With the flag:
+ *   - the activations are of the compute dtype: x, y, h_save, dy, dx (and the internal dh);
+ *   - A, B, bias, acc_down and acc_up are read as fp32, each element rounded once, to nearest even, to the compute dtype
+ *     before use (the cast autocast applies to every F.linear / matmul operand, bias included): one launch packs all of
+ *     them (every layer of a group call) into the caller's workspace, and the bf16 / f16 kernels run on the packed copies
+ *     -- results equal those of the unflagged call on pre-rounded parameters bit for bit;
+ *   - dA, dB and dbias are fp32, written as g = grad_beta * g + new, `new` the fp32 sum of the slab partials rounded once to
+ *     fp32 (never through a bf16 / f16 intermediate); T = 0 zeroes fp32-sized gradients;
+ *   - the workspace queries include the packed parameters: pass the flagged dtype to them.  The forward figure is then never
+ *     0; it is the unflagged forward figure plus the packed parameters (a forward that needs no scratch of its own asks for
+ *     the packed parameters only).  Nothing is cached between calls -- the parameters are packed again by every call that reads them (forward and
+ *     the DATA phase of backward) -- and the calls stay capturable (no host synchronisation, no allocation). */
+#define SOW_PARAM_F32 0x100
+
 #define SOW_OK 0
 #define SOW_ERR_NULL (-1)
 #define SOW_ERR_SHAPE (-2)
@@ -309,7 +327,8 @@ int sow_small_inverse(const float* A, float* out, int batch, int r, void* stream
 /* y = a*x + b*y over n elements. */
 int sow_axpby(const void* x, void* y, int64_t n, float a, float b, int dtype, void* stream);
 
-/* Strided 2-D cast copy between f32 / bf16. */
+/* Strided 2-D cast copy between any two of f32 / bf16 / f16 (RNE when narrowing; contiguous 16-byte-aligned buffers take a
+ * vectorised kernel).  Casts the fp32 x of a layer under autocast to the compute dtype, and its bf16 / f16 gradient back. */
 int sow_cast_copy(const void* src, int64_t lds, int src_dtype, void* dst, int64_t ldd, int dst_dtype, int64_t rows,
                   int cols, void* stream);
 

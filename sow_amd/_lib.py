@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SOW_AMD_LIB") or os.path.join(_HERE, "lib", "libsow_amd.so")
 
 F32, BF16, F16 = 0, 1, 2
+PARAM_F32 = 0x100        # OR-ed into BF16 / F16: fp32 parameters, fp32 weight gradients (mixed precision)
 ACC_NONE, ACC_LOWRANK, ACC_DENSE = 0, 1, 2
 H_COLS = 64
 BWD_DATA, BWD_WEIGHTS, BWD_WEIGHTS_PARTIAL, BWD_WEIGHTS_REDUCE = 1, 2, 4, 8

@@ -10,9 +10,9 @@
 
 namespace sow {
 
-// column sums of a [T, D] matrix (fallback path only: r_live > 64 with bias)
-template <typename T>
-__global__ __launch_bounds__(256) void colsum_kernel(const T* M, int64_t ld, int64_t rows, int D, T* out, float beta) {
+// column sums of a [T, D] matrix (fallback path only: r_live > 64 with bias); TO = T, or float (SOW_PARAM_F32)
+template <typename T, typename TO>
+__global__ __launch_bounds__(256) void colsum_kernel(const T* M, int64_t ld, int64_t rows, int D, TO* out, float beta) {
   __shared__ float red[4][64];
   const int c = blockIdx.x * 64 + (threadIdx.x & 63), w = threadIdx.x >> 6;
   float s = 0.f;
@@ -23,17 +23,24 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* M, int64_t ld, int
   if (w == 0 && c < D) {
     float v = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
     if (beta != 0.f) v += beta * to_f32(out[c]);
-    out[c] = from_f32<T>(v);
+    out[c] = from_f32<TO>(v);
   }
 }
-static int launch_colsum(const void* dy, int64_t T, int d_out, void* dbias, float beta, int dtype, hipStream_t stream) {
+static int launch_colsum(const void* dy, int64_t T, int d_out, void* dbias, float beta, int dtype, int out_dtype,
+                         hipStream_t stream) {
   const dim3 grid((d_out + 63) / 64);
+  if (out_dtype != dtype && out_dtype != SOW_F32) return SOW_ERR_DTYPE;
+  const bool o32 = out_dtype == SOW_F32;
   if (dtype == SOW_F32)
-    hipLaunchKernelGGL(colsum_kernel<float>, grid, dim3(256), 0, stream, (const float*)dy, (int64_t)d_out, T, d_out, (float*)dbias, beta);
+    hipLaunchKernelGGL((colsum_kernel<float, float>), grid, dim3(256), 0, stream, (const float*)dy, (int64_t)d_out, T, d_out, (float*)dbias, beta);
+  else if (dtype == SOW_BF16 && o32)
+    hipLaunchKernelGGL((colsum_kernel<bf16_t, float>), grid, dim3(256), 0, stream, (const bf16_t*)dy, (int64_t)d_out, T, d_out, (float*)dbias, beta);
   else if (dtype == SOW_BF16)
-    hipLaunchKernelGGL(colsum_kernel<bf16_t>, grid, dim3(256), 0, stream, (const bf16_t*)dy, (int64_t)d_out, T, d_out, (bf16_t*)dbias, beta);
+    hipLaunchKernelGGL((colsum_kernel<bf16_t, bf16_t>), grid, dim3(256), 0, stream, (const bf16_t*)dy, (int64_t)d_out, T, d_out, (bf16_t*)dbias, beta);
+  else if (dtype == SOW_F16 && o32)
+    hipLaunchKernelGGL((colsum_kernel<f16_t, float>), grid, dim3(256), 0, stream, (const f16_t*)dy, (int64_t)d_out, T, d_out, (float*)dbias, beta);
   else if (dtype == SOW_F16)
-    hipLaunchKernelGGL(colsum_kernel<f16_t>, grid, dim3(256), 0, stream, (const f16_t*)dy, (int64_t)d_out, T, d_out, (f16_t*)dbias, beta);
+    hipLaunchKernelGGL((colsum_kernel<f16_t, f16_t>), grid, dim3(256), 0, stream, (const f16_t*)dy, (int64_t)d_out, T, d_out, (f16_t*)dbias, beta);
   else
     return SOW_ERR_DTYPE;
   SOW_CHECK_LAUNCH();
@@ -72,6 +79,14 @@ static inline size_t esize(int dtype) { return dtype == SOW_F32 ? 4 : 2; }
 static inline bool ok_dtype(int d) { return d == SOW_F32 || d == SOW_BF16 || d == SOW_F16; }
 static inline bool al4p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 static inline bool al16p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// SOW_PARAM_F32: the compute dtype of a flagged dtype (*pf = flag present); -1 for a combination no layer entry point takes
+static inline int split_dtype(int d, bool* pf) {
+  *pf = (d & SOW_PARAM_F32) != 0;
+  const int cd = d & ~SOW_PARAM_F32;
+  if (!ok_dtype(cd) || (*pf && cd == SOW_F32)) return -1;
+  return cd;
+}
+static inline bool flagged(int d) { return (d & SOW_PARAM_F32) != 0; }
 
 // ---- short inputs ---------------------------------------------------------------------------------
 // T / 64 workgroups cannot fill 256 CUs: below SHORT_NTB token blocks the streaming chain is launched as
@@ -144,7 +159,7 @@ static int gemm_auto(const void* A, int64_t lda, const void* B, int64_t ldb, boo
 
 extern "C" {
 
-int sow_version(void) { return 113; }
+int sow_version(void) { return 114; }
 
 int sow_set_switch(const char* name, int value) {
   if (!name) return SOW_ERR_NULL;
@@ -271,6 +286,58 @@ static void set_planes(ChainParams& p, char* ws, const WsPlan& w, size_t workspa
   if (ws && w.planes_bytes && workspace_bytes >= w.total) p.planes = ws + w.off_planes, p.planes_bytes = w.planes_bytes;
 }
 
+// ---- fp32 parameters (SOW_PARAM_F32) ----------------------------------------------------------------------
+// The fp32 A, B, bias and accumulator of a call are rounded once to the compute dtype into a region of the layer's workspace
+// past the compute-dtype plan (pack_params_kernel, misc.hip); the bf16 / f16 kernels then read the packed copies, in the
+// layouts they read from the caller.  Packed again at every call: the factors change at every optimizer step.
+static inline size_t pack_elems_bytes(int64_t n) { return al256((size_t)n * 2); }
+static size_t pack_bytes(int d_in, int d_out, int r_live, int r_acc, int acc_kind) {
+  size_t b = pack_elems_bytes((int64_t)d_in * r_live) + pack_elems_bytes((int64_t)r_live * d_out) + pack_elems_bytes(d_out);
+  if (acc_kind == SOW_ACC_DENSE) b += pack_elems_bytes((int64_t)d_in * d_out);
+  if (acc_kind == SOW_ACC_LOWRANK) b += pack_elems_bytes((int64_t)d_in * r_acc) + pack_elems_bytes((int64_t)r_acc * d_out);
+  return b;
+}
+// Appends the pack items of layer L (T > 0, pointers checked) to `items` and points L's parameter operands at the packed
+// copies.  The packed copies go past the compute-dtype plan (where they never touch what a backward phase leaves in the
+// workspace), except for a forward (fwd) whose kernels need no scratch (sow_forward_workspace_bytes = 0 for the compute
+// dtype) given a workspace sized by the flagged forward query only: there they start the workspace.  Such a forward then runs
+// without workspace, exactly as the unflagged call.
+static int pack_layer(sow_layer_args& L, int cd, bool fwd, std::vector<PackItem>& items) {
+  const int r_acc = L.acc_kind == SOW_ACC_LOWRANK ? L.r_acc : 0;
+  const WsPlan w = plan_ws(L.T, L.d_in, L.d_out, L.r_live, r_acc, L.acc_kind, cd);
+  const size_t pack = pack_bytes(L.d_in, L.d_out, L.r_live, r_acc, L.acc_kind);
+  const bool no_scratch = fwd && sow_forward_workspace_bytes(L.T, L.d_in, L.d_out, L.r_live, r_acc, L.acc_kind, cd) == 0;
+  const size_t off = (no_scratch && L.workspace_bytes < w.total + pack + 255) ? 0 : w.total;
+  if (!L.workspace) return SOW_ERR_NULL;
+  if (L.workspace_bytes < off + pack + 255) return SOW_ERR_WORKSPACE;
+  char* dst = ws_base(L.workspace) + off;
+  if (no_scratch) L.workspace = nullptr, L.workspace_bytes = 0;
+  auto put = [&](const void*& src, int64_t n) {
+    if (!src) return;
+    items.push_back(PackItem{(const float*)src, dst, n});
+    src = dst;
+    dst += pack_elems_bytes(n);
+  };
+  put(L.A, (int64_t)L.d_in * L.r_live);
+  put(L.B, (int64_t)L.r_live * L.d_out);
+  put(L.bias, L.d_out);
+  if (L.acc_kind == SOW_ACC_DENSE) put(L.acc_down, (int64_t)L.d_in * L.d_out);
+  if (L.acc_kind == SOW_ACC_LOWRANK) {
+    put(L.acc_down, (int64_t)L.d_in * r_acc);
+    put(L.acc_up, (int64_t)r_acc * L.d_out);
+  }
+  return SOW_OK;
+}
+static sow_layer_args single_layer(const void* A, const void* B, const void* acc_down, const void* acc_up, const void* bias,
+                                   int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, void* workspace,
+                                   size_t workspace_bytes) {
+  sow_layer_args L{};
+  L.A = A, L.B = B, L.acc_down = acc_down, L.acc_up = acc_up, L.bias = bias;
+  L.T = T, L.d_in = d_in, L.d_out = d_out, L.r_live = r_live, L.r_acc = r_acc, L.acc_kind = acc_kind;
+  L.workspace = workspace, L.workspace_bytes = workspace_bytes;
+  return L;
+}
+
 // One term of a wide-rank layer on the fused chain (chain_wide.hip), the factors packed into the workspace's wide region;
 // SOW_ERR_UNSUPPORTED: nothing launched, the caller composes generic GEMMs.  Forward (bwd = false): F1 = A-like [D1][r],
 // F2 = B-like [r][D2]; data gradient: F1 = B-like [r][D1], F2 = A-like [D2][r].
@@ -305,7 +372,9 @@ size_t sow_reduce_desc_bytes(void) { return sizeof(ReduceParams); }
 int sow_backward_reduce_desc(void* dA, void* dB, void* dbias, int64_t T, int d_in, int d_out, int r_live, int r_acc,
                              int acc_kind, float grad_beta, int dtype, void* workspace, size_t workspace_bytes, void* desc_out,
                              int* blocks_out) {
-  if (!ok_dtype(dtype)) return SOW_ERR_DTYPE;
+  bool pf;
+  dtype = split_dtype(dtype, &pf);   // the descriptor is the same with fp32 gradients: sow_reduce_batch picks the output type
+  if (dtype < 0) return SOW_ERR_DTYPE;
   if (T <= 0 || d_in <= 0 || d_out <= 0 || r_live <= 0) return SOW_ERR_SHAPE;
   if (!dA || !dB || !workspace || !desc_out || !blocks_out) return SOW_ERR_NULL;
   if (r_live > 64) {
@@ -325,7 +394,10 @@ int sow_backward_reduce_desc(void* dA, void* dB, void* dbias, int64_t T, int d_i
 }
 
 int sow_reduce_batch(const void* descs, const int* starts, int n, int total_blocks, int dtype, void* stream) {
-  if (!ok_dtype(dtype)) return SOW_ERR_DTYPE;
+  bool pf;
+  const int cd = split_dtype(dtype, &pf);
+  if (cd < 0) return SOW_ERR_DTYPE;
+  if (pf) dtype = SOW_F32;   // the slab partials are fp32 whatever the compute dtype: fp32 gradients are their sums, rounded once
   if (n < 0 || total_blocks < 0) return SOW_ERR_SHAPE;
   if (n == 0) return SOW_OK;
   if (!descs || !starts) return SOW_ERR_NULL;
@@ -333,7 +405,14 @@ int sow_reduce_batch(const void* descs, const int* starts, int n, int total_bloc
 }
 
 size_t sow_forward_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, int dtype) {
-  if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0 || !ok_dtype(dtype)) return 0;
+  bool pf;
+  dtype = split_dtype(dtype, &pf);
+  if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0 || dtype < 0) return 0;
+  if (pf) {   // the forward's own scratch (if any) followed by the packed parameters (pack_layer)
+    const size_t own = sow_forward_workspace_bytes(T, d_in, d_out, r_live, r_acc, acc_kind, dtype);
+    const size_t pack = pack_bytes(d_in, d_out, r_live, acc_kind == SOW_ACC_LOWRANK ? r_acc : 0, acc_kind);
+    return own ? own + pack : pack + 256;
+  }
   const bool wide_acc = acc_kind == SOW_ACC_LOWRANK && r_acc > 64;
   const WsPlan w = plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, dtype);
   if (!wide_acc && r_live <= 64 && short_hp_bytes(T, d_in, d_out, r_live, dtype) == 0 && w.planes_bytes == 0 && w.sk_bytes == 0)
@@ -342,14 +421,17 @@ size_t sow_forward_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, i
 }
 
 size_t sow_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, int dtype) {
-  if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0 || !ok_dtype(dtype)) return 0;
-  return plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, dtype).total + 256;
+  bool pf;
+  dtype = split_dtype(dtype, &pf);
+  if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0 || dtype < 0) return 0;
+  const size_t pack = pf ? pack_bytes(d_in, d_out, r_live, acc_kind == SOW_ACC_LOWRANK ? r_acc : 0, acc_kind) : 0;
+  return plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, dtype).total + pack + 256;
 }
 
 
-int sow_forward(const void* x, const void* A, const void* B, const void* acc_down, const void* acc_up, const void* bias,
-                void* y, void* h_save, int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, float scale,
-                int dtype, void* workspace, size_t workspace_bytes, void* stream_) {
+static int forward_impl(const void* x, const void* A, const void* B, const void* acc_down, const void* acc_up, const void* bias,
+                        void* y, void* h_save, int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, float scale,
+                        int dtype, void* workspace, size_t workspace_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!ok_dtype(dtype)) return SOW_ERR_DTYPE;
   if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0) return SOW_ERR_SHAPE;
@@ -450,10 +532,37 @@ int sow_forward(const void* x, const void* A, const void* B, const void* acc_dow
   return launch_gemm(h, r_live, false, B, d_out, false, y, d_out, bias, T, d_out, r_live, scale, beta, dtype, stream);
 }
 
-int sow_backward_ex(const void* dy, const void* x, const void* h_save, const void* A, const void* B, const void* acc_down,
-                    const void* acc_up, void* dx, void* dA, void* dB, void* dbias, int64_t T, int d_in, int d_out,
-                    int r_live, int r_acc, int acc_kind, float scale, float grad_beta, int dtype, void* workspace,
-                    size_t workspace_bytes, int phases, void* stream_) {
+int sow_forward(const void* x, const void* A, const void* B, const void* acc_down, const void* acc_up, const void* bias,
+                void* y, void* h_save, int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, float scale,
+                int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  bool pf;
+  const int cd = split_dtype(dtype, &pf);
+  if (cd < 0) return SOW_ERR_DTYPE;
+  if (!pf)
+    return forward_impl(x, A, B, acc_down, acc_up, bias, y, h_save, T, d_in, d_out, r_live, r_acc, acc_kind, scale, dtype,
+                        workspace, workspace_bytes, stream);
+  // fp32 parameters: the same checks as forward_impl before the pack launch reads them
+  if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0) return SOW_ERR_SHAPE;
+  if (T == 0) return SOW_OK;
+  if (!x || !A || !B || !y) return SOW_ERR_NULL;
+  if (acc_kind != SOW_ACC_NONE && !acc_down) return SOW_ERR_NULL;
+  if (acc_kind == SOW_ACC_LOWRANK && (!acc_up || r_acc <= 0)) return SOW_ERR_SHAPE;
+  if (acc_kind != SOW_ACC_LOWRANK) r_acc = 0, acc_up = nullptr;
+  if (acc_kind == SOW_ACC_NONE) acc_down = nullptr;
+  sow_layer_args L = single_layer(A, B, acc_down, acc_up, bias, T, d_in, d_out, r_live, r_acc, acc_kind, workspace, workspace_bytes);
+  std::vector<PackItem> items;
+  int rc = pack_layer(L, cd, true, items);
+  if (rc) return rc;
+  if ((rc = launch_pack_params(items.data(), (int)items.size(), cd, (hipStream_t)stream))) return rc;
+  return forward_impl(x, L.A, L.B, L.acc_down, L.acc_up, L.bias, y, h_save, T, d_in, d_out, r_live, r_acc, acc_kind, scale, cd,
+                      L.workspace, L.workspace_bytes, stream);
+}
+
+// gdt: the dtype of dA / dB / dbias -- dtype, or SOW_F32 under SOW_PARAM_F32 (the fp32 slab sums rounded once to fp32)
+static int backward_impl(const void* dy, const void* x, const void* h_save, const void* A, const void* B, const void* acc_down,
+                         const void* acc_up, void* dx, void* dA, void* dB, void* dbias, int64_t T, int d_in, int d_out,
+                         int r_live, int r_acc, int acc_kind, float scale, float grad_beta, int dtype, int gdt, void* workspace,
+                         size_t workspace_bytes, int phases, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   const bool do_data = (phases & SOW_BWD_DATA) != 0;
   const bool do_partial = (phases & (SOW_BWD_WEIGHTS | SOW_BWD_WEIGHTS_PARTIAL)) != 0;
@@ -467,8 +576,8 @@ int sow_backward_ex(const void* dy, const void* x, const void* h_save, const voi
     if (!dA || !dB) return SOW_ERR_NULL;
     if (grad_beta == 0.f) {
       void* ptrs[3] = {dA, dB, dbias};
-      int64_t bytes[3] = {(int64_t)d_in * r_live * (int64_t)esize(dtype), (int64_t)r_live * d_out * (int64_t)esize(dtype),
-                          dbias ? (int64_t)d_out * (int64_t)esize(dtype) : 0};
+      int64_t bytes[3] = {(int64_t)d_in * r_live * (int64_t)esize(gdt), (int64_t)r_live * d_out * (int64_t)esize(gdt),
+                          dbias ? (int64_t)d_out * (int64_t)esize(gdt) : 0};
       return launch_multi_zero(ptrs, bytes, 3, stream);
     }
     return SOW_OK;
@@ -589,10 +698,10 @@ int sow_backward_ex(const void* dy, const void* x, const void* h_save, const voi
     }
     if (!do_reduce) return SOW_OK;
     const ReduceParams rp = make_reduce_params(w, ws, dA, dB, ones_ok ? dbias : nullptr, d_in, d_out, r_live, grad_beta);
-    rc = launch_tn_reduce(rp, dtype, stream);
+    rc = launch_tn_reduce(rp, gdt, stream);
     if (rc) return rc;
     if (dbias && !ones_ok) {
-      rc = launch_colsum(dy, T, d_out, dbias, grad_beta, dtype, stream);
+      rc = launch_colsum(dy, T, d_out, dbias, grad_beta, dtype, gdt, stream);
       if (rc) return rc;
     }
     return SOW_OK;
@@ -611,19 +720,51 @@ int sow_backward_ex(const void* dy, const void* x, const void* h_save, const voi
   }
   if (!do_partial) return SOW_OK;   // wide ranks: the PARTIAL phase does all of the weight gradients
   if (w.pw_bytes && !sw_on(SW_NO_WIDE_CHAIN)) {
-    rc = launch_tn_wide(x, dh, dy, h_save, dA, dB, dbias, T, d_in, d_out, r_live, scale, grad_beta, dtype, ws + w.off_pw,
+    rc = launch_tn_wide(x, dh, dy, h_save, dA, dB, dbias, T, d_in, d_out, r_live, scale, grad_beta, dtype, gdt, ws + w.off_pw,
                         w.pw_bytes, stream);
     if (rc != SOW_ERR_UNSUPPORTED) return rc;
   }
-  rc = launch_gemm(x, d_in, true, dh, r_live, false, dA, r_live, nullptr, d_in, r_live, (int)T, 1.f, grad_beta, dtype, stream);
+  rc = launch_gemm_out(x, d_in, true, dh, r_live, false, dA, r_live, nullptr, d_in, r_live, (int)T, 1.f, grad_beta, dtype, gdt,
+                       stream);
   if (rc) return rc;
-  rc = launch_gemm(h_save, r_live, true, dy, d_out, false, dB, d_out, nullptr, r_live, d_out, (int)T, scale, grad_beta, dtype, stream);
+  rc = launch_gemm_out(h_save, r_live, true, dy, d_out, false, dB, d_out, nullptr, r_live, d_out, (int)T, scale, grad_beta, dtype,
+                       gdt, stream);
   if (rc) return rc;
   if (dbias) {
-    rc = launch_colsum(dy, T, d_out, dbias, grad_beta, dtype, stream);
+    rc = launch_colsum(dy, T, d_out, dbias, grad_beta, dtype, gdt, stream);
     if (rc) return rc;
   }
   return SOW_OK;
+}
+
+int sow_backward_ex(const void* dy, const void* x, const void* h_save, const void* A, const void* B, const void* acc_down,
+                    const void* acc_up, void* dx, void* dA, void* dB, void* dbias, int64_t T, int d_in, int d_out,
+                    int r_live, int r_acc, int acc_kind, float scale, float grad_beta, int dtype, void* workspace,
+                    size_t workspace_bytes, int phases, void* stream) {
+  bool pf;
+  const int cd = split_dtype(dtype, &pf);
+  if (!pf)
+    return backward_impl(dy, x, h_save, A, B, acc_down, acc_up, dx, dA, dB, dbias, T, d_in, d_out, r_live, r_acc, acc_kind, scale,
+                         grad_beta, dtype, dtype, workspace, workspace_bytes, phases, stream);
+  if (cd < 0) return SOW_ERR_DTYPE;
+  // fp32 parameters: only the data gradient reads the factors (and the accumulator); they are packed when it runs
+  if ((phases & SOW_BWD_DATA) && T > 0) {
+    if (d_in <= 0 || d_out <= 0 || r_live <= 0) return SOW_ERR_SHAPE;
+    if (!dy || !x || !h_save || !A || !B || !dx || !dA || !dB || !workspace) return SOW_ERR_NULL;
+    if (acc_kind != SOW_ACC_NONE && !acc_down) return SOW_ERR_NULL;
+    if (acc_kind == SOW_ACC_LOWRANK && (!acc_up || r_acc <= 0)) return SOW_ERR_SHAPE;
+    if (acc_kind != SOW_ACC_LOWRANK) r_acc = 0, acc_up = nullptr;
+    if (acc_kind == SOW_ACC_NONE) acc_down = nullptr;
+    sow_layer_args L = single_layer(A, B, acc_down, acc_up, nullptr, T, d_in, d_out, r_live, r_acc, acc_kind, workspace,
+                                    workspace_bytes);
+    std::vector<PackItem> items;
+    int rc = pack_layer(L, cd, false, items);
+    if (rc) return rc;
+    if ((rc = launch_pack_params(items.data(), (int)items.size(), cd, (hipStream_t)stream))) return rc;
+    A = L.A, B = L.B, acc_down = L.acc_down, acc_up = L.acc_up;
+  }
+  return backward_impl(dy, x, h_save, A, B, acc_down, acc_up, dx, dA, dB, dbias, T, d_in, d_out, r_live, r_acc, acc_kind, scale,
+                       grad_beta, cd, SOW_F32, workspace, workspace_bytes, phases, stream);
 }
 
 int sow_backward(const void* dy, const void* x, const void* h_save, const void* A, const void* B, const void* acc_down,
@@ -694,7 +835,24 @@ static int check_layer(const sow_layer_args& L, bool bwd) {
   return SOW_OK;
 }
 
-int sow_forward_group(const sow_layer_args* layers, int n, int dtype, void* stream_) {
+// fp32 parameters of a group: a copy of the layer list pointing at the packed operands, every layer packed by ONE launch
+static int pack_group(const sow_layer_args* layers, int n, int cd, bool bwd, std::vector<sow_layer_args>& out, void* stream) {
+  out.assign(layers, layers + n);
+  std::vector<PackItem> items;
+  int rc;
+  for (sow_layer_args& L : out) {
+    if ((rc = check_layer(L, bwd))) return rc;
+    if (L.T == 0) continue;
+    if (L.acc_kind == SOW_ACC_LOWRANK && (!L.acc_up || L.r_acc <= 0)) return SOW_ERR_SHAPE;
+    if (L.acc_kind != SOW_ACC_LOWRANK) L.acc_up = nullptr;
+    if (L.acc_kind == SOW_ACC_NONE) L.acc_down = nullptr;
+    if (bwd) L.bias = nullptr;   // backward reads no bias
+    if ((rc = pack_layer(L, cd, !bwd, items))) return rc;
+  }
+  return launch_pack_params(items.data(), (int)items.size(), cd, (hipStream_t)stream);
+}
+
+static int forward_group_impl(const sow_layer_args* layers, int n, int dtype, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!ok_dtype(dtype)) return SOW_ERR_DTYPE;
   if (n < 0) return SOW_ERR_SHAPE;
@@ -744,7 +902,17 @@ int sow_forward_group(const sow_layer_args* layers, int n, int dtype, void* stre
   return nb ? launch_chain2_group(batch, nb, false, dtype, stream) : SOW_OK;
 }
 
-int sow_backward_group(const sow_layer_args* layers, int n, int dtype, int phases, void* stream_) {
+int sow_forward_group(const sow_layer_args* layers, int n, int dtype, void* stream) {
+  bool pf;
+  const int cd = split_dtype(dtype, &pf);
+  if (cd < 0) return SOW_ERR_DTYPE;
+  if (!pf || n <= 0 || !layers) return forward_group_impl(layers, n, cd, stream);
+  std::vector<sow_layer_args> packed;
+  const int rc = pack_group(layers, n, cd, false, packed, stream);
+  return rc ? rc : forward_group_impl(packed.data(), n, cd, stream);
+}
+
+static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, int gdt, int phases, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   const bool do_data = (phases & SOW_BWD_DATA) != 0;
   const bool do_partial = (phases & (SOW_BWD_WEIGHTS | SOW_BWD_WEIGHTS_PARTIAL)) != 0;
@@ -758,9 +926,9 @@ int sow_backward_group(const sow_layer_args* layers, int n, int dtype, int phase
   for (int i = 0; i < n; ++i)
     if ((rc = check_layer(layers[i], true))) return rc;
   auto single = [&](const sow_layer_args& L, int ph) {
-    return sow_backward_ex(L.dy, L.x, L.h_save, L.A, L.B, L.acc_down, L.acc_up, L.dx, L.dA, L.dB, L.dbias, L.T, L.d_in, L.d_out,
-                           L.r_live, L.r_acc, L.acc_kind, L.scale, L.grad_beta, dtype, L.workspace, L.workspace_bytes, ph,
-                           stream_);
+    return backward_impl(L.dy, L.x, L.h_save, L.A, L.B, L.acc_down, L.acc_up, L.dx, L.dA, L.dB, L.dbias, L.T, L.d_in, L.d_out,
+                         L.r_live, L.r_acc, L.acc_kind, L.scale, L.grad_beta, dtype, gdt, L.workspace, L.workspace_bytes, ph,
+                         stream_);
   };
   auto plan = [&](const sow_layer_args& L) {
     return plan_ws(L.T, L.d_in, L.d_out, L.r_live, L.acc_kind == SOW_ACC_LOWRANK ? L.r_acc : 0, L.acc_kind, dtype);
@@ -860,7 +1028,7 @@ int sow_backward_group(const sow_layer_args* layers, int n, int dtype, int phase
       const sow_layer_args& L = layers[i];
       ReduceParams rp = make_reduce_params(plan(L), ws_base(L.workspace), L.dA, L.dB, L.dbias, L.d_in, L.d_out, L.r_live, L.grad_beta);
       rp.job[0].ns = rns[2 * i], rp.job[1].ns = rns[2 * i + 1];
-      if ((rc = launch_tn_reduce(rp, dtype, stream))) return rc;
+      if ((rc = launch_tn_reduce(rp, gdt, stream))) return rc;
     }
   } else if (do_reduce) {
     for (int i = 0; i < n; ++i)
@@ -869,8 +1037,21 @@ int sow_backward_group(const sow_layer_args* layers, int n, int dtype, int phase
   return SOW_OK;
 }
 
+int sow_backward_group(const sow_layer_args* layers, int n, int dtype, int phases, void* stream) {
+  bool pf;
+  const int cd = split_dtype(dtype, &pf);
+  if (!pf) return backward_group_impl(layers, n, dtype, dtype, phases, stream);
+  if (cd < 0) return SOW_ERR_DTYPE;
+  if (n <= 0 || !layers || !(phases & SOW_BWD_DATA)) return backward_group_impl(layers, n, cd, SOW_F32, phases, stream);
+  std::vector<sow_layer_args> packed;
+  const int rc = pack_group(layers, n, cd, true, packed, stream);
+  return rc ? rc : backward_group_impl(packed.data(), n, cd, SOW_F32, phases, stream);
+}
+
 int sow_backward_group_plan(const sow_layer_args* layers, int n, int dtype, int phases, int* slabs_out) {
-  if (!ok_dtype(dtype)) return SOW_ERR_DTYPE;
+  bool pf;
+  dtype = split_dtype(dtype, &pf);   // the plan does not depend on the parameter dtype
+  if (dtype < 0) return SOW_ERR_DTYPE;
   if (n < 0) return SOW_ERR_SHAPE;
   if (n == 0) return 0;
   if (!layers) return SOW_ERR_NULL;
@@ -895,7 +1076,9 @@ int sow_backward_group_plan(const sow_layer_args* layers, int n, int dtype, int 
 }
 
 int sow_backward_group_reduce_desc(const sow_layer_args* layers, int n, int dtype, int phases, void* descs_out, int* blocks_out) {
-  if (!ok_dtype(dtype)) return SOW_ERR_DTYPE;
+  bool pf;
+  dtype = split_dtype(dtype, &pf);
+  if (dtype < 0) return SOW_ERR_DTYPE;
   if (n < 0) return SOW_ERR_SHAPE;
   if (n == 0) return SOW_OK;
   if (!layers || !descs_out || !blocks_out) return SOW_ERR_NULL;
@@ -933,6 +1116,7 @@ size_t sow_gemm_workspace_bytes(int64_t M, int N, int K, int trans_a, int dtype)
 int sow_gemm_ex(const void* A, int64_t lda, int trans_a, const void* B, int64_t ldb, int trans_b, void* C, int64_t ldc,
                 const void* bias, int64_t M, int N, int K, float alpha, float beta, int dtype, void* workspace,
                 size_t workspace_bytes, void* stream) {
+  if (flagged(dtype)) return SOW_ERR_DTYPE;   // SOW_PARAM_F32 is for the layer entry points only
   if (!trans_a)
     return gemm_auto(A, lda, B, ldb, trans_b != 0, C, ldc, bias, M, N, K, alpha, beta, dtype, (hipStream_t)stream, workspace,
                      workspace_bytes);
@@ -968,7 +1152,7 @@ size_t sow_qr_workspace_bytes(int m, int n, int k, int in_dtype, int need_r) {
 int sow_qr_thin(const void* W, int64_t ldw, int m, int n, int in_dtype, int k, void* Q_out, int64_t ldq, void* R_out,
                 int64_t ldr, int out_dtype, void* workspace, size_t workspace_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!ok_dtype(in_dtype) || !ok_dtype(out_dtype)) return SOW_ERR_DTYPE;
+  if (!ok_dtype(in_dtype) || !ok_dtype(out_dtype)) return SOW_ERR_DTYPE;   // rejects SOW_PARAM_F32 as well
   if (m <= 0 || n <= 0 || k <= 0 || k > m) return SOW_ERR_SHAPE;
   if (!W || !Q_out || !workspace) return SOW_ERR_NULL;
   const QrPlan q = plan_qr(m, n, k, in_dtype, R_out != nullptr, out_dtype == SOW_F32);
@@ -1049,6 +1233,7 @@ int sow_zero_state(void* const* ptrs, const int64_t* bytes, int n, void* stream)
 int sow_adamw_flat(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, float lr, float beta1,
                    float beta2, float eps, float weight_decay, int step, float grad_scale, int dtype, int state_dtype,
                    void* stream) {
+  if (flagged(dtype) || flagged(state_dtype)) return SOW_ERR_DTYPE;
   if (step < 1) return SOW_ERR_SHAPE;
   return launch_adamw_flat(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale,
                            dtype, state_dtype, (hipStream_t)stream);
@@ -1074,11 +1259,13 @@ int sow_small_inverse(const float* A, float* out, int batch, int r, void* stream
 }
 
 int sow_axpby(const void* x, void* y, int64_t n, float a, float b, int dtype, void* stream) {
+  if (flagged(dtype)) return SOW_ERR_DTYPE;
   return launch_axpby(x, y, n, a, b, dtype, (hipStream_t)stream);
 }
 
 int sow_cast_copy(const void* src, int64_t lds, int src_dtype, void* dst, int64_t ldd, int dst_dtype, int64_t rows,
                   int cols, void* stream) {
+  if (flagged(src_dtype) || flagged(dst_dtype) || !ok_dtype(src_dtype) || !ok_dtype(dst_dtype)) return SOW_ERR_DTYPE;
   if (!src || !dst) return SOW_ERR_NULL;
   return launch_cast_copy(src, lds, src_dtype, dst, ldd, dst_dtype, rows, cols, (hipStream_t)stream);
 }

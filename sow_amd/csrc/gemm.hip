@@ -150,8 +150,9 @@ template <typename T, bool KC> __device__ __forceinline__ auto frag(const char* 
   }
 }
 
-// TA: A given transposed (stored [K, M]); TB: B given as [N, K].
-template <typename T, bool TA, bool TB, bool FAST>
+// TA: A given transposed (stored [K, M]); TB: B given as [N, K].  TC: type of C and bias (T, or float for the fp32 weight
+// gradients of bf16 / f16 operands).
+template <typename T, bool TA, bool TB, bool FAST, typename TC = T>
 __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmParams p) {
   constexpr bool F32 = sizeof(T) == 4;
   constexpr int BK = GemmCfg<T>::BK;
@@ -209,21 +210,21 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmParams p) {
     __syncthreads();
   }
   float* scratch = (float*)(smem + w * SCR);
-  T* Cp = (T*)p.C;
+  TC* Cp = (TC*)p.C;
 #pragma unroll
   for (int mh = 0; mh < 2; ++mh)
-    wave_store_tiles<T, 2, FAST>(acc[mh], scratch, Cp, p.ldc, m0 + wm * 64 + mh * 32, n0 + wn * 64, p.M, p.N, p.alpha,
-                                 p.beta, (const T*)p.bias, lane);
+    wave_store_tiles<TC, 2, FAST>(acc[mh], scratch, Cp, p.ldc, m0 + wm * 64 + mh * 32, n0 + wn * 64, p.M, p.N, p.alpha,
+                                  p.beta, (const TC*)p.bias, lane);
 }
 
-template <typename T, bool TA, bool TB> static int launch_gemm_tt(const GemmParams& p, hipStream_t stream) {
+template <typename T, bool TA, bool TB, typename TC = T> static int launch_gemm_tt(const GemmParams& p, hipStream_t stream) {
   const int64_t tiles = (int64_t)ceil_div(p.M, G_BM) * ceil_div(p.N, G_BN);
   if (tiles <= 0) return SOW_OK;
   if (tiles > 0x7fffffff) return SOW_ERR_SHAPE;
   if (p.vecA && p.vecB && p.vecC)
-    hipLaunchKernelGGL((gemm_kernel<T, TA, TB, true>), dim3((unsigned)tiles), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((gemm_kernel<T, TA, TB, true, TC>), dim3((unsigned)tiles), dim3(256), 0, stream, p);
   else
-    hipLaunchKernelGGL((gemm_kernel<T, TA, TB, false>), dim3((unsigned)tiles), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((gemm_kernel<T, TA, TB, false, TC>), dim3((unsigned)tiles), dim3(256), 0, stream, p);
   SOW_CHECK_LAUNCH();
   return SOW_OK;
 }
@@ -234,6 +235,13 @@ static bool al4(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 
 // C[M,N] = alpha * op(A) op(B) + beta * C + bias.   transA: A stored [K,M]; transB: B stored [N,K].
 int launch_gemm(const void* A, int64_t lda, bool transA, const void* B, int64_t ldb, bool transB, void* C, int64_t ldc,
                 const void* bias, int64_t M, int N, int K, float alpha, float beta, int dtype, hipStream_t stream) {
+  return launch_gemm_out(A, lda, transA, B, ldb, transB, C, ldc, bias, M, N, K, alpha, beta, dtype, dtype, stream);
+}
+
+int launch_gemm_out(const void* A, int64_t lda, bool transA, const void* B, int64_t ldb, bool transB, void* C, int64_t ldc,
+                    const void* bias, int64_t M, int N, int K, float alpha, float beta, int dtype, int c_dtype,
+                    hipStream_t stream) {
+  if (c_dtype != dtype && !(c_dtype == SOW_F32 && (dtype == SOW_BF16 || dtype == SOW_F16))) return SOW_ERR_DTYPE;
   if (!A || !B || !C) return SOW_ERR_NULL;
   if (M < 0 || N < 0 || K < 0) return SOW_ERR_SHAPE;
   if (M == 0 || N == 0) return SOW_OK;
@@ -251,21 +259,29 @@ int launch_gemm(const void* A, int64_t lda, bool transA, const void* B, int64_t 
   };
   p.vecA = mode(A, lda, !transA, M);
   p.vecB = mode(B, ldb, transB, N);
-  p.vecC = (ldc % ve == 0 && N % ve == 0 && al16(C) && (!bias || al16(bias))) ? 1 : 0;
-#define SOW_GEMM_DISPATCH(T)                                                    \
-  if (transA)                                                                   \
-    return transB ? launch_gemm_tt<T, true, true>(p, stream) : launch_gemm_tt<T, true, false>(p, stream); \
-  else                                                                          \
-    return transB ? launch_gemm_tt<T, false, true>(p, stream) : launch_gemm_tt<T, false, false>(p, stream);
+  const int vc = c_dtype == SOW_F32 ? 4 : 8;
+  p.vecC = (ldc % vc == 0 && N % vc == 0 && al16(C) && (!bias || al16(bias))) ? 1 : 0;
+#define SOW_GEMM_DISPATCH(T, TC)                                                                                     \
+  if (transA)                                                                                                       \
+    return transB ? launch_gemm_tt<T, true, true, TC>(p, stream) : launch_gemm_tt<T, true, false, TC>(p, stream);   \
+  else                                                                                                              \
+    return transB ? launch_gemm_tt<T, false, true, TC>(p, stream) : launch_gemm_tt<T, false, false, TC>(p, stream);
+  if (c_dtype != dtype) {
+    if (dtype == SOW_BF16) {
+      SOW_GEMM_DISPATCH(bf16_t, float)
+    } else {
+      SOW_GEMM_DISPATCH(f16_t, float)
+    }
+  }
   if (dtype == SOW_BF16) {
-    SOW_GEMM_DISPATCH(bf16_t)
+    SOW_GEMM_DISPATCH(bf16_t, bf16_t)
   } else if (dtype == SOW_F16) {
-    SOW_GEMM_DISPATCH(f16_t)
+    SOW_GEMM_DISPATCH(f16_t, f16_t)
   } else if (dtype == SOW_F32) {
     // vector-aligned fp32 products run on the bf16 matrix pipe as 3 x bf16 splits (gemm_x3.hip; F32_EXACT switch: fp32 MFMA)
     if (p.vecA && p.vecB && p.vecC && K >= 16 && !sw_on(SW_F32_EXACT))
       return launch_gemm_x3(A, lda, transA, B, ldb, transB, C, ldc, bias, M, N, K, alpha, beta, stream);
-    SOW_GEMM_DISPATCH(float)
+    SOW_GEMM_DISPATCH(float, float)
   }
 #undef SOW_GEMM_DISPATCH
   return SOW_ERR_DTYPE;

@@ -178,13 +178,18 @@ struct TnwReduce {
 bool tnw_shape_ok(int r, int d_in, int d_out, int dtype);
 int tnw_pick_slabs(int64_t T, int d_in, int d_out, int* slab_len);
 size_t tnw_partial_bytes(int64_t T, int d_in, int d_out, int r);
-// dA = x^T dh, dB = scale h^T dY, dbias = colsum(dY), each g = beta g + new; `ws` 256-byte aligned (tnw_partial_bytes)
+// dA = x^T dh, dB = scale h^T dY, dbias = colsum(dY), each g = beta g + new; `ws` 256-byte aligned (tnw_partial_bytes);
+// the gradients are of out_dtype (dtype, or SOW_F32)
 int launch_tn_wide(const void* x, const void* dh, const void* dy, const void* h, void* dA, void* dB, void* dbias, int64_t T,
-                   int d_in, int d_out, int r, float scale, float beta, int dtype, void* ws, size_t ws_bytes,
+                   int d_in, int d_out, int r, float scale, float beta, int dtype, int out_dtype, void* ws, size_t ws_bytes,
                    hipStream_t stream);
 // gemm.hip
 int launch_gemm(const void* A, int64_t lda, bool transA, const void* B, int64_t ldb, bool transB, void* C, int64_t ldc,
                 const void* bias, int64_t M, int N, int K, float alpha, float beta, int dtype, hipStream_t stream);
+// the same with C (and bias) of c_dtype: c_dtype = dtype, or SOW_F32 for bf16 / f16 operands (fp32 weight gradients)
+int launch_gemm_out(const void* A, int64_t lda, bool transA, const void* B, int64_t ldb, bool transB, void* C, int64_t ldc,
+                    const void* bias, int64_t M, int N, int K, float alpha, float beta, int dtype, int c_dtype,
+                    hipStream_t stream);
 // gemm_x3.hip: the same contract for fp32 tensors on the bf16 matrix pipe (3 x bf16 splits); vector-aligned operands only
 int launch_gemm_x3(const void* A, int64_t lda, bool transA, const void* B, int64_t ldb, bool transB, void* C, int64_t ldc,
                    const void* bias, int64_t M, int N, int K, float alpha, float beta, hipStream_t stream);
@@ -288,4 +293,12 @@ int launch_tt_kron_core(const float* A, const float* B, float* out, int ra0, int
 int launch_absmax(const float* x, int64_t n, float* out, hipStream_t stream);
 int launch_small_inverse(const float* A, float* out, int batch, int r, hipStream_t stream);
 int launch_axpby(const void* x, void* y, int64_t n, float a, float b, int dtype, hipStream_t stream);
+// misc.hip: fp32 parameter operands (SOW_PARAM_F32) rounded once, RNE, to the compute dtype (bf16 / f16), many tensors per
+// launch; dst 16-byte aligned (the pack region of a layer's workspace)
+struct PackItem {
+  const float* src;
+  void* dst;
+  int64_t n;   // elements
+};
+int launch_pack_params(const PackItem* items, int n, int dtype, hipStream_t stream);
 }  // namespace sow

@@ -5,6 +5,7 @@
 //   * dense Adam moment update     -> TTAdam.step's dense section (ttadam.py:89-111)
 //   * TT Hadamard core product     -> TensorTrain.__mul__ (tt.py:469-475)
 //   * axpby / scale                -> TTSGD p += -lr * d_p (ttsgd.py:78)
+//   * parameter pack               -> the autocast cast of fp32 factors / bias / accumulator to bf16 / f16 (SOW_PARAM_F32)
 #include "kernels.hpp"
 
 namespace sow {
@@ -263,6 +264,63 @@ int launch_axpby(const void* x, void* y, int64_t n, float a, float b, int dtype,
   else
     return SOW_ERR_DTYPE;
   SOW_CHECK_LAUNCH();
+  return SOW_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Parameter pack (SOW_PARAM_F32): every fp32 parameter operand of a call -- A, B, bias, the accumulator, of every layer of a
+// group -- rounded once, RNE, to the compute dtype in ONE launch; grid.y = tensor, grid.x = chunks of 8 elements per thread.
+// from_f32<T> is the rounding the kernels apply to their own outputs, and torch's .to(bfloat16 / float16).
+// ---------------------------------------------------------------------------------------------
+constexpr int PK_MAX = 40;   // tensors per launch: 40 x 24 bytes of by-value arguments
+struct PackTable {
+  PackItem it[PK_MAX];
+  int n;
+};
+static_assert(sizeof(PackTable) <= 4096, "by-value kernel arguments must stay under 4 KiB");
+
+template <typename T> __global__ __launch_bounds__(256) void pack_params_kernel(const PackTable tb) {
+  const int ti = blockIdx.y;
+  if (ti >= tb.n) return;
+  const float* src = tb.it[ti].src;
+  T* dst = (T*)tb.it[ti].dst;
+  const int64_t n = tb.it[ti].n;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
+  int64_t done = 0;
+  if (((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0) {
+    const int64_t nv = n / 8;
+    for (int64_t i = tid; i < nv; i += nth) {
+      const f32x4 a = *(const f32x4*)(src + 8 * i), b = *(const f32x4*)(src + 8 * i + 4);
+      *(u32x4*)(dst + 8 * i) = u32x4{pack16x2<T>(a[0], a[1]), pack16x2<T>(a[2], a[3]), pack16x2<T>(b[0], b[1]),
+                                     pack16x2<T>(b[2], b[3])};
+    }
+    done = nv * 8;
+  }
+  for (int64_t i = done + tid; i < n; i += nth) dst[i] = from_f32<T>(src[i]);
+}
+
+int launch_pack_params(const PackItem* items, int n, int dtype, hipStream_t stream) {
+  if (dtype != SOW_BF16 && dtype != SOW_F16) return SOW_ERR_DTYPE;
+  for (int off = 0; off < n; off += PK_MAX) {
+    PackTable tb;
+    tb.n = n - off < PK_MAX ? n - off : PK_MAX;
+    int64_t maxn = 0;
+    for (int i = 0; i < tb.n; ++i) {
+      tb.it[i] = items[off + i];
+      if (tb.it[i].n < 0) return SOW_ERR_SHAPE;
+      if (tb.it[i].n > 0 && (!tb.it[i].src || !tb.it[i].dst)) return SOW_ERR_NULL;
+      if (tb.it[i].n > maxn) maxn = tb.it[i].n;
+    }
+    if (maxn == 0) continue;
+    int64_t gx = (maxn / 8 + 255) / 256;
+    if (gx < 1) gx = 1;
+    if (gx > 256) gx = 256;
+    if (dtype == SOW_BF16)
+      hipLaunchKernelGGL(pack_params_kernel<bf16_t>, dim3((unsigned)gx, tb.n), dim3(256), 0, stream, tb);
+    else
+      hipLaunchKernelGGL(pack_params_kernel<f16_t>, dim3((unsigned)gx, tb.n), dim3(256), 0, stream, tb);
+    SOW_CHECK_LAUNCH();
+  }
   return SOW_OK;
 }
 

@@ -190,9 +190,10 @@ size_t tnw_partial_bytes(int64_t T, int d_in, int d_out, int r) {
 static bool al4w(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; }
 
 int launch_tn_wide(const void* x, const void* dh, const void* dy, const void* h, void* dA, void* dB, void* dbias, int64_t T,
-                   int d_in, int d_out, int r, float scale, float beta, int dtype, void* ws, size_t ws_bytes,
+                   int d_in, int d_out, int r, float scale, float beta, int dtype, int out_dtype, void* ws, size_t ws_bytes,
                    hipStream_t stream) {
   if (!tnw_shape_ok(r, d_in, d_out, dtype)) return SOW_ERR_UNSUPPORTED;
+  if (out_dtype != dtype && out_dtype != SOW_F32) return SOW_ERR_DTYPE;
   if (!al4w(x) || !al4w(dh) || !al4w(dy) || !al4w(h) || !ws || (reinterpret_cast<uintptr_t>(ws) & 255) ||
       ws_bytes < tnw_partial_bytes(T, d_in, d_out, r))
     return SOW_ERR_UNSUPPORTED;
@@ -213,13 +214,18 @@ int launch_tn_wide(const void* x, const void* dh, const void* dy, const void* h,
   q.D0 = d_in, q.D1 = d_out, q.r = r, q.r_pad = (int)r_pad, q.ns = ns, q.scale = scale, q.beta = beta;
   const int64_t blocks = (int64_t)ns * (p.ncg[0] + p.ncg[1]);
   const int64_t nout = (int64_t)(d_in + d_out) * r + (dbias ? d_out : 0);
-  if (dtype == SOW_BF16) {
+  if (dtype == SOW_BF16)
     hipLaunchKernelGGL(tnw_partial_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, stream, p);
-    hipLaunchKernelGGL(tnw_reduce_kernel<bf16_t>, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, stream, q);
-  } else {
+  else
     hipLaunchKernelGGL(tnw_partial_kernel<f16_t>, dim3((unsigned)blocks), dim3(256), 0, stream, p);
-    hipLaunchKernelGGL(tnw_reduce_kernel<f16_t>, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, stream, q);
-  }
+  // the reduction reads fp32 partials only: its template type is the type of the gradients it writes
+  const dim3 rgrid((unsigned)((nout + 255) / 256));
+  if (out_dtype == SOW_F32)
+    hipLaunchKernelGGL(tnw_reduce_kernel<float>, rgrid, dim3(256), 0, stream, q);
+  else if (dtype == SOW_BF16)
+    hipLaunchKernelGGL(tnw_reduce_kernel<bf16_t>, rgrid, dim3(256), 0, stream, q);
+  else
+    hipLaunchKernelGGL(tnw_reduce_kernel<f16_t>, rgrid, dim3(256), 0, stream, q);
   SOW_CHECK_LAUNCH();
   return SOW_OK;
 }

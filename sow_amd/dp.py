@@ -46,6 +46,11 @@ def _block_key(name: str) -> str:
     return ".".join(parts[:-1])
 
 
+def _mixed(x2, B) -> bool:
+    """fp32 factors with bf16 / f16 activations: a layer under torch.autocast (SOW_PARAM_F32, fp32 gradients)."""
+    return B.dtype == torch.float32 and x2.dtype != torch.float32
+
+
 class _GradSink:
     """Per-layer hook used by SoWLinear's autograd backward after FactorBucket.attach(): runs the data gradient right away
     (dX is what the previous layer's backward waits for) and queues the layer's weight gradients with its decoder block.
@@ -80,7 +85,7 @@ class _GradSink:
         r, d_out = B.shape
         kind = ops.acc_kind(acc_down, acc_up)
         r_acc = acc_down.shape[1] if kind == _lib.ACC_LOWRANK else 0
-        need = ops.workspace_bytes(T, d_in, d_out, r, r_acc, kind, x2.dtype) + 256
+        need = ops.workspace_bytes(T, d_in, d_out, r, r_acc, kind, x2.dtype, param_f32=_mixed(x2, B)) + 256
         if self.ws is None or self.ws.numel() < need or self.ws.device != x2.device:
             self.ws = torch.empty(need, dtype=torch.uint8, device=x2.device)
         return kind, r_acc
@@ -97,7 +102,7 @@ class _GradSink:
         out = (self.pA.grad, self.pB.grad, None)
         dy2 = dy2.contiguous()
         dx, _, _, _ = ops.sow_backward(dy2, x2, h, A, B, acc_down, acc_up, scale, False, out=out, grad_beta=1.0,
-                                       phases=_lib.BWD_DATA, workspace=self.ws)
+                                       phases=_lib.BWD_DATA, workspace=self.ws, param_f32=_mixed(x2, B))
         self.queue(dy2, x2, h, A, B, acc_down, acc_up, scale, kind, r_acc)
         return dx
 
@@ -242,13 +247,22 @@ class FactorBucket:
         if not blk or not blk["queue"]:
             return
         q, blk["queue"] = blk["queue"], []
-        # layers of one dtype / device go together (a model holds one of each; anything else flushes in runs)
+        # layers of one dtype / device go together (a model holds one of each; anything else flushes in runs); the
+        # parameter dtype is part of the key: fp32 factors under autocast take the SOW_PARAM_F32 form (fp32 gradients)
+        def key(e):
+            return e[1][1].dtype, e[1][4].dtype, e[1][1].device
+
         while q:
-            dt, dev = q[0][1][1].dtype, q[0][1][1].device
-            run = [e for e in q if e[1][1].dtype == dt and e[1][1].device == dev]
-            q = [e for e in q if not (e[1][1].dtype == dt and e[1][1].device == dev)]
+            k0 = key(q[0])
+            run = [e for e in q if key(e) == k0]
+            q = [e for e in q if key(e) != k0]
+            dev = k0[2]
             arr = (_lib.LayerArgs * len(run))()
-            stable = []
+            x0, B0 = run[0][1][1], run[0][1][4]
+            # the run dtype of a bucket is not fixed by its parameters: an fp32 bucket runs as F32 outside autocast and as
+            # BF16 / F16 | PARAM_F32 under autocast, and the reduction descriptors (workspace offsets, slab counts) depend on it
+            dt = ops._dt(x0) | (_lib.PARAM_F32 if _mixed(x0, B0) else 0)
+            stable = [dt]
             for i, (sink, (dy2, x2, h, A, B, acc_down, acc_up, scale, kind, r_acc)) in enumerate(run):
                 T, d_in = x2.shape
                 r, d_out = B.shape
@@ -261,8 +275,8 @@ class FactorBucket:
                 a.T, a.d_in, a.d_out, a.r_live, a.r_acc, a.acc_kind = T, d_in, d_out, r, r_acc, kind
                 a.scale, a.grad_beta = scale, 1.0
                 a.workspace, a.workspace_bytes = sink.ws.data_ptr(), sink.ws.numel()
-                stable.append((a.dA, a.dB, a.workspace, T, d_in, d_out, r, r_acc, kind))
-            group = ops.LayerGroup.from_args(arr, len(run), ops._dt(run[0][1][1]), dev, keep=run)
+                stable.append((a.dA, a.dB, a.workspace, a.workspace_bytes, T, d_in, d_out, r, r_acc, kind))
+            group = ops.LayerGroup.from_args(arr, len(run), dt, dev, keep=run)
             phases = _lib.BWD_WEIGHTS_PARTIAL | _lib.BWD_GROUP_SLABS
             group.backward(phases)
             self._reducer.add_group(group, phases, stable_key=tuple(stable))

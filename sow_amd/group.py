@@ -18,21 +18,25 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from .layer import SoWLinear
+from .layer import SoWLinear, autocast_compute_dtype, autocast_input
 
 DEFAULT_GROUPS = (("q_proj", "k_proj", "v_proj"), ("gate_proj", "up_proj"),        # Llama (simple_train.py / finetune.py targets)
                   ("query", "key", "value"))                                       # RoBERTa self-attention (run_glue.py:572)
 
 
 class _SoWGroupFunction(torch.autograd.Function):
-    """y_i = SoWLinear_i(x) for n layers on one input.  Tensor arguments per layer: A, B, acc_down, acc_up, bias."""
+    """y_i = SoWLinear_i(x) for n layers on one input.  Tensor arguments per layer: A, B, acc_down, acc_up, bias.  cdt: the
+    compute dtype of fp32 layers under torch.autocast (SOW_PARAM_F32), or None."""
 
     @staticmethod
-    def forward(ctx, x, scales, sinks, *tensors):
+    def forward(ctx, x, scales, sinks, cdt, *tensors):
         n = len(scales)
         ctx.sinks = sinks
         lead = x.shape[:-1]
         x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        mixed = cdt is not None
+        if mixed:
+            x2 = autocast_input(x2, cdt)     # an fp32 input is cast once for the whole group
         per = [tensors[5 * i:5 * i + 5] for i in range(n)]
         need_bwd = any(ctx.needs_input_grad)
         calls = []
@@ -41,11 +45,11 @@ class _SoWGroupFunction(torch.autograd.Function):
             calls.append(ops.LayerCall(x2, A.contiguous(), B.contiguous(),
                                        acc_down=acc_down.contiguous() if kind != _lib.ACC_NONE else None,
                                        acc_up=acc_up.contiguous() if kind == _lib.ACC_LOWRANK else None,
-                                       bias=bias, scale=s, forward_only=True, save_h=need_bwd))
+                                       bias=bias, scale=s, forward_only=True, save_h=need_bwd, param_f32=mixed))
         ops.LayerGroup(calls).forward()
         if need_bwd:
             ctx.save_for_backward(x2, *[c.h for c in calls], *tensors)
-        ctx.scales, ctx.n, ctx.x_shape = scales, n, x.shape
+        ctx.scales, ctx.n, ctx.x_shape, ctx.x_dtype, ctx.mixed = scales, n, x.shape, x.dtype, mixed
         return tuple(c.y.reshape(*lead, c.y.shape[1]) for c in calls)
 
     @staticmethod
@@ -68,15 +72,12 @@ class _SoWGroupFunction(torch.autograd.Function):
                 calls.append(ops.LayerCall(x2, A, B, acc_down=acc_down if kind != _lib.ACC_NONE else None,
                                            acc_up=acc_up if kind == _lib.ACC_LOWRANK else None, scale=ctx.scales[i], h=hs[i],
                                            dy2=dy2, dx=torch.empty_like(x2), out=(sink.pA.grad, sink.pB.grad, None),
-                                           grad_beta=1.0, y=dy2, workspace=sink.ws))
+                                           grad_beta=1.0, y=dy2, workspace=sink.ws, param_f32=ctx.mixed))
                 recs.append((sink, dy2, A, B, acc_down, acc_up, kind, r_acc))
             ops.LayerGroup(calls).backward(_lib.BWD_DATA)
             for i, (sink, dy2, A, B, acc_down, acc_up, kind, r_acc) in enumerate(recs):
                 sink.queue(dy2, x2, hs[i], A, B, acc_down, acc_up, ctx.scales[i], kind, r_acc)
-            dx = calls[-1].dx
-            for c in reversed(calls[:-1]):
-                dx = dx + c.dx
-            return (dx.reshape(ctx.x_shape), None, None, *([None] * (5 * n)))
+            return (_SoWGroupFunction._input_grad(ctx, calls), None, None, None, *([None] * (5 * n)))
         calls, outs = [], []
         for i in range(n):
             A, B, acc_down, acc_up, bias = tensors[5 * i:5 * i + 5]
@@ -91,18 +92,24 @@ class _SoWGroupFunction(torch.autograd.Function):
                                        acc_down=acc_down.contiguous() if kind != _lib.ACC_NONE else None,
                                        acc_up=acc_up.contiguous() if kind == _lib.ACC_LOWRANK else None,
                                        bias=bias, scale=ctx.scales[i], h=hs[i], dy2=dy2, dx=torch.empty_like(x2), out=out,
-                                       grad_beta=0.0, y=dy2))   # y is not written by backward: any valid buffer
+                                       grad_beta=0.0, y=dy2, param_f32=ctx.mixed))   # y is not written by backward: any valid buffer
         ops.LayerGroup(calls).backward(_lib.BWD_DATA | _lib.BWD_WEIGHTS)
-        # the siblings share x: its gradient is the sum of theirs.  Summed last sibling first -- the order in which autograd
-        # accumulates the contributions of separately called layers (nodes run in reverse creation order), so the rounding
-        # matches the ungrouped model as closely as it can
-        dx = calls[-1].dx
-        for c in reversed(calls[:-1]):
-            dx = dx + c.dx
         grads: List[Optional[torch.Tensor]] = []
         for (dA, dB, dbias) in outs:
             grads += [dA, dB, None, None, dbias]
-        return (dx.reshape(ctx.x_shape), None, None, *grads)
+        return (_SoWGroupFunction._input_grad(ctx, calls), None, None, None, *grads)
+
+    @staticmethod
+    def _input_grad(ctx, calls):
+        """The siblings share x: its gradient is the sum of theirs.  Summed last sibling first -- the order in which autograd
+        accumulates the contributions of separately called layers (nodes run in reverse creation order), so the rounding
+        matches the ungrouped model as closely as it can.  An fp32 input under autocast gets each sibling's gradient cast to
+        fp32 first, as the ungrouped layers return it."""
+        dxs = [c.dx if c.dx.dtype == ctx.x_dtype else ops.cast(c.dx, ctx.x_dtype) for c in calls]
+        dx = dxs[-1]
+        for d in reversed(dxs[:-1]):
+            dx = dx + d
+        return dx.reshape(ctx.x_shape)
 
 
 class SiblingGroup:
@@ -114,32 +121,43 @@ class SiblingGroup:
         self._x = None                 # keeps the input alive while outputs are parked (no id() reuse)
         self._parked: dict = {}
 
-    def usable(self, x: torch.Tensor) -> bool:
+    def usable(self, x: torch.Tensor, cdt: Optional[torch.dtype] = None) -> bool:
+        """cdt: the compute dtype of fp32 layers under torch.autocast (SoWLinear's autocast_compute_dtype), or None."""
         if not x.is_cuda or x.dtype not in ops._DT:
             return False
         sinks = [getattr(m, "_grad_sink", None) for m in self.layers]
         if any(s is not None for s in sinks) and not all(s is not None for s in sinks):
             return False           # some siblings attached to a FactorBucket, some not: every layer runs on its own
+        if cdt is not None and x.dtype not in (torch.float32, cdt):
+            return False
+        pdt = torch.float32 if cdt is not None else x.dtype
         for m in self.layers:
-            if m.n_iter != 1 or m.downscale_weights[0].dtype != x.dtype:
+            if m.n_iter != 1 or m.downscale_weights[0].dtype != pdt or m.upscale_weights[0].dtype != pdt or (
+                    m.bias is not None and m.bias.dtype != pdt):
                 return False
             # an accumulator the grouped launch cannot take as it stands (dtype / shape / device of a checkpoint that was
             # loaded in another precision, load_sow): the layer runs on its own and raises exactly what the ungrouped
             # call raises
             try:
-                ops.check_accumulator(x, m.in_features, m.out_features, m.acc_downweight, m.acc_upweight)
+                ops.check_accumulator(x, m.in_features, m.out_features, m.acc_downweight, m.acc_upweight,
+                                      param_dtype=pdt if cdt is not None else None)
             except (TypeError, ValueError, RuntimeError):
                 return False
         return True
 
     def forward(self, layer: SoWLinear, x: torch.Tensor) -> Optional[torch.Tensor]:
-        key = (id(x), x._version, x.data_ptr(), tuple(x.shape), torch.is_grad_enabled())
+        key = (id(x), x._version, x.data_ptr(), tuple(x.shape), torch.is_grad_enabled(), torch.is_autocast_enabled("cuda"),
+               torch.get_autocast_dtype("cuda"))
         if self._key == key and id(layer) in self._parked:
             y = self._parked.pop(id(layer))
             if not self._parked:
                 self._key = self._x = None
             return y
-        if not self.usable(x):
+        try:
+            cdt = autocast_compute_dtype(layer.downscale_weights[0].dtype)
+        except TypeError:
+            return None            # the layer raises on its own
+        if not self.usable(x, cdt):
             return None
         tensors = []
         for m in self.layers:
@@ -147,7 +165,7 @@ class SiblingGroup:
                         m.acc_upweight, m.bias]
         sinks = tuple(getattr(m, "_grad_sink", None) for m in self.layers)
         ys = _SoWGroupFunction.apply(x, tuple(float(m.scale) for m in self.layers), sinks if sinks[0] is not None else None,
-                                     *tensors)
+                                     cdt, *tensors)
         self._key, self._x = key, x
         self._parked = {id(m): y for m, y in zip(self.layers, ys) if m is not layer}
         return ys[self.layers.index(layer)]

@@ -8,7 +8,7 @@ nn.Parameters (AdamW, DDP, save_pretrained, gradient checkpointing keep working)
 """
 from __future__ import annotations
 
-from typing import List
+from typing import List, Optional
 
 import torch
 import torch.nn as nn
@@ -35,26 +35,60 @@ class SoWParameter(nn.ParameterList):
         return f"{self.n_iter} x ({self.in_features}, {self.out_features})"
 
 
+_HALF = (torch.bfloat16, torch.float16)
+
+
+def autocast_compute_dtype(param_dtype: torch.dtype) -> Optional[torch.dtype]:
+    """The compute dtype of a SoW call with parameters of `param_dtype` under torch.autocast("cuda"): bf16 / f16 for fp32
+    parameters (fp32 master factors, the mixed-precision path: include/sow_amd.h SOW_PARAM_F32), None outside autocast or
+    when the parameters are already of the autocast dtype (the plain path).  Other combinations raise TypeError."""
+    if not torch.is_autocast_enabled("cuda"):
+        return None
+    ad = torch.get_autocast_dtype("cuda")
+    if ad not in _HALF:
+        raise TypeError(f"SoWLinear under torch.autocast: autocast dtype {ad} is not supported (bfloat16 or float16)")
+    if param_dtype == ad:
+        return None
+    if param_dtype != torch.float32:
+        raise TypeError(f"SoWLinear under torch.autocast({ad}): {param_dtype} parameters are not supported (float32 master "
+                        f"parameters, or parameters already in {ad})")
+    return ad
+
+
+def autocast_input(x2: torch.Tensor, cdt: torch.dtype) -> torch.Tensor:
+    """The input of a mixed-precision call in the compute dtype: fp32 is cast by the library (sow_cast_copy), as autocast
+    casts the input of F.linear."""
+    if x2.dtype == cdt:
+        return x2
+    if x2.dtype != torch.float32:
+        raise TypeError(f"SoWLinear under torch.autocast({cdt}): input of dtype {x2.dtype} (float32 or {cdt})")
+    return ops.cast(x2, cdt)
+
+
 class _SoWFunction(torch.autograd.Function):
-    """y = acc_term + scale * (x @ A) @ B + bias through sow_forward / sow_backward (include/sow_amd.h)."""
+    """y = acc_term + scale * (x @ A) @ B + bias through sow_forward / sow_backward (include/sow_amd.h).  cdt: the compute
+    dtype of a mixed-precision call (fp32 parameters, SOW_PARAM_F32) or None."""
 
     @staticmethod
-    def forward(ctx, x, A, B, acc_down, acc_up, bias, scale, sink=None):
+    def forward(ctx, x, A, B, acc_down, acc_up, bias, scale, sink=None, cdt=None):
         lead = x.shape[:-1]
         # the kernels take dense row-major buffers: a strided view (x = big[..., :d], seq[:, 0, :], W.t()) is packed ONCE
         # here so that forward and backward read the same rows (backward passes raw pointers of the saved tensors)
         x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        if cdt is not None:
+            x2 = autocast_input(x2, cdt)
         A, B = A.contiguous(), B.contiguous()
         if acc_down is not None and acc_down.numel():
             acc_down = acc_down.contiguous()
         if acc_up is not None and acc_up.numel():
             acc_up = acc_up.contiguous()
-        y, h = ops.sow_forward(x2, A, B, acc_down, acc_up, bias, scale)
+        y, h = ops.sow_forward(x2, A, B, acc_down, acc_up, bias, scale, param_f32=cdt is not None)
         ctx.save_for_backward(x2, h, A, B, acc_down, acc_up)
         ctx.scale = scale
         ctx.has_bias = bias is not None
-        ctx.x_shape = x.shape
+        ctx.x_shape, ctx.x_dtype = x.shape, x.dtype
         ctx.sink = sink
+        ctx.mixed = cdt is not None
         return y.reshape(*lead, B.shape[1])
 
     @staticmethod
@@ -67,9 +101,13 @@ class _SoWFunction(torch.autograd.Function):
             # view of it), so autograd gets None for A and B; their slab-partial sums are reduced for all layers in one
             # launch by FactorBucket.finalize() (sow_reduce_batch).
             dx = sink.backward(dy2, x2, h, A, B, acc_down, acc_up, ctx.scale)
-            return dx.reshape(ctx.x_shape), None, None, None, None, None, None, None
-        dx, dA, dB, dbias = ops.sow_backward(dy2, x2, h, A, B, acc_down, acc_up, ctx.scale, ctx.has_bias)
-        return dx.reshape(ctx.x_shape), dA, dB, None, None, dbias, None, None
+            dA = dB = dbias = None
+        else:
+            dx, dA, dB, dbias = ops.sow_backward(dy2, x2, h, A, B, acc_down, acc_up, ctx.scale, ctx.has_bias,
+                                                 param_f32=ctx.mixed)
+        if dx.dtype != ctx.x_dtype:
+            dx = ops.cast(dx, ctx.x_dtype)      # fp32 input under autocast: its gradient, cast back by the library
+        return dx.reshape(ctx.x_shape), dA, dB, None, None, dbias, None, None, None
 
 
 class SoWLinear(nn.Module):
@@ -141,15 +179,20 @@ class SoWLinear(nn.Module):
             if y is not None:
                 return y
         A, B = self._cat_factors()
+        # torch.autocast with fp32 factors: bf16 / f16 kernels on factors rounded once by the library, fp32 gradients
+        cdt = autocast_compute_dtype(A.dtype)
         if not (torch.is_grad_enabled() and (x.requires_grad or A.requires_grad or B.requires_grad
                                              or (self.bias is not None and self.bias.requires_grad))):
             # no backward will follow (eval / generate, commonsense_evaluate.py:268-287; the first pass of activation
             # checkpointing): the projection h = scale * x A is not written to HBM
             x2 = x.reshape(-1, x.shape[-1])
-            y, _ = ops.sow_forward(x2, A, B, self.acc_downweight, self.acc_upweight, self.bias, float(self.scale), save_h=False)
+            if cdt is not None:
+                x2 = autocast_input(x2.contiguous(), cdt)
+            y, _ = ops.sow_forward(x2, A, B, self.acc_downweight, self.acc_upweight, self.bias, float(self.scale), save_h=False,
+                                   param_f32=cdt is not None)
             return y.reshape(*x.shape[:-1], B.shape[1])
         return _SoWFunction.apply(x, A, B, self.acc_downweight, self.acc_upweight, self.bias, float(self.scale),
-                                  getattr(self, "_grad_sink", None))
+                                  getattr(self, "_grad_sink", None), cdt)
 
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()

@@ -23,6 +23,17 @@ def _dt(t: torch.Tensor) -> int:
         raise TypeError(f"sow_amd supports float32, bfloat16 and float16 tensors, got {t.dtype}") from None
 
 
+def _call_dtype(x2: torch.Tensor, param_f32: bool, who: str = "sow_amd") -> Tuple[int, torch.dtype]:
+    """(C-ABI dtype code, parameter dtype) of a layer call on activations x2.  param_f32: the parameters (factors, bias,
+    accumulator) are fp32 and x2 is of the compute dtype, bf16 or f16 (SOW_PARAM_F32: mixed precision, torch.autocast)."""
+    dt = _dt(x2)
+    if not param_f32:
+        return dt, x2.dtype
+    if dt == _lib.F32:
+        raise TypeError(f"{who}: fp32 parameters need bfloat16 or float16 activations, got {x2.dtype}")
+    return dt | _lib.PARAM_F32, torch.float32
+
+
 def _need_gpu(*ts: Optional[torch.Tensor]) -> torch.device:
     dev = None
     for t in ts:
@@ -102,18 +113,22 @@ def acc_kind(acc_down: Optional[torch.Tensor], acc_up: Optional[torch.Tensor]) -
     return _lib.ACC_LOWRANK
 
 
-def check_accumulator(x2: torch.Tensor, d_in: int, d_out: int, acc_down, acc_up, who: str = "sow_amd") -> Tuple[int, int]:
+def check_accumulator(x2: torch.Tensor, d_in: int, d_out: int, acc_down, acc_up, who: str = "sow_amd",
+                      param_dtype: Optional[torch.dtype] = None) -> Tuple[int, int]:
     """(acc_kind, r_acc) after the checks every entry point applies before raw pointers reach the kernels: the
     accumulator has the input's dtype (TypeError), the shapes of its kind (ValueError), lives on the input's device and is
     dense row-major.  A mismatch that got through would be read as the wrong type -- silent garbage for an fp32
-    accumulator under bf16 inputs, an out-of-bounds device read the other way round."""
+    accumulator under bf16 inputs, an out-of-bounds device read the other way round.  `param_dtype`: the parameter dtype
+    of the call when it is not the input's (fp32 under SOW_PARAM_F32)."""
     kind = acc_kind(acc_down, acc_up)
     if kind == _lib.ACC_NONE:
         return kind, 0
     r_acc = 0
-    if acc_down.dtype != x2.dtype or (kind == _lib.ACC_LOWRANK and acc_up.dtype != x2.dtype):
-        bad = acc_down.dtype if acc_down.dtype != x2.dtype else acc_up.dtype
-        raise TypeError(f"{who}: dtype mismatch, x is {x2.dtype} but the accumulator is {bad}")
+    want = x2.dtype if param_dtype is None else param_dtype
+    if acc_down.dtype != want or (kind == _lib.ACC_LOWRANK and acc_up.dtype != want):
+        bad = acc_down.dtype if acc_down.dtype != want else acc_up.dtype
+        raise TypeError(f"{who}: dtype mismatch, x is {x2.dtype} but the accumulator is {bad}"
+                        + ("" if param_dtype is None else f" (parameters must be {param_dtype})"))
     if kind == _lib.ACC_DENSE and tuple(acc_down.shape) != (d_in, d_out):
         raise ValueError(f"{who}: dense accumulator must be [in_features, out_features]")
     if kind == _lib.ACC_LOWRANK:
@@ -127,23 +142,26 @@ def check_accumulator(x2: torch.Tensor, d_in: int, d_out: int, acc_down, acc_up,
 
 
 def sow_forward(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, acc_up, bias, scale: float,
-                save_h: bool = True):
+                save_h: bool = True, *, param_f32: bool = False):
     """y, h_save = forward of the SoW contraction on a flattened [T, d_in] input.  save_h = False (no-grad / eval callers,
     e.g. the reload + generate loop of commonsense_evaluate.py:268-287): the projection is not written to HBM and None
     is returned in its place (every rank except r <= 64 with a dense accumulator, whose fused kernels write it as scratch;
-    a wide layer off the fused chain keeps its intermediate in the forward workspace)."""
+    a wide layer off the fused chain keeps its intermediate in the forward workspace).
+    param_f32: A, B, bias and the accumulator are fp32, x2 is bf16 / f16 (the compute dtype); the kernels round the
+    parameters once to x2's dtype (include/sow_amd.h: SOW_PARAM_F32) and y is of x2's dtype."""
     lib = _lib.load()
     dev = _need_gpu(x2, A, B, acc_down if acc_down is not None and acc_down.numel() else None,
                     acc_up if acc_up is not None and acc_up.numel() else None, bias)
-    dt = _dt(x2)
+    dt, pdt = _call_dtype(x2, param_f32)
     for name, t in (("A", A), ("B", B), ("bias", bias)):
-        if t is not None and t.dtype != x2.dtype:
-            raise TypeError(f"sow_amd: dtype mismatch, x is {x2.dtype} but {name} is {t.dtype}")
+        if t is not None and t.dtype != pdt:
+            raise TypeError(f"sow_amd: dtype mismatch, x is {x2.dtype} but {name} is {t.dtype}"
+                            + (" (parameters must be torch.float32)" if param_f32 else ""))
     T, d_in = x2.shape
     r, d_out = B.shape
     if A.shape != (d_in, r):
         raise ValueError(f"sow_amd: A has shape {tuple(A.shape)}, expected {(d_in, r)}")
-    kind, r_acc = check_accumulator(x2, d_in, d_out, acc_down, acc_up)
+    kind, r_acc = check_accumulator(x2, d_in, d_out, acc_down, acc_up, param_dtype=pdt if param_f32 else None)
     x2 = x2.contiguous()
     A, B = A.contiguous(), B.contiguous()
     acc_down = acc_down.contiguous() if kind != _lib.ACC_NONE else None
@@ -163,23 +181,27 @@ def sow_forward(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, ac
     return y, (h if save_h else None)
 
 
-def workspace_bytes(T: int, d_in: int, d_out: int, r: int, r_acc: int, kind: int, dtype: torch.dtype) -> int:
-    return _workspace_bytes(_lib.load(), T, d_in, d_out, r, r_acc, kind, _DT[dtype])
+def workspace_bytes(T: int, d_in: int, d_out: int, r: int, r_acc: int, kind: int, dtype: torch.dtype,
+                    param_f32: bool = False) -> int:
+    return _workspace_bytes(_lib.load(), T, d_in, d_out, r, r_acc, kind, _DT[dtype] | (_lib.PARAM_F32 if param_f32 else 0))
 
 
 def sow_backward(dy2: torch.Tensor, x2: torch.Tensor, h: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down,
                  acc_up, scale: float, need_bias: bool,
                  out: Optional[Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]] = None,
                  grad_beta: float = 0.0, *, phases: int = _lib.BWD_DATA | _lib.BWD_WEIGHTS,
-                 dx: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+                 dx: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, param_f32: bool = False):
     """dx, dA, dB, dbias.  `out` = (dA, dB, dbias) buffers to write/accumulate into (grad_beta).
     `phases` selects the data-gradient and / or weight-gradient kernels (see include/sow_amd.h); a split
-    call must pass the same `workspace` (and `dx`) to both phases, each enqueued on the current stream."""
+    call must pass the same `workspace` (and `dx`) to both phases, each enqueued on the current stream.
+    param_f32: fp32 parameters with bf16 / f16 activations (sow_forward); dA, dB and dbias are then fp32, dx of x2's dtype."""
     lib = _lib.load()
     dev = _need_gpu(dy2, x2, h, A, B)
-    dt = _dt(x2)
+    dt, pdt = _call_dtype(x2, param_f32)
     if dy2.dtype != x2.dtype:
         raise TypeError(f"sow_amd: grad dtype {dy2.dtype} differs from input dtype {x2.dtype}")
+    if param_f32 and (A.dtype != pdt or B.dtype != pdt):
+        raise TypeError("sow_amd: param_f32 needs torch.float32 factors")
     T, d_in = x2.shape
     r, d_out = B.shape
     kind = acc_kind(acc_down, acc_up)
@@ -188,12 +210,14 @@ def sow_backward(dy2: torch.Tensor, x2: torch.Tensor, h: torch.Tensor, A: torch.
     if dx is None:
         dx = torch.empty((T, d_in), dtype=x2.dtype, device=dev)
     if out is None:
-        dA = torch.empty((d_in, r), dtype=x2.dtype, device=dev)
-        dB = torch.empty((r, d_out), dtype=x2.dtype, device=dev)
-        dbias = torch.empty((d_out,), dtype=x2.dtype, device=dev) if need_bias else None
+        dA = torch.empty((d_in, r), dtype=pdt, device=dev)
+        dB = torch.empty((r, d_out), dtype=pdt, device=dev)
+        dbias = torch.empty((d_out,), dtype=pdt, device=dev) if need_bias else None
         grad_beta = 0.0
     else:
         dA, dB, dbias = out
+        if any(g is not None and g.dtype != pdt for g in out):
+            raise TypeError(f"sow_amd: gradient buffers must be {pdt}")
     nws = _workspace_bytes(lib, T, d_in, d_out, r, r_acc, kind, dt)
     ws = _ws(nws, dev) if workspace is None else workspace
     if ws.numel() < nws:
@@ -211,18 +235,21 @@ class LayerCall:
     own workspace (workspace_bytes())."""
 
     def __init__(self, x2, A, B, *, acc_down=None, acc_up=None, bias=None, scale=1.0, y=None, h=None, dy2=None, dx=None,
-                 out=None, grad_beta=0.0, workspace=None, forward_only=False, save_h=True):
+                 out=None, grad_beta=0.0, workspace=None, forward_only=False, save_h=True, param_f32=False):
         dev = _need_gpu(x2, A, B, bias, y, h, dy2, dx, workspace)
-        self.dtype = _dt(x2)
+        # param_f32: fp32 A, B, bias, accumulator and gradients, activations of the compute dtype (SOW_PARAM_F32)
+        self.dtype, pdt = _call_dtype(x2, param_f32, "sow_amd.LayerCall")
         T, d_in = x2.shape
         r, d_out = B.shape
         # the same accumulator checks as the single-layer entry point (ops.sow_forward): same exceptions for the same input
-        kind, _ = check_accumulator(x2, d_in, d_out, acc_down, acc_up, "sow_amd.LayerCall")
-        for name, t in (("x", x2), ("A", A), ("B", B), ("bias", bias), ("y", y), ("dy", dy2), ("dx", dx),
-                        ("acc_down", acc_down if kind != _lib.ACC_NONE else None),
-                        ("acc_up", acc_up if kind == _lib.ACC_LOWRANK else None)):
-            if t is not None and (not t.is_contiguous() or t.dtype != x2.dtype):
-                raise ValueError(f"sow_amd.LayerCall: {name} must be contiguous and of the input dtype")
+        kind, _ = check_accumulator(x2, d_in, d_out, acc_down, acc_up, "sow_amd.LayerCall", param_dtype=pdt if param_f32 else None)
+        for name, t, want in (("x", x2, x2.dtype), ("A", A, pdt), ("B", B, pdt), ("bias", bias, pdt), ("y", y, x2.dtype),
+                              ("dy", dy2, x2.dtype), ("dx", dx, x2.dtype),
+                              ("acc_down", acc_down if kind != _lib.ACC_NONE else None, pdt),
+                              ("acc_up", acc_up if kind == _lib.ACC_LOWRANK else None, pdt)):
+            if t is not None and (not t.is_contiguous() or t.dtype != want):
+                raise ValueError(f"sow_amd.LayerCall: {name} must be contiguous and of the "
+                                 + ("input" if want == x2.dtype else "parameter") + " dtype")
         if A.shape != (d_in, r):
             raise ValueError("sow_amd.LayerCall: factor shapes do not match the input")
         self.device, self.kind = dev, kind
@@ -235,11 +262,17 @@ class LayerCall:
         r_acc = acc_down.shape[1] if kind == _lib.ACC_LOWRANK else 0
         # a forward-only call needs scratch for a few shapes only (sow_forward_workspace_bytes), often none at all
         nws = (_forward_workspace_bytes(_lib.load(), T, d_in, d_out, r, r_acc, kind, self.dtype) if forward_only
-               else workspace_bytes(T, d_in, d_out, r, r_acc, kind, x2.dtype))
+               else _workspace_bytes(_lib.load(), T, d_in, d_out, r, r_acc, kind, self.dtype))
         self.workspace = workspace if workspace is not None else (_ws(nws, dev) if nws else None)
         if self.workspace is not None and self.workspace.numel() < nws:
             raise ValueError("sow_amd.LayerCall: workspace too small")
         dA, dB, dbias = out if out is not None else (None, None, None)
+        # the kernels write gradients of the parameter dtype (fp32 under param_f32): a buffer of another dtype or shape
+        # would be written out of bounds
+        for name, g, shape in (("dA", dA, (d_in, r)), ("dB", dB, (r, d_out)), ("dbias", dbias, (d_out,))):
+            if g is not None and (not g.is_contiguous() or g.dtype != pdt or tuple(g.shape) != shape or g.device != dev):
+                raise ValueError(f"sow_amd.LayerCall: gradient buffer {name} must be a contiguous {pdt} tensor of shape "
+                                 f"{shape} on {dev}")
         self._keep = (x2, A, B, acc_down, acc_up, bias, dy2, dA, dB, dbias)     # the struct holds raw pointers
         self.args = _lib.LayerArgs(
             x=_ptr(x2), A=_ptr(A), B=_ptr(B), acc_down=_ptr(acc_down) if kind != _lib.ACC_NONE else None,
@@ -315,7 +348,7 @@ class DeferredReduce:
         self._total = 0
         self._pos = 0
 
-    def add(self, x2, B, out, grad_beta, workspace, acc_down=None, acc_up=None):
+    def add(self, x2, B, out, grad_beta, workspace, acc_down=None, acc_up=None, param_f32=False):
         """Register (or re-validate) the layer whose PARTIAL phase was just enqueued."""
         lib = _lib.load()
         dA, dB, dbias = out
@@ -323,7 +356,8 @@ class DeferredReduce:
         r, d_out = B.shape
         kind = acc_kind(acc_down, acc_up)
         r_acc = acc_down.shape[1] if kind == _lib.ACC_LOWRANK else 0
-        key = (_ptr(dA), _ptr(dB), _ptr(dbias), T, d_in, d_out, r, r_acc, kind, float(grad_beta), _dt(x2), _ptr(workspace))
+        dt = _call_dtype(x2, param_f32)[0]
+        key = (_ptr(dA), _ptr(dB), _ptr(dbias), T, d_in, d_out, r, r_acc, kind, float(grad_beta), dt, _ptr(workspace))
         i = self._pos
         self._pos += 1
         if i < len(self._keys) and self._keys[i] == key:
@@ -334,12 +368,12 @@ class DeferredReduce:
         buf = ctypes.create_string_buffer(lib.sow_reduce_desc_bytes())
         nb = ctypes.c_int(0)
         _lib.check(lib.sow_backward_reduce_desc(_ptr(dA), _ptr(dB), _ptr(dbias), T, d_in, d_out, r, r_acc, kind, float(grad_beta),
-                                                _dt(x2), _ptr(workspace), workspace.numel(), buf, ctypes.byref(nb)),
+                                                dt, _ptr(workspace), workspace.numel(), buf, ctypes.byref(nb)),
                    "sow_backward_reduce_desc")
         self._keys.append(key)
         self._descs.append(buf.raw)
         self._blocks.append(nb.value)
-        self._dev, self._dt = x2.device, _dt(x2)
+        self._dev, self._dt = x2.device, dt
 
     def add_group(self, group: "LayerGroup", phases: int, stable_key=None):
         """Register (or re-validate) every layer of a group whose PARTIAL phase was just enqueued with `phases`.
@@ -445,6 +479,23 @@ def qr_thin(W: torch.Tensor, k: int, need_r: bool = True, out_dtype: Optional[to
     _launch(dev, "sow_qr_thin", lib.sow_qr_thin, _ptr(W), W.stride(0), m, n, _dt(W), k, _ptr(Q), k, _ptr(R), n, _DT[out_dtype],
             _ptr(ws), ws.numel())
     return Q, R
+
+
+def cast(t: torch.Tensor, dtype: torch.dtype, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """t converted to `dtype` (float32 / bfloat16 / float16; RNE when narrowing) by sow_cast_copy: the fp32 input of a layer
+    under autocast and its gradient, without an ATen cast on the hot path.  `out`: a contiguous buffer of t's shape."""
+    lib = _lib.load()
+    dev = _need_gpu(t, out)
+    t = t.contiguous()
+    if out is None:
+        out = torch.empty(t.shape, dtype=dtype, device=dev)
+    elif out.shape != t.shape or out.dtype != dtype or not out.is_contiguous():
+        raise ValueError("sow_amd.cast: bad output tensor")
+    if t.numel():
+        cols = t.shape[-1] if t.dim() else 1
+        rows = t.numel() // cols
+        _launch(dev, "sow_cast_copy", lib.sow_cast_copy, _ptr(t), cols, _dt(t), _ptr(out), cols, _DT[dtype], rows, cols)
+    return out
 
 
 def zero_(tensors: Sequence[torch.Tensor]) -> None:
