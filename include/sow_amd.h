@@ -43,8 +43,9 @@ extern "C" {
 /* Parameters in fp32 (mixed precision, as under torch.autocast): OR-ed into SOW_DTYPE_BF16 or SOW_DTYPE_F16 (the compute
  * dtype).  Accepted by sow_workspace_bytes, sow_forward_workspace_bytes, sow_forward, sow_backward, sow_backward_ex,
  * sow_backward_reduce_desc, sow_reduce_batch, sow_forward_group, sow_backward_group, sow_backward_group_reduce_desc and
- * sow_backward_group_plan; every other entry point, and SOW_DTYPE_F32 | SOW_PARAM_F32 anywhere, returns SOW_ERR_DTYPE
- * (checked on the host before anything is launched or dereferenced).  With the flag:
+ * sow_backward_group_plan; sow_forward_shared and sow_backward_shared return SOW_ERR_UNSUPPORTED for it (nothing launched:
+ * the caller takes the grouped calls); every other entry point, and SOW_DTYPE_F32 | SOW_PARAM_F32 anywhere, returns
+ * SOW_ERR_DTYPE (checked on the host before anything is launched or dereferenced).  With the flag:
  *   - the activations are of the compute dtype: x, y, h_save, dy, dx (and the internal dh);
  *   - A, B, bias, acc_down and acc_up are read as fp32, each element rounded once, to nearest even, to the compute dtype
  *     before use (the cast autocast applies to every F.linear / matmul operand, bias included): one launch packs all of
@@ -80,7 +81,7 @@ const char* sow_error_string(int code);
  * never touches them.  They are the library's ONLY process-wide state: a table of atomics initialised from the
  * environment (SOW_AMD_<NAME>) once, at first use; no launch path calls getenv.  Names: FORCE_CHAIN_V1, NO_SHORT_SPLIT,
  * NO_FUSED_H, FORCE_GEMM_V1, TN_NARROW, NO_GEMM3S, NO_GROUPED, NO_PERSIST, NO_NT_STORE, NT_LOAD, NO_PAIR_FLUSH, F32_EXACT, NO_PARK16, TN_NO_NT_LOAD, NO_TN_ROWS, NO_GEMM4H, NO_CHAIN3F, NO_TN_F32Q, NO_SPLITK,
- * NO_WIDE_CHAIN
+ * NO_WIDE_CHAIN, NO_SHARED_X
  * (value 1 = on, -1 / 0 = off) and GEMM3S, GEMM3, GEMM4
  * (1 = force, 0 = forbid, -1 = automatic).  sow_set_switch returns SOW_ERR_UNSUPPORTED for an unknown name;
  * sow_get_switch returns the value (-1 / 0 / 1).  Changing a switch while other threads launch is safe (atomic) but
@@ -210,6 +211,20 @@ int sow_backward_group_reduce_desc(const sow_layer_args* layers, int n, int dtyp
  * group-planned slabs runs, 0 if every layer keeps its single-layer slab count (negative: error); slabs_out (2 n ints,
  * may be NULL) receives the token-slab counts of the x / dY operand of every layer. */
 int sow_backward_group_plan(const sow_layer_args* layers, int n, int dtype, int phases, int* slabs_out);
+
+/* Shared-input calls: n <= 4 SIBLING layers on ONE input (q / k / v, gate / up), fused into one launch per direction.
+ * The forward streams x once for all of them; the data gradient writes ONE dX for the set:
+ *   dX = grad_beta * dX + sum_i dh_i @ A_i^T,   dh_i = scale_i * dY_i @ B_i^T,
+ * summed in fp32 inside the kernel and rounded ONCE to the compute dtype (not the rounding of n separate dX added later).
+ * Every layers[i].x must be the same pointer (else SOW_ERR_SHAPE), with one T and one d_in; d_out and r_live may differ.
+ * layers[0].dx receives the sum with layers[0].grad_beta; every other dx must be NULL or equal to it (else SOW_ERR_SHAPE).
+ * y_i, h_save_i and the dh_i the weight phases read are bit-identical to sow_forward_group / sow_backward_group on the same
+ * inputs.  The weight phases in `phases` (BWD_WEIGHTS, _PARTIAL, _REDUCE, GROUP_SLABS) run exactly as sow_backward_group
+ * runs them.  Admitted: bf16 or f16 (no SOW_PARAM_F32), SOW_ACC_NONE, r_live <= 64, T > 8192, the alignment of the
+ * streaming kernels; anything else -- and everything while the NO_SHARED_X switch is on -- returns SOW_ERR_UNSUPPORTED,
+ * and then nothing has been launched (the caller runs sow_forward_group / sow_backward_group instead). */
+int sow_forward_shared(const sow_layer_args* layers, int n, int dtype, void* stream);
+int sow_backward_shared(const sow_layer_args* layers, int n, int dtype, int phases, void* stream);
 
 /* General row-major GEMM  C[M,N] = alpha * op(A) op(B) + beta * C + bias[N]  (bias may be NULL).
  * trans_a: A is stored [K,M]; trans_b: B is stored [N,K].  Replaces the plain `@` / einsum call

@@ -20,6 +20,8 @@ ACC_NONE, ACC_LOWRANK, ACC_DENSE = 0, 1, 2
 H_COLS = 64
 BWD_DATA, BWD_WEIGHTS, BWD_WEIGHTS_PARTIAL, BWD_WEIGHTS_REDUCE = 1, 2, 4, 8
 BWD_GROUP_SLABS = 16     # sow_backward_group: slab counts planned over the group (deferred reduction from group descriptors)
+ERR_SHAPE = -2
+ERR_UNSUPPORTED = -6      # include/sow_amd.h SOW_ERR_UNSUPPORTED: nothing was launched
 
 
 
@@ -74,6 +76,8 @@ SIGNATURES = {
                                     c_void_p, c_size_t, c_int, c_void_p]),
     "sow_forward_group": (c_int, [POINTER(LayerArgs), c_int, c_int, c_void_p]),
     "sow_backward_group": (c_int, [POINTER(LayerArgs), c_int, c_int, c_int, c_void_p]),
+    "sow_forward_shared": (c_int, [POINTER(LayerArgs), c_int, c_int, c_void_p]),
+    "sow_backward_shared": (c_int, [POINTER(LayerArgs), c_int, c_int, c_int, c_void_p]),
     "sow_backward_group_reduce_desc": (c_int, [POINTER(LayerArgs), c_int, c_int, c_int, c_void_p, POINTER(c_int)]),
     "sow_backward_group_plan": (c_int, [POINTER(LayerArgs), c_int, c_int, c_int, POINTER(c_int)]),
     "sow_accumulate_batch": (c_int, [POINTER(AccumulateArgs), c_int, c_int, c_void_p]),

@@ -53,7 +53,7 @@ namespace sow {
 static const char* const kSwitchNames[SW_COUNT] = {"FORCE_CHAIN_V1", "NO_SHORT_SPLIT", "NO_FUSED_H", "FORCE_GEMM_V1", "TN_NARROW",
                                                    "NO_GEMM3S",      "GEMM3S",         "GEMM3",      "NO_GROUPED",     "NO_PERSIST",     "NO_NT_STORE",    "NT_LOAD",        "NO_PAIR_FLUSH",  "F32_EXACT",
                                                    "NO_PARK16",      "TN_NO_NT_LOAD",  "NO_TN_ROWS",     "GEMM4",          "NO_GEMM4H",      "NO_CHAIN3F",     "NO_TN_F32Q",     "NO_SPLITK",
-                                                   "NO_WIDE_CHAIN"};
+                                                   "NO_WIDE_CHAIN",  "NO_SHARED_X"};
 static std::atomic<int> g_switch[SW_COUNT];
 static std::once_flag g_switch_once;
 static void switches_from_env() {
@@ -1046,6 +1046,65 @@ int sow_backward_group(const sow_layer_args* layers, int n, int dtype, int phase
   std::vector<sow_layer_args> packed;
   const int rc = pack_group(layers, n, cd, true, packed, stream);
   return rc ? rc : backward_group_impl(packed.data(), n, cd, SOW_F32, phases, stream);
+}
+
+// ---- shared-input entry points (chain2_shared.hip) -----------------------------------------------------------------
+// Sibling layers on one x: the forward reads x once, the data gradient writes ONE dX.  Admitted: a set that
+// group_chain_params takes layer by layer (bf16 / f16, no accumulator, r_live <= 64, T > 8192, chain2 alignment) with one x
+// pointer and one d_in; anything else returns SOW_ERR_UNSUPPORTED before anything is launched.
+static int shared_common(const sow_layer_args* layers, int n, bool bwd) {
+  if (n <= 0) return SOW_ERR_SHAPE;
+  if (!layers) return SOW_ERR_NULL;
+  for (int i = 0; i < n; ++i) {
+    const sow_layer_args& L = layers[i];
+    if (L.x != layers[0].x || L.T != layers[0].T || L.d_in != layers[0].d_in) return SOW_ERR_SHAPE;
+    if (bwd && L.dx && L.dx != layers[0].dx) return SOW_ERR_SHAPE;
+  }
+  return SOW_OK;
+}
+static void shared_fill_dx(const sow_layer_args* layers, int n, sow_layer_args* out) {
+  for (int i = 0; i < n; ++i) out[i] = layers[i], out[i].dx = layers[0].dx;   // check_layer wants every dx
+}
+
+int sow_forward_shared(const sow_layer_args* layers, int n, int dtype, void* stream) {
+  if (!ok_dtype(dtype & ~SOW_PARAM_F32)) return SOW_ERR_DTYPE;
+  int rc;
+  if ((rc = shared_common(layers, n, false))) return rc;
+  for (int i = 0; i < n; ++i)
+    if ((rc = check_layer(layers[i], false))) return rc;
+  if (sw_on(SW_NO_SHARED_X) || flagged(dtype) || n > C2_MAXG || layers[0].T == 0) return SOW_ERR_UNSUPPORTED;
+  ChainParams ps[C2_MAXG];
+  for (int i = 0; i < n; ++i)
+    if (!group_chain_params(layers[i], false, dtype, WsPlan{}, &ps[i])) return SOW_ERR_UNSUPPORTED;
+  return launch_chain2_shared(ps, n, false, dtype, (hipStream_t)stream);
+}
+
+int sow_backward_shared(const sow_layer_args* layers, int n, int dtype, int phases, void* stream) {
+  if (!ok_dtype(dtype & ~SOW_PARAM_F32)) return SOW_ERR_DTYPE;
+  int rc;
+  if ((rc = shared_common(layers, n, true))) return rc;
+  if (n > C2_MAXG) return SOW_ERR_UNSUPPORTED;
+  if (flagged(dtype)) return SOW_ERR_UNSUPPORTED;
+  sow_layer_args filled[C2_MAXG];
+  shared_fill_dx(layers, n, filled);
+  if (!(phases & SOW_BWD_DATA)) return sow_backward_group(filled, n, dtype, phases, stream);
+  for (int i = 0; i < n; ++i)
+    if ((rc = check_layer(filled[i], true))) return rc;
+  if (sw_on(SW_NO_SHARED_X) || filled[0].T == 0) return SOW_ERR_UNSUPPORTED;
+  ChainParams ps[C2_MAXG];
+  for (int i = 0; i < n; ++i) {
+    const sow_layer_args& L = filled[i];
+    const WsPlan w = plan_ws(L.T, L.d_in, L.d_out, L.r_live, 0, L.acc_kind, dtype);
+    if (!group_chain_params(L, true, dtype, w, &ps[i])) return SOW_ERR_UNSUPPORTED;
+    if (L.workspace_bytes < w.total + 255) return SOW_ERR_WORKSPACE;
+    ps[i].beta = filled[0].grad_beta;   // dX = grad_beta * dX + sum_i dh_i A_i^T
+  }
+  if ((rc = launch_chain2_shared(ps, n, true, dtype, (hipStream_t)stream))) return rc;
+  // the weight phases read each layer's dh where the grouped data phase leaves it: exactly sow_backward_group's code
+  const int wph = phases & ~SOW_BWD_DATA;
+  return (wph & (SOW_BWD_WEIGHTS | SOW_BWD_WEIGHTS_PARTIAL | SOW_BWD_WEIGHTS_REDUCE))
+             ? backward_group_impl(filled, n, dtype, dtype, wph, stream)
+             : SOW_OK;
 }
 
 int sow_backward_group_plan(const sow_layer_args* layers, int n, int dtype, int phases, int* slabs_out) {

@@ -176,6 +176,7 @@ enum Switch : int {
   SW_NO_TN_F32Q,          // fp32 weight gradients: the wide (two column groups, private S stream) kernel instead of the quad one
   SW_NO_SPLITK,           // bf16 GEMM with few output tiles (short T): never split K over workgroups
   SW_NO_WIDE_CHAIN,       // 64 < r <= 256: the generic GEMM composition instead of chain_wide / skinny_tn_wide
+  SW_NO_SHARED_X,         // sow_forward_shared / sow_backward_shared return SOW_ERR_UNSUPPORTED (callers take the grouped path)
   SW_COUNT
 };
 int sw(int which);

@@ -49,6 +49,10 @@ bool chain2_supported(const ChainParams& p, int dtype);
 int launch_chain2(const ChainParams& p, bool bwd, int dtype, hipStream_t stream);
 // one grid for n <= C2_MAXG independent layers of the same direction (each one chain2_supported)
 int launch_chain2_group(const ChainParams* ps, int n, bool bwd, int dtype, hipStream_t stream);
+// chain2_shared.hip: n <= C2_MAXG sibling layers on ONE input in one grid (forward: one X; backward: one summed dX);
+// SOW_ERR_UNSUPPORTED (nothing launched) unless chain2_shared_supported
+bool chain2_shared_supported(const ChainParams* ps, int n, bool bwd, int dtype);
+int launch_chain2_shared(const ChainParams* ps, int n, bool bwd, int dtype, hipStream_t stream);
 int launch_h_reduce(const float* Hpartial, int nsplit, void* Hsave, int64_t M, int rb, float scale, int dtype,
                     hipStream_t stream);
 // chain2f.hip (fp32 streaming version)

@@ -9,6 +9,15 @@ parks the other outputs; the other siblings, called with the same tensor, pick t
 workgroups unchanged, so outputs and weight gradients for given inputs are bit-identical to the ungrouped calls; only the
 SUM of the siblings' input gradients may round differently from autograd's own accumulation.  A sibling called with a
 different input, or a group that the batched path does not cover, simply runs on its own.
+
+`group_siblings(model, shared_input=True)` goes one step further where the kernels admit the set (bf16 / f16 parameters, no
+accumulator, rank <= 64, more than 8192 tokens): the backward returns ONE input gradient, summed over the siblings in fp32
+inside the kernel and rounded once (sow_backward_shared) -- no separate per-sibling input gradients and no adds (q + k + v of
+llama_60m: 78.3 -> 43.9 us per backward data pass).  Outputs and weight gradients stay bit-identical
+to the grouped path; the input gradient rounds differently (once instead of per sibling and per add).  The forward keeps
+the grouped launch: the shared-input forward (sow_forward_shared, ops.SharedInputGroup) moves fewer bytes but measures
+no faster on the llama_60m shapes (q + k + v 43.2 against 42.4 us).  A set the fused kernels do not admit runs the grouped
+path unchanged.
 """
 from __future__ import annotations
 
@@ -26,10 +35,11 @@ DEFAULT_GROUPS = (("q_proj", "k_proj", "v_proj"), ("gate_proj", "up_proj"),     
 
 class _SoWGroupFunction(torch.autograd.Function):
     """y_i = SoWLinear_i(x) for n layers on one input.  Tensor arguments per layer: A, B, acc_down, acc_up, bias.  cdt: the
-    compute dtype of fp32 layers under torch.autocast (SOW_PARAM_F32), or None."""
+    compute dtype of fp32 layers under torch.autocast (SOW_PARAM_F32), or None.  shared: try the shared-input data
+    gradient first (group_siblings(shared_input=True))."""
 
     @staticmethod
-    def forward(ctx, x, scales, sinks, cdt, *tensors):
+    def forward(ctx, x, scales, sinks, cdt, shared, *tensors):
         n = len(scales)
         ctx.sinks = sinks
         lead = x.shape[:-1]
@@ -46,7 +56,8 @@ class _SoWGroupFunction(torch.autograd.Function):
                                        acc_down=acc_down.contiguous() if kind != _lib.ACC_NONE else None,
                                        acc_up=acc_up.contiguous() if kind == _lib.ACC_LOWRANK else None,
                                        bias=bias, scale=s, forward_only=True, save_h=need_bwd, param_f32=mixed))
-        ops.LayerGroup(calls).forward()
+        ops.LayerGroup(calls).forward()   # (the shared-input forward does not pay on these shapes: module docstring)
+        ctx.shared = shared
         if need_bwd:
             ctx.save_for_backward(x2, *[c.h for c in calls], *tensors)
         ctx.scales, ctx.n, ctx.x_shape, ctx.x_dtype, ctx.mixed = scales, n, x.shape, x.dtype, mixed
@@ -62,42 +73,79 @@ class _SoWGroupFunction(torch.autograd.Function):
                 s.usable(tensors[5 * i], tensors[5 * i + 1]) and tensors[5 * i + 4] is None for i, s in enumerate(sinks)):
             # FactorBucket.attach(): ONE data-gradient launch for the siblings, weight gradients queued with their decoder
             # block (dp._GradSink); autograd gets None for the factors
-            calls, recs = [], []
+            recs = []
             for i, sink in enumerate(sinks):
                 A, B, acc_down, acc_up, _ = tensors[5 * i:5 * i + 5]
                 kind, r_acc = sink.prepare(x2, B, acc_down, acc_up)
                 T, d_out = x2.shape[0], B.shape[1]
                 dy = dys[i]
                 dy2 = (torch.zeros(T, d_out, dtype=x2.dtype, device=x2.device) if dy is None else dy.reshape(-1, d_out).contiguous())
-                calls.append(ops.LayerCall(x2, A, B, acc_down=acc_down if kind != _lib.ACC_NONE else None,
-                                           acc_up=acc_up if kind == _lib.ACC_LOWRANK else None, scale=ctx.scales[i], h=hs[i],
-                                           dy2=dy2, dx=torch.empty_like(x2), out=(sink.pA.grad, sink.pB.grad, None),
-                                           grad_beta=1.0, y=dy2, workspace=sink.ws, param_f32=ctx.mixed))
                 recs.append((sink, dy2, A, B, acc_down, acc_up, kind, r_acc))
-            ops.LayerGroup(calls).backward(_lib.BWD_DATA)
+
+            def data_calls(dxs, grad_beta):
+                return [ops.LayerCall(x2, A, B, acc_down=acc_down if kind != _lib.ACC_NONE else None,
+                                      acc_up=acc_up if kind == _lib.ACC_LOWRANK else None, scale=ctx.scales[i], h=hs[i],
+                                      dy2=dy2, dx=dxs[i], out=(sink.pA.grad, sink.pB.grad, None), grad_beta=grad_beta, y=dy2,
+                                      workspace=sink.ws, param_f32=ctx.mixed)
+                        for i, (sink, dy2, A, B, acc_down, acc_up, kind, r_acc) in enumerate(recs)]
+
+            # the DATA phase writes no weight gradient: grad_beta = 0 of the shared call only means dX is overwritten
+            dx = _SoWGroupFunction._shared_data(ctx, x2, data_calls, n)
+            if dx is None:
+                calls = data_calls([torch.empty_like(x2) for _ in range(n)], 1.0)
+                ops.LayerGroup(calls).backward(_lib.BWD_DATA)
+                dx = _SoWGroupFunction._input_grad(ctx, calls)
             for i, (sink, dy2, A, B, acc_down, acc_up, kind, r_acc) in enumerate(recs):
                 sink.queue(dy2, x2, hs[i], A, B, acc_down, acc_up, ctx.scales[i], kind, r_acc)
-            return (_SoWGroupFunction._input_grad(ctx, calls), None, None, None, *([None] * (5 * n)))
-        calls, outs = [], []
+            return (dx, None, None, None, None, *([None] * (5 * n)))
+        outs, dy2s = [], []
         for i in range(n):
             A, B, acc_down, acc_up, bias = tensors[5 * i:5 * i + 5]
-            kind = ops.acc_kind(acc_down, acc_up)
             T, d_out = x2.shape[0], B.shape[1]
             dy = dys[i]
-            dy2 = (torch.zeros(T, d_out, dtype=x2.dtype, device=x2.device) if dy is None
-                   else dy.reshape(-1, d_out).contiguous())
-            out = (torch.empty_like(A), torch.empty_like(B), torch.empty_like(bias) if bias is not None else None)
-            outs.append(out)
-            calls.append(ops.LayerCall(x2, A.contiguous(), B.contiguous(),
-                                       acc_down=acc_down.contiguous() if kind != _lib.ACC_NONE else None,
-                                       acc_up=acc_up.contiguous() if kind == _lib.ACC_LOWRANK else None,
-                                       bias=bias, scale=ctx.scales[i], h=hs[i], dy2=dy2, dx=torch.empty_like(x2), out=out,
-                                       grad_beta=0.0, y=dy2, param_f32=ctx.mixed))   # y is not written by backward: any valid buffer
-        ops.LayerGroup(calls).backward(_lib.BWD_DATA | _lib.BWD_WEIGHTS)
+            dy2s.append(torch.zeros(T, d_out, dtype=x2.dtype, device=x2.device) if dy is None
+                        else dy.reshape(-1, d_out).contiguous())
+            outs.append((torch.empty_like(A), torch.empty_like(B), torch.empty_like(bias) if bias is not None else None))
+
+        def make_calls(dxs):
+            calls = []
+            for i in range(n):
+                A, B, acc_down, acc_up, bias = tensors[5 * i:5 * i + 5]
+                kind = ops.acc_kind(acc_down, acc_up)
+                calls.append(ops.LayerCall(x2, A.contiguous(), B.contiguous(),
+                                           acc_down=acc_down.contiguous() if kind != _lib.ACC_NONE else None,
+                                           acc_up=acc_up.contiguous() if kind == _lib.ACC_LOWRANK else None,
+                                           bias=bias, scale=ctx.scales[i], h=hs[i], dy2=dy2s[i], dx=dxs[i], out=outs[i],
+                                           grad_beta=0.0, y=dy2s[i], param_f32=ctx.mixed))   # y is not written by backward
+            return calls
+
+        dx = None
+        if ctx.shared:
+            shared_dx = torch.empty_like(x2)
+            if ops.SharedInputGroup(make_calls([shared_dx] * n)).backward(_lib.BWD_DATA | _lib.BWD_WEIGHTS):
+                dx = _SoWGroupFunction._cast_input_grad(ctx, shared_dx)
+        if dx is None:
+            calls = make_calls([torch.empty_like(x2) for _ in range(n)])
+            ops.LayerGroup(calls).backward(_lib.BWD_DATA | _lib.BWD_WEIGHTS)
+            dx = _SoWGroupFunction._input_grad(ctx, calls)
         grads: List[Optional[torch.Tensor]] = []
         for (dA, dB, dbias) in outs:
             grads += [dA, dB, None, None, dbias]
-        return (_SoWGroupFunction._input_grad(ctx, calls), None, None, None, *grads)
+        return (dx, None, None, None, None, *grads)
+
+    @staticmethod
+    def _shared_data(ctx, x2, data_calls, n):
+        """The data phase through the shared-input kernel: the one input gradient, or None when the set is not admitted."""
+        if not ctx.shared:
+            return None
+        dx = torch.empty_like(x2)
+        if not ops.SharedInputGroup(data_calls([dx] * n, 0.0)).backward(_lib.BWD_DATA):
+            return None
+        return _SoWGroupFunction._cast_input_grad(ctx, dx)
+
+    @staticmethod
+    def _cast_input_grad(ctx, dx):
+        return (dx if dx.dtype == ctx.x_dtype else ops.cast(dx, ctx.x_dtype)).reshape(ctx.x_shape)
 
     @staticmethod
     def _input_grad(ctx, calls):
@@ -115,8 +163,9 @@ class _SoWGroupFunction(torch.autograd.Function):
 class SiblingGroup:
     """SoWLinear layers of one parent module that the model calls with the same input tensor."""
 
-    def __init__(self, layers: Sequence[SoWLinear]):
+    def __init__(self, layers: Sequence[SoWLinear], shared_input: bool = False):
         self.layers = list(layers)
+        self.shared_input = bool(shared_input)
         self._key = None
         self._x = None                 # keeps the input alive while outputs are parked (no id() reuse)
         self._parked: dict = {}
@@ -165,22 +214,24 @@ class SiblingGroup:
                         m.acc_upweight, m.bias]
         sinks = tuple(getattr(m, "_grad_sink", None) for m in self.layers)
         ys = _SoWGroupFunction.apply(x, tuple(float(m.scale) for m in self.layers), sinks if sinks[0] is not None else None,
-                                     cdt, *tensors)
+                                     cdt, self.shared_input, *tensors)
         self._key, self._x = key, x
         self._parked = {id(m): y for m, y in zip(self.layers, ys) if m is not layer}
         return ys[self.layers.index(layer)]
 
 
-def group_siblings(model: nn.Module, groups: Iterable[Sequence[str]] = DEFAULT_GROUPS) -> int:
+def group_siblings(model: nn.Module, groups: Iterable[Sequence[str]] = DEFAULT_GROUPS, shared_input: bool = False) -> int:
     """Group sibling SoWLinear layers (same parent, same in_features, one factor pair) that the model calls on the same
-    input.  Returns the number of groups installed.  `ungroup_siblings(model)` removes them."""
+    input.  Returns the number of groups installed.  `ungroup_siblings(model)` removes them.  shared_input=True: the
+    backward returns one input gradient, summed in the kernel, where the shared-input kernels admit the group (see the
+    module docstring); otherwise the group runs exactly as with shared_input=False."""
     n = 0
     for parent in model.modules():
         for names in groups:
             mods = [getattr(parent, nm, None) for nm in names]
             if (all(isinstance(m, SoWLinear) for m in mods) and len({m.in_features for m in mods}) == 1
                     and all(m.n_iter == 1 for m in mods)):
-                g = SiblingGroup(mods)
+                g = SiblingGroup(mods, shared_input=shared_input)
                 for m in mods:
                     m._sibling_group = g
                 n += 1

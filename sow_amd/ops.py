@@ -334,6 +334,36 @@ class LayerGroup:
         return [buf.raw[i * size:(i + 1) * size] for i in range(n)], list(blocks)
 
 
+class SharedInputGroup(LayerGroup):
+    """Sibling calls on ONE input x2 (q / k / v, gate / up) through sow_forward_shared / sow_backward_shared: the forward
+    reads x once for all of them, the data gradient is ONE dX -- the fp32 sum over the siblings rounded once, written to
+    the first call's dx with its grad_beta (the other calls' dx are not written).  y, h and the weight gradients are
+    bit-identical to LayerGroup.  forward() / backward() return False when the set is not admitted (the C ABI returned
+    SOW_ERR_UNSUPPORTED and launched nothing); the caller then runs LayerGroup."""
+
+    def __init__(self, calls: Sequence[LayerCall]):
+        super().__init__(calls)
+        if len({c.args.x for c in self.calls}) != 1:
+            raise ValueError("sow_amd.SharedInputGroup: every call must read the same x")
+        for i in range(1, len(calls)):   # one dX for the set: the other calls' dx are not written
+            self.arr[i].dx = self.arr[0].dx
+
+    def _run(self, what: str, fn, *args) -> bool:
+        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        with torch.cuda.device(idx):
+            rc = fn(self.arr, len(self.calls), self.dtype, *args, _stream(self.device))
+        if rc == _lib.ERR_UNSUPPORTED:
+            return False
+        _lib.check(rc, what)
+        return True
+
+    def forward(self) -> bool:
+        return self._run("sow_forward_shared", _lib.load().sow_forward_shared)
+
+    def backward(self, phases: int = _lib.BWD_DATA | _lib.BWD_WEIGHTS) -> bool:
+        return self._run("sow_backward_shared", _lib.load().sow_backward_shared, int(phases))
+
+
 class DeferredReduce:
     """The weight-gradient reductions of many layers in one launch (include/sow_amd.h: sow_reduce_batch).
 
