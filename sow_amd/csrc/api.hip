@@ -53,7 +53,7 @@ namespace sow {
 static const char* const kSwitchNames[SW_COUNT] = {"FORCE_CHAIN_V1", "NO_SHORT_SPLIT", "NO_FUSED_H", "FORCE_GEMM_V1", "TN_NARROW",
                                                    "NO_GEMM3S",      "GEMM3S",         "GEMM3",      "NO_GROUPED",     "NO_PERSIST",     "NO_NT_STORE",    "NT_LOAD",        "NO_PAIR_FLUSH",  "F32_EXACT",
                                                    "NO_PARK16",      "TN_NO_NT_LOAD",  "NO_TN_ROWS",     "GEMM4",          "NO_GEMM4H",      "NO_CHAIN3F",     "NO_TN_F32Q",     "NO_SPLITK",
-                                                   "NO_WIDE_CHAIN",  "NO_SHARED_X"};
+                                                   "NO_WIDE_CHAIN",  "NO_SHARED_X",    "NO_RAGGED"};
 static std::atomic<int> g_switch[SW_COUNT];
 static std::once_flag g_switch_once;
 static void switches_from_env() {
@@ -159,7 +159,7 @@ static int gemm_auto(const void* A, int64_t lda, const void* B, int64_t ldb, boo
 
 extern "C" {
 
-int sow_version(void) { return 114; }
+int sow_version(void) { return 115; }
 
 int sow_set_switch(const char* name, int value) {
   if (!name) return SOW_ERR_NULL;
@@ -201,6 +201,14 @@ const char* sow_error_string(int code) {
 }
 
 size_t sow_h_save_elems(int64_t T, int r_live) { return (size_t)T * (size_t)(r_live <= 64 ? 64 : r_live); }
+
+// A layer of ragged widths (include/sow_amd.h): bf16 / f16 compute dtype, even r_live in (64, 256], d_in or d_out not a
+// multiple of 8, no accumulator or a low-rank one of even r_acc in [2, 256].  A pure function of the shape: the workspace
+// plan follows it whatever the NO_RAGGED switch says.
+static bool rag_layer(int r_live, int r_acc, int acc_kind, int d_in, int d_out, int dtype) {
+  return r_live > 64 && ragged_shape_ok(r_live, d_in, d_out, dtype) &&
+         (acc_kind == SOW_ACC_NONE || (acc_kind == SOW_ACC_LOWRANK && ragged_shape_ok(r_acc, d_in, d_out, dtype)));
+}
 
 // workspace carve (identical in the query and in the calls)
 struct WsPlan {
@@ -260,6 +268,8 @@ static WsPlan plan_ws(int64_t T, int d_in, int d_out, int r_live, int r_acc, int
   {
     int rw = chain_wide_shape_ok(r_live, d_in, d_out, dtype) ? r_live : 0;
     if (acc_kind == SOW_ACC_LOWRANK && chain_wide_shape_ok(r_acc, d_in, d_out, dtype) && r_acc > rw) rw = r_acc;
+    // ragged layer: the factors of its live term or of its low-rank accumulator, whichever is wider
+    if (rag_layer(r_live, r_acc, acc_kind, d_in, d_out, dtype)) rw = acc_kind == SOW_ACC_LOWRANK && r_acc > r_live ? r_acc : r_live;
     if (rw) {
       w.wide_bytes = chain_wide_pack_bytes(rw, d_in, d_out);
       off += al256(w.wide_bytes);
@@ -268,7 +278,7 @@ static WsPlan plan_ws(int64_t T, int d_in, int d_out, int r_live, int r_acc, int
   // token-slab partials of the wide weight-gradient kernel (skinny_tn_wide.hip)
   w.off_pw = off;
   w.pw_bytes = 0;
-  if (tnw_shape_ok(r_live, d_in, d_out, dtype)) {
+  if (tnw_shape_ok(r_live, d_in, d_out, dtype) || rag_layer(r_live, r_acc, acc_kind, d_in, d_out, dtype)) {
     w.pw_bytes = tnw_partial_bytes(T, d_in, d_out, r_live);
     off += al256(w.pw_bytes);
   }
@@ -341,10 +351,13 @@ static sow_layer_args single_layer(const void* A, const void* B, const void* acc
 // One term of a wide-rank layer on the fused chain (chain_wide.hip), the factors packed into the workspace's wide region;
 // SOW_ERR_UNSUPPORTED: nothing launched, the caller composes generic GEMMs.  Forward (bwd = false): F1 = A-like [D1][r],
 // F2 = B-like [r][D2]; data gradient: F1 = B-like [r][D1], F2 = A-like [D2][r].
+// rag: a term of an admitted ragged layer (rag_layer; the NO_WIDE_CHAIN switch does not apply); any other caller gets
+// SOW_ERR_UNSUPPORTED for ragged widths, so that they keep the generic kernels.
 static int wide_chain(const void* X, void* Y, const void* F1, int64_t ldf1, const void* F2, int64_t ldf2, void* Hsave,
                       const void* bias, int64_t T, int D1, int D2, int r, float hscale, float yscale, float beta, bool bwd,
-                      int dtype, char* ws, const WsPlan& w, size_t workspace_bytes, hipStream_t stream) {
-  if (sw_on(SW_NO_WIDE_CHAIN) || !ws || !w.wide_bytes || workspace_bytes < w.total + 255 ||
+                      int dtype, char* ws, const WsPlan& w, size_t workspace_bytes, hipStream_t stream, bool rag = false) {
+  const bool ragged = D1 % 8 != 0 || D2 % 8 != 0;
+  if ((ragged ? !rag : sw_on(SW_NO_WIDE_CHAIN)) || !ws || !w.wide_bytes || workspace_bytes < w.total + 255 ||
       chain_wide_pack_bytes(r, D1, D2) > w.wide_bytes)
     return SOW_ERR_UNSUPPORTED;
   WideArgs a{};
@@ -444,6 +457,20 @@ static int forward_impl(const void* x, const void* A, const void* B, const void*
   char* ws = workspace ? ws_base(workspace) : nullptr;
   float beta = 0.f;
   int rc;
+  // ragged widths: the fused chain for the low-rank accumulator (scale 1) and the live term, X read once per term; h_save
+  // holds the unscaled projection (the wide contract).  Without workspace or with views off 16 bytes, the generic kernels
+  // below.
+  if (rag_layer(r_live, r_acc, acc_kind, d_in, d_out, dtype) && !sw_on(SW_NO_RAGGED) && ws && workspace_bytes >= w.total + 255 &&
+      al16p(x) && al16p(y) && (!bias || al16p(bias)) && (!h_save || al4p(h_save))) {
+    if (acc_kind == SOW_ACC_LOWRANK) {
+      rc = wide_chain(x, y, acc_down, r_acc, acc_up, d_out, nullptr, nullptr, T, d_in, d_out, r_acc, 1.f, 1.f, 0.f, false, dtype,
+                      ws, w, workspace_bytes, stream, true);
+      if (rc) return rc;
+      beta = 1.f;
+    }
+    return wide_chain(x, y, A, r_live, B, d_out, h_save, bias, T, d_in, d_out, r_live, 1.f, scale, beta, false, dtype, ws, w,
+                      workspace_bytes, stream, true);
+  }
   if (acc_kind == SOW_ACC_DENSE) {
     if (r_live <= 64 && h_save) {
       // one product with the low-rank term as a K-extension:  y = [x, h] . [W_acc; B] + bias,  h = scale * x . A
@@ -564,7 +591,7 @@ static int backward_impl(const void* dy, const void* x, const void* h_save, cons
                          int r_live, int r_acc, int acc_kind, float scale, float grad_beta, int dtype, int gdt, void* workspace,
                          size_t workspace_bytes, int phases, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  const bool do_data = (phases & SOW_BWD_DATA) != 0;
+  bool do_data = (phases & SOW_BWD_DATA) != 0;
   const bool do_partial = (phases & (SOW_BWD_WEIGHTS | SOW_BWD_WEIGHTS_PARTIAL)) != 0;
   const bool do_reduce = (phases & (SOW_BWD_WEIGHTS | SOW_BWD_WEIGHTS_REDUCE)) != 0;
   const bool do_weights = do_partial || do_reduce;
@@ -593,6 +620,21 @@ static int backward_impl(const void* dy, const void* x, const void* h_save, cons
   float beta = 0.f;
   int rc;
   bool data_done = false;
+  // ragged widths: the fused chain for the data gradient (dY and dX views 16-byte aligned, else the generic kernels below:
+  // they leave the same dh) and skinny_tn_wide for every weight gradient, dbias included, in the PARTIAL phase
+  const bool rag_w = rag_layer(r_live, r_acc, acc_kind, d_in, d_out, dtype) && !sw_on(SW_NO_RAGGED);
+  if (rag_w && do_data && al16p(dy) && al16p(dx)) {
+    if (acc_kind == SOW_ACC_LOWRANK) {
+      rc = wide_chain(dy, dx, acc_up, d_out, acc_down, r_acc, nullptr, nullptr, T, d_out, d_in, r_acc, 1.f, 1.f, 0.f, true, dtype,
+                      ws, w, workspace_bytes, stream, true);
+      if (rc) return rc;
+      beta = 1.f;
+    }
+    rc = wide_chain(dy, dx, B, d_out, A, r_live, dh, nullptr, T, d_out, d_in, r_live, scale, 1.f, beta, true, dtype, ws, w,
+                    workspace_bytes, stream, true);
+    if (rc) return rc;
+    do_data = false;
+  }
   if (!do_data) {
     // weights-only call: dh was produced by an earlier SOW_BWD_DATA call on the same workspace
   } else if (acc_kind == SOW_ACC_DENSE) {
@@ -719,7 +761,7 @@ static int backward_impl(const void* dy, const void* x, const void* h_save, cons
     if (rc) return rc;
   }
   if (!do_partial) return SOW_OK;   // wide ranks: the PARTIAL phase does all of the weight gradients
-  if (w.pw_bytes && !sw_on(SW_NO_WIDE_CHAIN)) {
+  if (w.pw_bytes && (rag_w || (!sw_on(SW_NO_WIDE_CHAIN) && tnw_shape_ok(r_live, d_in, d_out, dtype)))) {
     rc = launch_tn_wide(x, dh, dy, h_save, dA, dB, dbias, T, d_in, d_out, r_live, scale, grad_beta, dtype, gdt, ws + w.off_pw,
                         w.pw_bytes, stream);
     if (rc != SOW_ERR_UNSUPPORTED) return rc;

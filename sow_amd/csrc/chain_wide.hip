@@ -17,6 +17,14 @@
 //            H tiles (2 token halves x r_pad / 32 column tiles) dealt round-robin to the waves, <= 4 per wave;
 //   phase 2 (per 64 output columns): [0, 32K) H as r_pad / 64 panels [64][64], [32K, 64K) F2 panels [64][64], reused as
 //            the epilogue scratch once the panel's products are done; wave (wm, wn) owns a 32 x 32 output tile.
+//
+// Ragged widths (RAG: D1 or D2 not a multiple of 8, even r in [2, 256]): a token row of X starts at any 2-byte offset.
+// Each thread still stages 8 consecutive elements of one row: it reads the one or two aligned 16-byte pieces that hold
+// them through a buffer descriptor limited to the workgroup's own rows (so the last piece of the tensor reads zeros past
+// its end), shifts them into place in registers and zeroes the columns >= D1; the LDS image is then written at its
+// natural alignment, exactly as in the aligned kernel.  F1T rows are padded to D1p = ceil8(D1) by the pack.  Y is
+// written element by element (2-byte stores): no byte of a token row is written by another workgroup, whatever D2.
+// The ragged kernel also takes 2 <= r <= 64 (r_pad = 64) for a layer's low-rank accumulator term, which saves no H.
 #include "kernels.hpp"
 #include "epilogue.hpp"
 
@@ -49,12 +57,12 @@ template <typename T> __global__ __launch_bounds__(256) void wide_pack_kernel(co
 struct WideParams {
   const void* X;
   void* Y;
-  const void* F1T;   // [r_pad][D1]
+  const void* F1T;   // [r_pad][ldf1t]
   const void* F2T;   // [D2][r_pad]
   void* Hsave;       // [M][r] or nullptr
   const void* bias;  // [D2] or nullptr
   int64_t M;
-  int D1, D2, r, r_pad;
+  int D1, D2, r, r_pad, ldf1t;
   float hscale, yscale, beta;
   int nt_store;
 };
@@ -65,7 +73,43 @@ template <typename T> __device__ __forceinline__ int cw_panel_off(int row, int k
   return (k >> 6) * CW_PANEL + bf16_img_off<64>(row, (k & 63) >> 3) + (k & 7) * 2;
 }
 
-template <typename T> __global__ __launch_bounds__(256, 2) void chain_wide_kernel(const WideParams p) {
+// 16-byte piece at byte `off` of a ragged workgroup's rows (`lim` bytes): the piece that crosses the limit (the end of the
+// tensor, for the last workgroup) is read dword by dword, a 2-byte load for a dword cut in half: nothing past the limit is
+// requested, and the bytes past it read as 0
+__device__ __forceinline__ u32x4 rag_piece(__amdgpu_buffer_rsrc_t rs, uint32_t off, uint32_t lim) {
+  if (off + 16 <= lim) return __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
+  u32x4 v;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const uint32_t o = off + 4 * q;
+    v[q] = o + 4 <= lim ? __builtin_amdgcn_raw_buffer_load_b32(rs, o, 0, 0)
+                        : (o < lim ? (uint32_t)__builtin_amdgcn_raw_buffer_load_b16(rs, o, 0, 0) : 0u);
+  }
+  return v;
+}
+
+// elements gk .. gk + 7 of row `row` (element e = row * D1 + gk of the workgroup's rows), zero past column D1
+__device__ __forceinline__ u32x4 rag_load8(__amdgpu_buffer_rsrc_t rs, uint32_t lim, int row, int D1, int gk) {
+  const uint32_t e = (uint32_t)row * (uint32_t)D1 + (uint32_t)gk, off = (e >> 3) << 4;
+  const int sh = e & 7, ws = sh >> 1;
+  const u32x4 p0 = rag_piece(rs, off, lim);
+  const u32x4 p1 = sh ? rag_piece(rs, off + 16, lim) : u32x4{0, 0, 0, 0};
+  const uint32_t d[8] = {p0[0], p0[1], p0[2], p0[3], p1[0], p1[1], p1[2], p1[3]};
+  uint32_t s5[5];
+#pragma unroll
+  for (int j = 0; j < 5; ++j) s5[j] = ws == 0 ? d[j] : ws == 1 ? d[j + 1] : ws == 2 ? d[j + 2] : d[j + 3 < 8 ? j + 3 : 7];
+  u32x4 v;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = (sh & 1) ? __builtin_amdgcn_alignbit(s5[j + 1], s5[j], 16) : s5[j];
+  const int n = D1 - gk;
+  if (n < 8) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = 2 * j >= n ? 0u : (2 * j + 1 >= n ? (v[j] & 0xffffu) : v[j]);
+  }
+  return v;
+}
+
+template <typename T, bool RAG> __global__ __launch_bounds__(256, 2) void chain_wide_kernel(const WideParams p) {
   using V8 = typename DT<T>::v8;
   __shared__ __attribute__((aligned(16))) char smem[CW_LDS];
   char* big = smem;              // F1 image, then the H panels
@@ -77,6 +121,10 @@ template <typename T> __global__ __launch_bounds__(256, 2) void chain_wide_kerne
   const T* F1T = (const T*)p.F1T;
   const T* F2T = (const T*)p.F2T;
   const int r_pad = p.r_pad, ntiles = 2 * (r_pad / 32), np = r_pad / 64;
+  // RAG: the workgroup's token rows as one buffer (base 16-byte aligned: X is, and t0 * D1 * 2 is a multiple of 128)
+  const int rows = p.M - t0 < 64 ? (int)(p.M - t0) : 64;
+  const uint32_t lim = (uint32_t)rows * (uint32_t)p.D1 * 2u;
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(X + t0 * p.D1), (short)0, (int)lim, 0x00020000);
 
   // ---- phase 1: H = X . F1 ------------------------------------------------------------------------------
   f32x16 acc[4];
@@ -91,13 +139,16 @@ template <typename T> __global__ __launch_bounds__(256, 2) void chain_wide_kerne
       const int idx = t + 256 * i, row = idx >> 3, c = idx & 7;
       const int64_t gt = t0 + row;
       const int gk = k0 + c * 8;
-      xv[i] = (gt < p.M && gk < p.D1) ? *(const u32x4*)(X + gt * p.D1 + gk) : u32x4{0, 0, 0, 0};
+      if constexpr (RAG)
+        xv[i] = (row < rows && gk < p.D1) ? rag_load8(rs, lim, row, p.D1, gk) : u32x4{0, 0, 0, 0};
+      else
+        xv[i] = (gt < p.M && gk < p.D1) ? *(const u32x4*)(X + gt * p.D1 + gk) : u32x4{0, 0, 0, 0};
     }
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int idx = t + 256 * i, row = idx >> 3, c = idx & 7;
       const int gk = k0 + c * 8;
-      fv[i] = (row < r_pad && gk < p.D1) ? *(const u32x4*)(F1T + (int64_t)row * p.D1 + gk) : u32x4{0, 0, 0, 0};
+      fv[i] = (row < r_pad && gk < p.D1) ? *(const u32x4*)(F1T + (int64_t)row * p.ldf1t + gk) : u32x4{0, 0, 0, 0};
     }
   };
   auto store1 = [&]() {
@@ -192,7 +243,7 @@ template <typename T> __global__ __launch_bounds__(256, 2) void chain_wide_kerne
       }
     }
     __syncthreads();   // the F2 panels are consumed: their space becomes the epilogue scratch
-    wave_store_tiles<T, 1, true>(&o, scratch, (T*)p.Y, p.D2, t0 + wm * 32, nb * 64 + wn * 32, p.M, p.D2, p.yscale, p.beta,
+    wave_store_tiles<T, 1, !RAG>(&o, scratch, (T*)p.Y, p.D2, t0 + wm * 32, nb * 64 + wn * 32, p.M, p.D2, p.yscale, p.beta,
                                  (const T*)p.bias, lane, p.nt_store != 0);
   }
 }
@@ -201,43 +252,52 @@ bool chain_wide_shape_ok(int r, int d1, int d2, int dtype) {
   return (dtype == SOW_BF16 || dtype == SOW_F16) && r > 64 && r <= 256 && r % 2 == 0 && d1 % 8 == 0 && d2 % 8 == 0;
 }
 
+bool ragged_shape_ok(int r, int d1, int d2, int dtype) {
+  return (dtype == SOW_BF16 || dtype == SOW_F16) && r >= 2 && r <= 256 && r % 2 == 0 && (d1 % 8 != 0 || d2 % 8 != 0) &&
+         d1 > 0 && d2 > 0 && d1 <= (1 << 23) && d2 <= (1 << 23);
+}
+
+// F1T [r_pad][ceil8(D1)] + F2T [D2][r_pad], D1 / D2 = d_in / d_out in either order
 size_t chain_wide_pack_bytes(int r, int d_in, int d_out) {
-  const size_t r_pad = (size_t)(r + 63) / 64 * 64;
-  return ((r_pad * d_in * 2 + 255) & ~(size_t)255) + ((r_pad * d_out * 2 + 255) & ~(size_t)255);
+  const size_t r_pad = (size_t)(r + 63) / 64 * 64, p_in = (size_t)(d_in + 7) / 8 * 8, p_out = (size_t)(d_out + 7) / 8 * 8;
+  return ((r_pad * p_in * 2 + 255) & ~(size_t)255) + ((r_pad * p_out * 2 + 255) & ~(size_t)255);
 }
 
 static bool al16w(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 int launch_chain_wide(const WideArgs& a, int dtype, hipStream_t stream) {
-  if (!chain_wide_shape_ok(a.r, a.D1, a.D2, dtype)) return SOW_ERR_UNSUPPORTED;
-  if (!al16w(a.X) || !al16w(a.Y) || (a.bias && !al16w(a.bias)) || !al16w(a.pack) ||
+  const bool rag = a.D1 % 8 != 0 || a.D2 % 8 != 0;
+  if (!(rag ? ragged_shape_ok(a.r, a.D1, a.D2, dtype) : chain_wide_shape_ok(a.r, a.D1, a.D2, dtype))) return SOW_ERR_UNSUPPORTED;
+  if ((rag && a.r <= 64 && a.Hsave) || !al16w(a.X) || !al16w(a.Y) || (a.bias && !al16w(a.bias)) || !al16w(a.pack) ||
       (a.Hsave && (reinterpret_cast<uintptr_t>(a.Hsave) & 3)) || !a.pack ||
       a.pack_bytes < chain_wide_pack_bytes(a.r, a.D1, a.D2))
     return SOW_ERR_UNSUPPORTED;
   if (a.M <= 0) return SOW_OK;
   if (ceil_div(a.M, 64) > 0x7fffffff) return SOW_ERR_SHAPE;
-  const int r_pad = (a.r + 63) / 64 * 64;
+  const int r_pad = (a.r + 63) / 64 * 64, d1p = (a.D1 + 7) / 8 * 8;
   char* f1t = (char*)a.pack;
-  char* f2t = f1t + (((size_t)r_pad * a.D1 * 2 + 255) & ~(size_t)255);
-  // F1T [r_pad][D1]: column c of F1 (forward: A [D1][r], transposed; data gradient: B [r][D1], as stored)
+  char* f2t = f1t + (((size_t)r_pad * d1p * 2 + 255) & ~(size_t)255);
+  // F1T [r_pad][d1p]: column c of F1 (forward: A [D1][r], transposed; data gradient: B [r][D1], as stored)
   // F2T [D2][r_pad]: column n of F2 (forward: B [r][D2], transposed; data gradient: A [D2][r], as stored)
   WidePackParams pk{};
-  pk.job[0] = WidePack{a.F1, a.ldf1, f1t, r_pad, a.D1, a.r, a.D1, a.bwd ? 0 : 1};
+  pk.job[0] = WidePack{a.F1, a.ldf1, f1t, r_pad, d1p, a.r, a.D1, a.bwd ? 0 : 1};
   pk.job[1] = WidePack{a.F2, a.ldf2, f2t, a.D2, r_pad, a.D2, a.r, a.bwd ? 0 : 1};
-  pk.n0 = (int64_t)r_pad * a.D1;
+  pk.n0 = (int64_t)r_pad * d1p;
   pk.n = pk.n0 + (int64_t)a.D2 * r_pad;
   WideParams p{};
   p.X = a.X, p.Y = a.Y, p.F1T = f1t, p.F2T = f2t, p.Hsave = a.Hsave, p.bias = a.bias;
-  p.M = a.M, p.D1 = a.D1, p.D2 = a.D2, p.r = a.r, p.r_pad = r_pad;
+  p.M = a.M, p.D1 = a.D1, p.D2 = a.D2, p.r = a.r, p.r_pad = r_pad, p.ldf1t = d1p;
   p.hscale = a.hscale, p.yscale = a.yscale, p.beta = a.beta;
   p.nt_store = SOW_GEMM_NT(a.M) ? 1 : 0;
   const dim3 pgrid((unsigned)((pk.n + 255) / 256)), grid((unsigned)ceil_div(a.M, 64));
   if (dtype == SOW_BF16) {
     hipLaunchKernelGGL(wide_pack_kernel<bf16_t>, pgrid, dim3(256), 0, stream, pk);
-    hipLaunchKernelGGL(chain_wide_kernel<bf16_t>, grid, dim3(256), 0, stream, p);
+    if (rag) hipLaunchKernelGGL((chain_wide_kernel<bf16_t, true>), grid, dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL((chain_wide_kernel<bf16_t, false>), grid, dim3(256), 0, stream, p);
   } else {
     hipLaunchKernelGGL(wide_pack_kernel<f16_t>, pgrid, dim3(256), 0, stream, pk);
-    hipLaunchKernelGGL(chain_wide_kernel<f16_t>, grid, dim3(256), 0, stream, p);
+    if (rag) hipLaunchKernelGGL((chain_wide_kernel<f16_t, true>), grid, dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL((chain_wide_kernel<f16_t, false>), grid, dim3(256), 0, stream, p);
   }
   SOW_CHECK_LAUNCH();
   return SOW_OK;

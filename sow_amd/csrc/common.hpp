@@ -177,6 +177,7 @@ enum Switch : int {
   SW_NO_SPLITK,           // bf16 GEMM with few output tiles (short T): never split K over workgroups
   SW_NO_WIDE_CHAIN,       // 64 < r <= 256: the generic GEMM composition instead of chain_wide / skinny_tn_wide
   SW_NO_SHARED_X,         // sow_forward_shared / sow_backward_shared return SOW_ERR_UNSUPPORTED (callers take the grouped path)
+  SW_NO_RAGGED,           // widths not multiples of 8: the generic kernels instead of the ragged chain_wide / skinny_tn_wide
   SW_COUNT
 };
 int sw(int which);

@@ -160,6 +160,10 @@ struct WideArgs {
   size_t pack_bytes;
 };
 bool chain_wide_shape_ok(int r, int d1, int d2, int dtype);
+// ragged widths (include/sow_amd.h): bf16 / f16, even r in [2, 256], d1 or d2 not a multiple of 8.  The same kernels with
+// X / Y rows at any 2-byte offset (X, Y, bias bases still 16-byte aligned).  r <= 64 only without Hsave (the low-rank
+// accumulator term of an admitted layer); the weight-gradient kernel takes r > 64 only
+bool ragged_shape_ok(int r, int d1, int d2, int dtype);
 size_t chain_wide_pack_bytes(int r, int d_in, int d_out);
 // SOW_ERR_UNSUPPORTED when the shape, the alignment or the scratch does not suit the kernel (nothing launched)
 int launch_chain_wide(const WideArgs& a, int dtype, hipStream_t stream);

@@ -12,11 +12,15 @@
 // Operands are stored token-major (the contraction index is the row index), so both are staged as dword pairs of 8
 // consecutive tokens and transposed in registers (transpose_8x2) into k-contiguous LDS images, as the generic GEMM does
 // for a transposed operand.  LDS: M image [64][64] 8 KiB, S image [256][64] 32 KiB.
+//
+// Ragged widths (RAG: d_in or d_out not a multiple of 8): a row of x / dY starts at any 2-byte offset, so the column pair
+// of an M item is read as two 16-bit loads (each column < D, nothing past a row or the tensor); the LDS images and the
+// products are those of the aligned kernel.
 #include "kernels.hpp"
 
 namespace sow {
 
-template <typename T>
+template <typename T, bool RAG>
 __global__ __launch_bounds__(256, 2) void tnw_partial_kernel(const TnwParams p) {
   using V8 = typename DT<T>::v8;
   __shared__ __attribute__((aligned(16))) char mimg[64 * 64 * 2];
@@ -52,7 +56,14 @@ __global__ __launch_bounds__(256, 2) void tnw_partial_kernel(const TnwParams p) 
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int64_t gt = k0 + mko * 8 + j;
-      md[j] = (mcol && gt < te) ? *(const uint32_t*)(M + gt * D + d0 + 2 * mrp) : 0u;
+      if constexpr (RAG) {
+        const unsigned short* m16 = (const unsigned short*)(M + gt * D + d0 + 2 * mrp);
+        const uint32_t lo = (mcol && gt < te) ? m16[0] : 0u;
+        const uint32_t hi = (d0 + 2 * mrp + 1 < D && gt < te) ? m16[1] : 0u;
+        md[j] = lo | (hi << 16);
+      } else {
+        md[j] = (mcol && gt < te) ? *(const uint32_t*)(M + gt * D + d0 + 2 * mrp) : 0u;
+      }
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -192,9 +203,11 @@ static bool al4w(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) ==
 int launch_tn_wide(const void* x, const void* dh, const void* dy, const void* h, void* dA, void* dB, void* dbias, int64_t T,
                    int d_in, int d_out, int r, float scale, float beta, int dtype, int out_dtype, void* ws, size_t ws_bytes,
                    hipStream_t stream) {
-  if (!tnw_shape_ok(r, d_in, d_out, dtype)) return SOW_ERR_UNSUPPORTED;
+  // ragged widths: x and dY at any 2-byte offset (16-bit loads)
+  const bool rag = d_in % 8 != 0 || d_out % 8 != 0;
+  if (!(rag ? ragged_shape_ok(r, d_in, d_out, dtype) && r > 64 : tnw_shape_ok(r, d_in, d_out, dtype))) return SOW_ERR_UNSUPPORTED;
   if (out_dtype != dtype && out_dtype != SOW_F32) return SOW_ERR_DTYPE;
-  if (!al4w(x) || !al4w(dh) || !al4w(dy) || !al4w(h) || !ws || (reinterpret_cast<uintptr_t>(ws) & 255) ||
+  if ((!rag && (!al4w(x) || !al4w(dy))) || !al4w(h) || !al4w(dh) || !ws || (reinterpret_cast<uintptr_t>(ws) & 255) ||
       ws_bytes < tnw_partial_bytes(T, d_in, d_out, r))
     return SOW_ERR_UNSUPPORTED;
   if (T <= 0) return SOW_ERR_SHAPE;
@@ -214,10 +227,15 @@ int launch_tn_wide(const void* x, const void* dh, const void* dy, const void* h,
   q.D0 = d_in, q.D1 = d_out, q.r = r, q.r_pad = (int)r_pad, q.ns = ns, q.scale = scale, q.beta = beta;
   const int64_t blocks = (int64_t)ns * (p.ncg[0] + p.ncg[1]);
   const int64_t nout = (int64_t)(d_in + d_out) * r + (dbias ? d_out : 0);
-  if (dtype == SOW_BF16)
-    hipLaunchKernelGGL(tnw_partial_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, stream, p);
+  const dim3 pgrid((unsigned)blocks);
+  if (dtype == SOW_BF16 && rag)
+    hipLaunchKernelGGL((tnw_partial_kernel<bf16_t, true>), pgrid, dim3(256), 0, stream, p);
+  else if (dtype == SOW_BF16)
+    hipLaunchKernelGGL((tnw_partial_kernel<bf16_t, false>), pgrid, dim3(256), 0, stream, p);
+  else if (rag)
+    hipLaunchKernelGGL((tnw_partial_kernel<f16_t, true>), pgrid, dim3(256), 0, stream, p);
   else
-    hipLaunchKernelGGL(tnw_partial_kernel<f16_t>, dim3((unsigned)blocks), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((tnw_partial_kernel<f16_t, false>), pgrid, dim3(256), 0, stream, p);
   // the reduction reads fp32 partials only: its template type is the type of the gradients it writes
   const dim3 rgrid((unsigned)((nout + 255) / 256));
   if (out_dtype == SOW_F32)
