@@ -250,7 +250,8 @@ int sow_gemm_ex(const void* A, int64_t lda, int trans_a, const void* B, int64_t 
 /* Truncated Householder QR -- replaces qr_weight (utils.py:8-30) and the truncated complete-mode QR
  * of TensorTrain.decompose (tt.py:128-136):  Q_out[m,k] = Q[:, :k], R_out[k,n] = R[:k, :]
  * with LAPACK's sign convention.  W [m,n] (ldw) of in_dtype; outputs of out_dtype; internals fp32.
- * R_out may be NULL (sow.py:168-172 only needs Q).  k <= m. */
+ * R_out may be NULL (sow.py:168-172 only needs Q).  k <= m.  For n < k only n columns are factored: Q_out[:, :n] is the
+ * reduced Q (all that qr_weight returns), Q_out[:, n:k] the complete-mode columns H_0 .. H_{n-1} e_j, R_out rows n.. are 0. */
 size_t sow_qr_workspace_bytes(int m, int n, int k, int in_dtype, int need_r);
 int sow_qr_thin(const void* W, int64_t ldw, int m, int n, int in_dtype, int k, void* Q_out, int64_t ldq, void* R_out,
                 int64_t ldr, int out_dtype, void* workspace, size_t workspace_bytes, void* stream);
@@ -285,14 +286,15 @@ int sow_accumulate_batch(const sow_accumulate_args* items, int n, int dtype, voi
 int sow_zero_state(void* const* ptrs, const int64_t* bytes, int n, void* stream);
 
 /* AdamW step over one flat parameter buffer (the factor param group of simple_train.py:502-506).
- * state_dtype = dtype of exp_avg / exp_avg_sq.  step is the 1-based step count. */
-int sow_adamw_flat(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, float lr, float beta1,
-                   float beta2, float eps, float weight_decay, int step, float grad_scale, int dtype, int state_dtype,
+ * state_dtype = dtype of exp_avg / exp_avg_sq.  step is the 1-based step count.  The betas are double: 1 - beta and the
+ * bias corrections are formed from them in double, as torch.optim.AdamW does, and rounded to fp32 once. */
+int sow_adamw_flat(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, float lr, double beta1,
+                   double beta2, float eps, float weight_decay, int step, float grad_scale, int dtype, int state_dtype,
                    void* stream);
 
-/* TTAdam dense section (ttadam.py:84-111), fp32 buffers. */
-int sow_ttadam_dense(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float beta1,
-                     float beta2, float eps, float step_size, float lr_times_wd, int clamp_v, void* stream);
+/* TTAdam dense section (ttadam.py:84-111), fp32 buffers; double betas (1 - beta formed in double). */
+int sow_ttadam_dense(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, double beta1,
+                     double beta2, float eps, float step_size, float lr_times_wd, int clamp_v, void* stream);
 
 /* TT Hadamard product of two cores (tt.py:469-475): out[(a,c),ij,(b,d)] = A[a,ij,b] * B[c,ij,d], fp32. */
 int sow_tt_kron_core(const float* A, const float* B, float* out, int ra0, int rb0, int ij, int ra1, int rb1,
@@ -339,7 +341,8 @@ int sow_tt_decompose_batch(const sow_tt_desc* tts, const void* const* mats, cons
                            const size_t* workspace_bytes, void* stream);
 int sow_ttadam_batch(const sow_ttadam_item* items, int n, float beta1, float beta2, float eps, void* stream);
 
-/* out[0] = max |x[i]| over n fp32 elements (TensorTrain.sqrt / sqrtinv scaling, tt.py:288, 322). */
+/* out[0] = max |x[i]| over n fp32 elements (TensorTrain.sqrt / sqrtinv scaling, tt.py:288, 322).  NaN elements are
+ * skipped (fmaxf): the result is the max over the others (0 when all are NaN), where torch.amax would return NaN. */
 int sow_absmax(const float* x, int64_t n, float* out, void* stream);
 
 /* Batched inverse of `batch` small [r, r] fp32 matrices, r <= 16 (TensorTrain.reciprocal, tt.py:480-494). */

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int64, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SOW_AMD_LIB: an alternative build of the same library (the `make STAMPS=1` timeline build used by tools/chain_stamps.py)
@@ -94,9 +94,9 @@ SIGNATURES = {
     "sow_qr_thin": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int,
                             c_void_p, c_size_t, c_void_p]),
     "sow_zero_state": (c_int, [POINTER(c_void_p), POINTER(c_int64), c_int, c_void_p]),
-    "sow_adamw_flat": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float,
+    "sow_adamw_flat": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_double, c_double, c_float,
                                c_float, c_int, c_float, c_int, c_int, c_void_p]),
-    "sow_ttadam_dense": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float,
+    "sow_ttadam_dense": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_float, c_float,
                                  c_float, c_int, c_void_p]),
     "sow_tt_kron_core": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "sow_tt_decompose_workspace_bytes": (c_size_t, [POINTER(TtDesc)]),

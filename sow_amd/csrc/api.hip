@@ -1331,8 +1331,8 @@ int sow_zero_state(void* const* ptrs, const int64_t* bytes, int n, void* stream)
   return launch_multi_zero(ptrs, bytes, n, (hipStream_t)stream);
 }
 
-int sow_adamw_flat(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, float lr, float beta1,
-                   float beta2, float eps, float weight_decay, int step, float grad_scale, int dtype, int state_dtype,
+int sow_adamw_flat(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, float lr, double beta1,
+                   double beta2, float eps, float weight_decay, int step, float grad_scale, int dtype, int state_dtype,
                    void* stream) {
   if (flagged(dtype) || flagged(state_dtype)) return SOW_ERR_DTYPE;
   if (step < 1) return SOW_ERR_SHAPE;
@@ -1340,8 +1340,8 @@ int sow_adamw_flat(void* param, const void* grad, void* exp_avg, void* exp_avg_s
                            dtype, state_dtype, (hipStream_t)stream);
 }
 
-int sow_ttadam_dense(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float beta1,
-                     float beta2, float eps, float step_size, float lr_times_wd, int clamp_v, void* stream) {
+int sow_ttadam_dense(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, double beta1,
+                     double beta2, float eps, float step_size, float lr_times_wd, int clamp_v, void* stream) {
   return launch_ttadam_dense(param, grad, exp_avg, exp_avg_sq, n, beta1, beta2, eps, step_size, lr_times_wd, clamp_v,
                              (hipStream_t)stream);
 }

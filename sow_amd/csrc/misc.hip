@@ -60,38 +60,42 @@ int launch_multi_zero(void* const* ptrs, const int64_t* bytes, int n, hipStream_
 // AdamW over one flat buffer (torch.optim.AdamW semantics, no amsgrad, maximize=False):
 //   p *= 1 - lr*wd ; m = b1*m + (1-b1)*g ; v = b2*v + (1-b2)*g*g ;
 //   p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)
-// State m, v are fp32 or the parameter dtype (TS); math in fp32.
+// State m, v are fp32 or the parameter dtype (TS); math in fp32.  The scalars 1 - b, 1 - lr*wd, lr/bc1 and sqrt(bc2) are
+// formed in double on the host from double betas, as torch forms them from Python floats, and rounded to fp32 once:
+// 1 - b2 taken in fp32 from b2 = 0.999 rounded to fp32 is 1.3e-5 relative (216 fp32 ulp) off 0.001, an error that would
+// enter v on every step.
 // ---------------------------------------------------------------------------------------------
 template <typename T, typename TS>
-__global__ __launch_bounds__(256) void adamw_flat_kernel(T* p, const T* g, TS* m, TS* v, int64_t n, float lr, float b1,
-                                                         float b2, float eps, float wd, float bc1, float bc2_sqrt,
-                                                         float grad_scale) {
+__global__ __launch_bounds__(256) void adamw_flat_kernel(T* p, const T* g, TS* m, TS* v, int64_t n, float b1, float c1,
+                                                         float b2, float c2, float eps, float decay, float step_size,
+                                                         float bc2_sqrt, float grad_scale) {
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = tid; i < n; i += nth) {
     float pv = to_f32(p[i]);
     const float gv = to_f32(g[i]) * grad_scale;
     float mv = to_f32(m[i]), vv = to_f32(v[i]);
-    pv *= 1.f - lr * wd;
-    mv = b1 * mv + (1.f - b1) * gv;
-    vv = b2 * vv + (1.f - b2) * gv * gv;
+    pv *= decay;
+    mv = b1 * mv + c1 * gv;
+    vv = b2 * vv + c2 * gv * gv;
     const float denom = sqrtf(vv) / bc2_sqrt + eps;
-    pv -= (lr / bc1) * (mv / denom);
+    pv -= step_size * (mv / denom);
     p[i] = from_f32<T>(pv);
     m[i] = from_f32<TS>(mv);
     v[i] = from_f32<TS>(vv);
   }
 }
 
-int launch_adamw_flat(void* p, const void* g, void* m, void* v, int64_t n, float lr, float b1, float b2, float eps,
+int launch_adamw_flat(void* p, const void* g, void* m, void* v, int64_t n, float lr, double b1, double b2, float eps,
                       float wd, int step, float grad_scale, int dtype, int state_dtype, hipStream_t stream) {
   if (n <= 0) return SOW_OK;
   if (!p || !g || !m || !v) return SOW_ERR_NULL;
-  const float bc1 = 1.f - powf(b1, (float)step);
-  const float bc2s = sqrtf(1.f - powf(b2, (float)step));
+  const double bc1 = 1.0 - std::pow(b1, (double)step), bc2 = 1.0 - std::pow(b2, (double)step);
+  const float b1f = (float)b1, c1 = (float)(1.0 - b1), b2f = (float)b2, c2 = (float)(1.0 - b2);
+  const float decay = (float)(1.0 - (double)lr * wd), step_size = (float)(lr / bc1), bc2s = (float)std::sqrt(bc2);
   int grid = (int)((n + 255) / 256);
   if (grid > 2048) grid = 2048;
 #define SOW_ADAMW(T, TS) \
-  hipLaunchKernelGGL((adamw_flat_kernel<T, TS>), dim3(grid), dim3(256), 0, stream, (T*)p, (const T*)g, (TS*)m, (TS*)v, n, lr, b1, b2, eps, wd, bc1, bc2s, grad_scale)
+  hipLaunchKernelGGL((adamw_flat_kernel<T, TS>), dim3(grid), dim3(256), 0, stream, (T*)p, (const T*)g, (TS*)m, (TS*)v, n, b1f, c1, b2f, c2, eps, decay, step_size, bc2s, grad_scale)
   if (dtype == SOW_F32 && state_dtype == SOW_F32) SOW_ADAMW(float, float);
   else if (dtype == SOW_BF16 && state_dtype == SOW_BF16) SOW_ADAMW(bf16_t, bf16_t);
   else if (dtype == SOW_BF16 && state_dtype == SOW_F32) SOW_ADAMW(bf16_t, float);
@@ -106,17 +110,18 @@ int launch_adamw_flat(void* p, const void* g, void* m, void* v, int64_t n, float
 // ---------------------------------------------------------------------------------------------
 // TTAdam dense section (ttadam.py:84-111), fp32:  v<0 -> 0 clamp (only when clamp_v), then
 //   m = b1*m + (1-b1)*g ; v = b2*v + (1-b2)*g*g ; p += -step_size * m/(sqrt(v)+eps) ; p += -lr*wd*p
+// 1 - b is formed in double on the host from double betas (the Python-float alpha = 1.0 - beta of ttadam.py:91-92).
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void ttadam_dense_kernel(float* p, const float* g, float* m, float* v, int64_t n,
-                                                           float b1, float b2, float eps, float step_size,
-                                                           float lr_wd, int clamp_v) {
+                                                           float b1, float c1, float b2, float c2, float eps,
+                                                           float step_size, float lr_wd, int clamp_v) {
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = tid; i < n; i += nth) {
     const float gv = g[i];
     float vv = v[i];
     if (clamp_v && vv < 0.f) vv = 0.f;
-    const float mv = m[i] * b1 + gv * (1.f - b1);
-    vv = vv * b2 + gv * gv * (1.f - b2);
+    const float mv = m[i] * b1 + gv * c1;
+    vv = vv * b2 + gv * gv * c2;
     float pv = p[i] + (mv / (sqrtf(vv) + eps)) * (-step_size);
     if (lr_wd > 0.f) pv = pv + pv * (-lr_wd);
     p[i] = pv;
@@ -125,13 +130,14 @@ __global__ __launch_bounds__(256) void ttadam_dense_kernel(float* p, const float
   }
 }
 
-int launch_ttadam_dense(float* p, const float* g, float* m, float* v, int64_t n, float b1, float b2, float eps,
+int launch_ttadam_dense(float* p, const float* g, float* m, float* v, int64_t n, double b1, double b2, float eps,
                         float step_size, float lr_wd, int clamp_v, hipStream_t stream) {
   if (n <= 0) return SOW_OK;
   if (!p || !g || !m || !v) return SOW_ERR_NULL;
   int grid = (int)((n + 255) / 256);
   if (grid > 2048) grid = 2048;
-  hipLaunchKernelGGL(ttadam_dense_kernel, dim3(grid), dim3(256), 0, stream, p, g, m, v, n, b1, b2, eps, step_size, lr_wd, clamp_v);
+  hipLaunchKernelGGL(ttadam_dense_kernel, dim3(grid), dim3(256), 0, stream, p, g, m, v, n, (float)b1, (float)(1.0 - b1),
+                     (float)b2, (float)(1.0 - b2), eps, step_size, lr_wd, clamp_v);
   SOW_CHECK_LAUNCH();
   return SOW_OK;
 }

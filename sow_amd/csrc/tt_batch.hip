@@ -161,7 +161,7 @@ template <int MAXR> __global__ __launch_bounds__(256) void tt_adam_eval_kernel(c
         if (vv < 0.f) vv = 0.f;                          // ttadam.py:84
       }
       const float gv = b.g[it][row * b.ldg[it] + col];
-      mv = mv * b.b1 + gv * (1.f - b.b1);                // the arithmetic of ttadam_dense_kernel (misc.hip), same order
+      mv = mv * b.b1 + gv * (1.f - b.b1);                // ttadam_dense_kernel's order; 1 - b here in fp32
       vv = vv * b.b2 + gv * gv * (1.f - b.b2);
       float* pp = b.p[it] + row * b.ldp[it] + col;
       float pv = *pp + (mv / (sqrtf(vv) + b.eps)) * (-b.step_size[it]);

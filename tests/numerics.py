@@ -22,9 +22,12 @@ import math
 import torch
 
 # significand bits (implicit bit included) and unit roundoff u = 2^-p of round-to-nearest
-_P = {torch.bfloat16: 8, torch.float32: 24}
+_P = {torch.bfloat16: 8, torch.float32: 24, torch.float16: 11}
 UNIT_ROUNDOFF = {dt: 2.0 ** -p for dt, p in _P.items()}
-_EMIN = -126   # smallest normal exponent of both formats
+# smallest normal exponent: 2^-126 for bf16 and fp32, 2^-14 for f16 (whose subnormal spacing is 2^-24)
+_EMIN = {torch.bfloat16: -126, torch.float32: -126, torch.float16: -14}
+# largest finite f16: RNE takes |t| >= 65504 + 16 (half an ulp, the tie rounds to the even 2^16) to inf
+F16_MAX = 65504.0
 
 # LAMBDA of the probabilistic accumulation term.  A sum of n intermediates c_k, each rounded with relative error
 # |delta_k| <= u, errs by sum c_k delta_k: at most u * sqrt(n) * sqrt(sum c_k^2) (Cauchy-Schwarz), and for large n close to
@@ -54,10 +57,12 @@ def ref64(fn, *args, **kw):
 
 
 def ulp(t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
-    """Spacing of `dtype` (bf16 / fp32) at |t|, as float64: 2^(e - p) for |t| in [2^(e-1), 2^e); subnormal spacing below."""
+    """Spacing of `dtype` (bf16 / fp32 / f16) at |t|, as float64: 2^(e - p) for |t| in [2^(e-1), 2^e); subnormal spacing
+    below."""
     t = to64(t)
     _, e = torch.frexp(t.abs())
-    e = torch.where(t == 0, _EMIN + 1, torch.clamp(e, min=_EMIN + 1))
+    emin = _EMIN[dtype]
+    e = torch.where(t == 0, emin + 1, torch.clamp(e, min=emin + 1))
     return torch.ldexp(torch.ones_like(t), e - _P[dtype])
 
 
@@ -66,7 +71,10 @@ def rne(t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     returned as float64."""
     t = to64(t)
     q = ulp(t, dtype)
-    return torch.round(t / q) * q   # t / q and the product are exact (powers of two); torch.round is half-to-even
+    r = torch.round(t / q) * q   # t / q and the product are exact (powers of two); torch.round is half-to-even
+    if dtype == torch.float16:
+        r = torch.where(r.abs() > F16_MAX, torch.copysign(torch.full_like(r, float("inf")), r), r)
+    return r
 
 
 def accumulation_term(sq: torch.Tensor, u: float, n: int = 1, lam: float = LAMBDA) -> torch.Tensor:
@@ -139,7 +147,7 @@ def check_rounded(out: torch.Tensor, ref: torch.Tensor, dtype: torch.dtype, max_
     out64, ref = to64(out), to64(ref)
     assert out64.shape == ref.shape, f"{name}: shape {tuple(out64.shape)} vs reference {tuple(ref.shape)}"
     r = rne(ref, dtype)
-    err = (out64 - r).abs()
+    err = torch.where(out64 == r, torch.zeros_like(r), (out64 - r).abs())   # an f16 inf equal to RNE(ref) = inf: err 0
     lim = max_ulp * ulp(r, dtype)
     if acc is not None:
         lim = lim + to64(acc)
