@@ -199,3 +199,32 @@ def check_h_save(h: torch.Tensor, ref_live: torch.Tensor, r: int, dtype: torch.d
             i = int(torch.nonzero(bad)[0])
             raise NumericsError(f"{name}: column 63 is not 1.0 in {int(bad.sum())} rows (first row {i}: {float(ones[i])})")
     return stats
+
+
+def gemm_epilogue(prod: torch.Tensor, alpha: float, beta: float, c0=None, bias=None) -> torch.Tensor:
+    """The fp32 epilogue of sow_gemm (C = alpha * acc + beta * C0 + bias): three fp32 roundings, each at most u of the sum
+    of the operand magnitudes."""
+    t = abs(alpha) * to64(prod).abs()
+    if c0 is not None:
+        t = t + abs(beta) * to64(c0).abs()
+    if bias is not None:
+        t = t + to64(bias).abs()
+    return 3 * UNIT_ROUNDOFF[torch.float32] * t
+
+
+def gemm_f32_bound(ref: torch.Tensor, sq: torch.Tensor, prod: torch.Tensor, K: int, epi: torch.Tensor) -> torch.Tensor:
+    """fp32 sow_gemm (gemm_x3's 3 x bf16 split with six plane products, or the fp32 generic kernel): one fp32 ulp, the
+    accumulation term of K fp32 running sums (as chain3f's planes, test_numerics_cpu.py: mm3f) and the epilogue.  A running
+    sum errs by sum_k delta_k S_k over its partial sums S_k; those follow the drift of the result as well as the
+    fluctuation of the terms: S_k ~ (k / K) prod + noise, so sum_k S_k^2 <= K (sq + prod^2 / 3) up to the noise -- the
+    drift term matters for a large |prod| (a long generic fp32 chain: K = 730 at a 3-sigma element)."""
+    return bound(ref, torch.float32, accumulation_term(sq + to64(prod) ** 2 / 3, UNIT_ROUNDOFF[torch.float32], K), epi)
+
+
+def check_gaps(buf: torch.Tensor, live: torch.Tensor, sentinel: float, name: str = "out"):
+    """Every element of an output buffer outside the live view (guards, the ldc gaps of a strided C) still holds the
+    sentinel."""
+    bad = (buf != sentinel) & ~live
+    if bad.any():
+        i = int(torch.nonzero(bad.reshape(-1))[0])
+        raise NumericsError(f"{name}: {int(bad.sum())} elements outside the view overwritten (first at flat index {i})")

@@ -12,10 +12,12 @@ import pytest
 import torch
 
 from conftest import rel_err
-from numerics import (MAX_INEXACT, UNIT_ROUNDOFF, NumericsError, accumulation_term, bound, check_bound, check_h_save,
-                      check_rounded, fp32_floor, ref64, rne, ulp)
+import fuzz_plan as FP
+import test_gpu_elementwise as E
+from numerics import (MAX_INEXACT, UNIT_ROUNDOFF, NumericsError, accumulation_term, bound, check_bound, check_gaps,
+                      check_h_save, check_rounded, fp32_floor, gemm_epilogue, gemm_f32_bound, ref64, rne, ulp)
 
-BF16, F32 = torch.bfloat16, torch.float32
+BF16, F32, F16 = torch.bfloat16, torch.float32, torch.float16
 U16 = UNIT_ROUNDOFF[BF16]
 MARGIN = 0.7
 
@@ -282,8 +284,87 @@ def _fault_ones_column_at_r():
     return bad, h_save_of(ref, r), lambda o: check_h_save(o, ref, r, BF16)
 
 
+def _wide_bf16(T, d_in, d_out, r, seed, drop_from=None):
+    """A wide (r > 64) bf16 layer's weight gradients as skinny_tn_wide.hip forms them -- h [T, r] (unscaled x A, saved),
+    dh = RNE(s dY B^T), fp32 slab partials summed in slab order, one rounding -- with the tokens from `drop_from` on left
+    out (a lost last slab).  Returns (dB, its reference, its check)."""
+    g = torch.Generator().manual_seed(seed)
+    x, A, B = _data((T, d_in), BF16, g), _data((d_in, r), BF16, g, 0.05), _data((r, d_out), BF16, g, 0.05)
+    dy = _data((T, d_out), BF16, g)
+    h = rne(mm32(x, A), BF16)
+    _, ln = FP.tnw_pick_slabs(T, d_in, d_out)
+    stop = T if drop_from is None else drop_from
+    acc = torch.zeros(r, d_out, dtype=torch.float32)
+    for t0 in range(0, stop, ln):
+        t1 = min(t0 + ln, stop)
+        acc += mm32(h[t0:t1].t(), dy[t0:t1], block=64).float()
+    dB = rne(acc.double(), BF16)
+    ref = h.t() @ dy
+    return dB, ref, lambda o: check_rounded(o, ref, BF16, acc=fp32_floor((h * h).t() @ (dy * dy), T), name="dB")
+
+
+def _fault_tnw_last_slab():
+    T = next(t for t in range(8193, 12000) if t % FP.tnw_pick_slabs(t, 256, 264)[1] == 1)   # k * slab_len + 1
+    ns, ln = FP.tnw_pick_slabs(T, 256, 264)   # the last slab holds one token
+    assert T % ln == 1 and ns >= 2
+    out, ref, chk = _wide_bf16(T, 256, 264, 96, seed=11, drop_from=(ns - 1) * ln)
+    return out, ref, chk
+
+
+def _fault_chain3f_last_column(odd=True):
+    """fp32 forward at odd d_out (chain3f's predicated column tail): the last column keeps only the bias."""
+    T, d_in, d_out, r = 256, 128, 131, 24
+    g = torch.Generator().manual_seed(12)
+    x = torch.randn(T, d_in, generator=g).double()
+    A, B = (torch.randn(d_in, r, generator=g) * 0.05).double(), (torch.randn(r, d_out, generator=g) * 0.05).double()
+    bias = (torch.randn(d_out, generator=g) * 0.1).double()
+    h = (mm3f(x, A).float() * 0.5).double()
+    y = (mm3f(h, B).float() + bias.float()).double()
+    y[:, -1] = bias[-1].float().double()
+    ref = h @ B + bias
+    by = bound(ref, F32, accumulation_term((h * h) @ (B * B), UNIT_ROUNDOFF[F32], 64 + r))
+    return y, ref, lambda o: check_bound(o, ref, by, name="y")
+
+
+def _fault_gemm_spills_into_ldc_gap():
+    """A strided C (ldc > N) whose store writes one element past every row: the values of the view are right, the gap
+    guard (the GPU test's check_gaps over the whole buffer) rejects the store."""
+    M, N, K, ldc, sentinel = 64, 100, 48, 104, E.SENTINEL
+    g = torch.Generator().manual_seed(13)
+    a, b = _data((M, K), BF16, g), _data((K, N), BF16, g, 0.05)
+    ref = a @ b
+    buf = torch.full((M * ldc + 2 * E.GUARD,), sentinel, dtype=torch.float64)
+    live = torch.zeros(buf.numel(), dtype=torch.bool)
+    live[E.GUARD:E.GUARD + M * ldc].view(M, ldc)[:, :N] = True
+    rows = buf[E.GUARD:E.GUARD + M * ldc].view(M, ldc)
+    rows[:, :N + 1] = torch.cat([rne(mm32(a, b), BF16), rne(mm32(a, b), BF16)[:, -1:]], dim=1)   # one element too many
+    out = rows[:, :N].clone()
+
+    def chk(o):
+        check_rounded(o, ref, BF16, acc=fp32_floor((a * a) @ (b * b), K), name="C")
+        check_gaps(buf, live, sentinel, name="C buffer")
+    return out, ref, chk
+
+
+def _fault_f16_y_truncated():
+    """f16 y stored by dropping the low 13 bits of the fp32 sum instead of rounding to nearest even."""
+    g = torch.Generator().manual_seed(14)
+    T, d_in, d_out, r = 2048, 512, 264, 32
+    x, A, B = _data((T, d_in), F16, g), _data((d_in, r), F16, g, 0.05), _data((r, d_out), F16, g, 0.05)
+    bias = _data((d_out,), F16, g, 0.1)
+    h = rne(mm32(x, A), F16)
+    acc = (mm32(h, B) + bias).float()
+    y = (acc.view(torch.int32) & ~0x1FFF).view(torch.float32).to(F16).double()   # exact: the low 13 bits are gone
+    ref = h @ B + bias
+    return y, ref, lambda o: E._rounded(o, ref, F16, fp32_floor((h * h) @ (B * B), 64), "y")
+
+
 # id -> (builder, rel_err tolerance of today's tests, would rel_err have passed it)
 FAULTS = {
+    "tnw_dB_drops_last_slab_at_k_slab_len_plus_1": (_fault_tnw_last_slab, 2e-2, True),
+    "chain3f_y_drops_last_column_at_odd_d_out": (_fault_chain3f_last_column, 1e-5, False),
+    "gemm_store_spills_into_ldc_gap": (_fault_gemm_spills_into_ldc_gap, 2e-2, True),
+    "f16_y_truncated_instead_of_rne": (_fault_f16_y_truncated, 2e-2, True),
     "dA_drops_last_token_T8193": (lambda: _fault_drop_last_token(8193, "dA"), 2e-2, True),
     "dB_drops_last_token_T8193": (lambda: _fault_drop_last_token(8193, "dB"), 2e-2, True),
     "dbias_drops_last_token_T8193": (lambda: _fault_drop_last_token(8193, "dbias"), 2e-2, True),
@@ -309,3 +390,91 @@ def test_fault_is_rejected(fault):
           f"{'PASSES' if passes_rel_err else 'fails'} today's {tol:g}")
     # the documented gap: which faults the max-norm tolerance alone lets through
     assert passes_rel_err == rel_err_blind, (fault, rel_err(out, ref))
+
+
+# ---- bounds added with the random sweep (tests/test_gpu_fuzz_elementwise.py) ------------------------------------------
+def _emulate_f16_layer(T, d_in, d_out, r, s, seed, save_h=True):
+    """An f16 layer as chain2_f16 / the f16 skinny-TN kernels compute it (fp32 sums of 64-wide blocks, one RNE_f16 per
+    stored value), in the output layout of tests/test_gpu_elementwise._run_single."""
+    g = torch.Generator().manual_seed(seed)
+    x, A, B = _data((T, d_in), F16, g), _data((d_in, r), F16, g, 0.05), _data((r, d_out), F16, g, 0.05)
+    bias, dy = _data((d_out,), F16, g, 0.1), _data((T, d_out), F16, g)
+    h = rne(mm32(x, A) * s, F16)
+    y = rne((mm32(h, B) + bias).float().double(), F16)
+    dh = rne(mm32(dy, B.t()) * s, F16)
+    dx = rne(mm32(dh, A.t()), F16)
+    dA, dB = rne(mm32(x.t(), dh), F16), rne(mm32(h.t(), dy), F16)
+    dbias = rne(mm32(torch.ones(1, T, dtype=torch.float64), dy).flatten(), F16)
+    data = dict(x=x, A=A, B=B, bias=bias, dy=dy)
+    out = dict(y=y, h=h_save_of(h, r) if save_h else None)
+    if save_h:
+        out.update(dx=dx, dA=dA, dB=dB, dbias=dbias)
+    return data, out
+
+
+@pytest.mark.parametrize("T,d_in,d_out,r,s,save_h", [(4097, 256, 264, 50, 0.5, True), (8193, 512, 136, 16, 2.0, True),
+                                                      (65, 1000, 264, 63, 1.0, True), (4097, 256, 264, 50, 0.5, False)])
+def test_f16_emulation_passes_elementwise_check_with_margin(T, d_in, d_out, r, s, save_h):
+    """The f16 limits of test_gpu_elementwise._check (subnormal floor of hidden roundings, the inexact share of _rounded)
+    pass an emulation of the f16 kernels with margin."""
+    data, out = _emulate_f16_layer(T, d_in, d_out, r, s, seed=T + r, save_h=save_h)
+    c = E.Case(f"emu_f16_T{T}_r{r}_{save_h}", F16, T, d_in, d_out, r, s=s, save_h=save_h)
+    E._check(c, {k: v.to(F16) for k, v in data.items()}, out)
+    st = {stage: v for (name, stage), v in E.WORST.items() if name == c.name}
+    print(c.name, {k: (round(w, 3), None if i is None else round(100 * i, 4)) for k, (w, i) in st.items()})
+    for stage, (w, inexact) in st.items():
+        if inexact is None:
+            assert w <= MARGIN, (stage, w)
+        else:   # within one ulp everywhere, and off RNE(ref64) in at most 0.7 of the share _rounded allows
+            assert w <= 1 and inexact <= MARGIN * E.ALLOWED[(c.name, stage)], (stage, w, inexact, E.ALLOWED[(c.name, stage)])
+
+
+def mm3f_gemm(a, b, block=32):
+    """gemm_x3.hip: a . b with both operands split into three truncated bf16 planes, six plane products, fp32 sums of
+    32-wide K tiles."""
+    pa, pb = split3(a), split3(b)
+    acc = torch.zeros(a.shape[0], b.shape[1], dtype=torch.float32)
+    for k0 in range(0, a.shape[1], block):
+        s = sum(pa[i][:, k0:k0 + block] @ pb[j][k0:k0 + block] for i in range(3) for j in range(3) if i + j <= 2)
+        acc += s.float()
+    return acc
+
+
+@pytest.mark.parametrize("M,N,K,alpha,beta", [(256, 264, 2048, 1.0, 0.0), (128, 100, 300, -2.0, 0.5), (64, 72, 17, 0.5, 1.0)])
+def test_gemm_x3_emulation_passes_with_margin(M, N, K, alpha, beta):
+    """The fp32 sow_gemm bound (numerics.gemm_f32_bound) against an emulation of gemm_x3 with its fp32 epilogue."""
+    g = torch.Generator().manual_seed(M + K)
+    a, b = torch.randn(M, K, generator=g).double(), (torch.randn(K, N, generator=g) * 0.05).double()
+    a, b = a.float().double(), b.float().double()
+    c0 = torch.randn(M, N, generator=g).float().double()
+    bias = (torch.randn(N, generator=g) * 0.1).float().double()
+    acc = mm3f_gemm(a, b)
+    out = (torch.tensor(alpha, dtype=torch.float32) * acc + torch.tensor(beta, dtype=torch.float32) * c0.float()
+           + bias.float()).double()
+    prod = a @ b
+    ref = alpha * prod + beta * c0 + bias
+    sq = alpha ** 2 * ((a * a) @ (b * b))
+    w = check_bound(out, ref, gemm_f32_bound(ref, sq, alpha * prod, K, gemm_epilogue(prod, alpha, beta, c0, bias)), name="C")["worst"]
+    print(f"gemm_x3 {M}x{N}x{K} alpha {alpha} beta {beta}: worst err/bound {w:.3f}")
+    assert w <= MARGIN
+
+
+def test_fp32_cancelled_dh_emulation_passes_with_margin():
+    """The fp32 dA / dX bound of test_gpu_elementwise._check with the error of the fp32 dh sum: an emulation of the generic
+    fp32 backward (dh = s dY B^T summed in fp32, dX = dh A^T, dA = x^T dh in fp32) at the sweep's r = 1, d_out = 80 layer,
+    where dh cancels to ~1/1000 of its terms in many rows, passes with margin."""
+    T, d_in, d_out, r, s = 4618, 304, 80, 1, 2.0
+    g = torch.Generator().manual_seed(15)
+    x = torch.randn(T, d_in, generator=g).float()
+    A, B = (torch.randn(d_in, r, generator=g) * 0.05).float(), (torch.randn(r, d_out, generator=g) * 0.05).float()
+    dy = torch.randn(T, d_out, generator=g).float()
+    h = (x @ A) * s
+    y = h @ B
+    dh = (dy @ B.t()) * s
+    out = dict(y=y.double(), h=h_save_of(h.double(), r), dx=(dh @ A.t()).double(), dA=(x.t() @ dh).double(),
+               dB=(h.t() @ dy).double(), dbias=None)
+    c = E.Case("emu_f32_r1_dout80", F32, T, d_in, d_out, r, bias=False, s=s)
+    E._check(c, dict(x=x, A=A, B=B, bias=None, dy=dy), out)
+    st = {stage: w for (name, stage), (w, _) in E.WORST.items() if name == c.name}
+    print(c.name, {k: round(w, 3) for k, w in st.items()})
+    assert max(st.values()) <= MARGIN, st
