@@ -313,8 +313,9 @@ int sow_tt_kron_core(const float* A, const float* B, float* out, int ra0, int rb
  *   sow_ttadam_batch          TTAdam.step (ttadam.py:68-115) for n parameters: reconstruct m and v, clamp v < 0, Adam
  *                             update of the parameter (+ the decoupled weight-decay line :110-111), re-decompose both
  *                             moments into the cores given (in place over the old ones); has_state = 0 on the first step
- *                             (m = v = 0).  step_size already carries the bias correction of :95-100.  Workspace per
- *                             item: sow_ttadam_workspace_bytes(&item.m). */
+ *                             (m = v = 0).  step_size already carries the bias correction of :95-100.  The betas are
+ *                             double: 1 - beta is formed in double and rounded to fp32 once, as sow_ttadam_dense
+ *                             does.  Workspace per item: sow_ttadam_workspace_bytes(&item.m). */
 #define SOW_TT_MAX_ORDER 6
 typedef struct sow_tt_desc {
   void* cores[SOW_TT_MAX_ORDER];
@@ -339,7 +340,7 @@ size_t sow_ttadam_workspace_bytes(const sow_tt_desc* tt);
 int sow_tt_reconstruct_batch(const sow_tt_desc* tts, void* const* out, const int64_t* ld_out, int n, void* stream);
 int sow_tt_decompose_batch(const sow_tt_desc* tts, const void* const* mats, const int64_t* ld, int n, void* const* workspaces,
                            const size_t* workspace_bytes, void* stream);
-int sow_ttadam_batch(const sow_ttadam_item* items, int n, float beta1, float beta2, float eps, void* stream);
+int sow_ttadam_batch(const sow_ttadam_item* items, int n, double beta1, double beta2, float eps, void* stream);
 
 /* out[0] = max |x[i]| over n fp32 elements (TensorTrain.sqrt / sqrtinv scaling, tt.py:288, 322).  NaN elements are
  * skipped (fmaxf): the result is the max over the others (0 when all are NaN), where torch.amax would return NaN. */

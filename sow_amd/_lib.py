@@ -104,7 +104,7 @@ SIGNATURES = {
     "sow_tt_reconstruct_batch": (c_int, [POINTER(TtDesc), POINTER(c_void_p), POINTER(c_int64), c_int, c_void_p]),
     "sow_tt_decompose_batch": (c_int, [POINTER(TtDesc), POINTER(c_void_p), POINTER(c_int64), c_int, POINTER(c_void_p),
                                        POINTER(c_size_t), c_void_p]),
-    "sow_ttadam_batch": (c_int, [POINTER(TtAdamItem), c_int, c_float, c_float, c_float, c_void_p]),
+    "sow_ttadam_batch": (c_int, [POINTER(TtAdamItem), c_int, c_double, c_double, c_float, c_void_p]),
     "sow_absmax": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "sow_small_inverse": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "sow_axpby": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_float, c_int, c_void_p]),

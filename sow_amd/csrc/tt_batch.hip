@@ -139,7 +139,7 @@ struct AdamBatch {
   float *Lm[TT_PER], *Lv[TT_PER];       // first unfoldings (padded, interleaved) of the new moments
   float step_size[TT_PER], lr_wd[TT_PER];
   int has_state[TT_PER];
-  float b1, b2, eps;
+  float b1, c1, b2, c2, eps;   // c = 1 - beta, formed in double on the host (as launch_ttadam_dense)
   int n;
 };
 
@@ -161,8 +161,8 @@ template <int MAXR> __global__ __launch_bounds__(256) void tt_adam_eval_kernel(c
         if (vv < 0.f) vv = 0.f;                          // ttadam.py:84
       }
       const float gv = b.g[it][row * b.ldg[it] + col];
-      mv = mv * b.b1 + gv * (1.f - b.b1);                // ttadam_dense_kernel's order; 1 - b here in fp32
-      vv = vv * b.b2 + gv * gv * (1.f - b.b2);
+      mv = mv * b.b1 + gv * b.c1;                        // ttadam_dense_kernel's order and its host-formed 1 - b
+      vv = vv * b.b2 + gv * gv * b.c2;
       float* pp = b.p[it] + row * b.ldp[it] + col;
       float pv = *pp + (mv / (sqrtf(vv) + b.eps)) * (-b.step_size[it]);
       if (b.lr_wd[it] > 0.f) pv = pv + pv * (-b.lr_wd[it]);
@@ -480,7 +480,7 @@ size_t sow_ttadam_workspace_bytes(const sow_tt_desc* tt) {
   return 2 * (tt_ws_plan(*tt).total + 256);
 }
 
-int sow_ttadam_batch(const sow_ttadam_item* items, int n, float beta1, float beta2, float eps, void* stream_) {
+int sow_ttadam_batch(const sow_ttadam_item* items, int n, double beta1, double beta2, float eps, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (n < 0) return SOW_ERR_SHAPE;
   if (n == 0) return SOW_OK;
@@ -498,7 +498,7 @@ int sow_ttadam_batch(const sow_ttadam_item* items, int n, float beta1, float bet
   for (int base = 0; base < n; base += TT_PER) {
     AdamBatch b{};
     b.n = n - base < TT_PER ? n - base : TT_PER;
-    b.b1 = beta1, b.b2 = beta2, b.eps = eps;
+    b.b1 = (float)beta1, b.c1 = (float)(1.0 - beta1), b.b2 = (float)beta2, b.c2 = (float)(1.0 - beta2), b.eps = eps;
     sow_tt_desc tts[2 * TT_PER];
     char* ws[2 * TT_PER];
     int64_t max_p = 0;

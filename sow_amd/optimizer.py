@@ -78,8 +78,7 @@ class TTAdam(torch.optim.Optimizer):
             by_dev.setdefault(k[0].device, []).append((it, k))
         for dev, lst in by_dev.items():
             arr = (_lib.TtAdamItem * len(lst))(*[it for it, _ in lst])
-            ops._launch(dev, "sow_ttadam_batch", lib.sow_ttadam_batch, arr, len(lst), float(beta1), float(beta2),
-                        float(group["eps"]))
+            ops._launch(dev, "sow_ttadam_batch", lib.sow_ttadam_batch, arr, len(lst), beta1, beta2, group["eps"])
             for _, (p, _, _, tm, tv, step) in lst:
                 st = self.state[p]
                 st["step"], st["exp_avg"], st["exp_avg_sq"] = step, tm, tv
