@@ -21,6 +21,26 @@
  *   - f16 numerics: every product accumulates in fp32 and each output element is rounded once, to nearest even, to f16;
  *     a result beyond +-65504 becomes +-inf (IEEE rounding, as torch's f16 matmul; no saturation); subnormal outputs are
  *     kept, not flushed; h_save has the bf16 layout (scale * x . A, 64 columns, column 63 = 1.0 when free);
+ *   - exact arithmetic: products are exact and every sum is accumulated in fp32, so where the terms of every sum are
+ *     multiples of one unit and sum |terms| stays below 2^24 units (and what is stored on the way -- h_save, the internal
+ *     dh, the first product of a two-pass accumulator path -- is representable), each output is the correctly rounded exact
+ *     result whatever the slab, K-split or sibling order.  SOW_DTYPE_F32 on the 3 x bf16 split: the same holds when one
+ *     factor of every product has at most 8 significant bits (the six plane products kept are then the whole product);
+ *   - powers of two: scaling x, A, B, dy (and the accumulator, bias and accumulated-onto gradients to match) by powers of
+ *     two shifts every output by the sum of the exponents, bit for bit, as long as operands, stored intermediates and
+ *     outputs stay in the normal range of the dtype and no non-zero term of a sum is below 2^-103 (fp32 on the split:
+ *     2^-72);
+ *   - non-finite values: a NaN or Inf inside x, dy or A makes non-finite exactly the output elements IEEE arithmetic makes
+ *     non-finite (the row of y and h_save and the rows of dA of a poisoned token of x, ...); every other element is
+ *     bit-identical to the run without it: zero padding never multiplies data of another token, layer or sibling.  bf16 /
+ *     f16: an Inf that no other Inf cancels comes out as that Inf.  SOW_DTYPE_F32 on the 3 x bf16 split: an Inf operand
+ *     yields NaN (the residual planes are Inf - Inf): only the set of non-finite elements is specified.  One exception: the kernels read a row of A
+ *     together with the up to 64 elements that follow it in storage, against explicit zeros of dh, so a non-finite
+ *     A[i, j] -- which makes all of y non-finite anyway -- may also make non-finite the columns i' < i of dx whose
+ *     64-element window reaches it, (i - i') * r_live + j < 64, where IEEE arithmetic touches column i only;
+ *   - subnormal operands are read at their value (the bf16 and f16 matrix pipe of gfx950 does not flush them; observed on
+ *     every chain path), and subnormal outputs are kept.  SOW_DTYPE_F32 on the 3 x bf16 split: an fp32 value below 2^-110 may
+ *     lose its mid / lo planes, which fall below the bf16 range -- an error of at most |x_k| |a_k| per such term;
  *   - `stream` is a hipStream_t passed as void* (0 = default stream); kernels are
  *     enqueued on it, so the calls are capturable into a hipGraph;
  *   - n_iter > 1 is presented as concatenated factors A = [A_1 .. A_n] ([d_in, n*r]),

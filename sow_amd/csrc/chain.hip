@@ -264,7 +264,9 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainParams p) {
     for (int reg = 0; reg < 16; ++reg) {
       const int row = wm * 32 + acc_row(reg, lane);
       const float hu = hacc[reg];
-      const float hsc = hu * cs;
+      // rank columns >= rtot meet zero rows of F2 in phase 2; their own sums are x . 0, which is NaN where x holds an Inf or
+      // a NaN, and NaN . 0 would turn a row of +-Inf into NaN: they are zeroed here, as in the saved copy
+      const float hsc = live ? hu * cs : 0.f;
       if constexpr (F32)
         ((float*)Hs)[row * (CH_RP + 1) + c] = hsc;
       else
@@ -272,7 +274,7 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainParams p) {
       if (Hsave && m0 + row < p.M) {
         // live columns, zero padding, and 1.0 in column 63 (when free): the skinny-TN kernel turns that
         // column into the column sums of its other operand (dbias) at no cost
-        float sv = live ? hsc : 0.f;  // saved SCALED (fwd: s*x.A, so dB = hsave^T dY needs no further scale)
+        float sv = hsc;  // saved SCALED (fwd: s*x.A, so dB = hsave^T dY needs no further scale)
         if (c == CH_RP - 1 && rtot < CH_RP) sv = 1.f;
         Hsave[(m0 + row) * CH_RP + hc] = from_f32<T>(sv);
       }

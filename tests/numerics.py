@@ -124,7 +124,9 @@ def _tail_note(over: torch.Tensor) -> str:
 
 
 def _report(name: str, err: torch.Tensor, lim: torch.Tensor, out64: torch.Tensor, ref: torch.Tensor, what: str):
-    ratio = torch.where(torch.isnan(err), torch.full_like(err, math.inf), err / lim)
+    # err = 0 is within any limit, a limit of 0 included (max_ulp = 0: 0 / 0 is not "over"); err > 0 over a limit of 0 is inf
+    ratio = torch.where(err == 0, torch.zeros_like(err), err / lim)
+    ratio = torch.where(torch.isnan(err) | torch.isnan(ratio), torch.full_like(err, math.inf), ratio)
     flat = int(torch.argmax(ratio.reshape(-1)))
     idx = tuple(int(i) for i in torch.unravel_index(torch.tensor(flat), ratio.shape)) if ratio.dim() else ()
     over = ratio > 1
@@ -143,7 +145,8 @@ def check_rounded(out: torch.Tensor, ref: torch.Tensor, dtype: torch.dtype, max_
     max(max_inexact * numel, min_count) elements (min_count: a handful of rare tie-crossings in a small tensor).
     `acc`: the fp32 accumulation noise of the kernel's sums (accumulation_term(sq, 2^-24, K)), added to the limit -- it
     matters only where the sum cancels to far below its terms, where one ulp of the result is below fp32's resolution of
-    the terms.  Returns the statistics (worst ratio, inexact fraction)."""
+    the terms.  max_ulp = 0, max_inexact = 0, min_count = 0 means bit-exact: every element equal to RNE_dtype(ref), the
+    first one that is not named in the error.  Returns the statistics (worst ratio, inexact fraction)."""
     out64, ref = to64(out), to64(ref)
     assert out64.shape == ref.shape, f"{name}: shape {tuple(out64.shape)} vs reference {tuple(ref.shape)}"
     r = rne(ref, dtype)

@@ -508,12 +508,23 @@ GEMMS = [
 
 @pytest.mark.parametrize("name,M,N,K,has_bias,beta,use_ws", GEMMS, ids=[g[0] for g in GEMMS])
 def test_gemm_path(name, M, N, K, has_bias, beta, use_ws):
-    lib = _lib.load()
     g = torch.Generator().manual_seed(M + N + K)
     a = torch.randn(M, K, generator=g).bfloat16()
     b = (torch.randn(K, N, generator=g) * 0.05).bfloat16()
     bias = (torch.randn(N, generator=g) * 0.1).bfloat16() if has_bias else None
     c0 = torch.randn(M, N, generator=g).bfloat16() if beta else None
+    out = _run_gemm(name, a, b, bias, c0, beta, use_ws)
+    a64, b64 = to64(a), to64(b)
+    ref = a64 @ b64 + (to64(bias) if has_bias else 0) + (beta * to64(c0) if beta else 0)
+    st = check_rounded(out, ref, BF16, acc=fp32_floor((a64 * a64) @ (b64 * b64), K), name=name)
+    WORST[(name, "C")] = (st["worst"], st["inexact"])
+
+
+def _run_gemm(name, a, b, bias, c0, beta, use_ws):
+    """bf16 sow_gemm_ex C = a b + beta C0 + bias on the given operands (a [M, K], b [K, N], bias [N] or None, C0 [M, N] or
+    None): three bit-identical runs with intact guards; C of the first on the CPU."""
+    lib = _lib.load()
+    (M, K), N = a.shape, b.shape[1]
     ar = Arena(BF16)
     A, B, Bi = ar.input(a), ar.input(b), ar.input(bias)
     C = ar.output((M, N), c0)
@@ -528,10 +539,7 @@ def test_gemm_path(name, M, N, K, has_bias, beta, use_ws):
         ar.check_guards(f"{name} run {len(runs)}")
         runs.append(C.clone())
     assert torch.equal(_bits(runs[0]), _bits(runs[1])) and torch.equal(_bits(runs[0]), _bits(runs[2]))
-    a64, b64 = to64(a), to64(b)
-    ref = a64 @ b64 + (to64(bias) if has_bias else 0) + (beta * to64(c0) if beta else 0)
-    st = check_rounded(runs[0].cpu(), ref, BF16, acc=fp32_floor((a64 * a64) @ (b64 * b64), K), name=name)
-    WORST[(name, "C")] = (st["worst"], st["inexact"])
+    return runs[0].cpu()
 
 
 def test_zz_report_worst_ratios():

@@ -146,11 +146,25 @@ def test_fuzz_layer(c):
 # ---------------------------------------------------------------------------------------------------------------- groups
 @pytest.mark.parametrize("gp", PLAN.groups, ids=lambda g: g.name)
 def test_fuzz_group(gp):
+    layers = [_to_case(c, "once", "once", name=f"{gp.name}.{c.name}") for c in gp.layers]
+    data = [E._inputs(c) for c in layers]
+    outs, seq = run_group(gp, layers, data)
+    labels = _labels(seq)
+    try:
+        for i, c in enumerate(layers):
+            E._check(c, data[i], outs[i])
+    finally:
+        ws = [w for w in (_case_worst(c.name) for c in layers) if w is not None]
+        _note(gp.name, labels, max(ws) if ws else None)
+
+
+def run_group(gp, layers, data):
+    """The grouped forward and backward of `layers` (test_gpu_elementwise.Case) on the operands `data` (one dict per layer,
+    as E._inputs gives): three runs (poisoned, zeroed, poisoned) that must be bit-identical, guards intact, the row-owner
+    plan as the trace shows it.  Returns (outputs of the first run per layer, on the CPU; kernel names of the third)."""
     lib = _lib.load()
     dtype = DT[gp.layers[0].dtype]
     dt = E._dt(dtype)
-    layers = [_to_case(c, "once", "once", name=f"{gp.name}.{c.name}") for c in gp.layers]
-    data = [E._inputs(c) for c in layers]
     ar = E.Arena(dtype)
     arr = (_lib.LayerArgs * len(layers))()
     bufs = []
@@ -209,49 +223,16 @@ def test_fuzz_group(gp):
             if runs[0][i][k] is not None:
                 assert torch.equal(E._bits(runs[0][i][k]), E._bits(runs[1][i][k])), f"{c.name}: {k} differs on zeroed memory"
                 assert torch.equal(E._bits(runs[0][i][k]), E._bits(runs[2][i][k])), f"{c.name}: {k} differs on a repeat"
-    labels = _labels(seq)
-    try:
-        for i, c in enumerate(layers):
-            E._check(c, data[i], {k: (None if v is None else v.cpu()) for k, v in runs[0][i].items()})
-    finally:
-        ws = [w for w in (_case_worst(c.name) for c in layers) if w is not None]
-        _note(gp.name, labels, max(ws) if ws else None)
+    return [{k: (None if v is None else v.cpu()) for k, v in runs[0][i].items()} for i in range(n)], seq
 
 
 # ---------------------------------------------------------------------------------------------------------------- shared
 @pytest.mark.parametrize("sp", PLAN.shared, ids=lambda s: s.name)
 def test_fuzz_shared(sp):
-    lib = _lib.load()
     dtype = DT[sp.dtype]
-    st = S.Set(sp.name, dtype, sp.T, sp.d_in, [S.Sib(sb.d_out, sb.r, sb.bias, sb.s) for sb in sp.sibs], grad_beta=sp.grad_beta)
+    st = shared_set(sp)
     x, per, dx0 = S._data(st, seed=FP.SEED % 1000)
-    b = S.Bound(st, x, per, dx0)
-    n, dt = len(st.sibs), S._dt(dtype)
-    sh = b.sets["shared"]
-
-    def step():
-        _lib.check(lib.sow_forward_shared(b.args("shared"), n, dt, E._stream()), "sow_forward_shared")
-        _lib.check(lib.sow_backward_shared(b.args("shared"), n, dt, _lib.BWD_DATA | _lib.BWD_WEIGHTS, E._stream()),
-                   "sow_backward_shared")
-
-    keys = ("y", "h", "dA", "dB", "dbias")
-    runs = []
-    seq = []
-    for byte in (0xFF, 0x00, 0xFF):
-        b.ar.fill(byte)
-        if len(runs) == 2:
-            seq = E._kernel_seq(step)
-        else:
-            step()
-        b.ar.check_guards(f"{sp.name} run {len(runs)}")
-        runs.append(([{k: (None if o[k] is None else o[k].clone()) for k in keys} for o in sh], sh[0]["dx"].clone()))
-    for i in (1, 2):
-        assert torch.equal(E._bits(runs[0][1]), E._bits(runs[i][1])), f"{sp.name}: dX differs between runs"
-        for j in range(n):
-            for k in keys:
-                if runs[0][0][j][k] is not None:
-                    assert torch.equal(E._bits(runs[0][0][j][k]), E._bits(runs[i][0][j][k])), f"{sp.name}: {k} of sibling {j}"
-    assert _has(seq, "chain2_shared_kernel"), f"{sp.name}: the trace holds {sorted(set(seq))}"
+    b, runs, seq = run_shared(st, x, per, dx0)
     labels = _labels(seq)
     names = []
     try:
@@ -272,6 +253,47 @@ def test_fuzz_shared(sp):
         _note(sp.name, labels, max(ws) if ws else None)
 
 
+def shared_set(sp):
+    return S.Set(sp.name, DT[sp.dtype], sp.T, sp.d_in, [S.Sib(sb.d_out, sb.r, sb.bias, sb.s) for sb in sp.sibs],
+                 grad_beta=sp.grad_beta)
+
+
+def run_shared(st, x, per, dx0):
+    """sow_forward_shared + sow_backward_shared of the sibling set `st` on the operands x, per (one dict of A, B, bias, dy
+    per sibling) and dx0 (as test_gpu_shared_input._data gives): three bit-identical runs, guards intact, the shared
+    kernel in the trace.  Returns (the bound buffers, the runs: ([per-sibling outputs], dX), kernel names of the third)."""
+    lib = _lib.load()
+    dtype = st.dtype
+    b = S.Bound(st, x, per, dx0)
+    n, dt = len(st.sibs), S._dt(dtype)
+    sh = b.sets["shared"]
+
+    def step():
+        _lib.check(lib.sow_forward_shared(b.args("shared"), n, dt, E._stream()), "sow_forward_shared")
+        _lib.check(lib.sow_backward_shared(b.args("shared"), n, dt, _lib.BWD_DATA | _lib.BWD_WEIGHTS, E._stream()),
+                   "sow_backward_shared")
+
+    keys = ("y", "h", "dA", "dB", "dbias")
+    runs = []
+    seq = []
+    for byte in (0xFF, 0x00, 0xFF):
+        b.ar.fill(byte)
+        if len(runs) == 2:
+            seq = E._kernel_seq(step)
+        else:
+            step()
+        b.ar.check_guards(f"{st.name} run {len(runs)}")
+        runs.append(([{k: (None if o[k] is None else o[k].clone()) for k in keys} for o in sh], sh[0]["dx"].clone()))
+    for i in (1, 2):
+        assert torch.equal(E._bits(runs[0][1]), E._bits(runs[i][1])), f"{st.name}: dX differs between runs"
+        for j in range(n):
+            for k in keys:
+                if runs[0][0][j][k] is not None:
+                    assert torch.equal(E._bits(runs[0][0][j][k]), E._bits(runs[i][0][j][k])), f"{st.name}: {k} of sibling {j}"
+    assert _has(seq, "chain2_shared_kernel"), f"{st.name}: the trace holds {sorted(set(seq))}"
+    return b, runs, seq
+
+
 # ---------------------------------------------------------------------------------------------------------------- gemm
 def _strided_input(vals, ld, dtype):
     """[rows, cols] values in a [rows, ld] buffer whose gaps and guards hold NaN."""
@@ -284,15 +306,38 @@ def _strided_input(vals, ld, dtype):
 
 @pytest.mark.parametrize("gm", PLAN.gemms, ids=lambda g: g.name)
 def test_fuzz_gemm(gm):
-    lib = _lib.load()
     dtype = DT[gm.dtype]
-    dt = E._dt(dtype)
     g = torch.Generator().manual_seed(5000 + gm.seed)
     M, N, K = gm.M, gm.N, gm.K
     a = torch.randn(M, K, generator=g).to(dtype)               # op(A)
     bm = (torch.randn(K, N, generator=g) * 0.05).to(dtype)     # op(B)
     bias = (torch.randn(N, generator=g) * 0.1).to(dtype) if gm.bias else None
     c0 = torch.randn(M, N, generator=g).to(dtype) if gm.beta else None
+    out, seq = run_gemm(gm, a, bm, bias, c0)
+    a64, b64 = to64(a), to64(bm)
+    prod = a64 @ b64
+    ref = gm.alpha * prod + (to64(bias) if bias is not None else 0) + (gm.beta * to64(c0) if c0 is not None else 0)
+    sq = gm.alpha ** 2 * ((a64 * a64) @ (b64 * b64))
+    epi = gemm_epilogue(prod, gm.alpha, gm.beta, c0 if gm.beta else None, bias)
+    try:
+        if dtype == torch.float32:
+            st = check_bound(out, ref, gemm_f32_bound(ref, sq, gm.alpha * prod, K, epi), name=gm.name)
+            E.WORST[(gm.name, "C")] = (st["worst"], None)
+        else:
+            st = E._rounded(out, ref, dtype, fp32_floor(sq, K) + epi, gm.name)
+            E.WORST[(gm.name, "C")] = (st["worst"], st["inexact"])
+    finally:
+        _note(gm.name, _labels(seq), _case_worst(gm.name))
+
+
+def run_gemm(gm, a, bm, bias, c0):
+    """sow_gemm_ex of the case `gm` on the operands op(A) = a [M, K], op(B) = bm [K, N], bias [N] or None and C0 [M, N] or
+    None (tensors of the case's dtype): strided NaN-gapped inputs, a sentinel-gapped C, three bit-identical runs, the
+    targeted kernel in the trace.  Returns (C of the first run on the CPU, kernel names of the third)."""
+    lib = _lib.load()
+    dtype = DT[gm.dtype]
+    dt = E._dt(dtype)
+    M, N, K = gm.M, gm.N, gm.K
     _, A = _strided_input(a.t() if gm.trans_a else a, gm.lda, dtype)
     _, B = _strided_input(bm.t() if gm.trans_b else bm, gm.ldb, dtype)
     ar = E.Arena(dtype)
@@ -328,20 +373,7 @@ def test_fuzz_gemm(gm):
     assert torch.equal(E._bits(runs[0]), E._bits(runs[1])) and torch.equal(E._bits(runs[0]), E._bits(runs[2])), \
         f"{gm.name}: runs differ"
     assert _has(seq, gm.family), f"{gm.name}: targets {gm.family}, the trace holds {sorted(set(seq))}"
-    a64, b64 = to64(a), to64(bm)
-    prod = a64 @ b64
-    ref = gm.alpha * prod + (to64(bias) if bias is not None else 0) + (gm.beta * to64(c0) if c0 is not None else 0)
-    sq = gm.alpha ** 2 * ((a64 * a64) @ (b64 * b64))
-    epi = gemm_epilogue(prod, gm.alpha, gm.beta, c0 if gm.beta else None, bias)
-    try:
-        if dtype == torch.float32:
-            st = check_bound(runs[0].cpu(), ref, gemm_f32_bound(ref, sq, gm.alpha * prod, K, epi), name=gm.name)
-            E.WORST[(gm.name, "C")] = (st["worst"], None)
-        else:
-            st = E._rounded(runs[0].cpu(), ref, dtype, fp32_floor(sq, K) + epi, gm.name)
-            E.WORST[(gm.name, "C")] = (st["worst"], st["inexact"])
-    finally:
-        _note(gm.name, _labels(seq), _case_worst(gm.name))
+    return runs[0].cpu(), seq
 
 
 # ---------------------------------------------------------------------------------------------------------------- coverage

@@ -478,3 +478,63 @@ def test_fp32_cancelled_dh_emulation_passes_with_margin():
     st = {stage: w for (name, stage), (w, _) in E.WORST.items() if name == c.name}
     print(c.name, {k: round(w, 3) for k, w in st.items()})
     assert max(st.values()) <= MARGIN, st
+
+
+# ---- bit-exact checks on exact operands (tests/value_plan.py) ---------------------------------------------------------
+def test_zero_tolerance_means_bit_exact_and_names_the_worst_element():
+    g = torch.Generator().manual_seed(3)
+    ref = torch.randint(-300, 300, (40, 70), generator=g).double() * 0.5
+    out = rne(ref, BF16)
+    st = check_rounded(out, ref, BF16, max_ulp=0, max_inexact=0, min_count=0, name="exact")
+    assert st["worst"] == 0.0 and st["inexact"] == 0.0 and st["over"] == 0
+    bad = out.clone()
+    bad[3, 5] += float(ulp(bad[3:4, 5], BF16))
+    with pytest.raises(NumericsError, match=r"worst element \(3, 5\) err/limit = inf.*1 of 2800 elements over the limit"):
+        check_rounded(bad, ref, BF16, max_ulp=0, max_inexact=0, min_count=0, name="exact")
+    check_rounded(bad, ref, BF16, name="default")           # one ulp in one element: within the default limits
+    nan = out.clone()
+    nan[0, 0] = float("nan")
+    with pytest.raises(NumericsError, match=r"worst element \(0, 0\)"):
+        check_rounded(nan, ref, BF16, max_ulp=0, max_inexact=0, min_count=0, name="exact")
+
+
+def test_one_token_in_32768_is_caught_only_on_exact_operands():
+    """One token dropped from one column of dB (T = 32768), for eight columns in turn.  On Gaussian operands the fault
+    moves an element by a fraction of an ulp unless the element happens to be small: some of the eight faulty dB pass the
+    limits of check_rounded (rounding noise moves more elements than the fault does).  On the exact operands of
+    value_plan.exact_layer the kernels' arithmetic (emulate_bf16) is exact, the zero-tolerance check passes, and every one
+    of the eight faults fails it."""
+    import value_plan as V
+    T, d_in, d_out, r, s = 32768, 64, 64, 8, 0.5
+    cols = range(0, 64, 8)
+
+    def faulty_dB(h_live, dy, t0, col):
+        dropped = dy.clone()
+        dropped[t0, col] = 0
+        return rne(mm32(h_live.t(), dropped), BF16)
+
+    x, A, B, bias, dy, _ = _layer_inputs(T, d_in, d_out, r, 11)
+    out = emulate_bf16(x, A, B, bias, dy, s)
+    h = out["h_save"][:, :r]
+    refs, bounds = layer_refs(x, A, B, bias, dy, s, h)
+    passed = 0
+    for col in cols:
+        try:
+            check_rounded(faulty_dB(h, dy, T // 2, col), refs["dB"], BF16, acc=bounds["dB"], name="dB")
+            passed += 1
+        except NumericsError:
+            pass
+    print(f"Gaussian operands: {passed} of {len(cols)} one-token faults pass the limits of check_rounded")
+    assert passed >= 1
+
+    c = FP.Layer("planted", "bf16", T, d_in, d_out, r, bias=True, s=s)
+    d, f = V.exact_layer_proved(c)
+    out = emulate_bf16(d["x"], d["A"], d["B"], d["bias"], d["dy"], s)
+    zero = dict(max_ulp=0, max_inexact=0, min_count=0)
+    for k in ("y", "dx", "dA", "dB", "dbias"):
+        check_rounded(out[k], f[k], BF16, name=k, **zero)                 # the emulated kernels are exact on these operands
+    assert torch.equal(out["h_save"][:, :r], f["h"]) and torch.equal(out["dh"], f["dh"])
+    for col in cols:
+        hit = torch.nonzero((d["dy"][T // 2:, col] != 0) & (f["h"][T // 2:] != 0).any(1))[0]
+        with pytest.raises(NumericsError, match="dB"):
+            check_rounded(faulty_dB(f["h"], d["dy"], T // 2 + int(hit), col), f["dB"], BF16, name="dB", **zero)
