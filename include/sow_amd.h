@@ -101,7 +101,7 @@ const char* sow_error_string(int code);
  * never touches them.  They are the library's ONLY process-wide state: a table of atomics initialised from the
  * environment (SOW_AMD_<NAME>) once, at first use; no launch path calls getenv.  Names: FORCE_CHAIN_V1, NO_SHORT_SPLIT,
  * NO_FUSED_H, FORCE_GEMM_V1, TN_NARROW, NO_GEMM3S, NO_GROUPED, NO_PERSIST, NO_NT_STORE, NT_LOAD, NO_PAIR_FLUSH, F32_EXACT, NO_PARK16, TN_NO_NT_LOAD, NO_TN_ROWS, NO_GEMM4H, NO_CHAIN3F, NO_TN_F32Q, NO_SPLITK,
- * NO_WIDE_CHAIN, NO_SHARED_X, NO_RAGGED
+ * NO_WIDE_CHAIN, NO_SHARED_X, NO_RAGGED, NO_RAGGED_GEMM
  * (value 1 = on, -1 / 0 = off) and GEMM3S, GEMM3, GEMM4
  * (1 = force, 0 = forbid, -1 = automatic).  sow_set_switch returns SOW_ERR_UNSUPPORTED for an unknown name;
  * sow_get_switch returns the value (-1 / 0 / 1).  Changing a switch while other threads launch is safe (atomic) but
@@ -132,11 +132,13 @@ size_t sow_h_save_elems(int64_t T, int r_live);
  * accumulator with even r_acc in (64, 256]; their backward runs the same chain for dX and a token-slab weight-gradient
  * kernel (dA, dB and dbias in one pass over x and dY, partial sums added in a fixed order).
  * Ragged widths: bf16 / f16 layers (SOW_PARAM_F32 included) with even r_live in (64, 256] and d_in or d_out NOT a multiple
- * of 8, with no accumulator or a low-rank one of even r_acc in [2, 256], run the same two kernels with token rows read
- * and written at any 2-byte offset (x / y / dY / dX / bias bases still 16-byte aligned; the weight gradients take any
- * x / dY view).  Their workspace query covers the pack and the slab partials whatever the NO_RAGGED switch says; the
- * switch (or a misaligned view) restores the generic kernels.  Ranks <= 64 at ragged widths, dense accumulators,
- * r_acc > 256, odd ranks and fp32 layers keep the generic kernels.
+ * of 8, with no accumulator, a dense one or a low-rank one of even r_acc in [2, 256], run the same two kernels with token
+ * rows read and written at any 2-byte offset (x / y / dY / dX / bias bases still 16-byte aligned; the weight gradients take
+ * any x / dY view).  A dense accumulator's products x W_acc and dY W_acc^T run on the ragged dense GEMM (gemm_rag.hip:
+ * W_acc read in place at its own row pitch, no copy, rounded once) ahead of the chain, which adds the live term with
+ * beta = 1; the NO_RAGGED_GEMM switch sends only that product to the generic GEMM.  Their workspace query covers the pack
+ * and the slab partials whatever the NO_RAGGED / NO_RAGGED_GEMM switches say; NO_RAGGED (or a misaligned view) restores
+ * the generic kernels.  Ranks <= 64 at ragged widths, r_acc > 256, odd ranks and fp32 layers keep the generic kernels.
  * x [T,d_in], A [d_in,r_live], B [r_live,d_out], y [T,d_out]; acc_down/acc_up per acc_kind
  * (r_acc = vr for SOW_ACC_LOWRANK, ignored otherwise); bias [d_out] or NULL.
  * The accumulator term is NOT scaled (sow.py:110-112). */

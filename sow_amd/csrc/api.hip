@@ -53,7 +53,7 @@ namespace sow {
 static const char* const kSwitchNames[SW_COUNT] = {"FORCE_CHAIN_V1", "NO_SHORT_SPLIT", "NO_FUSED_H", "FORCE_GEMM_V1", "TN_NARROW",
                                                    "NO_GEMM3S",      "GEMM3S",         "GEMM3",      "NO_GROUPED",     "NO_PERSIST",     "NO_NT_STORE",    "NT_LOAD",        "NO_PAIR_FLUSH",  "F32_EXACT",
                                                    "NO_PARK16",      "TN_NO_NT_LOAD",  "NO_TN_ROWS",     "GEMM4",          "NO_GEMM4H",      "NO_CHAIN3F",     "NO_TN_F32Q",     "NO_SPLITK",
-                                                   "NO_WIDE_CHAIN",  "NO_SHARED_X",    "NO_RAGGED"};
+                                                   "NO_WIDE_CHAIN",  "NO_SHARED_X",    "NO_RAGGED",      "NO_RAGGED_GEMM"};
 static std::atomic<int> g_switch[SW_COUNT];
 static std::once_flag g_switch_once;
 static void switches_from_env() {
@@ -159,7 +159,7 @@ static int gemm_auto(const void* A, int64_t lda, const void* B, int64_t ldb, boo
 
 extern "C" {
 
-int sow_version(void) { return 115; }
+int sow_version(void) { return 116; }
 
 int sow_set_switch(const char* name, int value) {
   if (!name) return SOW_ERR_NULL;
@@ -203,11 +203,21 @@ const char* sow_error_string(int code) {
 size_t sow_h_save_elems(int64_t T, int r_live) { return (size_t)T * (size_t)(r_live <= 64 ? 64 : r_live); }
 
 // A layer of ragged widths (include/sow_amd.h): bf16 / f16 compute dtype, even r_live in (64, 256], d_in or d_out not a
-// multiple of 8, no accumulator or a low-rank one of even r_acc in [2, 256].  A pure function of the shape: the workspace
-// plan follows it whatever the NO_RAGGED switch says.
+// multiple of 8, no accumulator, a dense one, or a low-rank one of even r_acc in [2, 256].  A pure function of the shape:
+// the workspace plan follows it whatever the NO_RAGGED / NO_RAGGED_GEMM switches say.
 static bool rag_layer(int r_live, int r_acc, int acc_kind, int d_in, int d_out, int dtype) {
   return r_live > 64 && ragged_shape_ok(r_live, d_in, d_out, dtype) &&
-         (acc_kind == SOW_ACC_NONE || (acc_kind == SOW_ACC_LOWRANK && ragged_shape_ok(r_acc, d_in, d_out, dtype)));
+         (acc_kind == SOW_ACC_NONE || acc_kind == SOW_ACC_DENSE ||
+          (acc_kind == SOW_ACC_LOWRANK && ragged_shape_ok(r_acc, d_in, d_out, dtype)));
+}
+
+// The dense-accumulator product of an admitted ragged layer (C = A . op(B), alpha = 1, beta = 0): gemm_rag, W_acc read in
+// place; gemm_auto (the generic kernel at these widths) under NO_RAGGED_GEMM or where gemm_rag does not take the operands.
+static int rag_dense_product(const void* A, int64_t lda, const void* B, int64_t ldb, bool transB, void* C, int64_t ldc, int64_t M,
+                             int N, int K, int dtype, hipStream_t stream) {
+  if (!sw_on(SW_NO_RAGGED_GEMM) && gemm_rag_supported(A, lda, B, ldb, transB, C, ldc, M, N, K, dtype))
+    return launch_gemm_rag(A, lda, B, ldb, transB, C, ldc, M, N, K, dtype, stream);
+  return gemm_auto(A, lda, B, ldb, transB, C, ldc, nullptr, M, N, K, 1.f, 0.f, dtype, stream);
 }
 
 // workspace carve (identical in the query and in the calls)
@@ -458,13 +468,17 @@ static int forward_impl(const void* x, const void* A, const void* B, const void*
   float beta = 0.f;
   int rc;
   // ragged widths: the fused chain for the low-rank accumulator (scale 1) and the live term, X read once per term; h_save
-  // holds the unscaled projection (the wide contract).  Without workspace or with views off 16 bytes, the generic kernels
-  // below.
+  // holds the unscaled projection (the wide contract); a dense accumulator's product x . W_acc is written by gemm_rag first.
+  // Without workspace or with views off 16 bytes, the generic kernels below.
   if (rag_layer(r_live, r_acc, acc_kind, d_in, d_out, dtype) && !sw_on(SW_NO_RAGGED) && ws && workspace_bytes >= w.total + 255 &&
       al16p(x) && al16p(y) && (!bias || al16p(bias)) && (!h_save || al4p(h_save))) {
     if (acc_kind == SOW_ACC_LOWRANK) {
       rc = wide_chain(x, y, acc_down, r_acc, acc_up, d_out, nullptr, nullptr, T, d_in, d_out, r_acc, 1.f, 1.f, 0.f, false, dtype,
                       ws, w, workspace_bytes, stream, true);
+      if (rc) return rc;
+      beta = 1.f;
+    } else if (acc_kind == SOW_ACC_DENSE) {
+      rc = rag_dense_product(x, d_in, acc_down, d_out, false, y, d_out, T, d_out, d_in, dtype, stream);
       if (rc) return rc;
       beta = 1.f;
     }
@@ -627,6 +641,11 @@ static int backward_impl(const void* dy, const void* x, const void* h_save, cons
     if (acc_kind == SOW_ACC_LOWRANK) {
       rc = wide_chain(dy, dx, acc_up, d_out, acc_down, r_acc, nullptr, nullptr, T, d_out, d_in, r_acc, 1.f, 1.f, 0.f, true, dtype,
                       ws, w, workspace_bytes, stream, true);
+      if (rc) return rc;
+      beta = 1.f;
+    } else if (acc_kind == SOW_ACC_DENSE) {
+      // dX = dY . W_acc^T   (W_acc stored [d_in, d_out] = [N, K])
+      rc = rag_dense_product(dy, d_out, acc_down, d_out, true, dx, d_in, T, d_in, d_out, dtype, stream);
       if (rc) return rc;
       beta = 1.f;
     }

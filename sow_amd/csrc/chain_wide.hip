@@ -27,6 +27,7 @@
 // The ragged kernel also takes 2 <= r <= 64 (r_pad = 64) for a layer's low-rank accumulator term, which saves no H.
 #include "kernels.hpp"
 #include "epilogue.hpp"
+#include "rag_load.hpp"
 
 namespace sow {
 
@@ -71,42 +72,6 @@ constexpr int CW_LDS = 65536, CW_PANEL = 64 * 64 * 2;
 
 template <typename T> __device__ __forceinline__ int cw_panel_off(int row, int k) {
   return (k >> 6) * CW_PANEL + bf16_img_off<64>(row, (k & 63) >> 3) + (k & 7) * 2;
-}
-
-// 16-byte piece at byte `off` of a ragged workgroup's rows (`lim` bytes): the piece that crosses the limit (the end of the
-// tensor, for the last workgroup) is read dword by dword, a 2-byte load for a dword cut in half: nothing past the limit is
-// requested, and the bytes past it read as 0
-__device__ __forceinline__ u32x4 rag_piece(__amdgpu_buffer_rsrc_t rs, uint32_t off, uint32_t lim) {
-  if (off + 16 <= lim) return __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
-  u32x4 v;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const uint32_t o = off + 4 * q;
-    v[q] = o + 4 <= lim ? __builtin_amdgcn_raw_buffer_load_b32(rs, o, 0, 0)
-                        : (o < lim ? (uint32_t)__builtin_amdgcn_raw_buffer_load_b16(rs, o, 0, 0) : 0u);
-  }
-  return v;
-}
-
-// elements gk .. gk + 7 of row `row` (element e = row * D1 + gk of the workgroup's rows), zero past column D1
-__device__ __forceinline__ u32x4 rag_load8(__amdgpu_buffer_rsrc_t rs, uint32_t lim, int row, int D1, int gk) {
-  const uint32_t e = (uint32_t)row * (uint32_t)D1 + (uint32_t)gk, off = (e >> 3) << 4;
-  const int sh = e & 7, ws = sh >> 1;
-  const u32x4 p0 = rag_piece(rs, off, lim);
-  const u32x4 p1 = sh ? rag_piece(rs, off + 16, lim) : u32x4{0, 0, 0, 0};
-  const uint32_t d[8] = {p0[0], p0[1], p0[2], p0[3], p1[0], p1[1], p1[2], p1[3]};
-  uint32_t s5[5];
-#pragma unroll
-  for (int j = 0; j < 5; ++j) s5[j] = ws == 0 ? d[j] : ws == 1 ? d[j + 1] : ws == 2 ? d[j + 2] : d[j + 3 < 8 ? j + 3 : 7];
-  u32x4 v;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = (sh & 1) ? __builtin_amdgcn_alignbit(s5[j + 1], s5[j], 16) : s5[j];
-  const int n = D1 - gk;
-  if (n < 8) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = 2 * j >= n ? 0u : (2 * j + 1 >= n ? (v[j] & 0xffffu) : v[j]);
-  }
-  return v;
 }
 
 template <typename T, bool RAG> __global__ __launch_bounds__(256, 2) void chain_wide_kernel(const WideParams p) {

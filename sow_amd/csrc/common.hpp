@@ -178,6 +178,8 @@ enum Switch : int {
   SW_NO_WIDE_CHAIN,       // 64 < r <= 256: the generic GEMM composition instead of chain_wide / skinny_tn_wide
   SW_NO_SHARED_X,         // sow_forward_shared / sow_backward_shared return SOW_ERR_UNSUPPORTED (callers take the grouped path)
   SW_NO_RAGGED,           // widths not multiples of 8: the generic kernels instead of the ragged chain_wide / skinny_tn_wide
+  SW_NO_RAGGED_GEMM,      // ragged layers with a dense accumulator: gemm_auto for the dense product instead of gemm_rag (the ragged
+                          // chain and weight-gradient kernels stay)
   SW_COUNT
 };
 int sw(int which);

@@ -198,6 +198,13 @@ int launch_gemm(const void* A, int64_t lda, bool transA, const void* B, int64_t 
 int launch_gemm_out(const void* A, int64_t lda, bool transA, const void* B, int64_t ldb, bool transB, void* C, int64_t ldc,
                     const void* bias, int64_t M, int N, int K, float alpha, float beta, int dtype, int c_dtype,
                     hipStream_t stream);
+// gemm_rag.hip: C[M, N] = A[M, K] . op(B) (alpha = 1, beta = 0, no bias) for bf16 / f16 operands whose leading dimensions are
+// any element counts (rows at any 2-byte offset; A, B, C bases 16-byte aligned).  transB: B stored [N, K].  B is read in
+// place: no copy, no workspace.  SOW_ERR_UNSUPPORTED (nothing launched) unless gemm_rag_supported
+bool gemm_rag_supported(const void* A, int64_t lda, const void* B, int64_t ldb, bool transB, const void* C, int64_t ldc, int64_t M,
+                        int N, int K, int dtype);
+int launch_gemm_rag(const void* A, int64_t lda, const void* B, int64_t ldb, bool transB, void* C, int64_t ldc, int64_t M, int N,
+                    int K, int dtype, hipStream_t stream);
 // gemm_x3.hip: the same contract for fp32 tensors on the bf16 matrix pipe (3 x bf16 splits); vector-aligned operands only
 int launch_gemm_x3(const void* A, int64_t lda, bool transA, const void* B, int64_t ldb, bool transB, void* C, int64_t ldc,
                    const void* bias, int64_t M, int N, int K, float alpha, float beta, hipStream_t stream);
