@@ -101,7 +101,7 @@ const char* sow_error_string(int code);
  * never touches them.  They are the library's ONLY process-wide state: a table of atomics initialised from the
  * environment (SOW_AMD_<NAME>) once, at first use; no launch path calls getenv.  Names: FORCE_CHAIN_V1, NO_SHORT_SPLIT,
  * NO_FUSED_H, FORCE_GEMM_V1, TN_NARROW, NO_GEMM3S, NO_GROUPED, NO_PERSIST, NO_NT_STORE, NT_LOAD, NO_PAIR_FLUSH, F32_EXACT, NO_PARK16, TN_NO_NT_LOAD, NO_TN_ROWS, NO_GEMM4H, NO_CHAIN3F, NO_TN_F32Q, NO_SPLITK,
- * NO_WIDE_CHAIN, NO_SHARED_X, NO_RAGGED, NO_RAGGED_GEMM
+ * NO_WIDE_CHAIN, NO_SHARED_X, NO_RAGGED, NO_RAGGED_GEMM, NO_BLOCKED_QR
  * (value 1 = on, -1 / 0 = off) and GEMM3S, GEMM3, GEMM4
  * (1 = force, 0 = forbid, -1 = automatic).  sow_set_switch returns SOW_ERR_UNSUPPORTED for an unknown name;
  * sow_get_switch returns the value (-1 / 0 / 1).  Changing a switch while other threads launch is safe (atomic) but
@@ -273,7 +273,12 @@ int sow_gemm_ex(const void* A, int64_t lda, int trans_a, const void* B, int64_t 
  * of TensorTrain.decompose (tt.py:128-136):  Q_out[m,k] = Q[:, :k], R_out[k,n] = R[:k, :]
  * with LAPACK's sign convention.  W [m,n] (ldw) of in_dtype; outputs of out_dtype; internals fp32.
  * R_out may be NULL (sow.py:168-172 only needs Q).  k <= m.  For n < k only n columns are factored: Q_out[:, :n] is the
- * reduced Q (all that qr_weight returns), Q_out[:, n:k] the complete-mode columns H_0 .. H_{n-1} e_j, R_out rows n.. are 0. */
+ * reduced Q (all that qr_weight returns), Q_out[:, n:k] the complete-mode columns H_0 .. H_{n-1} e_j, R_out rows n.. are 0.
+ * Up to 64 factored columns (kc = min(k, m, n)) one workgroup runs the unblocked panel; wider panels are factored by blocks
+ * of 32 columns (compact WY, qr_blocked.hip): the block on one workgroup, its trailing update and the formation of Q on
+ * the whole chip, same signs and taus, results repeatable bit for bit.  The NO_BLOCKED_QR switch keeps the one-workgroup
+ * panel at every width.  Both routes hold a reflector of m floats in LDS: SOW_ERR_UNSUPPORTED past about 38400 rows.  The workspace query is a pure function of the shape: it covers the blocks' triangular factors
+ * whenever kc > 64, whatever the switch says. */
 size_t sow_qr_workspace_bytes(int m, int n, int k, int in_dtype, int need_r);
 int sow_qr_thin(const void* W, int64_t ldw, int m, int n, int in_dtype, int k, void* Q_out, int64_t ldq, void* R_out,
                 int64_t ldr, int out_dtype, void* workspace, size_t workspace_bytes, void* stream);

@@ -53,7 +53,7 @@ namespace sow {
 static const char* const kSwitchNames[SW_COUNT] = {"FORCE_CHAIN_V1", "NO_SHORT_SPLIT", "NO_FUSED_H", "FORCE_GEMM_V1", "TN_NARROW",
                                                    "NO_GEMM3S",      "GEMM3S",         "GEMM3",      "NO_GROUPED",     "NO_PERSIST",     "NO_NT_STORE",    "NT_LOAD",        "NO_PAIR_FLUSH",  "F32_EXACT",
                                                    "NO_PARK16",      "TN_NO_NT_LOAD",  "NO_TN_ROWS",     "GEMM4",          "NO_GEMM4H",      "NO_CHAIN3F",     "NO_TN_F32Q",     "NO_SPLITK",
-                                                   "NO_WIDE_CHAIN",  "NO_SHARED_X",    "NO_RAGGED",      "NO_RAGGED_GEMM"};
+                                                   "NO_WIDE_CHAIN",  "NO_SHARED_X",    "NO_RAGGED",      "NO_RAGGED_GEMM", "NO_BLOCKED_QR"};
 static std::atomic<int> g_switch[SW_COUNT];
 static std::once_flag g_switch_once;
 static void switches_from_env() {
@@ -159,7 +159,7 @@ static int gemm_auto(const void* A, int64_t lda, const void* B, int64_t ldb, boo
 
 extern "C" {
 
-int sow_version(void) { return 116; }
+int sow_version(void) { return 117; }
 
 int sow_set_switch(const char* name, int value) {
   if (!name) return SOW_ERR_NULL;
@@ -1243,9 +1243,14 @@ int sow_gemm_ex(const void* A, int64_t lda, int trans_a, const void* B, int64_t 
   return launch_gemm(A, lda, trans_a != 0, B, ldb, trans_b != 0, C, ldc, bias, M, N, K, alpha, beta, dtype, (hipStream_t)stream);
 }
 
+// sow_qr_thin factors panels wider than QR_BLOCK_MIN columns by blocks (qr_blocked.hip).  Measured crossover: DESIGN.md
+// "Blocked QR"; it must stay >= 64 (the r <= 64 re-initialisation panels keep the one-workgroup kernel).
+constexpr int QR_BLOCK_MIN = 64;
+constexpr int QR_TAIL_K = 512;   // rows per partial product of the R tail on the blocked route
 struct QrPlan {
   int kc;
   size_t off_pt, off_qt, off_w, off_r, total;
+  size_t off_t, total_thin;   // sow_qr_thin only: the blocked route's T tiles behind everything else (kc > QR_BLOCK_MIN)
 };
 static QrPlan plan_qr(int m, int n, int k, int in_dtype, int need_r, int out_dtype_is_f32) {
   QrPlan q{};
@@ -1261,12 +1266,16 @@ static QrPlan plan_qr(int m, int n, int k, int in_dtype, int need_r, int out_dty
   q.off_r = off;
   if (need_r && n > q.kc && !out_dtype_is_f32) off += al256((size_t)k * (n - q.kc) * 4);
   q.total = off;
+  // a pure function of the shape: the T tiles are planned whatever the NO_BLOCKED_QR switch says
+  q.off_t = off;
+  if (q.kc > QR_BLOCK_MIN) off += al256(qr_blocked_t_floats(q.kc) * 4);
+  q.total_thin = off;
   return q;
 }
 
 size_t sow_qr_workspace_bytes(int m, int n, int k, int in_dtype, int need_r) {
   if (m <= 0 || n <= 0 || k <= 0) return 0;
-  return plan_qr(m, n, k, in_dtype, need_r, 0).total + 256;
+  return plan_qr(m, n, k, in_dtype, need_r, 0).total_thin + 256;
 }
 
 int sow_qr_thin(const void* W, int64_t ldw, int m, int n, int in_dtype, int k, void* Q_out, int64_t ldq, void* R_out,
@@ -1276,11 +1285,16 @@ int sow_qr_thin(const void* W, int64_t ldw, int m, int n, int in_dtype, int k, v
   if (m <= 0 || n <= 0 || k <= 0 || k > m) return SOW_ERR_SHAPE;
   if (!W || !Q_out || !workspace) return SOW_ERR_NULL;
   const QrPlan q = plan_qr(m, n, k, in_dtype, R_out != nullptr, out_dtype == SOW_F32);
-  if (workspace_bytes < q.total + 255) return SOW_ERR_WORKSPACE;
+  if (workspace_bytes < q.total_thin + 255) return SOW_ERR_WORKSPACE;
   char* ws = ws_base(workspace);
   float* Pt = (float*)(ws + q.off_pt);
   float* Qt = (float*)(ws + q.off_qt);
-  int rc = launch_qr_panel(W, ldw, in_dtype, m, q.kc, k, Pt, Qt, stream);
+  int rc;
+  const bool blocked = q.kc > QR_BLOCK_MIN && !sw_on(SW_NO_BLOCKED_QR);
+  if (blocked)
+    rc = launch_qr_blocked(W, ldw, in_dtype, m, q.kc, k, Pt, Qt, (float*)(ws + q.off_t), stream);
+  else
+    rc = launch_qr_panel(W, ldw, in_dtype, m, q.kc, k, Pt, Qt, stream);
   if (rc) return rc;
   rc = launch_qr_copy_out(Qt, Pt, Q_out, ldq, R_out, ldr, out_dtype, m, q.kc, k, k, stream);
   if (rc) return rc;
@@ -1297,13 +1311,24 @@ int sow_qr_thin(const void* W, int64_t ldw, int m, int n, int in_dtype, int k, v
       if (rc) return rc;
       Bp = wf, ldb = nt;
     }
-    if (out_dtype == SOW_F32) {
-      rc = launch_gemm(Qt, m, false, Bp, ldb, false, (float*)R_out + q.kc, ldr, nullptr, k, nt, m, 1.f, 0.f, SOW_F32, stream);
+    // The blocked route sums over the rows in chunks of QR_TAIL_K (C += partial product, rounded once per chunk); the
+    // one-workgroup route keeps its single product (the same bits as before).  Measured where it matters: 2048 x 5461 bf16,
+    // k = 2048 (tests/test_gpu_step_elementwise.py::test_qr_thin_large_k).  Its tail has 3413 columns, an odd row pitch, so
+    // every chunk runs gemm_kernel<float> on the exact fp32 MFMA whatever F32_EXACT says (the 3 x bf16 split needs
+    // vector-aligned rows), and 2048 = 4 x 512 has no ragged last chunk.  Worst |error| / limit of the tail check, always
+    // at element (202, 2290), error of one sign: 0.94 as one product from the one-workgroup Q, 1.03 as one product from
+    // the blocked Q, 0.31 in four chunks (profiles/qr_blocked.txt).  A last chunk shorter than 16 rows or not a multiple
+    // of 4 may take the exact kernel while the others take the split; both are fp32 products of the same contract.
+    const int kstep = blocked ? QR_TAIL_K : m;
+    float* rt = out_dtype == SOW_F32 ? (float*)R_out + q.kc : (float*)(ws + q.off_r);
+    const int64_t ldt = out_dtype == SOW_F32 ? ldr : nt;
+    for (int k0 = 0; k0 < m; k0 += kstep) {
+      const int kk = m - k0 < kstep ? m - k0 : kstep;
+      rc = launch_gemm(Qt + k0, m, false, (const float*)Bp + (int64_t)k0 * ldb, ldb, false, rt, ldt, nullptr, k, nt, kk, 1.f,
+                       k0 ? 1.f : 0.f, SOW_F32, stream);
       if (rc) return rc;
-    } else {
-      float* rt = (float*)(ws + q.off_r);
-      rc = launch_gemm(Qt, m, false, Bp, ldb, false, rt, nt, nullptr, k, nt, m, 1.f, 0.f, SOW_F32, stream);
-      if (rc) return rc;
+    }
+    if (out_dtype != SOW_F32) {
       rc = launch_cast_copy(rt, nt, SOW_F32, (char*)R_out + q.kc * esize(out_dtype), ldr, out_dtype, k, nt, stream);
       if (rc) return rc;
     }

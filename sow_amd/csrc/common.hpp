@@ -180,6 +180,7 @@ enum Switch : int {
   SW_NO_RAGGED,           // widths not multiples of 8: the generic kernels instead of the ragged chain_wide / skinny_tn_wide
   SW_NO_RAGGED_GEMM,      // ragged layers with a dense accumulator: gemm_auto for the dense product instead of gemm_rag (the ragged
                           // chain and weight-gradient kernels stay)
+  SW_NO_BLOCKED_QR,       // sow_qr_thin: the one-workgroup unblocked panel at every width instead of the blocked route past 64 columns
   SW_COUNT
 };
 int sw(int which);

@@ -269,6 +269,13 @@ int launch_qr_panel(const void* W, int64_t ldw, int in_dtype, int m, int kc, int
                     hipStream_t stream);
 int launch_qr_copy_out(const float* Qt, const float* Pt, void* Q, int64_t ldq, void* R, int64_t ldr, int out_dtype, int m,
                        int kc, int r, int k_rows, hipStream_t stream);
+// qr_blocked.hip: the same factorisation by blocks of 32 columns (compact WY), trailing updates and Q on the whole chip.
+// T: qr_blocked_t_floats(kc) floats of workspace, written before they are read.  Same Pt / Qt contents on return as
+// launch_qr_panel (R on and above the diagonal of Pt, Q[:, :r] in Qt), up to rounding; SOW_ERR_UNSUPPORTED (nothing
+// launched) for m > 38400 rows, where the block's reflector no longer fits the LDS -- launch_qr_panel's limit as well.
+size_t qr_blocked_t_floats(int kc);
+int launch_qr_blocked(const void* W, int64_t ldw, int in_dtype, int m, int kc, int r, float* Pt, float* Qt, float* T,
+                      hipStream_t stream);
 // accumulate.hip: batched Householder panels (one 1024-thread workgroup per matrix; Pt [kc][m] column-major panel in,
 // factored in place; Qt [r_new][m] = Q[:, :r_new] out)
 struct QrItem {
