@@ -101,7 +101,7 @@ const char* sow_error_string(int code);
  * never touches them.  They are the library's ONLY process-wide state: a table of atomics initialised from the
  * environment (SOW_AMD_<NAME>) once, at first use; no launch path calls getenv.  Names: FORCE_CHAIN_V1, NO_SHORT_SPLIT,
  * NO_FUSED_H, FORCE_GEMM_V1, TN_NARROW, NO_GEMM3S, NO_GROUPED, NO_PERSIST, NO_NT_STORE, NT_LOAD, NO_PAIR_FLUSH, F32_EXACT, NO_PARK16, TN_NO_NT_LOAD, NO_TN_ROWS, NO_GEMM4H, NO_CHAIN3F, NO_TN_F32Q, NO_SPLITK,
- * NO_WIDE_CHAIN, NO_SHARED_X, NO_RAGGED, NO_RAGGED_GEMM, NO_BLOCKED_QR
+ * NO_WIDE_CHAIN, NO_SHARED_X, NO_RAGGED, NO_RAGGED_GEMM, NO_BLOCKED_QR, NO_SKINNY
  * (value 1 = on, -1 / 0 = off) and GEMM3S, GEMM3, GEMM4
  * (1 = force, 0 = forbid, -1 = automatic).  sow_set_switch returns SOW_ERR_UNSUPPORTED for an unknown name;
  * sow_get_switch returns the value (-1 / 0 / 1).  Changing a switch while other threads launch is safe (atomic) but
@@ -253,6 +253,27 @@ int sow_backward_group_plan(const sow_layer_args* layers, int n, int dtype, int 
  * and then nothing has been launched (the caller runs sow_forward_group / sow_backward_group instead). */
 int sow_forward_shared(const sow_layer_args* layers, int n, int dtype, void* stream);
 int sow_backward_shared(const sow_layer_args* layers, int n, int dtype, int phases, void* stream);
+
+/* Generation-sized forwards: n <= 16 INDEPENDENT layers of at most 32 tokens each (the per-token calls of generate(): T =
+ * batch x beams; q / k / v or gate / up of a decoder block in one call) in TWO launches, whatever n:
+ *   h = rn( scale * sum_k x[t,k] A[k,j] )                                  fp32 sum, rounded once to the compute dtype
+ *   y = rn( sum_k x[t,k] acc_down[k,n] + sum_j h[t,j] B[j,n] + bias[n] )   fp32 sum, rounded ONCE
+ * (the h of the r_live <= 64 contract, never written to memory here; the single output rounding of the training forward's
+ * fused dense product).  The first launch streams the accumulator once on the whole chip -- a grid over column ranges x
+ * K-slabs -- and leaves fp32 slab partials of x . acc_down and x . A in the workspace; the second adds them in slab order
+ * with h . B and the bias.  No atomics: a repeat gives the same bits, and a layer computes inside a group exactly what it
+ * computes alone.  Rows are independent: a non-finite x[t, k] makes row t of y non-finite and no other.
+ * Fields used: x, A, B, acc_down, bias, y, T, d_in, d_out, r_live, acc_kind, scale, workspace, workspace_bytes (h_save and
+ * the backward fields are ignored).  Layers may share x or not.
+ * Admitted: SOW_DTYPE_BF16 / SOW_DTYPE_F16, T <= 32, SOW_ACC_DENSE or SOW_ACC_NONE, r_live <= 64, d_in and d_out multiples
+ * of 8, 16-byte-aligned x, y, acc_down, A, B and bias, n <= 16.  Anything else -- SOW_ACC_LOWRANK, SOW_PARAM_F32, and
+ * everything while the NO_SKINNY switch is on -- returns SOW_ERR_UNSUPPORTED; SOW_DTYPE_F32 returns SOW_ERR_DTYPE and a
+ * workspace below the query SOW_ERR_WORKSPACE.  All of it is decided on the host for every layer before anything is launched
+ * or dereferenced (the caller then takes sow_forward / sow_forward_group).  Layers with T = 0 are skipped (SOW_OK).
+ * sow_forward_skinny_workspace_bytes: per layer, a pure function of the shape (the switches do not enter); 0 outside the
+ * admitted set.  Every scratch byte is written before it is read. */
+size_t sow_forward_skinny_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype);
+int sow_forward_skinny(const sow_layer_args* layers, int n, int dtype, void* stream);
 
 /* General row-major GEMM  C[M,N] = alpha * op(A) op(B) + beta * C + bias[N]  (bias may be NULL).
  * trans_a: A is stored [K,M]; trans_b: B is stored [N,K].  Replaces the plain `@` / einsum call

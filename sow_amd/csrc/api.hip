@@ -53,7 +53,8 @@ namespace sow {
 static const char* const kSwitchNames[SW_COUNT] = {"FORCE_CHAIN_V1", "NO_SHORT_SPLIT", "NO_FUSED_H", "FORCE_GEMM_V1", "TN_NARROW",
                                                    "NO_GEMM3S",      "GEMM3S",         "GEMM3",      "NO_GROUPED",     "NO_PERSIST",     "NO_NT_STORE",    "NT_LOAD",        "NO_PAIR_FLUSH",  "F32_EXACT",
                                                    "NO_PARK16",      "TN_NO_NT_LOAD",  "NO_TN_ROWS",     "GEMM4",          "NO_GEMM4H",      "NO_CHAIN3F",     "NO_TN_F32Q",     "NO_SPLITK",
-                                                   "NO_WIDE_CHAIN",  "NO_SHARED_X",    "NO_RAGGED",      "NO_RAGGED_GEMM", "NO_BLOCKED_QR"};
+                                                   "NO_WIDE_CHAIN",  "NO_SHARED_X",    "NO_RAGGED",      "NO_RAGGED_GEMM", "NO_BLOCKED_QR",
+                                                   "NO_SKINNY"};
 static std::atomic<int> g_switch[SW_COUNT];
 static std::once_flag g_switch_once;
 static void switches_from_env() {
@@ -159,7 +160,7 @@ static int gemm_auto(const void* A, int64_t lda, const void* B, int64_t ldb, boo
 
 extern "C" {
 
-int sow_version(void) { return 117; }
+int sow_version(void) { return 118; }
 
 int sow_set_switch(const char* name, int value) {
   if (!name) return SOW_ERR_NULL;
@@ -971,6 +972,65 @@ int sow_forward_group(const sow_layer_args* layers, int n, int dtype, void* stre
   std::vector<sow_layer_args> packed;
   const int rc = pack_group(layers, n, cd, false, packed, stream);
   return rc ? rc : forward_group_impl(packed.data(), n, cd, stream);
+}
+
+// ---- generation-sized forwards (skinny_fwd.hip) --------------------------------------------------------------
+// The admitted set, decided from the shape alone: 1 <= T <= 32, bf16 / f16 without SOW_PARAM_F32, a dense accumulator or none,
+// r_live <= 64, widths multiples of 8.
+static bool skinny_shape_ok(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype) {
+  return (dtype == SOW_BF16 || dtype == SOW_F16) && T >= 1 && T <= 32 && d_in > 0 && d_out > 0 && r_live >= 1 && r_live <= 64 &&
+         (acc_kind == SOW_ACC_DENSE || acc_kind == SOW_ACC_NONE) && d_in % 8 == 0 && d_out % 8 == 0;
+}
+struct SkWs {
+  size_t off_py, off_ph, total;
+};
+static SkWs skinny_ws(int64_t T, int d_in, int d_out, int acc_kind) {
+  int S, KS, ncr;
+  skinny_plan(d_in, d_out, acc_kind, &S, &KS, &ncr);
+  SkWs w;
+  w.off_py = 0;
+  w.off_ph = acc_kind == SOW_ACC_DENSE ? al256(skinny_py_bytes(T, d_out, S)) : 0;
+  w.total = 256 + w.off_ph + al256(skinny_ph_bytes(T, S));
+  return w;
+}
+
+size_t sow_forward_skinny_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype) {
+  if (!skinny_shape_ok(T, d_in, d_out, r_live, acc_kind, dtype)) return 0;
+  return skinny_ws(T, d_in, d_out, acc_kind).total;
+}
+
+int sow_forward_skinny(const sow_layer_args* layers, int n, int dtype, void* stream) {
+  bool pf;
+  const int cd = split_dtype(dtype, &pf);
+  if (cd < 0 || cd == SOW_F32) return SOW_ERR_DTYPE;
+  if (pf || sw_on(SW_NO_SKINNY)) return SOW_ERR_UNSUPPORTED;
+  if (n < 0) return SOW_ERR_SHAPE;
+  if (n == 0) return SOW_OK;
+  if (!layers) return SOW_ERR_NULL;
+  if (n > SK_MAXL) return SOW_ERR_UNSUPPORTED;
+  SkLayer sk[SK_MAXL];
+  int m = 0;
+  // every layer is checked before the first launch: a refusal leaves all outputs and workspaces untouched
+  for (int i = 0; i < n; ++i) {
+    const sow_layer_args& L = layers[i];
+    if (L.T < 0 || L.d_in <= 0 || L.d_out <= 0 || L.r_live <= 0) return SOW_ERR_SHAPE;
+    if (L.acc_kind != SOW_ACC_NONE && L.acc_kind != SOW_ACC_LOWRANK && L.acc_kind != SOW_ACC_DENSE) return SOW_ERR_SHAPE;
+    if (L.T == 0) continue;
+    if (!skinny_shape_ok(L.T, L.d_in, L.d_out, L.r_live, L.acc_kind, cd)) return SOW_ERR_UNSUPPORTED;
+    const bool dense = L.acc_kind == SOW_ACC_DENSE;
+    if (!L.x || !L.A || !L.B || !L.y || (dense && !L.acc_down)) return SOW_ERR_NULL;
+    if (!al16p(L.x) || !al16p(L.y) || !al16p(L.A) || !al16p(L.B) || !al16p(L.bias) || (dense && !al16p(L.acc_down)))
+      return SOW_ERR_UNSUPPORTED;
+    const SkWs w = skinny_ws(L.T, L.d_in, L.d_out, L.acc_kind);
+    if (!L.workspace || L.workspace_bytes < w.total) return SOW_ERR_WORKSPACE;
+    char* ws = ws_base(L.workspace);
+    SkLayer& K = sk[m++];
+    K = SkLayer{};
+    K.x = L.x, K.W = dense ? L.acc_down : nullptr, K.A = L.A, K.B = L.B, K.bias = L.bias, K.y = L.y;
+    K.Py = dense ? (float*)(ws + w.off_py) : nullptr, K.Ph = (float*)(ws + w.off_ph);
+    K.T = (int)L.T, K.d_in = L.d_in, K.d_out = L.d_out, K.r = L.r_live, K.scale = L.scale;
+  }
+  return launch_skinny_fwd(sk, m, cd, (hipStream_t)stream);
 }
 
 static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, int gdt, int phases, void* stream_) {

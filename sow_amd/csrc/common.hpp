@@ -181,6 +181,7 @@ enum Switch : int {
   SW_NO_RAGGED_GEMM,      // ragged layers with a dense accumulator: gemm_auto for the dense product instead of gemm_rag (the ragged
                           // chain and weight-gradient kernels stay)
   SW_NO_BLOCKED_QR,       // sow_qr_thin: the one-workgroup unblocked panel at every width instead of the blocked route past 64 columns
+  SW_NO_SKINNY,           // sow_forward_skinny returns SOW_ERR_UNSUPPORTED (callers take sow_forward / sow_forward_group)
   SW_COUNT
 };
 int sw(int which);

@@ -191,6 +191,23 @@ size_t tnw_partial_bytes(int64_t T, int d_in, int d_out, int r);
 int launch_tn_wide(const void* x, const void* dh, const void* dy, const void* h, void* dA, void* dB, void* dbias, int64_t T,
                    int d_in, int d_out, int r, float scale, float beta, int dtype, int out_dtype, void* ws, size_t ws_bytes,
                    hipStream_t stream);
+// skinny_fwd.hip: the fused forward of generation-sized calls (T <= 32, bf16 / f16, r <= 64, dense accumulator or none), n <=
+// SK_MAXL independent layers in two launches: W streamed once by a grid over (column range) x (K-slab), fp32 slab partials
+// through the workspace, summed in slab order with h . B and the bias and rounded once
+constexpr int SK_MAXL = 16;
+struct SkLayer {
+  const void *x, *W, *A, *B, *bias;   // W = the dense accumulator [d_in][d_out], or nullptr
+  void* y;
+  float *Py, *Ph;                     // slab partials [S][T][d_out] (nullptr without W) and [S][T][64]
+  int T, d_in, d_out, r;
+  int S, KS, ncr, startA, startB;     // filled in by launch_skinny_fwd (skinny_plan)
+  float scale;
+};
+// K-slabs, slab length and phase-A column ranges of a layer: a pure function of the shape
+void skinny_plan(int d_in, int d_out, int acc_kind, int* S, int* KS, int* ncr);
+size_t skinny_py_bytes(int64_t T, int d_out, int S);
+size_t skinny_ph_bytes(int64_t T, int S);
+int launch_skinny_fwd(const SkLayer* layers, int n, int dtype, hipStream_t stream);
 // gemm.hip
 int launch_gemm(const void* A, int64_t lda, bool transA, const void* B, int64_t ldb, bool transB, void* C, int64_t ldc,
                 const void* bias, int64_t M, int N, int K, float alpha, float beta, int dtype, hipStream_t stream);

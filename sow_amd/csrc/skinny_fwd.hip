@@ -1,0 +1,317 @@
+// Fused forward for generation-sized inputs (T <= 32 tokens): bf16 / f16, r_live <= 64, dense accumulator or none.
+//
+//   h = rn( scale * sum_k x[t,k] A[k,j] )                               fp32 sum, rounded once to the compute dtype
+//   y = rn( sum_k x[t,k] W[k,n] + sum_j h[t,j] B[j,n] + bias[n] )       fp32 sum, rounded ONCE
+//
+// At these token counts the call is a stream of W (2 d_in d_out bytes) with next to no arithmetic per byte, so the grid is
+// cut over the WEIGHT, not over tokens:
+//
+//   phase A (skinny_a_kernel)  one workgroup per (64-column range of d_out) x (K-slab of d_in); the slab length is planned
+//       on the host so that the layer has >= 512 workgroups where its size allows (skinny_plan).  The workgroup stages its
+//       slab of x in LDS ([16 or 32 rows][KS], rows >= T and k >= d_in are zeros made here, never memory read past x);
+//       its four waves take the slab's 32-deep k-steps in turn.  A wave reads 32 rows x 64 columns of W per step straight
+//       into registers -- every lane 8 bytes of one row, 16 lanes = 128 contiguous bytes of a W row, non-temporal, each
+//       byte of W read exactly once by the whole grid -- and turns the 8 rows a lane holds into the four B fragments of
+//       v_mfma_f32_16x16x32_bf16 / _f16 with byte permutes (lane l: k = 8 (l >> 4) + i down the register, column
+//       4 (l & 15) + c for fragment c; the permutation of columns inside the range is undone when the tile is parked).  x
+//       is the A operand (one or two 16-row tiles).  The four waves' fp32 tiles are added in wave order through LDS and
+//       the sum goes to the workspace as the slab's partial product Py[s][t][n].
+//       A wave requests its first four k-steps before the x slab is staged, so the whole slab of a 4096 x 4096 layer is in
+//       flight from the first instruction on.
+//       The first S * ceil(r / 16) workgroups of a layer compute the partial sums of one 16-column tile of x . A instead
+//       (Ph[s][t][64]): A is [d_in][r] with any r, so its fragments are gathered with 2-byte loads; same x staging, same
+//       MFMA, same reduction.
+//   phase B (skinny_b_kernel)  one workgroup per 64 columns x 4 token rows, one output element per thread: h = rn(scale *
+//       sum_s Ph[s]) of its four rows into LDS, then per output element the slab partials in slab order, the r products
+//       h . B in order of j, the bias, one rounding, one store.
+//
+// No atomics, fixed summation order: a repeat gives the same bits, and a layer inside a group (grid concatenation, per-layer
+// block offset) computes exactly what it computes alone.
+#include "kernels.hpp"
+
+namespace sow {
+
+#ifndef SOW_SKINNY_NCT
+#define SOW_SKINNY_NCT 4   // 16-column MFMA tiles per wave: 4 (8-byte loads, 64-column ranges) or 8 (16-byte loads, 128)
+#endif
+constexpr int SK_NCT = SOW_SKINNY_NCT;
+constexpr int SK_CN = 16 * SK_NCT;        // columns per phase-A workgroup
+constexpr int SK_RS = SK_CN + 4;          // row pitch (floats) of the parked tiles: 4 rows apart = 16 banks apart
+constexpr int SK_KSTEP = 32;              // k per MFMA step
+constexpr int SK_KQ = 4 * SK_KSTEP;       // k per round of the four waves
+constexpr int SK_KS_MAX = 1024;           // longest K-slab (x slab in LDS: 32 x 1032 x 2 bytes)
+constexpr int SK_XPAD = 8;                // elements of padding per staged x row
+constexpr int SK_WANT_WGS = 512;          // two workgroups per CU
+constexpr int SK_BN = 64;                 // columns per phase-B workgroup
+typedef __attribute__((ext_vector_type(SK_NCT / 2))) uint32_t sk_wvec;
+
+struct SkGroup {
+  SkLayer L[SK_MAXL];
+  int n;
+};
+static_assert(sizeof(SkGroup) <= 4096, "by-value kernel arguments must stay under 4 KiB");
+
+void skinny_plan(int d_in, int d_out, int acc_kind, int* S, int* KS, int* ncr) {
+  const int nc = acc_kind == SOW_ACC_DENSE ? ceil_div(d_out, SK_CN) : 0;
+  const int want = nc ? ceil_div(SK_WANT_WGS, nc) : 32;
+  int ks = ceil_div(ceil_div(d_in, want), SK_KQ) * SK_KQ;
+  if (ks < SK_KQ) ks = SK_KQ;
+  if (ks > SK_KS_MAX) ks = SK_KS_MAX;
+  *KS = ks, *S = ceil_div(d_in, ks), *ncr = nc;
+}
+
+template <typename T> __device__ __forceinline__ f32x4 sk_mfma(u32x4 a, u32x4 b, f32x4 c);
+template <> __device__ __forceinline__ f32x4 sk_mfma<bf16_t>(u32x4 a, u32x4 b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_v8<bf16_t>(a), as_v8<bf16_t>(b), c, 0, 0, 0);
+}
+template <> __device__ __forceinline__ f32x4 sk_mfma<f16_t>(u32x4 a, u32x4 b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(as_v8<f16_t>(a), as_v8<f16_t>(b), c, 0, 0, 0);
+}
+
+__device__ __forceinline__ sk_wvec sk_load_w(const sk_wvec* p) {
+#ifdef SOW_SKINNY_NO_NT
+  return *p;
+#else
+  return __builtin_nontemporal_load(p);
+#endif
+}
+
+constexpr int SK_PF = 4;   // k-steps a wave keeps in flight: all of them are requested before the x slab is staged
+
+template <typename T> __global__ __launch_bounds__(256) void skinny_a_kernel(const SkGroup g) {
+  extern __shared__ __align__(16) char sk_smem[];
+  int li = 0;
+  for (int i = 1; i < g.n; ++i)
+    if ((int)blockIdx.x >= g.L[i].startA) li = i;
+  const SkLayer& L = g.L[li];
+  const int b = (int)blockIdx.x - L.startA;
+  const int ntj = (L.r + 15) >> 4;            // 16-column tiles of x . A
+  const bool is_xa = b < L.S * ntj;           // the first S * ntj workgroups: (slab, tile) of x . A
+  // column range fastest: workgroups that start together read neighbouring 128-byte pieces of the same rows of W
+  const int s = is_xa ? b / ntj : (b - L.S * ntj) / L.ncr;
+  const int cr = is_xa ? b % ntj : (b - L.S * ntj) % L.ncr;   // tile of x . A, or column range of W
+  const int Tn = L.T, d_in = L.d_in, d_out = L.d_out, KS = L.KS;
+  const int rows = Tn > 16 ? 32 : 16;
+  const int kbeg = s * KS;
+  const int klen = min(KS, d_in - kbeg);
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, n16 = lane & 15, kg = lane >> 4;
+  const int kk0 = w * SK_KSTEP;
+
+  // ---- requests first: the operand stream does not depend on x ----
+  // W: lane = rows k0 + 8 kg + i, columns col0 .. col0 + NCT - 1.  x . A: lane = the same rows, column j of A, one element.
+  sk_wvec d[SK_PF][8];
+  const int col0 = cr * SK_CN + n16 * SK_NCT;
+  const bool col_ok = col0 < d_out;   // d_out and NCT are multiples of 4: a lane's columns are all in or all out
+  const T* Wp = (const T*)L.W + col0;
+  const int r = L.r, ja = cr * 16 + n16;
+  const uint16_t* Ap = (const uint16_t*)L.A + ja;
+  auto load_step = [&](int kk, sk_wvec(&o)[8]) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int k = kbeg + kk + kg * 8 + i;
+      sk_wvec v = {};
+      if (!is_xa) {
+        if (col_ok && kk < klen && k < d_in) v = sk_load_w((const sk_wvec*)(Wp + (size_t)k * d_out));
+      } else {
+        if (ja < r && kk < klen && k < d_in) v[0] = Ap[(size_t)k * r];
+      }
+      o[i] = v;
+    }
+  };
+#pragma unroll
+  for (int p = 0; p < SK_PF; ++p) load_step(kk0 + p * SK_KQ, d[p]);
+
+  // ---- the slab of x: [rows][KS + pad], zeros for t >= T and k >= d_in ----
+  const int xpitch = (KS + SK_XPAD) * 2;   // bytes
+  {
+    const T* x = (const T*)L.x;
+    const int cpr = KS / 8;
+    for (int idx = tid; idx < rows * cpr; idx += 256) {
+      const int t = idx / cpr, c = idx - t * cpr, k = kbeg + c * 8;
+      u32x4 v = {0u, 0u, 0u, 0u};
+      if (t < Tn && k < d_in) v = *(const u32x4*)(x + (size_t)t * d_in + k);
+      *(u32x4*)(sk_smem + t * xpitch + c * 16) = v;
+    }
+  }
+  __syncthreads();
+
+  f32x4 acc[SK_NCT][2];
+#pragma unroll
+  for (int c = 0; c < SK_NCT; ++c) acc[c][0] = acc[c][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const char* xa0 = sk_smem + n16 * xpitch + kg * 16;
+  const char* xa1 = xa0 + 16 * xpitch;
+
+  for (int kb = kk0; kb < klen; kb += SK_PF * SK_KQ) {
+#pragma unroll
+    for (int p = 0; p < SK_PF; ++p) {
+      const int kk = kb + p * SK_KQ;
+      if (kk < klen) {   // uniform per wave
+        const u32x4 a0 = *(const u32x4*)(xa0 + kk * 2);
+        u32x4 a1 = {0u, 0u, 0u, 0u};
+        if (rows == 32) a1 = *(const u32x4*)(xa1 + kk * 2);
+        if (!is_xa) {
+#pragma unroll
+          for (int c = 0; c < SK_NCT; ++c) {
+            u32x4 f;
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+              f[m] = __builtin_amdgcn_perm(d[p][2 * m + 1][c >> 1], d[p][2 * m][c >> 1], (c & 1) ? 0x07060302u : 0x05040100u);
+            acc[c][0] = sk_mfma<T>(a0, f, acc[c][0]);
+            if (rows == 32) acc[c][1] = sk_mfma<T>(a1, f, acc[c][1]);
+          }
+        } else {
+          u32x4 f;
+#pragma unroll
+          for (int m = 0; m < 4; ++m) f[m] = d[p][2 * m][0] | (d[p][2 * m + 1][0] << 16);
+          acc[0][0] = sk_mfma<T>(a0, f, acc[0][0]);
+          if (rows == 32) acc[0][1] = sk_mfma<T>(a1, f, acc[0][1]);
+        }
+        load_step(kk + SK_PF * SK_KQ, d[p]);   // (requests nothing past the slab)
+      }
+    }
+  }
+
+  // ---- park the four waves' tiles, add them in wave order, store the slab partial ----
+  __syncthreads();   // every wave is done with the x slab: the parked tiles take its place
+  float* red = (float*)sk_smem;
+#pragma unroll
+  for (int c = 0; c < SK_NCT; ++c)
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf)
+      if ((hf == 0 || rows == 32) && (c == 0 || !is_xa)) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) red[(w * rows + hf * 16 + kg * 4 + q) * SK_RS + c * 16 + n16] = acc[c][hf][q];
+      }
+  __syncthreads();
+  if (!is_xa) {
+    float* Py = L.Py + (size_t)s * Tn * d_out;
+    for (int idx = tid; idx < Tn * SK_CN; idx += 256) {
+      const int t = idx / SK_CN, jc = idx - t * SK_CN;
+      const int n = cr * SK_CN + jc;
+      // local column jc = n16 * NCT + c sits in fragment c, tile column n16
+      const int slot = (jc % SK_NCT) * 16 + jc / SK_NCT;
+      float v = red[t * SK_RS + slot];
+#pragma unroll
+      for (int ww = 1; ww < 4; ++ww) v += red[(ww * rows + t) * SK_RS + slot];
+      if (n < d_out) Py[(size_t)t * d_out + n] = v;
+    }
+  } else {
+    // columns 16 cr .. 16 cr + 15 of Ph[s] (columns >= r hold zeros; those past the last tile are never read)
+    float* Ph = L.Ph + (size_t)s * Tn * 64 + cr * 16;
+    for (int idx = tid; idx < Tn * 16; idx += 256) {
+      const int t = idx >> 4, jj = idx & 15;
+      float v = red[t * SK_RS + jj];
+#pragma unroll
+      for (int ww = 1; ww < 4; ++ww) v += red[(ww * rows + t) * SK_RS + jj];
+      Ph[t * 64 + jj] = v;
+    }
+  }
+}
+
+// Phase B: workgroup = 64 columns x 4 token rows, one output element per thread.  Every load a thread needs is independent
+// of the others -- its column of B and its bias (cold, from HBM), its slab partials -- so all of them are requested before
+// the first is used (at clamped, always valid addresses: no branch stands between the requests): one memory round trip
+// instead of a chain of r + 2 S + 1, and only the fp32 additions run in order.
+constexpr int SK_BS = 16;   // slab partials requested up front; a layer with more slabs adds the rest in a second loop
+
+template <typename T> __global__ __launch_bounds__(256) void skinny_b_kernel(const SkGroup g) {
+  __shared__ float hs[4][64];
+  int li = 0;
+  for (int i = 1; i < g.n; ++i)
+    if ((int)blockIdx.x >= g.L[i].startB) li = i;
+  const SkLayer& L = g.L[li];
+  const int b = (int)blockIdx.x - L.startB;
+  const int Tn = L.T, d_out = L.d_out, r = L.r, S = L.S;
+  const int nrg = (Tn + 3) >> 2;
+  const int cb = b / nrg, rg = b - cb * nrg;
+  const int tid = threadIdx.x, nn = tid & 63, tl = tid >> 6;
+  const int t = rg * 4 + tl, n = cb * SK_BN + nn;
+  const bool live = t < Tn && n < d_out;
+  const int tc = min(t, Tn - 1), nc = min(n, d_out - 1), jc = min(nn, r - 1);
+  const bool dense = L.Py != nullptr;
+
+  T bv[64];
+  {
+    const T* B = (const T*)L.B + nc;
+#pragma unroll
+    for (int j = 0; j < 64; ++j) bv[j] = B[(size_t)min(j, r - 1) * d_out];
+  }
+  const T bias = L.bias ? ((const T*)L.bias)[nc] : from_f32<T>(0.f);
+  float ph[SK_BS], py[SK_BS];
+  const float* Ph = L.Ph + (size_t)tc * 64 + jc;
+  const size_t phs = (size_t)Tn * 64;
+  const float* Py = (dense ? L.Py : L.Ph) + (dense ? (size_t)tc * d_out + nc : 0);   // (never read without W)
+  const size_t pys = dense ? (size_t)Tn * d_out : 0;
+#pragma unroll
+  for (int u = 0; u < SK_BS; ++u) ph[u] = Ph[(size_t)min(u, S - 1) * phs];
+#pragma unroll
+  for (int u = 0; u < SK_BS; ++u) py[u] = Py[(size_t)min(u, S - 1) * pys];
+
+  // h[t][nn] = rn(scale * sum_s Ph[s][t][nn]), slab order
+  {
+    float v = 0.f;
+#pragma unroll
+    for (int u = 0; u < SK_BS; ++u)
+      if (u < S) v += ph[u];
+    for (int s = SK_BS; s < S; ++s) v += Ph[(size_t)s * phs];
+    hs[tl][nn] = (t < Tn && nn < r) ? to_f32(from_f32<T>(L.scale * v)) : 0.f;
+  }
+  float acc = 0.f;
+  if (dense) {
+#pragma unroll
+    for (int u = 0; u < SK_BS; ++u)
+      if (u < S) acc += py[u];
+    for (int s = SK_BS; s < S; ++s) acc += Py[(size_t)s * pys];
+  }
+  __syncthreads();
+  if (!live) return;
+#pragma unroll
+  for (int j = 0; j < 64; ++j)
+    if (j < r) acc = fmaf(hs[tl][j], to_f32(bv[j]), acc);
+  if (L.bias) acc += to_f32(bias);
+  ((T*)L.y)[(size_t)t * d_out + n] = from_f32<T>(acc);
+}
+
+size_t skinny_py_bytes(int64_t T, int d_out, int S) { return (size_t)S * (size_t)T * (size_t)d_out * sizeof(float); }
+size_t skinny_ph_bytes(int64_t T, int S) { return (size_t)S * (size_t)T * 64 * sizeof(float); }
+
+// layers: x, W (or nullptr), A, B, bias, y, Py (or nullptr), Ph, T in [1, 32], d_in, d_out, r, scale set by the caller (api.hip
+// has checked the admitted set); the plan and the block offsets are filled in here
+int launch_skinny_fwd(const SkLayer* layers, int n, int dtype, hipStream_t stream) {
+  if (n <= 0) return SOW_OK;
+  if (n > SK_MAXL || (dtype != SOW_BF16 && dtype != SOW_F16)) return SOW_ERR_UNSUPPORTED;
+  SkGroup g;
+  g.n = n;
+  int na = 0, nb = 0;
+  size_t lds = 0;
+  for (int i = 0; i < n; ++i) {
+    SkLayer& L = g.L[i];
+    L = layers[i];
+    int ncr;
+    skinny_plan(L.d_in, L.d_out, L.W ? SOW_ACC_DENSE : SOW_ACC_NONE, &L.S, &L.KS, &ncr);
+    L.ncr = ncr;
+    L.startA = na, L.startB = nb;
+    na += L.S * ((L.r + 15) / 16 + ncr);
+    nb += ceil_div(L.d_out, SK_BN) * ((L.T + 3) / 4);
+    const int rows = L.T > 16 ? 32 : 16;
+    const size_t xb = (size_t)rows * (L.KS + SK_XPAD) * 2, rb = (size_t)4 * rows * SK_RS * sizeof(float);
+    lds = xb > lds ? xb : lds;
+    lds = rb > lds ? rb : lds;
+  }
+  constexpr int LDS_MAX = 4 * 32 * SK_RS * 4 > 32 * (SK_KS_MAX + SK_XPAD) * 2 ? 4 * 32 * SK_RS * 4 : 32 * (SK_KS_MAX + SK_XPAD) * 2;
+  if (dtype == SOW_BF16) {
+    SOW_SET_MAX_LDS_ONCE(LDS_MAX, skinny_a_kernel<bf16_t>);
+    hipLaunchKernelGGL(skinny_a_kernel<bf16_t>, dim3(na), dim3(256), lds, stream, g);
+    SOW_CHECK_LAUNCH();
+    hipLaunchKernelGGL(skinny_b_kernel<bf16_t>, dim3(nb), dim3(256), 0, stream, g);
+  } else {
+    SOW_SET_MAX_LDS_ONCE(LDS_MAX, skinny_a_kernel<f16_t>);
+    hipLaunchKernelGGL(skinny_a_kernel<f16_t>, dim3(na), dim3(256), lds, stream, g);
+    SOW_CHECK_LAUNCH();
+    hipLaunchKernelGGL(skinny_b_kernel<f16_t>, dim3(nb), dim3(256), 0, stream, g);
+  }
+  SOW_CHECK_LAUNCH();
+  return SOW_OK;
+}
+
+}  // namespace sow

@@ -194,6 +194,24 @@ class SiblingGroup:
                 return False
         return True
 
+    def _forward_skinny(self, x: torch.Tensor):
+        """The siblings' outputs of a generation-sized no-grad call (at most 32 flattened tokens) through ONE
+        sow_forward_skinny call -- two launches for q / k / v -- or None: a set the skinny forward does not admit (any
+        sibling: low-rank accumulator, wide rank, ragged widths) or that the library refuses runs the grouped path."""
+        x2 = x.reshape(-1, x.shape[-1])
+        if not 1 <= x2.shape[0] <= ops.SKINNY_MAX_T:
+            return None
+        calls = []
+        for m in self.layers:
+            A, B = m.downscale_weights._parameters["0"], m.upscale_weights._parameters["0"]
+            if not ops.skinny_admits(x2, A, B, m.acc_downweight, m.acc_upweight, m.bias):
+                return None
+            calls.append((x2, A, B, m.acc_downweight if m.acc_downweight.numel() else None, m.bias, float(m.scale)))
+        ys = ops.sow_forward_skinny(calls)
+        if ys is None:
+            return None
+        return [y.reshape(*x.shape[:-1], y.shape[1]) for y in ys]
+
     def forward(self, layer: SoWLinear, x: torch.Tensor) -> Optional[torch.Tensor]:
         key = (id(x), x._version, x.data_ptr(), tuple(x.shape), torch.is_grad_enabled(), torch.is_autocast_enabled("cuda"),
                torch.get_autocast_dtype("cuda"))
@@ -208,6 +226,12 @@ class SiblingGroup:
             return None            # the layer raises on its own
         if not self.usable(x, cdt):
             return None
+        if cdt is None and not torch.is_grad_enabled():
+            ys = self._forward_skinny(x)
+            if ys is not None:
+                self._key, self._x = key, x
+                self._parked = {id(m): y for m, y in zip(self.layers, ys) if m is not layer}
+                return ys[self.layers.index(layer)]
         tensors = []
         for m in self.layers:
             tensors += [m.downscale_weights._parameters["0"], m.upscale_weights._parameters["0"], m.acc_downweight,

@@ -186,6 +186,15 @@ class SoWLinear(nn.Module):
             # no backward will follow (eval / generate, commonsense_evaluate.py:268-287; the first pass of activation
             # checkpointing): the projection h = scale * x A is not written to HBM
             x2 = x.reshape(-1, x.shape[-1])
+            # generation-sized calls (generate(): batch x beams rows per new token): the fused skinny forward, two launches,
+            # the accumulator streamed once on the whole chip.  Autocast with fp32 parameters, a low-rank accumulator, a
+            # wide rank, ragged widths and a refusal from the library keep the path below.
+            if cdt is None and x2.shape[0] <= ops.SKINNY_MAX_T and ops.skinny_admits(
+                    x2, A, B, self.acc_downweight, self.acc_upweight, self.bias):
+                acc = self.acc_downweight if self.acc_downweight.numel() else None
+                ys = ops.sow_forward_skinny([(x2, A, B, acc, self.bias, float(self.scale))])
+                if ys is not None:
+                    return ys[0].reshape(*x.shape[:-1], B.shape[1])
             if cdt is not None:
                 x2 = autocast_input(x2.contiguous(), cdt)
             y, _ = ops.sow_forward(x2, A, B, self.acc_downweight, self.acc_upweight, self.bias, float(self.scale), save_h=False,

@@ -181,6 +181,104 @@ def sow_forward(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, ac
     return y, (h if save_h else None)
 
 
+SKINNY_MAX_T = 32          # include/sow_amd.h: sow_forward_skinny admits at most 32 tokens per layer ...
+SKINNY_MAX_LAYERS = 16     # ... and 16 layers per call
+_SKINNY_WS_BYTES: dict = {}
+
+
+def skinny_workspace_bytes(T: int, d_in: int, d_out: int, r: int, kind: int, dt: int) -> int:
+    """sow_forward_skinny_workspace_bytes, memoised per shape: 0 = the shape is outside the admitted set.  A pure function
+    of the shape (no switch enters), so the memo is never dropped."""
+    key = (T, d_in, d_out, r, kind, dt)
+    n = _SKINNY_WS_BYTES.get(key)
+    if n is None:
+        n = _SKINNY_WS_BYTES[key] = int(_lib.load().sow_forward_skinny_workspace_bytes(T, d_in, d_out, r, kind, dt))
+    return n
+
+
+def skinny_pays(T: int, d_in: int, d_out: int) -> bool:
+    """The measured dispatch rule of the module surface (profiles/skinny_forward.txt): the token
+    counts and widths at which the fused skinny forward is faster than the path it replaces."""
+    return 1 <= T <= SKINNY_MAX_T
+
+
+def skinny_admits(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, acc_up, bias) -> bool:
+    """Whether a no-grad module call on the flattened input x2 may go to sow_forward_skinny: a bf16 / f16 call of at most 32
+    tokens with parameters of the input's dtype, a dense accumulator or none, and a shape the library admits and the
+    dispatch rule keeps.  False sends the caller to the existing path, which raises whatever it raises today."""
+    dt = _DT.get(x2.dtype)
+    if dt is None or dt == _lib.F32 or not x2.is_cuda or x2.dim() != 2 or not 1 <= x2.shape[0] <= SKINNY_MAX_T:
+        return False
+    kind = acc_kind(acc_down, acc_up)
+    if kind == _lib.ACC_LOWRANK or A.dim() != 2 or B.dim() != 2:
+        return False
+    T, d_in = x2.shape
+    r, d_out = B.shape
+    if tuple(A.shape) != (d_in, r) or (kind == _lib.ACC_DENSE and tuple(acc_down.shape) != (d_in, d_out)):
+        return False
+    for t in (A, B, bias, acc_down if kind == _lib.ACC_DENSE else None):
+        if t is not None and (t.dtype != x2.dtype or t.device != x2.device):
+            return False
+    return skinny_pays(T, d_in, d_out) and skinny_workspace_bytes(T, d_in, d_out, r, kind, dt) > 0
+
+
+def sow_forward_skinny(layers) -> Optional[list]:
+    """y_i of n <= 16 independent generation-sized layer calls (T_i <= 32 tokens) in two launches (include/sow_amd.h:
+    sow_forward_skinny).  `layers`: one (x2, A, B, acc_down, bias, scale) per layer -- x2 [T, d_in] bf16 / f16, acc_down the
+    dense accumulator or None.  Returns the list of outputs, or None when the library refuses the set (nothing was launched:
+    the caller runs sow_forward / LayerGroup instead)."""
+    lib = _lib.load()
+    n = len(layers)
+    if n == 0:
+        return []
+    if n > SKINNY_MAX_LAYERS:
+        return None
+    x0 = layers[0][0]
+    dt = _dt(x0)
+    keep, sizes, total = [], [], 0
+    for x2, A, B, acc_down, bias, scale in layers:
+        dev = _need_gpu(x2, A, B, acc_down, bias)
+        if dev != x0.device or any(t is not None and t.dtype != x0.dtype for t in (x2, A, B, acc_down, bias)):
+            raise TypeError("sow_amd.sow_forward_skinny: all tensors of a call share one dtype and one device")
+        T, d_in = x2.shape
+        r, d_out = B.shape
+        if tuple(A.shape) != (d_in, r) or (acc_down is not None and tuple(acc_down.shape) != (d_in, d_out)) or (
+                bias is not None and tuple(bias.shape) != (d_out,)):
+            raise ValueError("sow_amd.sow_forward_skinny: operand shapes do not match")
+        kind = _lib.ACC_NONE if acc_down is None else _lib.ACC_DENSE
+        nws = skinny_workspace_bytes(T, d_in, d_out, r, kind, dt) if T else 0
+        if T and not nws:
+            return None
+        nws = (nws + 255) & ~255
+        keep.append((x2.contiguous(), A.contiguous(), B.contiguous(), None if acc_down is None else acc_down.contiguous(),
+                     None if bias is None else bias.contiguous()))
+        sizes.append((total, nws))
+        total += nws
+    ws = _ws(total, x0.device)       # one allocation, carved at 256-byte offsets
+    base = ws.data_ptr()
+    arr = (_lib.LayerArgs * n)()
+    ys = []
+    for i, ((x2, A, B, acc_down, bias), (off, nws), layer) in enumerate(zip(keep, sizes, layers)):
+        y = torch.empty((x2.shape[0], B.shape[1]), dtype=x2.dtype, device=x0.device)
+        ys.append(y)
+        a = arr[i]
+        a.x, a.A, a.B, a.acc_down, a.bias, a.y = _ptr(x2), _ptr(A), _ptr(B), _ptr(acc_down), _ptr(bias), _ptr(y)
+        a.T, a.d_in, a.d_out, a.r_live = x2.shape[0], x2.shape[1], B.shape[1], B.shape[0]
+        a.acc_kind = _lib.ACC_NONE if acc_down is None else _lib.ACC_DENSE
+        a.scale = float(layer[5])
+        a.workspace, a.workspace_bytes = base + off, nws
+    idx = x0.device.index if x0.device.index is not None else torch.cuda.current_device()
+    if idx == torch.cuda.current_device():
+        rc = lib.sow_forward_skinny(arr, n, dt, _stream(x0.device))
+    else:
+        with torch.cuda.device(idx):
+            rc = lib.sow_forward_skinny(arr, n, dt, _stream(x0.device))
+    if rc == _lib.ERR_UNSUPPORTED:
+        return None
+    _lib.check(rc, "sow_forward_skinny")
+    return ys
+
+
 def workspace_bytes(T: int, d_in: int, d_out: int, r: int, r_acc: int, kind: int, dtype: torch.dtype,
                     param_f32: bool = False) -> int:
     return _workspace_bytes(_lib.load(), T, d_in, d_out, r, r_acc, kind, _DT[dtype] | (_lib.PARAM_F32 if param_f32 else 0))
