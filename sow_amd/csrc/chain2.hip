@@ -396,7 +396,8 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
       }
     } else {
       // scale, mask rank rows >= r (overlap garbage / zeros), round to bf16; the saved copy [M, 64] (scaled live columns,
-      // zeros, and 1.0 in column 63 when free -- the dbias trick of the skinny-TN kernel) is written as 8-byte row pieces
+      // zeros, and 1.0 in column 63 when free -- the dbias trick of the skinny-TN kernel) leaves as whole rows through an LDS
+      // image (h_rows), or straight from the registers as 8-byte row pieces
       float hv[16];
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
@@ -407,7 +408,20 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
       for (int a = 0; a < 2; ++a)
         own[a] = (u32x4){pack16x2<T>(hv[8 * a + 0], hv[8 * a + 1]), pack16x2<T>(hv[8 * a + 2], hv[8 * a + 3]),
                          pack16x2<T>(hv[8 * a + 4], hv[8 * a + 5]), pack16x2<T>(hv[8 * a + 6], hv[8 * a + 7])};
-      if (p.Hsave && tok < p.M) {
+      if (p.Hsave && p.h_rows) {
+        // row-major image [32 tok][64] of the saved copy in the X slot two past the last stage (free: both waves of the token
+        // group passed the barrier of stage nst - 1, so nobody reads the slots of stages nst - 2 and nst - 3 any more); 16-byte
+        // chunks XOR-swizzled by the row like an X stage.  Written out after the hand-off barrier as whole rows.
+        // (Slot (nst + 1) % C2_DEPTH differs from the exchange slot nst % C2_DEPTH and from the slot of stage nst - 1 only
+        // while C2_DEPTH >= 3, which the static_assert on the ring split guarantees.)
+        char* img = ring + ((nst + 1) % C2_DEPTH) * C2_STAGE + li * 128 + lh * 8;
+#pragma unroll
+        for (int rq = 0; rq < 4; ++rq) {
+          u32x2 v = {pack16x2<T>(hv[4 * rq + 0], hv[4 * rq + 1]), pack16x2<T>(hv[4 * rq + 2], hv[4 * rq + 3])};
+          if (hh == 1 && rq == 3 && lh == 1 && rb < 64) v[1] = (v[1] & 0xffffu) | (DT<T>::one_bits << 16);  // column 63 <- 1.0
+          *(u32x2*)(img + (((hh * 4 + rq) ^ ((li >> 1) & 7)) * 16)) = v;
+        }
+      } else if (p.Hsave && tok < p.M) {
         T* Hs = (T*)p.Hsave + tok * 64 + hh * 32 + 4 * lh;
 #pragma unroll
         for (int rq = 0; rq < 4; ++rq) {
@@ -425,6 +439,27 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
     const uint32_t pa = ring_a + (uint32_t)((nst % C2_DEPTH) * C2_STAGE + (hh ^ 1) * 2048 + lane * 16);
     DS_READ_B128(oth[0], pa, 0);
     DS_READ_B128(oth[1], pa, 1024);
+    if (p.Hsave && p.h_rows && !p.Hpartial) {   // (the image exists only off the Hpartial path)
+      // the saved copy: this wave stores rows 16 hh .. 16 hh + 15 of the image, 8 lanes x 16 bytes per row, streaming (h / dh
+      // are next read by the weight-gradient pass; plain stores would leave dirty lines in the L2s at the end of the kernel).
+      // The reads return before the first barrier of phase 2, ahead of which no park tile is written into this slot.
+      u32x4 hr[2];
+      const uint32_t ia = ring_a + (uint32_t)(((nst + 1) % C2_DEPTH) * C2_STAGE);
+#pragma unroll
+      for (int pass = 0; pass < 2; ++pass) {
+        const int r = 16 * hh + pass * 8 + (lane >> 3);
+        DS_READ_B128(hr[pass], ia + (uint32_t)(r * 128 + (((lane & 7) ^ ((r >> 1) & 7)) * 16)), 0);
+      }
+      LGKM_WAIT0();
+#pragma unroll
+      for (int pass = 0; pass < 2; ++pass) {
+        const int64_t tk = tok0 + 16 * hh + pass * 8 + (lane >> 3);
+        if (tk < p.M) {
+          T* dst = (T*)p.Hsave + tk * 64 + (lane & 7) * 8;
+          store_b128_nt(dst, hr[pass]);
+        }
+      }
+    }
     LGKM_WAIT0();
     hf[0] = hh ? oth[0] : own[0], hf[1] = hh ? oth[1] : own[1];   // (hh is wave-uniform; no dynamic register indexing)
     hf[2] = hh ? own[0] : oth[0], hf[3] = hh ? own[1] : oth[1];
@@ -481,7 +516,7 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
         // L2s are not coherent with each other): 512 -> 512 forward 23.0 -> 19.7 us per launch, step 4.48 -> 4.23 ms.
         // ("sc0 sc1" write-through: 22.3 us; "sc0 sc1 nt": 19.2 us -- no better than nt alone.)
         const u32x4 ov = {pack16x2<T>(v[0], v[1]), pack16x2<T>(v[2], v[3]), pack16x2<T>(v[4], v[5]), pack16x2<T>(v[6], v[7])};
-        if (p.nt_store) asm volatile("global_store_dwordx4 %0, %1, off nt" ::"v"(dst), "v"(ov) : "memory");
+        if (p.nt_store) store_b128_nt(dst, ov);
         else *(u32x4*)dst = ov;
       }
     }
@@ -526,7 +561,7 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
             for (int e = 0; e < 8; ++e) v[e] += (float)bb[e];
           }
           const u32x4 ov = {pack16x2<T>(v[0], v[1]), pack16x2<T>(v[2], v[3]), pack16x2<T>(v[4], v[5]), pack16x2<T>(v[6], v[7])};
-          if (p.nt_store) asm volatile("global_store_dwordx4 %0, %1, off nt" ::"v"(dst), "v"(ov) : "memory");
+          if (p.nt_store) store_b128_nt(dst, ov);
           else *(u32x4*)dst = ov;
         }
       }
@@ -543,7 +578,7 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
     const int64_t tk = tok0 + r;
     if (tk < p.M && col < D2) {
       T* dst = Y + tk * p.ldy + col;
-      if (p.nt_store) asm volatile("global_store_dwordx4 %0, %1, off nt" ::"v"(dst), "v"(ov) : "memory");
+      if (p.nt_store) store_b128_nt(dst, ov);
       else *(u32x4*)dst = ov;
     }
   };
@@ -769,6 +804,7 @@ int launch_chain2_group(const ChainParams* ps, int n, bool bwd, int dtype, hipSt
     g.p[i] = p;
     g.p[i].nt_store = sw_on(SW_NO_NT_STORE) ? 0 : 1;
     g.p[i].nt_load = sw_on(SW_NT_LOAD) ? 1 : 0;
+    g.p[i].h_rows = sw_on(SW_NO_H_ROWS) ? 0 : 1;
     g.p[i].pair_flush = sw_on(SW_NO_PAIR_FLUSH) ? 0 : 1;
     g.start[i] = (int)total;
     total += chain2_grid(p);

@@ -57,6 +57,12 @@ __device__ __forceinline__ void dma16_nt(const void* src, char* lds_dst) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                    (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 2);
 }
+// 16-byte global store with the non-temporal hint.  gfx950 needs two wait states between a store of more than 8 bytes and
+// a VALU write to its data registers; the compiler's hazard recognizer does not look into an asm statement and is free to
+// reuse those registers in the next instruction, so the statement carries the wait states itself.
+__device__ __forceinline__ void store_b128_nt(void* dst, u32x4 v) {
+  asm volatile("global_store_dwordx4 %0, %1, off nt\n\ts_nop 1" ::"v"(dst), "v"(v) : "memory");
+}
 __device__ __forceinline__ bf16x8 as_bf16x8(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
 __device__ __forceinline__ u32x4 join2(u32x2 lo, u32x2 hi) { return (u32x4){lo[0], lo[1], hi[0], hi[1]}; }
 // ---- fp32 on the bf16 matrix pipe ("3 x bf16"): x = hi + mid + lo with three bf16 values that hold the 24 mantissa bits
