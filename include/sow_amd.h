@@ -79,6 +79,28 @@ extern "C" {
  *     the DATA phase of backward) -- and the calls stay capturable (no host synchronisation, no allocation). */
 #define SOW_PARAM_F32 0x100
 
+/* Permission to fuse a low-rank accumulator with the live term: OR-ed into the dtype like SOW_PARAM_F32.  The library MAY
+ * then compute the SOW_ACC_LOWRANK term and the live term of a layer in one pass over the token rows (chain_wide_acc.hip)
+ * instead of one chain launch per term.  It acts in sow_forward, in the SOW_BWD_DATA phase of sow_backward /
+ * sow_backward_ex, in the per-layer fall-through of sow_forward_group / sow_backward_group, and in sow_workspace_bytes /
+ * sow_forward_workspace_bytes; every other entry point that takes a dtype accepts the flag and ignores it.  It is a
+ * permission, never a demand: a flagged call outside the admitted set runs exactly what the unflagged call runs and returns
+ * what it returns (never SOW_ERR_UNSUPPORTED because of the flag).  Admitted:
+ *   - compute dtype bf16 or f16 WITHOUT SOW_PARAM_F32 (with it the permission is ignored);
+ *   - SOW_ACC_LOWRANK, even r_live in [2, 64], even r_acc >= 2, r_acc + r_live <= 256, d_in and d_out multiples of 8;
+ *   - at call time: 16-byte-aligned x / y / dY / dX / bias / h_save, a workspace of at least the FLAGGED query (which is the
+ *     unflagged plan with a factor-pack region for r_acc + r_live columns, so a flagged workspace also serves the unflagged
+ *     call; sow_forward_workspace_bytes is non-zero for an admitted flagged shape), and the NO_FUSED_ACC switch off.  The
+ *     queries are pure functions of (shape, dtype with flags): NO_FUSED_ACC does not change them.
+ * Rounding contract of the fused pass (u = the compute dtype's rounding, products and sums in fp32):
+ *   forward   h_acc = rn(x Q), h_live = rn(scale * x A) = h_save (the r_live <= 64 layout), y = rn(h_acc R + h_live B + bias);
+ *   backward  dh_acc = rn(dY R^T), dh_live = rn(scale * dY B^T) = dh (the workspace, as the two-pass path leaves it),
+ *             dX = rn(dh_acc Q^T + dh_live A^T).
+ * The projections are the values the unflagged path rounds; y / dX are rounded ONCE (the unflagged path rounds the
+ * accumulator term to y / dX and adds the live term with a second rounding).  Fixed summation order: repeatable bits.  The
+ * weight-gradient phases are the unflagged ones; they read h_save and dh as written here. */
+#define SOW_FUSE_ACC 0x200
+
 #define SOW_OK 0
 #define SOW_ERR_NULL (-1)
 #define SOW_ERR_SHAPE (-2)
@@ -101,7 +123,7 @@ const char* sow_error_string(int code);
  * never touches them.  They are the library's ONLY process-wide state: a table of atomics initialised from the
  * environment (SOW_AMD_<NAME>) once, at first use; no launch path calls getenv.  Names: FORCE_CHAIN_V1, NO_SHORT_SPLIT,
  * NO_FUSED_H, FORCE_GEMM_V1, TN_NARROW, NO_GEMM3S, NO_GROUPED, NO_PERSIST, NO_NT_STORE, NT_LOAD, NO_PAIR_FLUSH, F32_EXACT, NO_PARK16, TN_NO_NT_LOAD, NO_TN_ROWS, NO_GEMM4H, NO_CHAIN3F, NO_TN_F32Q, NO_SPLITK,
- * NO_WIDE_CHAIN, NO_SHARED_X, NO_RAGGED, NO_RAGGED_GEMM, NO_BLOCKED_QR, NO_SKINNY
+ * NO_WIDE_CHAIN, NO_SHARED_X, NO_RAGGED, NO_RAGGED_GEMM, NO_BLOCKED_QR, NO_SKINNY, NO_H_ROWS, NO_FUSED_ACC
  * (value 1 = on, -1 / 0 = off) and GEMM3S, GEMM3, GEMM4
  * (1 = force, 0 = forbid, -1 = automatic).  sow_set_switch returns SOW_ERR_UNSUPPORTED for an unknown name;
  * sow_get_switch returns the value (-1 / 0 / 1).  Changing a switch while other threads launch is safe (atomic) but

@@ -54,7 +54,7 @@ static const char* const kSwitchNames[SW_COUNT] = {"FORCE_CHAIN_V1", "NO_SHORT_S
                                                    "NO_GEMM3S",      "GEMM3S",         "GEMM3",      "NO_GROUPED",     "NO_PERSIST",     "NO_NT_STORE",    "NT_LOAD",        "NO_PAIR_FLUSH",  "F32_EXACT",
                                                    "NO_PARK16",      "TN_NO_NT_LOAD",  "NO_TN_ROWS",     "GEMM4",          "NO_GEMM4H",      "NO_CHAIN3F",     "NO_TN_F32Q",     "NO_SPLITK",
                                                    "NO_WIDE_CHAIN",  "NO_SHARED_X",    "NO_RAGGED",      "NO_RAGGED_GEMM", "NO_BLOCKED_QR",
-                                                   "NO_SKINNY",      "NO_H_ROWS"};
+                                                   "NO_SKINNY",      "NO_FUSED_ACC",   "NO_H_ROWS"};
 static std::atomic<int> g_switch[SW_COUNT];
 static std::once_flag g_switch_once;
 static void switches_from_env() {
@@ -81,13 +81,18 @@ static inline bool ok_dtype(int d) { return d == SOW_F32 || d == SOW_BF16 || d =
 static inline bool al4p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 static inline bool al16p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // SOW_PARAM_F32: the compute dtype of a flagged dtype (*pf = flag present); -1 for a combination no layer entry point takes
+// SOW_FUSE_ACC is stripped here: the entry points where the permission acts read it with fuse_of() first
 static inline int split_dtype(int d, bool* pf) {
+  d &= ~SOW_FUSE_ACC;
   *pf = (d & SOW_PARAM_F32) != 0;
   const int cd = d & ~SOW_PARAM_F32;
   if (!ok_dtype(cd) || (*pf && cd == SOW_F32)) return -1;
   return cd;
 }
 static inline bool flagged(int d) { return (d & SOW_PARAM_F32) != 0; }
+// SOW_FUSE_ACC: the permission is ignored together with SOW_PARAM_F32
+static inline bool fuse_of(int d) { return (d & SOW_FUSE_ACC) != 0 && !flagged(d); }
+static inline int nofuse(int d) { return d & ~SOW_FUSE_ACC; }
 
 // ---- short inputs ---------------------------------------------------------------------------------
 // T / 64 workgroups cannot fill 256 CUs: below SHORT_NTB token blocks the streaming chain is launched as
@@ -160,7 +165,7 @@ static int gemm_auto(const void* A, int64_t lda, const void* B, int64_t ldb, boo
 
 extern "C" {
 
-int sow_version(void) { return 118; }
+int sow_version(void) { return 119; }
 
 int sow_set_switch(const char* name, int value) {
   if (!name) return SOW_ERR_NULL;
@@ -225,11 +230,15 @@ static int rag_dense_product(const void* A, int64_t lda, const void* B, int64_t 
 struct WsPlan {
   size_t off_dh, off_t, off_apad, off_hp, off_p0, off_p1, off_planes, planes_bytes, off_sk, sk_bytes, off_wide, wide_bytes,
       off_pw, pw_bytes, total;
+  bool fused;   // the plan holds the pack region of the fused accumulator pass (SOW_FUSE_ACC on an admitted shape)
   int ns, slab_len;
   int ns_cap;   // slabs the partial regions can hold (group-planned slab counts may exceed the single-layer choice)
 };
 constexpr int64_t C3F_MIN_T = 8192;   // chain3f_supported's threshold
-static WsPlan plan_ws(int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, int dtype) {
+// fuse: the caller's SOW_FUSE_ACC permission.  On an admitted shape the wide region also holds the factors of the fused pass
+// (r_acc + r_live columns); such a layer has r_live <= 64, so the region is the plan's last and every other offset is the
+// unflagged plan's: a flagged workspace serves the unflagged kernels as it is.  A pure function of its arguments.
+static WsPlan plan_ws(int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, int dtype, bool fuse = false) {
   WsPlan w{};
   const size_t es = esize(dtype);
   size_t off = 0;
@@ -281,10 +290,13 @@ static WsPlan plan_ws(int64_t T, int d_in, int d_out, int r_live, int r_acc, int
     if (acc_kind == SOW_ACC_LOWRANK && chain_wide_shape_ok(r_acc, d_in, d_out, dtype) && r_acc > rw) rw = r_acc;
     // ragged layer: the factors of its live term or of its low-rank accumulator, whichever is wider
     if (rag_layer(r_live, r_acc, acc_kind, d_in, d_out, dtype)) rw = acc_kind == SOW_ACC_LOWRANK && r_acc > r_live ? r_acc : r_live;
-    if (rw) {
-      w.wide_bytes = chain_wide_pack_bytes(rw, d_in, d_out);
-      off += al256(w.wide_bytes);
+    if (rw) w.wide_bytes = chain_wide_pack_bytes(rw, d_in, d_out);
+    w.fused = fuse && acc_kind == SOW_ACC_LOWRANK && fused_acc_shape_ok(r_live, r_acc, d_in, d_out, dtype);
+    if (w.fused) {
+      const size_t fb = chain_wide_pack_bytes(r_acc + r_live, d_in, d_out);
+      if (fb > w.wide_bytes) w.wide_bytes = fb;
     }
+    off += al256(w.wide_bytes);
   }
   // token-slab partials of the wide weight-gradient kernel (skinny_tn_wide.hip)
   w.off_pw = off;
@@ -430,6 +442,7 @@ int sow_reduce_batch(const void* descs, const int* starts, int n, int total_bloc
 
 size_t sow_forward_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, int dtype) {
   bool pf;
+  const bool fuse = fuse_of(dtype);
   dtype = split_dtype(dtype, &pf);
   if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0 || dtype < 0) return 0;
   if (pf) {   // the forward's own scratch (if any) followed by the packed parameters (pack_layer)
@@ -438,24 +451,25 @@ size_t sow_forward_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, i
     return own ? own + pack : pack + 256;
   }
   const bool wide_acc = acc_kind == SOW_ACC_LOWRANK && r_acc > 64;
-  const WsPlan w = plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, dtype);
-  if (!wide_acc && r_live <= 64 && short_hp_bytes(T, d_in, d_out, r_live, dtype) == 0 && w.planes_bytes == 0 && w.sk_bytes == 0)
+  const WsPlan w = plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, dtype, fuse);
+  if (!w.fused && !wide_acc && r_live <= 64 && short_hp_bytes(T, d_in, d_out, r_live, dtype) == 0 && w.planes_bytes == 0 && w.sk_bytes == 0)
     return 0;   // the forward does not touch it
   return w.total + 256;
 }
 
 size_t sow_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, int dtype) {
   bool pf;
+  const bool fuse = fuse_of(dtype);
   dtype = split_dtype(dtype, &pf);
   if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0 || dtype < 0) return 0;
   const size_t pack = pf ? pack_bytes(d_in, d_out, r_live, acc_kind == SOW_ACC_LOWRANK ? r_acc : 0, acc_kind) : 0;
-  return plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, dtype).total + pack + 256;
+  return plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, dtype, fuse).total + pack + 256;
 }
 
 
 static int forward_impl(const void* x, const void* A, const void* B, const void* acc_down, const void* acc_up, const void* bias,
                         void* y, void* h_save, int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, float scale,
-                        int dtype, void* workspace, size_t workspace_bytes, void* stream_) {
+                        int dtype, void* workspace, size_t workspace_bytes, void* stream_, bool fuse = false) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!ok_dtype(dtype)) return SOW_ERR_DTYPE;
   if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0) return SOW_ERR_SHAPE;
@@ -468,6 +482,20 @@ static int forward_impl(const void* x, const void* A, const void* B, const void*
   char* ws = workspace ? ws_base(workspace) : nullptr;
   float beta = 0.f;
   int rc;
+  // SOW_FUSE_ACC on an admitted call: the accumulator term and the live term as one chain (chain_wide_acc.hip), y written
+  // once.  Anything else falls through to the unflagged path, unchanged.
+  if (fuse && !sw_on(SW_NO_FUSED_ACC) && ws && al16p(x) && al16p(y) && al16p(bias) && al16p(h_save)) {
+    const WsPlan wf = plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, dtype, true);
+    if (wf.fused && workspace_bytes >= wf.total + 255) {
+      WideAccArgs a{};
+      a.X = x, a.Y = y, a.Fa1 = acc_down, a.Fl1 = A, a.Fa2 = acc_up, a.Fl2 = B;
+      a.ldfa1 = r_acc, a.ldfl1 = r_live, a.ldfa2 = d_out, a.ldfl2 = d_out;
+      a.Hsave = h_save, a.bias = bias, a.M = T, a.D1 = d_in, a.D2 = d_out, a.r_acc = r_acc, a.r_live = r_live;
+      a.scale = scale, a.bwd = 0, a.pack = ws + wf.off_wide, a.pack_bytes = wf.wide_bytes;
+      rc = launch_chain_wide_acc(a, dtype, stream);
+      if (rc != SOW_ERR_UNSUPPORTED) return rc;
+    }
+  }
   // ragged widths: the fused chain for the low-rank accumulator (scale 1) and the live term, X read once per term; h_save
   // holds the unscaled projection (the wide contract); a dense accumulator's product x . W_acc is written by gemm_rag first.
   // Without workspace or with views off 16 bytes, the generic kernels below.
@@ -581,8 +609,8 @@ int sow_forward(const void* x, const void* A, const void* B, const void* acc_dow
   const int cd = split_dtype(dtype, &pf);
   if (cd < 0) return SOW_ERR_DTYPE;
   if (!pf)
-    return forward_impl(x, A, B, acc_down, acc_up, bias, y, h_save, T, d_in, d_out, r_live, r_acc, acc_kind, scale, dtype,
-                        workspace, workspace_bytes, stream);
+    return forward_impl(x, A, B, acc_down, acc_up, bias, y, h_save, T, d_in, d_out, r_live, r_acc, acc_kind, scale, cd,
+                        workspace, workspace_bytes, stream, fuse_of(dtype));
   // fp32 parameters: the same checks as forward_impl before the pack launch reads them
   if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0) return SOW_ERR_SHAPE;
   if (T == 0) return SOW_OK;
@@ -604,7 +632,7 @@ int sow_forward(const void* x, const void* A, const void* B, const void* acc_dow
 static int backward_impl(const void* dy, const void* x, const void* h_save, const void* A, const void* B, const void* acc_down,
                          const void* acc_up, void* dx, void* dA, void* dB, void* dbias, int64_t T, int d_in, int d_out,
                          int r_live, int r_acc, int acc_kind, float scale, float grad_beta, int dtype, int gdt, void* workspace,
-                         size_t workspace_bytes, int phases, void* stream_) {
+                         size_t workspace_bytes, int phases, void* stream_, bool fuse = false) {
   hipStream_t stream = (hipStream_t)stream_;
   bool do_data = (phases & SOW_BWD_DATA) != 0;
   const bool do_partial = (phases & (SOW_BWD_WEIGHTS | SOW_BWD_WEIGHTS_PARTIAL)) != 0;
@@ -635,6 +663,21 @@ static int backward_impl(const void* dy, const void* x, const void* h_save, cons
   float beta = 0.f;
   int rc;
   bool data_done = false;
+  // SOW_FUSE_ACC on an admitted call: dX of the accumulator and of the live term as one chain (chain_wide_acc.hip), dh left
+  // in the workspace as the two-pass path leaves it; the weight phases below are the unflagged ones
+  if (do_data && fuse && !sw_on(SW_NO_FUSED_ACC) && al16p(dy) && al16p(dx)) {
+    const WsPlan wf = plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, dtype, true);
+    if (wf.fused && workspace_bytes >= wf.total + 255) {
+      WideAccArgs a{};
+      a.X = dy, a.Y = dx, a.Fa1 = acc_up, a.Fl1 = B, a.Fa2 = acc_down, a.Fl2 = A;
+      a.ldfa1 = d_out, a.ldfl1 = d_out, a.ldfa2 = r_acc, a.ldfl2 = r_live;
+      a.Hsave = dh, a.bias = nullptr, a.M = T, a.D1 = d_out, a.D2 = d_in, a.r_acc = r_acc, a.r_live = r_live;
+      a.scale = scale, a.bwd = 1, a.pack = ws + wf.off_wide, a.pack_bytes = wf.wide_bytes;
+      rc = launch_chain_wide_acc(a, dtype, stream);
+      if (rc && rc != SOW_ERR_UNSUPPORTED) return rc;
+      if (!rc) do_data = false;
+    }
+  }
   // ragged widths: the fused chain for the data gradient (dY and dX views 16-byte aligned, else the generic kernels below:
   // they leave the same dh) and skinny_tn_wide for every weight gradient, dbias included, in the PARTIAL phase
   const bool rag_w = rag_layer(r_live, r_acc, acc_kind, d_in, d_out, dtype) && !sw_on(SW_NO_RAGGED);
@@ -807,7 +850,7 @@ int sow_backward_ex(const void* dy, const void* x, const void* h_save, const voi
   const int cd = split_dtype(dtype, &pf);
   if (!pf)
     return backward_impl(dy, x, h_save, A, B, acc_down, acc_up, dx, dA, dB, dbias, T, d_in, d_out, r_live, r_acc, acc_kind, scale,
-                         grad_beta, dtype, dtype, workspace, workspace_bytes, phases, stream);
+                         grad_beta, nofuse(dtype), nofuse(dtype), workspace, workspace_bytes, phases, stream, fuse_of(dtype));
   if (cd < 0) return SOW_ERR_DTYPE;
   // fp32 parameters: only the data gradient reads the factors (and the accumulator); they are packed when it runs
   if ((phases & SOW_BWD_DATA) && T > 0) {
@@ -914,7 +957,7 @@ static int pack_group(const sow_layer_args* layers, int n, int cd, bool bwd, std
   return launch_pack_params(items.data(), (int)items.size(), cd, (hipStream_t)stream);
 }
 
-static int forward_group_impl(const sow_layer_args* layers, int n, int dtype, void* stream_) {
+static int forward_group_impl(const sow_layer_args* layers, int n, int dtype, void* stream_, bool fuse = false) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!ok_dtype(dtype)) return SOW_ERR_DTYPE;
   if (n < 0) return SOW_ERR_SHAPE;
@@ -957,7 +1000,7 @@ static int forward_group_impl(const sow_layer_args* layers, int n, int dtype, vo
       continue;
     }
     rc = sow_forward(L.x, L.A, L.B, L.acc_down, L.acc_up, L.bias, L.y, L.h_save, L.T, L.d_in, L.d_out, L.r_live, L.r_acc,
-                     L.acc_kind, L.scale, dtype, L.workspace, L.workspace_bytes, stream_);
+                     L.acc_kind, L.scale, fuse ? dtype | SOW_FUSE_ACC : dtype, L.workspace, L.workspace_bytes, stream_);
     if (rc) return rc;
   }
   if (ng && (rc = launch_gemm2h_group(gbatch, ng, false, stream))) return rc;
@@ -968,7 +1011,7 @@ int sow_forward_group(const sow_layer_args* layers, int n, int dtype, void* stre
   bool pf;
   const int cd = split_dtype(dtype, &pf);
   if (cd < 0) return SOW_ERR_DTYPE;
-  if (!pf || n <= 0 || !layers) return forward_group_impl(layers, n, cd, stream);
+  if (!pf || n <= 0 || !layers) return forward_group_impl(layers, n, cd, stream, fuse_of(dtype));
   std::vector<sow_layer_args> packed;
   const int rc = pack_group(layers, n, cd, false, packed, stream);
   return rc ? rc : forward_group_impl(packed.data(), n, cd, stream);
@@ -995,6 +1038,7 @@ static SkWs skinny_ws(int64_t T, int d_in, int d_out, int acc_kind) {
 }
 
 size_t sow_forward_skinny_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype) {
+  dtype = nofuse(dtype);
   if (!skinny_shape_ok(T, d_in, d_out, r_live, acc_kind, dtype)) return 0;
   return skinny_ws(T, d_in, d_out, acc_kind).total;
 }
@@ -1033,7 +1077,8 @@ int sow_forward_skinny(const sow_layer_args* layers, int n, int dtype, void* str
   return launch_skinny_fwd(sk, m, cd, (hipStream_t)stream);
 }
 
-static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, int gdt, int phases, void* stream_) {
+static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, int gdt, int phases, void* stream_,
+                               bool fuse = false) {
   hipStream_t stream = (hipStream_t)stream_;
   const bool do_data = (phases & SOW_BWD_DATA) != 0;
   const bool do_partial = (phases & (SOW_BWD_WEIGHTS | SOW_BWD_WEIGHTS_PARTIAL)) != 0;
@@ -1049,7 +1094,7 @@ static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, i
   auto single = [&](const sow_layer_args& L, int ph) {
     return backward_impl(L.dy, L.x, L.h_save, L.A, L.B, L.acc_down, L.acc_up, L.dx, L.dA, L.dB, L.dbias, L.T, L.d_in, L.d_out,
                          L.r_live, L.r_acc, L.acc_kind, L.scale, L.grad_beta, dtype, gdt, L.workspace, L.workspace_bytes, ph,
-                         stream_);
+                         stream_, fuse);
   };
   auto plan = [&](const sow_layer_args& L) {
     return plan_ws(L.T, L.d_in, L.d_out, L.r_live, L.acc_kind == SOW_ACC_LOWRANK ? L.r_acc : 0, L.acc_kind, dtype);
@@ -1161,7 +1206,7 @@ static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, i
 int sow_backward_group(const sow_layer_args* layers, int n, int dtype, int phases, void* stream) {
   bool pf;
   const int cd = split_dtype(dtype, &pf);
-  if (!pf) return backward_group_impl(layers, n, dtype, dtype, phases, stream);
+  if (!pf) return backward_group_impl(layers, n, nofuse(dtype), nofuse(dtype), phases, stream, fuse_of(dtype));
   if (cd < 0) return SOW_ERR_DTYPE;
   if (n <= 0 || !layers || !(phases & SOW_BWD_DATA)) return backward_group_impl(layers, n, cd, SOW_F32, phases, stream);
   std::vector<sow_layer_args> packed;
@@ -1188,6 +1233,7 @@ static void shared_fill_dx(const sow_layer_args* layers, int n, sow_layer_args* 
 }
 
 int sow_forward_shared(const sow_layer_args* layers, int n, int dtype, void* stream) {
+  dtype = nofuse(dtype);
   if (!ok_dtype(dtype & ~SOW_PARAM_F32)) return SOW_ERR_DTYPE;
   int rc;
   if ((rc = shared_common(layers, n, false))) return rc;
@@ -1201,6 +1247,7 @@ int sow_forward_shared(const sow_layer_args* layers, int n, int dtype, void* str
 }
 
 int sow_backward_shared(const sow_layer_args* layers, int n, int dtype, int phases, void* stream) {
+  dtype = nofuse(dtype);
   if (!ok_dtype(dtype & ~SOW_PARAM_F32)) return SOW_ERR_DTYPE;
   int rc;
   if ((rc = shared_common(layers, n, true))) return rc;
@@ -1289,6 +1336,7 @@ int sow_gemm(const void* A, int64_t lda, int trans_a, const void* B, int64_t ldb
 }
 
 size_t sow_gemm_workspace_bytes(int64_t M, int N, int K, int trans_a, int dtype) {
+  dtype = nofuse(dtype);
   if (trans_a || (dtype != SOW_BF16 && dtype != SOW_F16) || M <= 0 || N <= 0 || K <= 0) return 0;
   return gemm4_splitk_bytes(M, N, K, false);
 }
@@ -1296,6 +1344,7 @@ size_t sow_gemm_workspace_bytes(int64_t M, int N, int K, int trans_a, int dtype)
 int sow_gemm_ex(const void* A, int64_t lda, int trans_a, const void* B, int64_t ldb, int trans_b, void* C, int64_t ldc,
                 const void* bias, int64_t M, int N, int K, float alpha, float beta, int dtype, void* workspace,
                 size_t workspace_bytes, void* stream) {
+  dtype = nofuse(dtype);
   if (flagged(dtype)) return SOW_ERR_DTYPE;   // SOW_PARAM_F32 is for the layer entry points only
   if (!trans_a)
     return gemm_auto(A, lda, B, ldb, trans_b != 0, C, ldc, bias, M, N, K, alpha, beta, dtype, (hipStream_t)stream, workspace,
@@ -1334,6 +1383,7 @@ static QrPlan plan_qr(int m, int n, int k, int in_dtype, int need_r, int out_dty
 }
 
 size_t sow_qr_workspace_bytes(int m, int n, int k, int in_dtype, int need_r) {
+  in_dtype = nofuse(in_dtype);
   if (m <= 0 || n <= 0 || k <= 0) return 0;
   return plan_qr(m, n, k, in_dtype, need_r, 0).total_thin + 256;
 }
@@ -1341,6 +1391,7 @@ size_t sow_qr_workspace_bytes(int m, int n, int k, int in_dtype, int need_r) {
 int sow_qr_thin(const void* W, int64_t ldw, int m, int n, int in_dtype, int k, void* Q_out, int64_t ldq, void* R_out,
                 int64_t ldr, int out_dtype, void* workspace, size_t workspace_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
+  in_dtype = nofuse(in_dtype), out_dtype = nofuse(out_dtype);
   if (!ok_dtype(in_dtype) || !ok_dtype(out_dtype)) return SOW_ERR_DTYPE;   // rejects SOW_PARAM_F32 as well
   if (m <= 0 || n <= 0 || k <= 0 || k > m) return SOW_ERR_SHAPE;
   if (!W || !Q_out || !workspace) return SOW_ERR_NULL;
@@ -1398,6 +1449,7 @@ int sow_qr_thin(const void* W, int64_t ldw, int m, int n, int in_dtype, int k, v
 
 int sow_accumulate_batch(const sow_accumulate_args* items, int n, int dtype, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
+  dtype = nofuse(dtype);
   if (!ok_dtype(dtype)) return SOW_ERR_DTYPE;
   if (n < 0) return SOW_ERR_SHAPE;
   if (n == 0) return SOW_OK;
@@ -1438,6 +1490,7 @@ int sow_zero_state(void* const* ptrs, const int64_t* bytes, int n, void* stream)
 int sow_adamw_flat(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, float lr, double beta1,
                    double beta2, float eps, float weight_decay, int step, float grad_scale, int dtype, int state_dtype,
                    void* stream) {
+  dtype = nofuse(dtype), state_dtype = nofuse(state_dtype);
   if (flagged(dtype) || flagged(state_dtype)) return SOW_ERR_DTYPE;
   if (step < 1) return SOW_ERR_SHAPE;
   return launch_adamw_flat(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale,
@@ -1464,12 +1517,14 @@ int sow_small_inverse(const float* A, float* out, int batch, int r, void* stream
 }
 
 int sow_axpby(const void* x, void* y, int64_t n, float a, float b, int dtype, void* stream) {
+  dtype = nofuse(dtype);
   if (flagged(dtype)) return SOW_ERR_DTYPE;
   return launch_axpby(x, y, n, a, b, dtype, (hipStream_t)stream);
 }
 
 int sow_cast_copy(const void* src, int64_t lds, int src_dtype, void* dst, int64_t ldd, int dst_dtype, int64_t rows,
                   int cols, void* stream) {
+  src_dtype = nofuse(src_dtype), dst_dtype = nofuse(dst_dtype);
   if (flagged(src_dtype) || flagged(dst_dtype) || !ok_dtype(src_dtype) || !ok_dtype(dst_dtype)) return SOW_ERR_DTYPE;
   if (!src || !dst) return SOW_ERR_NULL;
   return launch_cast_copy(src, lds, src_dtype, dst, ldd, dst_dtype, rows, cols, (hipStream_t)stream);

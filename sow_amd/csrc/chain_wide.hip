@@ -25,9 +25,7 @@
 // natural alignment, exactly as in the aligned kernel.  F1T rows are padded to D1p = ceil8(D1) by the pack.  Y is
 // written element by element (2-byte stores): no byte of a token row is written by another workgroup, whatever D2.
 // The ragged kernel also takes 2 <= r <= 64 (r_pad = 64) for a layer's low-rank accumulator term, which saves no H.
-#include "kernels.hpp"
-#include "epilogue.hpp"
-#include "rag_load.hpp"
+#include "chain_wide_tile.hpp"
 
 namespace sow {
 
@@ -68,88 +66,18 @@ struct WideParams {
   int nt_store;
 };
 
-constexpr int CW_LDS = 65536, CW_PANEL = 64 * 64 * 2;
-
-template <typename T> __device__ __forceinline__ int cw_panel_off(int row, int k) {
-  return (k >> 6) * CW_PANEL + bf16_img_off<64>(row, (k & 63) >> 3) + (k & 7) * 2;
-}
-
 template <typename T, bool RAG> __global__ __launch_bounds__(256, 2) void chain_wide_kernel(const WideParams p) {
-  using V8 = typename DT<T>::v8;
   __shared__ __attribute__((aligned(16))) char smem[CW_LDS];
   char* big = smem;              // F1 image, then the H panels
   char* small = smem + 32768;    // X image, then the F2 panels / epilogue scratch
 
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6, li = lane & 31, lh = lane >> 5;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6, li = lane & 31;
   const int64_t t0 = (int64_t)blockIdx.x * 64;
-  const T* X = (const T*)p.X;
-  const T* F1T = (const T*)p.F1T;
-  const T* F2T = (const T*)p.F2T;
-  const int r_pad = p.r_pad, ntiles = 2 * (r_pad / 32), np = r_pad / 64;
-  // RAG: the workgroup's token rows as one buffer (base 16-byte aligned: X is, and t0 * D1 * 2 is a multiple of 128)
-  const int rows = p.M - t0 < 64 ? (int)(p.M - t0) : 64;
-  const uint32_t lim = (uint32_t)rows * (uint32_t)p.D1 * 2u;
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(X + t0 * p.D1), (short)0, (int)lim, 0x00020000);
+  const int r_pad = p.r_pad, ntiles = 2 * (r_pad / 32);
 
-  // ---- phase 1: H = X . F1 ------------------------------------------------------------------------------
+  // ---- phase 1: H = X . F1 (chain_wide_tile.hpp) ------------------------------------------------------------
   f32x16 acc[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
-  u32x4 xv[2], fv[8];
-  auto load1 = [&](int k0) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int idx = t + 256 * i, row = idx >> 3, c = idx & 7;
-      const int64_t gt = t0 + row;
-      const int gk = k0 + c * 8;
-      if constexpr (RAG)
-        xv[i] = (row < rows && gk < p.D1) ? rag_load8(rs, lim, row, p.D1, gk) : u32x4{0, 0, 0, 0};
-      else
-        xv[i] = (gt < p.M && gk < p.D1) ? *(const u32x4*)(X + gt * p.D1 + gk) : u32x4{0, 0, 0, 0};
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int idx = t + 256 * i, row = idx >> 3, c = idx & 7;
-      const int gk = k0 + c * 8;
-      fv[i] = (row < r_pad && gk < p.D1) ? *(const u32x4*)(F1T + (int64_t)row * p.ldf1t + gk) : u32x4{0, 0, 0, 0};
-    }
-  };
-  auto store1 = [&]() {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int idx = t + 256 * i;
-      *(u32x4*)(small + bf16_img_off<64>(idx >> 3, idx & 7)) = xv[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int idx = t + 256 * i;
-      if ((idx >> 3) < r_pad) *(u32x4*)(big + bf16_img_off<64>(idx >> 3, idx & 7)) = fv[i];
-    }
-  };
-  const int nk = (p.D1 + 63) / 64;
-  load1(0);
-  for (int kt = 0; kt < nk; ++kt) {
-    __syncthreads();
-    store1();
-    __syncthreads();
-    if (kt + 1 < nk) load1((kt + 1) * 64);
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const V8 a0 = *(const V8*)(small + bf16_img_off<64>(li, 2 * ks + lh));
-      const V8 a1 = *(const V8*)(small + bf16_img_off<64>(32 + li, 2 * ks + lh));
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int j = w + 4 * i;
-        if (j < ntiles) {
-          const V8 b = *(const V8*)(big + bf16_img_off<64>((j >> 1) * 32 + li, 2 * ks + lh));
-          acc[i] = mfma32((j & 1) ? a1 : a0, b, acc[i]);
-        }
-      }
-    }
-  }
-  __syncthreads();   // every wave is done with the F1 / X images
+  cw_phase1<T, RAG>(acc, big, small, (const T*)p.X, (const T*)p.F1T, p.M, t0, p.D1, p.ldf1t, r_pad);
 
   // ---- H (rounded once) -> LDS panels, then Hsave ---------------------------------------------------------
 #pragma unroll
@@ -174,43 +102,8 @@ template <typename T, bool RAG> __global__ __launch_bounds__(256, 2) void chain_
   }
 
   // ---- phase 2: Y = beta * Y + yscale * H . F2 + bias, 64 output columns at a time ------------------------
-  const int wm = w >> 1, wn = w & 1;
-  u32x4 gv[8];
-  auto load2 = [&](int n0) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int idx = t + 256 * i, pn = idx >> 9, row = (idx >> 3) & 63, c = idx & 7;
-      const int gn = n0 + row;
-      gv[i] = (pn < np && gn < p.D2) ? *(const u32x4*)(F2T + (int64_t)gn * r_pad + pn * 64 + c * 8) : u32x4{0, 0, 0, 0};
-    }
-  };
-  const int nn = (p.D2 + 63) / 64;
-  float* scratch = (float*)small + w * EpiScratch<1>::FLOATS;
-  load2(0);
-  for (int nb = 0; nb < nn; ++nb) {
-    __syncthreads();   // the previous tile's epilogue is done with the scratch
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int idx = t + 256 * i, pn = idx >> 9;
-      if (pn < np) *(u32x4*)(small + pn * CW_PANEL + bf16_img_off<64>((idx >> 3) & 63, idx & 7)) = gv[i];
-    }
-    __syncthreads();
-    if (nb + 1 < nn) load2((nb + 1) * 64);
-    f32x16 o;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) o[e] = 0.f;
-    for (int pn = 0; pn < np; ++pn) {
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        const V8 a = *(const V8*)(big + pn * CW_PANEL + bf16_img_off<64>(wm * 32 + li, 2 * ks + lh));
-        const V8 b = *(const V8*)(small + pn * CW_PANEL + bf16_img_off<64>(wn * 32 + li, 2 * ks + lh));
-        o = mfma32(a, b, o);
-      }
-    }
-    __syncthreads();   // the F2 panels are consumed: their space becomes the epilogue scratch
-    wave_store_tiles<T, 1, !RAG>(&o, scratch, (T*)p.Y, p.D2, t0 + wm * 32, nb * 64 + wn * 32, p.M, p.D2, p.yscale, p.beta,
-                                 (const T*)p.bias, lane, p.nt_store != 0);
-  }
+  cw_phase2<T, !RAG>(big, small, (const T*)p.F2T, (T*)p.Y, (const T*)p.bias, p.M, t0, p.D2, r_pad, p.yscale, p.beta,
+                     p.nt_store != 0);
 }
 
 bool chain_wide_shape_ok(int r, int d1, int d2, int dtype) {

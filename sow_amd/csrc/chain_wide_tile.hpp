@@ -1,0 +1,138 @@
+// Tile code shared by the fused wide chains (chain_wide.hip, chain_wide_acc.hip): one 64-token workgroup of 256 threads,
+// 64 KiB of LDS split into `big` (32 KiB: the F1 image [r_pad][64] of phase 1, then H as r_pad / 64 panels [64][64]) and
+// `small` (32 KiB: the X image [64][64] of phase 1, then the F2 panels [64][64] of phase 2, reused as the epilogue scratch).
+//   cw_phase1: acc = X . F1 over K = D1 in 64-wide steps; the H tiles (2 token halves x r_pad / 32 column tiles) are dealt
+//              round-robin to the waves: wave w owns tiles w, w + 4, ... (<= 4 each); tile j = token half j & 1, columns
+//              32 (j >> 1) ..; ends with a barrier (every wave done with the F1 / X images)
+//   (the caller rounds acc into the H panels at cw_panel_off, synchronises, saves what it saves)
+//   cw_phase2: Y = beta * Y + yscale * H . F2 + bias, 64 output columns at a time, wave (wm, wn) owns a 32 x 32 tile
+// The factors come packed: F1T [r_pad][ldf1t] (row c = column c of H), F2T [D2][r_pad] (row n = output column n).
+#pragma once
+#include "kernels.hpp"
+#include "epilogue.hpp"
+#include "rag_load.hpp"
+
+namespace sow {
+
+constexpr int CW_LDS = 65536, CW_PANEL = 64 * 64 * 2;
+
+// byte offset of H[row][k] in the phase-2 image
+template <typename T> __device__ __forceinline__ int cw_panel_off(int row, int k) {
+  return (k >> 6) * CW_PANEL + bf16_img_off<64>(row, (k & 63) >> 3) + (k & 7) * 2;
+}
+
+// RAG: D1 not a multiple of 8 -- a token row of X starts at any 2-byte offset (rag_load.hpp; X itself 16-byte aligned)
+template <typename T, bool RAG>
+__device__ __forceinline__ void cw_phase1(f32x16 (&acc)[4], char* big, char* small, const T* X, const T* F1T, int64_t M, int64_t t0,
+                                          int D1, int ldf1t, int r_pad) {
+  using V8 = typename DT<T>::v8;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6, li = lane & 31, lh = lane >> 5;
+  const int ntiles = 2 * (r_pad / 32);
+  // RAG: the workgroup's token rows as one buffer (base 16-byte aligned: X is, and t0 * D1 * 2 is a multiple of 128)
+  const int rows = M - t0 < 64 ? (int)(M - t0) : 64;
+  const uint32_t lim = (uint32_t)rows * (uint32_t)D1 * 2u;
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(X + t0 * D1), (short)0, (int)lim, 0x00020000);
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
+  u32x4 xv[2], fv[8];
+  auto load1 = [&](int k0) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int idx = t + 256 * i, row = idx >> 3, c = idx & 7;
+      const int64_t gt = t0 + row;
+      const int gk = k0 + c * 8;
+      if constexpr (RAG)
+        xv[i] = (row < rows && gk < D1) ? rag_load8(rs, lim, row, D1, gk) : u32x4{0, 0, 0, 0};
+      else
+        xv[i] = (gt < M && gk < D1) ? *(const u32x4*)(X + gt * D1 + gk) : u32x4{0, 0, 0, 0};
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int idx = t + 256 * i, row = idx >> 3, c = idx & 7;
+      const int gk = k0 + c * 8;
+      fv[i] = (row < r_pad && gk < D1) ? *(const u32x4*)(F1T + (int64_t)row * ldf1t + gk) : u32x4{0, 0, 0, 0};
+    }
+  };
+  auto store1 = [&]() {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int idx = t + 256 * i;
+      *(u32x4*)(small + bf16_img_off<64>(idx >> 3, idx & 7)) = xv[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int idx = t + 256 * i;
+      if ((idx >> 3) < r_pad) *(u32x4*)(big + bf16_img_off<64>(idx >> 3, idx & 7)) = fv[i];
+    }
+  };
+  const int nk = (D1 + 63) / 64;
+  load1(0);
+  for (int kt = 0; kt < nk; ++kt) {
+    __syncthreads();
+    store1();
+    __syncthreads();
+    if (kt + 1 < nk) load1((kt + 1) * 64);
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      const V8 a0 = *(const V8*)(small + bf16_img_off<64>(li, 2 * ks + lh));
+      const V8 a1 = *(const V8*)(small + bf16_img_off<64>(32 + li, 2 * ks + lh));
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int j = w + 4 * i;
+        if (j < ntiles) {
+          const V8 b = *(const V8*)(big + bf16_img_off<64>((j >> 1) * 32 + li, 2 * ks + lh));
+          acc[i] = mfma32((j & 1) ? a1 : a0, b, acc[i]);
+        }
+      }
+    }
+  }
+  __syncthreads();   // every wave is done with the F1 / X images
+}
+
+// VEC: D2 a multiple of 8 (16-byte row pieces of Y), else element by element
+template <typename T, bool VEC>
+__device__ __forceinline__ void cw_phase2(char* big, char* small, const T* F2T, T* Y, const T* bias, int64_t M, int64_t t0, int D2,
+                                          int r_pad, float yscale, float beta, bool nt) {
+  using V8 = typename DT<T>::v8;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6, li = lane & 31, lh = lane >> 5;
+  const int np = r_pad / 64, wm = w >> 1, wn = w & 1;
+  u32x4 gv[8];
+  auto load2 = [&](int n0) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int idx = t + 256 * i, pn = idx >> 9, row = (idx >> 3) & 63, c = idx & 7;
+      const int gn = n0 + row;
+      gv[i] = (pn < np && gn < D2) ? *(const u32x4*)(F2T + (int64_t)gn * r_pad + pn * 64 + c * 8) : u32x4{0, 0, 0, 0};
+    }
+  };
+  const int nn = (D2 + 63) / 64;
+  float* scratch = (float*)small + w * EpiScratch<1>::FLOATS;
+  load2(0);
+  for (int nb = 0; nb < nn; ++nb) {
+    __syncthreads();   // the previous tile's epilogue is done with the scratch
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int idx = t + 256 * i, pn = idx >> 9;
+      if (pn < np) *(u32x4*)(small + pn * CW_PANEL + bf16_img_off<64>((idx >> 3) & 63, idx & 7)) = gv[i];
+    }
+    __syncthreads();
+    if (nb + 1 < nn) load2((nb + 1) * 64);
+    f32x16 o;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) o[e] = 0.f;
+    for (int pn = 0; pn < np; ++pn) {
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        const V8 a = *(const V8*)(big + pn * CW_PANEL + bf16_img_off<64>(wm * 32 + li, 2 * ks + lh));
+        const V8 b = *(const V8*)(small + pn * CW_PANEL + bf16_img_off<64>(wn * 32 + li, 2 * ks + lh));
+        o = mfma32(a, b, o);
+      }
+    }
+    __syncthreads();   // the F2 panels are consumed: their space becomes the epilogue scratch
+    wave_store_tiles<T, 1, VEC>(&o, scratch, Y, D2, t0 + wm * 32, nb * 64 + wn * 32, M, D2, yscale, beta, bias, lane, nt);
+  }
+}
+
+}  // namespace sow

@@ -168,6 +168,31 @@ bool ragged_shape_ok(int r, int d1, int d2, int dtype);
 size_t chain_wide_pack_bytes(int r, int d_in, int d_out);
 // SOW_ERR_UNSUPPORTED when the shape, the alignment or the scratch does not suit the kernel (nothing launched)
 int launch_chain_wide(const WideArgs& a, int dtype, hipStream_t stream);
+// chain_wide_acc.hip (bf16 / f16; SOW_FUSE_ACC): a low-rank accumulator term and the live term of a layer as ONE chain,
+//   h = [rn(X . Fa1) | rn(scale * X . Fl1)],  Y = rn(h . [Fa2 ; Fl2] + bias),  Hsave [M, 64] = the live columns of h in the
+// r <= 64 contract (zeros above r_live, 1.0 in column 63 when r_live < 64), or nullptr.
+// Forward (bwd = 0): Fa1 = Q [D1][r_acc], Fl1 = A [D1][r_live], Fa2 = R [r_acc][D2], Fl2 = B [r_live][D2].  Data gradient
+// (bwd = 1): Fa1 = R [r_acc][D1], Fl1 = B [r_live][D1], Fa2 = Q [D2][r_acc], Fl2 = A [D2][r_live].  `pack` (16-byte aligned,
+// chain_wide_pack_bytes(r_acc + r_live, D1, D2)) receives the packed factors.
+struct WideAccArgs {
+  const void* X;
+  void* Y;
+  const void *Fa1, *Fl1, *Fa2, *Fl2;
+  int64_t ldfa1, ldfl1, ldfa2, ldfl2;
+  void* Hsave;
+  const void* bias;
+  int64_t M;
+  int D1, D2, r_acc, r_live;
+  float scale;
+  int bwd;
+  void* pack;
+  size_t pack_bytes;
+};
+// even r_live in [2, 64], even r_acc >= 2, r_acc + r_live <= 256, widths multiples of 8, bf16 / f16
+bool fused_acc_shape_ok(int r_live, int r_acc, int d_in, int d_out, int dtype);
+// SOW_ERR_UNSUPPORTED when the shape, the alignment (X, Y, bias, Hsave, pack: 16 bytes) or the scratch does not suit the
+// kernel (nothing launched)
+int launch_chain_wide_acc(const WideAccArgs& a, int dtype, hipStream_t stream);
 // skinny_tn_wide.hip: weight gradients of a wide-rank layer, token-slab partials + fixed-order reduction
 struct TnwParams {
   const void* M[2];     // x [T, d_in], dY [T, d_out]

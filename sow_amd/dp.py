@@ -85,7 +85,10 @@ class _GradSink:
         r, d_out = B.shape
         kind = ops.acc_kind(acc_down, acc_up)
         r_acc = acc_down.shape[1] if kind == _lib.ACC_LOWRANK else 0
-        need = ops.workspace_bytes(T, d_in, d_out, r, r_acc, kind, x2.dtype, param_f32=_mixed(x2, B)) + 256
+        # sized for the SOW_FUSE_ACC data gradient where the layer takes it (the flagged plan also serves the unflagged call)
+        self.fuse_acc = ops.fuse_acc_default(T, d_in, d_out, r, r_acc, kind, x2.dtype, _mixed(x2, B))
+        need = ops.workspace_bytes(T, d_in, d_out, r, r_acc, kind, x2.dtype, param_f32=_mixed(x2, B),
+                                   fuse_acc=self.fuse_acc) + 256
         if self.ws is None or self.ws.numel() < need or self.ws.device != x2.device:
             self.ws = torch.empty(need, dtype=torch.uint8, device=x2.device)
         return kind, r_acc
@@ -102,7 +105,8 @@ class _GradSink:
         out = (self.pA.grad, self.pB.grad, None)
         dy2 = dy2.contiguous()
         dx, _, _, _ = ops.sow_backward(dy2, x2, h, A, B, acc_down, acc_up, scale, False, out=out, grad_beta=1.0,
-                                       phases=_lib.BWD_DATA, workspace=self.ws, param_f32=_mixed(x2, B))
+                                       phases=_lib.BWD_DATA, workspace=self.ws, param_f32=_mixed(x2, B),
+                                       fuse_acc=self.fuse_acc)
         self.queue(dy2, x2, h, A, B, acc_down, acc_up, scale, kind, r_acc)
         return dx
 

@@ -27,7 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from .layer import SoWLinear, autocast_compute_dtype, autocast_input
+from .layer import SoWLinear, _fuse_acc, autocast_compute_dtype, autocast_input
 
 DEFAULT_GROUPS = (("q_proj", "k_proj", "v_proj"), ("gate_proj", "up_proj"),        # Llama (simple_train.py / finetune.py targets)
                   ("query", "key", "value"))                                       # RoBERTa self-attention (run_glue.py:572)
@@ -55,7 +55,8 @@ class _SoWGroupFunction(torch.autograd.Function):
             calls.append(ops.LayerCall(x2, A.contiguous(), B.contiguous(),
                                        acc_down=acc_down.contiguous() if kind != _lib.ACC_NONE else None,
                                        acc_up=acc_up.contiguous() if kind == _lib.ACC_LOWRANK else None,
-                                       bias=bias, scale=s, forward_only=True, save_h=need_bwd, param_f32=mixed))
+                                       bias=bias, scale=s, forward_only=True, save_h=need_bwd, param_f32=mixed,
+                                       fuse_acc=_fuse_acc(x2, B, acc_down, acc_up, mixed)))
         ops.LayerGroup(calls).forward()   # (the shared-input forward does not pay on these shapes: module docstring)
         ctx.shared = shared
         if need_bwd:
@@ -86,7 +87,8 @@ class _SoWGroupFunction(torch.autograd.Function):
                 return [ops.LayerCall(x2, A, B, acc_down=acc_down if kind != _lib.ACC_NONE else None,
                                       acc_up=acc_up if kind == _lib.ACC_LOWRANK else None, scale=ctx.scales[i], h=hs[i],
                                       dy2=dy2, dx=dxs[i], out=(sink.pA.grad, sink.pB.grad, None), grad_beta=grad_beta, y=dy2,
-                                      workspace=sink.ws, param_f32=ctx.mixed)
+                                      workspace=sink.ws, param_f32=ctx.mixed,
+                                      fuse_acc=_fuse_acc(x2, B, acc_down, acc_up, ctx.mixed))
                         for i, (sink, dy2, A, B, acc_down, acc_up, kind, r_acc) in enumerate(recs)]
 
             # the DATA phase writes no weight gradient: grad_beta = 0 of the shared call only means dX is overwritten
@@ -116,7 +118,8 @@ class _SoWGroupFunction(torch.autograd.Function):
                                            acc_down=acc_down.contiguous() if kind != _lib.ACC_NONE else None,
                                            acc_up=acc_up.contiguous() if kind == _lib.ACC_LOWRANK else None,
                                            bias=bias, scale=ctx.scales[i], h=hs[i], dy2=dy2s[i], dx=dxs[i], out=outs[i],
-                                           grad_beta=0.0, y=dy2s[i], param_f32=ctx.mixed))   # y is not written by backward
+                                           grad_beta=0.0, y=dy2s[i], param_f32=ctx.mixed,   # y is not written by backward
+                                           fuse_acc=_fuse_acc(x2, B, acc_down, acc_up, ctx.mixed)))
             return calls
 
         dx = None

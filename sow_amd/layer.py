@@ -65,6 +65,15 @@ def autocast_input(x2: torch.Tensor, cdt: torch.dtype) -> torch.Tensor:
     return ops.cast(x2, cdt)
 
 
+def _fuse_acc(x2, B, acc_down, acc_up, mixed: bool) -> bool:
+    """The SOW_FUSE_ACC permission of a module call (ops.fuse_acc_default): the same answer on the grad and the no-grad
+    route, so that eval and train outputs stay bit-identical."""
+    kind = ops.acc_kind(acc_down, acc_up)
+    if kind != ops._lib.ACC_LOWRANK or acc_down.dim() != 2:
+        return False
+    return ops.fuse_acc_default(x2.shape[0], x2.shape[1], B.shape[1], B.shape[0], acc_down.shape[1], kind, x2.dtype, mixed)
+
+
 class _SoWFunction(torch.autograd.Function):
     """y = acc_term + scale * (x @ A) @ B + bias through sow_forward / sow_backward (include/sow_amd.h).  cdt: the compute
     dtype of a mixed-precision call (fp32 parameters, SOW_PARAM_F32) or None."""
@@ -82,7 +91,10 @@ class _SoWFunction(torch.autograd.Function):
             acc_down = acc_down.contiguous()
         if acc_up is not None and acc_up.numel():
             acc_up = acc_up.contiguous()
-        y, h = ops.sow_forward(x2, A, B, acc_down, acc_up, bias, scale, param_f32=cdt is not None)
+        # a low-rank accumulator and the live term in one pass where the library admits it and it measures faster
+        fuse = _fuse_acc(x2, B, acc_down, acc_up, cdt is not None)
+        y, h = ops.sow_forward(x2, A, B, acc_down, acc_up, bias, scale, param_f32=cdt is not None, fuse_acc=fuse)
+        ctx.fuse_acc = fuse
         ctx.save_for_backward(x2, h, A, B, acc_down, acc_up)
         ctx.scale = scale
         ctx.has_bias = bias is not None
@@ -104,7 +116,7 @@ class _SoWFunction(torch.autograd.Function):
             dA = dB = dbias = None
         else:
             dx, dA, dB, dbias = ops.sow_backward(dy2, x2, h, A, B, acc_down, acc_up, ctx.scale, ctx.has_bias,
-                                                 param_f32=ctx.mixed)
+                                                 param_f32=ctx.mixed, fuse_acc=ctx.fuse_acc)
         if dx.dtype != ctx.x_dtype:
             dx = ops.cast(dx, ctx.x_dtype)      # fp32 input under autocast: its gradient, cast back by the library
         return dx.reshape(ctx.x_shape), dA, dB, None, None, dbias, None, None, None
@@ -198,7 +210,8 @@ class SoWLinear(nn.Module):
             if cdt is not None:
                 x2 = autocast_input(x2.contiguous(), cdt)
             y, _ = ops.sow_forward(x2, A, B, self.acc_downweight, self.acc_upweight, self.bias, float(self.scale), save_h=False,
-                                   param_f32=cdt is not None)
+                                   param_f32=cdt is not None,
+                                   fuse_acc=_fuse_acc(x2, B, self.acc_downweight, self.acc_upweight, cdt is not None))
             return y.reshape(*x.shape[:-1], B.shape[1])
         return _SoWFunction.apply(x, A, B, self.acc_downweight, self.acc_upweight, self.bias, float(self.scale),
                                   getattr(self, "_grad_sink", None), cdt)

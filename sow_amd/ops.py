@@ -23,12 +23,14 @@ def _dt(t: torch.Tensor) -> int:
         raise TypeError(f"sow_amd supports float32, bfloat16 and float16 tensors, got {t.dtype}") from None
 
 
-def _call_dtype(x2: torch.Tensor, param_f32: bool, who: str = "sow_amd") -> Tuple[int, torch.dtype]:
+def _call_dtype(x2: torch.Tensor, param_f32: bool, who: str = "sow_amd", fuse_acc: bool = False) -> Tuple[int, torch.dtype]:
     """(C-ABI dtype code, parameter dtype) of a layer call on activations x2.  param_f32: the parameters (factors, bias,
-    accumulator) are fp32 and x2 is of the compute dtype, bf16 or f16 (SOW_PARAM_F32: mixed precision, torch.autocast)."""
+    accumulator) are fp32 and x2 is of the compute dtype, bf16 or f16 (SOW_PARAM_F32: mixed precision, torch.autocast).
+    fuse_acc: the SOW_FUSE_ACC permission (bf16 / f16 parameters only: the library ignores it next to SOW_PARAM_F32, so it
+    is not passed there)."""
     dt = _dt(x2)
     if not param_f32:
-        return dt, x2.dtype
+        return (dt | _lib.FUSE_ACC if fuse_acc and dt != _lib.F32 else dt), x2.dtype
     if dt == _lib.F32:
         raise TypeError(f"{who}: fp32 parameters need bfloat16 or float16 activations, got {x2.dtype}")
     return dt | _lib.PARAM_F32, torch.float32
@@ -141,18 +143,61 @@ def check_accumulator(x2: torch.Tensor, d_in: int, d_out: int, acc_down, acc_up,
     return kind, r_acc
 
 
+def fused_acc_admits(d_in: int, d_out: int, r: int, r_acc: int, kind: int, dtype: torch.dtype,
+                     param_f32: bool = False) -> bool:
+    """The admitted set of SOW_FUSE_ACC (include/sow_amd.h; fused_acc_shape_ok in the library): a bf16 / f16 layer without
+    fp32 parameters, a low-rank accumulator, even r in [2, 64], even r_acc >= 2, r_acc + r <= 256, widths multiples of 8.
+    The call-time conditions (16-byte-aligned tensors, the flagged workspace) hold for every tensor the module surface
+    allocates."""
+    return (dtype in (torch.bfloat16, torch.float16) and not param_f32 and kind == _lib.ACC_LOWRANK
+            and 2 <= r <= 64 and r % 2 == 0 and r_acc >= 2 and r_acc % 2 == 0 and r_acc + r <= 256
+            and d_in > 0 and d_out > 0 and d_in % 8 == 0 and d_out % 8 == 0)
+
+
+FUSED_ACC_MIN_T = 32768     # the token count of profiles/lowrank_acc.txt
+FUSED_ACC_MAX_D = 1376      # its widest layer (512 -> 1376, 1376 -> 512)
+
+
+def fused_acc_pays(T: int, d_in: int, d_out: int, r: int, r_acc: int) -> bool:
+    """The measured dispatch rule of the module surface for SOW_FUSE_ACC (profiles/lowrank_acc.txt, DESIGN.md section
+    4.4e): the classes of (r_pad = ceil64(r_acc + r), shape) at which the fused pass beats the two chain launches it
+    replaces, forward + data gradient together, by more than the two-pass variant's own spread.
+
+    Measured (bf16; one f16 row), us of forward + data gradient, two-pass -> fused (two-pass spread), T = 32768:
+        512->512,  r = 50, r_acc = 50 / 100 / 150 / 200 (r_pad 128 / 192 / 256 / 256): 100 -> 73 (2.5), 129 -> 82 (4.5),
+                                                                                        136 -> 90 (5.0), 145 -> 90 (3.4)
+        512->1376: 183 -> 110 (1.1), 215 -> 126 (6.3), 230 -> 145 (10.6), 251 -> 147 (10.8)
+        1376->512: 178 -> 110 (1.2), 215 -> 127 (7.5), 232 -> 146 (10.2), 250 -> 143 (6.3)
+        768->768,  r = 8, r_acc = 8 / 56 (r_pad 64): 135 -> 81 (1.0), 138 -> 82 (1.4);   f16 512->512, r_acc = 100: 128 -> 82 (2.0)
+    Every class of r_pad (64, 128, 192, 256) pays at each of these shapes, by 27 to 43 %.  The rule is these rows: calls of at
+    least FUSED_ACC_MIN_T tokens on layers no wider than FUSED_ACC_MAX_D -- the envelope the test suite was run with.
+    Also measured, also paying (ratio 0.58 to 0.78), but outside the default until the suite has run with a wider one:
+    T = 16384 at the three llama_60m shapes, and 2048 -> 2048 / 4096 -> 4096 at r_acc = 50 and 200.
+    NOT measured: fewer than 16384 tokens (below 8193 the two-pass path also splits its chains over K and the output columns
+    to fill the chip, launch_chain_short, and the fused pass does not), widths above 4096, r other than 8 and 50."""
+    return T >= FUSED_ACC_MIN_T and max(d_in, d_out) <= FUSED_ACC_MAX_D
+
+
+def fuse_acc_default(T: int, d_in: int, d_out: int, r: int, r_acc: int, kind: int, dtype: torch.dtype,
+                     param_f32: bool = False) -> bool:
+    """Whether the module surface passes the SOW_FUSE_ACC permission for this layer call: admitted and measured to pay."""
+    return fused_acc_admits(d_in, d_out, r, r_acc, kind, dtype, param_f32) and fused_acc_pays(T, d_in, d_out, r, r_acc)
+
+
 def sow_forward(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, acc_up, bias, scale: float,
-                save_h: bool = True, *, param_f32: bool = False):
+                save_h: bool = True, *, param_f32: bool = False, fuse_acc: bool = False):
     """y, h_save = forward of the SoW contraction on a flattened [T, d_in] input.  save_h = False (no-grad / eval callers,
     e.g. the reload + generate loop of commonsense_evaluate.py:268-287): the projection is not written to HBM and None
     is returned in its place (every rank except r <= 64 with a dense accumulator, whose fused kernels write it as scratch;
     a wide layer off the fused chain keeps its intermediate in the forward workspace).
     param_f32: A, B, bias and the accumulator are fp32, x2 is bf16 / f16 (the compute dtype); the kernels round the
-    parameters once to x2's dtype (include/sow_amd.h: SOW_PARAM_F32) and y is of x2's dtype."""
+    parameters once to x2's dtype (include/sow_amd.h: SOW_PARAM_F32) and y is of x2's dtype.
+    fuse_acc: the SOW_FUSE_ACC permission -- a low-rank accumulator and the live term in one pass where the library admits
+    the call; the same result as without it everywhere else."""
     lib = _lib.load()
     dev = _need_gpu(x2, A, B, acc_down if acc_down is not None and acc_down.numel() else None,
                     acc_up if acc_up is not None and acc_up.numel() else None, bias)
-    dt, pdt = _call_dtype(x2, param_f32)
+    dt, pdt = _call_dtype(x2, param_f32, fuse_acc=fuse_acc)
     for name, t in (("A", A), ("B", B), ("bias", bias)):
         if t is not None and t.dtype != pdt:
             raise TypeError(f"sow_amd: dtype mismatch, x is {x2.dtype} but {name} is {t.dtype}"
@@ -280,22 +325,26 @@ def sow_forward_skinny(layers) -> Optional[list]:
 
 
 def workspace_bytes(T: int, d_in: int, d_out: int, r: int, r_acc: int, kind: int, dtype: torch.dtype,
-                    param_f32: bool = False) -> int:
-    return _workspace_bytes(_lib.load(), T, d_in, d_out, r, r_acc, kind, _DT[dtype] | (_lib.PARAM_F32 if param_f32 else 0))
+                    param_f32: bool = False, fuse_acc: bool = False) -> int:
+    flags = _lib.PARAM_F32 if param_f32 else (_lib.FUSE_ACC if fuse_acc and dtype != torch.float32 else 0)
+    return _workspace_bytes(_lib.load(), T, d_in, d_out, r, r_acc, kind, _DT[dtype] | flags)
 
 
 def sow_backward(dy2: torch.Tensor, x2: torch.Tensor, h: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down,
                  acc_up, scale: float, need_bias: bool,
                  out: Optional[Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]] = None,
                  grad_beta: float = 0.0, *, phases: int = _lib.BWD_DATA | _lib.BWD_WEIGHTS,
-                 dx: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, param_f32: bool = False):
+                 dx: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, param_f32: bool = False,
+                 fuse_acc: bool = False):
     """dx, dA, dB, dbias.  `out` = (dA, dB, dbias) buffers to write/accumulate into (grad_beta).
     `phases` selects the data-gradient and / or weight-gradient kernels (see include/sow_amd.h); a split
     call must pass the same `workspace` (and `dx`) to both phases, each enqueued on the current stream.
-    param_f32: fp32 parameters with bf16 / f16 activations (sow_forward); dA, dB and dbias are then fp32, dx of x2's dtype."""
+    param_f32: fp32 parameters with bf16 / f16 activations (sow_forward); dA, dB and dbias are then fp32, dx of x2's dtype.
+    fuse_acc: the SOW_FUSE_ACC permission for the data gradient (sow_forward); a workspace passed in must then come from
+    workspace_bytes(..., fuse_acc=True), a smaller one makes the call run the two-pass kernels."""
     lib = _lib.load()
     dev = _need_gpu(dy2, x2, h, A, B)
-    dt, pdt = _call_dtype(x2, param_f32)
+    dt, pdt = _call_dtype(x2, param_f32, fuse_acc=fuse_acc)
     if dy2.dtype != x2.dtype:
         raise TypeError(f"sow_amd: grad dtype {dy2.dtype} differs from input dtype {x2.dtype}")
     if param_f32 and (A.dtype != pdt or B.dtype != pdt):
@@ -318,6 +367,8 @@ def sow_backward(dy2: torch.Tensor, x2: torch.Tensor, h: torch.Tensor, A: torch.
             raise TypeError(f"sow_amd: gradient buffers must be {pdt}")
     nws = _workspace_bytes(lib, T, d_in, d_out, r, r_acc, kind, dt)
     ws = _ws(nws, dev) if workspace is None else workspace
+    if ws.numel() < nws and dt & _lib.FUSE_ACC:   # a permission: a workspace of the unflagged plan runs the two-pass kernels
+        nws = _workspace_bytes(lib, T, d_in, d_out, r, r_acc, kind, dt & ~_lib.FUSE_ACC)
     if ws.numel() < nws:
         raise ValueError("sow_amd: workspace too small")
     _launch(dev, "sow_backward", lib.sow_backward_ex, _ptr(dy2), _ptr(x2), _ptr(h), _ptr(A), _ptr(B),
@@ -333,10 +384,11 @@ class LayerCall:
     own workspace (workspace_bytes())."""
 
     def __init__(self, x2, A, B, *, acc_down=None, acc_up=None, bias=None, scale=1.0, y=None, h=None, dy2=None, dx=None,
-                 out=None, grad_beta=0.0, workspace=None, forward_only=False, save_h=True, param_f32=False):
+                 out=None, grad_beta=0.0, workspace=None, forward_only=False, save_h=True, param_f32=False, fuse_acc=False):
         dev = _need_gpu(x2, A, B, bias, y, h, dy2, dx, workspace)
         # param_f32: fp32 A, B, bias, accumulator and gradients, activations of the compute dtype (SOW_PARAM_F32)
-        self.dtype, pdt = _call_dtype(x2, param_f32, "sow_amd.LayerCall")
+        # fuse_acc: the SOW_FUSE_ACC permission; it rides in the dtype, so the workspace queries below are the flagged ones
+        self.dtype, pdt = _call_dtype(x2, param_f32, "sow_amd.LayerCall", fuse_acc=fuse_acc)
         T, d_in = x2.shape
         r, d_out = B.shape
         # the same accumulator checks as the single-layer entry point (ops.sow_forward): same exceptions for the same input
@@ -362,6 +414,10 @@ class LayerCall:
         nws = (_forward_workspace_bytes(_lib.load(), T, d_in, d_out, r, r_acc, kind, self.dtype) if forward_only
                else _workspace_bytes(_lib.load(), T, d_in, d_out, r, r_acc, kind, self.dtype))
         self.workspace = workspace if workspace is not None else (_ws(nws, dev) if nws else None)
+        if self.workspace is not None and self.workspace.numel() < nws and self.dtype & _lib.FUSE_ACC:
+            # a permission: a caller's workspace of the unflagged plan runs the two-pass kernels
+            q = _forward_workspace_bytes if forward_only else _workspace_bytes
+            nws = q(_lib.load(), T, d_in, d_out, r, r_acc, kind, self.dtype & ~_lib.FUSE_ACC)
         if self.workspace is not None and self.workspace.numel() < nws:
             raise ValueError("sow_amd.LayerCall: workspace too small")
         dA, dB, dbias = out if out is not None else (None, None, None)
@@ -390,26 +446,54 @@ class LayerGroup:
     def __init__(self, calls: Sequence[LayerCall]):
         if not calls:
             raise ValueError("empty group")
-        if len({c.dtype for c in calls}) != 1 or len({c.device for c in calls}) != 1:
+        if len({c.dtype & ~_lib.FUSE_ACC for c in calls}) != 1 or len({c.device for c in calls}) != 1:
             raise ValueError("sow_amd.LayerGroup: all layers must share dtype and device")
         self.calls = list(calls)
         self.arr = (_lib.LayerArgs * len(calls))(*[c.args for c in calls])
-        self.dtype, self.device = calls[0].dtype, calls[0].device
+        # SOW_FUSE_ACC rides in the dtype of the whole C call, the permission belongs to each LayerCall: a group of flagged
+        # and unflagged layers issues its forward and its data gradient as two C calls, one per kind (such layers never
+        # share a launch anyway: a low-rank accumulator takes the per-layer fall-through).  The weight-gradient phases and
+        # their plans ignore the flag and always see the whole group.
+        fused = [bool(c.dtype & _lib.FUSE_ACC) for c in calls]
+        self._fused = fused if any(fused) and not all(fused) else None
+        self.dtype, self.device = calls[0].dtype & ~_lib.FUSE_ACC | (_lib.FUSE_ACC if all(fused) else 0), calls[0].device
 
     @classmethod
     def from_args(cls, arr, n: int, dtype: int, device, keep=None) -> "LayerGroup":
         """A group over a ready-made sow_layer_args array (the caller has validated the tensors and keeps them alive --
         `keep` -- until the launches that read the raw pointers have been enqueued)."""
         g = cls.__new__(cls)
-        g.calls, g.arr, g.dtype, g.device, g._keep = [None] * n, arr, dtype, device, keep
+        g.calls, g.arr, g.dtype, g.device, g._keep, g._fused = [None] * n, arr, dtype, device, keep, None
         return g
 
+    def _by_permission(self):
+        """(sow_layer_args array, n, dtype) of the flagged and of the unflagged layers of a mixed group.  Rebuilt from
+        self.arr at every call, not cached: callers and subclasses edit self.arr after construction (SharedInputGroup points
+        every dx at the first), and only direct users of LayerGroup reach a mixed group -- the module surface gives siblings
+        one decision."""
+        out = []
+        for want in (True, False):
+            idx = [i for i, f in enumerate(self._fused) if f == want]
+            out.append(((_lib.LayerArgs * len(idx))(*[self.arr[i] for i in idx]), len(idx),
+                        self.dtype | (_lib.FUSE_ACC if want else 0)))
+        return out
+
     def forward(self) -> None:
-        _launch(self.device, "sow_forward_group", _lib.load().sow_forward_group, self.arr, len(self.calls), self.dtype)
+        fn = _lib.load().sow_forward_group
+        if self._fused is None:
+            return _launch(self.device, "sow_forward_group", fn, self.arr, len(self.calls), self.dtype)
+        for arr, n, dt in self._by_permission():
+            _launch(self.device, "sow_forward_group", fn, arr, n, dt)
 
     def backward(self, phases: int = _lib.BWD_DATA | _lib.BWD_WEIGHTS) -> None:
-        _launch(self.device, "sow_backward_group", _lib.load().sow_backward_group, self.arr, len(self.calls), self.dtype,
-                int(phases))
+        fn, phases = _lib.load().sow_backward_group, int(phases)
+        if self._fused is not None and phases & _lib.BWD_DATA:
+            for arr, n, dt in self._by_permission():
+                _launch(self.device, "sow_backward_group", fn, arr, n, dt, _lib.BWD_DATA)
+            phases &= ~_lib.BWD_DATA
+            if not phases & (_lib.BWD_WEIGHTS | _lib.BWD_WEIGHTS_PARTIAL | _lib.BWD_WEIGHTS_REDUCE):
+                return
+        _launch(self.device, "sow_backward_group", fn, self.arr, len(self.calls), self.dtype, phases)
 
     def weight_gradient_plan(self, phases: int = _lib.BWD_DATA | _lib.BWD_WEIGHTS):
         """(row_owner_kernel: bool, [(slabs of x, slabs of dY) per layer]) for backward(phases) -- sow_backward_group_plan."""
