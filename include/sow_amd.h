@@ -194,7 +194,8 @@ int sow_backward(const void* dy, const void* x, const void* h_save, const void* 
 #define SOW_BWD_WEIGHTS_REDUCE 8
 /* sow_backward_group only: the token-slab counts of the weight-gradient partial sums may be planned over the whole group
  * (row-owner kernel, see sow_backward_group) although the reduction is deferred; the deferred reduction must then be
- * built with sow_backward_group_reduce_desc(same layers, same flag).  Implied when one call runs PARTIAL and REDUCE. */
+ * built with sow_backward_group_reduce_desc(same layers, same flag).  bf16: implied when one call runs PARTIAL and REDUCE;
+ * f16: never implied (see sow_backward_group_reduce_desc below). */
 #define SOW_BWD_GROUP_SLABS 16
 int sow_backward_ex(const void* dy, const void* x, const void* h_save, const void* A, const void* B,
                     const void* acc_down, const void* acc_up, void* dx, void* dA, void* dB, void* dbias, int64_t T,
@@ -223,7 +224,7 @@ int sow_reduce_batch(const void* descs, const int* starts, int n, int total_bloc
  * an attention block (sow.py:107-126 called three times on the same hidden state by the HF model), gate / up of an MLP,
  * and their backward passes.  Each element carries exactly the arguments of sow_forward / sow_backward_ex for its
  * layer (fields a direction does not use are ignored).  Semantics = the n single calls, in any order; results are
- * bit-identical to them.  Layers that run the bf16 streaming kernels (no accumulator, r_live <= 64, T > 8192) share one
+ * bit-identical to them.  Layers that run the bf16 / f16 streaming kernels (no accumulator, r_live <= 64, T > 8192) share one
  * grid per kernel, up to 4 layers at a time: a launch costs ~8 us of ramp + first-load latency + write drain whatever
  * its size, which a 3-layer grid pays once.  Every other layer is forwarded to the single-layer entry point. */
 typedef struct sow_layer_args {
@@ -254,6 +255,10 @@ int sow_backward_group(const sow_layer_args* layers, int n, int dtype, int phase
  * of once per 128 columns and x / dY arrive as whole rows -- with slab counts planned over the group (equal work per
  * workgroup, one resident round; a pure function of the layer list).  The sums are then added in a different (still
  * fixed) order than by n single calls: dA / dB / dbias agree with them to fp32 rounding of the slab sums, not bit for bit.
+ * SOW_DTYPE_BF16 and SOW_DTYPE_F16 (SOW_PARAM_F32 included) take this plan, with one deliberate asymmetry: f16 takes it ONLY
+ * when the caller passes SOW_BWD_GROUP_SLABS (a deferred reduction, e.g. FactorBucket); an f16 call that runs PARTIAL and
+ * REDUCE itself keeps the column-owner kernel and stays bit-identical to n single calls (bf16: the flag is implied there).
+ * The NO_F16_TN switch sends every f16 weight gradient back to the generic kernel (no grouping, no row-owner plan).
  * sow_backward_group_reduce_desc: the descriptors (n x sow_reduce_desc_bytes(), HOST memory) and block counts of the
  * deferred reductions of exactly this group, for sow_reduce_batch; `phases` = the flags of the PARTIAL call. */
 int sow_backward_group_reduce_desc(const sow_layer_args* layers, int n, int dtype, int phases, void* descs_out, int* blocks_out);

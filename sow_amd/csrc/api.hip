@@ -54,7 +54,8 @@ static const char* const kSwitchNames[SW_COUNT] = {"FORCE_CHAIN_V1", "NO_SHORT_S
                                                    "NO_GEMM3S",      "GEMM3S",         "GEMM3",      "NO_GROUPED",     "NO_PERSIST",     "NO_NT_STORE",    "NT_LOAD",        "NO_PAIR_FLUSH",  "F32_EXACT",
                                                    "NO_PARK16",      "TN_NO_NT_LOAD",  "NO_TN_ROWS",     "GEMM4",          "NO_GEMM4H",      "NO_CHAIN3F",     "NO_TN_F32Q",     "NO_SPLITK",
                                                    "NO_WIDE_CHAIN",  "NO_SHARED_X",    "NO_RAGGED",      "NO_RAGGED_GEMM", "NO_BLOCKED_QR",
-                                                   "NO_SKINNY",      "NO_FUSED_ACC",   "NO_H_ROWS"};
+                                                   "NO_SKINNY",      "NO_FUSED_ACC",   "NO_F16_TN",
+                                                   "NO_H_ROWS"};
 static std::atomic<int> g_switch[SW_COUNT];
 static std::once_flag g_switch_once;
 static void switches_from_env() {
@@ -165,7 +166,7 @@ static int gemm_auto(const void* A, int64_t lda, const void* B, int64_t ldb, boo
 
 extern "C" {
 
-int sow_version(void) { return 119; }
+int sow_version(void) { return 120; }
 
 int sow_set_switch(const char* name, int value) {
   if (!name) return SOW_ERR_NULL;
@@ -255,7 +256,8 @@ static WsPlan plan_ws(int64_t T, int d_in, int d_out, int r_live, int r_acc, int
     const int quads = (dtype == SOW_F32 && tn_f32q_shape_ok(T, d_in, d_out)) ? (cg_in + 3) / 4 + (cg_out + 3) / 4 : 0;
     w.ns = tn_pick_slabs(T, cg_in + cg_out, (cg_in + 1) / 2 + (cg_out + 1) / 2, quads, dtype, &w.slab_len);
     w.ns_cap = w.ns;
-    if (dtype == SOW_BF16 && T >= 1024) {
+    // both 16-bit dtypes (a pure function of shape and dtype: NO_F16_TN does not shrink the f16 workspace)
+    if ((dtype == SOW_BF16 || dtype == SOW_F16) && T >= 1024) {
       const int by_len = (int)(T / 512 < TNR_MAX_SLABS ? T / 512 : TNR_MAX_SLABS);
       if (by_len > w.ns_cap) w.ns_cap = by_len;
     }
@@ -913,8 +915,10 @@ static bool group_chain_params(const sow_layer_args& L, bool bwd, int dtype, con
 // Group-planned slab counts for the weight-gradient partial sums (skinny_tn.hip: tn_partial_rows_kernel).  A pure function
 // of the layer list, so that sow_backward_group and sow_backward_group_reduce_desc agree.  Items 2 i, 2 i + 1 = the two
 // operands (x with dh, dY with h) of layer i.
-static bool group_rows_plan(const sow_layer_args* layers, int n, int dtype, int* ns, int* slab_len) {
-  if (dtype != SOW_BF16 || n < 1 || n > TN_MAXG) return false;
+// f16 takes the plan only when the caller asks for it (SOW_BWD_GROUP_SLABS: a deferred reduction); a call that runs both
+// weight phases itself keeps the column-owner kernel for f16, whose grouped results are pinned bit-identical to single calls.
+static bool group_rows_plan(const sow_layer_args* layers, int n, int dtype, int phases, int* ns, int* slab_len) {
+  if (!tn_dma_dtype(dtype) || (dtype == SOW_F16 && !(phases & SOW_BWD_GROUP_SLABS)) || n < 1 || n > TN_MAXG) return false;
   int64_t T[TNR_MAXI];
   int D[TNR_MAXI], cap[TNR_MAXI];
   for (int i = 0; i < n; ++i) {
@@ -1142,7 +1146,7 @@ static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, i
   // the deferred reduction from sow_backward_group_reduce_desc), or when this call runs the reduction itself
   int rns[TNR_MAXI], rslab[TNR_MAXI];
   const bool rows = (do_partial || do_reduce) && ((phases & SOW_BWD_GROUP_SLABS) || (do_partial && do_reduce)) &&
-                    group_rows_plan(layers, n, dtype, rns, rslab);
+                    group_rows_plan(layers, n, dtype, phases, rns, rslab);
   if (do_partial && rows) {
     TnRowsItem items[TNR_MAXI];
     for (int i = 0; i < n; ++i) {
@@ -1154,7 +1158,7 @@ static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, i
       items[2 * i + 1] = TnRowsItem{L.dy, L.h_save, (float*)(ws + w.off_p1), (int64_t)L.d_out, L.T, L.d_out, 0, 0, 0, 0,
                                     rns[2 * i + 1], rslab[2 * i + 1], 0};
     }
-    if ((rc = launch_tn_rows(items, 2 * n, stream))) return rc;
+    if ((rc = launch_tn_rows(items, 2 * n, dtype, stream))) return rc;
   } else if (do_partial) {
     TnParams batch[TN_MAXG];
     int nb = 0;
@@ -1180,14 +1184,14 @@ static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, i
           batch[nb] = tp;
           grouped = true;
           if (++nb == TN_MAXG) {
-            if ((rc = launch_tn_group(batch, nb, stream))) return rc;
+            if ((rc = launch_tn_group(batch, nb, dtype, stream))) return rc;
             nb = 0;
           }
         }
       }
       if (!grouped && (rc = single(L, SOW_BWD_WEIGHTS_PARTIAL))) return rc;
     }
-    if (nb && (rc = launch_tn_group(batch, nb, stream))) return rc;
+    if (nb && (rc = launch_tn_group(batch, nb, dtype, stream))) return rc;
   }
   if (do_reduce && rows) {
     for (int i = 0; i < n; ++i) {
@@ -1289,7 +1293,7 @@ int sow_backward_group_plan(const sow_layer_args* layers, int n, int dtype, int 
   const bool do_reduce = (phases & (SOW_BWD_WEIGHTS | SOW_BWD_WEIGHTS_REDUCE)) != 0;
   int rns[TNR_MAXI], rslab[TNR_MAXI];
   const bool rows = (do_partial || do_reduce) && ((phases & SOW_BWD_GROUP_SLABS) || (do_partial && do_reduce)) &&
-                    group_rows_plan(layers, n, dtype, rns, rslab);
+                    group_rows_plan(layers, n, dtype, phases, rns, rslab);
   if (slabs_out)
     for (int i = 0; i < n; ++i) {
       const sow_layer_args& L = layers[i];
@@ -1313,7 +1317,7 @@ int sow_backward_group_reduce_desc(const sow_layer_args* layers, int n, int dtyp
   for (int i = 0; i < n; ++i)
     if ((rc = check_layer(layers[i], true))) return rc;
   int rns[TNR_MAXI], rslab[TNR_MAXI];
-  const bool rows = (phases & SOW_BWD_GROUP_SLABS) && group_rows_plan(layers, n, dtype, rns, rslab);
+  const bool rows = (phases & SOW_BWD_GROUP_SLABS) && group_rows_plan(layers, n, dtype, phases, rns, rslab);
   for (int i = 0; i < n; ++i) {
     const sow_layer_args& L = layers[i];
     char* out = (char*)descs_out + (size_t)i * sizeof(ReduceParams);

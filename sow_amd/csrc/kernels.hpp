@@ -115,6 +115,7 @@ struct TnGroup {
   int n;
 };
 bool tn_group_supported(const TnParams& p, int dtype);
+bool tn_dma_dtype(int dtype);   // bf16, and f16 unless NO_F16_TN: the dtypes of the LDS-DMA weight-gradient kernels
 // Row-owner weight-gradient kernel (skinny_tn.hip: tn_partial_rows_kernel): one item per (layer, operand); a workgroup
 // owns ALL columns of a token slab (up to 1024 per column range), so S (h / dh) is read once per range instead of once
 // per 128 columns.  The slab counts are planned over the whole group (work per block equal across items).
@@ -138,8 +139,8 @@ constexpr int TNR_MAX_SLABS = 40;   // workspace capacity per operand (api.hip: 
 // n items (T[i] tokens x D[i] columns, at most cap[i] slabs): slab counts such that the blocks of the group fill one
 // resident round (256 workgroups) with equal work; false = this group does not suit the kernel (too few / too many blocks)
 bool tn_rows_plan(const int64_t* T, const int* D, const int* cap, int n, int* ns_out, int* slab_len_out);
-int launch_tn_rows(TnRowsItem* items, int n, hipStream_t stream);
-int launch_tn_group(const TnParams* ps, int n, hipStream_t stream);
+int launch_tn_rows(TnRowsItem* items, int n, int dtype, hipStream_t stream);
+int launch_tn_group(const TnParams* ps, int n, int dtype, hipStream_t stream);
 int launch_tn_reduce(ReduceParams p, int dtype, hipStream_t stream);
 int launch_tn_reduce_batch(const ReduceParams* descs, const int* starts, int n, int total_blocks, int dtype, hipStream_t stream);
 // chain_wide.hip (bf16 / f16, even r in (64, 256], D1 and D2 multiples of 8; X, Y, bias 16-byte aligned): the fused

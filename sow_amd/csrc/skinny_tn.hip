@@ -11,10 +11,13 @@
 // [D, r] or its transpose [r, D].
 // Column groups of one slab are NS blocks apart (NS % 8 == 0) so they share an XCD and S is served
 // from that XCD's L2 after the first read.
-// Kernels in this file: tn_partial_kernel (generic, any shape / dtype), tn_partial_dma_kernel (bf16, one column group per
-// block), tn_partial_dma_wide_kernel (bf16, two column groups per block; grouped + persistent: single layers and small
-// groups), tn_partial_rows_kernel (bf16, a workgroup owns ALL columns of a token slab: whole decoder blocks, slab counts
-// planned over the group), the fp32 forms (exact and 3 x bf16), and tn_reduce (fixed-order slab sum).
+// Kernels in this file: tn_partial_kernel (generic, any shape / dtype), tn_partial_dma_kernel (bf16 / f16, one column group
+// per block), tn_partial_dma_wide_kernel (bf16 / f16, two column groups per block; grouped + persistent: single layers and
+// small groups), tn_partial_rows_kernel (bf16 / f16, a workgroup owns ALL columns of a token slab: whole decoder blocks, slab
+// counts planned over the group), the fp32 forms (exact and 3 x bf16), and tn_reduce (fixed-order slab sum).
+// The three LDS-DMA kernels move raw 16-bit words and accumulate fp32: their bodies are templates on the element type and
+// differ between bf16 and f16 in the MFMA opcode alone.  The bf16 kernels keep their plain names; the f16 forms are
+// templates of the same names (tn_partial_rows_kernel<f16_t>, ...).
 #include "kernels.hpp"
 #include "lds_dma.hpp"
 #include <cstdlib>
@@ -195,7 +198,7 @@ template <typename T> __global__ __launch_bounds__(256, 2) void tn_partial_kerne
 }
 
 // =================================================================================================
-// bf16 fast path: wave-private LDS-DMA rings + transposed LDS reads (gfx950).
+// bf16 / f16 fast path: wave-private LDS-DMA rings + transposed LDS reads (gfx950).
 //
 // Each of the 4 waves streams its own 16-token groups (group g of the slab goes to wave g % 4, so the
 // workgroup as a whole reads contiguous memory): per group two 1-KiB `global_load_lds_dwordx4`
@@ -225,7 +228,10 @@ __device__ __forceinline__ void tn_wait_stages(int newer) {
   }
 }
 
-__global__ __launch_bounds__(256, 2) void tn_partial_dma_kernel(const TnParams p) {
+// A template on the element type alone (T = bf16_t, f16_t): this kernel reads its argument block directly, and moving its body
+// into a helper shared with a plain bf16 kernel changes the bf16 instruction schedule, so both dtypes are instantiations here;
+// tn_partial_dma_kernel<bf16_t> is instruction for instruction the former non-template kernel.
+template <typename T> __global__ __launch_bounds__(256, 2) void tn_partial_dma_kernel(const TnParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int t = threadIdx.x, lane = t & 63;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);  // wave id as a scalar: keeps the pipeline control flow uniform
@@ -236,8 +242,8 @@ __global__ __launch_bounds__(256, 2) void tn_partial_dma_kernel(const TnParams p
   }
   // copy the job into scalars once (a reference into the kernel-argument block with a runtime index
   // makes the compiler re-load it inside the loop)
-  const bf16_t* Mg = (const bf16_t*)(jid ? p.job[1].M : p.job[0].M);
-  const bf16_t* Sg = (const bf16_t*)(jid ? p.job[1].S : p.job[0].S);
+  const T* Mg = (const T*)(jid ? p.job[1].M : p.job[0].M);
+  const T* Sg = (const T*)(jid ? p.job[1].S : p.job[0].S);
   float* Pg = jid ? p.job[1].partial : p.job[0].partial;
   const int64_t ldm = jid ? p.job[1].ldm : p.job[0].ldm;
   const int D = jid ? p.job[1].D : p.job[0].D;
@@ -337,11 +343,12 @@ __global__ __launch_bounds__(256, 2) void tn_partial_dma_kernel(const TnParams p
         : "v"(ad0), "v"(ad1)
         : "memory");
     __builtin_amdgcn_sched_barrier(0);
-    bf16x8 af[2], bfr[2];
-    af[0] = __builtin_bit_cast(bf16x8, (u32x4){a00[0], a00[1], a01[0], a01[1]});
-    af[1] = __builtin_bit_cast(bf16x8, (u32x4){a10[0], a10[1], a11[0], a11[1]});
-    bfr[0] = __builtin_bit_cast(bf16x8, (u32x4){b00[0], b00[1], b01[0], b01[1]});
-    bfr[1] = __builtin_bit_cast(bf16x8, (u32x4){b10[0], b10[1], b11[0], b11[1]});
+    // integer registers up to the MFMA call: only the fragment type (and with it the opcode) depends on T
+    typename DT<T>::v8 af[2], bfr[2];
+    af[0] = as_v8<T>(join2(a00, a01));
+    af[1] = as_v8<T>(join2(a10, a11));
+    bfr[0] = as_v8<T>(join2(b00, b01));
+    bfr[1] = as_v8<T>(join2(b10, b11));
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -378,7 +385,7 @@ __global__ __launch_bounds__(256, 2) void tn_partial_dma_kernel(const TnParams p
 }
 
 // =================================================================================================
-// bf16 wide variant: 8 waves, TWO 64-column groups of M per workgroup.
+// bf16 / f16 wide variant: 8 waves, TWO 64-column groups of M per workgroup.
 //
 // With one column group per block the S stream (h / dh rows, served by L2) is as large as the M stream (HBM):
 // 134 MB of LDS-DMA for 67 MB of HBM on a 512/512 layer, and the kernel is bound by the DMA path as a whole.
@@ -398,6 +405,7 @@ __device__ __forceinline__ void tnw_wait_stages(int newer) {   // 6 DMA instruct
   }
 }
 
+template <typename T>
 __device__ __forceinline__ void tnw_block(const TnParams& p, int b, char* smem, const int t, const int lane, const int w) {
   int jid = 0;
   const int ncg2_0 = (p.job[0].ncg + 1) / 2;
@@ -405,8 +413,8 @@ __device__ __forceinline__ void tnw_block(const TnParams& p, int b, char* smem, 
     b -= ncg2_0 * p.ns;
     jid = 1;
   }
-  const bf16_t* Mg = (const bf16_t*)(jid ? p.job[1].M : p.job[0].M);
-  const bf16_t* Sg = (const bf16_t*)(jid ? p.job[1].S : p.job[0].S);
+  const T* Mg = (const T*)(jid ? p.job[1].M : p.job[0].M);
+  const T* Sg = (const T*)(jid ? p.job[1].S : p.job[0].S);
   float* Pg = jid ? p.job[1].partial : p.job[0].partial;
   const int64_t ldm = jid ? p.job[1].ldm : p.job[0].ldm;
   const int D = jid ? p.job[1].D : p.job[0].D;
@@ -496,12 +504,12 @@ __device__ __forceinline__ void tnw_block(const TnParams& p, int b, char* smem, 
       DS_READ_TR(sh[c], ad, 512);
     }
     LGKM_WAIT0();
-    bf16x8 bfr[2];
+    typename DT<T>::v8 bfr[2];
 #pragma unroll
-    for (int c = 0; c < 2; ++c) bfr[c] = as_bf16x8(join2(sl[c], sh[c]));
+    for (int c = 0; c < 2; ++c) bfr[c] = as_v8<T>(join2(sl[c], sh[c]));
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
-      const bf16x8 af = as_bf16x8(join2(ml[a], mh[a]));
+      const typename DT<T>::v8 af = as_v8<T>(join2(ml[a], mh[a]));
       acc[a][0] = mfma32(af, bfr[0], acc[a][0]);
       acc[a][1] = mfma32(af, bfr[1], acc[a][1]);
     }
@@ -554,12 +562,29 @@ __global__ __launch_bounds__(64 * TNW_WAVES, 1) void tn_partial_dma_wide_kernel(
       if (i < grp.n && blk >= grp.start[i]) layer = i;
     int tt = t;
     asm volatile("" : "+v"(tt));   // keeps per-lane address arithmetic inside the iteration (see chain2.hip)
-    tnw_block(grp.p[layer], blk - grp.start[layer], smem, tt, tt & 63, w);
+    tnw_block<bf16_t>(grp.p[layer], blk - grp.start[layer], smem, tt, tt & 63, w);
+  }
+}
+// The f16 form: the same loop over tnw_block<f16_t>, as a template of the same name.  (The bf16 kernel keeps its plain symbol
+// and its own copy of the loop: routing both through one inlined helper changes the bf16 kernel's instruction schedule.)
+template <typename T> __global__ __launch_bounds__(64 * TNW_WAVES, 1) void tn_partial_dma_wide_kernel(const TnGroup grp) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int t = threadIdx.x;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int total = grp.start[TN_MAXG];
+  for (int blk = (int)blockIdx.x; blk < total; blk += (int)gridDim.x) {
+    int layer = 0;
+#pragma unroll
+    for (int i = 1; i < TN_MAXG; ++i)
+      if (i < grp.n && blk >= grp.start[i]) layer = i;
+    int tt = t;
+    asm volatile("" : "+v"(tt));
+    tnw_block<T>(grp.p[layer], blk - grp.start[layer], smem, tt, tt & 63, w);
   }
 }
 
 // =================================================================================================
-// bf16 row-owner variant (grouped launches of whole decoder blocks): a workgroup owns ALL columns of its token slab.
+// bf16 / f16 row-owner variant (grouped launches of whole decoder blocks): a workgroup owns ALL columns of its token slab.
 //
 // The column-owner kernels above re-read S (h / dh: 128 bytes per token) once per 128 columns of M -- on a 512-wide
 // operand that is 4 x 4 MB from L2 beside 33.5 MB from HBM, and M arrives as 256-byte pieces of 1-KiB rows
@@ -595,7 +620,7 @@ __device__ __forceinline__ void tnr_wait(int n) {   // all but the n most recent
   __builtin_amdgcn_sched_barrier(0);
 }
 
-template <int CGW>
+template <typename T, int CGW>
 __device__ __forceinline__ void tnr_block(const TnRowsItem& J, const int b, char* smem, const int lane, const int w, const bool nt) {
   constexpr int KS = 2 / CGW;      // 16-token k-steps per stage
   constexpr int TOKS = 16 * KS;
@@ -612,8 +637,8 @@ __device__ __forceinline__ void tnr_block(const TnRowsItem& J, const int b, char
   const bool s_own = sq < 2 * KS;
   const int ni = 2 * (CGW == 2 ? nmy : 2 * nmy) + (s_own ? 1 : 0);   // DMA instructions of this wave per stage
 
-  const bf16_t* Mg = (const bf16_t*)J.M;
-  const bf16_t* Sg = (const bf16_t*)J.S;
+  const T* Mg = (const T*)J.M;
+  const T* Sg = (const T*)J.S;
   char* mring = smem + w * (TNR_DEPTH * TNR_MSLOT);
   char* sring = smem + TNR_WAVES * TNR_DEPTH * TNR_MSLOT;
   const char* zp = zero_page_for(lane);
@@ -721,15 +746,15 @@ __device__ __forceinline__ void tnr_block(const TnRowsItem& J, const int b, char
           DS_READ_TR(mh[gi][a], ad, 512);
         }
       LGKM_WAIT0();
-      bf16x8 bfr[2];
+      typename DT<T>::v8 bfr[2];
 #pragma unroll
-      for (int c = 0; c < 2; ++c) bfr[c] = as_bf16x8(join2(sl[c], sh[c]));
+      for (int c = 0; c < 2; ++c) bfr[c] = as_v8<T>(join2(sl[c], sh[c]));
 #pragma unroll
       for (int gi = 0; gi < CGW; ++gi) {
         if (gi < nmy) {   // wave-uniform; an image that is not this wave's holds stale data
 #pragma unroll
           for (int a = 0; a < 2; ++a) {
-            const bf16x8 af = as_bf16x8(join2(ml[gi][a], mh[gi][a]));
+            const typename DT<T>::v8 af = as_v8<T>(join2(ml[gi][a], mh[gi][a]));
             acc[gi][a][0] = mfma32(af, bfr[0], acc[gi][a][0]);
             acc[gi][a][1] = mfma32(af, bfr[1], acc[gi][a][1]);
           }
@@ -766,8 +791,24 @@ __global__ __launch_bounds__(64 * TNR_WAVES, 1) void tn_partial_rows_kernel(cons
       if (i < grp.n && blk >= grp.it[i].start) item = i;
     int tt = (int)threadIdx.x;
     asm volatile("" : "+v"(tt));   // keeps per-lane address arithmetic inside the iteration (see chain2.hip)
-    if (grp.it[item].cgw == 2) tnr_block<2>(grp.it[item], blk - grp.it[item].start, smem, tt & 63, w, grp.nt_load != 0);
-    else tnr_block<1>(grp.it[item], blk - grp.it[item].start, smem, tt & 63, w, grp.nt_load != 0);
+    if (grp.it[item].cgw == 2) tnr_block<bf16_t, 2>(grp.it[item], blk - grp.it[item].start, smem, tt & 63, w, grp.nt_load != 0);
+    else tnr_block<bf16_t, 1>(grp.it[item], blk - grp.it[item].start, smem, tt & 63, w, grp.nt_load != 0);
+  }
+}
+// The f16 form, a template of the same name (see tn_partial_dma_wide_kernel<T>): the traces of both dtypes show
+// sow::tn_partial_rows_kernel.
+template <typename T> __global__ __launch_bounds__(64 * TNR_WAVES, 1) void tn_partial_rows_kernel(const TnRowsGroup grp) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  for (int blk = (int)blockIdx.x; blk < grp.total; blk += (int)gridDim.x) {
+    int item = 0;
+#pragma unroll
+    for (int i = 1; i < TNR_MAXI; ++i)
+      if (i < grp.n && blk >= grp.it[i].start) item = i;
+    int tt = (int)threadIdx.x;
+    asm volatile("" : "+v"(tt));
+    if (grp.it[item].cgw == 2) tnr_block<T, 2>(grp.it[item], blk - grp.it[item].start, smem, tt & 63, w, grp.nt_load != 0);
+    else tnr_block<T, 1>(grp.it[item], blk - grp.it[item].start, smem, tt & 63, w, grp.nt_load != 0);
   }
 }
 
@@ -1291,12 +1332,16 @@ static int tn_wide_blocks(const TnParams& p) {
   return blocks2;
 }
 
+// the 16-bit dtypes whose weight gradients run on the LDS-DMA kernels (NO_F16_TN: f16 on the generic kernel, as before them)
+bool tn_dma_dtype(int dtype) { return dtype == SOW_BF16 || (dtype == SOW_F16 && !sw_on(SW_NO_F16_TN)); }
+
 bool tn_group_supported(const TnParams& p, int dtype) {
-  return dtype == SOW_BF16 && tn_wide_ok(p) && !sw_on(SW_TN_NARROW) && tn_wide_blocks(p) > 0;
+  return tn_dma_dtype(dtype) && tn_wide_ok(p) && !sw_on(SW_TN_NARROW) && tn_wide_blocks(p) > 0;
 }
 
-int launch_tn_group(const TnParams* ps, int n, hipStream_t stream) {
+int launch_tn_group(const TnParams* ps, int n, int dtype, hipStream_t stream) {
   if (n <= 0) return SOW_OK;
+  if (dtype != SOW_BF16 && dtype != SOW_F16) return SOW_ERR_DTYPE;
   if (n > TN_MAXG) return SOW_ERR_SHAPE;
   TnGroup g{};
   g.n = n;
@@ -1310,9 +1355,15 @@ int launch_tn_group(const TnParams* ps, int n, hipStream_t stream) {
   if (total <= 0) return SOW_OK;
   if (total > 0x7fffffff) return SOW_ERR_SHAPE;
   constexpr int LDS = TNW_WAVES * TNW_DEPTH * TNW_STAGE_BYTES;  // 144 KiB (rings; reused by the cross-wave sum)
-  SOW_SET_MAX_LDS_ONCE(LDS, tn_partial_dma_wide_kernel);
   const int64_t grid = (sw_on(SW_NO_PERSIST) || total < 256) ? total : 256;   // one resident workgroup per CU
-  hipLaunchKernelGGL(tn_partial_dma_wide_kernel, dim3((unsigned)grid), dim3(64 * TNW_WAVES), LDS, stream, g);
+  if (dtype == SOW_F16) {
+    SOW_SET_MAX_LDS_ONCE(LDS, tn_partial_dma_wide_kernel<f16_t>);
+    hipLaunchKernelGGL(tn_partial_dma_wide_kernel<f16_t>, dim3((unsigned)grid), dim3(64 * TNW_WAVES), LDS, stream, g);
+  } else {
+    void (*const bf16_kernel)(const TnGroup) = tn_partial_dma_wide_kernel;   // the plain (non-template) symbol
+    SOW_SET_MAX_LDS_ONCE(LDS, bf16_kernel);
+    hipLaunchKernelGGL(bf16_kernel, dim3((unsigned)grid), dim3(64 * TNW_WAVES), LDS, stream, g);
+  }
   SOW_CHECK_LAUNCH();
   return SOW_OK;
 }
@@ -1342,8 +1393,9 @@ bool tn_rows_plan(const int64_t* T, const int* D, const int* cap, int n, int* ns
   return total >= 160 && total <= 256;
 }
 
-int launch_tn_rows(TnRowsItem* items, int n, hipStream_t stream) {
+int launch_tn_rows(TnRowsItem* items, int n, int dtype, hipStream_t stream) {
   if (n <= 0) return SOW_OK;
+  if (dtype != SOW_BF16 && dtype != SOW_F16) return SOW_ERR_DTYPE;
   if (n > TNR_MAXI) return SOW_ERR_SHAPE;
   TnRowsGroup g{};
   g.n = n;
@@ -1365,8 +1417,15 @@ int launch_tn_rows(TnRowsItem* items, int n, hipStream_t stream) {
   // M (x, dY) is streamed once: non-temporal loads keep it out of the Infinity Cache, where dh, the slab partials and the next
   // kernels' operands live (the launch itself 135 -> 138 us, the step 3.82 -> 3.78 ms; TN_NO_NT_LOAD switch)
   g.nt_load = sw_on(SW_TN_NO_NT_LOAD) ? 0 : 1;
-  SOW_SET_MAX_LDS_ONCE(TNR_LDS, tn_partial_rows_kernel);
-  hipLaunchKernelGGL(tn_partial_rows_kernel, dim3((unsigned)(total < 256 ? total : 256)), dim3(64 * TNR_WAVES), TNR_LDS, stream, g);
+  const dim3 grid((unsigned)(total < 256 ? total : 256));
+  if (dtype == SOW_F16) {
+    SOW_SET_MAX_LDS_ONCE(TNR_LDS, tn_partial_rows_kernel<f16_t>);
+    hipLaunchKernelGGL(tn_partial_rows_kernel<f16_t>, grid, dim3(64 * TNR_WAVES), TNR_LDS, stream, g);
+  } else {
+    void (*const bf16_kernel)(const TnRowsGroup) = tn_partial_rows_kernel;   // the plain (non-template) symbol
+    SOW_SET_MAX_LDS_ONCE(TNR_LDS, bf16_kernel);
+    hipLaunchKernelGGL(bf16_kernel, grid, dim3(64 * TNR_WAVES), TNR_LDS, stream, g);
+  }
   SOW_CHECK_LAUNCH();
   return SOW_OK;
 }
@@ -1375,20 +1434,27 @@ int launch_tn(const TnParams& p, int dtype, hipStream_t stream) {
   int blocks = 0;
   for (int j = 0; j < p.njobs; ++j) blocks += p.job[j].ncg * p.ns;
   if (blocks == 0) return SOW_OK;
-  if (dtype == SOW_BF16) {
-    const bool dma = tn_wide_ok(p);
+  if (dtype == SOW_BF16 || dtype == SOW_F16) {
+    // one ladder for both 16-bit dtypes: wide DMA, narrow DMA under TN_NARROW, the generic kernel for ragged widths,
+    // misaligned views and slab lengths off 16 (and for every f16 shape under NO_F16_TN)
+    const bool f16 = dtype == SOW_F16;
+    const bool dma = tn_dma_dtype(dtype) && tn_wide_ok(p);
     if (dma && !sw_on(SW_TN_NARROW)) {
-      return launch_tn_group(&p, 1, stream);
+      return launch_tn_group(&p, 1, dtype, stream);
     } else if (dma) {
       constexpr int LDS = 4 * TN_DEPTH * TN_STAGE_BYTES;  // 64 KiB (rings; reused by the cross-wave sum)
-      SOW_SET_MAX_LDS_ONCE(LDS, tn_partial_dma_kernel);
-      hipLaunchKernelGGL(tn_partial_dma_kernel, dim3(blocks), dim3(256), LDS, stream, p);
+      if (f16) {
+        SOW_SET_MAX_LDS_ONCE(LDS, tn_partial_dma_kernel<f16_t>);
+        hipLaunchKernelGGL(tn_partial_dma_kernel<f16_t>, dim3(blocks), dim3(256), LDS, stream, p);
+      } else {
+        SOW_SET_MAX_LDS_ONCE(LDS, tn_partial_dma_kernel<bf16_t>);
+        hipLaunchKernelGGL(tn_partial_dma_kernel<bf16_t>, dim3(blocks), dim3(256), LDS, stream, p);
+      }
+    } else if (f16) {
+      hipLaunchKernelGGL(tn_partial_kernel<f16_t>, dim3(blocks), dim3(256), 0, stream, p);
     } else {
       hipLaunchKernelGGL(tn_partial_kernel<bf16_t>, dim3(blocks), dim3(256), 0, stream, p);
     }
-  } else if (dtype == SOW_F16) {
-    // no f16 LDS-DMA / row-owner kernels: the generic one for every shape
-    hipLaunchKernelGGL(tn_partial_kernel<f16_t>, dim3(blocks), dim3(256), 0, stream, p);
   } else if (dtype == SOW_F32) {
     bool dma = p.slab_len % 8 == 0;
     for (int j = 0; j < p.njobs; ++j) {

@@ -438,10 +438,12 @@ class LayerCall:
 
 
 class LayerGroup:
-    """n independent layer calls issued through sow_forward_group / sow_backward_group: layers on the bf16 streaming
+    """n independent layer calls issued through sow_forward_group / sow_backward_group: layers on the bf16 / f16 streaming
     kernels share launches (q / k / v; gate / up).  Outputs, input gradients and saved projections are bit-identical to n
     single calls; the weight gradients of a group large enough for the row-owner kernel (a whole decoder block) are summed
-    over differently cut token slabs and agree to fp32 rounding of those sums."""
+    over differently cut token slabs and agree to fp32 rounding of those sums.  bf16 takes the row-owner kernel under the
+    default phases too; f16 takes it only when `phases` carries BWD_GROUP_SLABS (the deferred reduction of FactorBucket),
+    so that backward() of an f16 group with the default phases stays bit-identical to single calls."""
 
     def __init__(self, calls: Sequence[LayerCall]):
         if not calls:
