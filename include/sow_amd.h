@@ -367,6 +367,24 @@ int sow_adamw_flat(void* param, const void* grad, void* exp_avg, void* exp_avg_s
                    double beta2, float eps, float weight_decay, int step, float grad_scale, int dtype, int state_dtype,
                    void* stream);
 
+/* AdamW over segments of one flat buffer: every segment [begin, end) (elements of the flat buffers) steps with its own lr,
+ * weight_decay and 1-based step count -- the factors and the biases of a biased model share one FactorBucket but not one
+ * torch param group (run_glue.py:796-808), and reset_optimizer zeroes the step of the factor group only.  `segs` is a
+ * HOST array, sorted by begin, ranges disjoint and non-empty; elements outside every segment are left untouched in all
+ * four buffers.  One launch per SOW_ADAMW_MAX_SEGMENTS segments.  Per segment 1 - lr*wd, lr/bc1 and sqrt(bc2) are formed in double and rounded
+ * once, as sow_adamw_flat forms them; the per-element arithmetic is sow_adamw_flat's, so one segment [0, n) reproduces it
+ * bit for bit.  Same dtype pairs as sow_adamw_flat.  SOW_ERR_SHAPE: an empty, negative, unsorted or overlapping range, a
+ * step < 1, n_segs < 0 (checked for every segment before anything is launched); SOW_ERR_NULL: a null pointer. */
+#define SOW_ADAMW_MAX_SEGMENTS 64 /* segments per launch; a longer table takes ceil(n_segs / 64) launches */
+typedef struct sow_adamw_segment {
+  int64_t begin, end;
+  float lr, weight_decay;
+  int step;
+} sow_adamw_segment;
+int sow_adamw_flat_seg(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, const sow_adamw_segment* segs,
+                       int n_segs, double beta1, double beta2, float eps, float grad_scale, int dtype, int state_dtype,
+                       void* stream);
+
 /* TTAdam dense section (ttadam.py:84-111), fp32 buffers; double betas (1 - beta formed in double). */
 int sow_ttadam_dense(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, double beta1,
                      double beta2, float eps, float step_size, float lr_times_wd, int clamp_v, void* stream);

@@ -21,6 +21,7 @@ ACC_NONE, ACC_LOWRANK, ACC_DENSE = 0, 1, 2
 H_COLS = 64
 BWD_DATA, BWD_WEIGHTS, BWD_WEIGHTS_PARTIAL, BWD_WEIGHTS_REDUCE = 1, 2, 4, 8
 BWD_GROUP_SLABS = 16     # sow_backward_group: slab counts planned over the group (deferred reduction from group descriptors)
+ERR_NULL = -1
 ERR_SHAPE = -2
 ERR_UNSUPPORTED = -6      # include/sow_amd.h SOW_ERR_UNSUPPORTED: nothing was launched
 
@@ -58,6 +59,14 @@ class TtAdamItem(ctypes.Structure):
     _fields_ = [("m", TtDesc), ("v", TtDesc), ("param", c_void_p), ("grad", c_void_p), ("ld_param", c_int64),
                 ("ld_grad", c_int64), ("step_size", c_float), ("lr_times_wd", c_float), ("has_state", ctypes.c_int32),
                 ("workspace", c_void_p), ("workspace_bytes", c_size_t)]
+
+
+ADAMW_MAX_SEGMENTS = 64   # include/sow_amd.h SOW_ADAMW_MAX_SEGMENTS: segments per launch of sow_adamw_flat_seg
+
+
+class AdamwSegment(ctypes.Structure):
+    """sow_adamw_segment of include/sow_amd.h."""
+    _fields_ = [("begin", c_int64), ("end", c_int64), ("lr", c_float), ("weight_decay", c_float), ("step", ctypes.c_int32)]
 
 
 # name -> (restype, argtypes); mirrors include/sow_amd.h one to one
@@ -99,6 +108,8 @@ SIGNATURES = {
     "sow_zero_state": (c_int, [POINTER(c_void_p), POINTER(c_int64), c_int, c_void_p]),
     "sow_adamw_flat": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_double, c_double, c_float,
                                c_float, c_int, c_float, c_int, c_int, c_void_p]),
+    "sow_adamw_flat_seg": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(AdamwSegment), c_int, c_double, c_double,
+                                   c_float, c_float, c_int, c_int, c_void_p]),
     "sow_ttadam_dense": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_float, c_float,
                                  c_float, c_int, c_void_p]),
     "sow_tt_kron_core": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),

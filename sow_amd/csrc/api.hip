@@ -1501,6 +1501,15 @@ int sow_adamw_flat(void* param, const void* grad, void* exp_avg, void* exp_avg_s
                            dtype, state_dtype, (hipStream_t)stream);
 }
 
+int sow_adamw_flat_seg(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, const sow_adamw_segment* segs,
+                       int n_segs, double beta1, double beta2, float eps, float grad_scale, int dtype, int state_dtype,
+                       void* stream) {
+  dtype = nofuse(dtype), state_dtype = nofuse(state_dtype);
+  if (flagged(dtype) || flagged(state_dtype)) return SOW_ERR_DTYPE;
+  return launch_adamw_flat_seg(param, grad, exp_avg, exp_avg_sq, segs, n_segs, beta1, beta2, eps, grad_scale, dtype,
+                               state_dtype, (hipStream_t)stream);
+}
+
 int sow_ttadam_dense(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, double beta1,
                      double beta2, float eps, float step_size, float lr_times_wd, int clamp_v, void* stream) {
   return launch_ttadam_dense(param, grad, exp_avg, exp_avg_sq, n, beta1, beta2, eps, step_size, lr_times_wd, clamp_v,

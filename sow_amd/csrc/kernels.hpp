@@ -352,6 +352,8 @@ int launch_accumulate_batch(const AccItem* items, int n, int dtype, hipStream_t 
 int launch_multi_zero(void* const* ptrs, const int64_t* bytes, int n, hipStream_t stream);
 int launch_adamw_flat(void* p, const void* g, void* m, void* v, int64_t n, float lr, double b1, double b2, float eps,
                       float wd, int step, float grad_scale, int dtype, int state_dtype, hipStream_t stream);
+int launch_adamw_flat_seg(void* p, const void* g, void* m, void* v, const sow_adamw_segment* segs, int n_segs, double b1,
+                          double b2, float eps, float grad_scale, int dtype, int state_dtype, hipStream_t stream);
 int launch_ttadam_dense(float* p, const float* g, float* m, float* v, int64_t n, double b1, double b2, float eps,
                         float step_size, float lr_wd, int clamp_v, hipStream_t stream);
 int launch_tt_kron_core(const float* A, const float* B, float* out, int ra0, int rb0, int ij, int ra1, int rb1,

@@ -108,6 +108,98 @@ int launch_adamw_flat(void* p, const void* g, void* m, void* v, int64_t n, float
 }
 
 // ---------------------------------------------------------------------------------------------
+// AdamW over SEGMENTS of one flat buffer: every segment [begin, end) has its own lr, weight decay and step count (the
+// factors at sow_lr with decay and a step that reset_optimizer zeroes, the biases at lr without decay: run_glue.py:796-808).
+// The per-element arithmetic is adamw_flat_kernel's, statement for statement; the three scalars that depend on lr, wd and
+// step come from the segment's table entry, formed on the host exactly as launch_adamw_flat forms them.  The table rides
+// in the kernel arguments.  A workgroup belongs to ONE segment (blocks [block0, block0 + nblocks) of the grid) and strides
+// over that segment only, so elements outside every segment are neither read nor written.
+// ---------------------------------------------------------------------------------------------
+constexpr int ADAMW_MAXSEG = SOW_ADAMW_MAX_SEGMENTS;   // segments per launch: 64 x 32 bytes of by-value arguments
+struct AdamwSeg {
+  int64_t begin, end;
+  float decay, step_size, bc2_sqrt;
+  int block0;   // first workgroup of this segment
+};
+struct AdamwSegTable {
+  AdamwSeg s[ADAMW_MAXSEG];
+  int n;
+};
+static_assert(sizeof(AdamwSegTable) + 4 * sizeof(void*) + 6 * sizeof(float) <= 4096,
+              "by-value kernel arguments must stay under 4 KiB");
+
+template <typename T, typename TS>
+__global__ __launch_bounds__(256) void adamw_flat_seg_kernel(T* p, const T* g, TS* m, TS* v, const AdamwSegTable tb, float b1,
+                                                             float c1, float b2, float c2, float eps, float grad_scale) {
+  const int blk = blockIdx.x;
+  int si = 0;
+  while (si + 1 < tb.n && blk >= tb.s[si + 1].block0) ++si;   // uniform: scalar loads of the argument table
+  const AdamwSeg& S = tb.s[si];
+  const int nblk = (si + 1 < tb.n ? tb.s[si + 1].block0 : (int)gridDim.x) - S.block0;
+  const float decay = S.decay, step_size = S.step_size, bc2_sqrt = S.bc2_sqrt;
+  const int64_t end = S.end, nth = (int64_t)nblk * blockDim.x;
+  for (int64_t i = S.begin + (int64_t)(blk - S.block0) * blockDim.x + threadIdx.x; i < end; i += nth) {
+    float pv = to_f32(p[i]);
+    const float gv = to_f32(g[i]) * grad_scale;
+    float mv = to_f32(m[i]), vv = to_f32(v[i]);
+    pv *= decay;
+    mv = b1 * mv + c1 * gv;
+    vv = b2 * vv + c2 * gv * gv;
+    const float denom = sqrtf(vv) / bc2_sqrt + eps;
+    pv -= step_size * (mv / denom);
+    p[i] = from_f32<T>(pv);
+    m[i] = from_f32<TS>(mv);
+    v[i] = from_f32<TS>(vv);
+  }
+}
+
+int launch_adamw_flat_seg(void* p, const void* g, void* m, void* v, const sow_adamw_segment* segs, int n_segs, double b1,
+                          double b2, float eps, float grad_scale, int dtype, int state_dtype, hipStream_t stream) {
+  if (n_segs < 0) return SOW_ERR_SHAPE;
+  if (n_segs == 0) return SOW_OK;
+  if (!p || !g || !m || !v || !segs) return SOW_ERR_NULL;
+  const bool dt_ok = (dtype == SOW_F32 && state_dtype == SOW_F32) ||
+                     ((dtype == SOW_BF16 || dtype == SOW_F16) && (state_dtype == dtype || state_dtype == SOW_F32));
+  if (!dt_ok) return SOW_ERR_DTYPE;
+  // every segment is checked before the first launch: sorted, disjoint, non-empty, step >= 1
+  for (int i = 0; i < n_segs; ++i) {
+    if (segs[i].begin < 0 || segs[i].end <= segs[i].begin || segs[i].step < 1) return SOW_ERR_SHAPE;
+    if (i && segs[i].begin < segs[i - 1].end) return SOW_ERR_SHAPE;
+  }
+  const float b1f = (float)b1, c1 = (float)(1.0 - b1), b2f = (float)b2, c2 = (float)(1.0 - b2);
+  for (int off = 0; off < n_segs; off += ADAMW_MAXSEG) {
+    AdamwSegTable tb;
+    tb.n = n_segs - off < ADAMW_MAXSEG ? n_segs - off : ADAMW_MAXSEG;
+    int64_t want = 0;
+    for (int i = 0; i < tb.n; ++i) want += (segs[off + i].end - segs[off + i].begin + 255) / 256;
+    int grid = 0;
+    for (int i = 0; i < tb.n; ++i) {
+      const sow_adamw_segment& s = segs[off + i];
+      const double bc1 = 1.0 - std::pow(b1, (double)s.step), bc2 = 1.0 - std::pow(b2, (double)s.step);
+      AdamwSeg& d = tb.s[i];
+      d.begin = s.begin, d.end = s.end;
+      d.decay = (float)(1.0 - (double)s.lr * s.weight_decay), d.step_size = (float)(s.lr / bc1), d.bc2_sqrt = (float)std::sqrt(bc2);
+      d.block0 = grid;
+      // as launch_adamw_flat: one workgroup per 256 elements, the launch capped at 2048 (shared in proportion)
+      int64_t nb = (s.end - s.begin + 255) / 256;
+      if (want > 2048) nb = nb * 2048 / want;
+      grid += nb < 1 ? 1 : (int)nb;
+    }
+    for (int i = tb.n; i < ADAMW_MAXSEG; ++i) tb.s[i] = AdamwSeg{0, 0, 1.f, 0.f, 1.f, grid};
+#define SOW_ADAMW_SEG(T, TS) \
+  hipLaunchKernelGGL((adamw_flat_seg_kernel<T, TS>), dim3(grid), dim3(256), 0, stream, (T*)p, (const T*)g, (TS*)m, (TS*)v, tb, b1f, c1, b2f, c2, eps, grad_scale)
+    if (dtype == SOW_F32) SOW_ADAMW_SEG(float, float);
+    else if (dtype == SOW_BF16 && state_dtype == SOW_BF16) SOW_ADAMW_SEG(bf16_t, bf16_t);
+    else if (dtype == SOW_BF16) SOW_ADAMW_SEG(bf16_t, float);
+    else if (state_dtype == SOW_F16) SOW_ADAMW_SEG(f16_t, f16_t);
+    else SOW_ADAMW_SEG(f16_t, float);
+#undef SOW_ADAMW_SEG
+    SOW_CHECK_LAUNCH();
+  }
+  return SOW_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // TTAdam dense section (ttadam.py:84-111), fp32:  v<0 -> 0 clamp (only when clamp_v), then
 //   m = b1*m + (1-b1)*g ; v = b2*v + (1-b2)*g*g ; p += -step_size * m/(sqrt(v)+eps) ; p += -lr*wd*p
 // 1 - b is formed in double on the host from double betas (the Python-float alpha = 1.0 - beta of ttadam.py:91-92).

@@ -24,15 +24,25 @@ import torch.nn as nn
 from .layer import SoWLinear
 
 
-def factor_parameters(model: nn.Module) -> List[nn.Parameter]:
+def factor_parameters(model: nn.Module, biases: bool = False) -> List[nn.Parameter]:
     """All A_i then B_i of every SoWLinear, in module order (the `special_params` list of
-    simple_train.py:389-405)."""
-    out = []
+    simple_train.py:389-405).  biases=True: followed by the bias of every SoWLinear that has one, in module order -- one
+    contiguous run at the end of a FactorBucket's flat buffers (RoBERTa: every SoW layer is biased, run_glue.py:796-808
+    trains those biases in a param group of their own)."""
+    out, tail = [], []
     for _, m in model.named_modules():
         if isinstance(m, SoWLinear):
             out.extend(list(m.downscale_weights))
             out.extend(list(m.upscale_weights))
-    return out
+            if biases and m.bias is not None:
+                tail.append(m.bias)
+    return out + tail
+
+
+def bias_route_ok(r: int) -> bool:
+    """Whether the weight-gradient kernels of a rank-r layer also produce dbias: through the all-ones column 63 of the saved
+    projection (r <= 63), or as the side sum of the wide kernel (even r in (64, 256]).  r == 64 has no free column."""
+    return r <= 63 or (64 < r <= 256 and r % 2 == 0)
 
 
 def _block_key(name: str) -> str:
@@ -59,16 +69,24 @@ class _GradSink:
     accumulating into the layers' views of the flat gradient buffer; the reductions of all blocks are deferred to
     FactorBucket.finalize()."""
 
-    def __init__(self, bucket, pA, pB, block=""):
+    def __init__(self, bucket, pA, pB, block="", pbias=None):
         self.bucket, self.pA, self.pB, self.block = bucket, pA, pB, block
+        self.pbias = pbias        # the layer's bias when it is a bucket member (its gradient comes with dB), else None
         self.ws = None
         self.pending = False      # partial sums launched, reduction not yet run
         self.queued = False       # data gradient done, waiting for the rest of the block
 
-    def usable(self, A, B) -> bool:
+    def usable(self, A, B, bias=None) -> bool:
         # n_iter == 1 layers only (A, B ARE the bucket's parameters), gradients bound to the flat buffer, r <= 256 (a wide
-        # layer's PARTIAL phase finishes its gradients; its deferred reduction is an empty descriptor)
-        pA, pB = self.pA, self.pB
+        # layer's PARTIAL phase finishes its gradients; its deferred reduction is an empty descriptor).  `bias`: the bias
+        # the forward ran with -- the sink's own (a bucket member whose gradient the kernels can produce) or none
+        pA, pB, pb = self.pA, self.pB, self.pbias
+        if bias is None:
+            if pb is not None:
+                return False
+        elif (pb is None or bias.data_ptr() != pb.data_ptr() or not bias_route_ok(B.shape[0]) or pb.grad is None
+              or pb.grad.data_ptr() != self.bucket.grad_ptr(pb)):
+            return False
         return (A.data_ptr() == pA.data_ptr() and B.data_ptr() == pB.data_ptr() and B.shape[0] <= 256
                 and pA.grad is not None and pB.grad is not None
                 and pA.grad.data_ptr() == self.bucket.grad_ptr(pA) and pB.grad.data_ptr() == self.bucket.grad_ptr(pB))
@@ -154,11 +172,18 @@ class FactorBucket:
         return self.flat_grad.data_ptr() + self._off_of[id(p)] * self.flat_grad.element_size()
 
     def attach(self, model: nn.Module, auto_all_reduce: bool = False, group=None) -> int:
-        """Let the SoWLinear layers of `model` (n_iter = 1, no bias) write their weight gradients straight into the
+        """Let the SoWLinear layers of `model` (n_iter = 1) write their weight gradients straight into the
         flat buffer and defer the final reduction to finalize(): one launch per step instead of one per layer, and no
         per-parameter AccumulateGrad.  Gradients ACCUMULATE (zero_grad() between steps); call finalize() after
         backward, before the gradients are read (all_reduce_async() and FactorAdamW.step() do).  Returns the number of
-        layers attached; layers with a bias or n_iter > 1 keep the ordinary autograd path.
+        layers attached; layers with n_iter > 1 keep the ordinary autograd path.
+
+        A layer with a bias is attached when and only when the bias is a member of this bucket
+        (`FactorBucket(factor_parameters(model, biases=True))`) and the layer's weight-gradient kernels can produce dbias:
+        rank <= 63 (the all-ones column 63 of the saved projection) or an even rank in (64, 256] (the side sum of the wide
+        kernel).  Its bias gradient then lands in the flat buffer with dB and autograd gets None for it.  A biased layer
+        of rank 64, or one whose bias is not in the bucket, keeps autograd; autograd's AccumulateGrad adds into the same
+        flat views, so its gradients still arrive in the bucket.
 
         auto_all_reduce: issue the bucket's single all-reduce FROM BACKWARD, as soon as the last attached layer has
         queued its partial sums (the first SoW layer of the model: what is left of backward -- embedding gradients, DDP's
@@ -181,11 +206,15 @@ class FactorBucket:
         n = 0
         self._blocks = {}
         for name, m in model.named_modules():
-            if isinstance(m, SoWLinear) and m.n_iter == 1 and m.bias is None:
+            if isinstance(m, SoWLinear) and m.n_iter == 1:
                 pA, pB = m.downscale_weights._parameters["0"], m.upscale_weights._parameters["0"]
+                pb = m.bias
+                if pb is not None and not (id(pb) in mine and bias_route_ok(pB.shape[0])
+                                           and pb.grad is not None and pb.grad.data_ptr() == self.grad_ptr(pb)):
+                    continue
                 if id(pA) in mine and id(pB) in mine:
                     key = _block_key(name)
-                    m._grad_sink = _GradSink(self, pA, pB, key)
+                    m._grad_sink = _GradSink(self, pA, pB, key, pb)
                     self._blocks.setdefault(key, {"n": 0, "queue": []})["n"] += 1
                     n += 1
         self._n_attached = n
@@ -195,7 +224,8 @@ class FactorBucket:
     def exclude_from_ddp(self, model: nn.Module) -> List[str]:
         """Put the bucket's parameters on DistributedDataParallel's ignore list for `model` (call before wrapping):
         DDP then reduces only the non-factor parameters (embeddings, norms, lm_head) in its own buckets while the
-        factors travel in this bucket's ONE all-reduce."""
+        factors -- and the biases of a bucket built with factor_parameters(model, biases=True) -- travel in this bucket's
+        ONE all-reduce.  Returns the names put on the list."""
         mine = {id(p) for p in self.params}
         names = [n for n, p in model.named_parameters() if id(p) in mine]
         torch.nn.parallel.DistributedDataParallel._set_params_and_buffers_to_ignore_for_model(model, names)
@@ -275,11 +305,12 @@ class FactorBucket:
                 a.acc_down = acc_down.data_ptr() if acc_down is not None else None
                 a.acc_up = acc_up.data_ptr() if acc_up is not None else None
                 a.bias, a.y, a.h_save, a.dy, a.dx = None, dy2.data_ptr(), h.data_ptr(), dy2.data_ptr(), x2.data_ptr()
-                a.dA, a.dB, a.dbias = sink.pA.grad.data_ptr(), sink.pB.grad.data_ptr(), None
+                a.dA, a.dB = sink.pA.grad.data_ptr(), sink.pB.grad.data_ptr()
+                a.dbias = sink.pbias.grad.data_ptr() if sink.pbias is not None else None
                 a.T, a.d_in, a.d_out, a.r_live, a.r_acc, a.acc_kind = T, d_in, d_out, r, r_acc, kind
                 a.scale, a.grad_beta = scale, 1.0
                 a.workspace, a.workspace_bytes = sink.ws.data_ptr(), sink.ws.numel()
-                stable.append((a.dA, a.dB, a.workspace, a.workspace_bytes, T, d_in, d_out, r, r_acc, kind))
+                stable.append((a.dA, a.dB, a.dbias, a.workspace, a.workspace_bytes, T, d_in, d_out, r, r_acc, kind))
             group = ops.LayerGroup.from_args(arr, len(run), dt, dev, keep=run)
             phases = _lib.BWD_WEIGHTS_PARTIAL | _lib.BWD_GROUP_SLABS
             group.backward(phases)

@@ -71,9 +71,10 @@ class _SoWGroupFunction(torch.autograd.Function):
         x2, hs, tensors = saved[0], saved[1:1 + n], saved[1 + n:]
         sinks = ctx.sinks
         if sinks is not None and x2.shape[0] > 0 and all(
-                s.usable(tensors[5 * i], tensors[5 * i + 1]) and tensors[5 * i + 4] is None for i, s in enumerate(sinks)):
+                s.usable(tensors[5 * i], tensors[5 * i + 1], tensors[5 * i + 4]) for i, s in enumerate(sinks)):
             # FactorBucket.attach(): ONE data-gradient launch for the siblings, weight gradients queued with their decoder
-            # block (dp._GradSink); autograd gets None for the factors
+            # block (dp._GradSink); autograd gets None for the factors and for biases that are bucket members (the data
+            # phase below writes no weight gradient: its dbias stays None)
             recs = []
             for i, sink in enumerate(sinks):
                 A, B, acc_down, acc_up, _ = tensors[5 * i:5 * i + 5]

@@ -98,6 +98,7 @@ class _SoWFunction(torch.autograd.Function):
         ctx.save_for_backward(x2, h, A, B, acc_down, acc_up)
         ctx.scale = scale
         ctx.has_bias = bias is not None
+        ctx.bias = bias           # identity only (the sink checks it is the bucket's parameter); backward reads no bias
         ctx.x_shape, ctx.x_dtype = x.shape, x.dtype
         ctx.sink = sink
         ctx.mixed = cdt is not None
@@ -108,10 +109,11 @@ class _SoWFunction(torch.autograd.Function):
         x2, h, A, B, acc_down, acc_up = ctx.saved_tensors
         dy2 = dy.reshape(-1, dy.shape[-1])
         sink = ctx.sink
-        if sink is not None and not ctx.has_bias and x2.shape[0] > 0 and sink.usable(A, B):
+        if sink is not None and x2.shape[0] > 0 and sink.usable(A, B, ctx.bias):
             # FactorBucket.attach(): the weight gradients accumulate straight into the flat gradient buffer (p.grad is a
-            # view of it), so autograd gets None for A and B; their slab-partial sums are reduced for all layers in one
-            # launch by FactorBucket.finalize() (sow_reduce_batch).
+            # view of it), so autograd gets None for A and B (and for a bias that is a bucket member: its gradient comes
+            # out of the same partial sums); the slab-partial sums are reduced for all layers in one launch by
+            # FactorBucket.finalize() (sow_reduce_batch).
             dx = sink.backward(dy2, x2, h, A, B, acc_down, acc_up, ctx.scale)
             dA = dB = dbias = None
         else:

@@ -737,6 +737,23 @@ def adamw_flat_(param: torch.Tensor, grad: torch.Tensor, exp_avg: torch.Tensor, 
             betas[0], betas[1], eps, weight_decay, int(step), grad_scale, _dt(param), _dt(exp_avg))
 
 
+def adamw_flat_seg_(param: torch.Tensor, grad: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, segments, *,
+                    betas=(0.9, 0.999), eps: float = 1e-8, grad_scale: float = 1.0) -> None:
+    """AdamW over segments of the flat buffers (include/sow_amd.h: sow_adamw_flat_seg).  `segments`: (begin, end, lr,
+    weight_decay, step) per segment, in elements, sorted and disjoint; everything outside them is left untouched."""
+    lib = _lib.load()
+    dev = _need_gpu(param, grad, exp_avg, exp_avg_sq)
+    n = len(segments)
+    if not (param.numel() == grad.numel() == exp_avg.numel() == exp_avg_sq.numel()):
+        raise ValueError("sow_amd.adamw_flat_seg_: the four buffers must have one length")
+    if any(int(e) > param.numel() for _, e, *_ in segments):
+        raise ValueError("sow_amd.adamw_flat_seg_: a segment ends past the buffers")
+    arr = (_lib.AdamwSegment * max(n, 1))(*[_lib.AdamwSegment(int(b), int(e), float(lr), float(wd), int(st))
+                                            for b, e, lr, wd, st in segments])
+    _launch(dev, "sow_adamw_flat_seg", lib.sow_adamw_flat_seg, _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), arr, n,
+            betas[0], betas[1], eps, grad_scale, _dt(param), _dt(exp_avg))
+
+
 def ttadam_dense_(param, grad, exp_avg, exp_avg_sq, *, beta1, beta2, eps, step_size, lr_times_wd, clamp_v: bool) -> None:
     lib = _lib.load()
     dev = _need_gpu(param, grad, exp_avg, exp_avg_sq)

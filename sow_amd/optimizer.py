@@ -192,15 +192,46 @@ class TTSGD(torch.optim.Optimizer):
 class FactorAdamW:
     """Fused AdamW for the SoW factor parameter group (simple_train.py:502-506): all factors and
     their gradients live in ONE flat buffer each, so the step is one kernel launch and the DP
-    all-reduce one collective (see sow_amd/dp.py).  torch.optim.AdamW semantics."""
+    all-reduce one collective (see sow_amd/dp.py).  torch.optim.AdamW semantics.
 
-    def __init__(self, bucket, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, state_dtype=None):
+    param_groups: a list of torch-style dicts {"params": [...], "lr": ..., "weight_decay": ...} that together hold every
+    parameter of the bucket exactly once (ValueError otherwise) -- the factors at sow_lr with weight decay and the biases
+    at lr without, run_glue.py:796-808.  betas and eps are shared; a group without "lr" / "weight_decay" takes the
+    constructor's.  Each group has its own step count, reset_state(group_id) resets one group, and step() is still ONE
+    launch (sow_adamw_flat_seg over the groups' segments of the flat buffer).  Without param_groups the object is the
+    one-group optimizer it has always been (sow_adamw_flat, the same state_dict keys)."""
+
+    def __init__(self, bucket, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, state_dtype=None, param_groups=None):
         self.bucket = bucket
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         sd = state_dtype or bucket.flat_param.dtype
         self.exp_avg = torch.zeros_like(bucket.flat_param, dtype=sd)
         self.exp_avg_sq = torch.zeros_like(bucket.flat_param, dtype=sd)
         self.step_count = 0
+        self._groups = None
+        if param_groups is not None:
+            slot = {id(p): i for i, p in enumerate(bucket.params)}
+            owner = [None] * len(bucket.params)
+            self._groups = []
+            for gi, g in enumerate(param_groups):
+                g = dict(g)
+                g["params"] = list(g["params"])
+                g.setdefault("lr", lr)
+                g.setdefault("weight_decay", weight_decay)
+                g["betas"], g["eps"] = betas, eps
+                for p in g["params"]:
+                    i = slot.get(id(p))
+                    if i is None:
+                        raise ValueError(f"FactorAdamW: a parameter of param group {gi} is not in the bucket")
+                    if owner[i] is not None:
+                        raise ValueError(f"FactorAdamW: bucket parameter {i} is in param groups {owner[i]} and {gi}")
+                    owner[i] = gi
+                self._groups.append(g)
+            missing = [i for i, o in enumerate(owner) if o is None]
+            if missing:
+                raise ValueError(f"FactorAdamW: {len(missing)} bucket parameters are in no param group (first: slot {missing[0]})")
+            self._owner = owner
+            self.group_steps = [0] * len(self._groups)
 
     def _sync_from_group(self):
         """Hyper-parameters written through param_groups[0] (what LR schedulers and drivers do: `group["lr"] = v`,
@@ -209,6 +240,26 @@ class FactorAdamW:
         if g is not None:
             self.lr, self.betas, self.eps, self.weight_decay = g["lr"], g["betas"], g["eps"], g["weight_decay"]
 
+    def _group_ranges(self):
+        """[(group id, begin, end)] over the flat buffer, sorted: adjacent slots of one group merged, the 64-element
+        padding of a slot belonging to the slot before it."""
+        offs = list(self.bucket.offsets) + [self.bucket.padded_numel]
+        out = []
+        for i, gi in enumerate(self._owner):
+            if out and out[-1][0] == gi:
+                out[-1][2] = offs[i + 1]
+            else:
+                out.append([gi, offs[i], offs[i + 1]])
+        return [tuple(r) for r in out]
+
+    def segments(self, advance: int = 1):
+        """The segment table the next step() launches: (begin, end, lr, weight_decay, step) per segment, each group's
+        current hyper-parameters and its step count + `advance`.  A pure function of the bucket layout and the groups."""
+        if self._groups is None:
+            raise RuntimeError("FactorAdamW.segments: the optimizer was built without param_groups")
+        return [(b, e, float(self._groups[gi]["lr"]), float(self._groups[gi]["weight_decay"]), self.group_steps[gi] + advance)
+                for gi, b, e in self._group_ranges()]
+
     def step(self, grad_scale: float = 1.0):
         self._sync_from_group()
         self.bucket.finalize()   # pending deferred weight-gradient reductions (FactorBucket.attach)
@@ -216,24 +267,47 @@ class FactorAdamW:
             if p.data_ptr() != self.bucket.flat_param.data_ptr() + o * self.bucket.flat_param.element_size():
                 raise RuntimeError("FactorAdamW.step: a factor no longer lives in the flat buffer (SoWLinear.accumulate() "
                                    "rebinds .data) -- call bucket.rebind() after accumulate(); sow_amd.accumulate(model) does")
+        if self._groups is not None:
+            segs = self.segments()
+            ops.adamw_flat_seg_(self.bucket.flat_param, self.bucket.flat_grad, self.exp_avg, self.exp_avg_sq, segs,
+                                betas=self.betas, eps=self.eps, grad_scale=grad_scale)
+            self.group_steps = [s + 1 for s in self.group_steps]
+            self.step_count += 1
+            return
         self.step_count += 1
         ops.adamw_flat_(self.bucket.flat_param, self.bucket.flat_grad, self.exp_avg, self.exp_avg_sq, lr=self.lr,
                         betas=self.betas, eps=self.eps, weight_decay=self.weight_decay, step=self.step_count,
                         grad_scale=grad_scale)
 
-    def reset_state(self):
-        """reset_optimizer for the factor group (training_utils.py:257-277) as one launch."""
-        ops.zero_([self.exp_avg, self.exp_avg_sq])
-        self.step_count = 0
+    def reset_state(self, group_id=None):
+        """reset_optimizer for the factor group (training_utils.py:257-277) as one launch.  group_id: zero the moments of
+        that param group only (its ranges of exp_avg and exp_avg_sq, ONE sow_zero_state call) and set its step to 0 --
+        the reference resets the factor group and leaves the bias group's state and step alone."""
+        if group_id is None:
+            ops.zero_([self.exp_avg, self.exp_avg_sq])
+            self.step_count = 0
+            if self._groups is not None:
+                self.group_steps = [0] * len(self._groups)
+            return
+        if self._groups is None or not 0 <= int(group_id) < len(self._groups):
+            raise ValueError(f"FactorAdamW.reset_state: no param group {group_id}")
+        views = []
+        for gi, b, e in self._group_ranges():
+            if gi == int(group_id):
+                views += [self.exp_avg[b:e], self.exp_avg_sq[b:e]]
+        ops.zero_(views)
+        self.group_steps[int(group_id)] = 0
 
     # ---- checkpoint / scheduler surface (simple_train.py:182, 537-563 save and restore optimizer + scheduler state)
     @property
     def param_groups(self):
-        """One group, torch.optim style.  A driver's own scheduler code (`for g in opt.param_groups: g["lr"] = lr`) works on
-        it: step() and state_dict() read the group's values.  torch.optim.lr_scheduler classes insist on a real
-        torch.optim.Optimizer instance and do not accept this object -- drive the factor lr from the loop instead (the
-        reference computes its schedule with a LambdaLR over the torch optimizer; read `scheduler.get_last_lr()` and write
-        it here)."""
+        """One group, torch.optim style -- or the groups the optimizer was built with.  A driver's own scheduler code
+        (`for g in opt.param_groups: g["lr"] = lr`) works on them: step() and state_dict() read the groups' values.
+        torch.optim.lr_scheduler classes insist on a real torch.optim.Optimizer instance and do not accept this object --
+        drive the factor lr from the loop instead (the reference computes its schedule with a LambdaLR over the torch
+        optimizer; read `scheduler.get_last_lr()` and write it here)."""
+        if self._groups is not None:
+            return self._groups
         if not hasattr(self, "_group"):
             self._group = {"params": self.bucket.params, "lr": self.lr, "betas": self.betas, "eps": self.eps,
                            "weight_decay": self.weight_decay}
@@ -246,16 +320,34 @@ class FactorAdamW:
 
     def state_dict(self):
         self._sync_from_group()
-        return {"step": self.step_count, "exp_avg": self.exp_avg.clone(), "exp_avg_sq": self.exp_avg_sq.clone(),
-                "lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
-                "numel": self.bucket.padded_numel}
+        sd = {"step": self.step_count, "exp_avg": self.exp_avg.clone(), "exp_avg_sq": self.exp_avg_sq.clone(),
+              "lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
+              "numel": self.bucket.padded_numel}
+        if self._groups is not None:
+            sd["group_lr"] = [float(g["lr"]) for g in self._groups]
+            sd["group_weight_decay"] = [float(g["weight_decay"]) for g in self._groups]
+            sd["group_steps"] = list(self.group_steps)
+        return sd
 
     def load_state_dict(self, sd):
         if int(sd["numel"]) != self.bucket.padded_numel:
             raise ValueError("FactorAdamW.load_state_dict: the checkpoint belongs to a different factor layout")
+        if self._groups is not None and "group_steps" in sd and len(sd["group_steps"]) != len(self._groups):
+            raise ValueError("FactorAdamW.load_state_dict: the checkpoint has a different number of param groups")
         self.step_count = int(sd["step"])
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         self.lr, self.betas, self.eps, self.weight_decay = float(sd["lr"]), tuple(sd["betas"]), float(sd["eps"]), float(sd["weight_decay"])
         if hasattr(self, "_group"):
             self._group.update(lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay)
+        if self._groups is not None:
+            if "group_steps" in sd:
+                for g, lr, wd in zip(self._groups, sd["group_lr"], sd["group_weight_decay"]):
+                    g["lr"], g["weight_decay"] = float(lr), float(wd)
+                self.group_steps = [int(s) for s in sd["group_steps"]]
+            else:   # a one-group checkpoint: its hyper-parameters and step for every group
+                for g in self._groups:
+                    g["lr"], g["weight_decay"] = self.lr, self.weight_decay
+                self.group_steps = [self.step_count] * len(self._groups)
+            for g in self._groups:
+                g["betas"], g["eps"] = self.betas, self.eps
