@@ -442,6 +442,52 @@ def test_layer_path(c):
     _check(c, d, out)
 
 
+def _has_kernel(seq, kernel):
+    # demangled ("sow::chain_kernel<...>") or mangled ("_ZN3sow12chain_kernel...") names of exactly this kernel
+    return any(f"sow::{kernel}" in n or f"{len(kernel)}{kernel}" in n for n in seq)
+
+
+# Dispatch switches (api.hip, gemm2.hip): (case, kernels the trace must show, kernels it must not).  The rounding class of
+# each is read off the path the switch leaves:
+# * NO_SHORT_SPLIT: launch_chain_short declines (api.hip:117), the layer (no accumulator) runs the unsplit chain: y and dX
+#   are still written by one kernel from operands the test sees ("once");
+# * FORCE_GEMM_V1: gemm4h / gemm2h / gemm2 all decline, gemm_auto takes the generic kernel for x W_acc and dY W_acc^T and
+#   the chain adds the low-rank term with beta = 1 ("twice", as dense_misaligned);
+# * NO_GEMM3S: a dense layer with fewer than 160 tiles of 256 x 256 fails gemm2_supported (gemm2.hip:246-248) and takes the
+#   same generic composition ("twice"); without the switch its >= 96 tiles of 128 x 128 run gemm3s_kernel.
+_FAST_GEMMS = ("gemm2_kernel", "gemm2h_kernel", "gemm3_kernel", "gemm3s_kernel", "gemm4_kernel", "gemm4_f16_kernel")
+SWITCHED = [
+    (Case("no_short_split_bf16", BF16, 700, 1024, 1536, 50, s=0.5, switches=dict(NO_SHORT_SPLIT=1)), ("chain2_kernel",), ("h_reduce_kernel",)),
+    (Case("no_short_split_f32", F32, 700, 1024, 1536, 50, s=0.5, switches=dict(NO_SHORT_SPLIT=1)), (), ("h_reduce_kernel",)),
+    (Case("force_gemm_v1_dense", BF16, 4097, 512, 264, 50, acc="dense", switches=dict(FORCE_GEMM_V1=1), y_rounds="twice"),
+     ("gemm_kernel",), _FAST_GEMMS),
+    (Case("no_gemm3s_dense_short", BF16, 1800, 1024, 1800, 16, acc="dense", s=0.5, switches=dict(NO_GEMM3S=1), y_rounds="twice"),
+     ("gemm_kernel",), ("gemm3s_kernel",)),
+]
+
+
+@pytest.mark.parametrize("c,present,absent", SWITCHED, ids=[s[0].name for s in SWITCHED])
+def test_switched_layer_path(c, present, absent):
+    d = _inputs(c)
+    trace = {}
+    out = _run_single(c, d, trace)
+    seq = trace["fwd"] + trace["bwd"]
+    for k in present:
+        assert _has_kernel(seq, k), f"{c.name}: no {k} in {sorted(set(seq))}"
+    for k in absent:
+        assert not _has_kernel(seq, k), f"{c.name}: {k} ran under {c.switches}: {sorted(set(seq))}"
+    _check(c, d, out)
+
+
+def test_short_split_and_gemm3s_are_the_defaults_the_switches_replace():
+    """The two shapes above without their switch: the short split's h_reduce_kernel and gemm3s_kernel do run by default, so
+    the switched cases take another path than the unswitched ones."""
+    for (c, _, absent) in (SWITCHED[0], SWITCHED[3]):
+        trace = {}
+        _run_single(dataclasses.replace(c, switches={}), _inputs(c), trace)
+        assert _has_kernel(trace["fwd"] + trace["bwd"], absent[0]), f"{c.name}: {absent[0]} is not the default path"
+
+
 # ---- grouped calls: sow_forward_group shares chain2 launches; sow_backward_group with DATA | WEIGHTS plans the row-owner
 # weight-gradient kernel (tn_partial_rows) over the group (group_rows_plan: bf16, widths % 8, 16-byte views, r <= 63
 # with a bias)
@@ -520,9 +566,26 @@ def test_gemm_path(name, M, N, K, has_bias, beta, use_ws):
     WORST[(name, "C")] = (st["worst"], st["inexact"])
 
 
-def _run_gemm(name, a, b, bias, c0, beta, use_ws):
+def test_gemm_force_v1():
+    """FORCE_GEMM_V1 = 1 on a shape whose 176 tiles of 128 x 128 take gemm3s by default: sow_gemm_ex runs the generic kernel alone."""
+    name, M, N, K = "gemm_force_v1", 2048, 1376, 512
+    g = torch.Generator().manual_seed(M + N + K + 1)
+    a = torch.randn(M, K, generator=g).bfloat16()
+    b = (torch.randn(K, N, generator=g) * 0.05).bfloat16()
+    bias = (torch.randn(N, generator=g) * 0.1).bfloat16()
+    trace = []
+    with _lib.switch(FORCE_GEMM_V1=1):
+        out = _run_gemm(name, a, b, bias, None, 0.0, False, trace=trace)
+    assert _has_kernel(trace, "gemm_kernel") and not any(_has_kernel(trace, k) for k in _FAST_GEMMS), sorted(set(trace))
+    a64, b64 = to64(a), to64(b)
+    st = check_rounded(out, a64 @ b64 + to64(bias), BF16, acc=fp32_floor((a64 * a64) @ (b64 * b64), K), name=name)
+    WORST[(name, "C")] = (st["worst"], st["inexact"])
+
+
+def _run_gemm(name, a, b, bias, c0, beta, use_ws, trace=None):
     """bf16 sow_gemm_ex C = a b + beta C0 + bias on the given operands (a [M, K], b [K, N], bias [N] or None, C0 [M, N] or
-    None): three bit-identical runs with intact guards; C of the first on the CPU."""
+    None): three bit-identical runs with intact guards; C of the first on the CPU.  `trace`: a list that receives the kernel
+    names of the third run."""
     lib = _lib.load()
     (M, K), N = a.shape, b.shape[1]
     ar = Arena(BF16)
@@ -534,8 +597,12 @@ def _run_gemm(name, a, b, bias, c0, beta, use_ws):
     runs = []
     for byte in (0xFF, 0x00, 0xFF):
         ar.fill(byte)
-        _lib.check(lib.sow_gemm_ex(_ptr(A), K, 0, _ptr(B), N, 0, _ptr(C), N, _ptr(Bi), M, N, K, 1.0, beta, _lib.BF16, _ptr(ws),
-                                   nws, _stream()), "sow_gemm_ex")
+        call = lambda: _lib.check(lib.sow_gemm_ex(_ptr(A), K, 0, _ptr(B), N, 0, _ptr(C), N, _ptr(Bi), M, N, K, 1.0, beta,
+                                                  _lib.BF16, _ptr(ws), nws, _stream()), "sow_gemm_ex")
+        if trace is not None and len(runs) == 2:
+            trace += _kernel_seq(call)
+        else:
+            call()
         ar.check_guards(f"{name} run {len(runs)}")
         runs.append(C.clone())
     assert torch.equal(_bits(runs[0]), _bits(runs[1])) and torch.equal(_bits(runs[0]), _bits(runs[2]))

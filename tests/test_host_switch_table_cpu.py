@@ -1,6 +1,7 @@
 """CPU tests of the kernel-selection switch table: kSwitchNames (api.hip) and enum Switch (common.hpp) stay parallel, the cache
-and store switches of the chain and weight-gradient kernels (NO_H_ROWS, NT_LOAD, TN_NO_NT_LOAD, NO_NT_STORE) exist, are unset
-unless the environment sets them and can be set and restored, and the C ABI carries no policy parameter (header and _lib.py
+and store switches of the chain and weight-gradient kernels (NO_H_ROWS, NT_LOAD, TN_NO_NT_LOAD, NO_NT_STORE) and the launch-shape
+and dispatch switches the GPU tests set (NO_PERSIST, NO_PAIR_FLUSH, NO_PARK16, NO_SHORT_SPLIT, FORCE_GEMM_V1, NO_GEMM3S) exist, are
+unset unless the environment sets them and can be set and restored, each on its own, and the C ABI carries no policy parameter (header and _lib.py
 stay one to one)."""
 import ctypes
 import os
@@ -9,7 +10,10 @@ import re
 from sow_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SWITCHES = ("NO_H_ROWS", "NT_LOAD", "TN_NO_NT_LOAD", "NO_NT_STORE")
+# the cache / store policies, then the launch-shape and dispatch switches the GPU tests set (test_gpu_stream_policy.py,
+# test_gpu_elementwise.py)
+SWITCHES = ("NO_H_ROWS", "NT_LOAD", "TN_NO_NT_LOAD", "NO_NT_STORE", "NO_PERSIST", "NO_PAIR_FLUSH", "NO_PARK16", "NO_SHORT_SPLIT",
+            "FORCE_GEMM_V1", "NO_GEMM3S")
 
 
 def test_switches_exist_and_default_to_unset():
@@ -30,6 +34,12 @@ def test_switches_set_and_restore():
             assert lib.sow_get_switch(b"NO_H_ROWS") == 0 and lib.sow_get_switch(b"NT_LOAD") == 1
         assert lib.sow_get_switch(b"NO_H_ROWS") == 1
     assert {n: lib.sow_get_switch(n.encode()) for n in SWITCHES} == before
+    for n in SWITCHES:                       # every name round-trips on its own: set, read back, cleared, restored
+        for v in (1, 0):
+            with _lib.switch(**{n: v}):
+                assert lib.sow_get_switch(n.encode()) == v, n
+                assert all(lib.sow_get_switch(o.encode()) == before[o] for o in SWITCHES if o != n), n
+        assert lib.sow_get_switch(n.encode()) == before[n], n
 
 
 def test_switch_names_match_the_enum():
