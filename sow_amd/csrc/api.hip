@@ -55,7 +55,7 @@ static const char* const kSwitchNames[SW_COUNT] = {"FORCE_CHAIN_V1", "NO_SHORT_S
                                                    "NO_PARK16",      "TN_NO_NT_LOAD",  "NO_TN_ROWS",     "GEMM4",          "NO_GEMM4H",      "NO_CHAIN3F",     "NO_TN_F32Q",     "NO_SPLITK",
                                                    "NO_WIDE_CHAIN",  "NO_SHARED_X",    "NO_RAGGED",      "NO_RAGGED_GEMM", "NO_BLOCKED_QR",
                                                    "NO_SKINNY",      "NO_FUSED_ACC",   "NO_F16_TN",
-                                                   "NO_H_ROWS"};
+                                                   "NO_ROW_ALIGN",   "NO_H_ROWS"};
 static std::atomic<int> g_switch[SW_COUNT];
 static std::once_flag g_switch_once;
 static void switches_from_env() {
@@ -65,7 +65,9 @@ static void switches_from_env() {
     const char* v = getenv(name);
     // tri-state switches take "0" / "1"; for the boolean ones any value (even empty) means on, as before
     const bool tri = i == SW_GEMM3S || i == SW_GEMM3 || i == SW_GEMM4;
-    g_switch[i].store(!v ? -1 : (tri ? (v[0] != '0') : 1), std::memory_order_relaxed);
+    // NO_ROW_ALIGN keeps its value (1 = both sides off, 2 / 3 = one side)
+    const int on = i == SW_NO_ROW_ALIGN && v && v[0] >= '1' && v[0] <= '3' ? v[0] - '0' : 1;
+    g_switch[i].store(!v ? -1 : (tri ? (v[0] != '0') : on), std::memory_order_relaxed);
   }
 }
 int sw(int which) {
@@ -173,7 +175,7 @@ int sow_set_switch(const char* name, int value) {
   (void)sw(0);   // make sure the environment has been read first
   for (int i = 0; i < SW_COUNT; ++i)
     if (!strcmp(name, kSwitchNames[i])) {
-      g_switch[i].store(value < 0 ? -1 : (value != 0), std::memory_order_relaxed);
+      g_switch[i].store(value < 0 ? -1 : (i == SW_NO_ROW_ALIGN && value <= 3 ? value : (value != 0)), std::memory_order_relaxed);
       return SOW_OK;
     }
   return SOW_ERR_UNSUPPORTED;

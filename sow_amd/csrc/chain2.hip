@@ -117,7 +117,23 @@ template <bool TR> __device__ __forceinline__ int img_chunk(int row, int c) {
 // 5.1 TB/s), so three 512-workgroup layers in one 1536-workgroup grid pay it once; later rounds start while earlier
 // workgroups drain.  Every workgroup runs exactly the single-layer code on its own layer's parameter block, so the
 // results are bit-identical to separate launches.
-template <typename T, bool BWD, bool P16>
+//
+// Row alignment (AL; NO_ROW_ALIGN switch).  A 16-bit row whose pitch is 64 bytes past a multiple of 128 (1376 columns: 21.5
+// lines) starts on a line boundary only on every other token: cut at multiples of 64 columns from the row start, every
+// 128-byte X piece of an odd row straddles two lines and every 256-byte Y piece touches three.  With p.row_align set the two
+// token groups of a workgroup are the EVEN and the ODD rows of its 64-token block (local row r of group tg = token 2 r + tg),
+// and the odd group cuts its pieces 32 columns earlier:
+//   bit 0 (X is the wide operand): stage st of the odd group holds k in [64 st - 32, 64 st + 32); its k-steps 0, 1 take F1
+//         rows 32..63 of chunk st - 1, k-steps 2, 3 rows 0..31 of chunk st -- the same k sequence per token, so h is
+//         bit-identical.  The k < 0 half of stage 0 is not multiplied at all (no chunk exists there).
+//   bit 1 (Y is the wide operand, bf16 park tiles only): slice sl of the odd group is columns [64 sl - 32, 64 sl + 32): its
+//         wave hh = 0 computes column tile 1 of chunk sl - 1, hh = 1 tile 0 of chunk sl; the park tile and the flush are
+//         unchanged but for the column origin.  Step 0 of wave hh = 0 parks columns that are never stored.
+// Widths are 32 columns past a multiple of 64 (or less: D % 64 in 8..32), so the odd group needs no extra step.  Both sides
+// need chunk c - 1 alive through step c: the loaders run one chunk less ahead (6 slots, 4 ahead).  AL is a template
+// parameter so that every other launch runs exactly the code it ran before; inside an AL launch a layer that does not
+// qualify differs only in address arithmetic (no LDS read sits under a runtime condition).
+template <typename T, bool BWD, bool P16, bool AL>
 __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid, char* smem, const int t, const int lane, const int w,
                                              uint64_t* stamps) {
   constexpr bool TR = !BWD;
@@ -139,6 +155,7 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
   const int64_t ldb = BWD ? p.ldf1b : p.ldf2b;
   const int rows_a = BWD ? D2 : D1, cols_b = BWD ? D1 : D2;
   const char* zp = zero_page_for(lane);
+  const int ral = AL ? p.row_align : 0;   // bit 0: X pieces, bit 1: Y pieces cut on line boundaries (never with a short-T split)
 
   if (w >= C2_NCW) {
     // ------------------------------------------------------------------ loader waves
@@ -200,11 +217,12 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
         }
       }
     };
-    const int pre = total < C2_AHEAD ? total : C2_AHEAD;
+    const int ahead = ral ? C2_AHEAD - 1 : C2_AHEAD;   // row alignment: chunk c - 1 stays in its slot through step c
+    const int pre = total < ahead ? total : ahead;
     for (int c = 0; c < pre; ++c) issue(c);
     uint64_t tw_dma = 0, tw_bar = 0;
     for (int c = 0; c < total; ++c) {
-      const int newer = (total - 1 - c) < (C2_AHEAD - 1) ? (total - 1 - c) : (C2_AHEAD - 1);
+      const int newer = (total - 1 - c) < (ahead - 1) ? (total - 1 - c) : (ahead - 1);
       const uint64_t tk0 = C2_TICK();
       wait_groups<C2_LPW>(newer);
       C2_ACC(tw_dma, tk0);
@@ -222,7 +240,7 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
       const uint64_t tk1 = C2_TICK();
       raw_barrier();   // chunk c visible to the consumers; they have finished chunk c-1
       C2_ACC(tw_bar, tk1);
-      if (c + C2_AHEAD < total) issue(c + C2_AHEAD);   // its slot held chunk c-1: every consumer finished it before barrier c
+      if (c + ahead < total) issue(c + ahead);   // its slot held chunk c-1 (row alignment: c-2): every consumer finished it before barrier c
     }
     C2_PUT(w == C2_NCW, 8, tw_dma);
     C2_PUT(w == C2_NCW, 9, tw_bar);
@@ -260,7 +278,11 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
   const uint32_t ring_a = lds_addr(ring);
   const uint32_t slot_a = lds_addr(smem);
   const T* X = (const T*)p.X;
-  const int64_t tok0 = m0 + 32 * tg;
+  // local row r of this token group -> token (row alignment: the groups are the even and the odd rows of the block)
+  const bool par = ral != 0;
+  const bool ord = par && tg == 1 && (ral & 1), owr = P16 && par && tg == 1 && (ral & 2);   // the odd group's shifted X stages / Y slices
+  auto trow = [&](int r) -> int64_t { return m0 + (par ? 2 * r + tg : 32 * tg + r); };
+  const int xsh = ord ? 32 : 0, ysh = owr ? 32 : 0;   // columns the odd group's pieces start early
 
   // X DMA: this wave issues instructions i = 2*hh, 2*hh+1 (token rows 16*hh .. 16*hh+15) of every stage
   const int drow = lane >> 3, dpc = lane & 7;
@@ -270,9 +292,9 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
   for (int ii = 0; ii < 2; ++ii) {
     const int row = 8 * (2 * hh + ii) + drow;
     const int lc = dpc ^ ((row >> 1) & 7);
-    const int64_t tk = tok0 + row;
+    const int64_t tk = trow(row);
     const bool v = tk < p.M;
-    xsrc[ii] = v ? (const char*)(X + tk * p.ldx + lc * 8) : zp;
+    xsrc[ii] = v ? (const char*)(X + tk * p.ldx + lc * 8 - xsh) : zp;
     xstride[ii] = v ? 128 : 0;
     xlc[ii] = lc;
   }
@@ -282,7 +304,12 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
 #pragma unroll
     for (int ii = 0; ii < 2; ++ii) {
       const char* qq = xsrc[ii] + (st0 + st) * xstride[ii];
-      if (x_ragged && (st0 + st) * 64 + xlc[ii] * 8 >= D1) qq = zp;
+      if constexpr (AL) {
+        const int col = (st0 + st) * 64 + xlc[ii] * 8 - xsh;   // (shifted stages: the k < 0 half of stage 0 reads zeros too)
+        if ((x_ragged || xsh) && (col < 0 || col >= D1)) qq = zp;
+      } else {
+        if (x_ragged && (st0 + st) * 64 + xlc[ii] * 8 >= D1) qq = zp;
+      }
       if (p.nt_load) dma16_nt((const void*)qq, dst + (2 * hh + ii) * 1024);
       else dma16((const void*)qq, dst + (2 * hh + ii) * 1024);
     }
@@ -301,12 +328,13 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
   } else {
     foff1[0] = (uint32_t)((hh * 32 + li) * 128);
   }
+  const int ct = owr ? hh ^ 1 : hh;   // phase-2 column tile inside its chunk
   if constexpr (TR) {
-    const int col = hh * 32 + 16 * (g & 1) + 4 * pp;
+    const int col = ct * 32 + 16 * (g & 1) + 4 * pp;
     const int r2 = 4 * h2 + q;
     foff2 = (uint32_t)(r2 * 128 + img_chunk<true>(r2, col >> 3) * 16 + (col & 7) * 2);
   } else {
-    foff2 = (uint32_t)((hh * 32 + li) * 128 + 8 * lh);
+    foff2 = (uint32_t)((ct * 32 + li) * 128 + 8 * lh);
   }
 
   f32x16 hacc;   // H^T tile hh (ranks 32 hh .. 32 hh + 31) over the whole K range: lane = token, registers = rank rows
@@ -333,6 +361,8 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
     if (st + C2_DEPTH - 1 < nst) issue_x(st + C2_DEPTH - 1);   // into the slot of stage st-1
     const uint32_t xs = ring_a + (uint32_t)((st % C2_DEPTH) * C2_STAGE) + xoff;
     const uint32_t fs = slot_a + (uint32_t)((st % C2_NSLOT) * C2_FSLOT);
+    // shifted stage: k-steps 0, 1 from the upper half of chunk st - 1 (stage 0: any resident slot, not multiplied)
+    const uint32_t fsp = AL && ord && st > 0 ? slot_a + (uint32_t)(((st - 1) % C2_NSLOT) * C2_FSLOT) : fs;
     // the two waves of a token group split the RANKS (tile hh each), not K: every wave contracts the whole stage, so its
     // accumulator is final and the hand-off is an exchange of 2 KiB of bf16 instead of a sum of 8 KiB of fp32 partials
     u32x4 xf[4], ff[4];
@@ -340,6 +370,18 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
     for (int ks = 0; ks < 4; ++ks) DS_READ_B128(xf[ks], xs + (uint32_t)(((2 * ks + lh) ^ xsw) * 16), 0);
     if constexpr (TR) {
       u32x2 bl[4], bh[4];
+      if constexpr (AL) {
+        const uint32_t b0 = fsp + foff1[0] + (ord ? 4096u : 0u);   // k-steps 0, 1
+        const uint32_t b1 = fs + foff1[0] + (ord ? 0u : 4096u);    // k-steps 2, 3
+        DS_READ_TR(bl[0], b0, 0);
+        DS_READ_TR(bh[0], b0, 512);
+        DS_READ_TR(bl[1], b0, 2048);
+        DS_READ_TR(bh[1], b0, 2048 + 512);
+        DS_READ_TR(bl[2], b1, 0);
+        DS_READ_TR(bh[2], b1, 512);
+        DS_READ_TR(bl[3], b1, 2048);
+        DS_READ_TR(bh[3], b1, 2048 + 512);
+      } else {
       const uint32_t b0 = fs + foff1[0];
       DS_READ_TR(bl[0], b0, 0);
       DS_READ_TR(bh[0], b0, 512);
@@ -349,16 +391,34 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
       DS_READ_TR(bh[2], b0, 4096 + 512);
       DS_READ_TR(bl[3], b0, 6144);
       DS_READ_TR(bh[3], b0, 6144 + 512);
+      }
       LGKM_WAIT0();
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) ff[ks] = join2(bl[ks], bh[ks]);
     } else {
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) DS_READ_B128(ff[ks], fs + foff1[0] + (uint32_t)(((2 * ks + lh) ^ xsw) * 16), 0);
+      for (int ks = 0; ks < 4; ++ks) {
+        if constexpr (AL) {   // shifted stage: k-chunks 4..7 of chunk st - 1, then 0..3 of chunk st
+          const int kk = (ks + (ord ? 2 : 0)) & 3;
+          DS_READ_B128(ff[ks], (ks < 2 ? fsp : fs) + foff1[0] + (uint32_t)(((2 * kk + lh) ^ xsw) * 16), 0);
+        } else {
+          DS_READ_B128(ff[ks], fs + foff1[0] + (uint32_t)(((2 * ks + lh) ^ xsw) * 16), 0);
+        }
+      }
       LGKM_WAIT0();
     }
+    if constexpr (AL) {
+      // the k < 0 half of a shifted stage 0 has no factor rows: predicated off (zeros x whatever the slot holds may be NaN)
+      if (!(ord && st == 0)) {
+        hacc = mfma32(as_v8<T>(ff[0]), as_v8<T>(xf[0]), hacc);
+        hacc = mfma32(as_v8<T>(ff[1]), as_v8<T>(xf[1]), hacc);
+      }
+      hacc = mfma32(as_v8<T>(ff[2]), as_v8<T>(xf[2]), hacc);
+      hacc = mfma32(as_v8<T>(ff[3]), as_v8<T>(xf[3]), hacc);
+    } else {
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) hacc = mfma32(as_v8<T>(ff[ks]), as_v8<T>(xf[ks]), hacc);
+    }
     __builtin_amdgcn_sched_barrier(0);
   }
 
@@ -368,7 +428,7 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
   // follows the last stage (free: the partner can only still be reading the slot of stage nst - 1), and after ONE barrier
   // reads the partner's two k-steps.
   u32x4 hf[4];
-  const int64_t tok = tok0 + li;
+  const int64_t tok = trow(li);
   if (p.Hload) {
     // phase-2-only workgroup: H comes from memory.  hf[s] of lane (li, lh) = ranks 16s + 4lh + (0..3) and
     // 16s + 8 + 4lh + (0..3) of token li; the 1.0 of column 63 (dbias trick) must not reach the product.
@@ -453,7 +513,7 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
       LGKM_WAIT0();
 #pragma unroll
       for (int pass = 0; pass < 2; ++pass) {
-        const int64_t tk = tok0 + 16 * hh + pass * 8 + (lane >> 3);
+        const int64_t tk = trow(16 * hh + pass * 8 + (lane >> 3));
         if (tk < p.M) {
           T* dst = (T*)p.Hsave + tk * 64 + (lane & 7) * 8;
           store_b128_nt(dst, hr[pass]);
@@ -490,7 +550,7 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass) {
       const int r = 16 * hh + pass * 8 + (lane >> 3), c8 = lane & 7;
-      const int64_t tk = tok0 + r;
+      const int64_t tk = trow(r);
       const int col = (sl0 + sl_prev) * 64 + c8 * 8;
       if (tk < p.M && col < D2) {
         float v[8];
@@ -539,7 +599,7 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
 #pragma unroll
       for (int ps = 0; ps < 2; ++ps) {
         const int r = 16 * hh + (2 * half + ps) * 4 + (lane >> 4), c16 = lane & 15;
-        const int64_t tk = tok0 + r;
+        const int64_t tk = trow(r);
         const int col = (sl0 + sl_a) * 64 + c16 * 8;
         if (tk < p.M && col < D2) {
           float v[8];
@@ -575,8 +635,8 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
     return ring_a + (uint32_t)((C2_DEPTH - 3) * C2_STAGE + buf * 4096 + row * 128 + ((chunk ^ ((row >> 1) & 7)) * 16));
   };
   auto store16 = [&](int r, int col, u32x4 ov) {
-    const int64_t tk = tok0 + r;
-    if (tk < p.M && col < D2) {
+    const int64_t tk = trow(r);
+    if (tk < p.M && col < D2 && (!AL || col >= 0)) {   // (shifted slices: the first starts 32 columns before the row)
       T* dst = Y + tk * p.ldy + col;
       if (p.nt_store) store_b128_nt(dst, ov);
       else *(u32x4*)dst = ov;
@@ -588,7 +648,7 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
     for (int pass = 0; pass < 2; ++pass) DS_READ_B128(v[pass], tile16_addr(sl_prev % 3, 16 * hh + pass * 8 + (lane >> 3), lane & 7), 0);
     LGKM_WAIT0();
 #pragma unroll
-    for (int pass = 0; pass < 2; ++pass) store16(16 * hh + pass * 8 + (lane >> 3), (sl0 + sl_prev) * 64 + (lane & 7) * 8, v[pass]);
+    for (int pass = 0; pass < 2; ++pass) store16(16 * hh + pass * 8 + (lane >> 3), (sl0 + sl_prev) * 64 + (lane & 7) * 8 - ysh, v[pass]);
   };
   auto flush_pair16 = [&](int sl_a) {   // two slices: 256 bytes per row
     u32x4 v[4];
@@ -599,14 +659,16 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
     }
     LGKM_WAIT0();
 #pragma unroll
-    for (int ps = 0; ps < 4; ++ps) store16(16 * hh + ps * 4 + (lane >> 4), (sl0 + sl_a) * 64 + (lane & 15) * 8, v[ps]);
+    for (int ps = 0; ps < 4; ++ps) store16(16 * hh + ps * 4 + (lane >> 4), (sl0 + sl_a) * 64 + (lane & 15) * 8 - ysh, v[ps]);
   };
 #pragma unroll 1
   for (int sl = 0; sl < nsl; ++sl) {
     const uint64_t tk2 = C2_TICK();
     raw_barrier();   // factor chunk nst + sl is in its slot; the partner has parked slice sl-1
     C2_ACC(tw_b2, tk2);
-    const uint32_t fs = slot_a + (uint32_t)(((nst + sl) % C2_NSLOT) * C2_FSLOT) + foff2;
+    // shifted slice: wave hh = 0 takes its tile from chunk sl - 1 (step 0: from chunk 0, parked in columns that are never stored)
+    const int fc = nst + sl - ((AL && owr && hh == 0 && sl > 0) ? 1 : 0);
+    const uint32_t fs = slot_a + (uint32_t)((fc % C2_NSLOT) * C2_FSLOT) + foff2;
     u32x2 bl[4], bh[4];
     if constexpr (TR) {
       DS_READ_TR(bl[0], fs, 0);
@@ -683,7 +745,7 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
 // round.  A resident workgroup issues the next block's first loads right after its last stores: the store drain and
 // the load latency overlap, and nothing is relaunched.  Every block runs exactly the single-layer code on its own
 // layer's parameter block, so the results are bit-identical to separate launches.
-template <bool BWD, bool P16> __global__ __launch_bounds__(C2_THREADS, 4) void chain2_kernel(const ChainGroup grp) {   // 4 waves per SIMD: caps the allocation at 128 VGPRs, above which a CU cannot place two of these workgroups
+template <bool BWD, bool P16, bool AL> __global__ __launch_bounds__(C2_THREADS, 4) void chain2_kernel(const ChainGroup grp) {   // 4 waves per SIMD: caps the allocation at 128 VGPRs, above which a CU cannot place two of these workgroups
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int t = threadIdx.x;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -697,11 +759,11 @@ template <bool BWD, bool P16> __global__ __launch_bounds__(C2_THREADS, 4) void c
     // loop by LICM it stays live across the whole block (168 VGPRs instead of ~100; above 128 a CU holds one workgroup)
     int tt = t;
     asm volatile("" : "+v"(tt));
-    chain2_block<bf16_t, BWD, P16>(grp.p[layer], blk - grp.start[layer], smem, tt, tt & 63, w, grp.stamps ? grp.stamps + (int64_t)blk * 16 : nullptr);
+    chain2_block<bf16_t, BWD, P16, AL>(grp.p[layer], blk - grp.start[layer], smem, tt, tt & 63, w, grp.stamps ? grp.stamps + (int64_t)blk * 16 : nullptr);
   }
 }
 // the f16 form of the same loop
-template <bool BWD, bool P16> __global__ __launch_bounds__(C2_THREADS, 4) void chain2_f16_kernel(const ChainGroup grp) {
+template <bool BWD, bool P16, bool AL> __global__ __launch_bounds__(C2_THREADS, 4) void chain2_f16_kernel(const ChainGroup grp) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int t = threadIdx.x;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -715,7 +777,7 @@ template <bool BWD, bool P16> __global__ __launch_bounds__(C2_THREADS, 4) void c
     // loop by LICM it stays live across the whole block (168 VGPRs instead of ~100; above 128 a CU holds one workgroup)
     int tt = t;
     asm volatile("" : "+v"(tt));
-    chain2_block<f16_t, BWD, P16>(grp.p[layer], blk - grp.start[layer], smem, tt, tt & 63, w, grp.stamps ? grp.stamps + (int64_t)blk * 16 : nullptr);
+    chain2_block<f16_t, BWD, P16, AL>(grp.p[layer], blk - grp.start[layer], smem, tt, tt & 63, w, grp.stamps ? grp.stamps + (int64_t)blk * 16 : nullptr);
   }
 }
 
@@ -817,15 +879,37 @@ int launch_chain2_group(const ChainParams* ps, int n, bool bwd, int dtype, hipSt
   const int64_t grid = (sw_on(SW_NO_PERSIST) || total < C2_RESIDENT) ? total : C2_RESIDENT;
   bool p16 = !sw_on(SW_NO_PARK16);   // bf16 park tiles: exact only when the epilogue adds nothing to the rounded product
   for (int i = 0; i < n; ++i) p16 = p16 && g.p[i].pair_flush && g.p[i].beta == 0.f && !g.p[i].bias;
-#define C2_LAUNCH(B, P)                                                                                              \
+  // row alignment (chain2_block): per layer and per side, where the pitch puts every other row half a line off, the width
+  // needs no extra step of the shifted group (D % 64 in 8..32) and the base sits on a line.  The shifted slices exist in the
+  // bf16 park form only (the fp32 park tiles of a beta / bias launch keep the unshifted columns); a short-T split cuts
+  // stages and slices at chunk boundaries and stays as it was.  NO_ROW_ALIGN = 1: neither side, 2: no read side, 3: no write side.
+  const int no_al = sw(SW_NO_ROW_ALIGN);
+  bool al = false;
+  for (int i = 0; i < n; ++i) {
+    ChainParams& q = g.p[i];
+    auto half_off = [](const void* base, int64_t ld, int D) {
+      return ld % 64 == 32 && D % 64 > 0 && D % 64 <= 32 && (reinterpret_cast<uintptr_t>(base) & 127) == 0;
+    };
+    q.row_align = 0;
+    if (q.ntb > 0) continue;
+    if (no_al != 1 && no_al != 2 && half_off(q.X, q.ldx, q.D1)) q.row_align |= 1;
+    if (no_al != 1 && no_al != 3 && p16 && half_off(q.Y, q.ldy, q.D2)) q.row_align |= 2;
+    al = al || q.row_align != 0;
+  }
+#define C2_LAUNCH_AL(B, P, A)                                                                                        \
   do {                                                                                                               \
     if (dtype == SOW_F16) {                                                                                          \
-      SOW_SET_MAX_LDS_ONCE(C2_LDS, (chain2_f16_kernel<B, P>));                                                       \
-      hipLaunchKernelGGL((chain2_f16_kernel<B, P>), dim3((unsigned)grid), dim3(C2_THREADS), C2_LDS, stream, g);      \
+      SOW_SET_MAX_LDS_ONCE(C2_LDS, (chain2_f16_kernel<B, P, A>));                                                    \
+      hipLaunchKernelGGL((chain2_f16_kernel<B, P, A>), dim3((unsigned)grid), dim3(C2_THREADS), C2_LDS, stream, g);   \
     } else {                                                                                                         \
-      SOW_SET_MAX_LDS_ONCE(C2_LDS, (chain2_kernel<B, P>));                                                           \
-      hipLaunchKernelGGL((chain2_kernel<B, P>), dim3((unsigned)grid), dim3(C2_THREADS), C2_LDS, stream, g);          \
+      SOW_SET_MAX_LDS_ONCE(C2_LDS, (chain2_kernel<B, P, A>));                                                        \
+      hipLaunchKernelGGL((chain2_kernel<B, P, A>), dim3((unsigned)grid), dim3(C2_THREADS), C2_LDS, stream, g);       \
     }                                                                                                                \
+  } while (0)
+#define C2_LAUNCH(B, P)                \
+  do {                                 \
+    if (al) C2_LAUNCH_AL(B, P, true);  \
+    else C2_LAUNCH_AL(B, P, false);    \
   } while (0)
   if (bwd) {
     if (p16) C2_LAUNCH(true, true);
@@ -835,6 +919,7 @@ int launch_chain2_group(const ChainParams* ps, int n, bool bwd, int dtype, hipSt
     else C2_LAUNCH(false, false);
   }
 #undef C2_LAUNCH
+#undef C2_LAUNCH_AL
   SOW_CHECK_LAUNCH();
   return SOW_OK;
 }
