@@ -83,18 +83,24 @@ static inline size_t esize(int dtype) { return dtype == SOW_F32 ? 4 : 2; }
 static inline bool ok_dtype(int d) { return d == SOW_F32 || d == SOW_BF16 || d == SOW_F16; }
 static inline bool al4p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 static inline bool al16p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-// SOW_PARAM_F32: the compute dtype of a flagged dtype (*pf = flag present); -1 for a combination no layer entry point takes
-// SOW_FUSE_ACC is stripped here: the entry points where the permission acts read it with fuse_of() first
-static inline int split_dtype(int d, bool* pf) {
-  d &= ~SOW_FUSE_ACC;
-  *pf = (d & SOW_PARAM_F32) != 0;
-  const int cd = d & ~SOW_PARAM_F32;
-  if (!ok_dtype(cd) || (*pf && cd == SOW_F32)) return -1;
-  return cd;
+// The dtype argument of an entry point, decoded once.  SOW_FUSE_ACC is a permission and is ignored together with SOW_PARAM_F32.
+// The layer entry points, their plans and descriptors take what layer_ok() admits; sow_*_shared refuses a flagged dtype as
+// unsupported after its own checks.  The entry points outside the layer surface (GEMM, QR, accumulate, optimizer, copies)
+// only strip the permission with nofuse() and refuse or reject SOW_PARAM_F32 themselves, each with its own code.
+struct Dtype {
+  int cd;           // compute dtype: the argument without its flag bits (not validated)
+  bool param_f32;   // SOW_PARAM_F32
+  bool fuse;        // SOW_FUSE_ACC, without SOW_PARAM_F32
+  bool layer_ok() const { return ok_dtype(cd) && !(param_f32 && cd == SOW_F32); }
+};
+static inline Dtype decode_dtype(int d) {
+  Dtype f;
+  f.cd = d & ~(SOW_FUSE_ACC | SOW_PARAM_F32);
+  f.param_f32 = (d & SOW_PARAM_F32) != 0;
+  f.fuse = (d & SOW_FUSE_ACC) != 0 && !f.param_f32;
+  return f;
 }
 static inline bool flagged(int d) { return (d & SOW_PARAM_F32) != 0; }
-// SOW_FUSE_ACC: the permission is ignored together with SOW_PARAM_F32
-static inline bool fuse_of(int d) { return (d & SOW_FUSE_ACC) != 0 && !flagged(d); }
 static inline int nofuse(int d) { return d & ~SOW_FUSE_ACC; }
 
 // ---- short inputs ---------------------------------------------------------------------------------
@@ -323,6 +329,54 @@ static void set_planes(ChainParams& p, char* ws, const WsPlan& w, size_t workspa
   if (ws && w.planes_bytes && workspace_bytes >= w.total) p.planes = ws + w.off_planes, p.planes_bytes = w.planes_bytes;
 }
 
+// ---- one layer ------------------------------------------------------------------------------------------------------
+// Every layer entry point works on a sow_layer_args: the single-layer entry points build one from their arguments, the
+// grouped and shared ones pass their elements through.
+static sow_layer_args single_layer(const void* x, const void* A, const void* B, const void* acc_down, const void* acc_up,
+                                   const void* bias, void* y, void* h_save, const void* dy, void* dx, void* dA, void* dB,
+                                   void* dbias, int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, float scale,
+                                   float grad_beta, void* workspace, size_t workspace_bytes) {
+  sow_layer_args L{};
+  L.x = x, L.A = A, L.B = B, L.acc_down = acc_down, L.acc_up = acc_up, L.bias = bias, L.y = y, L.h_save = h_save;
+  L.dy = dy, L.dx = dx, L.dA = dA, L.dB = dB, L.dbias = dbias;
+  L.T = T, L.d_in = d_in, L.d_out = d_out, L.r_live = r_live, L.r_acc = r_acc, L.acc_kind = acc_kind;
+  L.scale = scale, L.grad_beta = grad_beta, L.workspace = workspace, L.workspace_bytes = workspace_bytes;
+  return L;
+}
+// r_acc counts only for a low-rank accumulator
+static inline int acc_rank(const sow_layer_args& L) { return L.acc_kind == SOW_ACC_LOWRANK ? L.r_acc : 0; }
+// the accumulator fields a layer's kind does not use, cleared (before the parameters are packed: pack_layer)
+static void normalise_acc(sow_layer_args& L) {
+  if (L.acc_kind != SOW_ACC_LOWRANK) L.r_acc = 0, L.acc_up = nullptr;
+  if (L.acc_kind == SOW_ACC_NONE) L.acc_down = nullptr;
+}
+static inline WsPlan plan_of(const sow_layer_args& L, int cd, bool fuse = false) {
+  return plan_ws(L.T, L.d_in, L.d_out, L.r_live, acc_rank(L), L.acc_kind, cd, fuse);
+}
+// The argument checks of a layer, in the one order every entry point reports them: shape, then (T > 0 only) NULL operands,
+// then a missing accumulator (NULL), then, with `lowrank`, the second factor and rank of a low-rank accumulator (SHAPE).
+// T = 0 is valid whatever the pointers are.  What differs between the entry points is what they test BEFORE this and where
+// they call it; none of that may move across a launch:
+//   forward_impl, and sow_forward under SOW_PARAM_F32 (before the pack launch): dtype first.
+//   backward_impl: phases (SHAPE), then dtype, then this; at T = 0 it wants dA and dB (NULL).
+//   sow_backward_ex under SOW_PARAM_F32: dtype first, then -- DATA phase with T > 0 only, before the pack launch -- this, then
+//     backward_impl's sequence again.
+//   groups: dtype (backward: phases first when unflagged), n, layers; then this WITHOUT `lowrank`, for every layer up front
+//     (backward, plans, shared) or layer by layer between the launches (forward).  A low-rank accumulator without acc_up is
+//     refused by the per-layer fall-through (forward_impl / backward_impl), after the layers before it have been enqueued.
+//   pack_group (groups under SOW_PARAM_F32): this WITH `lowrank`, for every layer before the one pack launch.
+//   sow_forward_skinny has checks of its own, stricter and all before any launch.
+static int check_layer(const sow_layer_args& L, bool bwd, bool lowrank) {
+  if (L.T < 0 || L.d_in <= 0 || L.d_out <= 0 || L.r_live <= 0) return SOW_ERR_SHAPE;
+  if (L.T == 0) return SOW_OK;
+  if (!L.x || !L.A || !L.B) return SOW_ERR_NULL;
+  if (!bwd && !L.y) return SOW_ERR_NULL;
+  if (bwd && (!L.dy || !L.h_save || !L.dx || !L.dA || !L.dB || !L.workspace)) return SOW_ERR_NULL;
+  if (L.acc_kind != SOW_ACC_NONE && !L.acc_down) return SOW_ERR_NULL;
+  if (lowrank && L.acc_kind == SOW_ACC_LOWRANK && (!L.acc_up || L.r_acc <= 0)) return SOW_ERR_SHAPE;
+  return SOW_OK;
+}
+
 // ---- fp32 parameters (SOW_PARAM_F32) ----------------------------------------------------------------------
 // The fp32 A, B, bias and accumulator of a call are rounded once to the compute dtype into a region of the layer's workspace
 // past the compute-dtype plan (pack_params_kernel, misc.hip); the bf16 / f16 kernels then read the packed copies, in the
@@ -334,14 +388,14 @@ static size_t pack_bytes(int d_in, int d_out, int r_live, int r_acc, int acc_kin
   if (acc_kind == SOW_ACC_LOWRANK) b += pack_elems_bytes((int64_t)d_in * r_acc) + pack_elems_bytes((int64_t)r_acc * d_out);
   return b;
 }
-// Appends the pack items of layer L (T > 0, pointers checked) to `items` and points L's parameter operands at the packed
-// copies.  The packed copies go past the compute-dtype plan (where they never touch what a backward phase leaves in the
-// workspace), except for a forward (fwd) whose kernels need no scratch (sow_forward_workspace_bytes = 0 for the compute
+// Appends the pack items of layer L (T > 0, checked and normalised) to `items` and points L's parameter operands at the
+// packed copies.  The packed copies go past the compute-dtype plan (where they never touch what a backward phase leaves in
+// the workspace), except for a forward (fwd) whose kernels need no scratch (sow_forward_workspace_bytes = 0 for the compute
 // dtype) given a workspace sized by the flagged forward query only: there they start the workspace.  Such a forward then runs
 // without workspace, exactly as the unflagged call.
 static int pack_layer(sow_layer_args& L, int cd, bool fwd, std::vector<PackItem>& items) {
-  const int r_acc = L.acc_kind == SOW_ACC_LOWRANK ? L.r_acc : 0;
-  const WsPlan w = plan_ws(L.T, L.d_in, L.d_out, L.r_live, r_acc, L.acc_kind, cd);
+  const int r_acc = acc_rank(L);
+  const WsPlan w = plan_of(L, cd);
   const size_t pack = pack_bytes(L.d_in, L.d_out, L.r_live, r_acc, L.acc_kind);
   const bool no_scratch = fwd && sow_forward_workspace_bytes(L.T, L.d_in, L.d_out, L.r_live, r_acc, L.acc_kind, cd) == 0;
   const size_t off = (no_scratch && L.workspace_bytes < w.total + pack + 255) ? 0 : w.total;
@@ -365,35 +419,244 @@ static int pack_layer(sow_layer_args& L, int cd, bool fwd, std::vector<PackItem>
   }
   return SOW_OK;
 }
-static sow_layer_args single_layer(const void* A, const void* B, const void* acc_down, const void* acc_up, const void* bias,
-                                   int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, void* workspace,
-                                   size_t workspace_bytes) {
-  sow_layer_args L{};
-  L.A = A, L.B = B, L.acc_down = acc_down, L.acc_up = acc_up, L.bias = bias;
-  L.T = T, L.d_in = d_in, L.d_out = d_out, L.r_live = r_live, L.r_acc = r_acc, L.acc_kind = acc_kind;
-  L.workspace = workspace, L.workspace_bytes = workspace_bytes;
-  return L;
+// one layer of a single-layer call: checked as the unflagged call checks it, packed by a launch of its own
+static int pack_single(sow_layer_args& L, int cd, bool fwd, hipStream_t stream) {
+  int rc = check_layer(L, !fwd, true);
+  if (rc) return rc;
+  normalise_acc(L);
+  std::vector<PackItem> items;
+  if ((rc = pack_layer(L, cd, fwd, items))) return rc;
+  return launch_pack_params(items.data(), (int)items.size(), cd, stream);
 }
+
+// ---- one direction of a layer ---------------------------------------------------------------------------------------
+// What the chain kernels compute is  H = X . F1,  Y = beta Y + H . F2  for a pair of factors `down` [d_in][r] (row pitch r)
+// and `up` [r][d_out] (row pitch d_out): the live pair (A, B) or a low-rank accumulator (acc_down, acc_up).
+//   forward:        X = x,  Y = y,  D1 = d_in,  D2 = d_out, F1 = down, F2 = up,   H = h_save, bias
+//   data gradient:  X = dY, Y = dX, D1 = d_out, D2 = d_in,  F1 = up,   F2 = down, H = dh (workspace), no bias
+// A dense accumulator W [d_in][d_out] is read as it lies by the forward and transposed by the data gradient.
+// This is the only place that knows the mapping; the launches below are written once for both directions.
+struct Factors {
+  const void *F1, *F2;
+  int64_t ld1, ld2;
+  int r;
+};
+struct DirView {
+  bool bwd;
+  const void* X;
+  void* Y;
+  void* H;
+  const void* bias;
+  int64_t M;
+  int D1, D2;
+  Factors live, acc;
+  const void* W;
+  int64_t ldw;
+  float scale;   // of the live term
+};
+static Factors factor_pair(const void* down, const void* up, int r, int d_out, bool bwd) {
+  return bwd ? Factors{up, down, d_out, r, r} : Factors{down, up, r, d_out, r};
+}
+static DirView dir_view(const sow_layer_args& L, bool bwd, void* dh) {
+  DirView v{};
+  v.bwd = bwd, v.M = L.T, v.scale = L.scale;
+  v.X = bwd ? L.dy : L.x, v.Y = bwd ? L.dx : L.y, v.H = bwd ? dh : L.h_save, v.bias = bwd ? nullptr : L.bias;
+  v.D1 = bwd ? L.d_out : L.d_in, v.D2 = bwd ? L.d_in : L.d_out;
+  v.live = factor_pair(L.A, L.B, L.r_live, L.d_out, bwd);
+  v.acc = factor_pair(L.acc_down, L.acc_up, acc_rank(L), L.d_out, bwd);
+  v.W = L.acc_down, v.ldw = L.d_out;
+  return v;
+}
+// one term on the r <= 64 chain kernels; h_only: the projection alone (Hsave), nothing written to Y
+static ChainParams chain_params(const DirView& v, const Factors& f, void* Hsave, const void* bias, float scale, float beta,
+                                bool h_only = false) {
+  ChainParams p{};
+  p.X = v.X, p.Y = h_only ? nullptr : v.Y, p.Hsave = Hsave, p.bias = bias;
+  p.M = v.M, p.ldx = v.D1, p.ldy = v.D2, p.D1 = v.D1, p.D2 = h_only ? 0 : v.D2;
+  p.F1b = f.F1, p.ldf1b = f.ld1, p.F2b = f.F2, p.ldf2b = f.ld2, p.rb = f.r;
+  p.scale = scale, p.beta = beta;
+  return p;
+}
+static ChainParams live_chain(const DirView& v, float beta, bool h_only = false) {
+  return chain_params(v, v.live, v.H, h_only ? nullptr : v.bias, v.scale, beta, h_only);
+}
+// what the launches of one layer share: compute dtype, the layer's scratch (ws = NULL: none) under plan w, the stream
+struct LayerRun {
+  int dtype;
+  char* ws;
+  const WsPlan& w;
+  size_t bytes;
+  hipStream_t stream;
+};
 
 // One term of a wide-rank layer on the fused chain (chain_wide.hip), the factors packed into the workspace's wide region;
-// SOW_ERR_UNSUPPORTED: nothing launched, the caller composes generic GEMMs.  Forward (bwd = false): F1 = A-like [D1][r],
-// F2 = B-like [r][D2]; data gradient: F1 = B-like [r][D1], F2 = A-like [D2][r].
+// SOW_ERR_UNSUPPORTED: nothing launched, the caller composes generic GEMMs (gemm_pair).  The scale goes where the saved
+// projection wants it: the forward keeps H unscaled (the wide contract of h_save) and scales Y, the data gradient scales dh.
 // rag: a term of an admitted ragged layer (rag_layer; the NO_WIDE_CHAIN switch does not apply); any other caller gets
 // SOW_ERR_UNSUPPORTED for ragged widths, so that they keep the generic kernels.
-static int wide_chain(const void* X, void* Y, const void* F1, int64_t ldf1, const void* F2, int64_t ldf2, void* Hsave,
-                      const void* bias, int64_t T, int D1, int D2, int r, float hscale, float yscale, float beta, bool bwd,
-                      int dtype, char* ws, const WsPlan& w, size_t workspace_bytes, hipStream_t stream, bool rag = false) {
-  const bool ragged = D1 % 8 != 0 || D2 % 8 != 0;
-  if ((ragged ? !rag : sw_on(SW_NO_WIDE_CHAIN)) || !ws || !w.wide_bytes || workspace_bytes < w.total + 255 ||
-      chain_wide_pack_bytes(r, D1, D2) > w.wide_bytes)
+static int wide_chain(const DirView& v, const Factors& f, void* Hsave, const void* bias, float scale, float beta,
+                      const LayerRun& c, bool rag = false) {
+  const bool ragged = v.D1 % 8 != 0 || v.D2 % 8 != 0;
+  if ((ragged ? !rag : sw_on(SW_NO_WIDE_CHAIN)) || !c.ws || !c.w.wide_bytes || c.bytes < c.w.total + 255 ||
+      chain_wide_pack_bytes(f.r, v.D1, v.D2) > c.w.wide_bytes)
     return SOW_ERR_UNSUPPORTED;
   WideArgs a{};
-  a.X = X, a.Y = Y, a.F1 = F1, a.F2 = F2, a.ldf1 = ldf1, a.ldf2 = ldf2, a.Hsave = Hsave, a.bias = bias;
-  a.M = T, a.D1 = D1, a.D2 = D2, a.r = r, a.hscale = hscale, a.yscale = yscale, a.beta = beta, a.bwd = bwd ? 1 : 0;
-  a.pack = ws + w.off_wide, a.pack_bytes = w.wide_bytes;
-  return launch_chain_wide(a, dtype, stream);
+  a.X = v.X, a.Y = v.Y, a.F1 = f.F1, a.F2 = f.F2, a.ldf1 = f.ld1, a.ldf2 = f.ld2, a.Hsave = Hsave, a.bias = bias;
+  a.M = v.M, a.D1 = v.D1, a.D2 = v.D2, a.r = f.r, a.hscale = v.bwd ? scale : 1.f, a.yscale = v.bwd ? 1.f : scale, a.beta = beta;
+  a.bwd = v.bwd ? 1 : 0, a.pack = c.ws + c.w.off_wide, a.pack_bytes = c.w.wide_bytes;
+  return launch_chain_wide(a, c.dtype, c.stream);
+}
+// the same term as two generic GEMMs:  h = X . F1 ;  Y = beta * Y + h . F2 + bias  (scaled as in wide_chain)
+static int gemm_pair(const DirView& v, const Factors& f, void* h, const void* bias, float scale, float beta, const LayerRun& c) {
+  int rc = launch_gemm(v.X, v.D1, false, f.F1, f.ld1, v.bwd, h, f.r, nullptr, v.M, f.r, v.D1, v.bwd ? scale : 1.f, 0.f, c.dtype,
+                       c.stream);
+  if (rc) return rc;
+  return launch_gemm(h, f.r, false, f.F2, f.ld2, v.bwd, v.Y, v.D2, bias, v.M, v.D2, f.r, v.bwd ? 1.f : scale, beta, c.dtype,
+                     c.stream);
+}
+// SOW_FUSE_ACC on an admitted call: the accumulator term and the live term of one direction as one chain
+// (chain_wide_acc.hip), Y written once, H left as the two-pass path leaves it (the weight phases are the unflagged ones).
+// SOW_ERR_UNSUPPORTED: nothing launched, the caller goes on with the unflagged path, unchanged.  The data gradient has no
+// bias, and its H = dh lies in the workspace: the alignment tests on them are the forward's.
+static int fused_acc_pass(const sow_layer_args& L, const DirView& v, const LayerRun& c) {
+  if (sw_on(SW_NO_FUSED_ACC) || !c.ws || !al16p(v.X) || !al16p(v.Y) || !al16p(v.bias) || !al16p(v.H)) return SOW_ERR_UNSUPPORTED;
+  const WsPlan wf = plan_of(L, c.dtype, true);
+  if (!wf.fused || c.bytes < wf.total + 255) return SOW_ERR_UNSUPPORTED;
+  WideAccArgs a{};
+  a.X = v.X, a.Y = v.Y, a.Fa1 = v.acc.F1, a.Fl1 = v.live.F1, a.Fa2 = v.acc.F2, a.Fl2 = v.live.F2;
+  a.ldfa1 = v.acc.ld1, a.ldfl1 = v.live.ld1, a.ldfa2 = v.acc.ld2, a.ldfl2 = v.live.ld2;
+  a.Hsave = v.H, a.bias = v.bias, a.M = v.M, a.D1 = v.D1, a.D2 = v.D2, a.r_acc = v.acc.r, a.r_live = v.live.r;
+  a.scale = v.scale, a.bwd = v.bwd ? 1 : 0, a.pack = c.ws + wf.off_wide, a.pack_bytes = wf.wide_bytes;
+  return launch_chain_wide_acc(a, c.dtype, c.stream);
 }
 
+// Dense accumulator, r_live <= 64: the product with the live term as a K-extension,  Y = [X, H] . [op(W); F2] + bias,
+// H = scale * X . F1.  The operands of one layer and direction, as the one-launch kernels (gemm4h, gemm2h) take them:
+static Gemm2hArgs dense_args(const DirView& v) {
+  return Gemm2hArgs{v.X, v.W, v.live.F1, v.live.F2, v.Y, v.bias, v.H, v.M, v.D1, v.ldw, v.live.ld1, v.live.ld2, v.D2,
+                    v.D2, v.D1, v.live.r, v.scale};
+}
+static bool gemm4h_ok(const Gemm2hArgs& g, bool nt, int dtype) {
+  return gemm4h_supported(g.X, g.ldx, g.W, g.ldw, nt, g.F, g.ldf, g.G, g.ldg, g.C, g.ldc, g.bias, g.H, g.M, g.N, g.K, g.r, dtype);
+}
+static int run_gemm4h(const Gemm2hArgs& g, bool nt, int dtype, hipStream_t stream) {
+  return launch_gemm4h(g.X, g.ldx, g.W, g.ldw, nt, g.F, g.ldf, g.G, g.ldg, g.C, g.ldc, g.bias, g.H, g.M, g.N, g.K, g.r, g.hscale,
+                       dtype, stream);
+}
+static bool gemm2h_ok(const Gemm2hArgs& g, bool nt, int dtype) {
+  return gemm2h_supported(g.X, g.ldx, g.W, g.ldw, nt, g.F, g.ldf, g.G, g.ldg, g.C, g.ldc, g.bias, g.H, g.M, g.N, g.K, g.r, dtype);
+}
+static int run_gemm2h(const Gemm2hArgs& g, bool nt, hipStream_t stream) {
+  return launch_gemm2h(g.X, g.ldx, g.W, g.ldw, nt, g.F, g.ldf, g.G, g.ldg, g.C, g.ldc, g.bias, g.H, g.M, g.N, g.K, g.r, g.hscale,
+                       stream);
+}
+// the two-launch composition of the same product: H (64 columns) from a chain launch, then gemm2 with the extension operand
+// E [ke rows of N] -- the forward reads B in place (ke = r_live), the data gradient A zero-padded to 64 columns (ke = 64)
+static bool gemm2_ext_ok(const Gemm2hArgs& g, bool nt, const void* E, int64_t lde, int dtype) {
+  return gemm2_supported(g.X, g.ldx, g.W, g.ldw, nt, g.H, 64, E, lde, g.C, g.ldc, g.bias, g.M, g.N, g.K, dtype);
+}
+static int run_gemm2_ext(const Gemm2hArgs& g, bool nt, const void* E, int64_t lde, int ke, hipStream_t stream, void* sk,
+                         size_t sk_bytes) {
+  return launch_gemm2(g.X, g.ldx, g.W, g.ldw, nt, g.H, 64, E, lde, ke, g.C, g.ldc, g.bias, g.M, g.N, g.K, 1.f, 0.f, stream, sk,
+                      sk_bytes);
+}
+// Y = X . op(W) alone (the live term follows with beta = 1); rag: an admitted ragged layer
+static int dense_product(const DirView& v, bool rag, int dtype, hipStream_t stream) {
+  if (rag) return rag_dense_product(v.X, v.D1, v.W, v.ldw, v.bwd, v.Y, v.D2, v.M, v.D2, v.D1, dtype, stream);
+  return gemm_auto(v.X, v.D1, v.W, v.ldw, v.bwd, v.Y, v.D2, nullptr, v.M, v.D2, v.D1, 1.f, 0.f, dtype, stream);
+}
+// The dense accumulator and the live term (r_live <= 64) as one product, one direction: gemm4h (projection pass + anti-phase
+// main loop in one launch, the factors read in place), else gemm2h (one launch, H projected inside the GEMM, where the output
+// spans at most two column tiles), else H from a chain launch and gemm2 with the extension.  *taken = false (and SOW_OK):
+// none applies, nothing launched, the caller writes the dense product and the live term separately.
+static int dense_ext_term(const sow_layer_args& L, const DirView& v, const LayerRun& c, bool* taken) {
+  const Gemm2hArgs g = dense_args(v);
+  *taken = true;
+  if (gemm4h_ok(g, v.bwd, c.dtype)) return run_gemm4h(g, v.bwd, c.dtype, c.stream);
+  if (gemm2h_ok(g, v.bwd, c.dtype)) return run_gemm2h(g, v.bwd, c.stream);
+  ChainParams ph = live_chain(v, 0.f, true);
+  set_planes(ph, c.ws, c.w, c.bytes);
+  // the extension operand: the forward reads B in place, the data gradient A zero-padded to 64 columns (workspace)
+  void* apad = v.bwd ? c.ws + c.w.off_apad : nullptr;
+  const void* E = v.bwd ? apad : L.B;
+  const int64_t lde = v.bwd ? 64 : L.d_out;
+  if (!chain2_supported(ph, c.dtype) || !gemm2_ext_ok(g, v.bwd, E, lde, c.dtype)) {
+    *taken = false;
+    return SOW_OK;
+  }
+  // the padded A rides along in the dh launch when that grid is large enough
+  const bool pad_fused = v.bwd && (int64_t)ceil_div(L.T, 64) * 64 >= L.d_in;
+  if (pad_fused) ph.pad_src = L.A, ph.pad_dst = apad, ph.pad_rows = L.d_in, ph.pad_r = L.r_live;
+  // short T: the H-only pass split over K (T / 64 workgroups cannot fill the chip: 29 us on 16 workgroups at 1024 x 4096);
+  // launch_chain_short itself refuses longer inputs
+  const bool scratch = c.ws && c.bytes >= c.w.total;
+  int rc = SOW_ERR_UNSUPPORTED;
+  if (scratch) rc = launch_chain_short(ph, c.dtype, v.bwd, (float*)(c.ws + c.w.off_hp), c.stream);
+  if (rc == SOW_ERR_UNSUPPORTED) rc = launch_chain2(ph, v.bwd, c.dtype, c.stream);
+  if (rc) return rc;
+  if (v.bwd && !pad_fused && (rc = launch_pad64(L.A, apad, L.d_in, L.r_live, c.stream))) return rc;
+  const bool sk = scratch && c.w.sk_bytes;
+  return run_gemm2_ext(g, v.bwd, E, lde, v.bwd ? 64 : L.r_live, c.stream, sk ? c.ws + c.w.off_sk : nullptr, sk ? c.w.sk_bytes : 0);
+}
+
+// An admitted ragged layer (rag_layer), one direction: the fused chain for the low-rank accumulator (scale 1) and for the
+// live term, X read once per term; H holds the projection under the wide contract (forward: unscaled); a dense
+// accumulator's product is written by gemm_rag first.
+static int ragged_terms(const DirView& v, int acc_kind, const LayerRun& c) {
+  int rc = SOW_OK;
+  if (acc_kind == SOW_ACC_LOWRANK) rc = wide_chain(v, v.acc, nullptr, nullptr, 1.f, 0.f, c, true);
+  if (acc_kind == SOW_ACC_DENSE) rc = dense_product(v, true, c.dtype, c.stream);
+  if (rc) return rc;
+  return wide_chain(v, v.live, v.H, v.bias, v.scale, acc_kind == SOW_ACC_NONE ? 0.f : 1.f, c, true);
+}
+// The low-rank accumulator term  Y = (X . F1) . F2  with the frozen factors, scale 1 (the live term follows with beta = 1):
+// the r <= 64 chain kernel, or for a wide one the fused chain, else two generic GEMMs through the workspace.
+static int lowrank_acc_term(const DirView& v, const LayerRun& c) {
+  if (v.acc.r <= 64) {
+    ChainParams p = chain_params(v, v.acc, nullptr, nullptr, 1.f, 0.f);
+    set_planes(p, c.ws, c.w, c.bytes);
+    return launch_chain(p, c.dtype, v.bwd, c.stream);
+  }
+  if (!c.ws || c.bytes < c.w.total) return SOW_ERR_WORKSPACE;   // the forward's check; a backward never gets here without
+  const int rc = wide_chain(v, v.acc, nullptr, nullptr, 1.f, 0.f, c);
+  return rc == SOW_ERR_UNSUPPORTED ? gemm_pair(v, v.acc, c.ws + c.w.off_t, nullptr, 1.f, 0.f, c) : rc;
+}
+// The live term of a wide-rank layer: the fused chain (H kept on chip, copied to v.H when given), else the generic
+// composition with H in v.H or, for a forward without h_save, in the workspace.
+static int wide_live_term(const DirView& v, float beta, const LayerRun& c) {
+  const int rc = wide_chain(v, v.live, v.H, v.bias, v.scale, beta, c);
+  if (rc != SOW_ERR_UNSUPPORTED) return rc;
+  if (!v.H && !(c.ws && c.bytes >= c.w.total + 255)) return SOW_ERR_WORKSPACE;
+  return gemm_pair(v, v.live, v.H ? v.H : c.ws + c.w.off_dh, v.bias, v.scale, beta, c);
+}
+
+// ---- weight gradients -----------------------------------------------------------------------------------------------
+struct Phases {
+  bool data, partial, reduce;
+  bool weights() const { return partial || reduce; }
+};
+static inline Phases decode_phases(int phases) {
+  return Phases{(phases & SOW_BWD_DATA) != 0, (phases & (SOW_BWD_WEIGHTS | SOW_BWD_WEIGHTS_PARTIAL)) != 0,
+                (phases & (SOW_BWD_WEIGHTS | SOW_BWD_WEIGHTS_REDUCE)) != 0};
+}
+// The two slab-partial jobs of a layer with r_live <= 64: dA = x^T dh ; dB^T = dY^T h ; dbias = colsum(dY) via the all-ones
+// column 63 (the chain kernels write 1.0 into column 63 of h_save / dh whenever r_live <= 63).
+// vec: fp32 reads 16-byte vectors, the 16-bit dtypes 4-byte pairs.  The grouped launch takes 16-bit dtypes only
+// (tn_group_supported refuses fp32), so the one rule serves it as it serves the single layer.
+static TnParams tn_params(const sow_layer_args& L, const WsPlan& w, char* ws, int dtype) {
+  TnParams tp{};
+  tp.njobs = 2, tp.T = L.T, tp.ns = w.ns, tp.slab_len = w.slab_len;
+  auto vec_ok = [&](const void* ptr, int D) {
+    if (dtype == SOW_F32) return (D % 4 == 0 && al16p(ptr)) ? 1 : 0;
+    return (D % 2 == 0 && al4p(ptr)) ? 1 : 0;
+  };
+  const bool ones_ok = L.dbias && L.r_live <= 63;
+  tp.job[0] = TnJob{L.x, ws + w.off_dh, (float*)(ws + w.off_p0), (int64_t)L.d_in, L.d_in, -1, (L.d_in + 63) / 64,
+                    vec_ok(L.x, L.d_in), 1};
+  tp.job[1] = TnJob{L.dy, L.h_save, (float*)(ws + w.off_p1), (int64_t)L.d_out, L.d_out, ones_ok ? 63 : -1, (L.d_out + 63) / 64,
+                    vec_ok(L.dy, L.d_out), 1};
+  return tp;
+}
 // the reduction of the slab partials of one layer (shared by sow_backward_ex and the deferred, batched form)
 static ReduceParams make_reduce_params(const WsPlan& w, char* ws, void* dA, void* dB, void* dbias_ones, int d_in, int d_out,
                                        int r_live, float grad_beta) {
@@ -412,9 +675,8 @@ size_t sow_reduce_desc_bytes(void) { return sizeof(ReduceParams); }
 int sow_backward_reduce_desc(void* dA, void* dB, void* dbias, int64_t T, int d_in, int d_out, int r_live, int r_acc,
                              int acc_kind, float grad_beta, int dtype, void* workspace, size_t workspace_bytes, void* desc_out,
                              int* blocks_out) {
-  bool pf;
-  dtype = split_dtype(dtype, &pf);   // the descriptor is the same with fp32 gradients: sow_reduce_batch picks the output type
-  if (dtype < 0) return SOW_ERR_DTYPE;
+  const Dtype f = decode_dtype(dtype);   // the descriptor is the same with fp32 gradients: sow_reduce_batch picks the output type
+  if (!f.layer_ok()) return SOW_ERR_DTYPE;
   if (T <= 0 || d_in <= 0 || d_out <= 0 || r_live <= 0) return SOW_ERR_SHAPE;
   if (!dA || !dB || !workspace || !desc_out || !blocks_out) return SOW_ERR_NULL;
   if (r_live > 64) {
@@ -425,7 +687,7 @@ int sow_backward_reduce_desc(void* dA, void* dB, void* dbias, int64_t T, int d_i
   }
   if (dbias && r_live > 63) return SOW_ERR_UNSUPPORTED;   // no separate reduction: use SOW_BWD_WEIGHTS
   if (acc_kind != SOW_ACC_LOWRANK) r_acc = 0;
-  const WsPlan w = plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, dtype);
+  const WsPlan w = plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, f.cd);
   if (workspace_bytes < w.total + 255) return SOW_ERR_WORKSPACE;
   const ReduceParams rp = make_reduce_params(w, ws_base(workspace), dA, dB, dbias, d_in, d_out, r_live, grad_beta);
   memcpy(desc_out, &rp, sizeof(rp));
@@ -434,155 +696,73 @@ int sow_backward_reduce_desc(void* dA, void* dB, void* dbias, int64_t T, int d_i
 }
 
 int sow_reduce_batch(const void* descs, const int* starts, int n, int total_blocks, int dtype, void* stream) {
-  bool pf;
-  const int cd = split_dtype(dtype, &pf);
-  if (cd < 0) return SOW_ERR_DTYPE;
-  if (pf) dtype = SOW_F32;   // the slab partials are fp32 whatever the compute dtype: fp32 gradients are their sums, rounded once
+  const Dtype f = decode_dtype(dtype);
+  if (!f.layer_ok()) return SOW_ERR_DTYPE;
+  // the slab partials are fp32 whatever the compute dtype: fp32 gradients are their sums, rounded once.  An unflagged dtype
+  // goes through as it came: SOW_FUSE_ACC is not stripped here, the launcher refuses it (SOW_ERR_DTYPE)
+  const int gdt = f.param_f32 ? SOW_F32 : dtype;
   if (n < 0 || total_blocks < 0) return SOW_ERR_SHAPE;
   if (n == 0) return SOW_OK;
   if (!descs || !starts) return SOW_ERR_NULL;
-  return launch_tn_reduce_batch((const ReduceParams*)descs, starts, n, total_blocks, dtype, (hipStream_t)stream);
+  return launch_tn_reduce_batch((const ReduceParams*)descs, starts, n, total_blocks, gdt, (hipStream_t)stream);
 }
 
 size_t sow_forward_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, int dtype) {
-  bool pf;
-  const bool fuse = fuse_of(dtype);
-  dtype = split_dtype(dtype, &pf);
-  if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0 || dtype < 0) return 0;
-  if (pf) {   // the forward's own scratch (if any) followed by the packed parameters (pack_layer)
-    const size_t own = sow_forward_workspace_bytes(T, d_in, d_out, r_live, r_acc, acc_kind, dtype);
+  const Dtype f = decode_dtype(dtype);
+  if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0 || !f.layer_ok()) return 0;
+  if (f.param_f32) {   // the forward's own scratch (if any) followed by the packed parameters (pack_layer)
+    const size_t own = sow_forward_workspace_bytes(T, d_in, d_out, r_live, r_acc, acc_kind, f.cd);
     const size_t pack = pack_bytes(d_in, d_out, r_live, acc_kind == SOW_ACC_LOWRANK ? r_acc : 0, acc_kind);
     return own ? own + pack : pack + 256;
   }
   const bool wide_acc = acc_kind == SOW_ACC_LOWRANK && r_acc > 64;
-  const WsPlan w = plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, dtype, fuse);
-  if (!w.fused && !wide_acc && r_live <= 64 && short_hp_bytes(T, d_in, d_out, r_live, dtype) == 0 && w.planes_bytes == 0 && w.sk_bytes == 0)
+  const WsPlan w = plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, f.cd, f.fuse);
+  if (!w.fused && !wide_acc && r_live <= 64 && short_hp_bytes(T, d_in, d_out, r_live, f.cd) == 0 && w.planes_bytes == 0 && w.sk_bytes == 0)
     return 0;   // the forward does not touch it
   return w.total + 256;
 }
 
 size_t sow_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, int dtype) {
-  bool pf;
-  const bool fuse = fuse_of(dtype);
-  dtype = split_dtype(dtype, &pf);
-  if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0 || dtype < 0) return 0;
-  const size_t pack = pf ? pack_bytes(d_in, d_out, r_live, acc_kind == SOW_ACC_LOWRANK ? r_acc : 0, acc_kind) : 0;
-  return plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, dtype, fuse).total + pack + 256;
+  const Dtype f = decode_dtype(dtype);
+  if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0 || !f.layer_ok()) return 0;
+  const size_t pack = f.param_f32 ? pack_bytes(d_in, d_out, r_live, acc_kind == SOW_ACC_LOWRANK ? r_acc : 0, acc_kind) : 0;
+  return plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, f.cd, f.fuse).total + pack + 256;
 }
 
-
-static int forward_impl(const void* x, const void* A, const void* B, const void* acc_down, const void* acc_up, const void* bias,
-                        void* y, void* h_save, int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, float scale,
-                        int dtype, void* workspace, size_t workspace_bytes, void* stream_, bool fuse = false) {
-  hipStream_t stream = (hipStream_t)stream_;
+// ---- single layer -----------------------------------------------------------------------------------------------------
+static int forward_impl(const sow_layer_args& L, int dtype, bool fuse, hipStream_t stream) {
   if (!ok_dtype(dtype)) return SOW_ERR_DTYPE;
-  if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0) return SOW_ERR_SHAPE;
-  if (T == 0) return SOW_OK;
-  if (!x || !A || !B || !y) return SOW_ERR_NULL;
-  if (acc_kind != SOW_ACC_NONE && !acc_down) return SOW_ERR_NULL;
-  if (acc_kind == SOW_ACC_LOWRANK && (!acc_up || r_acc <= 0)) return SOW_ERR_SHAPE;
-  if (acc_kind != SOW_ACC_LOWRANK) r_acc = 0;
-  const WsPlan w = plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, dtype);
-  char* ws = workspace ? ws_base(workspace) : nullptr;
+  int rc = check_layer(L, false, true);
+  if (rc || L.T == 0) return rc;
+  const int r_live = L.r_live, r_acc = acc_rank(L), acc_kind = L.acc_kind;
+  const size_t workspace_bytes = L.workspace_bytes;
+  const WsPlan w = plan_of(L, dtype);
+  char* ws = L.workspace ? ws_base(L.workspace) : nullptr;
+  const DirView v = dir_view(L, false, nullptr);
+  const LayerRun c{dtype, ws, w, workspace_bytes, stream};
   float beta = 0.f;
-  int rc;
-  // SOW_FUSE_ACC on an admitted call: the accumulator term and the live term as one chain (chain_wide_acc.hip), y written
-  // once.  Anything else falls through to the unflagged path, unchanged.
-  if (fuse && !sw_on(SW_NO_FUSED_ACC) && ws && al16p(x) && al16p(y) && al16p(bias) && al16p(h_save)) {
-    const WsPlan wf = plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, dtype, true);
-    if (wf.fused && workspace_bytes >= wf.total + 255) {
-      WideAccArgs a{};
-      a.X = x, a.Y = y, a.Fa1 = acc_down, a.Fl1 = A, a.Fa2 = acc_up, a.Fl2 = B;
-      a.ldfa1 = r_acc, a.ldfl1 = r_live, a.ldfa2 = d_out, a.ldfl2 = d_out;
-      a.Hsave = h_save, a.bias = bias, a.M = T, a.D1 = d_in, a.D2 = d_out, a.r_acc = r_acc, a.r_live = r_live;
-      a.scale = scale, a.bwd = 0, a.pack = ws + wf.off_wide, a.pack_bytes = wf.wide_bytes;
-      rc = launch_chain_wide_acc(a, dtype, stream);
-      if (rc != SOW_ERR_UNSUPPORTED) return rc;
-    }
-  }
-  // ragged widths: the fused chain for the low-rank accumulator (scale 1) and the live term, X read once per term; h_save
-  // holds the unscaled projection (the wide contract); a dense accumulator's product x . W_acc is written by gemm_rag first.
-  // Without workspace or with views off 16 bytes, the generic kernels below.
-  if (rag_layer(r_live, r_acc, acc_kind, d_in, d_out, dtype) && !sw_on(SW_NO_RAGGED) && ws && workspace_bytes >= w.total + 255 &&
-      al16p(x) && al16p(y) && (!bias || al16p(bias)) && (!h_save || al4p(h_save))) {
-    if (acc_kind == SOW_ACC_LOWRANK) {
-      rc = wide_chain(x, y, acc_down, r_acc, acc_up, d_out, nullptr, nullptr, T, d_in, d_out, r_acc, 1.f, 1.f, 0.f, false, dtype,
-                      ws, w, workspace_bytes, stream, true);
-      if (rc) return rc;
-      beta = 1.f;
-    } else if (acc_kind == SOW_ACC_DENSE) {
-      rc = rag_dense_product(x, d_in, acc_down, d_out, false, y, d_out, T, d_out, d_in, dtype, stream);
-      if (rc) return rc;
-      beta = 1.f;
-    }
-    return wide_chain(x, y, A, r_live, B, d_out, h_save, bias, T, d_in, d_out, r_live, 1.f, scale, beta, false, dtype, ws, w,
-                      workspace_bytes, stream, true);
-  }
+  if (fuse && (rc = fused_acc_pass(L, v, c)) != SOW_ERR_UNSUPPORTED) return rc;
+  // ragged widths; without workspace or with views off 16 bytes, the generic kernels below
+  if (rag_layer(r_live, r_acc, acc_kind, L.d_in, L.d_out, dtype) && !sw_on(SW_NO_RAGGED) && ws &&
+      workspace_bytes >= w.total + 255 && al16p(L.x) && al16p(L.y) && (!L.bias || al16p(L.bias)) &&
+      (!L.h_save || al4p(L.h_save)))
+    return ragged_terms(v, acc_kind, c);
   if (acc_kind == SOW_ACC_DENSE) {
-    if (r_live <= 64 && h_save) {
+    if (r_live <= 64 && L.h_save) {
       // one product with the low-rank term as a K-extension:  y = [x, h] . [W_acc; B] + bias,  h = scale * x . A
-      // -- in one launch (h projected inside the GEMM) when d_out spans at most two column tiles
-      // gemm4h: projection pass + anti-phase main loop in one launch, A read in place
-      if (gemm4h_supported(x, d_in, acc_down, d_out, false, A, r_live, B, d_out, y, d_out, bias, h_save, T, d_out, d_in, r_live,
-                           dtype))
-        return launch_gemm4h(x, d_in, acc_down, d_out, false, A, r_live, B, d_out, y, d_out, bias, h_save, T, d_out, d_in,
-                             r_live, scale, dtype, stream);
-      if (gemm2h_supported(x, d_in, acc_down, d_out, false, A, r_live, B, d_out, y, d_out, bias, h_save, T, d_out, d_in,
-                           r_live, dtype))
-        return launch_gemm2h(x, d_in, acc_down, d_out, false, A, r_live, B, d_out, y, d_out, bias, h_save, T, d_out, d_in,
-                             r_live, scale, stream);
-      ChainParams ph{};
-      ph.X = x, ph.Y = nullptr, ph.Hsave = h_save, ph.bias = nullptr;
-      ph.M = T, ph.ldx = d_in, ph.ldy = d_out, ph.D1 = d_in, ph.D2 = 0;
-      ph.F1b = A, ph.ldf1b = r_live, ph.F2b = B, ph.ldf2b = d_out, ph.rb = r_live;
-      ph.scale = scale, ph.beta = 0.f;
-      set_planes(ph, ws, w, workspace_bytes);
-      if (chain2_supported(ph, dtype) &&
-          gemm2_supported(x, d_in, acc_down, d_out, false, h_save, 64, B, d_out, y, d_out, bias, T, d_out, d_in, dtype)) {
-        // short T: the H-only pass split over K (T / 64 workgroups cannot fill the chip: 29 us on 16 workgroups at 1024 x 4096)
-        rc = SOW_ERR_UNSUPPORTED;
-        if (ws && workspace_bytes >= w.total) rc = launch_chain_short(ph, dtype, false, (float*)(ws + w.off_hp), stream);
-        if (rc == SOW_ERR_UNSUPPORTED) rc = launch_chain2(ph, false, dtype, stream);
-        if (rc) return rc;
-        const bool sk = ws && w.sk_bytes && workspace_bytes >= w.total;
-        return launch_gemm2(x, d_in, acc_down, d_out, false, h_save, 64, B, d_out, r_live, y, d_out, bias, T, d_out, d_in,
-                            1.f, 0.f, stream, sk ? ws + w.off_sk : nullptr, sk ? w.sk_bytes : 0);
-      }
+      bool taken;
+      rc = dense_ext_term(L, v, c, &taken);
+      if (taken) return rc;
     }
-    rc = gemm_auto(x, d_in, acc_down, d_out, false, y, d_out, nullptr, T, d_out, d_in, 1.f, 0.f, dtype, stream);
+    rc = dense_product(v, false, dtype, stream);
     if (rc) return rc;
     beta = 1.f;
   } else if (acc_kind == SOW_ACC_LOWRANK) {
-    if (r_acc <= 64) {
-      ChainParams p{};
-      p.X = x, p.Y = y, p.Hsave = nullptr, p.bias = nullptr;
-      p.M = T, p.ldx = d_in, p.ldy = d_out, p.D1 = d_in, p.D2 = d_out;
-      p.F1b = acc_down, p.ldf1b = r_acc, p.F2b = acc_up, p.ldf2b = d_out, p.rb = r_acc;
-      p.scale = 1.f, p.beta = 0.f;
-      set_planes(p, ws, w, workspace_bytes);
-      rc = launch_chain(p, dtype, false, stream);
-      if (rc) return rc;
-      beta = 1.f;
-    } else {
-      if (!ws || workspace_bytes < w.total) return SOW_ERR_WORKSPACE;
-      rc = wide_chain(x, y, acc_down, r_acc, acc_up, d_out, nullptr, nullptr, T, d_in, d_out, r_acc, 1.f, 1.f, 0.f, false, dtype,
-                      ws, w, workspace_bytes, stream);
-      if (rc == SOW_ERR_UNSUPPORTED) {
-        void* t = ws + w.off_t;
-        rc = launch_gemm(x, d_in, false, acc_down, r_acc, false, t, r_acc, nullptr, T, r_acc, d_in, 1.f, 0.f, dtype, stream);
-        if (rc) return rc;
-        rc = launch_gemm(t, r_acc, false, acc_up, d_out, false, y, d_out, nullptr, T, d_out, r_acc, 1.f, 0.f, dtype, stream);
-      }
-      if (rc) return rc;
-      beta = 1.f;
-    }
+    if ((rc = lowrank_acc_term(v, c))) return rc;
+    beta = 1.f;
   }
   if (r_live <= 64) {
-    ChainParams p{};
-    p.X = x, p.Y = y, p.Hsave = h_save, p.bias = bias;
-    p.M = T, p.ldx = d_in, p.ldy = d_out, p.D1 = d_in, p.D2 = d_out;
-    p.F1b = A, p.ldf1b = r_live, p.F2b = B, p.ldf2b = d_out, p.rb = r_live;
-    p.scale = scale, p.beta = beta;
+    ChainParams p = live_chain(v, beta);
     set_planes(p, ws, w, workspace_bytes);
     if (ws && workspace_bytes >= w.total) {
       rc = launch_chain_short(p, dtype, false, (float*)(ws + w.off_hp), stream);
@@ -590,116 +770,64 @@ static int forward_impl(const void* x, const void* A, const void* B, const void*
     }
     return launch_chain(p, dtype, false, stream);
   }
-  // wide rank: the fused chain (h = x A kept on chip, copied to h_save when given), else the generic composition
-  //   h = x A ; y = beta*y + scale * h B + bias   with h in h_save or, without it, in the workspace
-  const bool ws_ok = ws && workspace_bytes >= w.total + 255;
-  rc = wide_chain(x, y, A, r_live, B, d_out, h_save, bias, T, d_in, d_out, r_live, 1.f, scale, beta, false, dtype, ws, w,
-                  workspace_bytes, stream);
-  if (rc != SOW_ERR_UNSUPPORTED) return rc;
-  void* h = h_save;
-  if (!h) {
-    if (!ws_ok) return SOW_ERR_WORKSPACE;
-    h = ws + w.off_dh;
-  }
-  rc = launch_gemm(x, d_in, false, A, r_live, false, h, r_live, nullptr, T, r_live, d_in, 1.f, 0.f, dtype, stream);
-  if (rc) return rc;
-  return launch_gemm(h, r_live, false, B, d_out, false, y, d_out, bias, T, d_out, r_live, scale, beta, dtype, stream);
+  // wide rank:  h = x A ; y = beta*y + scale * h B + bias
+  return wide_live_term(v, beta, c);
 }
 
 int sow_forward(const void* x, const void* A, const void* B, const void* acc_down, const void* acc_up, const void* bias,
                 void* y, void* h_save, int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, float scale,
                 int dtype, void* workspace, size_t workspace_bytes, void* stream) {
-  bool pf;
-  const int cd = split_dtype(dtype, &pf);
-  if (cd < 0) return SOW_ERR_DTYPE;
-  if (!pf)
-    return forward_impl(x, A, B, acc_down, acc_up, bias, y, h_save, T, d_in, d_out, r_live, r_acc, acc_kind, scale, cd,
-                        workspace, workspace_bytes, stream, fuse_of(dtype));
-  // fp32 parameters: the same checks as forward_impl before the pack launch reads them
-  if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0) return SOW_ERR_SHAPE;
-  if (T == 0) return SOW_OK;
-  if (!x || !A || !B || !y) return SOW_ERR_NULL;
-  if (acc_kind != SOW_ACC_NONE && !acc_down) return SOW_ERR_NULL;
-  if (acc_kind == SOW_ACC_LOWRANK && (!acc_up || r_acc <= 0)) return SOW_ERR_SHAPE;
-  if (acc_kind != SOW_ACC_LOWRANK) r_acc = 0, acc_up = nullptr;
-  if (acc_kind == SOW_ACC_NONE) acc_down = nullptr;
-  sow_layer_args L = single_layer(A, B, acc_down, acc_up, bias, T, d_in, d_out, r_live, r_acc, acc_kind, workspace, workspace_bytes);
-  std::vector<PackItem> items;
-  int rc = pack_layer(L, cd, true, items);
-  if (rc) return rc;
-  if ((rc = launch_pack_params(items.data(), (int)items.size(), cd, (hipStream_t)stream))) return rc;
-  return forward_impl(x, L.A, L.B, L.acc_down, L.acc_up, L.bias, y, h_save, T, d_in, d_out, r_live, r_acc, acc_kind, scale, cd,
-                      L.workspace, L.workspace_bytes, stream);
+  const Dtype f = decode_dtype(dtype);
+  if (!f.layer_ok()) return SOW_ERR_DTYPE;
+  sow_layer_args L = single_layer(x, A, B, acc_down, acc_up, bias, y, h_save, nullptr, nullptr, nullptr, nullptr, nullptr, T, d_in,
+                                  d_out, r_live, r_acc, acc_kind, scale, 0.f, workspace, workspace_bytes);
+  if (f.param_f32 && T > 0) {   // fp32 parameters: forward_impl's checks before the pack launch reads them
+    const int rc = pack_single(L, f.cd, true, (hipStream_t)stream);
+    if (rc) return rc;
+  }
+  return forward_impl(L, f.cd, f.fuse, (hipStream_t)stream);
 }
 
 // gdt: the dtype of dA / dB / dbias -- dtype, or SOW_F32 under SOW_PARAM_F32 (the fp32 slab sums rounded once to fp32)
-static int backward_impl(const void* dy, const void* x, const void* h_save, const void* A, const void* B, const void* acc_down,
-                         const void* acc_up, void* dx, void* dA, void* dB, void* dbias, int64_t T, int d_in, int d_out,
-                         int r_live, int r_acc, int acc_kind, float scale, float grad_beta, int dtype, int gdt, void* workspace,
-                         size_t workspace_bytes, int phases, void* stream_, bool fuse = false) {
-  hipStream_t stream = (hipStream_t)stream_;
-  bool do_data = (phases & SOW_BWD_DATA) != 0;
-  const bool do_partial = (phases & (SOW_BWD_WEIGHTS | SOW_BWD_WEIGHTS_PARTIAL)) != 0;
-  const bool do_reduce = (phases & (SOW_BWD_WEIGHTS | SOW_BWD_WEIGHTS_REDUCE)) != 0;
-  const bool do_weights = do_partial || do_reduce;
-  if (!do_data && !do_weights) return SOW_ERR_SHAPE;
+static int backward_impl(const sow_layer_args& L, int dtype, int gdt, int phases, bool fuse, hipStream_t stream) {
+  const Phases ph = decode_phases(phases);
+  bool do_data = ph.data;
+  if (!ph.data && !ph.weights()) return SOW_ERR_SHAPE;
   if (!ok_dtype(dtype)) return SOW_ERR_DTYPE;
-  if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0) return SOW_ERR_SHAPE;
+  int rc = check_layer(L, true, true);
+  if (rc) return rc;
+  const int64_t T = L.T;
+  const int d_in = L.d_in, d_out = L.d_out, r_live = L.r_live, r_acc = acc_rank(L), acc_kind = L.acc_kind;
   if (T == 0) {
     // empty batch: gradients are zero (or unchanged when accumulating); x / dy / dx may be NULL
-    if (!dA || !dB) return SOW_ERR_NULL;
-    if (grad_beta == 0.f) {
-      void* ptrs[3] = {dA, dB, dbias};
+    if (!L.dA || !L.dB) return SOW_ERR_NULL;
+    if (L.grad_beta == 0.f) {
+      void* ptrs[3] = {L.dA, L.dB, L.dbias};
       int64_t bytes[3] = {(int64_t)d_in * r_live * (int64_t)esize(gdt), (int64_t)r_live * d_out * (int64_t)esize(gdt),
-                          dbias ? (int64_t)d_out * (int64_t)esize(gdt) : 0};
+                          L.dbias ? (int64_t)d_out * (int64_t)esize(gdt) : 0};
       return launch_multi_zero(ptrs, bytes, 3, stream);
     }
     return SOW_OK;
   }
-  if (!dy || !x || !h_save || !A || !B || !dx || !dA || !dB || !workspace) return SOW_ERR_NULL;
-  if (acc_kind != SOW_ACC_NONE && !acc_down) return SOW_ERR_NULL;
-  if (acc_kind == SOW_ACC_LOWRANK && (!acc_up || r_acc <= 0)) return SOW_ERR_SHAPE;
-  if (acc_kind != SOW_ACC_LOWRANK) r_acc = 0;
-  const WsPlan w = plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, dtype);
+  const size_t workspace_bytes = L.workspace_bytes;
+  const WsPlan w = plan_of(L, dtype);
   if (workspace_bytes < w.total + 255) return SOW_ERR_WORKSPACE;
-  char* ws = ws_base(workspace);
+  char* ws = ws_base(L.workspace);
   void* dh = ws + w.off_dh;
+  const DirView v = dir_view(L, true, dh);
+  const LayerRun c{dtype, ws, w, workspace_bytes, stream};
   float beta = 0.f;
-  int rc;
   bool data_done = false;
-  // SOW_FUSE_ACC on an admitted call: dX of the accumulator and of the live term as one chain (chain_wide_acc.hip), dh left
-  // in the workspace as the two-pass path leaves it; the weight phases below are the unflagged ones
-  if (do_data && fuse && !sw_on(SW_NO_FUSED_ACC) && al16p(dy) && al16p(dx)) {
-    const WsPlan wf = plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, dtype, true);
-    if (wf.fused && workspace_bytes >= wf.total + 255) {
-      WideAccArgs a{};
-      a.X = dy, a.Y = dx, a.Fa1 = acc_up, a.Fl1 = B, a.Fa2 = acc_down, a.Fl2 = A;
-      a.ldfa1 = d_out, a.ldfl1 = d_out, a.ldfa2 = r_acc, a.ldfl2 = r_live;
-      a.Hsave = dh, a.bias = nullptr, a.M = T, a.D1 = d_out, a.D2 = d_in, a.r_acc = r_acc, a.r_live = r_live;
-      a.scale = scale, a.bwd = 1, a.pack = ws + wf.off_wide, a.pack_bytes = wf.wide_bytes;
-      rc = launch_chain_wide_acc(a, dtype, stream);
-      if (rc && rc != SOW_ERR_UNSUPPORTED) return rc;
-      if (!rc) do_data = false;
-    }
+  if (do_data && fuse) {
+    rc = fused_acc_pass(L, v, c);
+    if (rc && rc != SOW_ERR_UNSUPPORTED) return rc;
+    if (!rc) do_data = false;
   }
   // ragged widths: the fused chain for the data gradient (dY and dX views 16-byte aligned, else the generic kernels below:
   // they leave the same dh) and skinny_tn_wide for every weight gradient, dbias included, in the PARTIAL phase
   const bool rag_w = rag_layer(r_live, r_acc, acc_kind, d_in, d_out, dtype) && !sw_on(SW_NO_RAGGED);
-  if (rag_w && do_data && al16p(dy) && al16p(dx)) {
-    if (acc_kind == SOW_ACC_LOWRANK) {
-      rc = wide_chain(dy, dx, acc_up, d_out, acc_down, r_acc, nullptr, nullptr, T, d_out, d_in, r_acc, 1.f, 1.f, 0.f, true, dtype,
-                      ws, w, workspace_bytes, stream, true);
-      if (rc) return rc;
-      beta = 1.f;
-    } else if (acc_kind == SOW_ACC_DENSE) {
-      // dX = dY . W_acc^T   (W_acc stored [d_in, d_out] = [N, K])
-      rc = rag_dense_product(dy, d_out, acc_down, d_out, true, dx, d_in, T, d_in, d_out, dtype, stream);
-      if (rc) return rc;
-      beta = 1.f;
-    }
-    rc = wide_chain(dy, dx, B, d_out, A, r_live, dh, nullptr, T, d_out, d_in, r_live, scale, 1.f, beta, true, dtype, ws, w,
-                    workspace_bytes, stream, true);
-    if (rc) return rc;
+  if (rag_w && do_data && al16p(L.dy) && al16p(L.dx)) {
+    if ((rc = ragged_terms(v, acc_kind, c))) return rc;
     do_data = false;
   }
   if (!do_data) {
@@ -707,140 +835,58 @@ static int backward_impl(const void* dy, const void* x, const void* h_save, cons
   } else if (acc_kind == SOW_ACC_DENSE) {
     if (r_live <= 64) {
       // one product with the low-rank term as a K-extension:  dX = [dY, dh] . [W_acc^T; A^T],  dh = scale * dY . B^T
-      ChainParams pd{};
-      pd.X = dy, pd.Y = nullptr, pd.Hsave = dh, pd.bias = nullptr;
-      pd.M = T, pd.ldx = d_out, pd.ldy = d_in, pd.D1 = d_out, pd.D2 = 0;
-      pd.F1b = B, pd.ldf1b = d_out, pd.F2b = A, pd.ldf2b = r_live, pd.rb = r_live;
-      pd.scale = scale, pd.beta = 0.f;
-      set_planes(pd, ws, w, workspace_bytes);
-      void* apad = ws + w.off_apad;
-      if (gemm4h_supported(dy, d_out, acc_down, d_out, true, B, d_out, A, r_live, dx, d_in, nullptr, dh, T, d_in, d_out, r_live,
-                           dtype)) {
-        // one launch: dh projected by the kernel's own pass over dY, A^T read from A's own 2r-byte rows
-        rc = launch_gemm4h(dy, d_out, acc_down, d_out, true, B, d_out, A, r_live, dx, d_in, nullptr, dh, T, d_in, d_out, r_live,
-                           scale, dtype, stream);
-        if (rc) return rc;
-        data_done = true;
-      } else if (gemm2h_supported(dy, d_out, acc_down, d_out, true, B, d_out, A, r_live, dx, d_in, nullptr, dh, T, d_in, d_out,
-                           r_live, dtype)) {
-        // one launch: dh projected inside the GEMM, A^T read from A's own 2r-byte rows
-        rc = launch_gemm2h(dy, d_out, acc_down, d_out, true, B, d_out, A, r_live, dx, d_in, nullptr, dh, T, d_in, d_out,
-                           r_live, scale, stream);
-        if (rc) return rc;
-        data_done = true;
-      } else if (chain2_supported(pd, dtype) &&
-          gemm2_supported(dy, d_out, acc_down, d_out, true, dh, 64, apad, 64, dx, d_in, nullptr, T, d_in, d_out, dtype)) {
-        // A zero-padded to 64 columns rides along in the dh launch when that grid is large enough
-        const bool pad_fused = (int64_t)ceil_div(T, 64) * 64 >= d_in;
-        if (pad_fused) pd.pad_src = A, pd.pad_dst = apad, pd.pad_rows = d_in, pd.pad_r = r_live;
-        rc = SOW_ERR_UNSUPPORTED;
-        if (short_hp_bytes(T, d_in, d_out, r_live, dtype)) rc = launch_chain_short(pd, dtype, true, (float*)(ws + w.off_hp), stream);
-        if (rc == SOW_ERR_UNSUPPORTED) rc = launch_chain2(pd, true, dtype, stream);
-        if (rc) return rc;
-        if (!pad_fused) {
-          rc = launch_pad64(A, apad, d_in, r_live, stream);
-          if (rc) return rc;
-        }
-        rc = launch_gemm2(dy, d_out, acc_down, d_out, true, dh, 64, apad, 64, 64, dx, d_in, nullptr, T, d_in, d_out, 1.f, 0.f,
-                          stream, w.sk_bytes ? ws + w.off_sk : nullptr, w.sk_bytes);
-        if (rc) return rc;
-        data_done = true;
-      }
+      // (in the one-launch kernels dh is projected by the kernel itself, A^T read from A's own 2r-byte rows)
+      if ((rc = dense_ext_term(L, v, c, &data_done))) return rc;
     }
     // dX = dY . W_acc^T   (W_acc stored [d_in, d_out] = [N, K])
-    if (!data_done) rc = gemm_auto(dy, d_out, acc_down, d_out, true, dx, d_in, nullptr, T, d_in, d_out, 1.f, 0.f, dtype, stream);
+    if (!data_done) rc = dense_product(v, false, dtype, stream);
     if (rc) return rc;
     beta = 1.f;
   } else if (acc_kind == SOW_ACC_LOWRANK) {
-    if (r_acc <= 64) {
-      // dX = (dY . R_up^T) . Q^T : the same chain kernel with the frozen factors, scale 1
-      ChainParams p{};
-      p.X = dy, p.Y = dx, p.Hsave = nullptr, p.bias = nullptr;
-      p.M = T, p.ldx = d_out, p.ldy = d_in, p.D1 = d_out, p.D2 = d_in;
-      p.F1b = acc_up, p.ldf1b = d_out, p.F2b = acc_down, p.ldf2b = r_acc, p.rb = r_acc;
-      p.scale = 1.f, p.beta = 0.f;
-      set_planes(p, ws, w, workspace_bytes);
-      rc = launch_chain(p, dtype, true, stream);
-      if (rc) return rc;
-      beta = 1.f;
-    } else {
-      rc = wide_chain(dy, dx, acc_up, d_out, acc_down, r_acc, nullptr, nullptr, T, d_out, d_in, r_acc, 1.f, 1.f, 0.f, true, dtype,
-                      ws, w, workspace_bytes, stream);
-      if (rc == SOW_ERR_UNSUPPORTED) {
-        void* t = ws + w.off_t;
-        rc = launch_gemm(dy, d_out, false, acc_up, d_out, true, t, r_acc, nullptr, T, r_acc, d_out, 1.f, 0.f, dtype, stream);
-        if (rc) return rc;
-        rc = launch_gemm(t, r_acc, false, acc_down, r_acc, true, dx, d_in, nullptr, T, d_in, r_acc, 1.f, 0.f, dtype, stream);
-      }
-      if (rc) return rc;
-      beta = 1.f;
-    }
+    if ((rc = lowrank_acc_term(v, c))) return rc;   // dX = (dY . R_up^T) . Q^T
+    beta = 1.f;
   }
   if (r_live <= 64) {
-    ChainParams p{};
-    p.X = dy, p.Y = dx, p.Hsave = dh, p.bias = nullptr;
-    p.M = T, p.ldx = d_out, p.ldy = d_in, p.D1 = d_out, p.D2 = d_in;
-    p.F1b = B, p.ldf1b = d_out, p.F2b = A, p.ldf2b = r_live, p.rb = r_live;
-    p.scale = scale, p.beta = beta;
+    ChainParams p = live_chain(v, beta);
     set_planes(p, ws, w, workspace_bytes);
     if (do_data && !data_done) {
       rc = launch_chain_short(p, dtype, true, short_hp_bytes(T, d_in, d_out, r_live, dtype) ? (float*)(ws + w.off_hp) : nullptr, stream);
       if (rc == SOW_ERR_UNSUPPORTED) rc = launch_chain(p, dtype, true, stream);
       if (rc) return rc;
     }
-    if (!do_weights) return SOW_OK;
-    // weight gradients: dA = x^T dh ; dB^T = dY^T h ; dbias = colsum(dY) via the all-ones column 63
-    const bool ones_ok = dbias && r_live <= 63;
-    TnParams tp{};
-    tp.njobs = 2, tp.T = T, tp.ns = w.ns, tp.slab_len = w.slab_len;
-    auto vec_ok = [&](const void* ptr, int D) {
-      if (dtype == SOW_F32) return (D % 4 == 0 && al16p(ptr)) ? 1 : 0;
-      return (D % 2 == 0 && al4p(ptr)) ? 1 : 0;
-    };
-    // the chain kernels write 1.0 into column 63 of h_save / dh whenever r_live <= 63
-    tp.job[0] = TnJob{x, dh, (float*)(ws + w.off_p0), (int64_t)d_in, d_in, -1, (d_in + 63) / 64, vec_ok(x, d_in), 1};
-    tp.job[1] = TnJob{dy, h_save, (float*)(ws + w.off_p1), (int64_t)d_out, d_out, ones_ok ? 63 : -1, (d_out + 63) / 64,
-                      vec_ok(dy, d_out), 1};
-    if (do_partial) {
-      rc = launch_tn(tp, dtype, stream);
+    if (!ph.weights()) return SOW_OK;
+    const bool ones_ok = L.dbias && r_live <= 63;
+    if (ph.partial) {
+      rc = launch_tn(tn_params(L, w, ws, dtype), dtype, stream);
       if (rc) return rc;
     }
-    if (!do_reduce) return SOW_OK;
-    const ReduceParams rp = make_reduce_params(w, ws, dA, dB, ones_ok ? dbias : nullptr, d_in, d_out, r_live, grad_beta);
+    if (!ph.reduce) return SOW_OK;
+    const ReduceParams rp = make_reduce_params(w, ws, L.dA, L.dB, ones_ok ? L.dbias : nullptr, d_in, d_out, r_live, L.grad_beta);
     rc = launch_tn_reduce(rp, gdt, stream);
     if (rc) return rc;
-    if (dbias && !ones_ok) {
-      rc = launch_colsum(dy, T, d_out, dbias, grad_beta, dtype, gdt, stream);
+    if (L.dbias && !ones_ok) {
+      rc = launch_colsum(L.dy, T, d_out, L.dbias, L.grad_beta, dtype, gdt, stream);
       if (rc) return rc;
     }
     return SOW_OK;
   }
   // wide rank: the fused chain (dh = scale dY B^T to the workspace, dX = beta dX + dh A^T) and the token-slab weight-gradient
   // kernel, else the generic GEMM composition
-  if (do_data) {
-    rc = wide_chain(dy, dx, B, d_out, A, r_live, dh, nullptr, T, d_out, d_in, r_live, scale, 1.f, beta, true, dtype, ws, w,
-                    workspace_bytes, stream);
-    if (rc == SOW_ERR_UNSUPPORTED) {
-      rc = launch_gemm(dy, d_out, false, B, d_out, true, dh, r_live, nullptr, T, r_live, d_out, scale, 0.f, dtype, stream);
-      if (rc) return rc;
-      rc = launch_gemm(dh, r_live, false, A, r_live, true, dx, d_in, nullptr, T, d_in, r_live, 1.f, beta, dtype, stream);
-    }
-    if (rc) return rc;
-  }
-  if (!do_partial) return SOW_OK;   // wide ranks: the PARTIAL phase does all of the weight gradients
+  if (do_data && (rc = wide_live_term(v, beta, c))) return rc;
+  if (!ph.partial) return SOW_OK;   // wide ranks: the PARTIAL phase does all of the weight gradients
   if (w.pw_bytes && (rag_w || (!sw_on(SW_NO_WIDE_CHAIN) && tnw_shape_ok(r_live, d_in, d_out, dtype)))) {
-    rc = launch_tn_wide(x, dh, dy, h_save, dA, dB, dbias, T, d_in, d_out, r_live, scale, grad_beta, dtype, gdt, ws + w.off_pw,
-                        w.pw_bytes, stream);
+    rc = launch_tn_wide(L.x, dh, L.dy, L.h_save, L.dA, L.dB, L.dbias, T, d_in, d_out, r_live, L.scale, L.grad_beta, dtype, gdt,
+                        ws + w.off_pw, w.pw_bytes, stream);
     if (rc != SOW_ERR_UNSUPPORTED) return rc;
   }
-  rc = launch_gemm_out(x, d_in, true, dh, r_live, false, dA, r_live, nullptr, d_in, r_live, (int)T, 1.f, grad_beta, dtype, gdt,
+  rc = launch_gemm_out(L.x, d_in, true, dh, r_live, false, L.dA, r_live, nullptr, d_in, r_live, (int)T, 1.f, L.grad_beta, dtype, gdt,
                        stream);
   if (rc) return rc;
-  rc = launch_gemm_out(h_save, r_live, true, dy, d_out, false, dB, d_out, nullptr, r_live, d_out, (int)T, scale, grad_beta, dtype,
-                       gdt, stream);
+  rc = launch_gemm_out(L.h_save, r_live, true, L.dy, d_out, false, L.dB, d_out, nullptr, r_live, d_out, (int)T, L.scale, L.grad_beta,
+                       dtype, gdt, stream);
   if (rc) return rc;
-  if (dbias) {
-    rc = launch_colsum(dy, T, d_out, dbias, grad_beta, dtype, gdt, stream);
+  if (L.dbias) {
+    rc = launch_colsum(L.dy, T, d_out, L.dbias, L.grad_beta, dtype, gdt, stream);
     if (rc) return rc;
   }
   return SOW_OK;
@@ -850,30 +896,17 @@ int sow_backward_ex(const void* dy, const void* x, const void* h_save, const voi
                     const void* acc_up, void* dx, void* dA, void* dB, void* dbias, int64_t T, int d_in, int d_out,
                     int r_live, int r_acc, int acc_kind, float scale, float grad_beta, int dtype, void* workspace,
                     size_t workspace_bytes, int phases, void* stream) {
-  bool pf;
-  const int cd = split_dtype(dtype, &pf);
-  if (!pf)
-    return backward_impl(dy, x, h_save, A, B, acc_down, acc_up, dx, dA, dB, dbias, T, d_in, d_out, r_live, r_acc, acc_kind, scale,
-                         grad_beta, nofuse(dtype), nofuse(dtype), workspace, workspace_bytes, phases, stream, fuse_of(dtype));
-  if (cd < 0) return SOW_ERR_DTYPE;
+  const Dtype f = decode_dtype(dtype);
+  sow_layer_args L = single_layer(x, A, B, acc_down, acc_up, nullptr, nullptr, const_cast<void*>(h_save), dy, dx, dA, dB, dbias, T,
+                                  d_in, d_out, r_live, r_acc, acc_kind, scale, grad_beta, workspace, workspace_bytes);
+  if (!f.param_f32) return backward_impl(L, f.cd, f.cd, phases, f.fuse, (hipStream_t)stream);
+  if (!f.layer_ok()) return SOW_ERR_DTYPE;
   // fp32 parameters: only the data gradient reads the factors (and the accumulator); they are packed when it runs
   if ((phases & SOW_BWD_DATA) && T > 0) {
-    if (d_in <= 0 || d_out <= 0 || r_live <= 0) return SOW_ERR_SHAPE;
-    if (!dy || !x || !h_save || !A || !B || !dx || !dA || !dB || !workspace) return SOW_ERR_NULL;
-    if (acc_kind != SOW_ACC_NONE && !acc_down) return SOW_ERR_NULL;
-    if (acc_kind == SOW_ACC_LOWRANK && (!acc_up || r_acc <= 0)) return SOW_ERR_SHAPE;
-    if (acc_kind != SOW_ACC_LOWRANK) r_acc = 0, acc_up = nullptr;
-    if (acc_kind == SOW_ACC_NONE) acc_down = nullptr;
-    sow_layer_args L = single_layer(A, B, acc_down, acc_up, nullptr, T, d_in, d_out, r_live, r_acc, acc_kind, workspace,
-                                    workspace_bytes);
-    std::vector<PackItem> items;
-    int rc = pack_layer(L, cd, false, items);
+    const int rc = pack_single(L, f.cd, false, (hipStream_t)stream);
     if (rc) return rc;
-    if ((rc = launch_pack_params(items.data(), (int)items.size(), cd, (hipStream_t)stream))) return rc;
-    A = L.A, B = L.B, acc_down = L.acc_down, acc_up = L.acc_up;
   }
-  return backward_impl(dy, x, h_save, A, B, acc_down, acc_up, dx, dA, dB, dbias, T, d_in, d_out, r_live, r_acc, acc_kind, scale,
-                       grad_beta, cd, SOW_F32, workspace, workspace_bytes, phases, stream);
+  return backward_impl(L, f.cd, SOW_F32, phases, false, (hipStream_t)stream);
 }
 
 int sow_backward(const void* dy, const void* x, const void* h_save, const void* A, const void* B, const void* acc_down,
@@ -887,29 +920,17 @@ int sow_backward(const void* dy, const void* x, const void* h_save, const void* 
 // ---- grouped entry points ------------------------------------------------------------------------------------
 // A group is n INDEPENDENT SoWLinear calls (e.g. q / k / v of one attention block, gate / up of one MLP).  Layers that
 // take the plain bf16 / f16 streaming kernels (no accumulator, r <= 64, T / 64 > SHORT_NTB) share launches, C2_MAXG /
-// TN_MAXG at a time; every other layer is forwarded to the single-layer entry point.  Results are bit-identical to n
+// TN_MAXG at a time; every other layer is forwarded to the single-layer path.  Results are bit-identical to n
 // separate calls: the shared grid runs each layer's own workgroups unchanged.
+// w: the layer's plan (data gradient only: dh lies in the workspace)
 static bool group_chain_params(const sow_layer_args& L, bool bwd, int dtype, const WsPlan& w, ChainParams* out) {
   if ((dtype != SOW_BF16 && dtype != SOW_F16) || L.acc_kind != SOW_ACC_NONE || L.r_live > 64 || sw_on(SW_NO_GROUPED) || sw_on(SW_FORCE_CHAIN_V1))
     return false;
   if (ceil_div(L.T, 64) <= SHORT_NTB) return false;   // short inputs: K / column split, single-layer path
-  ChainParams p{};
-  if (!bwd) {
-    p.X = L.x, p.Y = L.y, p.Hsave = L.h_save, p.bias = L.bias;
-    p.M = L.T, p.ldx = L.d_in, p.ldy = L.d_out, p.D1 = L.d_in, p.D2 = L.d_out;
-    p.F1b = L.A, p.ldf1b = L.r_live, p.F2b = L.B, p.ldf2b = L.d_out, p.rb = L.r_live;
-  } else {
-    p.X = L.dy, p.Y = L.dx, p.Hsave = ws_base(L.workspace) + w.off_dh, p.bias = nullptr;
-    p.M = L.T, p.ldx = L.d_out, p.ldy = L.d_in, p.D1 = L.d_out, p.D2 = L.d_in;
-    p.F1b = L.B, p.ldf1b = L.d_out, p.F2b = L.A, p.ldf2b = L.r_live, p.rb = L.r_live;
-  }
-  p.scale = L.scale, p.beta = 0.f;
+  const ChainParams p = live_chain(dir_view(L, bwd, bwd ? ws_base(L.workspace) + w.off_dh : nullptr), 0.f);
   if (!chain2_supported(p, dtype)) return false;
   // the alignment conditions launch_chain2 would reject (it then falls back inside launch_chain)
-  const void* Bp = bwd ? p.F1b : p.F2b;
-  const int64_t ldB = bwd ? p.ldf1b : p.ldf2b;
-  const void* Ap = bwd ? p.F2b : p.F1b;
-  if ((reinterpret_cast<uintptr_t>(Bp) & 15) || ldB % 8 || (reinterpret_cast<uintptr_t>(Ap) & 3)) return false;
+  if (!al16p(L.B) || L.d_out % 8 || !al4p(L.A)) return false;
   *out = p;
   return true;
 }
@@ -926,7 +947,7 @@ static bool group_rows_plan(const sow_layer_args* layers, int n, int dtype, int 
   for (int i = 0; i < n; ++i) {
     const sow_layer_args& L = layers[i];
     if (L.T <= 0 || L.r_live > 64 || (L.dbias && L.r_live > 63)) return false;
-    const WsPlan w = plan_ws(L.T, L.d_in, L.d_out, L.r_live, L.acc_kind == SOW_ACC_LOWRANK ? L.r_acc : 0, L.acc_kind, dtype);
+    const WsPlan w = plan_of(L, dtype);
     if (L.workspace_bytes < w.total + 255) return false;
     if (L.d_in % 8 || L.d_out % 8 || !al16p(L.x) || !al16p(L.dy) || !al16p(L.h_save)) return false;
     T[2 * i] = T[2 * i + 1] = L.T;
@@ -935,36 +956,31 @@ static bool group_rows_plan(const sow_layer_args* layers, int n, int dtype, int 
   }
   return tn_rows_plan(T, D, cap, 2 * n, ns, slab_len);
 }
-
-static int check_layer(const sow_layer_args& L, bool bwd) {
-  if (L.T < 0 || L.d_in <= 0 || L.d_out <= 0 || L.r_live <= 0) return SOW_ERR_SHAPE;
-  if (L.T == 0) return SOW_OK;
-  if (!L.x || !L.A || !L.B) return SOW_ERR_NULL;
-  if (!bwd && !L.y) return SOW_ERR_NULL;
-  if (bwd && (!L.dy || !L.h_save || !L.dx || !L.dA || !L.dB || !L.workspace)) return SOW_ERR_NULL;
-  if (L.acc_kind != SOW_ACC_NONE && !L.acc_down) return SOW_ERR_NULL;
-  return SOW_OK;
+// What sow_backward_group does and sow_backward_group_plan reports: the row-owner weight-gradient kernel with slab counts
+// planned over the group, when the caller asks for it (and then builds the deferred reduction from
+// sow_backward_group_reduce_desc), or when the call runs the reduction itself.
+static bool group_rows(const sow_layer_args* layers, int n, int dtype, int phases, int* rns, int* rslab) {
+  const Phases ph = decode_phases(phases);
+  return ph.weights() && ((phases & SOW_BWD_GROUP_SLABS) || (ph.partial && ph.reduce)) &&
+         group_rows_plan(layers, n, dtype, phases, rns, rslab);
 }
 
 // fp32 parameters of a group: a copy of the layer list pointing at the packed operands, every layer packed by ONE launch
-static int pack_group(const sow_layer_args* layers, int n, int cd, bool bwd, std::vector<sow_layer_args>& out, void* stream) {
+static int pack_group(const sow_layer_args* layers, int n, int cd, bool bwd, std::vector<sow_layer_args>& out, hipStream_t stream) {
   out.assign(layers, layers + n);
   std::vector<PackItem> items;
   int rc;
   for (sow_layer_args& L : out) {
-    if ((rc = check_layer(L, bwd))) return rc;
+    if ((rc = check_layer(L, bwd, true))) return rc;
     if (L.T == 0) continue;
-    if (L.acc_kind == SOW_ACC_LOWRANK && (!L.acc_up || L.r_acc <= 0)) return SOW_ERR_SHAPE;
-    if (L.acc_kind != SOW_ACC_LOWRANK) L.acc_up = nullptr;
-    if (L.acc_kind == SOW_ACC_NONE) L.acc_down = nullptr;
+    normalise_acc(L);
     if (bwd) L.bias = nullptr;   // backward reads no bias
     if ((rc = pack_layer(L, cd, !bwd, items))) return rc;
   }
-  return launch_pack_params(items.data(), (int)items.size(), cd, (hipStream_t)stream);
+  return launch_pack_params(items.data(), (int)items.size(), cd, stream);
 }
 
-static int forward_group_impl(const sow_layer_args* layers, int n, int dtype, void* stream_, bool fuse = false) {
-  hipStream_t stream = (hipStream_t)stream_;
+static int forward_group_impl(const sow_layer_args* layers, int n, int dtype, bool fuse, hipStream_t stream) {
   if (!ok_dtype(dtype)) return SOW_ERR_DTYPE;
   if (n < 0) return SOW_ERR_SHAPE;
   if (n == 0) return SOW_OK;
@@ -974,53 +990,45 @@ static int forward_group_impl(const sow_layer_args* layers, int n, int dtype, vo
   int nb = 0, ng = 0, rc;
   for (int i = 0; i < n; ++i) {
     const sow_layer_args& L = layers[i];
-    if ((rc = check_layer(L, false))) return rc;
+    if ((rc = check_layer(L, false, false))) return rc;
     if (L.T == 0) continue;
-    const WsPlan w{};
-    if (group_chain_params(L, false, dtype, w, &batch[nb])) {   // h_save may be NULL (no backward follows)
+    if (group_chain_params(L, false, dtype, WsPlan{}, &batch[nb])) {   // h_save may be NULL (no backward follows)
       if (++nb == C2_MAXG) {
         if ((rc = launch_chain2_group(batch, nb, false, dtype, stream))) return rc;
         nb = 0;
       }
       continue;
     }
-    // dense accumulator: gemm4h (one launch per layer) where it applies
-    if (L.acc_kind == SOW_ACC_DENSE && L.r_live <= 64 && L.h_save &&
-        gemm4h_supported(L.x, L.d_in, L.acc_down, L.d_out, false, L.A, L.r_live, L.B, L.d_out, L.y, L.d_out, L.bias, L.h_save, L.T,
-                         L.d_out, L.d_in, L.r_live, dtype)) {
-      if ((rc = launch_gemm4h(L.x, L.d_in, L.acc_down, L.d_out, false, L.A, L.r_live, L.B, L.d_out, L.y, L.d_out, L.bias, L.h_save,
-                              L.T, L.d_out, L.d_in, L.r_live, L.scale, dtype, stream)))
-        return rc;
-      continue;
-    }
-    // dense accumulator, one launch per layer (gemm2h): the layers of a group share the grid
-    if (L.acc_kind == SOW_ACC_DENSE && L.r_live <= 64 && L.h_save && !sw_on(SW_NO_GROUPED) &&
-        gemm2h_supported(L.x, L.d_in, L.acc_down, L.d_out, false, L.A, L.r_live, L.B, L.d_out, L.y, L.d_out, L.bias, L.h_save, L.T,
-                         L.d_out, L.d_in, L.r_live, dtype)) {
-      gbatch[ng] = Gemm2hArgs{L.x, L.acc_down, L.A, L.B, L.y, L.bias, L.h_save, L.T, L.d_in, L.d_out, L.r_live, L.d_out, L.d_out,
-                              L.d_out, L.d_in, L.r_live, L.scale};
-      if (++ng == 4) {
-        if ((rc = launch_gemm2h_group(gbatch, ng, false, stream))) return rc;
-        ng = 0;
+    if (L.acc_kind == SOW_ACC_DENSE && L.r_live <= 64 && L.h_save) {
+      const Gemm2hArgs g = dense_args(dir_view(L, false, nullptr));
+      // dense accumulator: gemm4h (one launch per layer) where it applies
+      if (gemm4h_ok(g, false, dtype)) {
+        if ((rc = run_gemm4h(g, false, dtype, stream))) return rc;
+        continue;
       }
-      continue;
+      // dense accumulator, one launch per layer (gemm2h): the layers of a group share the grid
+      if (!sw_on(SW_NO_GROUPED) && gemm2h_ok(g, false, dtype)) {
+        gbatch[ng] = g;
+        if (++ng == 4) {
+          if ((rc = launch_gemm2h_group(gbatch, ng, false, stream))) return rc;
+          ng = 0;
+        }
+        continue;
+      }
     }
-    rc = sow_forward(L.x, L.A, L.B, L.acc_down, L.acc_up, L.bias, L.y, L.h_save, L.T, L.d_in, L.d_out, L.r_live, L.r_acc,
-                     L.acc_kind, L.scale, fuse ? dtype | SOW_FUSE_ACC : dtype, L.workspace, L.workspace_bytes, stream_);
-    if (rc) return rc;
+    if ((rc = forward_impl(L, dtype, fuse, stream))) return rc;
   }
   if (ng && (rc = launch_gemm2h_group(gbatch, ng, false, stream))) return rc;
   return nb ? launch_chain2_group(batch, nb, false, dtype, stream) : SOW_OK;
 }
 
 int sow_forward_group(const sow_layer_args* layers, int n, int dtype, void* stream) {
-  bool pf;
-  const int cd = split_dtype(dtype, &pf);
-  if (cd < 0) return SOW_ERR_DTYPE;
-  if (!pf || n <= 0 || !layers) return forward_group_impl(layers, n, cd, stream, fuse_of(dtype));
+  const Dtype f = decode_dtype(dtype);
+  if (!f.layer_ok()) return SOW_ERR_DTYPE;
+  if (!f.param_f32 || n <= 0 || !layers) return forward_group_impl(layers, n, f.cd, f.fuse, (hipStream_t)stream);
   std::vector<sow_layer_args> packed;
-  const int rc = pack_group(layers, n, cd, false, packed, stream);
-  return rc ? rc : forward_group_impl(packed.data(), n, cd, stream);
+  const int rc = pack_group(layers, n, f.cd, false, packed, (hipStream_t)stream);
+  return rc ? rc : forward_group_impl(packed.data(), n, f.cd, false, (hipStream_t)stream);
 }
 
 // ---- generation-sized forwards (skinny_fwd.hip) --------------------------------------------------------------
@@ -1044,23 +1052,24 @@ static SkWs skinny_ws(int64_t T, int d_in, int d_out, int acc_kind) {
 }
 
 size_t sow_forward_skinny_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype) {
-  dtype = nofuse(dtype);
-  if (!skinny_shape_ok(T, d_in, d_out, r_live, acc_kind, dtype)) return 0;
+  const Dtype f = decode_dtype(dtype);
+  if (f.param_f32 || !skinny_shape_ok(T, d_in, d_out, r_live, acc_kind, f.cd)) return 0;
   return skinny_ws(T, d_in, d_out, acc_kind).total;
 }
 
+// The checks of this entry point are its own (not check_layer): stricter, and every layer is checked before the first
+// launch, so that a refusal leaves all outputs and workspaces untouched.
 int sow_forward_skinny(const sow_layer_args* layers, int n, int dtype, void* stream) {
-  bool pf;
-  const int cd = split_dtype(dtype, &pf);
-  if (cd < 0 || cd == SOW_F32) return SOW_ERR_DTYPE;
-  if (pf || sw_on(SW_NO_SKINNY)) return SOW_ERR_UNSUPPORTED;
+  const Dtype f = decode_dtype(dtype);
+  const int cd = f.cd;
+  if (!f.layer_ok() || cd == SOW_F32) return SOW_ERR_DTYPE;
+  if (f.param_f32 || sw_on(SW_NO_SKINNY)) return SOW_ERR_UNSUPPORTED;
   if (n < 0) return SOW_ERR_SHAPE;
   if (n == 0) return SOW_OK;
   if (!layers) return SOW_ERR_NULL;
   if (n > SK_MAXL) return SOW_ERR_UNSUPPORTED;
   SkLayer sk[SK_MAXL];
   int m = 0;
-  // every layer is checked before the first launch: a refusal leaves all outputs and workspaces untouched
   for (int i = 0; i < n; ++i) {
     const sow_layer_args& L = layers[i];
     if (L.T < 0 || L.d_in <= 0 || L.d_out <= 0 || L.r_live <= 0) return SOW_ERR_SHAPE;
@@ -1083,77 +1092,62 @@ int sow_forward_skinny(const sow_layer_args* layers, int n, int dtype, void* str
   return launch_skinny_fwd(sk, m, cd, (hipStream_t)stream);
 }
 
-static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, int gdt, int phases, void* stream_,
-                               bool fuse = false) {
-  hipStream_t stream = (hipStream_t)stream_;
-  const bool do_data = (phases & SOW_BWD_DATA) != 0;
-  const bool do_partial = (phases & (SOW_BWD_WEIGHTS | SOW_BWD_WEIGHTS_PARTIAL)) != 0;
-  const bool do_reduce = (phases & (SOW_BWD_WEIGHTS | SOW_BWD_WEIGHTS_REDUCE)) != 0;
-  if (!do_data && !do_partial && !do_reduce) return SOW_ERR_SHAPE;
+static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, int gdt, int phases, bool fuse, hipStream_t stream) {
+  const Phases ph = decode_phases(phases);
+  if (!ph.data && !ph.weights()) return SOW_ERR_SHAPE;
   if (!ok_dtype(dtype)) return SOW_ERR_DTYPE;
   if (n < 0) return SOW_ERR_SHAPE;
   if (n == 0) return SOW_OK;
   if (!layers) return SOW_ERR_NULL;
   int rc;
   for (int i = 0; i < n; ++i)
-    if ((rc = check_layer(layers[i], true))) return rc;
-  auto single = [&](const sow_layer_args& L, int ph) {
-    return backward_impl(L.dy, L.x, L.h_save, L.A, L.B, L.acc_down, L.acc_up, L.dx, L.dA, L.dB, L.dbias, L.T, L.d_in, L.d_out,
-                         L.r_live, L.r_acc, L.acc_kind, L.scale, L.grad_beta, dtype, gdt, L.workspace, L.workspace_bytes, ph,
-                         stream_, fuse);
-  };
-  auto plan = [&](const sow_layer_args& L) {
-    return plan_ws(L.T, L.d_in, L.d_out, L.r_live, L.acc_kind == SOW_ACC_LOWRANK ? L.r_acc : 0, L.acc_kind, dtype);
-  };
-  if (do_data) {
+    if ((rc = check_layer(layers[i], true, false))) return rc;
+  if (ph.data) {
     ChainParams batch[C2_MAXG];
     Gemm2hArgs gbatch[4];
     int nb = 0, ng = 0;
     for (int i = 0; i < n; ++i) {
       const sow_layer_args& L = layers[i];
-      if (L.T == 0) {
-        if ((rc = single(L, SOW_BWD_DATA | (phases & ~SOW_BWD_DATA)))) return rc;   // empty batch: everything at once
+      if (L.T == 0) {   // empty batch: everything at once
+        if ((rc = backward_impl(L, dtype, gdt, SOW_BWD_DATA | (phases & ~SOW_BWD_DATA), fuse, stream))) return rc;
         continue;
       }
-      const WsPlan w = plan(L);
+      const WsPlan w = plan_of(L, dtype);
       if (L.workspace_bytes < w.total + 255) return SOW_ERR_WORKSPACE;
-      void* dh = ws_base(L.workspace) + w.off_dh;
       if (group_chain_params(L, true, dtype, w, &batch[nb])) {
         if (++nb == C2_MAXG) {
           if ((rc = launch_chain2_group(batch, nb, true, dtype, stream))) return rc;
           nb = 0;
         }
-      } else if (L.acc_kind == SOW_ACC_DENSE && L.r_live <= 64 &&
-                 gemm4h_supported(L.dy, L.d_out, L.acc_down, L.d_out, true, L.B, L.d_out, L.A, L.r_live, L.dx, L.d_in, nullptr, dh,
-                                  L.T, L.d_in, L.d_out, L.r_live, dtype)) {
-        if ((rc = launch_gemm4h(L.dy, L.d_out, L.acc_down, L.d_out, true, L.B, L.d_out, L.A, L.r_live, L.dx, L.d_in, nullptr, dh,
-                                L.T, L.d_in, L.d_out, L.r_live, L.scale, dtype, stream)))
-          return rc;
-      } else if (L.acc_kind == SOW_ACC_DENSE && L.r_live <= 64 && !sw_on(SW_NO_GROUPED) &&
-                 gemm2h_supported(L.dy, L.d_out, L.acc_down, L.d_out, true, L.B, L.d_out, L.A, L.r_live, L.dx, L.d_in, nullptr, dh,
-                                  L.T, L.d_in, L.d_out, L.r_live, dtype)) {
-        gbatch[ng] = Gemm2hArgs{L.dy, L.acc_down, L.B, L.A, L.dx, nullptr, dh, L.T, L.d_out, L.d_out, L.d_out, L.r_live, L.d_in,
-                                L.d_in, L.d_out, L.r_live, L.scale};
-        if (++ng == 4) {
-          if ((rc = launch_gemm2h_group(gbatch, ng, true, stream))) return rc;
-          ng = 0;
+        continue;
+      }
+      if (L.acc_kind == SOW_ACC_DENSE && L.r_live <= 64) {
+        const Gemm2hArgs g = dense_args(dir_view(L, true, ws_base(L.workspace) + w.off_dh));
+        if (gemm4h_ok(g, true, dtype)) {
+          if ((rc = run_gemm4h(g, true, dtype, stream))) return rc;
+          continue;
         }
-      } else if ((rc = single(L, SOW_BWD_DATA)))
-        return rc;
+        if (!sw_on(SW_NO_GROUPED) && gemm2h_ok(g, true, dtype)) {
+          gbatch[ng] = g;
+          if (++ng == 4) {
+            if ((rc = launch_gemm2h_group(gbatch, ng, true, stream))) return rc;
+            ng = 0;
+          }
+          continue;
+        }
+      }
+      if ((rc = backward_impl(L, dtype, gdt, SOW_BWD_DATA, fuse, stream))) return rc;
     }
     if (ng && (rc = launch_gemm2h_group(gbatch, ng, true, stream))) return rc;
     if (nb && (rc = launch_chain2_group(batch, nb, true, dtype, stream))) return rc;
   }
-  // row-owner weight-gradient kernel with slab counts planned over the group: when the caller asks for it (and then builds
-  // the deferred reduction from sow_backward_group_reduce_desc), or when this call runs the reduction itself
   int rns[TNR_MAXI], rslab[TNR_MAXI];
-  const bool rows = (do_partial || do_reduce) && ((phases & SOW_BWD_GROUP_SLABS) || (do_partial && do_reduce)) &&
-                    group_rows_plan(layers, n, dtype, phases, rns, rslab);
-  if (do_partial && rows) {
+  const bool rows = group_rows(layers, n, dtype, phases, rns, rslab);
+  if (ph.partial && rows) {
     TnRowsItem items[TNR_MAXI];
     for (int i = 0; i < n; ++i) {
       const sow_layer_args& L = layers[i];
-      const WsPlan w = plan(L);
+      const WsPlan w = plan_of(L, dtype);
       char* ws = ws_base(L.workspace);
       items[2 * i] = TnRowsItem{L.x, ws + w.off_dh, (float*)(ws + w.off_p0), (int64_t)L.d_in, L.T, L.d_in, 0, 0, 0, 0, rns[2 * i],
                                 rslab[2 * i], 0};
@@ -1161,27 +1155,20 @@ static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, i
                                     rns[2 * i + 1], rslab[2 * i + 1], 0};
     }
     if ((rc = launch_tn_rows(items, 2 * n, dtype, stream))) return rc;
-  } else if (do_partial) {
+  } else if (ph.partial) {
     TnParams batch[TN_MAXG];
     int nb = 0;
     for (int i = 0; i < n; ++i) {
       const sow_layer_args& L = layers[i];
       if (L.T == 0) {
-        if (!do_data && (rc = single(L, phases))) return rc;
+        if (!ph.data && (rc = backward_impl(L, dtype, gdt, phases, fuse, stream))) return rc;
         continue;
       }
-      const WsPlan w = plan(L);
+      const WsPlan w = plan_of(L, dtype);
       if (L.workspace_bytes < w.total + 255) return SOW_ERR_WORKSPACE;
       bool grouped = false;
       if (L.r_live <= 64 && !sw_on(SW_NO_GROUPED)) {
-        char* ws = ws_base(L.workspace);
-        TnParams tp{};
-        tp.njobs = 2, tp.T = L.T, tp.ns = w.ns, tp.slab_len = w.slab_len;
-        const bool ones_ok = L.dbias && L.r_live <= 63;
-        const int vx = (L.d_in % 2 == 0 && al4p(L.x)) ? 1 : 0, vy = (L.d_out % 2 == 0 && al4p(L.dy)) ? 1 : 0;
-        tp.job[0] = TnJob{L.x, ws + w.off_dh, (float*)(ws + w.off_p0), (int64_t)L.d_in, L.d_in, -1, (L.d_in + 63) / 64, vx, 1};
-        tp.job[1] = TnJob{L.dy, L.h_save, (float*)(ws + w.off_p1), (int64_t)L.d_out, L.d_out, ones_ok ? 63 : -1,
-                          (L.d_out + 63) / 64, vy, 1};
+        const TnParams tp = tn_params(L, w, ws_base(L.workspace), dtype);
         if (tn_group_supported(tp, dtype)) {
           batch[nb] = tp;
           grouped = true;
@@ -1191,39 +1178,41 @@ static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, i
           }
         }
       }
-      if (!grouped && (rc = single(L, SOW_BWD_WEIGHTS_PARTIAL))) return rc;
+      if (!grouped && (rc = backward_impl(L, dtype, gdt, SOW_BWD_WEIGHTS_PARTIAL, fuse, stream))) return rc;
     }
     if (nb && (rc = launch_tn_group(batch, nb, dtype, stream))) return rc;
   }
-  if (do_reduce && rows) {
+  if (ph.reduce && rows) {
     for (int i = 0; i < n; ++i) {
       const sow_layer_args& L = layers[i];
-      ReduceParams rp = make_reduce_params(plan(L), ws_base(L.workspace), L.dA, L.dB, L.dbias, L.d_in, L.d_out, L.r_live, L.grad_beta);
+      ReduceParams rp = make_reduce_params(plan_of(L, dtype), ws_base(L.workspace), L.dA, L.dB, L.dbias, L.d_in, L.d_out, L.r_live,
+                                           L.grad_beta);
       rp.job[0].ns = rns[2 * i], rp.job[1].ns = rns[2 * i + 1];
       if ((rc = launch_tn_reduce(rp, gdt, stream))) return rc;
     }
-  } else if (do_reduce) {
+  } else if (ph.reduce) {
     for (int i = 0; i < n; ++i)
-      if (layers[i].T != 0 && (rc = single(layers[i], SOW_BWD_WEIGHTS_REDUCE))) return rc;
+      if (layers[i].T != 0 && (rc = backward_impl(layers[i], dtype, gdt, SOW_BWD_WEIGHTS_REDUCE, fuse, stream))) return rc;
   }
   return SOW_OK;
 }
 
-int sow_backward_group(const sow_layer_args* layers, int n, int dtype, int phases, void* stream) {
-  bool pf;
-  const int cd = split_dtype(dtype, &pf);
-  if (!pf) return backward_group_impl(layers, n, nofuse(dtype), nofuse(dtype), phases, stream, fuse_of(dtype));
-  if (cd < 0) return SOW_ERR_DTYPE;
-  if (n <= 0 || !layers || !(phases & SOW_BWD_DATA)) return backward_group_impl(layers, n, cd, SOW_F32, phases, stream);
+int sow_backward_group(const sow_layer_args* layers, int n, int dtype, int phases, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const Dtype f = decode_dtype(dtype);
+  if (!f.param_f32) return backward_group_impl(layers, n, f.cd, f.cd, phases, f.fuse, stream);
+  if (!f.layer_ok()) return SOW_ERR_DTYPE;
+  if (n <= 0 || !layers || !(phases & SOW_BWD_DATA)) return backward_group_impl(layers, n, f.cd, SOW_F32, phases, false, stream);
   std::vector<sow_layer_args> packed;
-  const int rc = pack_group(layers, n, cd, true, packed, stream);
-  return rc ? rc : backward_group_impl(packed.data(), n, cd, SOW_F32, phases, stream);
+  const int rc = pack_group(layers, n, f.cd, true, packed, stream);
+  return rc ? rc : backward_group_impl(packed.data(), n, f.cd, SOW_F32, phases, false, stream);
 }
 
 // ---- shared-input entry points (chain2_shared.hip) -----------------------------------------------------------------
 // Sibling layers on one x: the forward reads x once, the data gradient writes ONE dX.  Admitted: a set that
 // group_chain_params takes layer by layer (bf16 / f16, no accumulator, r_live <= 64, T > 8192, chain2 alignment) with one x
-// pointer and one d_in; anything else returns SOW_ERR_UNSUPPORTED before anything is launched.
+// pointer and one d_in; anything else returns SOW_ERR_UNSUPPORTED before anything is launched.  SOW_PARAM_F32 is not
+// admitted either, but only after the checks before it: a flagged fp32 dtype gets that far too.
 static int shared_common(const sow_layer_args* layers, int n, bool bwd) {
   if (n <= 0) return SOW_ERR_SHAPE;
   if (!layers) return SOW_ERR_NULL;
@@ -1239,69 +1228,71 @@ static void shared_fill_dx(const sow_layer_args* layers, int n, sow_layer_args* 
 }
 
 int sow_forward_shared(const sow_layer_args* layers, int n, int dtype, void* stream) {
-  dtype = nofuse(dtype);
-  if (!ok_dtype(dtype & ~SOW_PARAM_F32)) return SOW_ERR_DTYPE;
+  const Dtype f = decode_dtype(dtype);
+  if (!ok_dtype(f.cd)) return SOW_ERR_DTYPE;
   int rc;
   if ((rc = shared_common(layers, n, false))) return rc;
   for (int i = 0; i < n; ++i)
-    if ((rc = check_layer(layers[i], false))) return rc;
-  if (sw_on(SW_NO_SHARED_X) || flagged(dtype) || n > C2_MAXG || layers[0].T == 0) return SOW_ERR_UNSUPPORTED;
+    if ((rc = check_layer(layers[i], false, false))) return rc;
+  if (sw_on(SW_NO_SHARED_X) || f.param_f32 || n > C2_MAXG || layers[0].T == 0) return SOW_ERR_UNSUPPORTED;
   ChainParams ps[C2_MAXG];
   for (int i = 0; i < n; ++i)
-    if (!group_chain_params(layers[i], false, dtype, WsPlan{}, &ps[i])) return SOW_ERR_UNSUPPORTED;
-  return launch_chain2_shared(ps, n, false, dtype, (hipStream_t)stream);
+    if (!group_chain_params(layers[i], false, f.cd, WsPlan{}, &ps[i])) return SOW_ERR_UNSUPPORTED;
+  return launch_chain2_shared(ps, n, false, f.cd, (hipStream_t)stream);
 }
 
-int sow_backward_shared(const sow_layer_args* layers, int n, int dtype, int phases, void* stream) {
-  dtype = nofuse(dtype);
-  if (!ok_dtype(dtype & ~SOW_PARAM_F32)) return SOW_ERR_DTYPE;
+int sow_backward_shared(const sow_layer_args* layers, int n, int dtype, int phases, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const Dtype f = decode_dtype(dtype);
+  const int cd = f.cd;
+  if (!ok_dtype(cd)) return SOW_ERR_DTYPE;
   int rc;
   if ((rc = shared_common(layers, n, true))) return rc;
   if (n > C2_MAXG) return SOW_ERR_UNSUPPORTED;
-  if (flagged(dtype)) return SOW_ERR_UNSUPPORTED;
+  if (f.param_f32) return SOW_ERR_UNSUPPORTED;
   sow_layer_args filled[C2_MAXG];
   shared_fill_dx(layers, n, filled);
-  if (!(phases & SOW_BWD_DATA)) return sow_backward_group(filled, n, dtype, phases, stream);
+  if (!(phases & SOW_BWD_DATA)) return backward_group_impl(filled, n, cd, cd, phases, false, stream);
   for (int i = 0; i < n; ++i)
-    if ((rc = check_layer(filled[i], true))) return rc;
+    if ((rc = check_layer(filled[i], true, false))) return rc;
   if (sw_on(SW_NO_SHARED_X) || filled[0].T == 0) return SOW_ERR_UNSUPPORTED;
   ChainParams ps[C2_MAXG];
   for (int i = 0; i < n; ++i) {
     const sow_layer_args& L = filled[i];
-    const WsPlan w = plan_ws(L.T, L.d_in, L.d_out, L.r_live, 0, L.acc_kind, dtype);
-    if (!group_chain_params(L, true, dtype, w, &ps[i])) return SOW_ERR_UNSUPPORTED;
+    const WsPlan w = plan_of(L, cd);
+    if (!group_chain_params(L, true, cd, w, &ps[i])) return SOW_ERR_UNSUPPORTED;
     if (L.workspace_bytes < w.total + 255) return SOW_ERR_WORKSPACE;
     ps[i].beta = filled[0].grad_beta;   // dX = grad_beta * dX + sum_i dh_i A_i^T
   }
-  if ((rc = launch_chain2_shared(ps, n, true, dtype, (hipStream_t)stream))) return rc;
+  if ((rc = launch_chain2_shared(ps, n, true, cd, stream))) return rc;
   // the weight phases read each layer's dh where the grouped data phase leaves it: exactly sow_backward_group's code
   const int wph = phases & ~SOW_BWD_DATA;
-  return (wph & (SOW_BWD_WEIGHTS | SOW_BWD_WEIGHTS_PARTIAL | SOW_BWD_WEIGHTS_REDUCE))
-             ? backward_group_impl(filled, n, dtype, dtype, wph, stream)
-             : SOW_OK;
+  return decode_phases(wph).weights() ? backward_group_impl(filled, n, cd, cd, wph, false, stream) : SOW_OK;
+}
+
+// the group entry points' checks for the two plan queries below
+static int check_group(const sow_layer_args* layers, int n) {
+  for (int i = 0; i < n; ++i) {
+    const int rc = check_layer(layers[i], true, false);
+    if (rc) return rc;
+  }
+  return SOW_OK;
 }
 
 int sow_backward_group_plan(const sow_layer_args* layers, int n, int dtype, int phases, int* slabs_out) {
-  bool pf;
-  dtype = split_dtype(dtype, &pf);   // the plan does not depend on the parameter dtype
-  if (dtype < 0) return SOW_ERR_DTYPE;
+  const Dtype f = decode_dtype(dtype);   // the plan does not depend on the parameter dtype
+  if (!f.layer_ok()) return SOW_ERR_DTYPE;
   if (n < 0) return SOW_ERR_SHAPE;
   if (n == 0) return 0;
   if (!layers) return SOW_ERR_NULL;
   int rc;
-  for (int i = 0; i < n; ++i)
-    if ((rc = check_layer(layers[i], true))) return rc;
-  const bool do_partial = (phases & (SOW_BWD_WEIGHTS | SOW_BWD_WEIGHTS_PARTIAL)) != 0;
-  const bool do_reduce = (phases & (SOW_BWD_WEIGHTS | SOW_BWD_WEIGHTS_REDUCE)) != 0;
+  if ((rc = check_group(layers, n))) return rc;
   int rns[TNR_MAXI], rslab[TNR_MAXI];
-  const bool rows = (do_partial || do_reduce) && ((phases & SOW_BWD_GROUP_SLABS) || (do_partial && do_reduce)) &&
-                    group_rows_plan(layers, n, dtype, phases, rns, rslab);
+  const bool rows = group_rows(layers, n, f.cd, phases, rns, rslab);
   if (slabs_out)
     for (int i = 0; i < n; ++i) {
       const sow_layer_args& L = layers[i];
-      int ns = 0;
-      if (L.T > 0 && L.r_live <= 64)
-        ns = plan_ws(L.T, L.d_in, L.d_out, L.r_live, L.acc_kind == SOW_ACC_LOWRANK ? L.r_acc : 0, L.acc_kind, dtype).ns;
+      const int ns = L.T > 0 && L.r_live <= 64 ? plan_of(L, f.cd).ns : 0;
       slabs_out[2 * i] = rows ? rns[2 * i] : ns;
       slabs_out[2 * i + 1] = rows ? rns[2 * i + 1] : ns;
     }
@@ -1309,21 +1300,21 @@ int sow_backward_group_plan(const sow_layer_args* layers, int n, int dtype, int 
 }
 
 int sow_backward_group_reduce_desc(const sow_layer_args* layers, int n, int dtype, int phases, void* descs_out, int* blocks_out) {
-  bool pf;
-  dtype = split_dtype(dtype, &pf);
-  if (dtype < 0) return SOW_ERR_DTYPE;
+  const Dtype f = decode_dtype(dtype);
+  if (!f.layer_ok()) return SOW_ERR_DTYPE;
   if (n < 0) return SOW_ERR_SHAPE;
   if (n == 0) return SOW_OK;
   if (!layers || !descs_out || !blocks_out) return SOW_ERR_NULL;
   int rc;
-  for (int i = 0; i < n; ++i)
-    if ((rc = check_layer(layers[i], true))) return rc;
+  if ((rc = check_group(layers, n))) return rc;
+  // Not group_rows(): `phases` are the flags of the PARTIAL call, whose reduction is deferred, so the group-planned slab
+  // counts apply exactly when that call asked for them (SOW_BWD_GROUP_SLABS), whatever its other phase bits say.
   int rns[TNR_MAXI], rslab[TNR_MAXI];
-  const bool rows = (phases & SOW_BWD_GROUP_SLABS) && group_rows_plan(layers, n, dtype, phases, rns, rslab);
+  const bool rows = (phases & SOW_BWD_GROUP_SLABS) && group_rows_plan(layers, n, f.cd, phases, rns, rslab);
   for (int i = 0; i < n; ++i) {
     const sow_layer_args& L = layers[i];
     char* out = (char*)descs_out + (size_t)i * sizeof(ReduceParams);
-    if ((rc = sow_backward_reduce_desc(L.dA, L.dB, L.dbias, L.T, L.d_in, L.d_out, L.r_live, L.r_acc, L.acc_kind, L.grad_beta, dtype,
+    if ((rc = sow_backward_reduce_desc(L.dA, L.dB, L.dbias, L.T, L.d_in, L.d_out, L.r_live, L.r_acc, L.acc_kind, L.grad_beta, f.cd,
                                        L.workspace, L.workspace_bytes, out, blocks_out + i)))
       return rc;
     if (rows) {

@@ -67,16 +67,21 @@ def _stream(device: Optional[torch.device] = None) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
-def _launch(dev: torch.device, what: str, fn, *args) -> None:
+def _launch_rc(dev: torch.device, fn, *args) -> int:
     """Call a C-ABI launcher with the tensors' device current (the kernels run on the HIP device that is current on the
-    calling thread; the stream argument is that device's current torch stream).  One process per GPU never takes the
-    slow branch; a process that touches several GPUs gets the right device instead of an invalid-handle error."""
+    calling thread; the stream argument is that device's current torch stream) and return its code.  One process per GPU
+    never takes the slow branch; a process that touches several GPUs gets the right device instead of an invalid-handle
+    error."""
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
     if idx == torch.cuda.current_device():
-        _lib.check(fn(*args, _stream(dev)), what)
-    else:
-        with torch.cuda.device(idx):
-            _lib.check(fn(*args, _stream(dev)), what)
+        return fn(*args, _stream(dev))
+    with torch.cuda.device(idx):
+        return fn(*args, _stream(dev))
+
+
+def _launch(dev: torch.device, what: str, fn, *args) -> None:
+    """_launch_rc for the callers that take any non-zero code as an error."""
+    _lib.check(_launch_rc(dev, fn, *args), what)
 
 
 def _ws(nbytes: int, device) -> torch.Tensor:
@@ -312,12 +317,7 @@ def sow_forward_skinny(layers) -> Optional[list]:
         a.acc_kind = _lib.ACC_NONE if acc_down is None else _lib.ACC_DENSE
         a.scale = float(layer[5])
         a.workspace, a.workspace_bytes = base + off, nws
-    idx = x0.device.index if x0.device.index is not None else torch.cuda.current_device()
-    if idx == torch.cuda.current_device():
-        rc = lib.sow_forward_skinny(arr, n, dt, _stream(x0.device))
-    else:
-        with torch.cuda.device(idx):
-            rc = lib.sow_forward_skinny(arr, n, dt, _stream(x0.device))
+    rc = _launch_rc(x0.device, lib.sow_forward_skinny, arr, n, dt)
     if rc == _lib.ERR_UNSUPPORTED:
         return None
     _lib.check(rc, "sow_forward_skinny")
@@ -533,9 +533,7 @@ class SharedInputGroup(LayerGroup):
             self.arr[i].dx = self.arr[0].dx
 
     def _run(self, what: str, fn, *args) -> bool:
-        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        with torch.cuda.device(idx):
-            rc = fn(self.arr, len(self.calls), self.dtype, *args, _stream(self.device))
+        rc = _launch_rc(self.device, fn, self.arr, len(self.calls), self.dtype, *args)
         if rc == _lib.ERR_UNSUPPORTED:
             return False
         _lib.check(rc, what)

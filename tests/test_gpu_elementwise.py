@@ -387,7 +387,7 @@ CASES = [
     # chain2 streaming forward / backward (chain2_supported: bf16, r even in [4, 64], widths % 8, 16-byte views, T >= 64;
     # T / 64 > SHORT_NTB = 128 token blocks, so no short split) + tn_partial_dma_wide + tn_reduce
     Case("chain2_T8193", BF16, 8193, 512, 264, 50, s=0.5),
-    Case("chain2_T32769_r64_colsum", BF16, 32769, 256, 520, 64),          # r = 64: dbias by colsum_kernel (api.hip:509)
+    Case("chain2_T32769_r64_colsum", BF16, 32769, 256, 520, 64),          # r = 64: dbias by colsum_kernel (api.hip: backward_impl)
     Case("chain2_T32769_grad_beta", BF16, 32769, 256, 264, 50, bias=True, s=0.5, grad_beta=1.0),
     # chain_short: T / 64 <= 128 token blocks and nst + nsl >= 24 column tiles: phase 1 split over K + h_reduce, phase 2
     # split over the output columns
@@ -449,7 +449,7 @@ def _has_kernel(seq, kernel):
 
 # Dispatch switches (api.hip, gemm2.hip): (case, kernels the trace must show, kernels it must not).  The rounding class of
 # each is read off the path the switch leaves:
-# * NO_SHORT_SPLIT: launch_chain_short declines (api.hip:117), the layer (no accumulator) runs the unsplit chain: y and dX
+# * NO_SHORT_SPLIT: launch_chain_short declines (api.hip), the layer (no accumulator) runs the unsplit chain: y and dX
 #   are still written by one kernel from operands the test sees ("once");
 # * FORCE_GEMM_V1: gemm4h / gemm2h / gemm2 all decline, gemm_auto takes the generic kernel for x W_acc and dY W_acc^T and
 #   the chain adds the low-rank term with beta = 1 ("twice", as dense_misaligned);
