@@ -386,6 +386,48 @@ int sow_adamw_flat_seg(void* param, const void* grad, void* exp_avg, void* exp_a
                        int n_segs, double beta1, double beta2, float eps, float grad_scale, int dtype, int state_dtype,
                        void* stream);
 
+/* Global gradient statistics of one flat buffer, kept on the device: the norm that torch.nn.utils.clip_grad_norm_ takes
+ * (simple_train.py:631, the Trainer's max_grad_norm), the clip coefficient, the one factor AdamW multiplies the gradient by
+ * and a flag for gradients that are not finite (the overflow check of an fp16 loop).  The host never reads any of it.
+ *   sow_grad_stats_flat   two launches on `stream`: one double per workgroup (at most 1024, each over a range of elements
+ *                         that depends on n only; 16-byte loads when grad is 16-byte aligned, element loads of the same
+ *                         elements otherwise; every element widened to double, squared and summed in double in a fixed
+ *                         order), then one workgroup that sums them in a fixed order and writes the record.  No atomics:
+ *                         the bits of the record depend on n, the dtype, the data and the scalars only.  Neither the
+ *                         workspace nor `out` has to be initialised.  extra_sumsq, loss_scale, extra_found_inf: DEVICE
+ *                         scalars, each may be NULL (0, 1, 0).  skip_counters: n_counters DEVICE int32, each raised by the
+ *                         record's nonfinite flag (NULL / 0: none).  n == 0: sumsq = 0 (grad may be NULL).
+ *   SOW_ERR_SHAPE: n < 0 or n_counters < 0; SOW_ERR_NULL: out, workspace, grad (n > 0) or skip_counters (n_counters > 0);
+ *   SOW_ERR_DTYPE: not SOW_DTYPE_F32 / BF16 / F16; SOW_ERR_WORKSPACE: below sow_grad_stats_workspace_bytes(n) (a pure,
+ *   monotone function of n, at most 8 KiB).  All of it before the first launch: a refused call writes nothing. */
+typedef struct sow_grad_stats {
+  double sumsq;      /* sum of g^2 over the flat buffer as stored (before any scale) */
+  double total_sq;   /* mult0^2 * sumsq + extra_sumsq, mult0 = grad_scale / loss_scale */
+  float total_norm;  /* (float)sqrt(total_sq) */
+  float clip_coef;   /* min(1, max_norm / (sqrt(total_sq) + 1e-6)); exactly 1.0f when max_norm <= 0 or +inf */
+  float grad_mult;   /* (float)(mult0 * clip_coef): the one factor AdamW multiplies g by */
+  int32_t nonfinite; /* 1 when total_sq is not finite or *extra_found_inf != 0, else 0 */
+} sow_grad_stats;
+size_t sow_grad_stats_workspace_bytes(int64_t n);
+int sow_grad_stats_flat(const void* grad, int64_t n, int dtype, float grad_scale, float max_norm, const double* extra_sumsq,
+                        const float* loss_scale, const float* extra_found_inf, int32_t* skip_counters, int n_counters,
+                        void* workspace, size_t workspace_bytes, sow_grad_stats* out, void* stream);
+
+/* sow_adamw_flat_seg with the gradient multiplier read from a device record: g is multiplied by stats->grad_mult, and with
+ * skip_nonfinite != 0 a record whose nonfinite flag is set leaves param, exp_avg and exp_avg_sq untouched.  `stats` must
+ * have been written on `stream` before this call (sow_grad_stats_flat).  seg_counter (HOST, n_segs entries, or NULL for
+ * none): per segment an index into the DEVICE array skip_counters, -1 for none.  A segment without a counter, or whose
+ * counter reads 0, runs with the host-formed scalars of sow_adamw_flat_seg -- with grad_mult equal to its grad_scale the
+ * results are its results bit for bit.  A counter that reads c > 0 makes the kernel form 1 - lr*wd, lr/bc1 and sqrt(bc2)
+ * for step max(1, step - c) in double on the device, each rounded once: host step counts advance on skipped steps, the
+ * bias correction does not.  Errors as sow_adamw_flat_seg, plus SOW_ERR_NULL for stats (or skip_counters with
+ * n_counters > 0) and SOW_ERR_SHAPE for n_counters < 0 or a seg_counter entry outside [-1, n_counters); all before the
+ * first launch. */
+int sow_adamw_flat_seg_stats(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, const sow_adamw_segment* segs,
+                             const int* seg_counter, int n_segs, double beta1, double beta2, float eps,
+                             const sow_grad_stats* stats, int skip_nonfinite, const int32_t* skip_counters, int n_counters,
+                             int dtype, int state_dtype, void* stream);
+
 /* TTAdam dense section (ttadam.py:84-111), fp32 buffers; double betas (1 - beta formed in double). */
 int sow_ttadam_dense(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, double beta1,
                      double beta2, float eps, float step_size, float lr_times_wd, int clamp_v, void* stream);

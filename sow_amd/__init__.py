@@ -6,7 +6,7 @@ include/sow_amd.h); this package is the host-side mirror of the reference's Pyth
 from .layer import SoWLinear, SoWParameter  # noqa: F401
 from .prepare import SoWConfig, accumulate, load_sow, prepare_sow, reset_optimizer  # noqa: F401
 from .tt import TensorTrain  # noqa: F401
-from .optimizer import TTAdam, TTSGD, FactorAdamW  # noqa: F401
+from .optimizer import TTAdam, TTSGD, FactorAdamW, clip_grad_norm_  # noqa: F401
 from .tensor_linear import TensorTrainLinear  # noqa: F401
 from .dp import FactorBucket, factor_parameters  # noqa: F401
 from .group import group_siblings, ungroup_siblings  # noqa: F401

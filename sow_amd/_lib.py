@@ -23,6 +23,8 @@ BWD_DATA, BWD_WEIGHTS, BWD_WEIGHTS_PARTIAL, BWD_WEIGHTS_REDUCE = 1, 2, 4, 8
 BWD_GROUP_SLABS = 16     # sow_backward_group: slab counts planned over the group (deferred reduction from group descriptors)
 ERR_NULL = -1
 ERR_SHAPE = -2
+ERR_DTYPE = -3
+ERR_WORKSPACE = -5
 ERR_UNSUPPORTED = -6      # include/sow_amd.h SOW_ERR_UNSUPPORTED: nothing was launched
 
 
@@ -69,6 +71,12 @@ class AdamwSegment(ctypes.Structure):
     _fields_ = [("begin", c_int64), ("end", c_int64), ("lr", c_float), ("weight_decay", c_float), ("step", ctypes.c_int32)]
 
 
+class GradStatsRecord(ctypes.Structure):
+    """sow_grad_stats of include/sow_amd.h: the 32-byte device record (this class only names its layout)."""
+    _fields_ = [("sumsq", c_double), ("total_sq", c_double), ("total_norm", c_float), ("clip_coef", c_float),
+                ("grad_mult", c_float), ("nonfinite", ctypes.c_int32)]
+
+
 # name -> (restype, argtypes); mirrors include/sow_amd.h one to one
 SIGNATURES = {
     "sow_version": (c_int, []),
@@ -110,6 +118,11 @@ SIGNATURES = {
                                c_float, c_int, c_float, c_int, c_int, c_void_p]),
     "sow_adamw_flat_seg": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(AdamwSegment), c_int, c_double, c_double,
                                    c_float, c_float, c_int, c_int, c_void_p]),
+    "sow_grad_stats_workspace_bytes": (c_size_t, [c_int64]),
+    "sow_grad_stats_flat": (c_int, [c_void_p, c_int64, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                    c_void_p, c_size_t, c_void_p, c_void_p]),
+    "sow_adamw_flat_seg_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(AdamwSegment), POINTER(c_int), c_int,
+                                         c_double, c_double, c_float, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "sow_ttadam_dense": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_float, c_float,
                                  c_float, c_int, c_void_p]),
     "sow_tt_kron_core": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),

@@ -1503,6 +1503,27 @@ int sow_adamw_flat_seg(void* param, const void* grad, void* exp_avg, void* exp_a
                                state_dtype, (hipStream_t)stream);
 }
 
+size_t sow_grad_stats_workspace_bytes(int64_t n) { return grad_stats_workspace_bytes(n); }
+
+int sow_grad_stats_flat(const void* grad, int64_t n, int dtype, float grad_scale, float max_norm, const double* extra_sumsq,
+                        const float* loss_scale, const float* extra_found_inf, int32_t* skip_counters, int n_counters,
+                        void* workspace, size_t workspace_bytes, sow_grad_stats* out, void* stream) {
+  dtype = nofuse(dtype);
+  if (flagged(dtype)) return SOW_ERR_DTYPE;
+  return launch_grad_stats(grad, n, dtype, grad_scale, max_norm, extra_sumsq, loss_scale, extra_found_inf, skip_counters,
+                           n_counters, workspace, workspace_bytes, out, (hipStream_t)stream);
+}
+
+int sow_adamw_flat_seg_stats(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, const sow_adamw_segment* segs,
+                             const int* seg_counter, int n_segs, double beta1, double beta2, float eps,
+                             const sow_grad_stats* stats, int skip_nonfinite, const int32_t* skip_counters, int n_counters,
+                             int dtype, int state_dtype, void* stream) {
+  dtype = nofuse(dtype), state_dtype = nofuse(state_dtype);
+  if (flagged(dtype) || flagged(state_dtype)) return SOW_ERR_DTYPE;
+  return launch_adamw_flat_seg_stats(param, grad, exp_avg, exp_avg_sq, segs, seg_counter, n_segs, beta1, beta2, eps, stats,
+                                     skip_nonfinite, skip_counters, n_counters, dtype, state_dtype, (hipStream_t)stream);
+}
+
 int sow_ttadam_dense(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, double beta1,
                      double beta2, float eps, float step_size, float lr_times_wd, int clamp_v, void* stream) {
   return launch_ttadam_dense(param, grad, exp_avg, exp_avg_sq, n, beta1, beta2, eps, step_size, lr_times_wd, clamp_v,

@@ -355,6 +355,14 @@ int launch_adamw_flat(void* p, const void* g, void* m, void* v, int64_t n, float
                       float wd, int step, float grad_scale, int dtype, int state_dtype, hipStream_t stream);
 int launch_adamw_flat_seg(void* p, const void* g, void* m, void* v, const sow_adamw_segment* segs, int n_segs, double b1,
                           double b2, float eps, float grad_scale, int dtype, int state_dtype, hipStream_t stream);
+int launch_adamw_flat_seg_stats(void* p, const void* g, void* m, void* v, const sow_adamw_segment* segs, const int* seg_counter,
+                                int n_segs, double b1, double b2, float eps, const sow_grad_stats* stats, int skip_nonfinite,
+                                const int32_t* skip_counters, int n_counters, int dtype, int state_dtype, hipStream_t stream);
+// grad_stats.hip
+size_t grad_stats_workspace_bytes(int64_t n);
+int launch_grad_stats(const void* grad, int64_t n, int dtype, float grad_scale, float max_norm, const double* extra_sumsq,
+                      const float* loss_scale, const float* extra_found_inf, int32_t* skip_counters, int n_counters,
+                      void* workspace, size_t workspace_bytes, sow_grad_stats* out, hipStream_t stream);
 int launch_ttadam_dense(float* p, const float* g, float* m, float* v, int64_t n, double b1, double b2, float eps,
                         float step_size, float lr_wd, int clamp_v, hipStream_t stream);
 int launch_tt_kron_core(const float* A, const float* B, float* out, int ra0, int rb0, int ij, int ra1, int rb1,

@@ -200,6 +200,122 @@ int launch_adamw_flat_seg(void* p, const void* g, void* m, void* v, const sow_ad
 }
 
 // ---------------------------------------------------------------------------------------------
+// The segment AdamW driven by a device record (sow_grad_stats, written by grad_stats.hip on the same stream before this
+// launch): the gradient multiplier is stats->grad_mult instead of a host number, and with skip_nonfinite a record whose
+// nonfinite flag is set makes every workgroup return before it touches p, m or v.  A segment may name a skip counter
+// (device int32, the number of steps skipped so far, this one included): while it reads 0 -- or the segment names none --
+// the three scalars are the host's, exactly adamw_flat_seg_kernel's, so with grad_mult == grad_scale the results are its
+// bits; once it reads c > 0 one lane of the workgroup forms them for step max(1, step - c) in double from lr, weight_decay
+// and the betas and rounds each once, as the host does.  Nobody writes the counters while this kernel reads them.
+// ---------------------------------------------------------------------------------------------
+struct AdamwStatSeg {
+  int64_t begin, end;
+  float decay, step_size, bc2_sqrt;
+  int block0;   // first workgroup of this segment
+  float lr, weight_decay;
+  int step;
+  int counter;  // index into skip_counters, -1: none
+};
+struct AdamwStatSegTable {
+  AdamwStatSeg s[ADAMW_MAXSEG];
+  int n;
+};
+static_assert(sizeof(AdamwStatSegTable) + 6 * sizeof(void*) + 2 * sizeof(double) + 5 * sizeof(float) + sizeof(int) <= 4096,
+              "by-value kernel arguments must stay under 4 KiB");
+
+template <typename T, typename TS>
+__global__ __launch_bounds__(256) void adamw_flat_seg_stats_kernel(T* p, const T* g, TS* m, TS* v, const AdamwStatSegTable tb,
+                                                                   float b1, float c1, float b2, float c2, float eps,
+                                                                   double beta1, double beta2, const sow_grad_stats* stats,
+                                                                   const int32_t* skip_counters, int skip_nonfinite) {
+  if (skip_nonfinite && stats->nonfinite) return;   // uniform: the whole grid leaves
+  const float grad_scale = stats->grad_mult;
+  const int blk = blockIdx.x;
+  int si = 0;
+  while (si + 1 < tb.n && blk >= tb.s[si + 1].block0) ++si;   // uniform: scalar loads of the argument table
+  const AdamwStatSeg& S = tb.s[si];
+  const int nblk = (si + 1 < tb.n ? tb.s[si + 1].block0 : (int)gridDim.x) - S.block0;
+  float decay = S.decay, step_size = S.step_size, bc2_sqrt = S.bc2_sqrt;
+  const int skipped = S.counter >= 0 ? skip_counters[S.counter] : 0;
+  if (skipped > 0) {   // uniform over the workgroup (one segment, one counter): lane 0 forms the scalars (the double pow, sqrt and
+    // divide run in one wave of the four), LDS hands them on
+    __shared__ float corrected[3];
+    if (threadIdx.x == 0) {
+      const int eff = S.step - skipped > 1 ? S.step - skipped : 1;
+      const double bc1 = 1.0 - pow(beta1, (double)eff), bc2 = 1.0 - pow(beta2, (double)eff);
+      corrected[0] = (float)(1.0 - (double)S.lr * S.weight_decay), corrected[1] = (float)(S.lr / bc1), corrected[2] = (float)sqrt(bc2);
+    }
+    __syncthreads();
+    decay = corrected[0], step_size = corrected[1], bc2_sqrt = corrected[2];
+  }
+  const int64_t end = S.end, nth = (int64_t)nblk * blockDim.x;
+  for (int64_t i = S.begin + (int64_t)(blk - S.block0) * blockDim.x + threadIdx.x; i < end; i += nth) {
+    float pv = to_f32(p[i]);
+    const float gv = to_f32(g[i]) * grad_scale;
+    float mv = to_f32(m[i]), vv = to_f32(v[i]);
+    pv *= decay;
+    mv = b1 * mv + c1 * gv;
+    vv = b2 * vv + c2 * gv * gv;
+    const float denom = sqrtf(vv) / bc2_sqrt + eps;
+    pv -= step_size * (mv / denom);
+    p[i] = from_f32<T>(pv);
+    m[i] = from_f32<TS>(mv);
+    v[i] = from_f32<TS>(vv);
+  }
+}
+
+int launch_adamw_flat_seg_stats(void* p, const void* g, void* m, void* v, const sow_adamw_segment* segs, const int* seg_counter,
+                                int n_segs, double b1, double b2, float eps, const sow_grad_stats* stats, int skip_nonfinite,
+                                const int32_t* skip_counters, int n_counters, int dtype, int state_dtype, hipStream_t stream) {
+  if (n_segs < 0 || n_counters < 0) return SOW_ERR_SHAPE;
+  if (!stats) return SOW_ERR_NULL;
+  if (n_segs == 0) return SOW_OK;
+  if (!p || !g || !m || !v || !segs || (n_counters > 0 && !skip_counters)) return SOW_ERR_NULL;
+  const bool dt_ok = (dtype == SOW_F32 && state_dtype == SOW_F32) ||
+                     ((dtype == SOW_BF16 || dtype == SOW_F16) && (state_dtype == dtype || state_dtype == SOW_F32));
+  if (!dt_ok) return SOW_ERR_DTYPE;
+  // every segment is checked before the first launch, by the rules of launch_adamw_flat_seg; a counter index is -1 or a
+  // counter that exists
+  for (int i = 0; i < n_segs; ++i) {
+    if (segs[i].begin < 0 || segs[i].end <= segs[i].begin || segs[i].step < 1) return SOW_ERR_SHAPE;
+    if (i && segs[i].begin < segs[i - 1].end) return SOW_ERR_SHAPE;
+    if (seg_counter && (seg_counter[i] < -1 || seg_counter[i] >= n_counters)) return SOW_ERR_SHAPE;
+  }
+  const float b1f = (float)b1, c1 = (float)(1.0 - b1), b2f = (float)b2, c2 = (float)(1.0 - b2);
+  for (int off = 0; off < n_segs; off += ADAMW_MAXSEG) {
+    AdamwStatSegTable tb;
+    tb.n = n_segs - off < ADAMW_MAXSEG ? n_segs - off : ADAMW_MAXSEG;
+    int64_t want = 0;
+    for (int i = 0; i < tb.n; ++i) want += (segs[off + i].end - segs[off + i].begin + 255) / 256;
+    int grid = 0;
+    for (int i = 0; i < tb.n; ++i) {
+      const sow_adamw_segment& s = segs[off + i];
+      const double bc1 = 1.0 - std::pow(b1, (double)s.step), bc2 = 1.0 - std::pow(b2, (double)s.step);
+      AdamwStatSeg& d = tb.s[i];
+      d.begin = s.begin, d.end = s.end;
+      d.decay = (float)(1.0 - (double)s.lr * s.weight_decay), d.step_size = (float)(s.lr / bc1), d.bc2_sqrt = (float)std::sqrt(bc2);
+      d.block0 = grid;
+      d.lr = s.lr, d.weight_decay = s.weight_decay, d.step = s.step, d.counter = seg_counter ? seg_counter[off + i] : -1;
+      // the grid of launch_adamw_flat_seg: one workgroup per 256 elements, the launch capped at 2048 (shared in proportion)
+      int64_t nb = (s.end - s.begin + 255) / 256;
+      if (want > 2048) nb = nb * 2048 / want;
+      grid += nb < 1 ? 1 : (int)nb;
+    }
+    for (int i = tb.n; i < ADAMW_MAXSEG; ++i) tb.s[i] = AdamwStatSeg{0, 0, 1.f, 0.f, 1.f, grid, 0.f, 0.f, 1, -1};
+#define SOW_ADAMW_SEG_STATS(T, TS) \
+  hipLaunchKernelGGL((adamw_flat_seg_stats_kernel<T, TS>), dim3(grid), dim3(256), 0, stream, (T*)p, (const T*)g, (TS*)m, (TS*)v, tb, b1f, c1, b2f, c2, eps, b1, b2, stats, skip_counters, skip_nonfinite)
+    if (dtype == SOW_F32) SOW_ADAMW_SEG_STATS(float, float);
+    else if (dtype == SOW_BF16 && state_dtype == SOW_BF16) SOW_ADAMW_SEG_STATS(bf16_t, bf16_t);
+    else if (dtype == SOW_BF16) SOW_ADAMW_SEG_STATS(bf16_t, float);
+    else if (state_dtype == SOW_F16) SOW_ADAMW_SEG_STATS(f16_t, f16_t);
+    else SOW_ADAMW_SEG_STATS(f16_t, float);
+#undef SOW_ADAMW_SEG_STATS
+    SOW_CHECK_LAUNCH();
+  }
+  return SOW_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // TTAdam dense section (ttadam.py:84-111), fp32:  v<0 -> 0 clamp (only when clamp_v), then
 //   m = b1*m + (1-b1)*g ; v = b2*v + (1-b2)*g*g ; p += -step_size * m/(sqrt(v)+eps) ; p += -lr*wd*p
 // 1 - b is formed in double on the host from double betas (the Python-float alpha = 1.0 - beta of ttadam.py:91-92).

@@ -331,6 +331,17 @@ class FactorBucket:
                 s.pending = False
             self._sinks_pending.clear()
 
+    def grad_stats(self, **kwargs):
+        """Global statistics of the bucket's gradient on the device (ops.grad_stats_flat, same keywords): squared norm,
+        clip coefficient, gradient multiplier and non-finite flag, after finalize(), in two launches and without a host
+        read.  The sum runs over the whole flat buffer [0, padded_numel) and relies on the padding between slots being
+        ZERO: flat_grad is allocated zeroed, every parameter's .grad view ends at its numel, and the kernels write through
+        those views only -- code that writes flat_grad directly must keep the padding zero."""
+        from . import ops
+        ops._need_gpu(self.flat_grad)
+        self.finalize()
+        return ops.grad_stats_flat(self.flat_grad, **kwargs)
+
     def rebind(self) -> None:
         """Call after SoWLinear.accumulate(): `from_weights` rebinds .data to fresh tensors
         (reference sow.py:37-39); copy them back into the flat buffer and re-point the views."""

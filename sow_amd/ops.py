@@ -752,6 +752,112 @@ def adamw_flat_seg_(param: torch.Tensor, grad: torch.Tensor, exp_avg: torch.Tens
             betas[0], betas[1], eps, grad_scale, _dt(param), _dt(exp_avg))
 
 
+class GradStats:
+    """The 32-byte device record of ops.grad_stats_flat (include/sow_amd.h: sow_grad_stats).  Every property is a 0-dim
+    view of the record in device memory: reading one launches nothing and does not synchronise; `.item()` on it does.
+    sq_norm (float64): sum of g^2 of the flat buffer as stored; total_norm, clip_coef, grad_mult (float32) and nonfinite
+    (int32) as the header describes them.  grad_scale: the host multiplier the record was formed with (grad_scale /
+    loss_scale for a host loss_scale); counters: the skip-counter tensor its nonfinite flag was added to, or None."""
+
+    NBYTES = ctypes.sizeof(_lib.GradStatsRecord)
+
+    def __init__(self, buf: torch.Tensor, grad_scale: float = 1.0, counters: Optional[torch.Tensor] = None):
+        if buf.dtype != torch.uint8 or buf.numel() != self.NBYTES or not buf.is_contiguous():
+            raise ValueError("GradStats: the record is 32 contiguous bytes (torch.uint8)")
+        self.buf, self.grad_scale, self.counters = buf, float(grad_scale), counters
+
+    def _field(self, name: str, dtype) -> torch.Tensor:
+        f = getattr(_lib.GradStatsRecord, name)       # the field's place in the C struct
+        return self.buf[f.offset:f.offset + f.size].view(dtype).view(())
+
+    sq_norm = property(lambda self: self._field("sumsq", torch.float64))
+    total_sq = property(lambda self: self._field("total_sq", torch.float64))
+    total_norm = property(lambda self: self._field("total_norm", torch.float32))
+    clip_coef = property(lambda self: self._field("clip_coef", torch.float32))
+    grad_mult = property(lambda self: self._field("grad_mult", torch.float32))
+    nonfinite = property(lambda self: self._field("nonfinite", torch.int32))
+
+
+_GRAD_STATS_WS: dict = {}       # device -> workspace: one per device, sized for any n
+
+
+def _device_scalar(t, dtype, dev, what: str) -> Optional[torch.Tensor]:
+    """A 1-element device tensor of `dtype` from a tensor (converted on the device when its dtype differs) or a number."""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor):
+        return torch.full((1,), float(t), dtype=dtype, device=dev)
+    if t.numel() != 1:
+        raise ValueError(f"sow_amd.grad_stats_flat: {what} must have one element")
+    _need_gpu(t)
+    return t.reshape(1).to(dtype).contiguous()
+
+
+def grad_stats_flat(grad: torch.Tensor, *, grad_scale: float = 1.0, max_norm: Optional[float] = None, extra_sq_norm=None,
+                    loss_scale=None, found_inf=None, skip_counters: Optional[torch.Tensor] = None,
+                    out: Optional[GradStats] = None) -> GradStats:
+    """Global gradient statistics of one flat buffer, on the device (include/sow_amd.h: sow_grad_stats_flat): the squared
+    norm of `grad`, total_norm = sqrt(mult0^2 * sq_norm + extra_sq_norm) with mult0 = grad_scale / loss_scale, clip_coef =
+    min(1, max_norm / (total_norm + 1e-6)) (exactly 1 for max_norm None, 0 or inf), grad_mult = mult0 * clip_coef and the
+    nonfinite flag (total_norm not finite, or found_inf != 0).  Two launches on the current stream, no host read.
+    extra_sq_norm: the squared norm of gradients that live elsewhere (a device tensor; float64 is taken as it is);
+    loss_scale: a float (folded into grad_scale on the host) or a 1-element float32 device tensor; found_inf: a 1-element
+    float32 device tensor (torch.amp's convention: non-zero = overflow seen); skip_counters: an int32 device tensor, every
+    entry raised by the flag; out: a GradStats to write into (a fresh record otherwise).
+    The partial sums go through ONE cached workspace per device: calls on one stream are ordered by it, calls on two
+    streams of one device that may overlap race on that workspace -- order such streams with an event."""
+    lib = _lib.load()
+    dev = _need_gpu(grad, skip_counters, None if out is None else out.buf)
+    if not grad.is_contiguous():
+        raise ValueError("sow_amd.grad_stats_flat: the gradient buffer must be contiguous")
+    mult = float(grad_scale)
+    ls = None
+    if isinstance(loss_scale, torch.Tensor):
+        ls = _device_scalar(loss_scale, torch.float32, dev, "loss_scale")
+    elif loss_scale is not None:
+        mult = mult / float(loss_scale)
+    extra = _device_scalar(extra_sq_norm, torch.float64, dev, "extra_sq_norm")
+    finf = _device_scalar(found_inf, torch.float32, dev, "found_inf")
+    if skip_counters is not None and (skip_counters.dtype != torch.int32 or not skip_counters.is_contiguous()):
+        raise TypeError("sow_amd.grad_stats_flat: skip_counters must be a contiguous int32 tensor")
+    ws = _GRAD_STATS_WS.get(dev)
+    if ws is None:      # the query is monotone in n and capped: what it asks for the largest n serves every n
+        ws = _GRAD_STATS_WS[dev] = torch.empty(lib.sow_grad_stats_workspace_bytes(2 ** 62), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = GradStats(torch.empty(GradStats.NBYTES, dtype=torch.uint8, device=dev))
+    out.grad_scale, out.counters = mult, skip_counters
+    _launch(dev, "sow_grad_stats_flat", lib.sow_grad_stats_flat, _ptr(grad) if grad.numel() else None, grad.numel(), _dt(grad),
+            mult, 0.0 if max_norm is None else float(max_norm), _ptr(extra), _ptr(ls), _ptr(finf), _ptr(skip_counters),
+            0 if skip_counters is None else skip_counters.numel(), _ptr(ws), ws.numel(), _ptr(out.buf))
+    return out
+
+
+def adamw_flat_seg_stats_(param: torch.Tensor, grad: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, segments,
+                          stats: GradStats, *, betas=(0.9, 0.999), eps: float = 1e-8, seg_counter=None,
+                          skip_counters: Optional[torch.Tensor] = None, skip_nonfinite: bool = False) -> None:
+    """adamw_flat_seg_ with the gradient multiplier read from `stats` on the device (include/sow_amd.h:
+    sow_adamw_flat_seg_stats).  skip_nonfinite: a record whose nonfinite flag is set leaves param and both moments as they
+    are.  seg_counter: per segment an index into the int32 device tensor skip_counters (-1: none); a segment whose counter
+    reads c > 0 steps with the bias correction of step max(1, step - c)."""
+    lib = _lib.load()
+    dev = _need_gpu(param, grad, exp_avg, exp_avg_sq, stats.buf, skip_counters)
+    n = len(segments)
+    if not (param.numel() == grad.numel() == exp_avg.numel() == exp_avg_sq.numel()):
+        raise ValueError("sow_amd.adamw_flat_seg_stats_: the four buffers must have one length")
+    if any(int(e) > param.numel() for _, e, *_ in segments):
+        raise ValueError("sow_amd.adamw_flat_seg_stats_: a segment ends past the buffers")
+    if seg_counter is not None and len(seg_counter) != n:
+        raise ValueError("sow_amd.adamw_flat_seg_stats_: seg_counter needs one entry per segment")
+    if skip_counters is not None and (skip_counters.dtype != torch.int32 or not skip_counters.is_contiguous()):
+        raise TypeError("sow_amd.adamw_flat_seg_stats_: skip_counters must be a contiguous int32 tensor")
+    arr = (_lib.AdamwSegment * max(n, 1))(*[_lib.AdamwSegment(int(b), int(e), float(lr), float(wd), int(st))
+                                            for b, e, lr, wd, st in segments])
+    cnt = None if seg_counter is None else (ctypes.c_int * max(n, 1))(*[int(c) for c in seg_counter])
+    _launch(dev, "sow_adamw_flat_seg_stats", lib.sow_adamw_flat_seg_stats, _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq),
+            arr, cnt, n, betas[0], betas[1], eps, _ptr(stats.buf), int(bool(skip_nonfinite)), _ptr(skip_counters),
+            0 if skip_counters is None else skip_counters.numel(), _dt(param), _dt(exp_avg))
+
+
 def ttadam_dense_(param, grad, exp_avg, exp_avg_sq, *, beta1, beta2, eps, step_size, lr_times_wd, clamp_v: bool) -> None:
     lib = _lib.load()
     dev = _need_gpu(param, grad, exp_avg, exp_avg_sq)

@@ -199,7 +199,22 @@ class FactorAdamW:
     at lr without, run_glue.py:796-808.  betas and eps are shared; a group without "lr" / "weight_decay" takes the
     constructor's.  Each group has its own step count, reset_state(group_id) resets one group, and step() is still ONE
     launch (sow_adamw_flat_seg over the groups' segments of the flat buffer).  Without param_groups the object is the
-    one-group optimizer it has always been (sow_adamw_flat, the same state_dict keys)."""
+    one-group optimizer it has always been (sow_adamw_flat, the same state_dict keys).
+
+    Clipping and skipping without a host read: step(max_grad_norm=..., loss_scale=..., found_inf=..., skip_nonfinite=...)
+    takes the global norm of the flat gradient on the device (FactorBucket.grad_stats) and makes ONE
+    sow_adamw_flat_seg_stats launch that reads its gradient multiplier and its go / no-go flag from that record: the
+    gradient is neither rewritten nor rounded a second time, and the step can be captured in a HIP graph.  With
+    skip_nonfinite the optimizer owns one device int32 counter per param group (plus one for the whole optimizer when it
+    has groups) that counts the skipped steps; the host step counts advance as always and the kernel corrects the bias
+    for step - counter.  state_dict() reads the counters (the one host read), folds them into the step counts and zeroes
+    them, so a checkpoint holds true step counts under today's keys."""
+
+    # class-level defaults (an instance sets them when it first needs them)
+    last_grad_stats = None     # the GradStats of the last step() that took the device-record path
+    _armed_stats = None        # sow_amd.clip_grad_norm_: consumed by the next step()
+    _stats_out = None
+    _counters = None           # device int32 skip counters, created by the first skip_nonfinite use
 
     def __init__(self, bucket, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, state_dtype=None, param_groups=None):
         self.bucket = bucket
@@ -260,13 +275,107 @@ class FactorAdamW:
         return [(b, e, float(self._groups[gi]["lr"]), float(self._groups[gi]["weight_decay"]), self.group_steps[gi] + advance)
                 for gi, b, e in self._group_ranges()]
 
-    def step(self, grad_scale: float = 1.0):
-        self._sync_from_group()
-        self.bucket.finalize()   # pending deferred weight-gradient reductions (FactorBucket.attach)
+    @property
+    def skip_counters(self) -> torch.Tensor:
+        """The device int32 skip counters (created zeroed on first use): entry g counts the skipped steps of param group g
+        since its last reset; a grouped optimizer has one more, for step_count."""
+        if self._counters is None:
+            n = 1 if self._groups is None else len(self._groups) + 1
+            self._counters = torch.zeros(n, dtype=torch.int32, device=self.bucket.flat_param.device)
+        return self._counters
+
+    def _fold_counters(self) -> None:
+        """Read the skip counters (synchronises), take them off the host step counts and zero them."""
+        if self._counters is None:
+            return
+        c = [int(x) for x in self._counters.tolist()]
+        if any(c):
+            if self._groups is None:
+                self.step_count = max(0, self.step_count - c[0])
+            else:
+                self.group_steps = [max(0, s - k) for s, k in zip(self.group_steps, c)]
+                self.step_count = max(0, self.step_count - c[-1])
+            self._counters.zero_()
+
+    def arm_grad_stats(self, stats) -> None:
+        """Hand the next step() a record computed beforehand (sow_amd.clip_grad_norm_ does): that step() multiplies the
+        gradient by stats.grad_mult, whatever its own keywords say, and the one after it is an ordinary step again."""
+        self._armed_stats = stats
+
+    def _check_layout(self):
         for p, o in zip(self.bucket.params, self.bucket.offsets):
             if p.data_ptr() != self.bucket.flat_param.data_ptr() + o * self.bucket.flat_param.element_size():
                 raise RuntimeError("FactorAdamW.step: a factor no longer lives in the flat buffer (SoWLinear.accumulate() "
                                    "rebinds .data) -- call bucket.rebind() after accumulate(); sow_amd.accumulate(model) does")
+
+    def step(self, grad_scale: float = 1.0, *, max_grad_norm=None, extra_sq_norm=None, loss_scale=None, found_inf=None,
+             skip_nonfinite: bool = False, stats=None):
+        """One AdamW step of the whole bucket.  grad_scale: a host multiplier of the gradient (1 / world size after a sum
+        all-reduce).  With every keyword at its default (and nothing armed by clip_grad_norm_) this is the plain
+        sow_adamw_flat / sow_adamw_flat_seg launch and returns None.  Otherwise -- max_grad_norm: clip the global norm
+        (torch.nn.utils.clip_grad_norm_'s formula); extra_sq_norm: squared norm of gradients outside the bucket that count
+        towards it; loss_scale: divide the gradient by it (float or 1-element float32 device tensor); found_inf: a device
+        flag that marks the gradients as overflowed; skip_nonfinite: leave parameters and moments untouched when the norm is
+        not finite or found_inf is set; stats: a GradStats computed beforehand instead of computing one here (the record
+        holds its own scale, clipping and flag: giving max_grad_norm, extra_sq_norm, loss_scale, found_inf or another
+        grad_scale along with it, or with a record armed by clip_grad_norm_, raises).  Returns the GradStats, also kept as
+        last_grad_stats; nothing on this path reads device memory from the host.  Once skip_nonfinite has been used the
+        skip counters exist, and from then on every step() -- a plain one included -- takes this path and reads them, so
+        that the bias correction stays that of the effective step whatever form of step() follows a skipped one."""
+        armed, self._armed_stats = self._armed_stats, None
+        formed_here = {k: v for k, v in (("max_grad_norm", max_grad_norm), ("extra_sq_norm", extra_sq_norm),
+                                         ("loss_scale", loss_scale), ("found_inf", found_inf)) if v is not None}
+        if armed is None and stats is None and not formed_here and not skip_nonfinite and self._counters is None:
+            return self._step_plain(grad_scale)
+        if armed is not None:
+            if stats is not None and stats is not armed:
+                raise ValueError("FactorAdamW.step: stats= given while clip_grad_norm_ has armed another record")
+            stats = armed
+        if stats is not None:
+            # the record already holds its scale, its clipping and its flag: a keyword that says otherwise would be ignored
+            if float(grad_scale) not in (1.0, stats.grad_scale):
+                raise ValueError(f"FactorAdamW.step: grad_scale={grad_scale} but the record of this step was formed with "
+                                 f"{stats.grad_scale} -- pass the scale where the record is computed (clip_grad_norm_, "
+                                 "grad_stats) only")
+            if formed_here:
+                raise ValueError(f"FactorAdamW.step: {', '.join(formed_here)} given together with a record computed beforehand "
+                                 "-- pass them where the record is computed (clip_grad_norm_, grad_stats)")
+        from . import ops
+        ops._need_gpu(self.bucket.flat_param, self.bucket.flat_grad)
+        self._sync_from_group()
+        self.bucket.finalize()
+        self._check_layout()
+        if stats is None:
+            if self._stats_out is None:
+                self._stats_out = ops.GradStats(torch.empty(ops.GradStats.NBYTES, dtype=torch.uint8,
+                                                            device=self.bucket.flat_grad.device))
+            stats = self.bucket.grad_stats(grad_scale=grad_scale, max_norm=max_grad_norm, extra_sq_norm=extra_sq_norm,
+                                           loss_scale=loss_scale, found_inf=found_inf,
+                                           skip_counters=self.skip_counters if skip_nonfinite else None, out=self._stats_out)
+        elif skip_nonfinite and stats.counters is not self.skip_counters:
+            self.skip_counters.add_(stats.nonfinite)     # a record formed elsewhere: its flag is counted here, on the stream
+        # Once the counters exist every step reads them, whatever its keywords: the host step counts still hold the
+        # skipped steps until state_dict() folds them, and only the kernel can take them off without a host read.
+        counted = self._counters is not None
+        if self._groups is not None:
+            segs = self.segments()
+            cnt = [gi if counted else -1 for gi, _, _ in self._group_ranges()]
+            self.group_steps = [s + 1 for s in self.group_steps]
+            self.step_count += 1
+        else:
+            self.step_count += 1
+            segs = [(0, self.bucket.padded_numel, float(self.lr), float(self.weight_decay), self.step_count)]
+            cnt = [0 if counted else -1]
+        ops.adamw_flat_seg_stats_(self.bucket.flat_param, self.bucket.flat_grad, self.exp_avg, self.exp_avg_sq, segs, stats,
+                                  betas=self.betas, eps=self.eps, seg_counter=cnt, skip_counters=self._counters,
+                                  skip_nonfinite=skip_nonfinite)
+        self.last_grad_stats = stats
+        return stats
+
+    def _step_plain(self, grad_scale: float = 1.0):
+        self._sync_from_group()
+        self.bucket.finalize()   # pending deferred weight-gradient reductions (FactorBucket.attach)
+        self._check_layout()
         if self._groups is not None:
             segs = self.segments()
             ops.adamw_flat_seg_(self.bucket.flat_param, self.bucket.flat_grad, self.exp_avg, self.exp_avg_sq, segs,
@@ -284,7 +393,7 @@ class FactorAdamW:
         that param group only (its ranges of exp_avg and exp_avg_sq, ONE sow_zero_state call) and set its step to 0 --
         the reference resets the factor group and leaves the bias group's state and step alone."""
         if group_id is None:
-            ops.zero_([self.exp_avg, self.exp_avg_sq])
+            ops.zero_([self.exp_avg, self.exp_avg_sq] + ([self._counters] if self._counters is not None else []))
             self.step_count = 0
             if self._groups is not None:
                 self.group_steps = [0] * len(self._groups)
@@ -295,6 +404,8 @@ class FactorAdamW:
         for gi, b, e in self._group_ranges():
             if gi == int(group_id):
                 views += [self.exp_avg[b:e], self.exp_avg_sq[b:e]]
+        if self._counters is not None:     # the group's skipped steps go with its step count, in the same launch
+            views.append(self._counters[int(group_id):int(group_id) + 1])
         ops.zero_(views)
         self.group_steps[int(group_id)] = 0
 
@@ -320,6 +431,7 @@ class FactorAdamW:
 
     def state_dict(self):
         self._sync_from_group()
+        self._fold_counters()
         sd = {"step": self.step_count, "exp_avg": self.exp_avg.clone(), "exp_avg_sq": self.exp_avg_sq.clone(),
               "lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
               "numel": self.bucket.padded_numel}
@@ -335,6 +447,8 @@ class FactorAdamW:
         if self._groups is not None and "group_steps" in sd and len(sd["group_steps"]) != len(self._groups):
             raise ValueError("FactorAdamW.load_state_dict: the checkpoint has a different number of param groups")
         self.step_count = int(sd["step"])
+        if self._counters is not None:
+            self._counters.zero_()
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         self.lr, self.betas, self.eps, self.weight_decay = float(sd["lr"]), tuple(sd["betas"]), float(sd["eps"]), float(sd["weight_decay"])
@@ -351,3 +465,30 @@ class FactorAdamW:
                 self.group_steps = [self.step_count] * len(self._groups)
             for g in self._groups:
                 g["betas"], g["eps"] = self.betas, self.eps
+
+
+def clip_grad_norm_(factor_opt: FactorAdamW, other_parameters, max_norm: float, *, grad_scale: float = 1.0, loss_scale=None,
+                    found_inf=None) -> torch.Tensor:
+    """torch.nn.utils.clip_grad_norm_ (simple_train.py:631, the Trainer's max_grad_norm) for a model whose factors live in a
+    FactorBucket and whose other parameters are ordinary tensors: ONE global 2-norm over both, on the device.  The squared
+    norm of the other gradients is taken with torch (in float64) and enters the bucket's record as extra_sq_norm; the other gradients
+    are multiplied by the record's clip_coef in place (torch._foreach_mul_ with the device scalar); flat_grad is NOT
+    touched -- the record is armed on factor_opt and its next step() multiplies by grad_mult inside the AdamW kernel,
+    exactly once.  grad_scale and loss_scale apply to the bucket's gradient only (the other gradients are taken as they
+    are: unscale them first); the grad_scale given here is the one the armed step uses.  Returns total_norm, a 0-dim device
+    tensor; nothing synchronises."""
+    grads = [p.grad for p in ([other_parameters] if isinstance(other_parameters, torch.Tensor) else other_parameters)
+             if p.grad is not None]
+    bucket = factor_opt.bucket
+    from . import ops
+    ops._need_gpu(bucket.flat_grad, *grads)
+    extra = None
+    if grads:
+        extra = torch.stack(torch._foreach_norm(grads, 2.0, dtype=torch.float64)).square().sum()   # accumulated in double
+    st = bucket.grad_stats(grad_scale=grad_scale, max_norm=max_norm, extra_sq_norm=extra, loss_scale=loss_scale,
+                           found_inf=found_inf)
+    if grads:
+        torch._foreach_mul_(grads, st.clip_coef)
+    st.grad_scale = float(grad_scale)
+    factor_opt.arm_grad_stats(st)
+    return st.total_norm
