@@ -83,7 +83,8 @@ extern "C" {
  * then compute the SOW_ACC_LOWRANK term and the live term of a layer in one pass over the token rows (chain_wide_acc.hip)
  * instead of one chain launch per term.  It acts in sow_forward, in the SOW_BWD_DATA phase of sow_backward /
  * sow_backward_ex, in the per-layer fall-through of sow_forward_group / sow_backward_group, and in sow_workspace_bytes /
- * sow_forward_workspace_bytes; every other entry point that takes a dtype accepts the flag and ignores it.  It is a
+ * sow_forward_workspace_bytes, and it admits sibling sets with low-rank accumulators to the SOW_BWD_DATA phase of
+ * sow_backward_shared (see there); every other entry point that takes a dtype accepts the flag and ignores it.  It is a
  * permission, never a demand: a flagged call outside the admitted set runs exactly what the unflagged call runs and returns
  * what it returns (never SOW_ERR_UNSUPPORTED because of the flag).  Admitted:
  *   - compute dtype bf16 or f16 WITHOUT SOW_PARAM_F32 (with it the permission is ignored);
@@ -278,7 +279,35 @@ int sow_backward_group_plan(const sow_layer_args* layers, int n, int dtype, int 
  * inputs.  The weight phases in `phases` (BWD_WEIGHTS, _PARTIAL, _REDUCE, GROUP_SLABS) run exactly as sow_backward_group
  * runs them.  Admitted: bf16 or f16 (no SOW_PARAM_F32), SOW_ACC_NONE, r_live <= 64, T > 8192, the alignment of the
  * streaming kernels; anything else -- and everything while the NO_SHARED_X switch is on -- returns SOW_ERR_UNSUPPORTED,
- * and then nothing has been launched (the caller runs sow_forward_group / sow_backward_group instead). */
+ * and then nothing has been launched (the caller runs sow_forward_group / sow_backward_group instead).
+ *
+ * SOW_FUSE_ACC in the dtype of sow_backward_shared admits a second set to its SOW_BWD_DATA phase: siblings that ALL carry a
+ * low-rank accumulator (chain_shared_acc.hip: the fused chains of the siblings over one token block, their dX summed on
+ * chip; a factor pack launch and one kernel launch whatever n).  Tested where the set above is refused, after every check
+ * before it.  Admitted when all of these hold:
+ *   - compute dtype bf16 or f16, SOW_FUSE_ACC without SOW_PARAM_F32, n <= 4, T > 8192;
+ *   - every sibling SOW_ACC_LOWRANK (both factors given) in the admitted set of SOW_FUSE_ACC: even r_live in [2, 64], even
+ *     r_acc >= 2, r_acc + r_live <= 256, d_in and d_out multiples of 8;
+ *   - the LDS plan fits into 160 KiB: with r_pad_i = ceil64(r_acc_i + r_live_i),
+ *       128 * sum_i r_pad_i + max(128 * max_i r_pad_i + 8192, 24576) bytes
+ *     (three siblings of r_pad = 256 plan 136 KiB; the largest admitted set is r_pad = 256, 256, 256, 192: 15 panels of 64
+ *     columns, exactly 160 KiB; four of 256 do not fit; q / k / v at r_pad = 128 plan 72 KiB: two workgroups per CU);
+ *   - every dY_i, dX and every dh_i (the workspaces) 16-byte aligned;
+ *   - every sibling's workspace at least its FLAGGED sow_workspace_bytes;
+ *   - the NO_SHARED_X and NO_FUSED_ACC switches off.
+ * Any other set returns SOW_ERR_UNSUPPORTED with nothing launched and nothing written, as before: an unflagged dtype, a set
+ * mixed with SOW_ACC_NONE or dense siblings, a workspace between the unflagged and the flagged plan (the permission the
+ * caller cannot use: sow_backward_group runs it).  A workspace below the UNFLAGGED plan of an otherwise admitted set is
+ * SOW_ERR_WORKSPACE.  A call without SOW_BWD_DATA is unchanged.
+ * Contract (u = the compute dtype's rounding, products and sums in fp32):
+ *   dh_acc_i = rn(dY_i R_i^T), dh_live_i = rn(scale_i * dY_i B_i^T) = dh_i, written where and as the single fused pass writes
+ *   it ([T, 64], zeros above r_live, 1.0 in column 63 when r_live < 64): each dh_i the weight phases read is bit-identical
+ *   to a sow_backward_group call flagged with SOW_FUSE_ACC on the same inputs, and so are dA, dB and dbias from it;
+ *   dX = rn(grad_beta * dX + sum_i (dh_acc_i Q_i^T + dh_live_i A_i^T)): ONE fp32 accumulation -- sibling 0's columns in
+ *   ascending order, then sibling 1's, ... -- and ONE rounding.  No atomics: a repeated call gives the same bits.
+ * sow_forward_shared keeps refusing low-rank sets, flagged or not: the shared forward measured no gain even without an
+ * accumulator (q + k + v 43.2 against 42.4 us grouped), and a phase 1 over the siblings' sum_i r_pad_i columns side by side
+ * -- what reading x once would take -- has no room in the register file (r_pad = 256 of ONE sibling fills the accumulators). */
 int sow_forward_shared(const sow_layer_args* layers, int n, int dtype, void* stream);
 int sow_backward_shared(const sow_layer_args* layers, int n, int dtype, int phases, void* stream);
 

@@ -84,7 +84,7 @@ static inline bool ok_dtype(int d) { return d == SOW_F32 || d == SOW_BF16 || d =
 static inline bool al4p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 static inline bool al16p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // The dtype argument of an entry point, decoded once.  SOW_FUSE_ACC is a permission and is ignored together with SOW_PARAM_F32.
-// The layer entry points, their plans and descriptors take what layer_ok() admits; sow_*_shared refuses a flagged dtype as
+// The layer entry points, their plans and descriptors take what layer_ok() admits; sow_*_shared refuses SOW_PARAM_F32 as
 // unsupported after its own checks.  The entry points outside the layer surface (GEMM, QR, accumulate, optimizer, copies)
 // only strip the permission with nofuse() and refuse or reject SOW_PARAM_F32 themselves, each with its own code.
 struct Dtype {
@@ -514,6 +514,15 @@ static int gemm_pair(const DirView& v, const Factors& f, void* h, const void* bi
   return launch_gemm(h, f.r, false, f.F2, f.ld2, v.bwd, v.Y, v.D2, bias, v.M, v.D2, f.r, v.bwd ? 1.f : scale, beta, c.dtype,
                      c.stream);
 }
+// the operands of a fused low-rank-accumulator chain: one layer and direction, the factor pack in the flagged plan wf of ws
+static WideAccArgs wide_acc_args(const DirView& v, char* ws, const WsPlan& wf) {
+  WideAccArgs a{};
+  a.X = v.X, a.Y = v.Y, a.Fa1 = v.acc.F1, a.Fl1 = v.live.F1, a.Fa2 = v.acc.F2, a.Fl2 = v.live.F2;
+  a.ldfa1 = v.acc.ld1, a.ldfl1 = v.live.ld1, a.ldfa2 = v.acc.ld2, a.ldfl2 = v.live.ld2;
+  a.Hsave = v.H, a.bias = v.bias, a.M = v.M, a.D1 = v.D1, a.D2 = v.D2, a.r_acc = v.acc.r, a.r_live = v.live.r;
+  a.scale = v.scale, a.bwd = v.bwd ? 1 : 0, a.pack = ws + wf.off_wide, a.pack_bytes = wf.wide_bytes;
+  return a;
+}
 // SOW_FUSE_ACC on an admitted call: the accumulator term and the live term of one direction as one chain
 // (chain_wide_acc.hip), Y written once, H left as the two-pass path leaves it (the weight phases are the unflagged ones).
 // SOW_ERR_UNSUPPORTED: nothing launched, the caller goes on with the unflagged path, unchanged.  The data gradient has no
@@ -522,12 +531,37 @@ static int fused_acc_pass(const sow_layer_args& L, const DirView& v, const Layer
   if (sw_on(SW_NO_FUSED_ACC) || !c.ws || !al16p(v.X) || !al16p(v.Y) || !al16p(v.bias) || !al16p(v.H)) return SOW_ERR_UNSUPPORTED;
   const WsPlan wf = plan_of(L, c.dtype, true);
   if (!wf.fused || c.bytes < wf.total + 255) return SOW_ERR_UNSUPPORTED;
-  WideAccArgs a{};
-  a.X = v.X, a.Y = v.Y, a.Fa1 = v.acc.F1, a.Fl1 = v.live.F1, a.Fa2 = v.acc.F2, a.Fl2 = v.live.F2;
-  a.ldfa1 = v.acc.ld1, a.ldfl1 = v.live.ld1, a.ldfa2 = v.acc.ld2, a.ldfl2 = v.live.ld2;
-  a.Hsave = v.H, a.bias = v.bias, a.M = v.M, a.D1 = v.D1, a.D2 = v.D2, a.r_acc = v.acc.r, a.r_live = v.live.r;
-  a.scale = v.scale, a.bwd = v.bwd ? 1 : 0, a.pack = c.ws + wf.off_wide, a.pack_bytes = wf.wide_bytes;
-  return launch_chain_wide_acc(a, c.dtype, c.stream);
+  return launch_chain_wide_acc(wide_acc_args(v, c.ws, wf), c.dtype, c.stream);
+}
+// The shared-input data gradient of siblings that all carry a low-rank accumulator (chain_shared_acc.hip): the admitted set
+// of sow_backward_shared under SOW_FUSE_ACC (include/sow_amd.h).  `layers`: checked, one x, T, d_in and dx (shared_common,
+// shared_fill_dx).  SOW_ERR_UNSUPPORTED and SOW_ERR_WORKSPACE: nothing launched, nothing written.
+static int shared_fused_acc_data(const sow_layer_args* layers, int n, const Dtype& f, hipStream_t stream) {
+  const int cd = f.cd;
+  if (!f.fuse || (cd != SOW_BF16 && cd != SOW_F16) || sw_on(SW_NO_FUSED_ACC) || n > 4) return SOW_ERR_UNSUPPORTED;
+  if (ceil_div(layers[0].T, 64) <= SHORT_NTB) return SOW_ERR_UNSUPPORTED;   // the streaming shared kernel's threshold
+  int r_tot[4];
+  for (int i = 0; i < n; ++i) {
+    const sow_layer_args& L = layers[i];
+    if (L.acc_kind != SOW_ACC_LOWRANK || !L.acc_up || !fused_acc_shape_ok(L.r_live, L.r_acc, L.d_in, L.d_out, cd))
+      return SOW_ERR_UNSUPPORTED;
+    r_tot[i] = L.r_acc + L.r_live;
+  }
+  if (!shared_acc_lds_ok(r_tot, n) || !al16p(layers[0].dx)) return SOW_ERR_UNSUPPORTED;
+  for (int i = 0; i < n; ++i)
+    if (!al16p(layers[i].dy)) return SOW_ERR_UNSUPPORTED;
+  // below the unflagged plan no path runs the layer; between the two plans the grouped path does (the flag is a permission)
+  for (int i = 0; i < n; ++i)
+    if (layers[i].workspace_bytes < plan_of(layers[i], cd).total + 255) return SOW_ERR_WORKSPACE;
+  WideAccArgs sib[4];
+  for (int i = 0; i < n; ++i) {
+    const sow_layer_args& L = layers[i];
+    const WsPlan wf = plan_of(L, cd, true);
+    if (!wf.fused || L.workspace_bytes < wf.total + 255) return SOW_ERR_UNSUPPORTED;
+    char* ws = ws_base(L.workspace);
+    sib[i] = wide_acc_args(dir_view(L, true, ws + wf.off_dh), ws, wf);
+  }
+  return launch_chain_shared_acc(sib, n, layers[0].dx, layers[0].grad_beta, cd, stream);
 }
 
 // Dense accumulator, r_live <= 64: the product with the live term as a K-extension,  Y = [X, H] . [op(W); F2] + bias,
@@ -1213,6 +1247,8 @@ int sow_backward_group(const sow_layer_args* layers, int n, int dtype, int phase
 // group_chain_params takes layer by layer (bf16 / f16, no accumulator, r_live <= 64, T > 8192, chain2 alignment) with one x
 // pointer and one d_in; anything else returns SOW_ERR_UNSUPPORTED before anything is launched.  SOW_PARAM_F32 is not
 // admitted either, but only after the checks before it: a flagged fp32 dtype gets that far too.
+// The data gradient also admits, under SOW_FUSE_ACC, siblings that ALL carry a low-rank accumulator (shared_fused_acc_data,
+// chain_shared_acc.hip); the forward does not: a side-by-side phase 1 over the siblings' columns has no room in the registers.
 static int shared_common(const sow_layer_args* layers, int n, bool bwd) {
   if (n <= 0) return SOW_ERR_SHAPE;
   if (!layers) return SOW_ERR_NULL;
@@ -1257,14 +1293,20 @@ int sow_backward_shared(const sow_layer_args* layers, int n, int dtype, int phas
     if ((rc = check_layer(filled[i], true, false))) return rc;
   if (sw_on(SW_NO_SHARED_X) || filled[0].T == 0) return SOW_ERR_UNSUPPORTED;
   ChainParams ps[C2_MAXG];
+  bool streaming = true;
   for (int i = 0; i < n; ++i) {
     const sow_layer_args& L = filled[i];
     const WsPlan w = plan_of(L, cd);
-    if (!group_chain_params(L, true, cd, w, &ps[i])) return SOW_ERR_UNSUPPORTED;
+    if (!group_chain_params(L, true, cd, w, &ps[i])) {
+      // not the streaming set: siblings that all carry a low-rank accumulator, under SOW_FUSE_ACC, or nothing
+      if ((rc = shared_fused_acc_data(filled, n, f, stream))) return rc;
+      streaming = false;
+      break;
+    }
     if (L.workspace_bytes < w.total + 255) return SOW_ERR_WORKSPACE;
     ps[i].beta = filled[0].grad_beta;   // dX = grad_beta * dX + sum_i dh_i A_i^T
   }
-  if ((rc = launch_chain2_shared(ps, n, true, cd, stream))) return rc;
+  if (streaming && (rc = launch_chain2_shared(ps, n, true, cd, stream))) return rc;
   // the weight phases read each layer's dh where the grouped data phase leaves it: exactly sow_backward_group's code
   const int wph = phases & ~SOW_BWD_DATA;
   return decode_phases(wph).weights() ? backward_group_impl(filled, n, cd, cd, wph, false, stream) : SOW_OK;

@@ -27,40 +27,9 @@
 
 namespace sow {
 
-struct WideAccPack {
-  const void *Fa, *Fl;   // accumulator and live source of this image
-  int64_t lda, ldl;
-  int trans;             // source element (rank k, width index j) = trans ? F[j][k] : F[k][j]
-};
-struct WideAccPackParams {
-  WideAccPack img[2];    // 0: F1T [r_pad][d1p], 1: F2T [D2][r_pad]
-  void *f1t, *f2t;
-  int r_acc, r_tot, r_pad, D1, d1p, D2;
-  int64_t n0, n;         // elements of image 0, of both
-};
-
 template <typename T> __global__ __launch_bounds__(256) void wide_acc_pack_kernel(const WideAccPackParams p) {
-  int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= p.n) return;
-  const int which = i >= p.n0 ? 1 : 0;
-  int k, j, D;   // rank index, width index, valid width
-  T* dst;
-  if (!which) {
-    k = (int)(i / p.d1p), j = (int)(i % p.d1p), D = p.D1, dst = (T*)p.f1t + i;
-  } else {
-    i -= p.n0;
-    j = (int)(i / p.r_pad), k = (int)(i % p.r_pad), D = p.D2, dst = (T*)p.f2t + i;
-  }
-  const WideAccPack& J = p.img[which];
-  T v = from_f32<T>(0.f);
-  if (k < p.r_tot && j < D) {
-    const bool live = k >= p.r_acc;
-    const T* src = (const T*)(live ? J.Fl : J.Fa);
-    const int64_t ld = live ? J.ldl : J.lda;
-    const int kk = live ? k - p.r_acc : k;
-    v = J.trans ? src[(int64_t)j * ld + kk] : src[(int64_t)kk * ld + j];
-  }
-  *dst = v;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < p.n) wide_acc_pack_elem<T>(p, i);
 }
 
 struct WideAccParams {
@@ -141,17 +110,8 @@ int launch_chain_wide_acc(const WideAccArgs& a, int dtype, hipStream_t stream) {
   if (a.M <= 0) return SOW_OK;
   if (ceil_div(a.M, 64) > 0x7fffffff) return SOW_ERR_SHAPE;
   const int r_tot = a.r_acc + a.r_live, r_pad = (r_tot + 63) / 64 * 64;
-  char* f1t = (char*)a.pack;
-  char* f2t = f1t + (((size_t)r_pad * a.D1 * 2 + 255) & ~(size_t)255);
-  WideAccPackParams pk{};
-  // forward: F1 = [Q | A] stored [D1][r] (transposed on the way in), F2 = [R ; B] stored [r][D2];
-  // data gradient: F1 = [R^T | B^T], R / B stored [r][D1] (as stored), F2 = [Q^T ; A^T], Q / A stored [D2][r]
-  pk.img[0] = WideAccPack{a.Fa1, a.Fl1, a.ldfa1, a.ldfl1, a.bwd ? 0 : 1};
-  pk.img[1] = WideAccPack{a.Fa2, a.Fl2, a.ldfa2, a.ldfl2, a.bwd ? 1 : 0};
-  pk.f1t = f1t, pk.f2t = f2t;
-  pk.r_acc = a.r_acc, pk.r_tot = r_tot, pk.r_pad = r_pad, pk.D1 = a.D1, pk.d1p = a.D1, pk.D2 = a.D2;
-  pk.n0 = (int64_t)r_pad * a.D1;
-  pk.n = pk.n0 + (int64_t)a.D2 * r_pad;
+  const WideAccPackParams pk = wide_acc_pack_params(a);
+  void *f1t = pk.f1t, *f2t = pk.f2t;
   WideAccParams p{};
   p.X = a.X, p.Y = a.Y, p.F1T = f1t, p.F2T = f2t, p.Hsave = a.Hsave, p.bias = a.bias;
   p.M = a.M, p.D1 = a.D1, p.D2 = a.D2, p.r_acc = a.r_acc, p.r_live = a.r_live, p.r_pad = r_pad;

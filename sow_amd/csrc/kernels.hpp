@@ -195,6 +195,16 @@ bool fused_acc_shape_ok(int r_live, int r_acc, int d_in, int d_out, int dtype);
 // SOW_ERR_UNSUPPORTED when the shape, the alignment (X, Y, bias, Hsave, pack: 16 bytes) or the scratch does not suit the
 // kernel (nothing launched)
 int launch_chain_wide_acc(const WideAccArgs& a, int dtype, hipStream_t stream);
+// chain_shared_acc.hip (bf16 / f16): the data gradients of n <= 4 sibling layers with low-rank accumulators on one input,
+// summed on chip:  dh_i as launch_chain_wide_acc(bwd = 1) leaves it,  dX = rn(beta dX + sum_i h_i . [Q_i^T ; A_i^T]).
+// sib[i]: the sibling's operands as for launch_chain_wide_acc with bwd = 1 (X = dY_i, Hsave = dh_i, its own pack region; Y
+// and bias are not read); one M and one D2 = d_in for the set.  Two launches whatever n.
+// The LDS plan of a set, from r_tot[i] = r_acc_i + r_live_i: its bytes (0: n out of range), and whether it fits (160 KiB)
+size_t shared_acc_lds_bytes(const int* r_tot, int n);
+bool shared_acc_lds_ok(const int* r_tot, int n);
+// SOW_ERR_UNSUPPORTED when a shape, the LDS plan, an alignment (dY_i, dh_i, pack, dX: 16 bytes) or the scratch does not suit
+// the kernel (nothing launched)
+int launch_chain_shared_acc(const WideAccArgs* sib, int n, void* dX, float beta, int dtype, hipStream_t stream);
 // skinny_tn_wide.hip: weight gradients of a wide-rank layer, token-slab partials + fixed-order reduction
 struct TnwParams {
   const void* M[2];     // x [T, d_in], dY [T, d_out]

@@ -18,6 +18,16 @@ to the grouped path; the input gradient rounds differently (once instead of per 
 the grouped launch: the shared-input forward (sow_forward_shared, ops.SharedInputGroup) moves fewer bytes but measures
 no faster on the llama_60m shapes (q + k + v 43.2 against 42.4 us).  A set the fused kernels do not admit runs the grouped
 path unchanged.
+
+Siblings that all carry a LOW-RANK accumulator -- the state of a from-scratch pretraining run between its first accumulate()
+and the dense accumulator -- take the shared data gradient too, where their calls hold the SOW_FUSE_ACC permission
+(ops.fuse_acc_default: at least 32768 tokens, widths up to 1376) and the library admits the set (ops.shared_fused_acc_admits):
+ONE kernel runs every sibling's fused accumulator + live chain over a token block and sums the input gradients on chip
+(chain_shared_acc.hip), dX = rn(sum_i (rn(dY_i R_i^T) Q_i^T + rn(s_i dY_i B_i^T) A_i^T)) with one rounding, instead of one
+fused pass per sibling and the adds of _input_grad.  Measured at T = 32768, r = 50 (profiles/shared_fused_acc.txt): q + k + v
+at r_acc = 50 128 -> 80 us, gate + up at r_acc = 50 / 100 123 -> 97 / 137 -> 114 us.  Sets whose LDS plan allows only one
+workgroup per CU measured SLOWER (q + k + v at r_acc = 100 / 200: 1.12 / 1.18 of the grouped path, gate + up at 200: 1.36)
+and keep the grouped path (ops.shared_fused_acc_pays).  The forward of such sets is the grouped launch, as for every set.
 """
 from __future__ import annotations
 
@@ -126,7 +136,7 @@ class _SoWGroupFunction(torch.autograd.Function):
         dx = None
         if ctx.shared:
             shared_dx = torch.empty_like(x2)
-            if ops.SharedInputGroup(make_calls([shared_dx] * n)).backward(_lib.BWD_DATA | _lib.BWD_WEIGHTS):
+            if ops.SharedInputGroup(make_calls([shared_dx] * n), measured_only=True).backward(_lib.BWD_DATA | _lib.BWD_WEIGHTS):
                 dx = _SoWGroupFunction._cast_input_grad(ctx, shared_dx)
         if dx is None:
             calls = make_calls([torch.empty_like(x2) for _ in range(n)])
@@ -143,7 +153,7 @@ class _SoWGroupFunction(torch.autograd.Function):
         if not ctx.shared:
             return None
         dx = torch.empty_like(x2)
-        if not ops.SharedInputGroup(data_calls([dx] * n, 0.0)).backward(_lib.BWD_DATA):
+        if not ops.SharedInputGroup(data_calls([dx] * n, 0.0), measured_only=True).backward(_lib.BWD_DATA):
             return None
         return _SoWGroupFunction._cast_input_grad(ctx, dx)
 

@@ -189,6 +189,56 @@ def fuse_acc_default(T: int, d_in: int, d_out: int, r: int, r_acc: int, kind: in
     return fused_acc_admits(d_in, d_out, r, r_acc, kind, dtype, param_f32) and fused_acc_pays(T, d_in, d_out, r, r_acc)
 
 
+SHARED_FUSED_ACC_MIN_T = 8193          # more than 8192 tokens: the threshold of the streaming shared-input kernel
+SHARED_FUSED_ACC_MAX_N = 4
+SHARED_FUSED_ACC_MAX_LDS = 160 * 1024   # bytes of LDS a workgroup of chain_shared_acc.hip may plan
+
+
+def shared_fused_acc_lds_bytes(r_tots: Sequence[int]) -> int:
+    """The LDS plan of chain_shared_acc.hip for siblings of r_acc + r = r_tots: the H panels of every sibling (r_pad x 128
+    bytes each, r_pad = ceil64(r_acc + r)) and the stage -- the widest sibling's packed-factor image with the 8 KiB input
+    image in phase 1, at least 24 KiB (F2 panel groups, epilogue scratch) in phase 2."""
+    r_pads = [(rt + 63) // 64 * 64 for rt in r_tots]
+    return sum(rp * 128 for rp in r_pads) + max(max(r_pads) * 128 + 8192, 24576)
+
+
+def shared_fused_acc_admits(T: int, d_in: int, layers: Sequence[Tuple[int, int, int, int]], dtype: torch.dtype,
+                            param_f32: bool = False) -> bool:
+    """The set sow_backward_shared admits under SOW_FUSE_ACC (include/sow_amd.h): `layers` = (d_out, r, r_acc, kind) of at
+    most four siblings on one [T, d_in] input with T > 8192, EVERY one a low-rank-accumulator layer of the SOW_FUSE_ACC set
+    (fused_acc_admits), whose LDS plan fits (three siblings of r_acc + r <= 256 always do, four of more than 192 do not).
+    The call-time conditions (the flag in the dtype, 16-byte-aligned tensors, flagged workspaces, the NO_SHARED_X and
+    NO_FUSED_ACC switches off) are not part of it."""
+    if not 1 <= len(layers) <= SHARED_FUSED_ACC_MAX_N or T < SHARED_FUSED_ACC_MIN_T:
+        return False
+    if not all(fused_acc_admits(d_in, d_out, r, r_acc, kind, dtype, param_f32) for d_out, r, r_acc, kind in layers):
+        return False
+    return shared_fused_acc_lds_bytes([r + r_acc for _, r, r_acc, _ in layers]) <= SHARED_FUSED_ACC_MAX_LDS
+
+
+SHARED_FUSED_ACC_PAYS_LDS = 80 * 1024   # the largest LDS plan at which two workgroups share a CU (160 KiB)
+
+
+def shared_fused_acc_pays(r_tots: Sequence[int]) -> bool:
+    """The measured dispatch rule of the module surface for the shared-input data gradient of low-rank-accumulator siblings
+    (profiles/shared_fused_acc.txt): the sets whose LDS plan (shared_fused_acc_lds_bytes of the
+    siblings' r_acc + r) leaves room for TWO workgroups per CU.
+
+    Measured (bf16, T = 32768, r = 50; us per backward data pass, grouped path with the module surface's dX adds -> shared
+    kernel, +- = spread of the window medians, LDS plan):
+        q+k+v   3 x 512->512,  r_acc =  50 (r_pad 128,  72 KiB): 128.3 +- 7.0 ->  79.8   0.62   pays
+        q+k+v   3 x 512->512,  r_acc = 100 (r_pad 192, 104 KiB): 141.6 +- 4.4 -> 159.0   1.12   loses
+        q+k+v   3 x 512->512,  r_acc = 200 (r_pad 256, 136 KiB): 156.7 +- 6.8 -> 185.3   1.18   loses
+        gate+up 2 x 512->1376, r_acc =  50 (r_pad 128,  56 KiB): 123.4 +- 6.3 ->  97.1   0.79   pays
+        gate+up 2 x 512->1376, r_acc = 100 (r_pad 192,  80 KiB): 137.4 +- 8.9 -> 114.2   0.83   pays
+        gate+up 2 x 512->1376, r_acc = 200 (r_pad 256, 104 KiB): 160.6 +- 5.7 -> 218.0   1.36   loses
+    Every row at two workgroups per CU (plan <= 80 KiB) beats the grouped path by more than its spread; every row at one
+    4-wave workgroup per CU loses to it: with nothing else resident the barriers of the 64-token tile code leave the CU idle.
+    Those sets keep the grouped path.  NOT measured: r_pad = 64 sets (they plan at most 56 KiB: the paying class), f16, other
+    widths."""
+    return shared_fused_acc_lds_bytes(r_tots) <= SHARED_FUSED_ACC_PAYS_LDS
+
+
 def sow_forward(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, acc_up, bias, scale: float,
                 save_h: bool = True, *, param_f32: bool = False, fuse_acc: bool = False):
     """y, h_save = forward of the SoW contraction on a flattened [T, d_in] input.  save_h = False (no-grad / eval callers,
@@ -523,14 +573,25 @@ class SharedInputGroup(LayerGroup):
     reads x once for all of them, the data gradient is ONE dX -- the fp32 sum over the siblings rounded once, written to
     the first call's dx with its grad_beta (the other calls' dx are not written).  y, h and the weight gradients are
     bit-identical to LayerGroup.  forward() / backward() return False when the set is not admitted (the C ABI returned
-    SOW_ERR_UNSUPPORTED and launched nothing); the caller then runs LayerGroup."""
+    SOW_ERR_UNSUPPORTED and launched nothing); the caller then runs LayerGroup.
 
-    def __init__(self, calls: Sequence[LayerCall]):
+    Admitted: layers without accumulator (bf16 / f16, r <= 64, more than 8192 tokens), in both directions; and, in
+    backward() only, siblings that ALL carry a low-rank accumulator when every call holds the SOW_FUSE_ACC permission
+    (LayerCall(fuse_acc=True): the group's dtype then carries the flag) and shared_fused_acc_admits() holds: dX =
+    rn(grad_beta dX + sum_i (rn(dY_i R_i^T) Q_i^T + rn(s_i dY_i B_i^T) A_i^T)), one rounding; dh and the weight gradients
+    bit-identical to the flagged LayerGroup.  measured_only=True (the module surface) keeps such a set on LayerGroup --
+    backward() returns False without a call -- where the shared kernel measured slower (shared_fused_acc_pays)."""
+
+    _skip_data = False
+
+    def __init__(self, calls: Sequence[LayerCall], measured_only: bool = False):
         super().__init__(calls)
         if len({c.args.x for c in self.calls}) != 1:
             raise ValueError("sow_amd.SharedInputGroup: every call must read the same x")
         for i in range(1, len(calls)):   # one dX for the set: the other calls' dx are not written
             self.arr[i].dx = self.arr[0].dx
+        self._skip_data = (measured_only and all(c.kind == _lib.ACC_LOWRANK for c in self.calls)
+                           and not shared_fused_acc_pays([c.args.r_live + c.args.r_acc for c in self.calls]))
 
     def _run(self, what: str, fn, *args) -> bool:
         rc = _launch_rc(self.device, fn, self.arr, len(self.calls), self.dtype, *args)
@@ -543,6 +604,8 @@ class SharedInputGroup(LayerGroup):
         return self._run("sow_forward_shared", _lib.load().sow_forward_shared)
 
     def backward(self, phases: int = _lib.BWD_DATA | _lib.BWD_WEIGHTS) -> bool:
+        if self._skip_data and int(phases) & _lib.BWD_DATA:
+            return False
         return self._run("sow_backward_shared", _lib.load().sow_backward_shared, int(phases))
 
 
