@@ -102,6 +102,24 @@ extern "C" {
  * weight-gradient phases are the unflagged ones; they read h_save and dh as written here. */
 #define SOW_FUSE_ACC 0x200
 
+/* The same permission for low-rank accumulators past the 256 columns of SOW_FUSE_ACC: a second bit, OR-ed into the dtype next
+ * to it (a caller may pass both; the two admitted sets are disjoint by r_acc + r_live, and SOW_FUSE_ACC keeps its set and its
+ * workspace plan whatever this bit says).  The library MAY then run the SOW_ACC_LOWRANK term and the live term in one pass
+ * whose H columns are computed in groups of 256 and kept on chip (chain_deep_acc.hip), instead of two generic GEMM launches
+ * through a [T, r_acc] intermediate followed by the live chain with beta = 1.  It acts in sow_forward, in the SOW_BWD_DATA
+ * phase of sow_backward / sow_backward_ex, in the per-layer fall-through of sow_forward_group / sow_backward_group and in
+ * sow_workspace_bytes / sow_forward_workspace_bytes; every other entry point that takes a dtype, sow_forward_shared and
+ * sow_backward_shared included, accepts the bit and ignores it.  A permission, never a demand, as SOW_FUSE_ACC.  Admitted:
+ *   - compute dtype bf16 or f16 WITHOUT SOW_PARAM_F32 (with it the permission is ignored);
+ *   - SOW_ACC_LOWRANK with both factors, even r_live in [2, 64], even r_acc, 256 < r_acc + r_live <= 960 (160 KiB of LDS:
+ *     128 bytes per column of ceil64(r_acc + r_live) and a 40 KiB stage), d_in and d_out multiples of 8;
+ *   - at call time: 16-byte-aligned x / y / dY / dX / bias / h_save, a workspace of at least the FLAGGED query (the unflagged
+ *     plan, the [T, r_acc] scratch of the generic path included, with a factor-pack region for r_acc + r_live columns: it also
+ *     serves the unflagged call), and the NO_DEEP_ACC switch off.  The queries do not depend on the switch.
+ * Rounding contract, results (h_save, dh, y, dX) and the weight-gradient phases: those of SOW_FUSE_ACC above -- the bias is
+ * added in fp32 before the one rounding of y. */
+#define SOW_FUSE_ACC_DEEP 0x400
+
 #define SOW_OK 0
 #define SOW_ERR_NULL (-1)
 #define SOW_ERR_SHAPE (-2)
@@ -124,7 +142,7 @@ const char* sow_error_string(int code);
  * never touches them.  They are the library's ONLY process-wide state: a table of atomics initialised from the
  * environment (SOW_AMD_<NAME>) once, at first use; no launch path calls getenv.  Names: FORCE_CHAIN_V1, NO_SHORT_SPLIT,
  * NO_FUSED_H, FORCE_GEMM_V1, TN_NARROW, NO_GEMM3S, NO_GROUPED, NO_PERSIST, NO_NT_STORE, NT_LOAD, NO_PAIR_FLUSH, F32_EXACT, NO_PARK16, TN_NO_NT_LOAD, NO_TN_ROWS, NO_GEMM4H, NO_CHAIN3F, NO_TN_F32Q, NO_SPLITK,
- * NO_WIDE_CHAIN, NO_SHARED_X, NO_RAGGED, NO_RAGGED_GEMM, NO_BLOCKED_QR, NO_SKINNY, NO_H_ROWS, NO_FUSED_ACC
+ * NO_WIDE_CHAIN, NO_SHARED_X, NO_RAGGED, NO_RAGGED_GEMM, NO_BLOCKED_QR, NO_SKINNY, NO_H_ROWS, NO_FUSED_ACC, NO_DEEP_ACC
  * (value 1 = on, -1 / 0 = off), NO_ROW_ALIGN (1 = on, 2 = on for the X stages only, 3 = on for the Y slices only; it keeps
  * and returns that value) and GEMM3S, GEMM3, GEMM4
  * (1 = force, 0 = forbid, -1 = automatic).  sow_set_switch returns SOW_ERR_UNSUPPORTED for an unknown name;

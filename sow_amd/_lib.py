@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("SOW_AMD_LIB") or os.path.join(_HERE, "lib", "libsow_a
 F32, BF16, F16 = 0, 1, 2
 PARAM_F32 = 0x100        # OR-ed into BF16 / F16: fp32 parameters, fp32 weight gradients (mixed precision)
 FUSE_ACC = 0x200         # OR-ed into BF16 / F16: permission to run a low-rank accumulator and the live term in one pass
+FUSE_ACC_DEEP = 0x400    # the same permission for 256 < r_acc + r <= 960 (chain_deep_acc.hip); a call carries one of the two
 ACC_NONE, ACC_LOWRANK, ACC_DENSE = 0, 1, 2
 H_COLS = 64
 BWD_DATA, BWD_WEIGHTS, BWD_WEIGHTS_PARTIAL, BWD_WEIGHTS_REDUCE = 1, 2, 4, 8

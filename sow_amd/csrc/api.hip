@@ -54,7 +54,7 @@ static const char* const kSwitchNames[SW_COUNT] = {"FORCE_CHAIN_V1", "NO_SHORT_S
                                                    "NO_GEMM3S",      "GEMM3S",         "GEMM3",      "NO_GROUPED",     "NO_PERSIST",     "NO_NT_STORE",    "NT_LOAD",        "NO_PAIR_FLUSH",  "F32_EXACT",
                                                    "NO_PARK16",      "TN_NO_NT_LOAD",  "NO_TN_ROWS",     "GEMM4",          "NO_GEMM4H",      "NO_CHAIN3F",     "NO_TN_F32Q",     "NO_SPLITK",
                                                    "NO_WIDE_CHAIN",  "NO_SHARED_X",    "NO_RAGGED",      "NO_RAGGED_GEMM", "NO_BLOCKED_QR",
-                                                   "NO_SKINNY",      "NO_FUSED_ACC",   "NO_F16_TN",
+                                                   "NO_SKINNY",      "NO_FUSED_ACC",   "NO_DEEP_ACC",    "NO_F16_TN",
                                                    "NO_ROW_ALIGN",   "NO_H_ROWS"};
 static std::atomic<int> g_switch[SW_COUNT];
 static std::once_flag g_switch_once;
@@ -83,7 +83,8 @@ static inline size_t esize(int dtype) { return dtype == SOW_F32 ? 4 : 2; }
 static inline bool ok_dtype(int d) { return d == SOW_F32 || d == SOW_BF16 || d == SOW_F16; }
 static inline bool al4p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 static inline bool al16p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-// The dtype argument of an entry point, decoded once.  SOW_FUSE_ACC is a permission and is ignored together with SOW_PARAM_F32.
+// The dtype argument of an entry point, decoded once.  SOW_FUSE_ACC and SOW_FUSE_ACC_DEEP are permissions and are ignored
+// together with SOW_PARAM_F32.
 // The layer entry points, their plans and descriptors take what layer_ok() admits; sow_*_shared refuses SOW_PARAM_F32 as
 // unsupported after its own checks.  The entry points outside the layer surface (GEMM, QR, accumulate, optimizer, copies)
 // only strip the permission with nofuse() and refuse or reject SOW_PARAM_F32 themselves, each with its own code.
@@ -91,17 +92,21 @@ struct Dtype {
   int cd;           // compute dtype: the argument without its flag bits (not validated)
   bool param_f32;   // SOW_PARAM_F32
   bool fuse;        // SOW_FUSE_ACC, without SOW_PARAM_F32
+  bool deep;        // SOW_FUSE_ACC_DEEP, without SOW_PARAM_F32
+  // the permission bits a layer call carries on (SOW_FUSE_ACC | SOW_FUSE_ACC_DEEP, or 0)
+  int perm() const { return (fuse ? SOW_FUSE_ACC : 0) | (deep ? SOW_FUSE_ACC_DEEP : 0); }
   bool layer_ok() const { return ok_dtype(cd) && !(param_f32 && cd == SOW_F32); }
 };
 static inline Dtype decode_dtype(int d) {
   Dtype f;
-  f.cd = d & ~(SOW_FUSE_ACC | SOW_PARAM_F32);
+  f.cd = d & ~(SOW_FUSE_ACC | SOW_FUSE_ACC_DEEP | SOW_PARAM_F32);
   f.param_f32 = (d & SOW_PARAM_F32) != 0;
   f.fuse = (d & SOW_FUSE_ACC) != 0 && !f.param_f32;
+  f.deep = (d & SOW_FUSE_ACC_DEEP) != 0 && !f.param_f32;
   return f;
 }
 static inline bool flagged(int d) { return (d & SOW_PARAM_F32) != 0; }
-static inline int nofuse(int d) { return d & ~SOW_FUSE_ACC; }
+static inline int nofuse(int d) { return d & ~(SOW_FUSE_ACC | SOW_FUSE_ACC_DEEP); }
 
 // ---- short inputs ---------------------------------------------------------------------------------
 // T / 64 workgroups cannot fill 256 CUs: below SHORT_NTB token blocks the streaming chain is launched as
@@ -240,14 +245,16 @@ struct WsPlan {
   size_t off_dh, off_t, off_apad, off_hp, off_p0, off_p1, off_planes, planes_bytes, off_sk, sk_bytes, off_wide, wide_bytes,
       off_pw, pw_bytes, total;
   bool fused;   // the plan holds the pack region of the fused accumulator pass (SOW_FUSE_ACC on an admitted shape)
+  bool deep;    // ... of the fused pass past 256 columns (SOW_FUSE_ACC_DEEP on an admitted shape)
   int ns, slab_len;
   int ns_cap;   // slabs the partial regions can hold (group-planned slab counts may exceed the single-layer choice)
 };
 constexpr int64_t C3F_MIN_T = 8192;   // chain3f_supported's threshold
-// fuse: the caller's SOW_FUSE_ACC permission.  On an admitted shape the wide region also holds the factors of the fused pass
-// (r_acc + r_live columns); such a layer has r_live <= 64, so the region is the plan's last and every other offset is the
-// unflagged plan's: a flagged workspace serves the unflagged kernels as it is.  A pure function of its arguments.
-static WsPlan plan_ws(int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, int dtype, bool fuse = false) {
+// perm: the caller's permission bits (SOW_FUSE_ACC, SOW_FUSE_ACC_DEEP).  On a shape a bit admits (the two sets are disjoint
+// by r_acc + r_live) the wide region also holds the factors of the fused pass (r_acc + r_live columns); such a layer has
+// r_live <= 64, so the region is the plan's last and every other offset is the unflagged plan's -- the [T x r_acc] scratch of
+// gemm_pair included: a flagged workspace serves the unflagged kernels as it is.  A pure function of its arguments.
+static WsPlan plan_ws(int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, int dtype, int perm = 0) {
   WsPlan w{};
   const size_t es = esize(dtype);
   size_t off = 0;
@@ -301,8 +308,9 @@ static WsPlan plan_ws(int64_t T, int d_in, int d_out, int r_live, int r_acc, int
     // ragged layer: the factors of its live term or of its low-rank accumulator, whichever is wider
     if (rag_layer(r_live, r_acc, acc_kind, d_in, d_out, dtype)) rw = acc_kind == SOW_ACC_LOWRANK && r_acc > r_live ? r_acc : r_live;
     if (rw) w.wide_bytes = chain_wide_pack_bytes(rw, d_in, d_out);
-    w.fused = fuse && acc_kind == SOW_ACC_LOWRANK && fused_acc_shape_ok(r_live, r_acc, d_in, d_out, dtype);
-    if (w.fused) {
+    w.fused = (perm & SOW_FUSE_ACC) && acc_kind == SOW_ACC_LOWRANK && fused_acc_shape_ok(r_live, r_acc, d_in, d_out, dtype);
+    w.deep = (perm & SOW_FUSE_ACC_DEEP) && acc_kind == SOW_ACC_LOWRANK && deep_acc_shape_ok(r_live, r_acc, d_in, d_out, dtype);
+    if (w.fused || w.deep) {
       const size_t fb = chain_wide_pack_bytes(r_acc + r_live, d_in, d_out);
       if (fb > w.wide_bytes) w.wide_bytes = fb;
     }
@@ -350,8 +358,8 @@ static void normalise_acc(sow_layer_args& L) {
   if (L.acc_kind != SOW_ACC_LOWRANK) L.r_acc = 0, L.acc_up = nullptr;
   if (L.acc_kind == SOW_ACC_NONE) L.acc_down = nullptr;
 }
-static inline WsPlan plan_of(const sow_layer_args& L, int cd, bool fuse = false) {
-  return plan_ws(L.T, L.d_in, L.d_out, L.r_live, acc_rank(L), L.acc_kind, cd, fuse);
+static inline WsPlan plan_of(const sow_layer_args& L, int cd, int perm = 0) {
+  return plan_ws(L.T, L.d_in, L.d_out, L.r_live, acc_rank(L), L.acc_kind, cd, perm);
 }
 // The argument checks of a layer, in the one order every entry point reports them: shape, then (T > 0 only) NULL operands,
 // then a missing accumulator (NULL), then, with `lowrank`, the second factor and rank of a low-rank accumulator (SHAPE).
@@ -529,9 +537,17 @@ static WideAccArgs wide_acc_args(const DirView& v, char* ws, const WsPlan& wf) {
 // bias, and its H = dh lies in the workspace: the alignment tests on them are the forward's.
 static int fused_acc_pass(const sow_layer_args& L, const DirView& v, const LayerRun& c) {
   if (sw_on(SW_NO_FUSED_ACC) || !c.ws || !al16p(v.X) || !al16p(v.Y) || !al16p(v.bias) || !al16p(v.H)) return SOW_ERR_UNSUPPORTED;
-  const WsPlan wf = plan_of(L, c.dtype, true);
+  const WsPlan wf = plan_of(L, c.dtype, SOW_FUSE_ACC);
   if (!wf.fused || c.bytes < wf.total + 255) return SOW_ERR_UNSUPPORTED;
   return launch_chain_wide_acc(wide_acc_args(v, c.ws, wf), c.dtype, c.stream);
+}
+// SOW_FUSE_ACC_DEEP on an admitted call (256 < r_acc + r_live <= 960): the same chain with H in column groups
+// (chain_deep_acc.hip), in place of gemm_pair and the live chain with beta = 1.  Returns as fused_acc_pass does.
+static int deep_acc_pass(const sow_layer_args& L, const DirView& v, const LayerRun& c) {
+  if (sw_on(SW_NO_DEEP_ACC) || !c.ws || !al16p(v.X) || !al16p(v.Y) || !al16p(v.bias) || !al16p(v.H)) return SOW_ERR_UNSUPPORTED;
+  const WsPlan wf = plan_of(L, c.dtype, SOW_FUSE_ACC_DEEP);
+  if (!wf.deep || c.bytes < wf.total + 255) return SOW_ERR_UNSUPPORTED;
+  return launch_chain_deep_acc(wide_acc_args(v, c.ws, wf), c.dtype, c.stream);
 }
 // The shared-input data gradient of siblings that all carry a low-rank accumulator (chain_shared_acc.hip): the admitted set
 // of sow_backward_shared under SOW_FUSE_ACC (include/sow_amd.h).  `layers`: checked, one x, T, d_in and dx (shared_common,
@@ -556,7 +572,7 @@ static int shared_fused_acc_data(const sow_layer_args* layers, int n, const Dtyp
   WideAccArgs sib[4];
   for (int i = 0; i < n; ++i) {
     const sow_layer_args& L = layers[i];
-    const WsPlan wf = plan_of(L, cd, true);
+    const WsPlan wf = plan_of(L, cd, SOW_FUSE_ACC);
     if (!wf.fused || L.workspace_bytes < wf.total + 255) return SOW_ERR_UNSUPPORTED;
     char* ws = ws_base(L.workspace);
     sib[i] = wide_acc_args(dir_view(L, true, ws + wf.off_dh), ws, wf);
@@ -750,8 +766,8 @@ size_t sow_forward_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, i
     return own ? own + pack : pack + 256;
   }
   const bool wide_acc = acc_kind == SOW_ACC_LOWRANK && r_acc > 64;
-  const WsPlan w = plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, f.cd, f.fuse);
-  if (!w.fused && !wide_acc && r_live <= 64 && short_hp_bytes(T, d_in, d_out, r_live, f.cd) == 0 && w.planes_bytes == 0 && w.sk_bytes == 0)
+  const WsPlan w = plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, f.cd, f.perm());
+  if (!w.fused && !w.deep && !wide_acc && r_live <= 64 && short_hp_bytes(T, d_in, d_out, r_live, f.cd) == 0 && w.planes_bytes == 0 && w.sk_bytes == 0)
     return 0;   // the forward does not touch it
   return w.total + 256;
 }
@@ -760,11 +776,11 @@ size_t sow_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int r_acc
   const Dtype f = decode_dtype(dtype);
   if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0 || !f.layer_ok()) return 0;
   const size_t pack = f.param_f32 ? pack_bytes(d_in, d_out, r_live, acc_kind == SOW_ACC_LOWRANK ? r_acc : 0, acc_kind) : 0;
-  return plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, f.cd, f.fuse).total + pack + 256;
+  return plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, f.cd, f.perm()).total + pack + 256;
 }
 
 // ---- single layer -----------------------------------------------------------------------------------------------------
-static int forward_impl(const sow_layer_args& L, int dtype, bool fuse, hipStream_t stream) {
+static int forward_impl(const sow_layer_args& L, int dtype, int perm, hipStream_t stream) {
   if (!ok_dtype(dtype)) return SOW_ERR_DTYPE;
   int rc = check_layer(L, false, true);
   if (rc || L.T == 0) return rc;
@@ -775,7 +791,8 @@ static int forward_impl(const sow_layer_args& L, int dtype, bool fuse, hipStream
   const DirView v = dir_view(L, false, nullptr);
   const LayerRun c{dtype, ws, w, workspace_bytes, stream};
   float beta = 0.f;
-  if (fuse && (rc = fused_acc_pass(L, v, c)) != SOW_ERR_UNSUPPORTED) return rc;
+  if ((perm & SOW_FUSE_ACC) && (rc = fused_acc_pass(L, v, c)) != SOW_ERR_UNSUPPORTED) return rc;
+  if ((perm & SOW_FUSE_ACC_DEEP) && (rc = deep_acc_pass(L, v, c)) != SOW_ERR_UNSUPPORTED) return rc;
   // ragged widths; without workspace or with views off 16 bytes, the generic kernels below
   if (rag_layer(r_live, r_acc, acc_kind, L.d_in, L.d_out, dtype) && !sw_on(SW_NO_RAGGED) && ws &&
       workspace_bytes >= w.total + 255 && al16p(L.x) && al16p(L.y) && (!L.bias || al16p(L.bias)) &&
@@ -819,11 +836,11 @@ int sow_forward(const void* x, const void* A, const void* B, const void* acc_dow
     const int rc = pack_single(L, f.cd, true, (hipStream_t)stream);
     if (rc) return rc;
   }
-  return forward_impl(L, f.cd, f.fuse, (hipStream_t)stream);
+  return forward_impl(L, f.cd, f.perm(), (hipStream_t)stream);
 }
 
 // gdt: the dtype of dA / dB / dbias -- dtype, or SOW_F32 under SOW_PARAM_F32 (the fp32 slab sums rounded once to fp32)
-static int backward_impl(const sow_layer_args& L, int dtype, int gdt, int phases, bool fuse, hipStream_t stream) {
+static int backward_impl(const sow_layer_args& L, int dtype, int gdt, int phases, int perm, hipStream_t stream) {
   const Phases ph = decode_phases(phases);
   bool do_data = ph.data;
   if (!ph.data && !ph.weights()) return SOW_ERR_SHAPE;
@@ -852,8 +869,13 @@ static int backward_impl(const sow_layer_args& L, int dtype, int gdt, int phases
   const LayerRun c{dtype, ws, w, workspace_bytes, stream};
   float beta = 0.f;
   bool data_done = false;
-  if (do_data && fuse) {
+  if (do_data && (perm & SOW_FUSE_ACC)) {
     rc = fused_acc_pass(L, v, c);
+    if (rc && rc != SOW_ERR_UNSUPPORTED) return rc;
+    if (!rc) do_data = false;
+  }
+  if (do_data && (perm & SOW_FUSE_ACC_DEEP)) {
+    rc = deep_acc_pass(L, v, c);
     if (rc && rc != SOW_ERR_UNSUPPORTED) return rc;
     if (!rc) do_data = false;
   }
@@ -933,14 +955,14 @@ int sow_backward_ex(const void* dy, const void* x, const void* h_save, const voi
   const Dtype f = decode_dtype(dtype);
   sow_layer_args L = single_layer(x, A, B, acc_down, acc_up, nullptr, nullptr, const_cast<void*>(h_save), dy, dx, dA, dB, dbias, T,
                                   d_in, d_out, r_live, r_acc, acc_kind, scale, grad_beta, workspace, workspace_bytes);
-  if (!f.param_f32) return backward_impl(L, f.cd, f.cd, phases, f.fuse, (hipStream_t)stream);
+  if (!f.param_f32) return backward_impl(L, f.cd, f.cd, phases, f.perm(), (hipStream_t)stream);
   if (!f.layer_ok()) return SOW_ERR_DTYPE;
   // fp32 parameters: only the data gradient reads the factors (and the accumulator); they are packed when it runs
   if ((phases & SOW_BWD_DATA) && T > 0) {
     const int rc = pack_single(L, f.cd, false, (hipStream_t)stream);
     if (rc) return rc;
   }
-  return backward_impl(L, f.cd, SOW_F32, phases, false, (hipStream_t)stream);
+  return backward_impl(L, f.cd, SOW_F32, phases, 0, (hipStream_t)stream);
 }
 
 int sow_backward(const void* dy, const void* x, const void* h_save, const void* A, const void* B, const void* acc_down,
@@ -1014,7 +1036,7 @@ static int pack_group(const sow_layer_args* layers, int n, int cd, bool bwd, std
   return launch_pack_params(items.data(), (int)items.size(), cd, stream);
 }
 
-static int forward_group_impl(const sow_layer_args* layers, int n, int dtype, bool fuse, hipStream_t stream) {
+static int forward_group_impl(const sow_layer_args* layers, int n, int dtype, int perm, hipStream_t stream) {
   if (!ok_dtype(dtype)) return SOW_ERR_DTYPE;
   if (n < 0) return SOW_ERR_SHAPE;
   if (n == 0) return SOW_OK;
@@ -1050,7 +1072,7 @@ static int forward_group_impl(const sow_layer_args* layers, int n, int dtype, bo
         continue;
       }
     }
-    if ((rc = forward_impl(L, dtype, fuse, stream))) return rc;
+    if ((rc = forward_impl(L, dtype, perm, stream))) return rc;
   }
   if (ng && (rc = launch_gemm2h_group(gbatch, ng, false, stream))) return rc;
   return nb ? launch_chain2_group(batch, nb, false, dtype, stream) : SOW_OK;
@@ -1059,10 +1081,10 @@ static int forward_group_impl(const sow_layer_args* layers, int n, int dtype, bo
 int sow_forward_group(const sow_layer_args* layers, int n, int dtype, void* stream) {
   const Dtype f = decode_dtype(dtype);
   if (!f.layer_ok()) return SOW_ERR_DTYPE;
-  if (!f.param_f32 || n <= 0 || !layers) return forward_group_impl(layers, n, f.cd, f.fuse, (hipStream_t)stream);
+  if (!f.param_f32 || n <= 0 || !layers) return forward_group_impl(layers, n, f.cd, f.perm(), (hipStream_t)stream);
   std::vector<sow_layer_args> packed;
   const int rc = pack_group(layers, n, f.cd, false, packed, (hipStream_t)stream);
-  return rc ? rc : forward_group_impl(packed.data(), n, f.cd, false, (hipStream_t)stream);
+  return rc ? rc : forward_group_impl(packed.data(), n, f.cd, 0, (hipStream_t)stream);
 }
 
 // ---- generation-sized forwards (skinny_fwd.hip) --------------------------------------------------------------
@@ -1126,7 +1148,7 @@ int sow_forward_skinny(const sow_layer_args* layers, int n, int dtype, void* str
   return launch_skinny_fwd(sk, m, cd, (hipStream_t)stream);
 }
 
-static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, int gdt, int phases, bool fuse, hipStream_t stream) {
+static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, int gdt, int phases, int perm, hipStream_t stream) {
   const Phases ph = decode_phases(phases);
   if (!ph.data && !ph.weights()) return SOW_ERR_SHAPE;
   if (!ok_dtype(dtype)) return SOW_ERR_DTYPE;
@@ -1143,7 +1165,7 @@ static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, i
     for (int i = 0; i < n; ++i) {
       const sow_layer_args& L = layers[i];
       if (L.T == 0) {   // empty batch: everything at once
-        if ((rc = backward_impl(L, dtype, gdt, SOW_BWD_DATA | (phases & ~SOW_BWD_DATA), fuse, stream))) return rc;
+        if ((rc = backward_impl(L, dtype, gdt, SOW_BWD_DATA | (phases & ~SOW_BWD_DATA), perm, stream))) return rc;
         continue;
       }
       const WsPlan w = plan_of(L, dtype);
@@ -1170,7 +1192,7 @@ static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, i
           continue;
         }
       }
-      if ((rc = backward_impl(L, dtype, gdt, SOW_BWD_DATA, fuse, stream))) return rc;
+      if ((rc = backward_impl(L, dtype, gdt, SOW_BWD_DATA, perm, stream))) return rc;
     }
     if (ng && (rc = launch_gemm2h_group(gbatch, ng, true, stream))) return rc;
     if (nb && (rc = launch_chain2_group(batch, nb, true, dtype, stream))) return rc;
@@ -1195,7 +1217,7 @@ static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, i
     for (int i = 0; i < n; ++i) {
       const sow_layer_args& L = layers[i];
       if (L.T == 0) {
-        if (!ph.data && (rc = backward_impl(L, dtype, gdt, phases, fuse, stream))) return rc;
+        if (!ph.data && (rc = backward_impl(L, dtype, gdt, phases, perm, stream))) return rc;
         continue;
       }
       const WsPlan w = plan_of(L, dtype);
@@ -1212,7 +1234,7 @@ static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, i
           }
         }
       }
-      if (!grouped && (rc = backward_impl(L, dtype, gdt, SOW_BWD_WEIGHTS_PARTIAL, fuse, stream))) return rc;
+      if (!grouped && (rc = backward_impl(L, dtype, gdt, SOW_BWD_WEIGHTS_PARTIAL, perm, stream))) return rc;
     }
     if (nb && (rc = launch_tn_group(batch, nb, dtype, stream))) return rc;
   }
@@ -1226,7 +1248,7 @@ static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, i
     }
   } else if (ph.reduce) {
     for (int i = 0; i < n; ++i)
-      if (layers[i].T != 0 && (rc = backward_impl(layers[i], dtype, gdt, SOW_BWD_WEIGHTS_REDUCE, fuse, stream))) return rc;
+      if (layers[i].T != 0 && (rc = backward_impl(layers[i], dtype, gdt, SOW_BWD_WEIGHTS_REDUCE, perm, stream))) return rc;
   }
   return SOW_OK;
 }
@@ -1234,12 +1256,12 @@ static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, i
 int sow_backward_group(const sow_layer_args* layers, int n, int dtype, int phases, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   const Dtype f = decode_dtype(dtype);
-  if (!f.param_f32) return backward_group_impl(layers, n, f.cd, f.cd, phases, f.fuse, stream);
+  if (!f.param_f32) return backward_group_impl(layers, n, f.cd, f.cd, phases, f.perm(), stream);
   if (!f.layer_ok()) return SOW_ERR_DTYPE;
-  if (n <= 0 || !layers || !(phases & SOW_BWD_DATA)) return backward_group_impl(layers, n, f.cd, SOW_F32, phases, false, stream);
+  if (n <= 0 || !layers || !(phases & SOW_BWD_DATA)) return backward_group_impl(layers, n, f.cd, SOW_F32, phases, 0, stream);
   std::vector<sow_layer_args> packed;
   const int rc = pack_group(layers, n, f.cd, true, packed, stream);
-  return rc ? rc : backward_group_impl(packed.data(), n, f.cd, SOW_F32, phases, false, stream);
+  return rc ? rc : backward_group_impl(packed.data(), n, f.cd, SOW_F32, phases, 0, stream);
 }
 
 // ---- shared-input entry points (chain2_shared.hip) -----------------------------------------------------------------
@@ -1288,7 +1310,7 @@ int sow_backward_shared(const sow_layer_args* layers, int n, int dtype, int phas
   if (f.param_f32) return SOW_ERR_UNSUPPORTED;
   sow_layer_args filled[C2_MAXG];
   shared_fill_dx(layers, n, filled);
-  if (!(phases & SOW_BWD_DATA)) return backward_group_impl(filled, n, cd, cd, phases, false, stream);
+  if (!(phases & SOW_BWD_DATA)) return backward_group_impl(filled, n, cd, cd, phases, 0, stream);
   for (int i = 0; i < n; ++i)
     if ((rc = check_layer(filled[i], true, false))) return rc;
   if (sw_on(SW_NO_SHARED_X) || filled[0].T == 0) return SOW_ERR_UNSUPPORTED;
@@ -1309,7 +1331,7 @@ int sow_backward_shared(const sow_layer_args* layers, int n, int dtype, int phas
   if (streaming && (rc = launch_chain2_shared(ps, n, true, cd, stream))) return rc;
   // the weight phases read each layer's dh where the grouped data phase leaves it: exactly sow_backward_group's code
   const int wph = phases & ~SOW_BWD_DATA;
-  return decode_phases(wph).weights() ? backward_group_impl(filled, n, cd, cd, wph, false, stream) : SOW_OK;
+  return decode_phases(wph).weights() ? backward_group_impl(filled, n, cd, cd, wph, 0, stream) : SOW_OK;
 }
 
 // the group entry points' checks for the two plan queries below

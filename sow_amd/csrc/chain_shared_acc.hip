@@ -124,7 +124,8 @@ template <typename T> __global__ __launch_bounds__(256, 2) void chain_shared_acc
   }
 
   // ---- phase 2: dX = rn(beta dX + sum_i h_i . [Q_i^T ; A_i^T]), 64 columns of d_in at a time, one rounding ----------------
-  cw_phase2_panels<T>(smem, stage, p.g, &p.pan, (T*)p.Y, p.M, t0, p.D2, p.beta, p.nt_store != 0, threadIdx.x);
+  cw_phase2_panels<T>(smem, stage, p.g, &p.pan, (T*)p.Y, p.M, t0, p.D2, p.beta, p.nt_store != 0, threadIdx.x,
+                      (const T*)nullptr);
 }
 
 // The LDS plan of a set (r_tot[i] = r_acc_i + r_i): bytes of the H panels, of the stage, and the F2 panels per group

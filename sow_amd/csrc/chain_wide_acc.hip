@@ -27,11 +27,6 @@
 
 namespace sow {
 
-template <typename T> __global__ __launch_bounds__(256) void wide_acc_pack_kernel(const WideAccPackParams p) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < p.n) wide_acc_pack_elem<T>(p, i);
-}
-
 struct WideAccParams {
   const void* X;
   void* Y;

@@ -8,7 +8,8 @@
 //   cw_phase2: Y = beta * Y + yscale * H . F2 + bias, 64 output columns at a time, wave (wm, wn) owns a 32 x 32 tile
 // The factors come packed: F1T [r_pad][ldf1t] (row c = column c of H), F2T [D2][r_pad] (row n = output column n).
 // chain_shared_acc.hip runs the same phase 1 once per sibling (cw_phase1_at) into panels of several chains side by side and
-// one phase 2 over all of them (cw_phase2_panels), in dynamic LDS of its own plan.
+// one phase 2 over all of them (cw_phase2_panels), in dynamic LDS of its own plan; chain_deep_acc.hip does the same with the
+// column groups of ONE chain.
 #pragma once
 #include "kernels.hpp"
 #include "epilogue.hpp"
@@ -148,6 +149,7 @@ __device__ __forceinline__ void cw_phase2(char* big, char* small, const T* F2T, 
 // into ONE output.  Panel q multiplies the 64 columns of F2 that start at f2[q] (row n = output column n, row pitch ld[q]
 // elements): a sibling's own F2T, 64 pn columns in.  The F2 panels pass through `stage` g at a time (g <= 4; g panels and the
 // epilogue scratch fit into `stage`); the fp32 accumulation runs over the panels in ascending q, ascending k inside a panel.
+// bias [D2] (or null) is added in fp32 before the one rounding.
 // CW_MAXP: four chains of r_pad = 256 -- more than any LDS plan holds (chain_shared_acc.hip admits at most 15 panels), so that
 // the table cannot overflow whatever the plan's limit becomes; the launcher checks the count all the same.
 constexpr int CW_MAXP = 16;
@@ -160,7 +162,7 @@ struct CwPanels {
 // index)
 template <typename T, typename PP>
 __device__ __forceinline__ void cw_phase2_panels(const char* hp, char* stage, int g, PP P, T* Y, int64_t M, int64_t t0, int D2,
-                                                 float beta, bool nt, const int t) {
+                                                 float beta, bool nt, const int t, const T* bias) {
   using V8 = typename DT<T>::v8;
   const int lane = t & 63, w = t >> 6, li = lane & 31, lh = lane >> 5;
   const int np = P->np, wm = w >> 1, wn = w & 1;
@@ -201,7 +203,7 @@ __device__ __forceinline__ void cw_phase2_panels(const char* hp, char* stage, in
       }
     }
     __syncthreads();   // the F2 panels are consumed: their space becomes the epilogue scratch
-    wave_store_tiles<T, 1, true>(&o, scratch, Y, D2, t0 + wm * 32, nb * 64 + wn * 32, M, D2, 1.f, beta, (const T*)nullptr, lane, nt);
+    wave_store_tiles<T, 1, true>(&o, scratch, Y, D2, t0 + wm * 32, nb * 64 + wn * 32, M, D2, 1.f, beta, bias, lane, nt);
   }
 }
 
@@ -238,6 +240,11 @@ template <typename T> __device__ __forceinline__ void wide_acc_pack_elem(const W
     v = J.trans ? src[(int64_t)j * ld + kk] : src[(int64_t)kk * ld + j];
   }
   *dst = v;
+}
+// one launch packs both images of a layer and direction (chain_wide_acc.hip, chain_deep_acc.hip)
+template <typename T> __global__ __launch_bounds__(256) void wide_acc_pack_kernel(const WideAccPackParams p) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < p.n) wide_acc_pack_elem<T>(p, i);
 }
 // The pack of one layer and direction into `a.pack`: F1T at its start, F2T at the next 256-byte boundary.
 // forward: F1 = [Q | A] stored [D1][r] (transposed on the way in), F2 = [R ; B] stored [r][D2];

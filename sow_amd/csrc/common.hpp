@@ -183,6 +183,7 @@ enum Switch : int {
   SW_NO_BLOCKED_QR,       // sow_qr_thin: the one-workgroup unblocked panel at every width instead of the blocked route past 64 columns
   SW_NO_SKINNY,           // sow_forward_skinny returns SOW_ERR_UNSUPPORTED (callers take sow_forward / sow_forward_group)
   SW_NO_FUSED_ACC,        // SOW_FUSE_ACC is ignored: a low-rank accumulator and the live term keep one chain launch each
+  SW_NO_DEEP_ACC,         // SOW_FUSE_ACC_DEEP is ignored: a low-rank accumulator past 256 columns keeps the generic GEMM pair
   SW_NO_F16_TN,           // f16 weight gradients on the generic kernel for every shape, never grouped, no row-owner plan
   SW_NO_ROW_ALIGN,        // chain kernel cuts the pieces of 64-bytes-off-a-line row pitches at multiples of 64 columns, as for every other
                           // pitch: 1 = both sides, 2 = the X stages only, 3 = the Y slices only

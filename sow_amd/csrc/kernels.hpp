@@ -195,6 +195,15 @@ bool fused_acc_shape_ok(int r_live, int r_acc, int d_in, int d_out, int dtype);
 // SOW_ERR_UNSUPPORTED when the shape, the alignment (X, Y, bias, Hsave, pack: 16 bytes) or the scratch does not suit the
 // kernel (nothing launched)
 int launch_chain_wide_acc(const WideAccArgs& a, int dtype, hipStream_t stream);
+// chain_deep_acc.hip (bf16 / f16; SOW_FUSE_ACC_DEEP): the same chain for 256 < r_acc + r_live <= 960, the H columns computed
+// in groups of 256 and kept in dynamic LDS (deep_acc_lds_bytes: 128 bytes per padded column + a 40 KiB stage, at most 160
+// KiB).  The operands, the pack and the results' contract are launch_chain_wide_acc's.
+// even r_live in [2, 64], even r_acc >= 2, 256 < r_acc + r_live <= 960, widths multiples of 8, bf16 / f16
+bool deep_acc_shape_ok(int r_live, int r_acc, int d_in, int d_out, int dtype);
+size_t deep_acc_lds_bytes(int r_tot);
+// SOW_ERR_UNSUPPORTED when the shape, the alignment (X, Y, bias, Hsave, pack: 16 bytes) or the scratch does not suit the
+// kernel (nothing launched)
+int launch_chain_deep_acc(const WideAccArgs& a, int dtype, hipStream_t stream);
 // chain_shared_acc.hip (bf16 / f16): the data gradients of n <= 4 sibling layers with low-rank accumulators on one input,
 // summed on chip:  dh_i as launch_chain_wide_acc(bwd = 1) leaves it,  dX = rn(beta dX + sum_i h_i . [Q_i^T ; A_i^T]).
 // sib[i]: the sibling's operands as for launch_chain_wide_acc with bwd = 1 (X = dY_i, Hsave = dh_i, its own pack region; Y

@@ -103,8 +103,9 @@ class _GradSink:
         r, d_out = B.shape
         kind = ops.acc_kind(acc_down, acc_up)
         r_acc = acc_down.shape[1] if kind == _lib.ACC_LOWRANK else 0
-        # sized for the SOW_FUSE_ACC data gradient where the layer takes it (the flagged plan also serves the unflagged call)
-        self.fuse_acc = ops.fuse_acc_default(T, d_in, d_out, r, r_acc, kind, x2.dtype, _mixed(x2, B))
+        # sized for the fused data gradient (SOW_FUSE_ACC / SOW_FUSE_ACC_DEEP) where the layer takes it (the flagged plan also
+        # serves the unflagged call)
+        self.fuse_acc = ops.acc_permission(T, d_in, d_out, r, r_acc, kind, x2.dtype, _mixed(x2, B))
         need = ops.workspace_bytes(T, d_in, d_out, r, r_acc, kind, x2.dtype, param_f32=_mixed(x2, B),
                                    fuse_acc=self.fuse_acc) + 256
         if self.ws is None or self.ws.numel() < need or self.ws.device != x2.device:

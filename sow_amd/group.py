@@ -28,6 +28,8 @@ fused pass per sibling and the adds of _input_grad.  Measured at T = 32768, r = 
 at r_acc = 50 128 -> 80 us, gate + up at r_acc = 50 / 100 123 -> 97 / 137 -> 114 us.  Sets whose LDS plan allows only one
 workgroup per CU measured SLOWER (q + k + v at r_acc = 100 / 200: 1.12 / 1.18 of the grouped path, gate + up at 200: 1.36)
 and keep the grouped path (ops.shared_fused_acc_pays).  The forward of such sets is the grouped launch, as for every set.
+Siblings past 256 accumulator + live columns hold the SOW_FUSE_ACC_DEEP permission instead (ops.acc_permission); the shared
+entry points ignore it, so such sets run the grouped path, one deep pass per sibling (chain_deep_acc.hip).
 """
 from __future__ import annotations
 

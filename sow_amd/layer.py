@@ -65,13 +65,13 @@ def autocast_input(x2: torch.Tensor, cdt: torch.dtype) -> torch.Tensor:
     return ops.cast(x2, cdt)
 
 
-def _fuse_acc(x2, B, acc_down, acc_up, mixed: bool) -> bool:
-    """The SOW_FUSE_ACC permission of a module call (ops.fuse_acc_default): the same answer on the grad and the no-grad
-    route, so that eval and train outputs stay bit-identical."""
+def _fuse_acc(x2, B, acc_down, acc_up, mixed: bool) -> int:
+    """The permission of a module call (ops.acc_permission: SOW_FUSE_ACC, SOW_FUSE_ACC_DEEP or 0): the same answer on the
+    grad and the no-grad route, so that eval and train outputs stay bit-identical."""
     kind = ops.acc_kind(acc_down, acc_up)
     if kind != ops._lib.ACC_LOWRANK or acc_down.dim() != 2:
-        return False
-    return ops.fuse_acc_default(x2.shape[0], x2.shape[1], B.shape[1], B.shape[0], acc_down.shape[1], kind, x2.dtype, mixed)
+        return 0
+    return ops.acc_permission(x2.shape[0], x2.shape[1], B.shape[1], B.shape[0], acc_down.shape[1], kind, x2.dtype, mixed)
 
 
 class _SoWFunction(torch.autograd.Function):

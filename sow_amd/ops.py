@@ -23,14 +23,29 @@ def _dt(t: torch.Tensor) -> int:
         raise TypeError(f"sow_amd supports float32, bfloat16 and float16 tensors, got {t.dtype}") from None
 
 
-def _call_dtype(x2: torch.Tensor, param_f32: bool, who: str = "sow_amd", fuse_acc: bool = False) -> Tuple[int, torch.dtype]:
+_PERMS = _lib.FUSE_ACC | _lib.FUSE_ACC_DEEP
+
+
+def _perm(fuse_acc) -> int:
+    """The ONE permission value a layer call carries, as its dtype bit: 0 (none), SOW_FUSE_ACC or SOW_FUSE_ACC_DEEP.
+    `fuse_acc` is that bit, or a bool with today's meaning (True = SOW_FUSE_ACC)."""
+    if fuse_acc is True:
+        return _lib.FUSE_ACC
+    if not fuse_acc:
+        return 0
+    if fuse_acc not in (_lib.FUSE_ACC, _lib.FUSE_ACC_DEEP):
+        raise ValueError("sow_amd: fuse_acc is a bool, _lib.FUSE_ACC or _lib.FUSE_ACC_DEEP")
+    return int(fuse_acc)
+
+
+def _call_dtype(x2: torch.Tensor, param_f32: bool, who: str = "sow_amd", fuse_acc=False) -> Tuple[int, torch.dtype]:
     """(C-ABI dtype code, parameter dtype) of a layer call on activations x2.  param_f32: the parameters (factors, bias,
     accumulator) are fp32 and x2 is of the compute dtype, bf16 or f16 (SOW_PARAM_F32: mixed precision, torch.autocast).
-    fuse_acc: the SOW_FUSE_ACC permission (bf16 / f16 parameters only: the library ignores it next to SOW_PARAM_F32, so it
-    is not passed there)."""
+    fuse_acc: the call's permission (_perm: SOW_FUSE_ACC or SOW_FUSE_ACC_DEEP; bf16 / f16 parameters only: the library
+    ignores it next to SOW_PARAM_F32, so it is not passed there)."""
     dt = _dt(x2)
     if not param_f32:
-        return (dt | _lib.FUSE_ACC if fuse_acc and dt != _lib.F32 else dt), x2.dtype
+        return (dt | _perm(fuse_acc) if dt != _lib.F32 else dt), x2.dtype
     if dt == _lib.F32:
         raise TypeError(f"{who}: fp32 parameters need bfloat16 or float16 activations, got {x2.dtype}")
     return dt | _lib.PARAM_F32, torch.float32
@@ -189,6 +204,70 @@ def fuse_acc_default(T: int, d_in: int, d_out: int, r: int, r_acc: int, kind: in
     return fused_acc_admits(d_in, d_out, r, r_acc, kind, dtype, param_f32) and fused_acc_pays(T, d_in, d_out, r, r_acc)
 
 
+DEEP_ACC_MAX_TOT = 960                  # 15 panels of 64 columns: 120 KiB of H next to the 40 KiB stage
+DEEP_ACC_MAX_LDS = 160 * 1024
+
+
+def deep_acc_admits(d_in: int, d_out: int, r: int, r_acc: int, kind: int, dtype: torch.dtype,
+                    param_f32: bool = False) -> bool:
+    """The admitted set of SOW_FUSE_ACC_DEEP (include/sow_amd.h; deep_acc_shape_ok in the library): a bf16 / f16 layer
+    without fp32 parameters, a low-rank accumulator, even r in [2, 64], even r_acc, 256 < r_acc + r <= 960, widths
+    multiples of 8.  Disjoint from fused_acc_admits by the total.  The call-time conditions hold for every tensor the module
+    surface allocates."""
+    return (dtype in (torch.bfloat16, torch.float16) and not param_f32 and kind == _lib.ACC_LOWRANK
+            and 2 <= r <= 64 and r % 2 == 0 and r_acc >= 2 and r_acc % 2 == 0 and 256 < r_acc + r <= DEEP_ACC_MAX_TOT
+            and d_in > 0 and d_out > 0 and d_in % 8 == 0 and d_out % 8 == 0)
+
+
+def deep_acc_lds_bytes(r_tot: int) -> int:
+    """The LDS plan of chain_deep_acc.hip for r_tot = r_acc + r: 128 bytes per column of r_pad = ceil64(r_tot) and the 40
+    KiB stage.  At most 80 KiB (r_pad <= 320) two workgroups share a CU."""
+    return (r_tot + 63) // 64 * 64 * 128 + 40960
+
+
+DEEP_ACC_MIN_T = 16384      # the shortest row of profiles/deep_acc.txt (an r_acc that is no multiple of 8)
+DEEP_ACC_MIN_T_WIDE = 32768  # ... and the only token count measured where the unflagged accumulator term is chain_wide
+DEEP_ACC_MAX_D = 1376       # its widest layer (512 -> 1376, 1376 -> 512)
+
+
+def deep_acc_pays(T: int, d_in: int, d_out: int, r: int, r_acc: int) -> bool:
+    """The measured dispatch rule of the module surface for SOW_FUSE_ACC_DEEP (profiles/deep_acc.txt, DESIGN.md section
+    4.4f), the one place that encodes it: the classes at which the deep pass beats the unflagged call, forward and data
+    gradient each and together, by more than the unflagged variant's own spread.  What decides is the kernel the unflagged
+    accumulator term runs on, which follows from r_acc:
+
+    Measured (bf16, r = 50, T = 32768; us of forward + data gradient, unflagged -> deep (unflagged spread)):
+      r_acc <= 256 (unflagged: chain_wide + live chain; deep plans 80 KiB, two workgroups per CU), r_acc = 250:
+        512->512 154 -> 132 (9.6), 512->1376 257 -> 209 (13.2), 1376->512 256 -> 209 (11.5): pays, ratio 0.81 to 0.86
+      r_acc > 256, no multiple of 8 (unflagged: two launches of the generic GEMM off its vector path), r_acc = 300 / 450 / 500:
+        512->512 1810 -> 225, 2338 -> 260, 2336 -> 318; 512->1376 3290 -> 385, 4383 -> 454, 4402 -> 559;
+        1376->512 3393 -> 390, 4283 -> 455, 4297 -> 559; 1024->1024 at r_acc = 900 (160 KiB): 8570 -> 880;
+        f16 512->512 at 300: 1807 -> 223; T = 16384, 512->1376 at 450: 2232 -> 241: pays, ratio 0.10 to 0.14
+      r_acc > 256, a multiple of 8 (unflagged: the generic GEMM on its vector path), one workgroup per CU for the deep pass:
+        r_acc = 400: 512->512 192 -> 246, 512->1376 320 -> 425, 1376->512 322 -> 424; 768->768 at 600: 311 -> 469;
+        768->768, r = 8, r_acc = 504: 264 -> 348: LOSES, ratio 1.28 to 1.51 -- stays off
+    The rule is these rows: widths up to DEEP_ACC_MAX_D; r_acc no multiple of 8 past 256 columns from DEEP_ACC_MIN_T tokens,
+    r_acc <= 256 from DEEP_ACC_MIN_T_WIDE tokens; multiples of 8 past 256 never.  NOT measured, hence off: fewer tokens
+    and widths above 1376.  Inside the envelope but not timed one by one: r_acc = 350 (its class, no multiple of 8, has five
+    rows), r_acc <= 256 at an r other than 50."""
+    if T < DEEP_ACC_MIN_T or max(d_in, d_out) > DEEP_ACC_MAX_D:
+        return False
+    if r_acc <= 256:
+        return T >= DEEP_ACC_MIN_T_WIDE
+    return r_acc % 8 != 0
+
+
+def acc_permission(T: int, d_in: int, d_out: int, r: int, r_acc: int, kind: int, dtype: torch.dtype,
+                   param_f32: bool = False) -> int:
+    """The ONE permission the module surface passes for this layer call: _lib.FUSE_ACC (fuse_acc_default), _lib.FUSE_ACC_DEEP
+    (admitted past 256 columns and measured to pay) or 0.  The grad and the no-grad forward both ask here."""
+    if fuse_acc_default(T, d_in, d_out, r, r_acc, kind, dtype, param_f32):
+        return _lib.FUSE_ACC
+    if deep_acc_admits(d_in, d_out, r, r_acc, kind, dtype, param_f32) and deep_acc_pays(T, d_in, d_out, r, r_acc):
+        return _lib.FUSE_ACC_DEEP
+    return 0
+
+
 SHARED_FUSED_ACC_MIN_T = 8193          # more than 8192 tokens: the threshold of the streaming shared-input kernel
 SHARED_FUSED_ACC_MAX_N = 4
 SHARED_FUSED_ACC_MAX_LDS = 160 * 1024   # bytes of LDS a workgroup of chain_shared_acc.hip may plan
@@ -240,15 +319,16 @@ def shared_fused_acc_pays(r_tots: Sequence[int]) -> bool:
 
 
 def sow_forward(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, acc_up, bias, scale: float,
-                save_h: bool = True, *, param_f32: bool = False, fuse_acc: bool = False):
+                save_h: bool = True, *, param_f32: bool = False, fuse_acc=False):
     """y, h_save = forward of the SoW contraction on a flattened [T, d_in] input.  save_h = False (no-grad / eval callers,
     e.g. the reload + generate loop of commonsense_evaluate.py:268-287): the projection is not written to HBM and None
     is returned in its place (every rank except r <= 64 with a dense accumulator, whose fused kernels write it as scratch;
     a wide layer off the fused chain keeps its intermediate in the forward workspace).
     param_f32: A, B, bias and the accumulator are fp32, x2 is bf16 / f16 (the compute dtype); the kernels round the
     parameters once to x2's dtype (include/sow_amd.h: SOW_PARAM_F32) and y is of x2's dtype.
-    fuse_acc: the SOW_FUSE_ACC permission -- a low-rank accumulator and the live term in one pass where the library admits
-    the call; the same result as without it everywhere else."""
+    fuse_acc: the call's permission (True or _lib.FUSE_ACC: SOW_FUSE_ACC; _lib.FUSE_ACC_DEEP: SOW_FUSE_ACC_DEEP) -- a low-rank
+    accumulator and the live term in one pass where the library admits the call; the same result as without it everywhere
+    else."""
     lib = _lib.load()
     dev = _need_gpu(x2, A, B, acc_down if acc_down is not None and acc_down.numel() else None,
                     acc_up if acc_up is not None and acc_up.numel() else None, bias)
@@ -375,8 +455,8 @@ def sow_forward_skinny(layers) -> Optional[list]:
 
 
 def workspace_bytes(T: int, d_in: int, d_out: int, r: int, r_acc: int, kind: int, dtype: torch.dtype,
-                    param_f32: bool = False, fuse_acc: bool = False) -> int:
-    flags = _lib.PARAM_F32 if param_f32 else (_lib.FUSE_ACC if fuse_acc and dtype != torch.float32 else 0)
+                    param_f32: bool = False, fuse_acc=False) -> int:
+    flags = _lib.PARAM_F32 if param_f32 else (_perm(fuse_acc) if dtype != torch.float32 else 0)
     return _workspace_bytes(_lib.load(), T, d_in, d_out, r, r_acc, kind, _DT[dtype] | flags)
 
 
@@ -385,13 +465,13 @@ def sow_backward(dy2: torch.Tensor, x2: torch.Tensor, h: torch.Tensor, A: torch.
                  out: Optional[Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]] = None,
                  grad_beta: float = 0.0, *, phases: int = _lib.BWD_DATA | _lib.BWD_WEIGHTS,
                  dx: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, param_f32: bool = False,
-                 fuse_acc: bool = False):
+                 fuse_acc=False):
     """dx, dA, dB, dbias.  `out` = (dA, dB, dbias) buffers to write/accumulate into (grad_beta).
     `phases` selects the data-gradient and / or weight-gradient kernels (see include/sow_amd.h); a split
     call must pass the same `workspace` (and `dx`) to both phases, each enqueued on the current stream.
     param_f32: fp32 parameters with bf16 / f16 activations (sow_forward); dA, dB and dbias are then fp32, dx of x2's dtype.
-    fuse_acc: the SOW_FUSE_ACC permission for the data gradient (sow_forward); a workspace passed in must then come from
-    workspace_bytes(..., fuse_acc=True), a smaller one makes the call run the two-pass kernels."""
+    fuse_acc: the permission for the data gradient (sow_forward); a workspace passed in must then come from
+    workspace_bytes(..., fuse_acc=the same value), a smaller one makes the call run the unflagged kernels."""
     lib = _lib.load()
     dev = _need_gpu(dy2, x2, h, A, B)
     dt, pdt = _call_dtype(x2, param_f32, fuse_acc=fuse_acc)
@@ -417,8 +497,8 @@ def sow_backward(dy2: torch.Tensor, x2: torch.Tensor, h: torch.Tensor, A: torch.
             raise TypeError(f"sow_amd: gradient buffers must be {pdt}")
     nws = _workspace_bytes(lib, T, d_in, d_out, r, r_acc, kind, dt)
     ws = _ws(nws, dev) if workspace is None else workspace
-    if ws.numel() < nws and dt & _lib.FUSE_ACC:   # a permission: a workspace of the unflagged plan runs the two-pass kernels
-        nws = _workspace_bytes(lib, T, d_in, d_out, r, r_acc, kind, dt & ~_lib.FUSE_ACC)
+    if ws.numel() < nws and dt & _PERMS:   # a permission: a workspace of the unflagged plan runs the unflagged kernels
+        nws = _workspace_bytes(lib, T, d_in, d_out, r, r_acc, kind, dt & ~_PERMS)
     if ws.numel() < nws:
         raise ValueError("sow_amd: workspace too small")
     _launch(dev, "sow_backward", lib.sow_backward_ex, _ptr(dy2), _ptr(x2), _ptr(h), _ptr(A), _ptr(B),
@@ -437,7 +517,7 @@ class LayerCall:
                  out=None, grad_beta=0.0, workspace=None, forward_only=False, save_h=True, param_f32=False, fuse_acc=False):
         dev = _need_gpu(x2, A, B, bias, y, h, dy2, dx, workspace)
         # param_f32: fp32 A, B, bias, accumulator and gradients, activations of the compute dtype (SOW_PARAM_F32)
-        # fuse_acc: the SOW_FUSE_ACC permission; it rides in the dtype, so the workspace queries below are the flagged ones
+        # fuse_acc: the call's permission (_perm); it rides in the dtype, so the workspace queries below are the flagged ones
         self.dtype, pdt = _call_dtype(x2, param_f32, "sow_amd.LayerCall", fuse_acc=fuse_acc)
         T, d_in = x2.shape
         r, d_out = B.shape
@@ -464,10 +544,10 @@ class LayerCall:
         nws = (_forward_workspace_bytes(_lib.load(), T, d_in, d_out, r, r_acc, kind, self.dtype) if forward_only
                else _workspace_bytes(_lib.load(), T, d_in, d_out, r, r_acc, kind, self.dtype))
         self.workspace = workspace if workspace is not None else (_ws(nws, dev) if nws else None)
-        if self.workspace is not None and self.workspace.numel() < nws and self.dtype & _lib.FUSE_ACC:
+        if self.workspace is not None and self.workspace.numel() < nws and self.dtype & _PERMS:
             # a permission: a caller's workspace of the unflagged plan runs the two-pass kernels
             q = _forward_workspace_bytes if forward_only else _workspace_bytes
-            nws = q(_lib.load(), T, d_in, d_out, r, r_acc, kind, self.dtype & ~_lib.FUSE_ACC)
+            nws = q(_lib.load(), T, d_in, d_out, r, r_acc, kind, self.dtype & ~_PERMS)
         if self.workspace is not None and self.workspace.numel() < nws:
             raise ValueError("sow_amd.LayerCall: workspace too small")
         dA, dB, dbias = out if out is not None else (None, None, None)
@@ -498,36 +578,38 @@ class LayerGroup:
     def __init__(self, calls: Sequence[LayerCall]):
         if not calls:
             raise ValueError("empty group")
-        if len({c.dtype & ~_lib.FUSE_ACC for c in calls}) != 1 or len({c.device for c in calls}) != 1:
+        if len({c.dtype & ~_PERMS for c in calls}) != 1 or len({c.device for c in calls}) != 1:
             raise ValueError("sow_amd.LayerGroup: all layers must share dtype and device")
         self.calls = list(calls)
         self.arr = (_lib.LayerArgs * len(calls))(*[c.args for c in calls])
-        # SOW_FUSE_ACC rides in the dtype of the whole C call, the permission belongs to each LayerCall: a group of flagged
-        # and unflagged layers issues its forward and its data gradient as two C calls, one per kind (such layers never
-        # share a launch anyway: a low-rank accumulator takes the per-layer fall-through).  The weight-gradient phases and
-        # their plans ignore the flag and always see the whole group.
-        fused = [bool(c.dtype & _lib.FUSE_ACC) for c in calls]
-        self._fused = fused if any(fused) and not all(fused) else None
-        self.dtype, self.device = calls[0].dtype & ~_lib.FUSE_ACC | (_lib.FUSE_ACC if all(fused) else 0), calls[0].device
+        # A permission rides in the dtype of the whole C call and belongs to each LayerCall: a group whose layers hold
+        # different values (none, SOW_FUSE_ACC, SOW_FUSE_ACC_DEEP) issues its forward and its data gradient as one C call
+        # per value (such layers never share a launch anyway: a low-rank accumulator takes the per-layer fall-through).  The
+        # weight-gradient phases and their plans ignore the flags and always see the whole group.
+        self._perms = [c.dtype & _PERMS for c in calls]
+        mixed = len(set(self._perms)) > 1
+        self._fused = [p == _lib.FUSE_ACC for p in self._perms] if mixed else None   # None: one value, one C call
+        self.dtype, self.device = calls[0].dtype & ~_PERMS | (0 if mixed else self._perms[0]), calls[0].device
 
     @classmethod
     def from_args(cls, arr, n: int, dtype: int, device, keep=None) -> "LayerGroup":
         """A group over a ready-made sow_layer_args array (the caller has validated the tensors and keeps them alive --
         `keep` -- until the launches that read the raw pointers have been enqueued)."""
         g = cls.__new__(cls)
-        g.calls, g.arr, g.dtype, g.device, g._keep, g._fused = [None] * n, arr, dtype, device, keep, None
+        g.calls, g.arr, g.dtype, g.device, g._keep, g._fused, g._perms = [None] * n, arr, dtype, device, keep, None, None
         return g
 
     def _by_permission(self):
-        """(sow_layer_args array, n, dtype) of the flagged and of the unflagged layers of a mixed group.  Rebuilt from
+        """(sow_layer_args array, n, dtype) per permission value of a mixed group, in the order SOW_FUSE_ACC,
+        SOW_FUSE_ACC_DEEP, none (values no layer holds are left out).  Rebuilt from
         self.arr at every call, not cached: callers and subclasses edit self.arr after construction (SharedInputGroup points
         every dx at the first), and only direct users of LayerGroup reach a mixed group -- the module surface gives siblings
         one decision."""
         out = []
-        for want in (True, False):
-            idx = [i for i, f in enumerate(self._fused) if f == want]
-            out.append(((_lib.LayerArgs * len(idx))(*[self.arr[i] for i in idx]), len(idx),
-                        self.dtype | (_lib.FUSE_ACC if want else 0)))
+        for want in (_lib.FUSE_ACC, _lib.FUSE_ACC_DEEP, 0):
+            idx = [i for i, p in enumerate(self._perms) if p == want]
+            if idx:
+                out.append(((_lib.LayerArgs * len(idx))(*[self.arr[i] for i in idx]), len(idx), self.dtype | want))
         return out
 
     def forward(self) -> None:
