@@ -81,8 +81,6 @@ using namespace sow;
 static inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 static inline size_t esize(int dtype) { return dtype == SOW_F32 ? 4 : 2; }
 static inline bool ok_dtype(int d) { return d == SOW_F32 || d == SOW_BF16 || d == SOW_F16; }
-static inline bool al4p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-static inline bool al16p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // The dtype argument of an entry point, decoded once.  SOW_FUSE_ACC and SOW_FUSE_ACC_DEEP are permissions and are ignored
 // together with SOW_PARAM_F32.
 // The layer entry points, their plans and descriptors take what layer_ok() admits; sow_*_shared refuses SOW_PARAM_F32 as
@@ -157,24 +155,66 @@ static int launch_chain_short(const ChainParams& p, int dtype, bool bwd, float* 
   return f32 ? launch_chain2f(b, bwd, stream) : launch_chain2(b, bwd, dtype, stream);
 }
 
-// row-major A, plain product: the streaming kernel when it fills the chip, else the 128x128 kernel
-static int gemm_auto(const void* A, int64_t lda, const void* B, int64_t ldb, bool transB, void* C, int64_t ldc,
-                     const void* bias, int64_t M, int N, int K, float alpha, float beta, int dtype, hipStream_t stream,
-                     void* ws = nullptr, size_t ws_bytes = 0) {
+// ---- dense products with a row-major A (trans_a = 0): which kernel writes C -----------------------------------------
+// The one place where the kernel of  C = alpha (A . op(B) + A2 . op(B2)) + beta C + bias  is chosen.  pick_gemm reads the
+// operands, the split-K scratch and the switches and launches nothing; launch_picked launches what it said.
+// t256 / t128: output tiles of 256 x 256 / 128 x 128.  `work`: gemm4's workgroups, t256 x its K-splits with this scratch.
+//   * gemm4 (anti-phase wave groups, 64-wide K-tiles) is 15-30 % faster than the older main loops wherever its tiles fill at
+//     least half of the chip (work >= 120; profiles/r03_gemm4_vs_round2_vs_hipblaslt.txt: 4096^3 1.38 vs 0.97-1.03 PF, 32768 x
+//     512 -> 1376 58 vs 72 us).  With scratch from the caller, short products (<= 128 tiles, long K) reach that split over K:
+//     M = 1024 x N = 4096 as 64 tiles x 4 splits instead of gemm3s's 256 small tiles.  GEMM4 = 1 forces it on every shape it
+//     supports, 0 forbids it.
+//   * bf16 below that: with fewer than 160 big tiles the 128 x 128 tiles of gemm3s fill more CUs; from K ~ 2048 on the
+//     one-wave-per-SIMD gemm3 is 7-19 % ahead of gemm2 (4096^3: 1.05 vs 0.90-0.96 PF), at K <= 1376 they are level or gemm2 is
+//     ahead.  GEMM3S and GEMM3 = 1 / 0 force or forbid either.
+//   * bf16 products too small for gemm3s (t128 < 96, or K < 512, or NO_GEMM3S) and every other dtype: the generic kernel.
+// Asymmetries, kept as they were measured and tested:
+//   * the bf16 gate stands before gemm4 and f16 has none: 120-159 big tiles with K < 512 are generic in bf16, gemm4 in f16;
+//   * NO_GEMM3S acts only in the gate (a product that passes it may still take gemm3s); GEMM3S = 0 acts only after it;
+//   * t256 >= 160 with 32 <= K < 64: gemm4 needs K >= 64, so bf16 takes gemm2_kernel by default;
+//   * GEMM4 = 1 with K < 64 (gemm4_supported fails) falls through to the others.
+enum GemmKernel { GEMM_GENERIC, GEMM_2, GEMM_3, GEMM_3S, GEMM_4 };
+static GemmKernel pick_gemm(const ExtGemm& g, int dtype, const void* ws, size_t ws_bytes) {
+  if (dtype != SOW_BF16 && dtype != SOW_F16) return GEMM_GENERIC;
+  const int64_t t256 = (int64_t)ceil_div(g.M, 256) * ceil_div(g.N, 256);
+  const int g4 = sw(SW_GEMM4);
+  auto half_chip = [&] { return t256 * gemm4_splits(g.M, g.N, g.K, g.A2 != nullptr, ws, ws_bytes) >= 120; };
   if (dtype == SOW_F16) {
-    // f16 has gemm4 (and its split-K form) only: taken where its 256 x 256 tiles fill at least half of the chip, as for bf16
-    // (launch_gemm2); shorter products and the FORCE_GEMM_V1 / GEMM4 = 0 switches take the generic kernel
-    const int g4 = sw(SW_GEMM4);
-    const int64_t work = (int64_t)ceil_div(M, 256) * ceil_div(N, 256) * gemm4_splits(M, N, K, false, ws, ws_bytes);
-    if (!sw_on(SW_FORCE_GEMM_V1) && (g4 > 0 || (g4 < 0 && work >= 120)) &&
-        gemm4_supported(A, lda, B, ldb, transB, nullptr, 0, nullptr, 0, C, ldc, bias, M, N, K, dtype))
-      return launch_gemm4(A, lda, B, ldb, transB, nullptr, 0, nullptr, 0, 0, C, ldc, bias, M, N, K, alpha, beta, stream, ws,
-                          ws_bytes, dtype);
-    return launch_gemm(A, lda, false, B, ldb, transB, C, ldc, bias, M, N, K, alpha, beta, dtype, stream);
+    // f16 has gemm4 (and its split-K form) only, and no caller with a K-extension
+    const bool take = !g.A2 && !sw_on(SW_FORCE_GEMM_V1) && (g4 > 0 || (g4 < 0 && half_chip())) && gemm4_supported(g, dtype);
+    return take ? GEMM_4 : GEMM_GENERIC;
   }
-  if (gemm2_supported(A, lda, B, ldb, transB, nullptr, 0, nullptr, 0, C, ldc, bias, M, N, K, dtype))
-    return launch_gemm2(A, lda, B, ldb, transB, nullptr, 0, nullptr, 0, 0, C, ldc, bias, M, N, K, alpha, beta, stream, ws, ws_bytes);
-  return launch_gemm(A, lda, false, B, ldb, transB, C, ldc, bias, M, N, K, alpha, beta, dtype, stream);
+  // the bf16 gate
+  if (!ext_gemm_operands_ok(g) || g.N < 64 || g.K < 32) return GEMM_GENERIC;
+  const int64_t t128 = (int64_t)ceil_div(g.M, 128) * ceil_div(g.N, 128);
+  if (t256 < 160 && (t128 < 96 || g.K < 512 || sw_on(SW_NO_GEMM3S))) return GEMM_GENERIC;
+  if (sw_on(SW_FORCE_GEMM_V1)) return GEMM_GENERIC;   // A/B switch, as SOW_AMD_FORCE_CHAIN_V1
+  if ((g4 > 0 || (g4 < 0 && half_chip() && g.K >= 64)) && gemm4_supported(g, SOW_BF16)) return GEMM_4;
+  const int gs = sw(SW_GEMM3S);
+  if (gs >= 0 ? gs != 0 : t256 < 160) return GEMM_3S;
+  const int g3 = sw(SW_GEMM3);
+  if (g3 >= 0 ? g3 != 0 : g.K >= 2048) return GEMM_3;
+  return GEMM_2;
+}
+// dtype: of the call pick_gemm saw (gemm2 / gemm3 / gemm3s are picked for SOW_BF16 only); the generic kernel has no
+// K-extension, so a product with one that no streaming kernel takes is refused (dense_ext_term asks before it launches)
+static int launch_picked(GemmKernel k, const ExtGemm& g, int dtype, void* ws, size_t ws_bytes, hipStream_t stream) {
+  switch (k) {
+    case GEMM_4: return launch_gemm4(g, dtype, ws, ws_bytes, stream);
+    case GEMM_3S: return launch_gemm3s(g, stream);
+    case GEMM_3: return launch_gemm3(g, stream);
+    case GEMM_2: return launch_gemm2(g, stream);
+    default: break;
+  }
+  if (g.A2) return SOW_ERR_UNSUPPORTED;
+  return launch_gemm(g.A, g.lda, false, g.B, g.ldb, g.nt, g.C, g.ldc, g.bias, g.M, g.N, g.K, g.alpha, g.beta, dtype, stream);
+}
+// the plain product C = alpha A . op(B) + beta C + bias on the kernel pick_gemm chooses
+static int gemm_auto(const void* A, int64_t lda, const void* B, int64_t ldb, bool transB, void* C, int64_t ldc, const void* bias,
+                     int64_t M, int N, int K, float alpha, float beta, int dtype, hipStream_t stream, void* ws = nullptr,
+                     size_t ws_bytes = 0) {
+  const ExtGemm g{A, B, nullptr, nullptr, C, bias, M, lda, ldb, 0, 0, ldc, N, K, 0, transB, alpha, beta};
+  return launch_picked(pick_gemm(g, dtype, ws, ws_bytes), g, dtype, ws, ws_bytes, stream);
 }
 
 extern "C" {
@@ -582,33 +622,9 @@ static int shared_fused_acc_data(const sow_layer_args* layers, int n, const Dtyp
 
 // Dense accumulator, r_live <= 64: the product with the live term as a K-extension,  Y = [X, H] . [op(W); F2] + bias,
 // H = scale * X . F1.  The operands of one layer and direction, as the one-launch kernels (gemm4h, gemm2h) take them:
-static Gemm2hArgs dense_args(const DirView& v) {
-  return Gemm2hArgs{v.X, v.W, v.live.F1, v.live.F2, v.Y, v.bias, v.H, v.M, v.D1, v.ldw, v.live.ld1, v.live.ld2, v.D2,
-                    v.D2, v.D1, v.live.r, v.scale};
-}
-static bool gemm4h_ok(const Gemm2hArgs& g, bool nt, int dtype) {
-  return gemm4h_supported(g.X, g.ldx, g.W, g.ldw, nt, g.F, g.ldf, g.G, g.ldg, g.C, g.ldc, g.bias, g.H, g.M, g.N, g.K, g.r, dtype);
-}
-static int run_gemm4h(const Gemm2hArgs& g, bool nt, int dtype, hipStream_t stream) {
-  return launch_gemm4h(g.X, g.ldx, g.W, g.ldw, nt, g.F, g.ldf, g.G, g.ldg, g.C, g.ldc, g.bias, g.H, g.M, g.N, g.K, g.r, g.hscale,
-                       dtype, stream);
-}
-static bool gemm2h_ok(const Gemm2hArgs& g, bool nt, int dtype) {
-  return gemm2h_supported(g.X, g.ldx, g.W, g.ldw, nt, g.F, g.ldf, g.G, g.ldg, g.C, g.ldc, g.bias, g.H, g.M, g.N, g.K, g.r, dtype);
-}
-static int run_gemm2h(const Gemm2hArgs& g, bool nt, hipStream_t stream) {
-  return launch_gemm2h(g.X, g.ldx, g.W, g.ldw, nt, g.F, g.ldf, g.G, g.ldg, g.C, g.ldc, g.bias, g.H, g.M, g.N, g.K, g.r, g.hscale,
-                       stream);
-}
-// the two-launch composition of the same product: H (64 columns) from a chain launch, then gemm2 with the extension operand
-// E [ke rows of N] -- the forward reads B in place (ke = r_live), the data gradient A zero-padded to 64 columns (ke = 64)
-static bool gemm2_ext_ok(const Gemm2hArgs& g, bool nt, const void* E, int64_t lde, int dtype) {
-  return gemm2_supported(g.X, g.ldx, g.W, g.ldw, nt, g.H, 64, E, lde, g.C, g.ldc, g.bias, g.M, g.N, g.K, dtype);
-}
-static int run_gemm2_ext(const Gemm2hArgs& g, bool nt, const void* E, int64_t lde, int ke, hipStream_t stream, void* sk,
-                         size_t sk_bytes) {
-  return launch_gemm2(g.X, g.ldx, g.W, g.ldw, nt, g.H, 64, E, lde, ke, g.C, g.ldc, g.bias, g.M, g.N, g.K, 1.f, 0.f, stream, sk,
-                      sk_bytes);
+static ProjGemm dense_args(const DirView& v) {
+  return ProjGemm{v.X, v.W, v.live.F1, v.live.F2, v.Y, v.bias, v.H, v.M, v.D1, v.ldw, v.live.ld1, v.live.ld2, v.D2,
+                  v.D2, v.D1, v.live.r, v.scale};
 }
 // Y = X . op(W) alone (the live term follows with beta = 1); rag: an admitted ragged layer
 static int dense_product(const DirView& v, bool rag, int dtype, hipStream_t stream) {
@@ -617,20 +633,29 @@ static int dense_product(const DirView& v, bool rag, int dtype, hipStream_t stre
 }
 // The dense accumulator and the live term (r_live <= 64) as one product, one direction: gemm4h (projection pass + anti-phase
 // main loop in one launch, the factors read in place), else gemm2h (one launch, H projected inside the GEMM, where the output
-// spans at most two column tiles), else H from a chain launch and gemm2 with the extension.  *taken = false (and SOW_OK):
-// none applies, nothing launched, the caller writes the dense product and the live term separately.
+// spans at most two column tiles), else the two-launch composition: H (64 columns) from a chain launch, then the streaming
+// kernel pick_gemm chooses with the extension operand E [ke rows of N].  *taken = false (and SOW_OK): none applies, nothing
+// launched, the caller writes the dense product and the live term separately.
 static int dense_ext_term(const sow_layer_args& L, const DirView& v, const LayerRun& c, bool* taken) {
-  const Gemm2hArgs g = dense_args(v);
+  const ProjGemm g = dense_args(v);
   *taken = true;
-  if (gemm4h_ok(g, v.bwd, c.dtype)) return run_gemm4h(g, v.bwd, c.dtype, c.stream);
-  if (gemm2h_ok(g, v.bwd, c.dtype)) return run_gemm2h(g, v.bwd, c.stream);
+  if (gemm4h_supported(g, v.bwd, c.dtype)) return launch_gemm4h(g, v.bwd, c.dtype, c.stream);
+  if (gemm2h_supported(g, v.bwd, c.dtype)) return launch_gemm2h_group(&g, 1, v.bwd, c.stream);
   ChainParams ph = live_chain(v, 0.f, true);
   set_planes(ph, c.ws, c.w, c.bytes);
   // the extension operand: the forward reads B in place, the data gradient A zero-padded to 64 columns (workspace)
   void* apad = v.bwd ? c.ws + c.w.off_apad : nullptr;
   const void* E = v.bwd ? apad : L.B;
   const int64_t lde = v.bwd ? 64 : L.d_out;
-  if (!chain2_supported(ph, c.dtype) || !gemm2_ext_ok(g, v.bwd, E, lde, c.dtype)) {
+  // the split-K scratch of the plan, where the workspace holds it
+  const bool scratch = c.ws && c.bytes >= c.w.total;
+  const bool sk = scratch && c.w.sk_bytes;
+  void* const skp = sk ? c.ws + c.w.off_sk : nullptr;
+  const size_t skb = sk ? c.w.sk_bytes : 0;
+  // ke = r_live rows of B (forward), the 64 columns of the padded A (data gradient)
+  const ExtGemm e{g.X, g.W, g.H, E, g.C, g.bias, g.M, g.ldx, g.ldw, 64, lde, g.ldc, g.N, g.K, v.bwd ? 64 : L.r_live, v.bwd, 1.f, 0.f};
+  const GemmKernel k = chain2_supported(ph, c.dtype) ? pick_gemm(e, c.dtype, skp, skb) : GEMM_GENERIC;
+  if (k == GEMM_GENERIC) {
     *taken = false;
     return SOW_OK;
   }
@@ -639,14 +664,12 @@ static int dense_ext_term(const sow_layer_args& L, const DirView& v, const Layer
   if (pad_fused) ph.pad_src = L.A, ph.pad_dst = apad, ph.pad_rows = L.d_in, ph.pad_r = L.r_live;
   // short T: the H-only pass split over K (T / 64 workgroups cannot fill the chip: 29 us on 16 workgroups at 1024 x 4096);
   // launch_chain_short itself refuses longer inputs
-  const bool scratch = c.ws && c.bytes >= c.w.total;
   int rc = SOW_ERR_UNSUPPORTED;
   if (scratch) rc = launch_chain_short(ph, c.dtype, v.bwd, (float*)(c.ws + c.w.off_hp), c.stream);
   if (rc == SOW_ERR_UNSUPPORTED) rc = launch_chain2(ph, v.bwd, c.dtype, c.stream);
   if (rc) return rc;
   if (v.bwd && !pad_fused && (rc = launch_pad64(L.A, apad, L.d_in, L.r_live, c.stream))) return rc;
-  const bool sk = scratch && c.w.sk_bytes;
-  return run_gemm2_ext(g, v.bwd, E, lde, v.bwd ? 64 : L.r_live, c.stream, sk ? c.ws + c.w.off_sk : nullptr, sk ? c.w.sk_bytes : 0);
+  return launch_picked(k, e, c.dtype, skp, skb, c.stream);
 }
 
 // An admitted ragged layer (rag_layer), one direction: the fused chain for the low-rank accumulator (scale 1) and for the
@@ -1042,7 +1065,7 @@ static int forward_group_impl(const sow_layer_args* layers, int n, int dtype, in
   if (n == 0) return SOW_OK;
   if (!layers) return SOW_ERR_NULL;
   ChainParams batch[C2_MAXG];
-  Gemm2hArgs gbatch[4];
+  ProjGemm gbatch[4];
   int nb = 0, ng = 0, rc;
   for (int i = 0; i < n; ++i) {
     const sow_layer_args& L = layers[i];
@@ -1056,14 +1079,14 @@ static int forward_group_impl(const sow_layer_args* layers, int n, int dtype, in
       continue;
     }
     if (L.acc_kind == SOW_ACC_DENSE && L.r_live <= 64 && L.h_save) {
-      const Gemm2hArgs g = dense_args(dir_view(L, false, nullptr));
+      const ProjGemm g = dense_args(dir_view(L, false, nullptr));
       // dense accumulator: gemm4h (one launch per layer) where it applies
-      if (gemm4h_ok(g, false, dtype)) {
-        if ((rc = run_gemm4h(g, false, dtype, stream))) return rc;
+      if (gemm4h_supported(g, false, dtype)) {
+        if ((rc = launch_gemm4h(g, false, dtype, stream))) return rc;
         continue;
       }
       // dense accumulator, one launch per layer (gemm2h): the layers of a group share the grid
-      if (!sw_on(SW_NO_GROUPED) && gemm2h_ok(g, false, dtype)) {
+      if (!sw_on(SW_NO_GROUPED) && gemm2h_supported(g, false, dtype)) {
         gbatch[ng] = g;
         if (++ng == 4) {
           if ((rc = launch_gemm2h_group(gbatch, ng, false, stream))) return rc;
@@ -1160,7 +1183,7 @@ static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, i
     if ((rc = check_layer(layers[i], true, false))) return rc;
   if (ph.data) {
     ChainParams batch[C2_MAXG];
-    Gemm2hArgs gbatch[4];
+    ProjGemm gbatch[4];
     int nb = 0, ng = 0;
     for (int i = 0; i < n; ++i) {
       const sow_layer_args& L = layers[i];
@@ -1178,12 +1201,12 @@ static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, i
         continue;
       }
       if (L.acc_kind == SOW_ACC_DENSE && L.r_live <= 64) {
-        const Gemm2hArgs g = dense_args(dir_view(L, true, ws_base(L.workspace) + w.off_dh));
-        if (gemm4h_ok(g, true, dtype)) {
-          if ((rc = run_gemm4h(g, true, dtype, stream))) return rc;
+        const ProjGemm g = dense_args(dir_view(L, true, ws_base(L.workspace) + w.off_dh));
+        if (gemm4h_supported(g, true, dtype)) {
+          if ((rc = launch_gemm4h(g, true, dtype, stream))) return rc;
           continue;
         }
-        if (!sw_on(SW_NO_GROUPED) && gemm2h_ok(g, true, dtype)) {
+        if (!sw_on(SW_NO_GROUPED) && gemm2h_supported(g, true, dtype)) {
           gbatch[ng] = g;
           if (++ng == 4) {
             if ((rc = launch_gemm2h_group(gbatch, ng, true, stream))) return rc;

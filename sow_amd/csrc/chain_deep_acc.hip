@@ -114,11 +114,9 @@ bool deep_acc_shape_ok(int r_live, int r_acc, int d_in, int d_out, int dtype) {
 }
 size_t deep_acc_lds_bytes(int r_tot) { return (size_t)((r_tot + 63) / 64 * 64) * 128 + DEEP_STAGE; }
 
-static bool al16d(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 int launch_chain_deep_acc(const WideAccArgs& a, int dtype, hipStream_t stream) {
   if (!deep_acc_shape_ok(a.r_live, a.r_acc, a.D1, a.D2, dtype)) return SOW_ERR_UNSUPPORTED;
-  if (!al16d(a.X) || !al16d(a.Y) || !al16d(a.bias) || !al16d(a.Hsave) || !a.pack || !al16d(a.pack) ||
+  if (!al16p(a.X) || !al16p(a.Y) || !al16p(a.bias) || !al16p(a.Hsave) || !a.pack || !al16p(a.pack) ||
       a.pack_bytes < chain_wide_pack_bytes(a.r_acc + a.r_live, a.D1, a.D2))
     return SOW_ERR_UNSUPPORTED;
   const size_t lds = deep_acc_lds_bytes(a.r_acc + a.r_live);

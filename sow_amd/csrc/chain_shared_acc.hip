@@ -157,16 +157,14 @@ bool shared_acc_lds_ok(const int* r_tot, int n) {
   return b != 0 && b <= SHA_MAX_LDS;
 }
 
-static bool al16s(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 int launch_chain_shared_acc(const WideAccArgs* sib, int n, void* dX, float beta, int dtype, hipStream_t stream) {
-  if (n < 1 || n > SHA_MAXN || !dX || !al16s(dX)) return SOW_ERR_UNSUPPORTED;
+  if (n < 1 || n > SHA_MAXN || !dX || !al16p(dX)) return SOW_ERR_UNSUPPORTED;
   int r_tot[SHA_MAXN];
   for (int i = 0; i < n; ++i) {
     const WideAccArgs& a = sib[i];
     if (!a.bwd || a.M != sib[0].M || a.D2 != sib[0].D2 || !fused_acc_shape_ok(a.r_live, a.r_acc, a.D1, a.D2, dtype))
       return SOW_ERR_UNSUPPORTED;
-    if (!a.X || !al16s(a.X) || !a.Hsave || !al16s(a.Hsave) || !a.pack || !al16s(a.pack) ||
+    if (!a.X || !al16p(a.X) || !a.Hsave || !al16p(a.Hsave) || !a.pack || !al16p(a.pack) ||
         a.pack_bytes < chain_wide_pack_bytes(a.r_acc + a.r_live, a.D1, a.D2))
       return SOW_ERR_UNSUPPORTED;
     r_tot[i] = a.r_acc + a.r_live;

@@ -121,12 +121,10 @@ size_t chain_wide_pack_bytes(int r, int d_in, int d_out) {
   return ((r_pad * p_in * 2 + 255) & ~(size_t)255) + ((r_pad * p_out * 2 + 255) & ~(size_t)255);
 }
 
-static bool al16w(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 int launch_chain_wide(const WideArgs& a, int dtype, hipStream_t stream) {
   const bool rag = a.D1 % 8 != 0 || a.D2 % 8 != 0;
   if (!(rag ? ragged_shape_ok(a.r, a.D1, a.D2, dtype) : chain_wide_shape_ok(a.r, a.D1, a.D2, dtype))) return SOW_ERR_UNSUPPORTED;
-  if ((rag && a.r <= 64 && a.Hsave) || !al16w(a.X) || !al16w(a.Y) || (a.bias && !al16w(a.bias)) || !al16w(a.pack) ||
+  if ((rag && a.r <= 64 && a.Hsave) || !al16p(a.X) || !al16p(a.Y) || (a.bias && !al16p(a.bias)) || !al16p(a.pack) ||
       (a.Hsave && (reinterpret_cast<uintptr_t>(a.Hsave) & 3)) || !a.pack ||
       a.pack_bytes < chain_wide_pack_bytes(a.r, a.D1, a.D2))
     return SOW_ERR_UNSUPPORTED;

@@ -95,11 +95,9 @@ bool fused_acc_shape_ok(int r_live, int r_acc, int d_in, int d_out, int dtype) {
          r_acc % 2 == 0 && r_acc + r_live <= 256 && d_in > 0 && d_out > 0 && d_in % 8 == 0 && d_out % 8 == 0;
 }
 
-static bool al16a(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 int launch_chain_wide_acc(const WideAccArgs& a, int dtype, hipStream_t stream) {
   if (!fused_acc_shape_ok(a.r_live, a.r_acc, a.D1, a.D2, dtype)) return SOW_ERR_UNSUPPORTED;
-  if (!al16a(a.X) || !al16a(a.Y) || !al16a(a.bias) || !al16a(a.Hsave) || !a.pack || !al16a(a.pack) ||
+  if (!al16p(a.X) || !al16p(a.Y) || !al16p(a.bias) || !al16p(a.Hsave) || !a.pack || !al16p(a.pack) ||
       a.pack_bytes < chain_wide_pack_bytes(a.r_acc + a.r_live, a.D1, a.D2))
     return SOW_ERR_UNSUPPORTED;
   if (a.M <= 0) return SOW_OK;

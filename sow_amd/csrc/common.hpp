@@ -134,6 +134,10 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 
 inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// host: pointer alignment to 16 bytes (DMA pieces, vector loads and stores) / to 4 bytes; nullptr counts as aligned
+inline bool al16p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline bool al4p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+
 // Raise a kernel's dynamic-LDS limit once per DEVICE (the attribute is per device; thread-safe: forward runs on the
 // caller's thread, backward on the autograd thread -- two threads racing here both set the same value).  The kernel
 // expression goes last because template-ids contain commas.

@@ -229,9 +229,6 @@ template <typename T, bool TA, bool TB, typename TC = T> static int launch_gemm_
   return SOW_OK;
 }
 
-static bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-static bool al4(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; }
-
 // C[M,N] = alpha * op(A) op(B) + beta * C + bias.   transA: A stored [K,M]; transB: B stored [N,K].
 int launch_gemm(const void* A, int64_t lda, bool transA, const void* B, int64_t ldb, bool transB, void* C, int64_t ldc,
                 const void* bias, int64_t M, int N, int K, float alpha, float beta, int dtype, hipStream_t stream) {
@@ -253,14 +250,14 @@ int launch_gemm_out(const void* A, int64_t lda, bool transA, const void* B, int6
   // mode 2 = vector/dword staging, 0 = scalar.  k-contiguous operands need 16-byte aligned rows along k;
   // k-major operands need aligned rows along m/n (f32: 16 bytes; bf16: dword pairs -> even extents).
   auto mode = [&](const void* ptr, int64_t ld, bool kcontig, int64_t rows) -> int {
-    if (kcontig) return (ld % ve == 0 && K % ve == 0 && al16(ptr)) ? 2 : 0;
-    if (dtype == SOW_F32) return (ld % 4 == 0 && rows % 4 == 0 && al16(ptr)) ? 2 : 0;
-    return (ld % 2 == 0 && rows % 2 == 0 && al4(ptr)) ? 2 : 0;
+    if (kcontig) return (ld % ve == 0 && K % ve == 0 && al16p(ptr)) ? 2 : 0;
+    if (dtype == SOW_F32) return (ld % 4 == 0 && rows % 4 == 0 && al16p(ptr)) ? 2 : 0;
+    return (ld % 2 == 0 && rows % 2 == 0 && al4p(ptr)) ? 2 : 0;
   };
   p.vecA = mode(A, lda, !transA, M);
   p.vecB = mode(B, ldb, transB, N);
   const int vc = c_dtype == SOW_F32 ? 4 : 8;
-  p.vecC = (ldc % vc == 0 && N % vc == 0 && al16(C) && (!bias || al16(bias))) ? 1 : 0;
+  p.vecC = (ldc % vc == 0 && N % vc == 0 && al16p(C) && (!bias || al16p(bias))) ? 1 : 0;
 #define SOW_GEMM_DISPATCH(T, TC)                                                                                     \
   if (transA)                                                                                                       \
     return transB ? launch_gemm_tt<T, true, true, TC>(p, stream) : launch_gemm_tt<T, true, false, TC>(p, stream);   \

@@ -38,20 +38,7 @@ constexpr int G2_STAGE = 2 * G2_PIECE;          // 32 KiB
 constexpr int G2_LDS = G2_NSLOT * G2_STAGE;     // 128 KiB
 constexpr int G2_DPW = 4;                       // DMA instructions per wave per stage (2 A + 2 B)
 
-
-struct Gemm2Params {
-  const bf16_t* A;
-  const bf16_t* B;
-  const bf16_t* A2;   // [M, 64] or nullptr
-  const bf16_t* B2;   // NT: [N, 64]; NN: [k2, N]
-  bf16_t* C;
-  const bf16_t* bias;
-  int64_t M, lda, ldb, lda2, ldb2, ldc;
-  int N, K, k2;
-  float alpha, beta;
-};
-
-template <bool NT> __global__ __launch_bounds__(G2_THREADS, 1) void gemm2_kernel(const Gemm2Params p) {
+template <bool NT> __global__ __launch_bounds__(G2_THREADS, 1) void gemm2_kernel(const ExtGemmParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int t = threadIdx.x, lane = t & 63;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -234,60 +221,30 @@ int launch_pad64(const void* in, void* out, int rows, int r, hipStream_t stream)
 }
 
 // ------------------------------------------------------------------------------------------------
-static bool g2_al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
-bool gemm2_supported(const void* A, int64_t lda, const void* B, int64_t ldb, bool nt, const void* A2, int64_t lda2,
-                     const void* B2, int64_t ldb2, const void* C, int64_t ldc, const void* bias, int64_t M, int N, int K,
-                     int dtype) {
-  if (dtype != SOW_BF16 || !A || !B || !C) return false;
-  // one 256x256 tile per CU: below ~160 tiles the 128x128 tiles of gemm3s.hip fill the chip better (launch_gemm2
-  // picks the kernel); below ~96 of those, or with a short K, the generic kernel is as good
-  if (N < 64 || K < 32) return false;
-  if ((int64_t)ceil_div(M, G2_BM) * ceil_div(N, G2_BN) < 160 &&
-      ((int64_t)ceil_div(M, 128) * ceil_div(N, 128) < 96 || K < 512 || sw_on(SW_NO_GEMM3S)))
-    return false;
-  if (sw_on(SW_FORCE_GEMM_V1)) return false;      // A/B switch, as SOW_AMD_FORCE_CHAIN_V1
-  if (K % 8 || N % 8 || lda % 8 || ldb % 8 || ldc % 8) return false;
-  if (!g2_al16(A) || !g2_al16(B) || !g2_al16(C) || (bias && !g2_al16(bias))) return false;
-  if (A2) {
-    if (!B2 || lda2 % 8 || ldb2 % 8 || !g2_al16(A2) || !g2_al16(B2)) return false;
-  }
-  (void)nt;
+bool ext_gemm_operands_ok(const ExtGemm& g) {
+  if (!g.A || !g.B || !g.C) return false;
+  if (g.K % 8 || g.N % 8 || g.lda % 8 || g.ldb % 8 || g.ldc % 8) return false;
+  if (!al16p(g.A) || !al16p(g.B) || !al16p(g.C) || !al16p(g.bias)) return false;
+  if (g.A2 && (!g.B2 || g.lda2 % 8 || g.ldb2 % 8 || !al16p(g.A2) || !al16p(g.B2))) return false;
   return true;
 }
 
-int launch_gemm2(const void* A, int64_t lda, const void* B, int64_t ldb, bool nt, const void* A2, int64_t lda2,
-                 const void* B2, int64_t ldb2, int k2, void* C, int64_t ldc, const void* bias, int64_t M, int N, int K,
-                 float alpha, float beta, hipStream_t stream, void* ws, size_t ws_bytes) {
-  Gemm2Params p;
-  p.A = (const bf16_t*)A, p.B = (const bf16_t*)B, p.A2 = (const bf16_t*)A2, p.B2 = (const bf16_t*)B2;
-  p.C = (bf16_t*)C, p.bias = (const bf16_t*)bias;
-  p.M = M, p.lda = lda, p.ldb = ldb, p.lda2 = lda2, p.ldb2 = ldb2, p.ldc = ldc;
-  p.N = N, p.K = K, p.k2 = k2 < 64 ? k2 : 64;
-  p.alpha = alpha, p.beta = beta;
-  const int64_t tiles = (int64_t)ceil_div(M, G2_BM) * ceil_div(N, G2_BN);
+ExtGemmParams ext_gemm_params(const ExtGemm& g) {
+  ExtGemmParams p;
+  p.A = (const bf16_t*)g.A, p.B = (const bf16_t*)g.B, p.A2 = (const bf16_t*)g.A2, p.B2 = (const bf16_t*)g.B2;
+  p.C = (bf16_t*)g.C, p.bias = (const bf16_t*)g.bias;
+  p.M = g.M, p.lda = g.lda, p.ldb = g.ldb, p.lda2 = g.lda2, p.ldb2 = g.ldb2, p.ldc = g.ldc;
+  p.N = g.N, p.K = g.K, p.k2 = g.k2 < 64 ? g.k2 : 64;
+  p.alpha = g.alpha, p.beta = g.beta;
+  return p;
+}
+
+int launch_gemm2(const ExtGemm& g, hipStream_t stream) {
+  const ExtGemmParams p = ext_gemm_params(g);
+  const int64_t tiles = (int64_t)ceil_div(g.M, G2_BM) * ceil_div(g.N, G2_BN);
   if (tiles <= 0) return SOW_OK;
   if (tiles > 0x7fffffff) return SOW_ERR_SHAPE;
-  // gemm4 (anti-phase wave groups, 64-wide K-tiles): 15-30 % faster than the kernels below wherever its 256 x 256 tiles
-  // fill at least half of the chip (profiles/r03_gemm4_vs_round2_vs_hipblaslt.txt: 4096^3 1.38 vs 0.97-1.03 PF, 32768 x 512
-  // -> 1376 58 vs 72 us); with fewer tiles (M = 1024 x N = 4096: 64) the 128 x 128 tiles of gemm3s fill more CUs.
-  // GEMM4 = 1 forces it on every supported shape, 0 forbids it.
-  // With scratch from the caller, short products (<= 128 tiles, long K) run gemm4 split over K: M = 1024 x N = 4096 as 64 tiles
-  // x 4 splits instead of gemm3s's 256 small tiles.
-  const int g4 = sw(SW_GEMM4);
-  const int64_t work = tiles * gemm4_splits(M, N, K, A2 != nullptr, ws, ws_bytes);
-  if ((g4 > 0 || (g4 < 0 && work >= 120 && K >= 64)) &&
-      gemm4_supported(A, lda, B, ldb, nt, A2, lda2, B2, ldb2, C, ldc, bias, M, N, K, SOW_BF16))
-    return launch_gemm4(A, lda, B, ldb, nt, A2, lda2, B2, ldb2, k2, C, ldc, bias, M, N, K, alpha, beta, stream, ws, ws_bytes);
-  const int gs = sw(SW_GEMM3S);
-  if (gs >= 0 ? gs != 0 : ((int64_t)ceil_div(M, G2_BM) * ceil_div(N, G2_BN) < 160))
-    return launch_gemm3s(A, lda, B, ldb, nt, A2, lda2, B2, ldb2, k2, C, ldc, bias, M, N, K, alpha, beta, stream);
-  // long K: the one-wave-per-SIMD kernel (gemm3.hip) is 7-19 % faster from K ~ 2048 on (4096^3: 1.05 vs 0.90-0.96 PF);
-  // at the llama_60m widths (K <= 1376) the two are level or this one is ahead.  SOW_AMD_GEMM3=1 / =0 force either.
-  const int g3 = sw(SW_GEMM3);
-  if (g3 >= 0 ? g3 != 0 : (K >= 2048))
-    return launch_gemm3(A, lda, B, ldb, nt, A2, lda2, B2, ldb2, k2, C, ldc, bias, M, N, K, alpha, beta, stream);
-  if (nt) {
+  if (g.nt) {
     SOW_SET_MAX_LDS_ONCE(G2_LDS, gemm2_kernel<true>);
     hipLaunchKernelGGL(gemm2_kernel<true>, dim3((unsigned)tiles), dim3(G2_THREADS), G2_LDS, stream, p);
   } else {

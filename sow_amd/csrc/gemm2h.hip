@@ -397,30 +397,26 @@ template <bool NT> __global__ __launch_bounds__(GH_THREADS, 1) void gemm2h_kerne
 }
 
 // ------------------------------------------------------------------------------------------------
-static bool gh_al(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; }
-
-bool gemm2h_supported(const void* X, int64_t ldx, const void* W, int64_t ldw, bool nt, const void* F, int64_t ldf,
-                      const void* G, int64_t ldg, const void* C, int64_t ldc, const void* bias, const void* H, int64_t M,
-                      int N, int K, int r, int dtype) {
-  if (dtype != SOW_BF16 || !X || !W || !F || !G || !C || !H) return false;
+bool gemm2h_supported(const ProjGemm& g, bool nt, int dtype) {
+  if (dtype != SOW_BF16 || !g.X || !g.W || !g.F || !g.G || !g.C || !g.H) return false;
   if (sw_on(SW_NO_FUSED_H) || sw_on(SW_FORCE_GEMM_V1)) return false;   // A/B switches
   // r >= 4: a 16-byte piece spans at most two 2r-byte rows, so only the LAST row has pieces crossing the end of the buffer
-  if (r < 4 || r > 64 || (r & 1)) return false;
-  if (N < 64 || K < 128) return false;
-  const int tiles_n = ceil_div(N, GH_BN);
+  if (g.r < 4 || g.r > 64 || (g.r & 1)) return false;
+  if (g.N < 64 || g.K < 128) return false;
+  const int tiles_n = ceil_div(g.N, GH_BN);
   // every column tile recomputes the projection (+25 % MFMA, +12 % DMA per tile): pays for one or two of them
-  if (tiles_n > 2 || (int64_t)ceil_div(M, GH_BM) * tiles_n < 160) return false;
-  if (K % 8 || N % 8 || ldx % 8 || ldw % 8 || ldc % 8) return false;
-  if (!gh_al(X, 16) || !gh_al(W, 16) || !gh_al(C, 16) || !gh_al(H, 16) || (bias && !gh_al(bias, 16))) return false;
+  if (tiles_n > 2 || (int64_t)ceil_div(g.M, GH_BM) * tiles_n < 160) return false;
+  if (g.K % 8 || g.N % 8 || g.ldx % 8 || g.ldw % 8 || g.ldc % 8) return false;
+  if (!al16p(g.X) || !al16p(g.W) || !al16p(g.C) || !al16p(g.H) || !al16p(g.bias)) return false;
   if (nt) {
-    if (ldf % 8 || !gh_al(F, 16) || !gh_al(G, 4)) return false;
+    if (g.ldf % 8 || !al16p(g.F) || !al4p(g.G)) return false;
   } else {
-    if (ldg % 8 || !gh_al(G, 16) || !gh_al(F, 4)) return false;
+    if (g.ldg % 8 || !al16p(g.G) || !al4p(g.F)) return false;
   }
   return true;
 }
 
-int launch_gemm2h_group(const Gemm2hArgs* a, int n, bool nt, hipStream_t stream) {
+int launch_gemm2h_group(const ProjGemm* a, int n, bool nt, hipStream_t stream) {
   if (n <= 0) return SOW_OK;
   if (n > GH_MAXG) return SOW_ERR_SHAPE;
   Gemm2hGroup g{};
@@ -447,13 +443,6 @@ int launch_gemm2h_group(const Gemm2hArgs* a, int n, bool nt, hipStream_t stream)
   }
   SOW_CHECK_LAUNCH();
   return SOW_OK;
-}
-
-int launch_gemm2h(const void* X, int64_t ldx, const void* W, int64_t ldw, bool nt, const void* F, int64_t ldf,
-                  const void* G, int64_t ldg, void* C, int64_t ldc, const void* bias, void* H, int64_t M, int N, int K,
-                  int r, float hscale, hipStream_t stream) {
-  const Gemm2hArgs a{X, W, F, G, C, bias, H, M, ldx, ldw, ldf, ldg, ldc, N, K, r, hscale};
-  return launch_gemm2h_group(&a, 1, nt, stream);
 }
 
 }  // namespace sow

@@ -22,18 +22,6 @@ constexpr int G3_PIECE = 256 * G3_BK * 2;       // 16 KiB
 constexpr int G3_STAGE = 2 * G3_PIECE;          // 32 KiB
 constexpr int G3_LDS = G3_NSLOT * G3_STAGE;     // 128 KiB
 
-struct Gemm3Params {
-  const bf16_t* A;
-  const bf16_t* B;
-  const bf16_t* A2;   // [M, 64] or nullptr
-  const bf16_t* B2;   // NT: [N, 64]; NN: [k2, N]
-  bf16_t* C;
-  const bf16_t* bias;
-  int64_t M, lda, ldb, lda2, ldb2, ldc;
-  int N, K, k2;
-  float alpha, beta;
-};
-
 __device__ __forceinline__ void g3_vm_wait(int n) {
   switch (n) {
     case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
@@ -50,7 +38,7 @@ __device__ __forceinline__ void g3_vm_wait(int n) {
 #define G3_MF(i, FA, FB) \
   acc[(i) >> 2][(i)&3] = mfma32(as_bf16x8(FA[(i) >> 2]), as_bf16x8(FB[(i)&3]), acc[(i) >> 2][(i)&3])
 
-template <bool NT> __global__ __launch_bounds__(G3_THREADS, 1) void gemm3_kernel(const Gemm3Params p) {
+template <bool NT> __global__ __launch_bounds__(G3_THREADS, 1) void gemm3_kernel(const ExtGemmParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int t = threadIdx.x, lane = t & 63;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -266,19 +254,12 @@ template <bool NT> __global__ __launch_bounds__(G3_THREADS, 1) void gemm3_kernel
   }
 }
 
-int launch_gemm3(const void* A, int64_t lda, const void* B, int64_t ldb, bool nt, const void* A2, int64_t lda2,
-                 const void* B2, int64_t ldb2, int k2, void* C, int64_t ldc, const void* bias, int64_t M, int N, int K,
-                 float alpha, float beta, hipStream_t stream) {
-  Gemm3Params p;
-  p.A = (const bf16_t*)A, p.B = (const bf16_t*)B, p.A2 = (const bf16_t*)A2, p.B2 = (const bf16_t*)B2;
-  p.C = (bf16_t*)C, p.bias = (const bf16_t*)bias;
-  p.M = M, p.lda = lda, p.ldb = ldb, p.lda2 = lda2, p.ldb2 = ldb2, p.ldc = ldc;
-  p.N = N, p.K = K, p.k2 = k2 < 64 ? k2 : 64;
-  p.alpha = alpha, p.beta = beta;
-  const int64_t tiles = (int64_t)ceil_div(M, G3_BM) * ceil_div(N, G3_BN);
+int launch_gemm3(const ExtGemm& g, hipStream_t stream) {
+  const ExtGemmParams p = ext_gemm_params(g);
+  const int64_t tiles = (int64_t)ceil_div(g.M, G3_BM) * ceil_div(g.N, G3_BN);
   if (tiles <= 0) return SOW_OK;
   if (tiles > 0x7fffffff) return SOW_ERR_SHAPE;
-  if (nt) {
+  if (g.nt) {
     SOW_SET_MAX_LDS_ONCE(G3_LDS, gemm3_kernel<true>);
     hipLaunchKernelGGL(gemm3_kernel<true>, dim3((unsigned)tiles), dim3(G3_THREADS), G3_LDS, stream, p);
   } else {

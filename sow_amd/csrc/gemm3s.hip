@@ -27,18 +27,6 @@ constexpr int GS_SLICE = 2 * GS_PIECE;          // 16 KiB: [A | B] of one slice
 constexpr int GS_STAGE = 2 * GS_SLICE;          // 32 KiB
 constexpr int GS_LDS = GS_NSLOT * GS_STAGE;     // 128 KiB
 
-struct Gemm3sParams {
-  const bf16_t* A;
-  const bf16_t* B;
-  const bf16_t* A2;   // [M, 64] or nullptr
-  const bf16_t* B2;   // NT: [N, 64]; NN: [k2, N]
-  bf16_t* C;
-  const bf16_t* bias;
-  int64_t M, lda, ldb, lda2, ldb2, ldc;
-  int N, K, k2;
-  float alpha, beta;
-};
-
 __device__ __forceinline__ void gs_vm_wait(int n) {
   switch (n) {
     case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
@@ -50,7 +38,7 @@ __device__ __forceinline__ void gs_vm_wait(int n) {
 }
 #define GS_SB() __builtin_amdgcn_sched_barrier(0)
 
-template <bool NT> __global__ __launch_bounds__(GS_THREADS, 1) void gemm3s_kernel(const Gemm3sParams p) {
+template <bool NT> __global__ __launch_bounds__(GS_THREADS, 1) void gemm3s_kernel(const ExtGemmParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int t = threadIdx.x, lane = t & 63;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -275,19 +263,12 @@ template <bool NT> __global__ __launch_bounds__(GS_THREADS, 1) void gemm3s_kerne
   }
 }
 
-int launch_gemm3s(const void* A, int64_t lda, const void* B, int64_t ldb, bool nt, const void* A2, int64_t lda2,
-                  const void* B2, int64_t ldb2, int k2, void* C, int64_t ldc, const void* bias, int64_t M, int N, int K,
-                  float alpha, float beta, hipStream_t stream) {
-  Gemm3sParams p;
-  p.A = (const bf16_t*)A, p.B = (const bf16_t*)B, p.A2 = (const bf16_t*)A2, p.B2 = (const bf16_t*)B2;
-  p.C = (bf16_t*)C, p.bias = (const bf16_t*)bias;
-  p.M = M, p.lda = lda, p.ldb = ldb, p.lda2 = lda2, p.ldb2 = ldb2, p.ldc = ldc;
-  p.N = N, p.K = K, p.k2 = k2 < 64 ? k2 : 64;
-  p.alpha = alpha, p.beta = beta;
-  const int64_t tiles = (int64_t)ceil_div(M, GS_BM) * ceil_div(N, GS_BN);
+int launch_gemm3s(const ExtGemm& g, hipStream_t stream) {
+  const ExtGemmParams p = ext_gemm_params(g);
+  const int64_t tiles = (int64_t)ceil_div(g.M, GS_BM) * ceil_div(g.N, GS_BN);
   if (tiles <= 0) return SOW_OK;
   if (tiles > 0x7fffffff) return SOW_ERR_SHAPE;
-  if (nt) {
+  if (g.nt) {
     SOW_SET_MAX_LDS_ONCE(GS_LDS, gemm3s_kernel<true>);
     hipLaunchKernelGGL(gemm3s_kernel<true>, dim3((unsigned)tiles), dim3(GS_THREADS), GS_LDS, stream, p);
   } else {

@@ -157,18 +157,9 @@ template <int KIND> __device__ __forceinline__ constexpr int g4_slot_off() {
 #undef G4_ONE
 
 // ------------------------------------------------------------------------------------------------
-static bool g4_al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
-bool gemm4_supported(const void* A, int64_t lda, const void* B, int64_t ldb, bool nt, const void* A2, int64_t lda2,
-                     const void* B2, int64_t ldb2, const void* C, int64_t ldc, const void* bias, int64_t M, int N, int K,
-                     int dtype) {
-  if ((dtype != SOW_BF16 && dtype != SOW_F16) || !A || !B || !C) return false;
-  if (M < 1 || N < 64 || K < 64) return false;
-  if (K % 8 || N % 8 || lda % 8 || ldb % 8 || ldc % 8) return false;
-  if (!g4_al16(A) || !g4_al16(B) || !g4_al16(C) || (bias && !g4_al16(bias))) return false;
-  if (A2 && (!B2 || lda2 % 8 || ldb2 % 8 || !g4_al16(A2) || !g4_al16(B2))) return false;
-  (void)nt;
-  return true;
+bool gemm4_supported(const ExtGemm& g, int dtype) {
+  if (dtype != SOW_BF16 && dtype != SOW_F16) return false;
+  return g.M >= 1 && g.N >= 64 && g.K >= 64 && ext_gemm_operands_ok(g);
 }
 
 // split-K plan for an M x N x K product with an optional K-extension tile: splits (1 = none) and K-tiles per split.  Taken
@@ -200,18 +191,18 @@ int gemm4_splits(int64_t M, int N, int K, bool has_ext, const void* ws, size_t w
   return (s > 1 && ws && ws_bytes >= gemm4_splitk_bytes(M, N, K, has_ext)) ? s : 1;
 }
 
-int launch_gemm4(const void* A, int64_t lda, const void* B, int64_t ldb, bool nt, const void* A2, int64_t lda2,
-                 const void* B2, int64_t ldb2, int k2, void* C, int64_t ldc, const void* bias, int64_t M, int N, int K,
-                 float alpha, float beta, hipStream_t stream, void* ws, size_t ws_bytes, int dtype) {
+int launch_gemm4(const ExtGemm& g, int dtype, void* ws, size_t ws_bytes, hipStream_t stream) {
   if (dtype != SOW_BF16 && dtype != SOW_F16) return SOW_ERR_DTYPE;
-  const bool f16 = dtype == SOW_F16;
+  const bool f16 = dtype == SOW_F16, nt = g.nt;
+  const int64_t M = g.M;
+  const int N = g.N, K = g.K;
   Gemm4Params p;
-  p.A = (const bf16_t*)A, p.B = (const bf16_t*)B, p.A2 = (const bf16_t*)A2, p.B2 = (const bf16_t*)B2;
-  p.C = (bf16_t*)C, p.bias = (const bf16_t*)bias;
-  p.M = M, p.lda = lda, p.ldb = ldb, p.lda2 = lda2, p.ldb2 = ldb2, p.ldc = ldc;
-  p.N = N, p.K = K, p.k2 = k2 < 64 ? k2 : 64;
+  p.A = (const bf16_t*)g.A, p.B = (const bf16_t*)g.B, p.A2 = (const bf16_t*)g.A2, p.B2 = (const bf16_t*)g.B2;
+  p.C = (bf16_t*)g.C, p.bias = (const bf16_t*)g.bias;
+  p.M = M, p.lda = g.lda, p.ldb = g.ldb, p.lda2 = g.lda2, p.ldb2 = g.ldb2, p.ldc = g.ldc;
+  p.N = N, p.K = K, p.k2 = g.k2 < 64 ? g.k2 : 64;
   p.k2e = 64;
-  p.alpha = alpha, p.beta = beta;
+  p.alpha = g.alpha, p.beta = g.beta;
   p.nt_store = SOW_GEMM_NT(M) ? 1 : 0;
   p.F = nullptr, p.ldf = 0, p.Hout = nullptr, p.r = 0, p.hscale = 0.f;
   p.splits = 1, p.kt_per = 0, p.partials = nullptr;
@@ -219,8 +210,8 @@ int launch_gemm4(const void* A, int64_t lda, const void* B, int64_t ldb, bool nt
   if (tiles <= 0) return SOW_OK;
   if (tiles > 0x7fffffff) return SOW_ERR_SHAPE;
   int64_t grid = tiles;
-  if (gemm4_splits(M, N, K, A2 != nullptr, ws, ws_bytes) > 1) {
-    p.splits = gemm4_split_plan(M, N, K, A2 != nullptr, &p.kt_per);
+  if (gemm4_splits(M, N, K, g.A2 != nullptr, ws, ws_bytes) > 1) {
+    p.splits = gemm4_split_plan(M, N, K, g.A2 != nullptr, &p.kt_per);
     p.partials = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
     grid = tiles * p.splits;
   }
@@ -260,42 +251,37 @@ int launch_gemm4(const void* A, int64_t lda, const void* B, int64_t ldb, bool nt
 // ---- gemm4h: C = X . op(W) + H . op(G) + bias with H = hscale * X . op(F) computed in the kernel and saved -------------
 // NN (forward: y = x W_acc + h B): W [K, N], F = A zero-padded to [K, 64] (ldf = 64), G = B [r, N].
 // NT (backward: dX = dY W_acc^T + dh A^T): W [N, K], F = B [r, K], G = A zero-padded to [N, 64] (ldg = 64).
-bool gemm4h_supported(const void* X, int64_t ldx, const void* W, int64_t ldw, bool nt, const void* F, int64_t ldf,
-                      const void* G, int64_t ldg, const void* C, int64_t ldc, const void* bias, const void* H, int64_t M,
-                      int N, int K, int r, int dtype) {
-  if ((dtype != SOW_BF16 && dtype != SOW_F16) || !X || !W || !F || !G || !C || !H) return false;
+bool gemm4h_supported(const ProjGemm& g, bool nt, int dtype) {
+  if ((dtype != SOW_BF16 && dtype != SOW_F16) || !g.X || !g.W || !g.F || !g.G || !g.C || !g.H) return false;
   if (sw_on(SW_NO_FUSED_H) || sw_on(SW_FORCE_GEMM_V1) || sw(SW_GEMM4) == 0 || sw_on(SW_NO_GEMM4H)) return false;
-  if (r < 2 || r > 64 || (r & 1) || N < 64 || K < 64) return false;   // r even: A's 2r-byte rows stay 4-byte aligned
-  const int tiles_n = ceil_div(N, G4_BN);
+  if (g.r < 2 || g.r > 64 || (g.r & 1) || g.N < 64 || g.K < 64) return false;   // r even: A's 2r-byte rows stay 4-byte aligned
+  const int tiles_n = ceil_div(g.N, G4_BN);
   // every column tile repeats the projection pass (the row panel streams in once more per tile): one or two tiles
-  if (tiles_n > 2 || (int64_t)ceil_div(M, G4_BM) * tiles_n < 120) return false;
-  if (K % 8 || N % 8 || ldx % 8 || ldw % 8 || ldc % 8) return false;
-  if (!g4_al16(X) || !g4_al16(W) || !g4_al16(C) || !g4_al16(H) || (bias && !g4_al16(bias))) return false;
-  auto al4 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; };
+  if (tiles_n > 2 || (int64_t)ceil_div(g.M, G4_BM) * tiles_n < 120) return false;
+  if (g.K % 8 || g.N % 8 || g.ldx % 8 || g.ldw % 8 || g.ldc % 8) return false;
+  if (!al16p(g.X) || !al16p(g.W) || !al16p(g.C) || !al16p(g.H) || !al16p(g.bias)) return false;
   if (nt) {   // F = B [r, K] (16-byte pieces along rows), G = A [N, r] as stored (or zero-padded to 64 columns)
-    if (ldf % 8 || !g4_al16(F) || !al4(G) || (ldg != r && ldg != 64)) return false;
+    if (g.ldf % 8 || !al16p(g.F) || !al4p(g.G) || (g.ldg != g.r && g.ldg != 64)) return false;
   } else {    // F = A [K, r] as stored (or [K, 64]), G = B [r, N]
-    if (ldg % 8 || !g4_al16(G) || !al4(F) || (ldf != r && ldf != 64)) return false;
+    if (g.ldg % 8 || !al16p(g.G) || !al4p(g.F) || (g.ldf != g.r && g.ldf != 64)) return false;
   }
   return true;
 }
 
-int launch_gemm4h(const void* X, int64_t ldx, const void* W, int64_t ldw, bool nt, const void* F, int64_t ldf,
-                  const void* G, int64_t ldg, void* C, int64_t ldc, const void* bias, void* H, int64_t M, int N, int K,
-                  int r, float hscale, int dtype, hipStream_t stream) {
+int launch_gemm4h(const ProjGemm& g, bool nt, int dtype, hipStream_t stream) {
   if (dtype != SOW_BF16 && dtype != SOW_F16) return SOW_ERR_DTYPE;
   const bool f16 = dtype == SOW_F16;
   Gemm4Params p;
-  p.A = (const bf16_t*)X, p.B = (const bf16_t*)W, p.A2 = nullptr, p.B2 = (const bf16_t*)G;
-  p.C = (bf16_t*)C, p.bias = (const bf16_t*)bias;
-  p.M = M, p.lda = ldx, p.ldb = ldw, p.lda2 = 64, p.ldb2 = ldg, p.ldc = ldc;
-  p.N = N, p.K = K, p.k2 = r < 64 ? r : 64;
-  p.k2e = nt ? (ldg == 64 ? 64 : r) : 64;
+  p.A = (const bf16_t*)g.X, p.B = (const bf16_t*)g.W, p.A2 = nullptr, p.B2 = (const bf16_t*)g.G;
+  p.C = (bf16_t*)g.C, p.bias = (const bf16_t*)g.bias;
+  p.M = g.M, p.lda = g.ldx, p.ldb = g.ldw, p.lda2 = 64, p.ldb2 = g.ldg, p.ldc = g.ldc;
+  p.N = g.N, p.K = g.K, p.k2 = g.r < 64 ? g.r : 64;
+  p.k2e = nt ? (g.ldg == 64 ? 64 : g.r) : 64;
   p.alpha = 1.f, p.beta = 0.f;
-  p.nt_store = SOW_GEMM_NT(M) ? 1 : 0;
-  p.F = (const bf16_t*)F, p.ldf = ldf, p.Hout = (bf16_t*)H, p.r = r, p.hscale = hscale;
+  p.nt_store = SOW_GEMM_NT(g.M) ? 1 : 0;
+  p.F = (const bf16_t*)g.F, p.ldf = g.ldf, p.Hout = (bf16_t*)g.H, p.r = g.r, p.hscale = g.hscale;
   p.splits = 1, p.kt_per = 0, p.partials = nullptr;
-  const int64_t tiles = (int64_t)ceil_div(M, G4_BM) * ceil_div(N, G4_BN);
+  const int64_t tiles = (int64_t)ceil_div(g.M, G4_BM) * ceil_div(g.N, G4_BN);
   if (tiles <= 0) return SOW_OK;
   if (tiles > 0x7fffffff) return SOW_ERR_SHAPE;
   const int64_t grid = tiles;

@@ -165,15 +165,13 @@ template <typename T, bool NT, bool VECC> __global__ __launch_bounds__(256, 2) v
                                  (const T*)nullptr, lane, p.nt_store != 0);
 }
 
-static bool al16r(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 // bf16 / f16, 16-byte aligned bases, leading dimensions that cover the rows; every descriptor offset stays below 2^31:
 // 128 rows of a k-contiguous operand, K rows of the k-major one
 bool gemm_rag_supported(const void* A, int64_t lda, const void* B, int64_t ldb, bool transB, const void* C, int64_t ldc, int64_t M,
                         int N, int K, int dtype) {
   if (dtype != SOW_BF16 && dtype != SOW_F16) return false;
   if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0) return false;
-  if (!al16r(A) || !al16r(B) || !al16r(C)) return false;
+  if (!al16p(A) || !al16p(B) || !al16p(C)) return false;
   if (lda < K || ldb < (transB ? K : N) || ldc < N) return false;
   constexpr int64_t LIM = (int64_t)1 << 31;
   if (RG_BM * lda * 2 >= LIM) return false;

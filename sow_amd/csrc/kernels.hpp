@@ -272,47 +272,55 @@ int launch_gemm_rag(const void* A, int64_t lda, const void* B, int64_t ldb, bool
 // gemm_x3.hip: the same contract for fp32 tensors on the bf16 matrix pipe (3 x bf16 splits); vector-aligned operands only
 int launch_gemm_x3(const void* A, int64_t lda, bool transA, const void* B, int64_t ldb, bool transB, void* C, int64_t ldc,
                    const void* bias, int64_t M, int N, int K, float alpha, float beta, hipStream_t stream);
-// gemm2.hip (bf16 streaming GEMM with K-extension: the dense-accumulator form of the layer)
-bool gemm2_supported(const void* A, int64_t lda, const void* B, int64_t ldb, bool nt, const void* A2, int64_t lda2,
-                     const void* B2, int64_t ldb2, const void* C, int64_t ldc, const void* bias, int64_t M, int N, int K,
-                     int dtype);
-// ws / ws_bytes: optional scratch for split-K (gemm4_splitk_bytes; short M), nullptr = never split
-int launch_gemm2(const void* A, int64_t lda, const void* B, int64_t ldb, bool nt, const void* A2, int64_t lda2,
-                 const void* B2, int64_t ldb2, int k2, void* C, int64_t ldc, const void* bias, int64_t M, int N, int K,
-                 float alpha, float beta, hipStream_t stream, void* ws = nullptr, size_t ws_bytes = 0);
+// The streaming GEMM family with an optional K-extension (gemm2 / gemm3 / gemm3s / gemm4):
+//     C[M,N] = alpha * (A[M,K] . op(B) + A2[M,64] . op(B2)) + beta * C + bias[N]
+// nt: op(B) = B^T, B given as [N, K] (B2 as [N, 64]); else B is [K, N] (B2 [k2, N]).  A2 = nullptr: no extension.
+// Which kernel runs a product is decided in api.hip (pick_gemm); the launchers below launch their own kernel only.
+struct ExtGemm {
+  const void *A, *B, *A2, *B2;
+  void* C;
+  const void* bias;
+  int64_t M, lda, ldb, lda2, ldb2, ldc;
+  int N, K, k2;
+  bool nt;
+  float alpha, beta;
+};
+// what every kernel of the family asks of the operands: A, B, C given; K, N, lda, ldb, ldc multiples of 8; A, B, C, bias
+// 16-byte aligned; with an extension B2 given, lda2 and ldb2 multiples of 8, A2 and B2 16-byte aligned
+bool ext_gemm_operands_ok(const ExtGemm& g);
+// the kernel-argument block of gemm2_kernel / gemm3_kernel / gemm3s_kernel (bf16)
+struct ExtGemmParams {
+  const bf16_t* A;
+  const bf16_t* B;
+  const bf16_t* A2;   // [M, 64] or nullptr
+  const bf16_t* B2;   // NT: [N, 64]; NN: [k2, N]
+  bf16_t* C;
+  const bf16_t* bias;
+  int64_t M, lda, ldb, lda2, ldb2, ldc;
+  int N, K, k2;
+  float alpha, beta;
+};
+ExtGemmParams ext_gemm_params(const ExtGemm& g);   // k2 clamped to the 64 rows of the extension
+// gemm2.hip (bf16; 256x256 tiles, 8 waves, 32-wide K stages)
+int launch_gemm2(const ExtGemm& g, hipStream_t stream);
 int launch_pad64(const void* in, void* out, int rows, int r, hipStream_t stream);
-// gemm3.hip (same contract as launch_gemm2; one wave per SIMD, 128x128 per wave, hand-interleaved k-loop: long K)
-int launch_gemm3(const void* A, int64_t lda, const void* B, int64_t ldb, bool nt, const void* A2, int64_t lda2,
-                 const void* B2, int64_t ldb2, int k2, void* C, int64_t ldc, const void* bias, int64_t M, int N, int K,
-                 float alpha, float beta, hipStream_t stream);
-// gemm4.hip (same contract as launch_gemm2; 256x256x64 tiles, two wave groups in anti-phase, v_mfma_f32_16x16x32_bf16 / _f16)
-bool gemm4_supported(const void* A, int64_t lda, const void* B, int64_t ldb, bool nt, const void* A2, int64_t lda2,
-                     const void* B2, int64_t ldb2, const void* C, int64_t ldc, const void* bias, int64_t M, int N, int K,
-                     int dtype);
-// dtype: SOW_BF16 or SOW_F16 (gemm4_f16_kernel)
-int launch_gemm4(const void* A, int64_t lda, const void* B, int64_t ldb, bool nt, const void* A2, int64_t lda2,
-                 const void* B2, int64_t ldb2, int k2, void* C, int64_t ldc, const void* bias, int64_t M, int N, int K,
-                 float alpha, float beta, hipStream_t stream, void* ws = nullptr, size_t ws_bytes = 0, int dtype = SOW_BF16);
+// gemm3.hip (bf16; one wave per SIMD, 128x128 per wave, hand-interleaved k-loop: long K)
+int launch_gemm3(const ExtGemm& g, hipStream_t stream);
+// gemm3s.hip (bf16; 128x128 tiles for products with few 256x256 tiles: short M)
+int launch_gemm3s(const ExtGemm& g, hipStream_t stream);
+// gemm4.hip (256x256x64 tiles, two wave groups in anti-phase, v_mfma_f32_16x16x32_bf16 / _f16).  dtype: SOW_BF16 or SOW_F16
+// (gemm4_f16_kernel).  ext_gemm_operands_ok and M >= 1, N >= 64, K >= 64
+bool gemm4_supported(const ExtGemm& g, int dtype);
+// ws / ws_bytes: optional scratch for split-K (gemm4_splitk_bytes; short M), nullptr = never split
+int launch_gemm4(const ExtGemm& g, int dtype, void* ws, size_t ws_bytes, hipStream_t stream);
 // split-K of gemm4 for short M (<= 128 output tiles): scratch bytes (0 = the shape does not split), and the split count a
 // launch with this scratch takes (1 = none)
 size_t gemm4_splitk_bytes(int64_t M, int N, int K, bool has_ext);
 int gemm4_splits(int64_t M, int N, int K, bool has_ext, const void* ws, size_t ws_bytes);
-// gemm4.hip, gemm4h form: the projection H = hscale * X . op(F) computed by the kernel (a streaming pass over the row panel
-// ahead of the main loop) and used as the extension's A operand; F / G zero-padded to 64 columns where they are k-major
-bool gemm4h_supported(const void* X, int64_t ldx, const void* W, int64_t ldw, bool nt, const void* F, int64_t ldf,
-                      const void* G, int64_t ldg, const void* C, int64_t ldc, const void* bias, const void* H, int64_t M,
-                      int N, int K, int r, int dtype);
-int launch_gemm4h(const void* X, int64_t ldx, const void* W, int64_t ldw, bool nt, const void* F, int64_t ldf,
-                  const void* G, int64_t ldg, void* C, int64_t ldc, const void* bias, void* H, int64_t M, int N, int K,
-                  int r, float hscale, int dtype, hipStream_t stream);
-// gemm2h.hip (the same product with the projection h = hscale * X . op(F) computed in the kernel: one launch per pass)
-bool gemm2h_supported(const void* X, int64_t ldx, const void* W, int64_t ldw, bool nt, const void* F, int64_t ldf,
-                      const void* G, int64_t ldg, const void* C, int64_t ldc, const void* bias, const void* H, int64_t M,
-                      int N, int K, int r, int dtype);
-int launch_gemm2h(const void* X, int64_t ldx, const void* W, int64_t ldw, bool nt, const void* F, int64_t ldf,
-                  const void* G, int64_t ldg, void* C, int64_t ldc, const void* bias, void* H, int64_t M, int N, int K,
-                  int r, float hscale, hipStream_t stream);
-struct Gemm2hArgs {   // the arguments of launch_gemm2h for one layer of a grouped launch (same nt for the whole group)
+// The same product with the projection H = hscale * X . op(F) computed by the kernel and used as the extension's A operand
+// (one launch per pass):  C = X . op(W) + H . op(G) + bias, H [M, 64] saved.  The operands of one layer; nt is a separate
+// argument because a grouped launch has one for the whole group.
+struct ProjGemm {
   const void *X, *W, *F, *G;
   void* C;
   const void* bias;
@@ -321,11 +329,13 @@ struct Gemm2hArgs {   // the arguments of launch_gemm2h for one layer of a group
   int N, K, r;
   float hscale;
 };
-int launch_gemm2h_group(const Gemm2hArgs* a, int n, bool nt, hipStream_t stream);   // n <= 4, every layer gemm2h_supported
-// gemm3s.hip (same contract; 128x128 tiles for products with few 256x256 tiles: short M)
-int launch_gemm3s(const void* A, int64_t lda, const void* B, int64_t ldb, bool nt, const void* A2, int64_t lda2,
-                  const void* B2, int64_t ldb2, int k2, void* C, int64_t ldc, const void* bias, int64_t M, int N, int K,
-                  float alpha, float beta, hipStream_t stream);
+// gemm4.hip, gemm4h form: a streaming pass over the row panel ahead of the main loop; F / G zero-padded to 64 columns where
+// they are k-major
+bool gemm4h_supported(const ProjGemm& g, bool nt, int dtype);
+int launch_gemm4h(const ProjGemm& g, bool nt, int dtype, hipStream_t stream);
+// gemm2h.hip (bf16): n <= 4 layers in one launch, every one gemm2h_supported
+bool gemm2h_supported(const ProjGemm& g, bool nt, int dtype);
+int launch_gemm2h_group(const ProjGemm* g, int n, bool nt, hipStream_t stream);
 // qr.hip
 int launch_cast_copy(const void* src, int64_t lds, int src_dtype, void* dst, int64_t ldd, int dst_dtype, int64_t rows,
                      int cols, hipStream_t stream);

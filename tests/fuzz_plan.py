@@ -249,7 +249,7 @@ def _layers(d: _Draw) -> List[Layer]:
                   stratum="gemm2h", family="gemm2h_kernel")
         add(c, "gemm2h", {"NO_GEMM4H": 1} if i != 1 else {"GEMM4": 0}, h_null_ok=False)
     # dense d_out > 512 at short T: chain2 H-only pass, then the dense product with the rank extension in one accumulator
-    for i in range(3):   # split over K: <= 128 output tiles, >= 96 K-tiles of 64 (d_in >= 6080), tiles x splits >= 120; gemm2_supported
+    for i in range(3):   # split over K: <= 128 output tiles, >= 96 K-tiles of 64 (d_in >= 6080), tiles x splits >= 120; the bf16 gate of pick_gemm
         # wants >= 96 tiles of 128 x 128, so d_out >= 2048 at T = 1024
         c = Layer("", "bf16", g.choice([1024, 1025]), g.choice([6144, 6152]), g.choice([2048, 2056]),
                   d.even(4, 64), acc="dense", stratum="dense_short", family="gemm4_splitk_reduce_kernel")
@@ -264,7 +264,7 @@ def _layers(d: _Draw) -> List[Layer]:
         if i >= 2:
             sw, c.family = {"GEMM3S": 0}, "gemm2_kernel"
         add(c, "dense_short", sw, h_null_ok=False)
-        # the backward's dY W^T (N = d_in, K = d_out) takes the fused gemm2 form only where gemm2_supported admits it
+        # the backward's dY W^T (N = d_in, K = d_out) takes the fused gemm2 form only where the bf16 gate of pick_gemm admits it
         c.dx_rounds = "once" if gemm2_ok(c.T, c.d_in, c.d_out) else "twice"
     for i in range(3):   # gemm2_kernel at long T: >= 160 big tiles with gemm4 switched off, K < 2048
         # (d_in > 128: the backward's dY W^T then has >= 96 tiles of 128 x 128 and takes the fused gemm2 form too)
@@ -506,7 +506,7 @@ def _gemm_family(dt, M, N, K, ta, tb, lda, ldb, ldc):
 
 
 def gemm2_ok(M, N, K):
-    """gemm2_supported (gemm2.hip) for aligned bf16 operands with the defaults of the switches."""
+    """The bf16 gate of pick_gemm (api.hip) for aligned bf16 operands with the defaults of the switches."""
     t256, t128 = cdiv(M, 256) * cdiv(N, 256), cdiv(M, 128) * cdiv(N, 128)
     return N >= 64 and K >= 32 and N % 8 == 0 and K % 8 == 0 and not (t256 < 160 and (t128 < 96 or K < 512))
 

@@ -447,13 +447,13 @@ def _has_kernel(seq, kernel):
     return any(f"sow::{kernel}" in n or f"{len(kernel)}{kernel}" in n for n in seq)
 
 
-# Dispatch switches (api.hip, gemm2.hip): (case, kernels the trace must show, kernels it must not).  The rounding class of
+# Dispatch switches (api.hip): (case, kernels the trace must show, kernels it must not).  The rounding class of
 # each is read off the path the switch leaves:
 # * NO_SHORT_SPLIT: launch_chain_short declines (api.hip), the layer (no accumulator) runs the unsplit chain: y and dX
 #   are still written by one kernel from operands the test sees ("once");
 # * FORCE_GEMM_V1: gemm4h / gemm2h / gemm2 all decline, gemm_auto takes the generic kernel for x W_acc and dY W_acc^T and
 #   the chain adds the low-rank term with beta = 1 ("twice", as dense_misaligned);
-# * NO_GEMM3S: a dense layer with fewer than 160 tiles of 256 x 256 fails gemm2_supported (gemm2.hip:246-248) and takes the
+# * NO_GEMM3S: a dense layer with fewer than 160 tiles of 256 x 256 fails the bf16 gate of pick_gemm (api.hip) and takes the
 #   same generic composition ("twice"); without the switch its >= 96 tiles of 128 x 128 run gemm3s_kernel.
 _FAST_GEMMS = ("gemm2_kernel", "gemm2h_kernel", "gemm3_kernel", "gemm3s_kernel", "gemm4_kernel", "gemm4_f16_kernel")
 SWITCHED = [
@@ -541,7 +541,7 @@ def test_grouped_path(name, layers, rows):
 
 # ---- sow_gemm: C = alpha op(A) op(B) + beta C + bias (one rounding of an fp32 sum)
 GEMMS = [
-    # gemm4 streaming: gemm2_supported and >= 120 tiles of 256 x 256 (32 x 6)
+    # gemm4 streaming: the bf16 gate of pick_gemm and >= 120 tiles of 256 x 256 (32 x 6)
     ("gemm4_stream", 8192, 1376, 512, True, 0.0, False),
     # gemm3s: fewer than 160 big tiles, >= 96 tiles of 128 x 128 and K >= 512 (no workspace, so no split)
     ("gemm3s_beta1", 4096, 1024, 1024, True, 1.0, False),
