@@ -132,6 +132,16 @@ extern "C" {
 #define SOW_ACC_NONE 0    /* acc_downweight empty                                   */
 #define SOW_ACC_LOWRANK 1 /* out = (x @ acc_down[d_in,vr]) @ acc_up[vr,d_out]       */
 #define SOW_ACC_DENSE 2   /* out = x @ acc_down[d_in,d_out]                         */
+/* A frozen dense accumulator stored as OCP E4M3 codes with one power-of-two exponent per column:
+ *   acc_down = the codes q [d_in, d_out], row-major, one byte each (e4m3fn; the two NaN codes are never produced),
+ *   acc_up   = the exponents e [d_out], int8: the smallest e_n with max_k |W[k,n]| <= 448 * 2^e_n, clamped to [-117, 119]
+ *              (bf16) or [-15, 7] (f16), 0 for an all-zero column;  q[k,n] = e4m3_rne(clamp(W[k,n] * 2^-e_n, -448, 448)).
+ * The layer computes what SOW_ACC_DENSE computes on the dequantised matrix  W^[k,n] = q[k,n] * 2^e_n,  which inside those
+ * clamps is exactly a number of the compute dtype: no rounding is added anywhere.  d_in * d_out + d_out bytes instead of
+ * 2 * d_in * d_out.  sow_forward_skinny streams the codes as they are; every other layer entry point returns
+ * SOW_ERR_UNSUPPORTED for this kind before anything is launched or dereferenced (the caller runs it on the image that
+ * sow_acc_dequantize writes, with SOW_ACC_DENSE). */
+#define SOW_ACC_DENSE_FP8 3
 
 #define SOW_H_COLS 64 /* column count of the saved h / dh buffers when r_live <= 64 */
 
@@ -340,14 +350,24 @@ int sow_backward_shared(const sow_layer_args* layers, int n, int dtype, int phas
  * computes alone.  Rows are independent: a non-finite x[t, k] makes row t of y non-finite and no other.
  * Fields used: x, A, B, acc_down, bias, y, T, d_in, d_out, r_live, acc_kind, scale, workspace, workspace_bytes (h_save and
  * the backward fields are ignored).  Layers may share x or not.
- * Admitted: SOW_DTYPE_BF16 / SOW_DTYPE_F16, T <= 32, SOW_ACC_DENSE or SOW_ACC_NONE, r_live <= 64, d_in and d_out multiples
- * of 8, 16-byte-aligned x, y, acc_down, A, B and bias, n <= 16.  Anything else -- SOW_ACC_LOWRANK, SOW_PARAM_F32, and
- * everything while the NO_SKINNY switch is on -- returns SOW_ERR_UNSUPPORTED; SOW_DTYPE_F32 returns SOW_ERR_DTYPE and a
+ * Admitted: SOW_DTYPE_BF16 / SOW_DTYPE_F16, T <= 32, SOW_ACC_DENSE, SOW_ACC_DENSE_FP8 or SOW_ACC_NONE, r_live <= 64, d_in and
+ * d_out multiples of 8, 16-byte-aligned x, y, acc_down, A, B and bias, n <= 16.  Anything else -- SOW_ACC_LOWRANK, SOW_PARAM_F32,
+ * and everything while the NO_SKINNY switch is on -- returns SOW_ERR_UNSUPPORTED; SOW_DTYPE_F32 returns SOW_ERR_DTYPE and a
  * workspace below the query SOW_ERR_WORKSPACE.  All of it is decided on the host for every layer before anything is launched
  * or dereferenced (the caller then takes sow_forward / sow_forward_group).  Layers with T = 0 are skipped (SOW_OK).
  * sow_forward_skinny_workspace_bytes: per layer, a pure function of the shape (the switches do not enter); 0 outside the
- * admitted set.  Every scratch byte is written before it is read. */
+ * admitted set.  Every scratch byte is written before it is read.
+ * SOW_ACC_DENSE_FP8 (acc_down = codes, acc_up = exponents, 8-byte aligned): the first launch reads the codes as bytes --
+ * half the stream -- converts them unscaled in registers and leaves sum_k x[t,k] q[k,n] in the slab partials; the second
+ * multiplies their slab-order sum by 2^e_n in fp32 (exact) before h . B and the bias: y = rn(x W^ + h B + bias), one
+ * rounding, the contract above with acc_down := W^.  Its column ranges are 128 wide, so its slab plan and workspace differ
+ * from SOW_ACC_DENSE's: size the workspace of such a layer with sow_forward_skinny_fp8_workspace_bytes (below).  The dense layers of one call must all be of one kind (SOW_ERR_UNSUPPORTED otherwise; layers without
+ * an accumulator mix with either). */
 size_t sow_forward_skinny_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype);
+/* The same query for a layer with SOW_ACC_DENSE_FP8, under the conditions of SOW_ACC_DENSE (0 outside them).  A query of
+ * its own: sow_forward_skinny_workspace_bytes answers 0 for acc_kind = 3, as it did while 3 was no kind, so that a caller
+ * written against it keeps reading 3 as "not admitted" there. */
+size_t sow_forward_skinny_fp8_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int dtype);
 int sow_forward_skinny(const sow_layer_args* layers, int n, int dtype, void* stream);
 
 /* General row-major GEMM  C[M,N] = alpha * op(A) op(B) + beta * C + bias[N]  (bias may be NULL).
@@ -539,6 +559,13 @@ int sow_axpby(const void* x, void* y, int64_t n, float a, float b, int dtype, vo
  * vectorised kernel).  Casts the fp32 x of a layer under autocast to the compute dtype, and its bf16 / f16 gradient back. */
 int sow_cast_copy(const void* src, int64_t lds, int src_dtype, void* dst, int64_t ldd, int dst_dtype, int64_t rows,
                   int cols, void* stream);
+
+/* The image of a SOW_ACC_DENSE_FP8 accumulator:  dst[k, n] = e4m3(q[k, n]) * 2^exps[n]  in SOW_DTYPE_BF16 or SOW_DTYPE_F16,
+ * exact (a NaN code gives NaN).  q [d_in, d_out] codes, exps [d_out] int8, dst [d_in, ldd >= d_out]; columns past d_out of a
+ * dst row are not written.  One streaming pass: every code read once, 16-byte stores.  d_out and ldd multiples of 8
+ * (SOW_ERR_UNSUPPORTED), q and exps 8-byte and dst 16-byte aligned (SOW_ERR_ALIGN), |exps[n]| <= 119. */
+int sow_acc_dequantize(const void* q, const void* exps, int d_in, int d_out, void* dst, int64_t ldd, int dst_dtype,
+                       void* stream);
 
 #ifdef __cplusplus
 }

@@ -398,6 +398,14 @@ static void normalise_acc(sow_layer_args& L) {
   if (L.acc_kind != SOW_ACC_LOWRANK) L.r_acc = 0, L.acc_up = nullptr;
   if (L.acc_kind == SOW_ACC_NONE) L.acc_down = nullptr;
 }
+// An E4M3 accumulator (SOW_ACC_DENSE_FP8) is read by sow_forward_skinny only: every other layer entry point asks here first,
+// before any other check, launch or dereference
+static inline bool any_fp8_acc(const sow_layer_args* layers, int n) {
+  if (layers)
+    for (int i = 0; i < n; ++i)
+      if (layers[i].acc_kind == SOW_ACC_DENSE_FP8) return true;
+  return false;
+}
 static inline WsPlan plan_of(const sow_layer_args& L, int cd, int perm = 0) {
   return plan_ws(L.T, L.d_in, L.d_out, L.r_live, acc_rank(L), L.acc_kind, cd, perm);
 }
@@ -748,6 +756,7 @@ size_t sow_reduce_desc_bytes(void) { return sizeof(ReduceParams); }
 int sow_backward_reduce_desc(void* dA, void* dB, void* dbias, int64_t T, int d_in, int d_out, int r_live, int r_acc,
                              int acc_kind, float grad_beta, int dtype, void* workspace, size_t workspace_bytes, void* desc_out,
                              int* blocks_out) {
+  if (acc_kind == SOW_ACC_DENSE_FP8) return SOW_ERR_UNSUPPORTED;
   const Dtype f = decode_dtype(dtype);   // the descriptor is the same with fp32 gradients: sow_reduce_batch picks the output type
   if (!f.layer_ok()) return SOW_ERR_DTYPE;
   if (T <= 0 || d_in <= 0 || d_out <= 0 || r_live <= 0) return SOW_ERR_SHAPE;
@@ -782,6 +791,7 @@ int sow_reduce_batch(const void* descs, const int* starts, int n, int total_bloc
 
 size_t sow_forward_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, int dtype) {
   const Dtype f = decode_dtype(dtype);
+  if (acc_kind == SOW_ACC_DENSE_FP8) return 0;
   if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0 || !f.layer_ok()) return 0;
   if (f.param_f32) {   // the forward's own scratch (if any) followed by the packed parameters (pack_layer)
     const size_t own = sow_forward_workspace_bytes(T, d_in, d_out, r_live, r_acc, acc_kind, f.cd);
@@ -797,6 +807,7 @@ size_t sow_forward_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, i
 
 size_t sow_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, int dtype) {
   const Dtype f = decode_dtype(dtype);
+  if (acc_kind == SOW_ACC_DENSE_FP8) return 0;
   if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0 || !f.layer_ok()) return 0;
   const size_t pack = f.param_f32 ? pack_bytes(d_in, d_out, r_live, acc_kind == SOW_ACC_LOWRANK ? r_acc : 0, acc_kind) : 0;
   return plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, f.cd, f.perm()).total + pack + 256;
@@ -851,6 +862,7 @@ static int forward_impl(const sow_layer_args& L, int dtype, int perm, hipStream_
 int sow_forward(const void* x, const void* A, const void* B, const void* acc_down, const void* acc_up, const void* bias,
                 void* y, void* h_save, int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, float scale,
                 int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  if (acc_kind == SOW_ACC_DENSE_FP8) return SOW_ERR_UNSUPPORTED;
   const Dtype f = decode_dtype(dtype);
   if (!f.layer_ok()) return SOW_ERR_DTYPE;
   sow_layer_args L = single_layer(x, A, B, acc_down, acc_up, bias, y, h_save, nullptr, nullptr, nullptr, nullptr, nullptr, T, d_in,
@@ -975,6 +987,7 @@ int sow_backward_ex(const void* dy, const void* x, const void* h_save, const voi
                     const void* acc_up, void* dx, void* dA, void* dB, void* dbias, int64_t T, int d_in, int d_out,
                     int r_live, int r_acc, int acc_kind, float scale, float grad_beta, int dtype, void* workspace,
                     size_t workspace_bytes, int phases, void* stream) {
+  if (acc_kind == SOW_ACC_DENSE_FP8) return SOW_ERR_UNSUPPORTED;
   const Dtype f = decode_dtype(dtype);
   sow_layer_args L = single_layer(x, A, B, acc_down, acc_up, nullptr, nullptr, const_cast<void*>(h_save), dy, dx, dA, dB, dbias, T,
                                   d_in, d_out, r_live, r_acc, acc_kind, scale, grad_beta, workspace, workspace_bytes);
@@ -1102,6 +1115,7 @@ static int forward_group_impl(const sow_layer_args* layers, int n, int dtype, in
 }
 
 int sow_forward_group(const sow_layer_args* layers, int n, int dtype, void* stream) {
+  if (any_fp8_acc(layers, n)) return SOW_ERR_UNSUPPORTED;
   const Dtype f = decode_dtype(dtype);
   if (!f.layer_ok()) return SOW_ERR_DTYPE;
   if (!f.param_f32 || n <= 0 || !layers) return forward_group_impl(layers, n, f.cd, f.perm(), (hipStream_t)stream);
@@ -1111,11 +1125,11 @@ int sow_forward_group(const sow_layer_args* layers, int n, int dtype, void* stre
 }
 
 // ---- generation-sized forwards (skinny_fwd.hip) --------------------------------------------------------------
-// The admitted set, decided from the shape alone: 1 <= T <= 32, bf16 / f16 without SOW_PARAM_F32, a dense accumulator or none,
-// r_live <= 64, widths multiples of 8.
+// The admitted set, decided from the shape alone: 1 <= T <= 32, bf16 / f16 without SOW_PARAM_F32, a dense accumulator (in the
+// compute dtype or as E4M3 codes) or none, r_live <= 64, widths multiples of 8.
 static bool skinny_shape_ok(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype) {
   return (dtype == SOW_BF16 || dtype == SOW_F16) && T >= 1 && T <= 32 && d_in > 0 && d_out > 0 && r_live >= 1 && r_live <= 64 &&
-         (acc_kind == SOW_ACC_DENSE || acc_kind == SOW_ACC_NONE) && d_in % 8 == 0 && d_out % 8 == 0;
+         (acc_kind == SOW_ACC_DENSE || acc_kind == SOW_ACC_DENSE_FP8 || acc_kind == SOW_ACC_NONE) && d_in % 8 == 0 && d_out % 8 == 0;
 }
 struct SkWs {
   size_t off_py, off_ph, total;
@@ -1125,15 +1139,22 @@ static SkWs skinny_ws(int64_t T, int d_in, int d_out, int acc_kind) {
   skinny_plan(d_in, d_out, acc_kind, &S, &KS, &ncr);
   SkWs w;
   w.off_py = 0;
-  w.off_ph = acc_kind == SOW_ACC_DENSE ? al256(skinny_py_bytes(T, d_out, S)) : 0;
+  w.off_ph = acc_kind != SOW_ACC_NONE ? al256(skinny_py_bytes(T, d_out, S)) : 0;
   w.total = 256 + w.off_ph + al256(skinny_ph_bytes(T, S));
   return w;
 }
 
+// (an E4M3 accumulator has a query of its own: this one keeps answering 0 for every kind value it answered 0 for before)
 size_t sow_forward_skinny_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype) {
   const Dtype f = decode_dtype(dtype);
-  if (f.param_f32 || !skinny_shape_ok(T, d_in, d_out, r_live, acc_kind, f.cd)) return 0;
+  if (f.param_f32 || acc_kind == SOW_ACC_DENSE_FP8 || !skinny_shape_ok(T, d_in, d_out, r_live, acc_kind, f.cd)) return 0;
   return skinny_ws(T, d_in, d_out, acc_kind).total;
+}
+
+size_t sow_forward_skinny_fp8_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int dtype) {
+  const Dtype f = decode_dtype(dtype);
+  if (f.param_f32 || !skinny_shape_ok(T, d_in, d_out, r_live, SOW_ACC_DENSE_FP8, f.cd)) return 0;
+  return skinny_ws(T, d_in, d_out, SOW_ACC_DENSE_FP8).total;
 }
 
 // The checks of this entry point are its own (not check_layer): stricter, and every layer is checked before the first
@@ -1148,17 +1169,22 @@ int sow_forward_skinny(const sow_layer_args* layers, int n, int dtype, void* str
   if (!layers) return SOW_ERR_NULL;
   if (n > SK_MAXL) return SOW_ERR_UNSUPPORTED;
   SkLayer sk[SK_MAXL];
-  int m = 0;
+  int m = 0, n_fp8 = 0, n_plain = 0;
   for (int i = 0; i < n; ++i) {
     const sow_layer_args& L = layers[i];
     if (L.T < 0 || L.d_in <= 0 || L.d_out <= 0 || L.r_live <= 0) return SOW_ERR_SHAPE;
-    if (L.acc_kind != SOW_ACC_NONE && L.acc_kind != SOW_ACC_LOWRANK && L.acc_kind != SOW_ACC_DENSE) return SOW_ERR_SHAPE;
+    if (L.acc_kind != SOW_ACC_NONE && L.acc_kind != SOW_ACC_LOWRANK && L.acc_kind != SOW_ACC_DENSE && L.acc_kind != SOW_ACC_DENSE_FP8)
+      return SOW_ERR_SHAPE;
     if (L.T == 0) continue;
     if (!skinny_shape_ok(L.T, L.d_in, L.d_out, L.r_live, L.acc_kind, cd)) return SOW_ERR_UNSUPPORTED;
-    const bool dense = L.acc_kind == SOW_ACC_DENSE;
-    if (!L.x || !L.A || !L.B || !L.y || (dense && !L.acc_down)) return SOW_ERR_NULL;
+    const bool fp8 = L.acc_kind == SOW_ACC_DENSE_FP8;
+    const bool dense = L.acc_kind == SOW_ACC_DENSE || fp8;
+    if (!L.x || !L.A || !L.B || !L.y || (dense && !L.acc_down) || (fp8 && !L.acc_up)) return SOW_ERR_NULL;
     if (!al16p(L.x) || !al16p(L.y) || !al16p(L.A) || !al16p(L.B) || !al16p(L.bias) || (dense && !al16p(L.acc_down)))
       return SOW_ERR_UNSUPPORTED;
+    // one kind of dense accumulator per call (the kernels are instantiated per kind)
+    n_fp8 += fp8, n_plain += dense && !fp8;
+    if (n_fp8 && n_plain) return SOW_ERR_UNSUPPORTED;
     const SkWs w = skinny_ws(L.T, L.d_in, L.d_out, L.acc_kind);
     if (!L.workspace || L.workspace_bytes < w.total) return SOW_ERR_WORKSPACE;
     char* ws = ws_base(L.workspace);
@@ -1167,6 +1193,7 @@ int sow_forward_skinny(const sow_layer_args* layers, int n, int dtype, void* str
     K.x = L.x, K.W = dense ? L.acc_down : nullptr, K.A = L.A, K.B = L.B, K.bias = L.bias, K.y = L.y;
     K.Py = dense ? (float*)(ws + w.off_py) : nullptr, K.Ph = (float*)(ws + w.off_ph);
     K.T = (int)L.T, K.d_in = L.d_in, K.d_out = L.d_out, K.r = L.r_live, K.scale = L.scale;
+    K.wexp = fp8 ? (const int8_t*)L.acc_up : nullptr;
   }
   return launch_skinny_fwd(sk, m, cd, (hipStream_t)stream);
 }
@@ -1277,6 +1304,7 @@ static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, i
 }
 
 int sow_backward_group(const sow_layer_args* layers, int n, int dtype, int phases, void* stream_) {
+  if (any_fp8_acc(layers, n)) return SOW_ERR_UNSUPPORTED;
   hipStream_t stream = (hipStream_t)stream_;
   const Dtype f = decode_dtype(dtype);
   if (!f.param_f32) return backward_group_impl(layers, n, f.cd, f.cd, phases, f.perm(), stream);
@@ -1309,6 +1337,7 @@ static void shared_fill_dx(const sow_layer_args* layers, int n, sow_layer_args* 
 }
 
 int sow_forward_shared(const sow_layer_args* layers, int n, int dtype, void* stream) {
+  if (any_fp8_acc(layers, n)) return SOW_ERR_UNSUPPORTED;
   const Dtype f = decode_dtype(dtype);
   if (!ok_dtype(f.cd)) return SOW_ERR_DTYPE;
   int rc;
@@ -1323,6 +1352,7 @@ int sow_forward_shared(const sow_layer_args* layers, int n, int dtype, void* str
 }
 
 int sow_backward_shared(const sow_layer_args* layers, int n, int dtype, int phases, void* stream_) {
+  if (any_fp8_acc(layers, n)) return SOW_ERR_UNSUPPORTED;
   hipStream_t stream = (hipStream_t)stream_;
   const Dtype f = decode_dtype(dtype);
   const int cd = f.cd;
@@ -1367,6 +1397,7 @@ static int check_group(const sow_layer_args* layers, int n) {
 }
 
 int sow_backward_group_plan(const sow_layer_args* layers, int n, int dtype, int phases, int* slabs_out) {
+  if (any_fp8_acc(layers, n)) return SOW_ERR_UNSUPPORTED;
   const Dtype f = decode_dtype(dtype);   // the plan does not depend on the parameter dtype
   if (!f.layer_ok()) return SOW_ERR_DTYPE;
   if (n < 0) return SOW_ERR_SHAPE;
@@ -1387,6 +1418,7 @@ int sow_backward_group_plan(const sow_layer_args* layers, int n, int dtype, int 
 }
 
 int sow_backward_group_reduce_desc(const sow_layer_args* layers, int n, int dtype, int phases, void* descs_out, int* blocks_out) {
+  if (any_fp8_acc(layers, n)) return SOW_ERR_UNSUPPORTED;
   const Dtype f = decode_dtype(dtype);
   if (!f.layer_ok()) return SOW_ERR_DTYPE;
   if (n < 0) return SOW_ERR_SHAPE;
@@ -1634,6 +1666,17 @@ int sow_axpby(const void* x, void* y, int64_t n, float a, float b, int dtype, vo
   dtype = nofuse(dtype);
   if (flagged(dtype)) return SOW_ERR_DTYPE;
   return launch_axpby(x, y, n, a, b, dtype, (hipStream_t)stream);
+}
+
+int sow_acc_dequantize(const void* q, const void* exps, int d_in, int d_out, void* dst, int64_t ldd, int dst_dtype,
+                       void* stream) {
+  if (d_in < 0 || d_out < 0 || ldd < d_out) return SOW_ERR_SHAPE;
+  if (dst_dtype != SOW_BF16 && dst_dtype != SOW_F16) return SOW_ERR_DTYPE;
+  if (d_in == 0 || d_out == 0) return SOW_OK;
+  if (!q || !exps || !dst) return SOW_ERR_NULL;
+  if (d_out % 8 || ldd % 8) return SOW_ERR_UNSUPPORTED;
+  if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(exps)) & 7 || !al16p(dst)) return SOW_ERR_ALIGN;
+  return launch_acc_dequantize(q, exps, d_in, d_out, dst, ldd, dst_dtype, (hipStream_t)stream);
 }
 
 int sow_cast_copy(const void* src, int64_t lds, int src_dtype, void* dst, int64_t ldd, int dst_dtype, int64_t rows,

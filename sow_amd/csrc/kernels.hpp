@@ -240,15 +240,19 @@ int launch_tn_wide(const void* x, const void* dh, const void* dy, const void* h,
                    hipStream_t stream);
 // skinny_fwd.hip: the fused forward of generation-sized calls (T <= 32, bf16 / f16, r <= 64, dense accumulator or none), n <=
 // SK_MAXL independent layers in two launches: W streamed once by a grid over (column range) x (K-slab), fp32 slab partials
-// through the workspace, summed in slab order with h . B and the bias and rounded once
+// through the workspace, summed in slab order with h . B and the bias and rounded once.  An E4M3 accumulator (SOW_ACC_DENSE_FP8:
+// W = the codes, 1 byte per element, wexp = the column exponents) is streamed as bytes by instantiations of the same two
+// kernels: 128-column ranges, codes converted unscaled in registers, the column's 2^e applied to the slab-order sum in phase B.
+// The dense layers of one call are all of one kind.
 constexpr int SK_MAXL = 16;
 struct SkLayer {
-  const void *x, *W, *A, *B, *bias;   // W = the dense accumulator [d_in][d_out], or nullptr
+  const void *x, *W, *A, *B, *bias;   // W = the dense accumulator [d_in][d_out] (or its E4M3 codes), or nullptr
   void* y;
   float *Py, *Ph;                     // slab partials [S][T][d_out] (nullptr without W) and [S][T][64]
   int T, d_in, d_out, r;
   int S, KS, ncr, startA, startB;     // filled in by launch_skinny_fwd (skinny_plan)
   float scale;
+  const int8_t* wexp;                 // column exponents [d_out] of an E4M3 accumulator, or nullptr
 };
 // K-slabs, slab length and phase-A column ranges of a layer: a pure function of the shape
 void skinny_plan(int d_in, int d_out, int acc_kind, int* S, int* KS, int* ncr);
@@ -339,6 +343,10 @@ int launch_gemm2h_group(const ProjGemm* g, int n, bool nt, hipStream_t stream);
 // qr.hip
 int launch_cast_copy(const void* src, int64_t lds, int src_dtype, void* dst, int64_t ldd, int dst_dtype, int64_t rows,
                      int cols, hipStream_t stream);
+// dst[k][n] = e4m3(q[k][n]) * 2^exps[n] in bf16 / f16 (exact): the image of an E4M3 accumulator; d_out % 8 == 0, ldd % 8 == 0,
+// q 8-byte and dst 16-byte aligned
+int launch_acc_dequantize(const void* q, const void* exps, int d_in, int d_out, void* dst, int64_t ldd, int dst_dtype,
+                          hipStream_t stream);
 int launch_qr_panel(const void* W, int64_t ldw, int in_dtype, int m, int kc, int r, float* Pt, float* Qt,
                     hipStream_t stream);
 int launch_qr_copy_out(const float* Qt, const float* Pt, void* Q, int64_t ldq, void* R, int64_t ldr, int out_dtype, int m,

@@ -88,6 +88,49 @@ static int grid_for(int64_t n) {
   return (int)g;
 }
 
+// The image of an E4M3 accumulator: dst[k][n] = e4m3(q[k][n]) * 2^exps[n], codes [d_in][d_out] row-major, one byte each.  A
+// thread takes 8 columns of a row: an 8-byte load of codes (each read once), an 8-byte load of exponents, the hardware
+// conversion, the scaling in fp32 (v_ldexp_f32, exact: |e| <= 119) and a conversion that rounds nothing (the product is a number of
+// Tout by the format's contract), one 16-byte store.  The two NaN codes give NaN.
+template <typename Tout>
+__global__ __launch_bounds__(256) void cast_copy_kernel(const uint8_t* q, const int8_t* exps, Tout* dst, int64_t ldd, int d_in, int d_out) {
+  typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
+  const int nv = d_out / 8;
+  const int64_t n = (int64_t)d_in * nv;
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t k = idx / nv;
+    const int c = (int)(idx - k * nv) * 8;
+    const u32x2 qv = *(const u32x2*)(q + k * d_out + c);
+    const u32x2 ev = *(const u32x2*)(exps + c);
+    Tout o[8];
+#pragma unroll
+    for (int wd = 0; wd < 2; ++wd) {
+      const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8(qv[wd], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(qv[wd], true);
+      const float v[4] = {lo[0], lo[1], hi[0], hi[1]};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int e = (int)(int8_t)(ev[wd] >> (8 * j));
+        o[4 * wd + j] = from_f32<Tout>(__builtin_ldexpf(v[j], e));   // (not a multiply: fused into the f16 conversion it loses -0)
+      }
+    }
+    *(u32x4*)(dst + k * ldd + c) = *(const u32x4*)o;
+  }
+}
+
+int launch_acc_dequantize(const void* q, const void* exps, int d_in, int d_out, void* dst, int64_t ldd, int dst_dtype,
+                          hipStream_t stream) {
+  if (dst_dtype != SOW_BF16 && dst_dtype != SOW_F16) return SOW_ERR_DTYPE;
+  const int g = grid_for((int64_t)d_in * (d_out / 8));
+  if (dst_dtype == SOW_BF16)
+    hipLaunchKernelGGL((cast_copy_kernel<bf16_t>), dim3(g), dim3(256), 0, stream, (const uint8_t*)q, (const int8_t*)exps,
+                       (bf16_t*)dst, ldd, d_in, d_out);
+  else
+    hipLaunchKernelGGL((cast_copy_kernel<f16_t>), dim3(g), dim3(256), 0, stream, (const uint8_t*)q, (const int8_t*)exps,
+                       (f16_t*)dst, ldd, d_in, d_out);
+  SOW_CHECK_LAUNCH();
+  return SOW_OK;
+}
+
 int launch_cast_copy(const void* src, int64_t lds, int src_dtype, void* dst, int64_t ldd, int dst_dtype, int64_t rows,
                      int cols, hipStream_t stream) {
   if (rows <= 0 || cols <= 0) return SOW_OK;

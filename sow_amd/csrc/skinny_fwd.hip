@@ -27,6 +27,14 @@
 //
 // No atomics, fixed summation order: a repeat gives the same bits, and a layer inside a group (grid concatenation, per-layer
 // block offset) computes exactly what it computes alone.
+//
+// E4M3 accumulator (SOW_ACC_DENSE_FP8, the FP8 = true instantiations): W is the codes, one byte per element, and the column
+// exponents come with it.  Phase A reads a lane's 8 bytes of a row -- 8 columns, 16 lanes = 128 contiguous bytes, so a column
+// range is 128 wide and a wave holds eight 16-column tiles -- converts the codes UNSCALED to the compute dtype in registers
+// (v_cvt_pk_f32_fp8, then the upper halves / v_cvt_pkrtz: every E4M3 value is a bf16 and an f16 number, no rounding happens)
+// and feeds the same MFMA; Py holds sum x . q.  Phase B multiplies the slab-order sum of column n by 2^e_n (exact in fp32)
+// before h . B and the bias.  Everything else -- x staging, the x . A workgroups, the reduction, the order of every sum -- is
+// the code above.
 #include "kernels.hpp"
 
 namespace sow {
@@ -35,15 +43,28 @@ namespace sow {
 #define SOW_SKINNY_NCT 4   // 16-column MFMA tiles per wave: 4 (8-byte loads, 64-column ranges) or 8 (16-byte loads, 128)
 #endif
 constexpr int SK_NCT = SOW_SKINNY_NCT;
-constexpr int SK_CN = 16 * SK_NCT;        // columns per phase-A workgroup
-constexpr int SK_RS = SK_CN + 4;          // row pitch (floats) of the parked tiles: 4 rows apart = 16 banks apart
+constexpr int SK_NCT8 = 8;                // ... of an E4M3 accumulator: 8-byte loads of 8 columns, 128-column ranges
 constexpr int SK_KSTEP = 32;              // k per MFMA step
 constexpr int SK_KQ = 4 * SK_KSTEP;       // k per round of the four waves
 constexpr int SK_KS_MAX = 1024;           // longest K-slab (x slab in LDS: 32 x 1032 x 2 bytes)
 constexpr int SK_XPAD = 8;                // elements of padding per staged x row
 constexpr int SK_WANT_WGS = 512;          // two workgroups per CU
+#ifndef SOW_SKINNY_WANT8
+#define SOW_SKINNY_WANT8 512
+#endif
+constexpr int SK_WANT_WGS8 = SOW_SKINNY_WANT8;   // ... of an E4M3 accumulator (256 and 1024 each win some shapes and lose others: DESIGN 4.5b)
 constexpr int SK_BN = 64;                 // columns per phase-B workgroup
-typedef __attribute__((ext_vector_type(SK_NCT / 2))) uint32_t sk_wvec;
+// what a lane holds of one row of W: NCT columns in NDW dwords
+template <bool FP8> struct SkW {
+  static constexpr int NCT = SK_NCT, NDW = SK_NCT / 2;
+  typedef __attribute__((ext_vector_type(SK_NCT / 2))) uint32_t vec;
+};
+template <> struct SkW<true> {
+  static constexpr int NCT = SK_NCT8, NDW = 2;
+  typedef __attribute__((ext_vector_type(2))) uint32_t vec;
+};
+constexpr int sk_cn(bool fp8) { return 16 * (fp8 ? SK_NCT8 : SK_NCT); }   // columns per phase-A workgroup
+constexpr int sk_rs(bool fp8) { return sk_cn(fp8) + 4; }   // row pitch (floats) of the parked tiles: 4 rows apart = 16 banks apart
 
 struct SkGroup {
   SkLayer L[SK_MAXL];
@@ -52,8 +73,8 @@ struct SkGroup {
 static_assert(sizeof(SkGroup) <= 4096, "by-value kernel arguments must stay under 4 KiB");
 
 void skinny_plan(int d_in, int d_out, int acc_kind, int* S, int* KS, int* ncr) {
-  const int nc = acc_kind == SOW_ACC_DENSE ? ceil_div(d_out, SK_CN) : 0;
-  const int want = nc ? ceil_div(SK_WANT_WGS, nc) : 32;
+  const int nc = acc_kind == SOW_ACC_DENSE ? ceil_div(d_out, sk_cn(false)) : acc_kind == SOW_ACC_DENSE_FP8 ? ceil_div(d_out, sk_cn(true)) : 0;
+  const int want = nc ? ceil_div(acc_kind == SOW_ACC_DENSE_FP8 ? SK_WANT_WGS8 : SK_WANT_WGS, nc) : 32;
   int ks = ceil_div(ceil_div(d_in, want), SK_KQ) * SK_KQ;
   if (ks < SK_KQ) ks = SK_KQ;
   if (ks > SK_KS_MAX) ks = SK_KS_MAX;
@@ -68,7 +89,7 @@ template <> __device__ __forceinline__ f32x4 sk_mfma<f16_t>(u32x4 a, u32x4 b, f3
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(as_v8<f16_t>(a), as_v8<f16_t>(b), c, 0, 0, 0);
 }
 
-__device__ __forceinline__ sk_wvec sk_load_w(const sk_wvec* p) {
+template <typename V> __device__ __forceinline__ V sk_load_w(const V* p) {
 #ifdef SOW_SKINNY_NO_NT
   return *p;
 #else
@@ -76,10 +97,24 @@ __device__ __forceinline__ sk_wvec sk_load_w(const sk_wvec* p) {
 #endif
 }
 
+// two fp32 values that ARE numbers of T (converted E4M3 codes) as a pair of T: nothing is rounded
+template <typename T> __device__ __forceinline__ uint32_t sk_pack_exact(float lo, float hi);
+template <> __device__ __forceinline__ uint32_t sk_pack_exact<bf16_t>(float lo, float hi) {
+  return __builtin_amdgcn_perm(__float_as_uint(hi), __float_as_uint(lo), 0x07060302u);
+}
+template <> __device__ __forceinline__ uint32_t sk_pack_exact<f16_t>(float lo, float hi) {
+  const auto h = __builtin_amdgcn_cvt_pkrtz(lo, hi);
+  uint32_t u;
+  __builtin_memcpy(&u, &h, 4);
+  return u;
+}
+
 constexpr int SK_PF = 4;   // k-steps a wave keeps in flight: all of them are requested before the x slab is staged
 
-template <typename T> __global__ __launch_bounds__(256) void skinny_a_kernel(const SkGroup g) {
+template <typename T, bool FP8 = false> __global__ __launch_bounds__(256) void skinny_a_kernel(const SkGroup g) {
   extern __shared__ __align__(16) char sk_smem[];
+  constexpr int SK_NCT = SkW<FP8>::NCT, SK_CN = sk_cn(FP8), SK_RS = sk_rs(FP8);
+  typedef typename SkW<FP8>::vec sk_wvec;
   int li = 0;
   for (int i = 1; i < g.n; ++i)
     if ((int)blockIdx.x >= g.L[i].startA) li = i;
@@ -101,8 +136,9 @@ template <typename T> __global__ __launch_bounds__(256) void skinny_a_kernel(con
   // W: lane = rows k0 + 8 kg + i, columns col0 .. col0 + NCT - 1.  x . A: lane = the same rows, column j of A, one element.
   sk_wvec d[SK_PF][8];
   const int col0 = cr * SK_CN + n16 * SK_NCT;
-  const bool col_ok = col0 < d_out;   // d_out and NCT are multiples of 4: a lane's columns are all in or all out
-  const T* Wp = (const T*)L.W + col0;
+  const bool col_ok = col0 < d_out;   // d_out is a multiple of 8, NCT of 4 (8 for E4M3): a lane's columns are all in or all out
+  const char* Wp = (const char*)L.W + (size_t)col0 * (FP8 ? 1 : sizeof(T));
+  const size_t wpitch = (size_t)d_out * (FP8 ? 1 : sizeof(T));   // bytes per row of W
   const int r = L.r, ja = cr * 16 + n16;
   const uint16_t* Ap = (const uint16_t*)L.A + ja;
   auto load_step = [&](int kk, sk_wvec(&o)[8]) {
@@ -111,7 +147,7 @@ template <typename T> __global__ __launch_bounds__(256) void skinny_a_kernel(con
       const int k = kbeg + kk + kg * 8 + i;
       sk_wvec v = {};
       if (!is_xa) {
-        if (col_ok && kk < klen && k < d_in) v = sk_load_w((const sk_wvec*)(Wp + (size_t)k * d_out));
+        if (col_ok && kk < klen && k < d_in) v = sk_load_w((const sk_wvec*)(Wp + (size_t)k * wpitch));
       } else {
         if (ja < r && kk < klen && k < d_in) v[0] = Ap[(size_t)k * r];
       }
@@ -149,7 +185,36 @@ template <typename T> __global__ __launch_bounds__(256) void skinny_a_kernel(con
         const u32x4 a0 = *(const u32x4*)(xa0 + kk * 2);
         u32x4 a1 = {0u, 0u, 0u, 0u};
         if (rows == 32) a1 = *(const u32x4*)(xa1 + kk * 2);
-        if (!is_xa) {
+        if (is_xa) {
+          u32x4 f;
+#pragma unroll
+          for (int m = 0; m < 4; ++m) f[m] = d[p][2 * m][0] | (d[p][2 * m + 1][0] << 16);
+          acc[0][0] = sk_mfma<T>(a0, f, acc[0][0]);
+          if (rows == 32) acc[0][1] = sk_mfma<T>(a1, f, acc[0][1]);
+        } else if constexpr (FP8) {
+          // dword wd of a row = columns 4 wd .. 4 wd + 3: the conversion yields two columns of one row, a fragment register
+          // wants two rows of one column
+#pragma unroll
+          for (int wd = 0; wd < 2; ++wd) {
+            u32x4 f[4];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+              const uint32_t r0 = d[p][2 * m][wd], r1 = d[p][2 * m + 1][wd];
+              const auto r0l = __builtin_amdgcn_cvt_pk_f32_fp8(r0, false), r0h = __builtin_amdgcn_cvt_pk_f32_fp8(r0, true);
+              const auto r1l = __builtin_amdgcn_cvt_pk_f32_fp8(r1, false), r1h = __builtin_amdgcn_cvt_pk_f32_fp8(r1, true);
+              f[0][m] = sk_pack_exact<T>(r0l[0], r1l[0]);
+              f[1][m] = sk_pack_exact<T>(r0l[1], r1l[1]);
+              f[2][m] = sk_pack_exact<T>(r0h[0], r1h[0]);
+              f[3][m] = sk_pack_exact<T>(r0h[1], r1h[1]);
+            }
+#pragma unroll
+            for (int cc = 0; cc < 4; ++cc) {
+              const int c = 4 * wd + cc;
+              acc[c][0] = sk_mfma<T>(a0, f[cc], acc[c][0]);
+              if (rows == 32) acc[c][1] = sk_mfma<T>(a1, f[cc], acc[c][1]);
+            }
+          }
+        } else {
 #pragma unroll
           for (int c = 0; c < SK_NCT; ++c) {
             u32x4 f;
@@ -159,12 +224,6 @@ template <typename T> __global__ __launch_bounds__(256) void skinny_a_kernel(con
             acc[c][0] = sk_mfma<T>(a0, f, acc[c][0]);
             if (rows == 32) acc[c][1] = sk_mfma<T>(a1, f, acc[c][1]);
           }
-        } else {
-          u32x4 f;
-#pragma unroll
-          for (int m = 0; m < 4; ++m) f[m] = d[p][2 * m][0] | (d[p][2 * m + 1][0] << 16);
-          acc[0][0] = sk_mfma<T>(a0, f, acc[0][0]);
-          if (rows == 32) acc[0][1] = sk_mfma<T>(a1, f, acc[0][1]);
         }
         load_step(kk + SK_PF * SK_KQ, d[p]);   // (requests nothing past the slab)
       }
@@ -214,7 +273,7 @@ template <typename T> __global__ __launch_bounds__(256) void skinny_a_kernel(con
 // instead of a chain of r + 2 S + 1, and only the fp32 additions run in order.
 constexpr int SK_BS = 16;   // slab partials requested up front; a layer with more slabs adds the rest in a second loop
 
-template <typename T> __global__ __launch_bounds__(256) void skinny_b_kernel(const SkGroup g) {
+template <typename T, bool FP8 = false> __global__ __launch_bounds__(256) void skinny_b_kernel(const SkGroup g) {
   __shared__ float hs[4][64];
   int li = 0;
   for (int i = 1; i < g.n; ++i)
@@ -237,6 +296,9 @@ template <typename T> __global__ __launch_bounds__(256) void skinny_b_kernel(con
     for (int j = 0; j < 64; ++j) bv[j] = B[(size_t)min(j, r - 1) * d_out];
   }
   const T bias = L.bias ? ((const T*)L.bias)[nc] : from_f32<T>(0.f);
+  int wexp = 0;   // the column's exponent: |e| <= 119, 2^e is a normal fp32 number
+  if constexpr (FP8)
+    if (dense) wexp = L.wexp[nc];
   float ph[SK_BS], py[SK_BS];
   const float* Ph = L.Ph + (size_t)tc * 64 + jc;
   const size_t phs = (size_t)Tn * 64;
@@ -262,6 +324,7 @@ template <typename T> __global__ __launch_bounds__(256) void skinny_b_kernel(con
     for (int u = 0; u < SK_BS; ++u)
       if (u < S) acc += py[u];
     for (int s = SK_BS; s < S; ++s) acc += Py[(size_t)s * pys];
+    if constexpr (FP8) acc *= __uint_as_float((uint32_t)(wexp + 127) << 23);   // sum x . q, scaled once: exact
   }
   __syncthreads();
   if (!live) return;
@@ -280,6 +343,11 @@ size_t skinny_ph_bytes(int64_t T, int S) { return (size_t)S * (size_t)T * 64 * s
 int launch_skinny_fwd(const SkLayer* layers, int n, int dtype, hipStream_t stream) {
   if (n <= 0) return SOW_OK;
   if (n > SK_MAXL || (dtype != SOW_BF16 && dtype != SOW_F16)) return SOW_ERR_UNSUPPORTED;
+  // the dense layers of a call are of one kind: the kernels are instantiated per kind
+  bool fp8 = false, plain = false;
+  for (int i = 0; i < n; ++i) (layers[i].wexp ? fp8 : plain) |= layers[i].W != nullptr;
+  if (fp8 && plain) return SOW_ERR_UNSUPPORTED;
+  const int SK_RS = sk_rs(fp8);
   SkGroup g;
   g.n = n;
   int na = 0, nb = 0;
@@ -287,8 +355,9 @@ int launch_skinny_fwd(const SkLayer* layers, int n, int dtype, hipStream_t strea
   for (int i = 0; i < n; ++i) {
     SkLayer& L = g.L[i];
     L = layers[i];
+    if (!L.W) L.wexp = nullptr;
     int ncr;
-    skinny_plan(L.d_in, L.d_out, L.W ? SOW_ACC_DENSE : SOW_ACC_NONE, &L.S, &L.KS, &ncr);
+    skinny_plan(L.d_in, L.d_out, !L.W ? SOW_ACC_NONE : fp8 ? SOW_ACC_DENSE_FP8 : SOW_ACC_DENSE, &L.S, &L.KS, &ncr);
     L.ncr = ncr;
     L.startA = na, L.startB = nb;
     na += L.S * ((L.r + 15) / 16 + ncr);
@@ -298,8 +367,20 @@ int launch_skinny_fwd(const SkLayer* layers, int n, int dtype, hipStream_t strea
     lds = xb > lds ? xb : lds;
     lds = rb > lds ? rb : lds;
   }
-  constexpr int LDS_MAX = 4 * 32 * SK_RS * 4 > 32 * (SK_KS_MAX + SK_XPAD) * 2 ? 4 * 32 * SK_RS * 4 : 32 * (SK_KS_MAX + SK_XPAD) * 2;
-  if (dtype == SOW_BF16) {
+  constexpr int LDS_X = 32 * (SK_KS_MAX + SK_XPAD) * 2;
+  constexpr int LDS_MAX = 4 * 32 * sk_rs(false) * 4 > LDS_X ? 4 * 32 * sk_rs(false) * 4 : LDS_X;
+  constexpr int LDS_MAX8 = 4 * 32 * sk_rs(true) * 4 > LDS_X ? 4 * 32 * sk_rs(true) * 4 : LDS_X;
+  if (fp8 && dtype == SOW_BF16) {
+    SOW_SET_MAX_LDS_ONCE(LDS_MAX8, skinny_a_kernel<bf16_t, true>);
+    hipLaunchKernelGGL((skinny_a_kernel<bf16_t, true>), dim3(na), dim3(256), lds, stream, g);
+    SOW_CHECK_LAUNCH();
+    hipLaunchKernelGGL((skinny_b_kernel<bf16_t, true>), dim3(nb), dim3(256), 0, stream, g);
+  } else if (fp8) {
+    SOW_SET_MAX_LDS_ONCE(LDS_MAX8, skinny_a_kernel<f16_t, true>);
+    hipLaunchKernelGGL((skinny_a_kernel<f16_t, true>), dim3(na), dim3(256), lds, stream, g);
+    SOW_CHECK_LAUNCH();
+    hipLaunchKernelGGL((skinny_b_kernel<f16_t, true>), dim3(nb), dim3(256), 0, stream, g);
+  } else if (dtype == SOW_BF16) {
     SOW_SET_MAX_LDS_ONCE(LDS_MAX, skinny_a_kernel<bf16_t>);
     hipLaunchKernelGGL(skinny_a_kernel<bf16_t>, dim3(na), dim3(256), lds, stream, g);
     SOW_CHECK_LAUNCH();

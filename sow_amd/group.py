@@ -61,8 +61,11 @@ class _SoWGroupFunction(torch.autograd.Function):
             x2 = autocast_input(x2, cdt)     # an fp32 input is cast once for the whole group
         per = [tensors[5 * i:5 * i + 5] for i in range(n)]
         need_bwd = any(ctx.needs_input_grad)
+        # E4M3 accumulators (codes, exponents): the siblings' images side by side in the scratch arena; the codes are what is
+        # saved, backward builds the images again
+        accs = ops.acc_operands([(t[2], t[3]) for t in per], x2.dtype)
         calls = []
-        for (A, B, acc_down, acc_up, bias), s in zip(per, scales):
+        for (A, B, _, _, bias), (acc_down, acc_up), s in zip(per, accs, scales):
             kind = ops.acc_kind(acc_down, acc_up)
             calls.append(ops.LayerCall(x2, A.contiguous(), B.contiguous(),
                                        acc_down=acc_down.contiguous() if kind != _lib.ACC_NONE else None,
@@ -80,7 +83,10 @@ class _SoWGroupFunction(torch.autograd.Function):
     def backward(ctx, *dys):
         n = ctx.n
         saved = ctx.saved_tensors
-        x2, hs, tensors = saved[0], saved[1:1 + n], saved[1 + n:]
+        x2, hs, tensors = saved[0], saved[1:1 + n], list(saved[1 + n:])
+        for i, (acc_down, acc_up) in enumerate(ops.acc_operands([(tensors[5 * i + 2], tensors[5 * i + 3]) for i in range(n)],
+                                                                x2.dtype)):
+            tensors[5 * i + 2], tensors[5 * i + 3] = acc_down, acc_up
         sinks = ctx.sinks
         if sinks is not None and x2.shape[0] > 0 and all(
                 s.usable(tensors[5 * i], tensors[5 * i + 1], tensors[5 * i + 4]) for i, s in enumerate(sinks)):
@@ -204,7 +210,7 @@ class SiblingGroup:
             # loaded in another precision, load_sow): the layer runs on its own and raises exactly what the ungrouped
             # call raises
             try:
-                ops.check_accumulator(x, m.in_features, m.out_features, m.acc_downweight, m.acc_upweight,
+                ops.check_accumulator(x, m.in_features, m.out_features, *m._acc_pair(),
                                       param_dtype=pdt if cdt is not None else None)
             except (TypeError, ValueError, RuntimeError):
                 return False
@@ -220,9 +226,12 @@ class SiblingGroup:
         calls = []
         for m in self.layers:
             A, B = m.downscale_weights._parameters["0"], m.upscale_weights._parameters["0"]
-            if not ops.skinny_admits(x2, A, B, m.acc_downweight, m.acc_upweight, m.bias):
+            acc_down, acc_up = m._acc_pair()
+            if not ops.skinny_admits(x2, A, B, acc_down, acc_up, m.bias):
                 return None
-            calls.append((x2, A, B, m.acc_downweight if m.acc_downweight.numel() else None, m.bias, float(m.scale)))
+            calls.append((x2, A, B, ops.skinny_acc(acc_down, acc_up), m.bias, float(m.scale)))
+        if len({isinstance(c[3], tuple) for c in calls if c[3] is not None}) > 1:
+            return None        # E4M3 and unquantised dense accumulators in one set: the library takes one kind per call
         ys = ops.sow_forward_skinny(calls)
         if ys is None:
             return None
@@ -250,8 +259,7 @@ class SiblingGroup:
                 return ys[self.layers.index(layer)]
         tensors = []
         for m in self.layers:
-            tensors += [m.downscale_weights._parameters["0"], m.upscale_weights._parameters["0"], m.acc_downweight,
-                        m.acc_upweight, m.bias]
+            tensors += [m.downscale_weights._parameters["0"], m.upscale_weights._parameters["0"], *m._acc_pair(), m.bias]
         sinks = tuple(getattr(m, "_grad_sink", None) for m in self.layers)
         ys = _SoWGroupFunction.apply(x, tuple(float(m.scale) for m in self.layers), sinks if sinks[0] is not None else None,
                                      cdt, self.shared_input, *tensors)

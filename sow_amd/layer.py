@@ -69,7 +69,7 @@ def _fuse_acc(x2, B, acc_down, acc_up, mixed: bool) -> int:
     """The permission of a module call (ops.acc_permission: SOW_FUSE_ACC, SOW_FUSE_ACC_DEEP or 0): the same answer on the
     grad and the no-grad route, so that eval and train outputs stay bit-identical."""
     kind = ops.acc_kind(acc_down, acc_up)
-    if kind != ops._lib.ACC_LOWRANK or acc_down.dim() != 2:
+    if kind != ops._lib.ACC_LOWRANK or acc_down.dim() != 2:     # (an E4M3 accumulator is dense: no permission)
         return 0
     return ops.acc_permission(x2.shape[0], x2.shape[1], B.shape[1], B.shape[0], acc_down.shape[1], kind, x2.dtype, mixed)
 
@@ -93,7 +93,10 @@ class _SoWFunction(torch.autograd.Function):
             acc_up = acc_up.contiguous()
         # a low-rank accumulator and the live term in one pass where the library admits it and it measures faster
         fuse = _fuse_acc(x2, B, acc_down, acc_up, cdt is not None)
-        y, h = ops.sow_forward(x2, A, B, acc_down, acc_up, bias, scale, param_f32=cdt is not None, fuse_acc=fuse)
+        # an E4M3 accumulator (codes, exponents): the dense kernels run on its image in the scratch arena; what is saved
+        # below is the codes, and backward builds the image again
+        (img_down, img_up), = ops.acc_operands([(acc_down, acc_up)], x2.dtype)
+        y, h = ops.sow_forward(x2, A, B, img_down, img_up, bias, scale, param_f32=cdt is not None, fuse_acc=fuse)
         ctx.fuse_acc = fuse
         ctx.save_for_backward(x2, h, A, B, acc_down, acc_up)
         ctx.scale = scale
@@ -107,6 +110,7 @@ class _SoWFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x2, h, A, B, acc_down, acc_up = ctx.saved_tensors
+        (acc_down, acc_up), = ops.acc_operands([(acc_down, acc_up)], x2.dtype)
         dy2 = dy.reshape(-1, dy.shape[-1])
         sink = ctx.sink
         if sink is not None and x2.shape[0] > 0 and sink.usable(A, B, ctx.bias):
@@ -185,6 +189,43 @@ class SoWLinear(nn.Module):
         # sum_i A_i B_i = [A_1 .. A_n] [B_1; ..; B_n]; autograd splits the gradients back
         return torch.cat(list(self.downscale_weights), dim=1), torch.cat(list(self.upscale_weights), dim=0)
 
+    # ------------------------------------------------------------------------------------------
+    # A dense accumulator quantised by sow_amd.quantize_accumulators: acc_downweight holds the E4M3 codes (a frozen
+    # float8_e4m3fn parameter) and the persistent buffer acc_exponent the int8 column exponents.  An unquantised layer has no
+    # such buffer: its state-dict keys are the reference's.
+    def acc_quantized(self) -> bool:
+        return self._buffers.get("acc_exponent") is not None
+
+    def _acc_pair(self):
+        """(acc_down, acc_up) as the kernels' wrappers take them: the exponents ride in acc_up's place next to the codes."""
+        exps = self._buffers.get("acc_exponent")
+        return (self.acc_downweight, self.acc_upweight if exps is None else exps)
+
+    def _apply(self, fn, *args, **kwargs):
+        # .half() / .bfloat16() / .to(dtype) cast every floating-point parameter: the codes would become their unscaled values
+        # in the new dtype.  They stay codes (moved with the module); the layer then computes in the dtype of its factors.
+        codes = self.acc_downweight.data if self.acc_quantized() else None     # (the tensor: _apply rebinds the parameter's .data)
+        super()._apply(fn, *args, **kwargs)
+        if codes is not None and self.acc_downweight.dtype != ops.FP8:
+            self.acc_downweight = nn.Parameter(codes.to(self.acc_downweight.device), requires_grad=False)
+        return self
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        # a quantised state dict into an unquantised layer (or the other way round): the layer takes the form of what it loads,
+        # so that strict loading sees the keys it expects and the codes are copied as codes
+        codes, exps = state_dict.get(prefix + "acc_downweight"), state_dict.get(prefix + "acc_exponent")
+        if exps is not None and codes is not None and codes.dtype == ops.FP8 and not (
+                self.acc_quantized() and self.acc_downweight.dtype == ops.FP8 and self.acc_downweight.shape == codes.shape):
+            dev = self.acc_downweight.device
+            self.acc_downweight = nn.Parameter(torch.empty(codes.shape, dtype=ops.FP8, device=dev), requires_grad=False)
+            self._buffers.pop("acc_exponent", None)
+            self.register_buffer("acc_exponent", torch.empty(exps.shape, dtype=torch.int8, device=dev))
+        elif exps is None and codes is not None and codes.dtype != ops.FP8 and self.acc_quantized():
+            del self._buffers["acc_exponent"]
+            self.acc_downweight = nn.Parameter(torch.empty(codes.shape, dtype=codes.dtype, device=self.acc_downweight.device),
+                                               requires_grad=False)
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """sow.py:107-126 in one fused call: accumulator term (not scaled) + scale * (x A) B + bias."""
         group = self.__dict__.get("_sibling_group")     # sow_amd.group.group_siblings: q/k/v or gate/up in one launch
@@ -193,6 +234,7 @@ class SoWLinear(nn.Module):
             if y is not None:
                 return y
         A, B = self._cat_factors()
+        acc_down, acc_up = self._acc_pair()
         # torch.autocast with fp32 factors: bf16 / f16 kernels on factors rounded once by the library, fp32 gradients
         cdt = autocast_compute_dtype(A.dtype)
         if not (torch.is_grad_enabled() and (x.requires_grad or A.requires_grad or B.requires_grad
@@ -201,28 +243,29 @@ class SoWLinear(nn.Module):
             # checkpointing): the projection h = scale * x A is not written to HBM
             x2 = x.reshape(-1, x.shape[-1])
             # generation-sized calls (generate(): batch x beams rows per new token): the fused skinny forward, two launches,
-            # the accumulator streamed once on the whole chip.  Autocast with fp32 parameters, a low-rank accumulator, a
-            # wide rank, ragged widths and a refusal from the library keep the path below.
-            if cdt is None and x2.shape[0] <= ops.SKINNY_MAX_T and ops.skinny_admits(
-                    x2, A, B, self.acc_downweight, self.acc_upweight, self.bias):
-                acc = self.acc_downweight if self.acc_downweight.numel() else None
-                ys = ops.sow_forward_skinny([(x2, A, B, acc, self.bias, float(self.scale))])
+            # the accumulator (or its E4M3 codes: half the bytes) streamed once on the whole chip.  Autocast with fp32
+            # parameters, a low-rank accumulator, a wide rank, ragged widths and a refusal from the library keep the path below.
+            if cdt is None and x2.shape[0] <= ops.SKINNY_MAX_T and ops.skinny_admits(x2, A, B, acc_down, acc_up, self.bias):
+                ys = ops.sow_forward_skinny([(x2, A, B, ops.skinny_acc(acc_down, acc_up), self.bias, float(self.scale))])
                 if ys is not None:
                     return ys[0].reshape(*x.shape[:-1], B.shape[1])
             if cdt is not None:
                 x2 = autocast_input(x2.contiguous(), cdt)
-            y, _ = ops.sow_forward(x2, A, B, self.acc_downweight, self.acc_upweight, self.bias, float(self.scale), save_h=False,
-                                   param_f32=cdt is not None,
-                                   fuse_acc=_fuse_acc(x2, B, self.acc_downweight, self.acc_upweight, cdt is not None))
+            # every other call of a quantised layer: the existing dense path on the image
+            (acc_down, acc_up), = ops.acc_operands([(acc_down, acc_up)], x2.dtype)
+            y, _ = ops.sow_forward(x2, A, B, acc_down, acc_up, self.bias, float(self.scale), save_h=False,
+                                   param_f32=cdt is not None, fuse_acc=_fuse_acc(x2, B, acc_down, acc_up, cdt is not None))
             return y.reshape(*x.shape[:-1], B.shape[1])
-        return _SoWFunction.apply(x, A, B, self.acc_downweight, self.acc_upweight, self.bias, float(self.scale),
-                                  getattr(self, "_grad_sink", None), cdt)
+        return _SoWFunction.apply(x, A, B, acc_down, acc_up, self.bias, float(self.scale), getattr(self, "_grad_sink", None), cdt)
 
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
     def accumulate(self):
         """sow.py:128-178: fold scale * sum_i A_i B_i into the accumulator, optionally re-factor it by
         truncated QR, re-initialise A, zero B."""
+        if self.acc_quantized():
+            raise RuntimeError("SoWLinear.accumulate: the accumulator is quantised (E4M3) and frozen; merging into it would "
+                               "requantise it.  Call sow_amd.dequantize_accumulators(model) first")
         A = torch.cat([w.data for w in self.downscale_weights], dim=1) if self.n_iter > 1 else self.downscale_weights[0].data
         B = torch.cat([w.data for w in self.upscale_weights], dim=0) if self.n_iter > 1 else self.upscale_weights[0].data
         if not A.is_cuda:

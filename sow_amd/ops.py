@@ -14,6 +14,7 @@ import torch
 from . import _lib
 
 _DT = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
+FP8 = torch.float8_e4m3fn      # the codes of a quantised dense accumulator (include/sow_amd.h: SOW_ACC_DENSE_FP8)
 
 
 def _dt(t: torch.Tensor) -> int:
@@ -127,9 +128,12 @@ def _workspace_bytes(lib, T: int, d_in: int, d_out: int, r: int, r_acc: int, kin
 
 
 def acc_kind(acc_down: Optional[torch.Tensor], acc_up: Optional[torch.Tensor]) -> int:
-    """Accumulator kind as SoWLinear.forward decides it (reference sow.py:109-112)."""
+    """Accumulator kind as SoWLinear.forward decides it (reference sow.py:109-112).  E4M3 codes in acc_down (with their int8
+    column exponents in acc_up) are a quantised dense accumulator."""
     if acc_down is None or acc_down.numel() == 0:
         return _lib.ACC_NONE
+    if acc_down.dtype == FP8:
+        return _lib.ACC_DENSE_FP8
     if acc_up is None or acc_up.numel() == 0:
         return _lib.ACC_DENSE
     return _lib.ACC_LOWRANK
@@ -146,6 +150,19 @@ def check_accumulator(x2: torch.Tensor, d_in: int, d_out: int, acc_down, acc_up,
     if kind == _lib.ACC_NONE:
         return kind, 0
     r_acc = 0
+    if kind == _lib.ACC_DENSE_FP8:
+        if param_dtype is not None or x2.dtype not in (torch.bfloat16, torch.float16):
+            raise TypeError(f"{who}: an E4M3 accumulator runs with bfloat16 or float16 inputs and parameters, got {x2.dtype}"
+                            + ("" if param_dtype is None else f" inputs and {param_dtype} parameters"))
+        if acc_up is None or acc_up.dtype != torch.int8:
+            raise TypeError(f"{who}: an E4M3 accumulator comes with int8 column exponents")
+        if tuple(acc_down.shape) != (d_in, d_out) or tuple(acc_up.shape) != (d_out,) or d_out % 8:
+            raise ValueError(f"{who}: an E4M3 accumulator is [in_features, out_features] codes and [out_features] exponents, "
+                             "out_features a multiple of 8")
+        for t in (acc_down, acc_up):
+            if not t.is_cuda or t.device != x2.device:
+                raise RuntimeError(f"{who}: the accumulator is on {t.device}, the input on {x2.device}")
+        return kind, 0
     want = x2.dtype if param_dtype is None else param_dtype
     if acc_down.dtype != want or (kind == _lib.ACC_LOWRANK and acc_up.dtype != want):
         bad = acc_down.dtype if acc_down.dtype != want else acc_up.dtype
@@ -318,6 +335,75 @@ def shared_fused_acc_pays(r_tots: Sequence[int]) -> bool:
     return shared_fused_acc_lds_bytes(r_tots) <= SHARED_FUSED_ACC_PAYS_LDS
 
 
+def acc_dequantize(codes: torch.Tensor, exps: torch.Tensor, dtype: torch.dtype, out: Optional[torch.Tensor] = None):
+    """The image of an E4M3 accumulator, W^[k, n] = codes[k, n] * 2^exps[n], exactly, in bf16 or f16 (sow_acc_dequantize: one
+    streaming pass).  `out`: a [d_in, d_out] tensor of `dtype` whose rows are contiguous (any row pitch that is a multiple of
+    8), written in place."""
+    dev = _need_gpu(codes, exps, out)
+    if codes.dtype != FP8 or exps.dtype != torch.int8 or codes.dim() != 2 or tuple(exps.shape) != (codes.shape[1],):
+        raise TypeError("sow_amd.acc_dequantize: float8_e4m3fn codes [d_in, d_out] and int8 exponents [d_out]")
+    if dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"sow_amd.acc_dequantize: the image is bfloat16 or float16, not {dtype}")
+    d_in, d_out = codes.shape
+    codes, exps = codes.contiguous(), exps.contiguous()
+    if out is None:
+        out = torch.empty((d_in, d_out), dtype=dtype, device=dev)
+    elif out.dtype != dtype or tuple(out.shape) != (d_in, d_out) or (d_out > 1 and out.stride(1) != 1):
+        raise ValueError("sow_amd.acc_dequantize: `out` must be a [d_in, d_out] tensor of the image dtype with contiguous rows")
+    if d_in and d_out:
+        _launch(dev, "sow_acc_dequantize", _lib.load().sow_acc_dequantize, _ptr(codes), _ptr(exps), d_in, d_out, _ptr(out),
+                out.stride(0) if d_in > 1 else d_out, _DT[dtype])
+    return out
+
+
+# The scratch arena of the images: one buffer per (device, dtype), sized to the largest single call so far (one layer, or the
+# siblings of a group), reused by every quantised layer in stream order.  An image is valid until the next acc_images() call
+# for that (device, dtype) on the stream it was built on; nothing keeps it (autograd saves the codes and rebuilds it).
+_ARENAS: dict = {}
+_ARENAS_CAPTURED: set = set()    # arenas a HIP graph has recorded the address of ...
+_ARENAS_RETIRED: list = []       # ... are kept alive when a larger one replaces them: a replay still writes there
+
+
+def acc_images(pairs, dtype: torch.dtype) -> list:
+    """The images of the E4M3 accumulators `pairs` = [(codes, exps), ...] of ONE call, side by side in the scratch arena.
+    The arena grows only outside graph capture: a capture needs one eager call of the same model first."""
+    dev = pairs[0][0].device
+    es = torch.empty((), dtype=dtype).element_size()
+    sizes = [(c.numel() * es + 255) // 256 * 256 for c, _ in pairs]
+    need, key = sum(sizes), (dev, dtype)
+    buf = _ARENAS.get(key)
+    capturing = torch.cuda.is_current_stream_capturing()
+    if buf is None or buf.numel() < need:
+        if capturing:
+            raise RuntimeError("sow_amd: the scratch arena of the E4M3 accumulator images cannot grow during graph capture; "
+                               "run the captured calls once eagerly first")
+        if buf is not None and key in _ARENAS_CAPTURED:
+            _ARENAS_RETIRED.append(buf)
+            _ARENAS_CAPTURED.discard(key)
+        with torch.cuda.device(dev):
+            buf = _ARENAS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+    if capturing:
+        _ARENAS_CAPTURED.add(key)
+    out, off = [], 0
+    for (codes, exps), n in zip(pairs, sizes):
+        img = buf[off:off + codes.numel() * es].view(dtype).view(codes.shape)
+        out.append(acc_dequantize(codes, exps, dtype, out=img))
+        off += n
+    return out
+
+
+def acc_operands(accs, dtype: torch.dtype) -> list:
+    """(acc_down, acc_up) of every layer of ONE call as the dense kernels read them: an E4M3 accumulator (codes, exponents)
+    is replaced by (its image in the scratch arena, None), everything else passes through."""
+    fp8 = [i for i, (d, _) in enumerate(accs) if d is not None and d.numel() and d.dtype == FP8]
+    if not fp8:
+        return list(accs)
+    out = list(accs)
+    for i, img in zip(fp8, acc_images([accs[i] for i in fp8], dtype)):
+        out[i] = (img, None)
+    return out
+
+
 def sow_forward(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, acc_up, bias, scale: float,
                 save_h: bool = True, *, param_f32: bool = False, fuse_acc=False):
     """y, h_save = forward of the SoW contraction on a flattened [T, d_in] input.  save_h = False (no-grad / eval callers,
@@ -367,12 +453,14 @@ _SKINNY_WS_BYTES: dict = {}
 
 
 def skinny_workspace_bytes(T: int, d_in: int, d_out: int, r: int, kind: int, dt: int) -> int:
-    """sow_forward_skinny_workspace_bytes, memoised per shape: 0 = the shape is outside the admitted set.  A pure function
+    """sow_forward_skinny_workspace_bytes (sow_forward_skinny_fp8_workspace_bytes for an E4M3 accumulator), memoised per shape: 0 = the shape is outside the admitted set.  A pure function
     of the shape (no switch enters), so the memo is never dropped."""
     key = (T, d_in, d_out, r, kind, dt)
     n = _SKINNY_WS_BYTES.get(key)
     if n is None:
-        n = _SKINNY_WS_BYTES[key] = int(_lib.load().sow_forward_skinny_workspace_bytes(T, d_in, d_out, r, kind, dt))
+        lib = _lib.load()
+        n = _SKINNY_WS_BYTES[key] = int(lib.sow_forward_skinny_fp8_workspace_bytes(T, d_in, d_out, r, dt) if kind == _lib.ACC_DENSE_FP8
+                                        else lib.sow_forward_skinny_workspace_bytes(T, d_in, d_out, r, kind, dt))
     return n
 
 
@@ -382,10 +470,29 @@ def skinny_pays(T: int, d_in: int, d_out: int) -> bool:
     return 1 <= T <= SKINNY_MAX_T
 
 
+def skinny_fp8_pays(T: int, d_in: int, d_out: int) -> bool:
+    """The measured dispatch rule for an E4M3 accumulator (profiles/fp8_acc.txt), the one place that
+    encodes it: the calls at which streaming the codes (q) is faster than the image pass followed by the bf16 skinny forward
+    on the image (d).  Measured (us, r = 50, T = 4 / 32): 4096->4096 25.4 / 32.9 against 40.8 / 44.2, 4096->11008 37.6 / 47.4
+    against 67.4 / 92.6, 11008->4096 37.4 / 47.4 against 67.8 / 83.7, 512->512 17.7 / 19.8 against 20.5 / 22.2, q + k + v of
+    4096->4096 39.9 / 59.3 against 73.7 / 88.0; q / d lies between 0.47 and 0.89 in all 48 rows (T = 1, 4, 16, 32; r = 8, 50):
+    the rule excludes nothing.  NOT measured: f16, widths above 11008."""
+    return 1 <= T <= SKINNY_MAX_T
+
+
+def skinny_acc(acc_down, acc_up):
+    """The accumulator element of a sow_forward_skinny layer tuple: None, the dense tensor, or (codes, exponents)."""
+    kind = acc_kind(acc_down, acc_up)
+    if kind == _lib.ACC_NONE:
+        return None
+    return (acc_down, acc_up) if kind == _lib.ACC_DENSE_FP8 else acc_down
+
+
 def skinny_admits(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, acc_up, bias) -> bool:
     """Whether a no-grad module call on the flattened input x2 may go to sow_forward_skinny: a bf16 / f16 call of at most 32
-    tokens with parameters of the input's dtype, a dense accumulator or none, and a shape the library admits and the
-    dispatch rule keeps.  False sends the caller to the existing path, which raises whatever it raises today."""
+    tokens with parameters of the input's dtype, a dense accumulator (in that dtype or as E4M3 codes) or none, and a shape the
+    library admits and the dispatch rule keeps.  False sends the caller to the existing path, which raises whatever it raises
+    today."""
     dt = _DT.get(x2.dtype)
     if dt is None or dt == _lib.F32 or not x2.is_cuda or x2.dim() != 2 or not 1 <= x2.shape[0] <= SKINNY_MAX_T:
         return False
@@ -394,10 +501,14 @@ def skinny_admits(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, 
         return False
     T, d_in = x2.shape
     r, d_out = B.shape
-    if tuple(A.shape) != (d_in, r) or (kind == _lib.ACC_DENSE and tuple(acc_down.shape) != (d_in, d_out)):
+    if tuple(A.shape) != (d_in, r) or (kind != _lib.ACC_NONE and tuple(acc_down.shape) != (d_in, d_out)):
         return False
     for t in (A, B, bias, acc_down if kind == _lib.ACC_DENSE else None):
         if t is not None and (t.dtype != x2.dtype or t.device != x2.device):
+            return False
+    if kind == _lib.ACC_DENSE_FP8:
+        if (acc_up is None or acc_up.dtype != torch.int8 or tuple(acc_up.shape) != (d_out,) or acc_down.device != x2.device
+                or acc_up.device != x2.device or not skinny_fp8_pays(T, d_in, d_out)):
             return False
     return skinny_pays(T, d_in, d_out) and skinny_workspace_bytes(T, d_in, d_out, r, kind, dt) > 0
 
@@ -405,7 +516,7 @@ def skinny_admits(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, 
 def sow_forward_skinny(layers) -> Optional[list]:
     """y_i of n <= 16 independent generation-sized layer calls (T_i <= 32 tokens) in two launches (include/sow_amd.h:
     sow_forward_skinny).  `layers`: one (x2, A, B, acc_down, bias, scale) per layer -- x2 [T, d_in] bf16 / f16, acc_down the
-    dense accumulator or None.  Returns the list of outputs, or None when the library refuses the set (nothing was launched:
+    dense accumulator, the (codes, exponents) pair of an E4M3 one, or None.  Returns the list of outputs, or None when the library refuses the set (nothing was launched:
     the caller runs sow_forward / LayerGroup instead)."""
     lib = _lib.load()
     n = len(layers)
@@ -417,34 +528,40 @@ def sow_forward_skinny(layers) -> Optional[list]:
     dt = _dt(x0)
     keep, sizes, total = [], [], 0
     for x2, A, B, acc_down, bias, scale in layers:
-        dev = _need_gpu(x2, A, B, acc_down, bias)
-        if dev != x0.device or any(t is not None and t.dtype != x0.dtype for t in (x2, A, B, acc_down, bias)):
+        exps = None
+        if isinstance(acc_down, tuple):
+            acc_down, exps = acc_down
+            if acc_down.dtype != FP8 or exps.dtype != torch.int8 or tuple(exps.shape) != (acc_down.shape[-1],):
+                raise TypeError("sow_amd.sow_forward_skinny: an E4M3 accumulator is (float8_e4m3fn codes, int8 exponents)")
+        dev = _need_gpu(x2, A, B, acc_down, exps, bias)
+        if dev != x0.device or any(t is not None and t.dtype != x0.dtype
+                                   for t in (x2, A, B, acc_down if exps is None else None, bias)):
             raise TypeError("sow_amd.sow_forward_skinny: all tensors of a call share one dtype and one device")
         T, d_in = x2.shape
         r, d_out = B.shape
         if tuple(A.shape) != (d_in, r) or (acc_down is not None and tuple(acc_down.shape) != (d_in, d_out)) or (
                 bias is not None and tuple(bias.shape) != (d_out,)):
             raise ValueError("sow_amd.sow_forward_skinny: operand shapes do not match")
-        kind = _lib.ACC_NONE if acc_down is None else _lib.ACC_DENSE
+        kind = _lib.ACC_NONE if acc_down is None else _lib.ACC_DENSE if exps is None else _lib.ACC_DENSE_FP8
         nws = skinny_workspace_bytes(T, d_in, d_out, r, kind, dt) if T else 0
         if T and not nws:
             return None
         nws = (nws + 255) & ~255
         keep.append((x2.contiguous(), A.contiguous(), B.contiguous(), None if acc_down is None else acc_down.contiguous(),
-                     None if bias is None else bias.contiguous()))
+                     None if bias is None else bias.contiguous(), None if exps is None else exps.contiguous(), kind))
         sizes.append((total, nws))
         total += nws
     ws = _ws(total, x0.device)       # one allocation, carved at 256-byte offsets
     base = ws.data_ptr()
     arr = (_lib.LayerArgs * n)()
     ys = []
-    for i, ((x2, A, B, acc_down, bias), (off, nws), layer) in enumerate(zip(keep, sizes, layers)):
+    for i, ((x2, A, B, acc_down, bias, exps, kind), (off, nws), layer) in enumerate(zip(keep, sizes, layers)):
         y = torch.empty((x2.shape[0], B.shape[1]), dtype=x2.dtype, device=x0.device)
         ys.append(y)
         a = arr[i]
         a.x, a.A, a.B, a.acc_down, a.bias, a.y = _ptr(x2), _ptr(A), _ptr(B), _ptr(acc_down), _ptr(bias), _ptr(y)
         a.T, a.d_in, a.d_out, a.r_live = x2.shape[0], x2.shape[1], B.shape[1], B.shape[0]
-        a.acc_kind = _lib.ACC_NONE if acc_down is None else _lib.ACC_DENSE
+        a.acc_up, a.acc_kind = _ptr(exps), kind
         a.scale = float(layer[5])
         a.workspace, a.workspace_bytes = base + off, nws
     rc = _launch_rc(x0.device, lib.sow_forward_skinny, arr, n, dt)

@@ -145,6 +145,9 @@ def accumulate(model):
     Q[:, :rank], for all its layers in one normal_() per (device, dtype), where the per-layer path (and the reference,
     sow.py:163-165) draws [in, out] per layer -- so a seeded run is reproducible within a path, not across the two."""
     mods = [m for _, m in model.named_modules() if isinstance(m, SoWLinear)]
+    if any(m.acc_quantized() for m in mods):      # before any layer is touched
+        raise RuntimeError("sow_amd.accumulate: the model holds quantised (E4M3) accumulators, which are frozen; call "
+                           "sow_amd.dequantize_accumulators(model) first")
     # layers attached to a FactorBucket (sow_amd/dp.py): pending partial sums belong to the OLD factors -- reduce them
     # first; afterwards the rebound .data tensors are copied back into the flat buffer so the fused optimizer and the
     # all-reduce keep seeing them
