@@ -142,6 +142,20 @@ extern "C" {
  * SOW_ERR_UNSUPPORTED for this kind before anything is launched or dereferenced (the caller runs it on the image that
  * sow_acc_dequantize writes, with SOW_ACC_DENSE). */
 #define SOW_ACC_DENSE_FP8 3
+/* A frozen dense accumulator stored as MXFP4: E2M1 codes with one power-of-two scale per block of 32 consecutive rows k of one
+ * column n (the MX block along the reduction dimension).  d_in a multiple of 32, d_out of 8.
+ *   acc_up   = the block scales [d_in / 32, d_out], row-major, one E8M0 byte  e + 127  each:  e[kb, n] is the smallest integer
+ *              with  max_{k in block} |W[k,n]| <= 6 * 2^e,  clamped to [-125, 125] (bf16) or [-13, 13] (f16), 0 for an all-zero
+ *              block; the byte lies in [2, 252] (255, the E8M0 NaN, never occurs) and  byte << 23  is the fp32 scale;
+ *   acc_down = the codes [d_in / 2, d_out], row-major:  byte[k / 2, n] = code(k, n) | code(k + 1, n) << 4  for even k, with
+ *              code(k, n) = e2m1_rne(clamp(W[k,n] * 2^-e, -6, 6)),  values +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}, ties to the even
+ *              code, the sign kept (-0 codes occur).
+ * The layer computes what SOW_ACC_DENSE computes on  W^[k,n] = code(k, n) * 2^e[k / 32, n],  which inside those clamps is
+ * exactly a (normal or zero) number of the compute dtype: no rounding is added anywhere.  (0.5 + 1/32) * d_in * d_out bytes.
+ * sow_forward_skinny streams the codes as they are; every other layer entry point returns SOW_ERR_UNSUPPORTED for this kind
+ * before anything is launched or dereferenced, and its workspace queries return 0 (the caller runs it on the image that
+ * sow_acc_dequantize_fp4 writes, with SOW_ACC_DENSE). */
+#define SOW_ACC_DENSE_FP4 4
 
 #define SOW_H_COLS 64 /* column count of the saved h / dh buffers when r_live <= 64 */
 
@@ -350,8 +364,8 @@ int sow_backward_shared(const sow_layer_args* layers, int n, int dtype, int phas
  * computes alone.  Rows are independent: a non-finite x[t, k] makes row t of y non-finite and no other.
  * Fields used: x, A, B, acc_down, bias, y, T, d_in, d_out, r_live, acc_kind, scale, workspace, workspace_bytes (h_save and
  * the backward fields are ignored).  Layers may share x or not.
- * Admitted: SOW_DTYPE_BF16 / SOW_DTYPE_F16, T <= 32, SOW_ACC_DENSE, SOW_ACC_DENSE_FP8 or SOW_ACC_NONE, r_live <= 64, d_in and
- * d_out multiples of 8, 16-byte-aligned x, y, acc_down, A, B and bias, n <= 16.  Anything else -- SOW_ACC_LOWRANK, SOW_PARAM_F32,
+ * Admitted: SOW_DTYPE_BF16 / SOW_DTYPE_F16, T <= 32, SOW_ACC_DENSE, SOW_ACC_DENSE_FP8, SOW_ACC_DENSE_FP4 or SOW_ACC_NONE, r_live <= 64,
+ * d_in and d_out multiples of 8 (d_in of 32 with SOW_ACC_DENSE_FP4), 16-byte-aligned x, y, acc_down, A, B and bias, n <= 16.  Anything else -- SOW_ACC_LOWRANK, SOW_PARAM_F32,
  * and everything while the NO_SKINNY switch is on -- returns SOW_ERR_UNSUPPORTED; SOW_DTYPE_F32 returns SOW_ERR_DTYPE and a
  * workspace below the query SOW_ERR_WORKSPACE.  All of it is decided on the host for every layer before anything is launched
  * or dereferenced (the caller then takes sow_forward / sow_forward_group).  Layers with T = 0 are skipped (SOW_OK).
@@ -362,12 +376,20 @@ int sow_backward_shared(const sow_layer_args* layers, int n, int dtype, int phas
  * multiplies their slab-order sum by 2^e_n in fp32 (exact) before h . B and the bias: y = rn(x W^ + h B + bias), one
  * rounding, the contract above with acc_down := W^.  Its column ranges are 128 wide, so its slab plan and workspace differ
  * from SOW_ACC_DENSE's: size the workspace of such a layer with sow_forward_skinny_fp8_workspace_bytes (below).  The dense layers of one call must all be of one kind (SOW_ERR_UNSUPPORTED otherwise; layers without
- * an accumulator mix with either). */
+ * an accumulator mix with either).
+ * SOW_ACC_DENSE_FP4 (acc_down = packed codes, acc_up = E8M0 block scales, both 8-byte aligned): the first launch reads a
+ * quarter of the stream -- 8-byte pieces of 8 columns x 2 rows, and the block's 8 scale bytes once per 32 rows -- and converts a
+ * byte and its scale straight into an MFMA operand register (v_cvt_scalef32_pk_{bf16,f16}_fp4: exact); the slab partials
+ * hold sum_k x[t,k] W^[k,n] and the second launch is the one of SOW_ACC_DENSE.  128-column ranges as for SOW_ACC_DENSE_FP8;
+ * size the workspace with sow_forward_skinny_fp4_workspace_bytes.  Kinds 2, 3 and 4 do not mix in one call. */
 size_t sow_forward_skinny_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype);
 /* The same query for a layer with SOW_ACC_DENSE_FP8, under the conditions of SOW_ACC_DENSE (0 outside them).  A query of
  * its own: sow_forward_skinny_workspace_bytes answers 0 for acc_kind = 3, as it did while 3 was no kind, so that a caller
  * written against it keeps reading 3 as "not admitted" there. */
 size_t sow_forward_skinny_fp8_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int dtype);
+/* The same for SOW_ACC_DENSE_FP4 (0 outside SOW_ACC_DENSE's conditions or when d_in is no multiple of 32); the query above
+ * answers 0 for acc_kind = 4 for the same reason. */
+size_t sow_forward_skinny_fp4_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int dtype);
 int sow_forward_skinny(const sow_layer_args* layers, int n, int dtype, void* stream);
 
 /* General row-major GEMM  C[M,N] = alpha * op(A) op(B) + beta * C + bias[N]  (bias may be NULL).
@@ -566,6 +588,14 @@ int sow_cast_copy(const void* src, int64_t lds, int src_dtype, void* dst, int64_
  * (SOW_ERR_UNSUPPORTED), q and exps 8-byte and dst 16-byte aligned (SOW_ERR_ALIGN), |exps[n]| <= 119. */
 int sow_acc_dequantize(const void* q, const void* exps, int d_in, int d_out, void* dst, int64_t ldd, int dst_dtype,
                        void* stream);
+
+/* The image of a SOW_ACC_DENSE_FP4 accumulator:  dst[k, n] = e2m1(code(k, n)) * 2^(scales[k / 32, n] - 127)  in SOW_DTYPE_BF16 or
+ * SOW_DTYPE_F16, exact, -0 kept.  codes [d_in / 2, d_out], scales [d_in / 32, d_out] (SOW_ACC_DENSE_FP4 above), dst [d_in,
+ * ldd >= d_out]; columns past d_out of a dst row are not written.  One streaming pass: every code read once, 16-byte stores.
+ * d_in a multiple of 32, d_out and ldd multiples of 8 (SOW_ERR_UNSUPPORTED), codes and scales 8-byte and dst 16-byte aligned
+ * (SOW_ERR_ALIGN).  Error codes as sow_acc_dequantize. */
+int sow_acc_dequantize_fp4(const void* codes, const void* scales, int d_in, int d_out, void* dst, int64_t ldd, int dst_dtype,
+                           void* stream);
 
 #ifdef __cplusplus
 }

@@ -20,6 +20,7 @@ FUSE_ACC = 0x200         # OR-ed into BF16 / F16: permission to run a low-rank a
 FUSE_ACC_DEEP = 0x400    # the same permission for 256 < r_acc + r <= 960 (chain_deep_acc.hip); a call carries one of the two
 ACC_NONE, ACC_LOWRANK, ACC_DENSE = 0, 1, 2
 ACC_DENSE_FP8 = 3        # a dense accumulator as E4M3 codes (acc_down) with int8 column exponents (acc_up)
+ACC_DENSE_FP4 = 4        # a dense accumulator as packed E2M1 codes (acc_down) with E8M0 block scales (acc_up): MXFP4
 H_COLS = 64
 BWD_DATA, BWD_WEIGHTS, BWD_WEIGHTS_PARTIAL, BWD_WEIGHTS_REDUCE = 1, 2, 4, 8
 BWD_GROUP_SLABS = 16     # sow_backward_group: slab counts planned over the group (deferred reduction from group descriptors)
@@ -100,6 +101,7 @@ SIGNATURES = {
     "sow_backward_shared": (c_int, [POINTER(LayerArgs), c_int, c_int, c_int, c_void_p]),
     "sow_forward_skinny_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int, c_int, c_int]),
     "sow_forward_skinny_fp8_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int, c_int]),
+    "sow_forward_skinny_fp4_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int, c_int]),
     "sow_forward_skinny": (c_int, [POINTER(LayerArgs), c_int, c_int, c_void_p]),
     "sow_backward_group_reduce_desc": (c_int, [POINTER(LayerArgs), c_int, c_int, c_int, c_void_p, POINTER(c_int)]),
     "sow_backward_group_plan": (c_int, [POINTER(LayerArgs), c_int, c_int, c_int, POINTER(c_int)]),
@@ -140,6 +142,7 @@ SIGNATURES = {
     "sow_axpby": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_float, c_int, c_void_p]),
     "sow_cast_copy": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_int64, c_int, c_void_p]),
     "sow_acc_dequantize": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_void_p]),
+    "sow_acc_dequantize_fp4": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_void_p]),
 }
 
 _lib = None

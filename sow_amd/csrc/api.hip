@@ -398,12 +398,12 @@ static void normalise_acc(sow_layer_args& L) {
   if (L.acc_kind != SOW_ACC_LOWRANK) L.r_acc = 0, L.acc_up = nullptr;
   if (L.acc_kind == SOW_ACC_NONE) L.acc_down = nullptr;
 }
-// An E4M3 accumulator (SOW_ACC_DENSE_FP8) is read by sow_forward_skinny only: every other layer entry point asks here first,
+// A quantised accumulator (SOW_ACC_DENSE_FP8, SOW_ACC_DENSE_FP4) is read by sow_forward_skinny only: every other layer entry point asks here first,
 // before any other check, launch or dereference
 static inline bool any_fp8_acc(const sow_layer_args* layers, int n) {
   if (layers)
     for (int i = 0; i < n; ++i)
-      if (layers[i].acc_kind == SOW_ACC_DENSE_FP8) return true;
+      if (layers[i].acc_kind == SOW_ACC_DENSE_FP8 || layers[i].acc_kind == SOW_ACC_DENSE_FP4) return true;
   return false;
 }
 static inline WsPlan plan_of(const sow_layer_args& L, int cd, int perm = 0) {
@@ -756,7 +756,7 @@ size_t sow_reduce_desc_bytes(void) { return sizeof(ReduceParams); }
 int sow_backward_reduce_desc(void* dA, void* dB, void* dbias, int64_t T, int d_in, int d_out, int r_live, int r_acc,
                              int acc_kind, float grad_beta, int dtype, void* workspace, size_t workspace_bytes, void* desc_out,
                              int* blocks_out) {
-  if (acc_kind == SOW_ACC_DENSE_FP8) return SOW_ERR_UNSUPPORTED;
+  if (acc_kind == SOW_ACC_DENSE_FP8 || acc_kind == SOW_ACC_DENSE_FP4) return SOW_ERR_UNSUPPORTED;
   const Dtype f = decode_dtype(dtype);   // the descriptor is the same with fp32 gradients: sow_reduce_batch picks the output type
   if (!f.layer_ok()) return SOW_ERR_DTYPE;
   if (T <= 0 || d_in <= 0 || d_out <= 0 || r_live <= 0) return SOW_ERR_SHAPE;
@@ -791,7 +791,7 @@ int sow_reduce_batch(const void* descs, const int* starts, int n, int total_bloc
 
 size_t sow_forward_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, int dtype) {
   const Dtype f = decode_dtype(dtype);
-  if (acc_kind == SOW_ACC_DENSE_FP8) return 0;
+  if (acc_kind == SOW_ACC_DENSE_FP8 || acc_kind == SOW_ACC_DENSE_FP4) return 0;
   if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0 || !f.layer_ok()) return 0;
   if (f.param_f32) {   // the forward's own scratch (if any) followed by the packed parameters (pack_layer)
     const size_t own = sow_forward_workspace_bytes(T, d_in, d_out, r_live, r_acc, acc_kind, f.cd);
@@ -807,7 +807,7 @@ size_t sow_forward_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, i
 
 size_t sow_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, int dtype) {
   const Dtype f = decode_dtype(dtype);
-  if (acc_kind == SOW_ACC_DENSE_FP8) return 0;
+  if (acc_kind == SOW_ACC_DENSE_FP8 || acc_kind == SOW_ACC_DENSE_FP4) return 0;
   if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0 || !f.layer_ok()) return 0;
   const size_t pack = f.param_f32 ? pack_bytes(d_in, d_out, r_live, acc_kind == SOW_ACC_LOWRANK ? r_acc : 0, acc_kind) : 0;
   return plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, f.cd, f.perm()).total + pack + 256;
@@ -862,7 +862,7 @@ static int forward_impl(const sow_layer_args& L, int dtype, int perm, hipStream_
 int sow_forward(const void* x, const void* A, const void* B, const void* acc_down, const void* acc_up, const void* bias,
                 void* y, void* h_save, int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, float scale,
                 int dtype, void* workspace, size_t workspace_bytes, void* stream) {
-  if (acc_kind == SOW_ACC_DENSE_FP8) return SOW_ERR_UNSUPPORTED;
+  if (acc_kind == SOW_ACC_DENSE_FP8 || acc_kind == SOW_ACC_DENSE_FP4) return SOW_ERR_UNSUPPORTED;
   const Dtype f = decode_dtype(dtype);
   if (!f.layer_ok()) return SOW_ERR_DTYPE;
   sow_layer_args L = single_layer(x, A, B, acc_down, acc_up, bias, y, h_save, nullptr, nullptr, nullptr, nullptr, nullptr, T, d_in,
@@ -987,7 +987,7 @@ int sow_backward_ex(const void* dy, const void* x, const void* h_save, const voi
                     const void* acc_up, void* dx, void* dA, void* dB, void* dbias, int64_t T, int d_in, int d_out,
                     int r_live, int r_acc, int acc_kind, float scale, float grad_beta, int dtype, void* workspace,
                     size_t workspace_bytes, int phases, void* stream) {
-  if (acc_kind == SOW_ACC_DENSE_FP8) return SOW_ERR_UNSUPPORTED;
+  if (acc_kind == SOW_ACC_DENSE_FP8 || acc_kind == SOW_ACC_DENSE_FP4) return SOW_ERR_UNSUPPORTED;
   const Dtype f = decode_dtype(dtype);
   sow_layer_args L = single_layer(x, A, B, acc_down, acc_up, nullptr, nullptr, const_cast<void*>(h_save), dy, dx, dA, dB, dbias, T,
                                   d_in, d_out, r_live, r_acc, acc_kind, scale, grad_beta, workspace, workspace_bytes);
@@ -1126,10 +1126,11 @@ int sow_forward_group(const sow_layer_args* layers, int n, int dtype, void* stre
 
 // ---- generation-sized forwards (skinny_fwd.hip) --------------------------------------------------------------
 // The admitted set, decided from the shape alone: 1 <= T <= 32, bf16 / f16 without SOW_PARAM_F32, a dense accumulator (in the
-// compute dtype or as E4M3 codes) or none, r_live <= 64, widths multiples of 8.
+// compute dtype, as E4M3 codes or as MXFP4 codes) or none, r_live <= 64, widths multiples of 8 (d_in of 32 for MXFP4: whole blocks).
 static bool skinny_shape_ok(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype) {
   return (dtype == SOW_BF16 || dtype == SOW_F16) && T >= 1 && T <= 32 && d_in > 0 && d_out > 0 && r_live >= 1 && r_live <= 64 &&
-         (acc_kind == SOW_ACC_DENSE || acc_kind == SOW_ACC_DENSE_FP8 || acc_kind == SOW_ACC_NONE) && d_in % 8 == 0 && d_out % 8 == 0;
+         (acc_kind == SOW_ACC_DENSE || acc_kind == SOW_ACC_DENSE_FP8 || acc_kind == SOW_ACC_DENSE_FP4 || acc_kind == SOW_ACC_NONE) &&
+         d_in % 8 == 0 && d_out % 8 == 0 && (acc_kind != SOW_ACC_DENSE_FP4 || d_in % 32 == 0);
 }
 struct SkWs {
   size_t off_py, off_ph, total;
@@ -1144,10 +1145,10 @@ static SkWs skinny_ws(int64_t T, int d_in, int d_out, int acc_kind) {
   return w;
 }
 
-// (an E4M3 accumulator has a query of its own: this one keeps answering 0 for every kind value it answered 0 for before)
+// (an E4M3 and an MXFP4 accumulator have queries of their own: this one keeps answering 0 for every kind value it answered 0 for before)
 size_t sow_forward_skinny_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype) {
   const Dtype f = decode_dtype(dtype);
-  if (f.param_f32 || acc_kind == SOW_ACC_DENSE_FP8 || !skinny_shape_ok(T, d_in, d_out, r_live, acc_kind, f.cd)) return 0;
+  if (f.param_f32 || acc_kind == SOW_ACC_DENSE_FP8 || acc_kind == SOW_ACC_DENSE_FP4 || !skinny_shape_ok(T, d_in, d_out, r_live, acc_kind, f.cd)) return 0;
   return skinny_ws(T, d_in, d_out, acc_kind).total;
 }
 
@@ -1155,6 +1156,12 @@ size_t sow_forward_skinny_fp8_workspace_bytes(int64_t T, int d_in, int d_out, in
   const Dtype f = decode_dtype(dtype);
   if (f.param_f32 || !skinny_shape_ok(T, d_in, d_out, r_live, SOW_ACC_DENSE_FP8, f.cd)) return 0;
   return skinny_ws(T, d_in, d_out, SOW_ACC_DENSE_FP8).total;
+}
+
+size_t sow_forward_skinny_fp4_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int dtype) {
+  const Dtype f = decode_dtype(dtype);
+  if (f.param_f32 || !skinny_shape_ok(T, d_in, d_out, r_live, SOW_ACC_DENSE_FP4, f.cd)) return 0;
+  return skinny_ws(T, d_in, d_out, SOW_ACC_DENSE_FP4).total;
 }
 
 // The checks of this entry point are its own (not check_layer): stricter, and every layer is checked before the first
@@ -1169,22 +1176,25 @@ int sow_forward_skinny(const sow_layer_args* layers, int n, int dtype, void* str
   if (!layers) return SOW_ERR_NULL;
   if (n > SK_MAXL) return SOW_ERR_UNSUPPORTED;
   SkLayer sk[SK_MAXL];
-  int m = 0, n_fp8 = 0, n_plain = 0;
+  int m = 0, n_fp8 = 0, n_fp4 = 0, n_plain = 0;
   for (int i = 0; i < n; ++i) {
     const sow_layer_args& L = layers[i];
     if (L.T < 0 || L.d_in <= 0 || L.d_out <= 0 || L.r_live <= 0) return SOW_ERR_SHAPE;
-    if (L.acc_kind != SOW_ACC_NONE && L.acc_kind != SOW_ACC_LOWRANK && L.acc_kind != SOW_ACC_DENSE && L.acc_kind != SOW_ACC_DENSE_FP8)
+    if (L.acc_kind != SOW_ACC_NONE && L.acc_kind != SOW_ACC_LOWRANK && L.acc_kind != SOW_ACC_DENSE && L.acc_kind != SOW_ACC_DENSE_FP8 &&
+        L.acc_kind != SOW_ACC_DENSE_FP4)
       return SOW_ERR_SHAPE;
     if (L.T == 0) continue;
     if (!skinny_shape_ok(L.T, L.d_in, L.d_out, L.r_live, L.acc_kind, cd)) return SOW_ERR_UNSUPPORTED;
-    const bool fp8 = L.acc_kind == SOW_ACC_DENSE_FP8;
-    const bool dense = L.acc_kind == SOW_ACC_DENSE || fp8;
-    if (!L.x || !L.A || !L.B || !L.y || (dense && !L.acc_down) || (fp8 && !L.acc_up)) return SOW_ERR_NULL;
-    if (!al16p(L.x) || !al16p(L.y) || !al16p(L.A) || !al16p(L.B) || !al16p(L.bias) || (dense && !al16p(L.acc_down)))
+    const bool fp8 = L.acc_kind == SOW_ACC_DENSE_FP8, fp4 = L.acc_kind == SOW_ACC_DENSE_FP4;
+    const bool dense = L.acc_kind == SOW_ACC_DENSE || fp8 || fp4;
+    if (!L.x || !L.A || !L.B || !L.y || (dense && !L.acc_down) || ((fp8 || fp4) && !L.acc_up)) return SOW_ERR_NULL;
+    if (!al16p(L.x) || !al16p(L.y) || !al16p(L.A) || !al16p(L.B) || !al16p(L.bias) || (dense && !fp4 && !al16p(L.acc_down)))
       return SOW_ERR_UNSUPPORTED;
+    // MXFP4: codes and block scales are read in 8-byte pieces
+    if (fp4 && ((reinterpret_cast<uintptr_t>(L.acc_down) | reinterpret_cast<uintptr_t>(L.acc_up)) & 7)) return SOW_ERR_UNSUPPORTED;
     // one kind of dense accumulator per call (the kernels are instantiated per kind)
-    n_fp8 += fp8, n_plain += dense && !fp8;
-    if (n_fp8 && n_plain) return SOW_ERR_UNSUPPORTED;
+    n_fp8 += fp8, n_fp4 += fp4, n_plain += dense && !fp8 && !fp4;
+    if ((n_fp8 != 0) + (n_fp4 != 0) + (n_plain != 0) > 1) return SOW_ERR_UNSUPPORTED;
     const SkWs w = skinny_ws(L.T, L.d_in, L.d_out, L.acc_kind);
     if (!L.workspace || L.workspace_bytes < w.total) return SOW_ERR_WORKSPACE;
     char* ws = ws_base(L.workspace);
@@ -1193,9 +1203,9 @@ int sow_forward_skinny(const sow_layer_args* layers, int n, int dtype, void* str
     K.x = L.x, K.W = dense ? L.acc_down : nullptr, K.A = L.A, K.B = L.B, K.bias = L.bias, K.y = L.y;
     K.Py = dense ? (float*)(ws + w.off_py) : nullptr, K.Ph = (float*)(ws + w.off_ph);
     K.T = (int)L.T, K.d_in = L.d_in, K.d_out = L.d_out, K.r = L.r_live, K.scale = L.scale;
-    K.wexp = fp8 ? (const int8_t*)L.acc_up : nullptr;
+    K.wexp = fp8 || fp4 ? (const int8_t*)L.acc_up : nullptr;
   }
-  return launch_skinny_fwd(sk, m, cd, (hipStream_t)stream);
+  return launch_skinny_fwd(sk, m, cd, n_fp4 ? SOW_ACC_DENSE_FP4 : n_fp8 ? SOW_ACC_DENSE_FP8 : SOW_ACC_DENSE, (hipStream_t)stream);
 }
 
 static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, int gdt, int phases, int perm, hipStream_t stream) {
@@ -1677,6 +1687,17 @@ int sow_acc_dequantize(const void* q, const void* exps, int d_in, int d_out, voi
   if (d_out % 8 || ldd % 8) return SOW_ERR_UNSUPPORTED;
   if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(exps)) & 7 || !al16p(dst)) return SOW_ERR_ALIGN;
   return launch_acc_dequantize(q, exps, d_in, d_out, dst, ldd, dst_dtype, (hipStream_t)stream);
+}
+
+int sow_acc_dequantize_fp4(const void* codes, const void* scales, int d_in, int d_out, void* dst, int64_t ldd, int dst_dtype,
+                           void* stream) {
+  if (d_in < 0 || d_out < 0 || ldd < d_out) return SOW_ERR_SHAPE;
+  if (dst_dtype != SOW_BF16 && dst_dtype != SOW_F16) return SOW_ERR_DTYPE;
+  if (d_in == 0 || d_out == 0) return SOW_OK;
+  if (!codes || !scales || !dst) return SOW_ERR_NULL;
+  if (d_in % 32 || d_out % 8 || ldd % 8) return SOW_ERR_UNSUPPORTED;
+  if ((reinterpret_cast<uintptr_t>(codes) | reinterpret_cast<uintptr_t>(scales)) & 7 || !al16p(dst)) return SOW_ERR_ALIGN;
+  return launch_acc_dequantize_fp4(codes, scales, d_in, d_out, dst, ldd, dst_dtype, (hipStream_t)stream);
 }
 
 int sow_cast_copy(const void* src, int64_t lds, int src_dtype, void* dst, int64_t ldd, int dst_dtype, int64_t rows,

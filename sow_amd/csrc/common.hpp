@@ -65,6 +65,25 @@ template <> __device__ __forceinline__ bf16_t from_f32<bf16_t>(float v) { return
 // RNE (v_cvt_f16_f32): |v| past 65504 + half an ulp becomes +-inf, subnormals are kept.  Never the pkrtz forms: they truncate.
 template <> __device__ __forceinline__ f16_t from_f32<f16_t>(float v) { return (f16_t)v; }
 
+// Byte `sel` of `dw` = two E2M1 codes, rows k (low nibble) and k + 1 of one column: both times the power of two in the
+// exponent field of `sc`, as a pair of T -- one MFMA B-fragment register, in one instruction (v_cvt_scalef32_pk_*_fp4).  Every
+// such product is a number of T inside the format's exponent clamps: nothing is rounded, -0 stays -0.
+template <typename T> __device__ __forceinline__ uint32_t cvt_fp4_pair(uint32_t dw, float sc, int sel);
+#define SOW_CVT_FP4(NAME, R)                                      \
+  R v;                                                            \
+  switch (sel) {                                                  \
+    case 0: v = __builtin_amdgcn_cvt_scalef32_pk_##NAME##_fp4(dw, sc, 0); break; \
+    case 1: v = __builtin_amdgcn_cvt_scalef32_pk_##NAME##_fp4(dw, sc, 1); break; \
+    case 2: v = __builtin_amdgcn_cvt_scalef32_pk_##NAME##_fp4(dw, sc, 2); break; \
+    default: v = __builtin_amdgcn_cvt_scalef32_pk_##NAME##_fp4(dw, sc, 3); break; \
+  }                                                               \
+  uint32_t u;                                                     \
+  __builtin_memcpy(&u, &v, 4);                                    \
+  return u;
+template <> __device__ __forceinline__ uint32_t cvt_fp4_pair<bf16_t>(uint32_t dw, float sc, int sel) { SOW_CVT_FP4(bf16, bf16x2) }
+template <> __device__ __forceinline__ uint32_t cvt_fp4_pair<f16_t>(uint32_t dw, float sc, int sel) { SOW_CVT_FP4(f16, f16x2) }
+#undef SOW_CVT_FP4
+
 __device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }

@@ -243,6 +243,8 @@ int launch_tn_wide(const void* x, const void* dh, const void* dy, const void* h,
 // through the workspace, summed in slab order with h . B and the bias and rounded once.  An E4M3 accumulator (SOW_ACC_DENSE_FP8:
 // W = the codes, 1 byte per element, wexp = the column exponents) is streamed as bytes by instantiations of the same two
 // kernels: 128-column ranges, codes converted unscaled in registers, the column's 2^e applied to the slab-order sum in phase B.
+// An MXFP4 accumulator (SOW_ACC_DENSE_FP4: W = the packed E2M1 codes [d_in / 2][d_out], wexp = the E8M0 block scales
+// [d_in / 32][d_out]) takes the same geometry with the scale applied in the conversion, and the plain second kernel.
 // The dense layers of one call are all of one kind.
 constexpr int SK_MAXL = 16;
 struct SkLayer {
@@ -252,13 +254,14 @@ struct SkLayer {
   int T, d_in, d_out, r;
   int S, KS, ncr, startA, startB;     // filled in by launch_skinny_fwd (skinny_plan)
   float scale;
-  const int8_t* wexp;                 // column exponents [d_out] of an E4M3 accumulator, or nullptr
+  const int8_t* wexp;                 // column exponents [d_out] of an E4M3 accumulator, the E8M0 block scale bytes of an MXFP4 one, or nullptr
 };
 // K-slabs, slab length and phase-A column ranges of a layer: a pure function of the shape
 void skinny_plan(int d_in, int d_out, int acc_kind, int* S, int* KS, int* ncr);
 size_t skinny_py_bytes(int64_t T, int d_out, int S);
 size_t skinny_ph_bytes(int64_t T, int S);
-int launch_skinny_fwd(const SkLayer* layers, int n, int dtype, hipStream_t stream);
+// acc_kind: the kind of the call's dense layers (SOW_ACC_DENSE, SOW_ACC_DENSE_FP8 or SOW_ACC_DENSE_FP4; any of them without one)
+int launch_skinny_fwd(const SkLayer* layers, int n, int dtype, int acc_kind, hipStream_t stream);
 // gemm.hip
 int launch_gemm(const void* A, int64_t lda, bool transA, const void* B, int64_t ldb, bool transB, void* C, int64_t ldc,
                 const void* bias, int64_t M, int N, int K, float alpha, float beta, int dtype, hipStream_t stream);
@@ -347,6 +350,10 @@ int launch_cast_copy(const void* src, int64_t lds, int src_dtype, void* dst, int
 // q 8-byte and dst 16-byte aligned
 int launch_acc_dequantize(const void* q, const void* exps, int d_in, int d_out, void* dst, int64_t ldd, int dst_dtype,
                           hipStream_t stream);
+// dst[k][n] = e2m1(code(k, n)) * 2^(scales[k / 32][n] - 127) in bf16 / f16 (exact): the image of an MXFP4 accumulator; d_in % 32
+// == 0, d_out % 8 == 0, ldd % 8 == 0, q and scales 8-byte and dst 16-byte aligned
+int launch_acc_dequantize_fp4(const void* q, const void* scales, int d_in, int d_out, void* dst, int64_t ldd, int dst_dtype,
+                              hipStream_t stream);
 int launch_qr_panel(const void* W, int64_t ldw, int in_dtype, int m, int kc, int r, float* Pt, float* Qt,
                     hipStream_t stream);
 int launch_qr_copy_out(const float* Qt, const float* Pt, void* Q, int64_t ldq, void* R, int64_t ldr, int out_dtype, int m,

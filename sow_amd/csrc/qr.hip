@@ -131,6 +131,51 @@ int launch_acc_dequantize(const void* q, const void* exps, int d_in, int d_out, 
   return SOW_OK;
 }
 
+// The image of an MXFP4 accumulator: dst[k][n] = e2m1(code(k, n)) * 2^(scales[k / 32][n] - 127), codes [d_in / 2][d_out], one
+// byte = rows k (low nibble) and k + 1 of a column, scales [d_in / 32][d_out] E8M0 bytes.  A thread takes 8 columns of a row
+// pair: an 8-byte load of codes (each read once), an 8-byte load of scale bytes, eight scaled conversions (each a pair of Tout:
+// the two rows of one column, exact, -0 kept), regrouped into the two rows: two 16-byte stores.
+template <typename Tout>
+__global__ __launch_bounds__(256) void cast_copy_kernel(const uint8_t* q, const uint8_t* scales, Tout* dst, int64_t ldd, int d_in, int d_out) {
+  const int nv = d_out / 8;
+  const int64_t n = (int64_t)(d_in / 2) * nv;
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t kp = idx / nv;
+    const int c = (int)(idx - kp * nv) * 8;
+    const u32x2 qv = *(const u32x2*)(q + kp * d_out + c);
+    const u32x2 sv = *(const u32x2*)(scales + (kp >> 4) * d_out + c);
+    uint32_t pr[8];   // column j: row 2 kp in the low half, row 2 kp + 1 in the high half
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float sc = __uint_as_float(((sv[j >> 2] >> (8 * (j & 3))) & 0xffu) << 23);
+      pr[j] = cvt_fp4_pair<Tout>(qv[j >> 2], sc, j & 3);
+    }
+    u32x4 r0, r1;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      r0[j] = __builtin_amdgcn_perm(pr[2 * j + 1], pr[2 * j], 0x05040100u);
+      r1[j] = __builtin_amdgcn_perm(pr[2 * j + 1], pr[2 * j], 0x07060302u);
+    }
+    Tout* d = dst + 2 * kp * ldd + c;
+    *(u32x4*)d = r0;
+    *(u32x4*)(d + ldd) = r1;
+  }
+}
+
+int launch_acc_dequantize_fp4(const void* q, const void* scales, int d_in, int d_out, void* dst, int64_t ldd, int dst_dtype,
+                              hipStream_t stream) {
+  if (dst_dtype != SOW_BF16 && dst_dtype != SOW_F16) return SOW_ERR_DTYPE;
+  const int g = grid_for((int64_t)(d_in / 2) * (d_out / 8));
+  if (dst_dtype == SOW_BF16)
+    hipLaunchKernelGGL((cast_copy_kernel<bf16_t>), dim3(g), dim3(256), 0, stream, (const uint8_t*)q, (const uint8_t*)scales,
+                       (bf16_t*)dst, ldd, d_in, d_out);
+  else
+    hipLaunchKernelGGL((cast_copy_kernel<f16_t>), dim3(g), dim3(256), 0, stream, (const uint8_t*)q, (const uint8_t*)scales,
+                       (f16_t*)dst, ldd, d_in, d_out);
+  SOW_CHECK_LAUNCH();
+  return SOW_OK;
+}
+
 int launch_cast_copy(const void* src, int64_t lds, int src_dtype, void* dst, int64_t ldd, int dst_dtype, int64_t rows,
                      int cols, hipStream_t stream) {
   if (rows <= 0 || cols <= 0) return SOW_OK;

@@ -28,13 +28,20 @@
 // No atomics, fixed summation order: a repeat gives the same bits, and a layer inside a group (grid concatenation, per-layer
 // block offset) computes exactly what it computes alone.
 //
-// E4M3 accumulator (SOW_ACC_DENSE_FP8, the FP8 = true instantiations): W is the codes, one byte per element, and the column
+// E4M3 accumulator (SOW_ACC_DENSE_FP8, the SK_FP8 / FP8 = true instantiations): W is the codes, one byte per element, and the column
 // exponents come with it.  Phase A reads a lane's 8 bytes of a row -- 8 columns, 16 lanes = 128 contiguous bytes, so a column
 // range is 128 wide and a wave holds eight 16-column tiles -- converts the codes UNSCALED to the compute dtype in registers
 // (v_cvt_pk_f32_fp8, then the upper halves / v_cvt_pkrtz: every E4M3 value is a bf16 and an f16 number, no rounding happens)
 // and feeds the same MFMA; Py holds sum x . q.  Phase B multiplies the slab-order sum of column n by 2^e_n (exact in fp32)
 // before h . B and the bias.  Everything else -- x staging, the x . A workgroups, the reduction, the order of every sum -- is
 // the code above.
+//
+// MXFP4 accumulator (SOW_ACC_DENSE_FP4, the SK_FP4 instantiations of phase A): W is packed E2M1 codes, one byte = rows k, k + 1
+// of one column, and one E8M0 scale byte per (32-row block, column) comes with it.  The geometry is the E4M3 one -- 8-byte
+// loads of 8 columns, 128-column ranges -- but a lane's 8 bytes are a row PAIR: four loads per 32-deep step (one MX block)
+// instead of eight, plus one 8-byte load of the block's scale bytes.  v_cvt_scalef32_pk_{bf16,f16}_fp4 turns one byte and the
+// scale into a fragment register (two rows of one column): 32 conversions per step, no packs.  The scale is applied in the
+// conversion, so Py holds sum x . W^ and phase B is the plain one.
 #include "kernels.hpp"
 
 namespace sow {
@@ -54,17 +61,20 @@ constexpr int SK_WANT_WGS = 512;          // two workgroups per CU
 #endif
 constexpr int SK_WANT_WGS8 = SOW_SKINNY_WANT8;   // ... of an E4M3 accumulator (256 and 1024 each win some shapes and lose others: DESIGN 4.5b)
 constexpr int SK_BN = 64;                 // columns per phase-B workgroup
-// what a lane holds of one row of W: NCT columns in NDW dwords
-template <bool FP8> struct SkW {
-  static constexpr int NCT = SK_NCT, NDW = SK_NCT / 2;
-  typedef __attribute__((ext_vector_type(SK_NCT / 2))) uint32_t vec;
-};
-template <> struct SkW<true> {
+// how the dense accumulator of a call is stored: in the compute dtype, as E4M3 codes, or as packed E2M1 codes (MXFP4)
+enum SkFmt : int { SK_PLAIN = 0, SK_FP8 = 1, SK_FP4 = 2 };
+// what a lane holds of one row of W (one row pair of MXFP4 codes): NCT columns in NDW dwords
+template <SkFmt F> struct SkW {
   static constexpr int NCT = SK_NCT8, NDW = 2;
   typedef __attribute__((ext_vector_type(2))) uint32_t vec;
 };
-constexpr int sk_cn(bool fp8) { return 16 * (fp8 ? SK_NCT8 : SK_NCT); }   // columns per phase-A workgroup
-constexpr int sk_rs(bool fp8) { return sk_cn(fp8) + 4; }   // row pitch (floats) of the parked tiles: 4 rows apart = 16 banks apart
+template <> struct SkW<SK_PLAIN> {
+  static constexpr int NCT = SK_NCT, NDW = SK_NCT / 2;
+  typedef __attribute__((ext_vector_type(SK_NCT / 2))) uint32_t vec;
+};
+constexpr int sk_cn(bool codes) { return 16 * (codes ? SK_NCT8 : SK_NCT); }   // columns per phase-A workgroup
+constexpr int sk_rs(bool codes) { return sk_cn(codes) + 4; }   // row pitch (floats) of the parked tiles: 4 rows apart = 16 banks apart
+constexpr bool sk_codes(int acc_kind) { return acc_kind == SOW_ACC_DENSE_FP8 || acc_kind == SOW_ACC_DENSE_FP4; }
 
 struct SkGroup {
   SkLayer L[SK_MAXL];
@@ -73,8 +83,8 @@ struct SkGroup {
 static_assert(sizeof(SkGroup) <= 4096, "by-value kernel arguments must stay under 4 KiB");
 
 void skinny_plan(int d_in, int d_out, int acc_kind, int* S, int* KS, int* ncr) {
-  const int nc = acc_kind == SOW_ACC_DENSE ? ceil_div(d_out, sk_cn(false)) : acc_kind == SOW_ACC_DENSE_FP8 ? ceil_div(d_out, sk_cn(true)) : 0;
-  const int want = nc ? ceil_div(acc_kind == SOW_ACC_DENSE_FP8 ? SK_WANT_WGS8 : SK_WANT_WGS, nc) : 32;
+  const int nc = acc_kind == SOW_ACC_DENSE ? ceil_div(d_out, sk_cn(false)) : sk_codes(acc_kind) ? ceil_div(d_out, sk_cn(true)) : 0;
+  const int want = nc ? ceil_div(sk_codes(acc_kind) ? SK_WANT_WGS8 : SK_WANT_WGS, nc) : 32;
   int ks = ceil_div(ceil_div(d_in, want), SK_KQ) * SK_KQ;
   if (ks < SK_KQ) ks = SK_KQ;
   if (ks > SK_KS_MAX) ks = SK_KS_MAX;
@@ -111,10 +121,11 @@ template <> __device__ __forceinline__ uint32_t sk_pack_exact<f16_t>(float lo, f
 
 constexpr int SK_PF = 4;   // k-steps a wave keeps in flight: all of them are requested before the x slab is staged
 
-template <typename T, bool FP8 = false> __global__ __launch_bounds__(256) void skinny_a_kernel(const SkGroup g) {
+template <typename T, SkFmt F = SK_PLAIN> __global__ __launch_bounds__(256) void skinny_a_kernel(const SkGroup g) {
   extern __shared__ __align__(16) char sk_smem[];
-  constexpr int SK_NCT = SkW<FP8>::NCT, SK_CN = sk_cn(FP8), SK_RS = sk_rs(FP8);
-  typedef typename SkW<FP8>::vec sk_wvec;
+  constexpr bool FP8 = F == SK_FP8, FP4 = F == SK_FP4;
+  constexpr int SK_NCT = SkW<F>::NCT, SK_CN = sk_cn(F != SK_PLAIN), SK_RS = sk_rs(F != SK_PLAIN);
+  typedef typename SkW<F>::vec sk_wvec;
   int li = 0;
   for (int i = 1; i < g.n; ++i)
     if ((int)blockIdx.x >= g.L[i].startA) li = i;
@@ -137,8 +148,8 @@ template <typename T, bool FP8 = false> __global__ __launch_bounds__(256) void s
   sk_wvec d[SK_PF][8];
   const int col0 = cr * SK_CN + n16 * SK_NCT;
   const bool col_ok = col0 < d_out;   // d_out is a multiple of 8, NCT of 4 (8 for E4M3): a lane's columns are all in or all out
-  const char* Wp = (const char*)L.W + (size_t)col0 * (FP8 ? 1 : sizeof(T));
-  const size_t wpitch = (size_t)d_out * (FP8 ? 1 : sizeof(T));   // bytes per row of W
+  const char* Wp = (const char*)L.W + (size_t)col0 * (F != SK_PLAIN ? 1 : sizeof(T));
+  const size_t wpitch = (size_t)d_out * (F != SK_PLAIN ? 1 : sizeof(T));   // bytes per row of W (per row pair of MXFP4 codes)
   const int r = L.r, ja = cr * 16 + n16;
   const uint16_t* Ap = (const uint16_t*)L.A + ja;
   auto load_step = [&](int kk, sk_wvec(&o)[8]) {
@@ -147,7 +158,17 @@ template <typename T, bool FP8 = false> __global__ __launch_bounds__(256) void s
       const int k = kbeg + kk + kg * 8 + i;
       sk_wvec v = {};
       if (!is_xa) {
-        if (col_ok && kk < klen && k < d_in) v = sk_load_w((const sk_wvec*)(Wp + (size_t)k * wpitch));
+        if constexpr (FP4) {
+          // o[0..3] = row pairs 8 kg + 2 i of the step's block (d_in % 32 == 0 and slabs begin on block boundaries: a block is
+          // whole or absent), o[4] = the block's scale bytes of the same 8 columns
+          const int k2 = kbeg + kk + kg * 8 + 2 * i;
+          if (i < 4) {
+            if (col_ok && kk < klen && k2 < d_in) v = sk_load_w((const sk_wvec*)(Wp + (size_t)(k2 >> 1) * wpitch));
+          } else if (i == 4) {
+            if (col_ok && kk < klen && kbeg + kk < d_in)
+              v = sk_load_w((const sk_wvec*)((const char*)L.wexp + (size_t)((kbeg + kk) >> 5) * d_out + col0));
+          }
+        } else if (col_ok && kk < klen && k < d_in) v = sk_load_w((const sk_wvec*)(Wp + (size_t)k * wpitch));
       } else {
         if (ja < r && kk < klen && k < d_in) v[0] = Ap[(size_t)k * r];
       }
@@ -213,6 +234,18 @@ template <typename T, bool FP8 = false> __global__ __launch_bounds__(256) void s
               acc[c][0] = sk_mfma<T>(a0, f[cc], acc[c][0]);
               if (rows == 32) acc[c][1] = sk_mfma<T>(a1, f[cc], acc[c][1]);
             }
+          }
+        } else if constexpr (FP4) {
+          // byte c of a row pair = column c, rows 2 m and 2 m + 1 of the lane's eight: the scaled conversion IS fragment
+          // register m of tile c
+#pragma unroll
+          for (int c = 0; c < SK_NCT; ++c) {
+            const float sc = __uint_as_float(((d[p][4][c >> 2] >> (8 * (c & 3))) & 0xffu) << 23);   // E8M0 byte -> 2^e
+            u32x4 f;
+#pragma unroll
+            for (int m = 0; m < 4; ++m) f[m] = cvt_fp4_pair<T>(d[p][m][c >> 2], sc, c & 3);
+            acc[c][0] = sk_mfma<T>(a0, f, acc[c][0]);
+            if (rows == 32) acc[c][1] = sk_mfma<T>(a1, f, acc[c][1]);
           }
         } else {
 #pragma unroll
@@ -340,13 +373,15 @@ size_t skinny_ph_bytes(int64_t T, int S) { return (size_t)S * (size_t)T * 64 * s
 
 // layers: x, W (or nullptr), A, B, bias, y, Py (or nullptr), Ph, T in [1, 32], d_in, d_out, r, scale set by the caller (api.hip
 // has checked the admitted set); the plan and the block offsets are filled in here
-int launch_skinny_fwd(const SkLayer* layers, int n, int dtype, hipStream_t stream) {
+int launch_skinny_fwd(const SkLayer* layers, int n, int dtype, int acc_kind, hipStream_t stream) {
   if (n <= 0) return SOW_OK;
   if (n > SK_MAXL || (dtype != SOW_BF16 && dtype != SOW_F16)) return SOW_ERR_UNSUPPORTED;
   // the dense layers of a call are of one kind: the kernels are instantiated per kind
   bool fp8 = false, plain = false;
   for (int i = 0; i < n; ++i) (layers[i].wexp ? fp8 : plain) |= layers[i].W != nullptr;
-  if (fp8 && plain) return SOW_ERR_UNSUPPORTED;
+  if ((fp8 && plain) || (acc_kind != SOW_ACC_DENSE_FP8 && acc_kind != SOW_ACC_DENSE_FP4 && fp8) || (sk_codes(acc_kind) && plain))
+    return SOW_ERR_UNSUPPORTED;
+  const bool fp4 = fp8 && acc_kind == SOW_ACC_DENSE_FP4;   // (fp8 below: the accumulator is codes, of either format)
   const int SK_RS = sk_rs(fp8);
   SkGroup g;
   g.n = n;
@@ -357,7 +392,7 @@ int launch_skinny_fwd(const SkLayer* layers, int n, int dtype, hipStream_t strea
     L = layers[i];
     if (!L.W) L.wexp = nullptr;
     int ncr;
-    skinny_plan(L.d_in, L.d_out, !L.W ? SOW_ACC_NONE : fp8 ? SOW_ACC_DENSE_FP8 : SOW_ACC_DENSE, &L.S, &L.KS, &ncr);
+    skinny_plan(L.d_in, L.d_out, !L.W ? SOW_ACC_NONE : fp8 ? acc_kind : SOW_ACC_DENSE, &L.S, &L.KS, &ncr);
     L.ncr = ncr;
     L.startA = na, L.startB = nb;
     na += L.S * ((L.r + 15) / 16 + ncr);
@@ -370,14 +405,24 @@ int launch_skinny_fwd(const SkLayer* layers, int n, int dtype, hipStream_t strea
   constexpr int LDS_X = 32 * (SK_KS_MAX + SK_XPAD) * 2;
   constexpr int LDS_MAX = 4 * 32 * sk_rs(false) * 4 > LDS_X ? 4 * 32 * sk_rs(false) * 4 : LDS_X;
   constexpr int LDS_MAX8 = 4 * 32 * sk_rs(true) * 4 > LDS_X ? 4 * 32 * sk_rs(true) * 4 : LDS_X;
-  if (fp8 && dtype == SOW_BF16) {
-    SOW_SET_MAX_LDS_ONCE(LDS_MAX8, skinny_a_kernel<bf16_t, true>);
-    hipLaunchKernelGGL((skinny_a_kernel<bf16_t, true>), dim3(na), dim3(256), lds, stream, g);
+  if (fp4 && dtype == SOW_BF16) {   // the scale went into the conversion: Py holds sum x . W^, phase B is the plain one
+    SOW_SET_MAX_LDS_ONCE(LDS_MAX8, skinny_a_kernel<bf16_t, SK_FP4>);
+    hipLaunchKernelGGL((skinny_a_kernel<bf16_t, SK_FP4>), dim3(na), dim3(256), lds, stream, g);
+    SOW_CHECK_LAUNCH();
+    hipLaunchKernelGGL(skinny_b_kernel<bf16_t>, dim3(nb), dim3(256), 0, stream, g);
+  } else if (fp4) {
+    SOW_SET_MAX_LDS_ONCE(LDS_MAX8, skinny_a_kernel<f16_t, SK_FP4>);
+    hipLaunchKernelGGL((skinny_a_kernel<f16_t, SK_FP4>), dim3(na), dim3(256), lds, stream, g);
+    SOW_CHECK_LAUNCH();
+    hipLaunchKernelGGL(skinny_b_kernel<f16_t>, dim3(nb), dim3(256), 0, stream, g);
+  } else if (fp8 && dtype == SOW_BF16) {
+    SOW_SET_MAX_LDS_ONCE(LDS_MAX8, skinny_a_kernel<bf16_t, SK_FP8>);
+    hipLaunchKernelGGL((skinny_a_kernel<bf16_t, SK_FP8>), dim3(na), dim3(256), lds, stream, g);
     SOW_CHECK_LAUNCH();
     hipLaunchKernelGGL((skinny_b_kernel<bf16_t, true>), dim3(nb), dim3(256), 0, stream, g);
   } else if (fp8) {
-    SOW_SET_MAX_LDS_ONCE(LDS_MAX8, skinny_a_kernel<f16_t, true>);
-    hipLaunchKernelGGL((skinny_a_kernel<f16_t, true>), dim3(na), dim3(256), lds, stream, g);
+    SOW_SET_MAX_LDS_ONCE(LDS_MAX8, skinny_a_kernel<f16_t, SK_FP8>);
+    hipLaunchKernelGGL((skinny_a_kernel<f16_t, SK_FP8>), dim3(na), dim3(256), lds, stream, g);
     SOW_CHECK_LAUNCH();
     hipLaunchKernelGGL((skinny_b_kernel<f16_t, true>), dim3(nb), dim3(256), 0, stream, g);
   } else if (dtype == SOW_BF16) {

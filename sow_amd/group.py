@@ -182,6 +182,9 @@ class _SoWGroupFunction(torch.autograd.Function):
         return dx.reshape(ctx.x_shape)
 
 
+_PER_LAYER = object()      # SiblingGroup._forward_skinny: the siblings run as single layers
+
+
 class SiblingGroup:
     """SoWLinear layers of one parent module that the model calls with the same input tensor."""
 
@@ -219,7 +222,8 @@ class SiblingGroup:
     def _forward_skinny(self, x: torch.Tensor):
         """The siblings' outputs of a generation-sized no-grad call (at most 32 flattened tokens) through ONE
         sow_forward_skinny call -- two launches for q / k / v -- or None: a set the skinny forward does not admit (any
-        sibling: low-rank accumulator, wide rank, ragged widths) or that the library refuses runs the grouped path."""
+        sibling: low-rank accumulator, wide rank, ragged widths) or that the library refuses runs the grouped path.  _PER_LAYER:
+        every sibling is admitted, but their dense accumulators are of differing kinds."""
         x2 = x.reshape(-1, x.shape[-1])
         if not 1 <= x2.shape[0] <= ops.SKINNY_MAX_T:
             return None
@@ -230,8 +234,10 @@ class SiblingGroup:
             if not ops.skinny_admits(x2, A, B, acc_down, acc_up, m.bias):
                 return None
             calls.append((x2, A, B, ops.skinny_acc(acc_down, acc_up), m.bias, float(m.scale)))
-        if len({isinstance(c[3], tuple) for c in calls if c[3] is not None}) > 1:
-            return None        # E4M3 and unquantised dense accumulators in one set: the library takes one kind per call
+        if len({c[3][0].dtype if isinstance(c[3], tuple) else None for c in calls if c[3] is not None}) > 1:
+            # E4M3, MXFP4 and unquantised dense accumulators in one set: the library takes one kind per call, and every
+            # sibling is admitted on its own -- each streams its own accumulator in a call of its own
+            return _PER_LAYER
         ys = ops.sow_forward_skinny(calls)
         if ys is None:
             return None
@@ -253,6 +259,8 @@ class SiblingGroup:
             return None
         if cdt is None and not torch.is_grad_enabled():
             ys = self._forward_skinny(x)
+            if ys is _PER_LAYER:
+                return None
             if ys is not None:
                 self._key, self._x = key, x
                 self._parked = {id(m): y for m, y in zip(self.layers, ys) if m is not layer}

@@ -191,7 +191,8 @@ class SoWLinear(nn.Module):
 
     # ------------------------------------------------------------------------------------------
     # A dense accumulator quantised by sow_amd.quantize_accumulators: acc_downweight holds the E4M3 codes (a frozen
-    # float8_e4m3fn parameter) and the persistent buffer acc_exponent the int8 column exponents.  An unquantised layer has no
+    # float8_e4m3fn parameter) and the persistent buffer acc_exponent the int8 column exponents -- or, for fmt="mxfp4", the packed
+    # E2M1 codes (uint8 [d_in / 2, d_out]) and the uint8 E8M0 block scales [d_in / 32, d_out].  An unquantised layer has no
     # such buffer: its state-dict keys are the reference's.
     def acc_quantized(self) -> bool:
         return self._buffers.get("acc_exponent") is not None
@@ -206,21 +207,23 @@ class SoWLinear(nn.Module):
         # in the new dtype.  They stay codes (moved with the module); the layer then computes in the dtype of its factors.
         codes = self.acc_downweight.data if self.acc_quantized() else None     # (the tensor: _apply rebinds the parameter's .data)
         super()._apply(fn, *args, **kwargs)
-        if codes is not None and self.acc_downweight.dtype != ops.FP8:
+        if codes is not None and self.acc_downweight.dtype != codes.dtype:     # (uint8 MXFP4 codes are left alone by casts anyway)
             self.acc_downweight = nn.Parameter(codes.to(self.acc_downweight.device), requires_grad=False)
         return self
 
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
         # a quantised state dict into an unquantised layer (or the other way round): the layer takes the form of what it loads,
         # so that strict loading sees the keys it expects and the codes are copied as codes
+        # (E4M3 codes with int8 exponents, or packed MXFP4 codes with uint8 block scales)
         codes, exps = state_dict.get(prefix + "acc_downweight"), state_dict.get(prefix + "acc_exponent")
-        if exps is not None and codes is not None and codes.dtype == ops.FP8 and not (
-                self.acc_quantized() and self.acc_downweight.dtype == ops.FP8 and self.acc_downweight.shape == codes.shape):
+        if exps is not None and codes is not None and codes.dtype in ops.CODES and not (
+                self.acc_quantized() and self.acc_downweight.dtype == codes.dtype and self.acc_downweight.shape == codes.shape
+                and self.acc_exponent.dtype == exps.dtype and self.acc_exponent.shape == exps.shape):
             dev = self.acc_downweight.device
-            self.acc_downweight = nn.Parameter(torch.empty(codes.shape, dtype=ops.FP8, device=dev), requires_grad=False)
+            self.acc_downweight = nn.Parameter(torch.empty(codes.shape, dtype=codes.dtype, device=dev), requires_grad=False)
             self._buffers.pop("acc_exponent", None)
-            self.register_buffer("acc_exponent", torch.empty(exps.shape, dtype=torch.int8, device=dev))
-        elif exps is None and codes is not None and codes.dtype != ops.FP8 and self.acc_quantized():
+            self.register_buffer("acc_exponent", torch.empty(exps.shape, dtype=exps.dtype, device=dev))
+        elif exps is None and codes is not None and codes.dtype not in ops.CODES and self.acc_quantized():
             del self._buffers["acc_exponent"]
             self.acc_downweight = nn.Parameter(torch.empty(codes.shape, dtype=codes.dtype, device=self.acc_downweight.device),
                                                requires_grad=False)
@@ -243,7 +246,7 @@ class SoWLinear(nn.Module):
             # checkpointing): the projection h = scale * x A is not written to HBM
             x2 = x.reshape(-1, x.shape[-1])
             # generation-sized calls (generate(): batch x beams rows per new token): the fused skinny forward, two launches,
-            # the accumulator (or its E4M3 codes: half the bytes) streamed once on the whole chip.  Autocast with fp32
+            # the accumulator (or its E4M3 / MXFP4 codes: a half / a quarter of the bytes) streamed once on the whole chip.  Autocast with fp32
             # parameters, a low-rank accumulator, a wide rank, ragged widths and a refusal from the library keep the path below.
             if cdt is None and x2.shape[0] <= ops.SKINNY_MAX_T and ops.skinny_admits(x2, A, B, acc_down, acc_up, self.bias):
                 ys = ops.sow_forward_skinny([(x2, A, B, ops.skinny_acc(acc_down, acc_up), self.bias, float(self.scale))])
@@ -264,7 +267,7 @@ class SoWLinear(nn.Module):
         """sow.py:128-178: fold scale * sum_i A_i B_i into the accumulator, optionally re-factor it by
         truncated QR, re-initialise A, zero B."""
         if self.acc_quantized():
-            raise RuntimeError("SoWLinear.accumulate: the accumulator is quantised (E4M3) and frozen; merging into it would "
+            raise RuntimeError("SoWLinear.accumulate: the accumulator is quantised (E4M3 / MXFP4) and frozen; merging into it would "
                                "requantise it.  Call sow_amd.dequantize_accumulators(model) first")
         A = torch.cat([w.data for w in self.downscale_weights], dim=1) if self.n_iter > 1 else self.downscale_weights[0].data
         B = torch.cat([w.data for w in self.upscale_weights], dim=0) if self.n_iter > 1 else self.upscale_weights[0].data

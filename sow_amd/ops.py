@@ -15,6 +15,9 @@ from . import _lib
 
 _DT = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
 FP8 = torch.float8_e4m3fn      # the codes of a quantised dense accumulator (include/sow_amd.h: SOW_ACC_DENSE_FP8)
+FP4 = torch.uint8              # ... of an MXFP4 one (SOW_ACC_DENSE_FP4): two E2M1 codes per byte, rows k and k + 1 of a column
+CODES = (FP8, FP4)
+FP4_BLOCK = 32                 # rows per MXFP4 scale block
 
 
 def _dt(t: torch.Tensor) -> int:
@@ -129,11 +132,14 @@ def _workspace_bytes(lib, T: int, d_in: int, d_out: int, r: int, r_acc: int, kin
 
 def acc_kind(acc_down: Optional[torch.Tensor], acc_up: Optional[torch.Tensor]) -> int:
     """Accumulator kind as SoWLinear.forward decides it (reference sow.py:109-112).  E4M3 codes in acc_down (with their int8
-    column exponents in acc_up) are a quantised dense accumulator."""
+    column exponents in acc_up) are a quantised dense accumulator, and so are packed uint8 MXFP4 codes (with their uint8 E8M0
+    block scales in acc_up)."""
     if acc_down is None or acc_down.numel() == 0:
         return _lib.ACC_NONE
     if acc_down.dtype == FP8:
         return _lib.ACC_DENSE_FP8
+    if acc_down.dtype == FP4:
+        return _lib.ACC_DENSE_FP4
     if acc_up is None or acc_up.numel() == 0:
         return _lib.ACC_DENSE
     return _lib.ACC_LOWRANK
@@ -159,6 +165,20 @@ def check_accumulator(x2: torch.Tensor, d_in: int, d_out: int, acc_down, acc_up,
         if tuple(acc_down.shape) != (d_in, d_out) or tuple(acc_up.shape) != (d_out,) or d_out % 8:
             raise ValueError(f"{who}: an E4M3 accumulator is [in_features, out_features] codes and [out_features] exponents, "
                              "out_features a multiple of 8")
+        for t in (acc_down, acc_up):
+            if not t.is_cuda or t.device != x2.device:
+                raise RuntimeError(f"{who}: the accumulator is on {t.device}, the input on {x2.device}")
+        return kind, 0
+    if kind == _lib.ACC_DENSE_FP4:
+        if param_dtype is not None or x2.dtype not in (torch.bfloat16, torch.float16):
+            raise TypeError(f"{who}: an MXFP4 accumulator runs with bfloat16 or float16 inputs and parameters, got {x2.dtype}"
+                            + ("" if param_dtype is None else f" inputs and {param_dtype} parameters"))
+        if acc_up is None or acc_up.dtype != torch.uint8:
+            raise TypeError(f"{who}: an MXFP4 accumulator comes with uint8 (E8M0) block scales")
+        if (d_in % FP4_BLOCK or d_out % 8 or tuple(acc_down.shape) != (d_in // 2, d_out)
+                or tuple(acc_up.shape) != (d_in // FP4_BLOCK, d_out)):
+            raise ValueError(f"{who}: an MXFP4 accumulator is [in_features / 2, out_features] packed codes and [in_features / 32, "
+                             "out_features] block scales, in_features a multiple of 32, out_features of 8")
         for t in (acc_down, acc_up):
             if not t.is_cuda or t.device != x2.device:
                 raise RuntimeError(f"{who}: the accumulator is on {t.device}, the input on {x2.device}")
@@ -335,23 +355,35 @@ def shared_fused_acc_pays(r_tots: Sequence[int]) -> bool:
     return shared_fused_acc_lds_bytes(r_tots) <= SHARED_FUSED_ACC_PAYS_LDS
 
 
+def acc_logical_shape(codes: torch.Tensor) -> Tuple[int, int]:
+    """(d_in, d_out) of the matrix a codes tensor stands for: MXFP4 packs two rows into one byte."""
+    return (2 * codes.shape[0], codes.shape[1]) if codes.dtype == FP4 else (codes.shape[0], codes.shape[1])
+
+
 def acc_dequantize(codes: torch.Tensor, exps: torch.Tensor, dtype: torch.dtype, out: Optional[torch.Tensor] = None):
-    """The image of an E4M3 accumulator, W^[k, n] = codes[k, n] * 2^exps[n], exactly, in bf16 or f16 (sow_acc_dequantize: one
-    streaming pass).  `out`: a [d_in, d_out] tensor of `dtype` whose rows are contiguous (any row pitch that is a multiple of
+    """The image of an E4M3 accumulator, W^[k, n] = codes[k, n] * 2^exps[n], or of an MXFP4 one (packed uint8 codes, uint8 block
+    scales in `exps`: W^[k, n] = e2m1(code(k, n)) * 2^(exps[k // 32, n] - 127)), exactly, in bf16 or f16 (sow_acc_dequantize /
+    sow_acc_dequantize_fp4: one streaming pass).  `out`: a [d_in, d_out] tensor of `dtype` whose rows are contiguous (any row pitch that is a multiple of
     8), written in place."""
     dev = _need_gpu(codes, exps, out)
-    if codes.dtype != FP8 or exps.dtype != torch.int8 or codes.dim() != 2 or tuple(exps.shape) != (codes.shape[1],):
+    fp4 = codes.dtype == FP4
+    if fp4:
+        if exps.dtype != torch.uint8 or codes.dim() != 2 or (2 * codes.shape[0]) % FP4_BLOCK or tuple(exps.shape) != (
+                2 * codes.shape[0] // FP4_BLOCK, codes.shape[1]):
+            raise TypeError("sow_amd.acc_dequantize: packed uint8 MXFP4 codes [d_in / 2, d_out] and uint8 block scales [d_in / 32, d_out]")
+    elif codes.dtype != FP8 or exps.dtype != torch.int8 or codes.dim() != 2 or tuple(exps.shape) != (codes.shape[1],):
         raise TypeError("sow_amd.acc_dequantize: float8_e4m3fn codes [d_in, d_out] and int8 exponents [d_out]")
     if dtype not in (torch.bfloat16, torch.float16):
         raise TypeError(f"sow_amd.acc_dequantize: the image is bfloat16 or float16, not {dtype}")
-    d_in, d_out = codes.shape
+    d_in, d_out = acc_logical_shape(codes)
     codes, exps = codes.contiguous(), exps.contiguous()
     if out is None:
         out = torch.empty((d_in, d_out), dtype=dtype, device=dev)
     elif out.dtype != dtype or tuple(out.shape) != (d_in, d_out) or (d_out > 1 and out.stride(1) != 1):
         raise ValueError("sow_amd.acc_dequantize: `out` must be a [d_in, d_out] tensor of the image dtype with contiguous rows")
     if d_in and d_out:
-        _launch(dev, "sow_acc_dequantize", _lib.load().sow_acc_dequantize, _ptr(codes), _ptr(exps), d_in, d_out, _ptr(out),
+        name = "sow_acc_dequantize_fp4" if fp4 else "sow_acc_dequantize"
+        _launch(dev, name, getattr(_lib.load(), name), _ptr(codes), _ptr(exps), d_in, d_out, _ptr(out),
                 out.stride(0) if d_in > 1 else d_out, _DT[dtype])
     return out
 
@@ -365,11 +397,12 @@ _ARENAS_RETIRED: list = []       # ... are kept alive when a larger one replaces
 
 
 def acc_images(pairs, dtype: torch.dtype) -> list:
-    """The images of the E4M3 accumulators `pairs` = [(codes, exps), ...] of ONE call, side by side in the scratch arena.
+    """The images of the E4M3 / MXFP4 accumulators `pairs` = [(codes, exps), ...] of ONE call, side by side in the scratch arena.
     The arena grows only outside graph capture: a capture needs one eager call of the same model first."""
     dev = pairs[0][0].device
     es = torch.empty((), dtype=dtype).element_size()
-    sizes = [(c.numel() * es + 255) // 256 * 256 for c, _ in pairs]
+    shapes = [acc_logical_shape(c) for c, _ in pairs]
+    sizes = [(a * b * es + 255) // 256 * 256 for a, b in shapes]
     need, key = sum(sizes), (dev, dtype)
     buf = _ARENAS.get(key)
     capturing = torch.cuda.is_current_stream_capturing()
@@ -385,17 +418,17 @@ def acc_images(pairs, dtype: torch.dtype) -> list:
     if capturing:
         _ARENAS_CAPTURED.add(key)
     out, off = [], 0
-    for (codes, exps), n in zip(pairs, sizes):
-        img = buf[off:off + codes.numel() * es].view(dtype).view(codes.shape)
+    for (codes, exps), n, shape in zip(pairs, sizes, shapes):
+        img = buf[off:off + shape[0] * shape[1] * es].view(dtype).view(shape)
         out.append(acc_dequantize(codes, exps, dtype, out=img))
         off += n
     return out
 
 
 def acc_operands(accs, dtype: torch.dtype) -> list:
-    """(acc_down, acc_up) of every layer of ONE call as the dense kernels read them: an E4M3 accumulator (codes, exponents)
+    """(acc_down, acc_up) of every layer of ONE call as the dense kernels read them: an E4M3 or MXFP4 accumulator (codes, exponents)
     is replaced by (its image in the scratch arena, None), everything else passes through."""
-    fp8 = [i for i, (d, _) in enumerate(accs) if d is not None and d.numel() and d.dtype == FP8]
+    fp8 = [i for i, (d, _) in enumerate(accs) if d is not None and d.numel() and d.dtype in CODES]
     if not fp8:
         return list(accs)
     out = list(accs)
@@ -453,13 +486,15 @@ _SKINNY_WS_BYTES: dict = {}
 
 
 def skinny_workspace_bytes(T: int, d_in: int, d_out: int, r: int, kind: int, dt: int) -> int:
-    """sow_forward_skinny_workspace_bytes (sow_forward_skinny_fp8_workspace_bytes for an E4M3 accumulator), memoised per shape: 0 = the shape is outside the admitted set.  A pure function
+    """sow_forward_skinny_workspace_bytes (sow_forward_skinny_fp8_workspace_bytes for an E4M3 accumulator,
+    sow_forward_skinny_fp4_workspace_bytes for an MXFP4 one), memoised per shape: 0 = the shape is outside the admitted set.  A pure function
     of the shape (no switch enters), so the memo is never dropped."""
     key = (T, d_in, d_out, r, kind, dt)
     n = _SKINNY_WS_BYTES.get(key)
     if n is None:
         lib = _lib.load()
         n = _SKINNY_WS_BYTES[key] = int(lib.sow_forward_skinny_fp8_workspace_bytes(T, d_in, d_out, r, dt) if kind == _lib.ACC_DENSE_FP8
+                                        else lib.sow_forward_skinny_fp4_workspace_bytes(T, d_in, d_out, r, dt) if kind == _lib.ACC_DENSE_FP4
                                         else lib.sow_forward_skinny_workspace_bytes(T, d_in, d_out, r, kind, dt))
     return n
 
@@ -480,12 +515,26 @@ def skinny_fp8_pays(T: int, d_in: int, d_out: int) -> bool:
     return 1 <= T <= SKINNY_MAX_T
 
 
+def skinny_fp4_pays(T: int, d_in: int, d_out: int) -> bool:
+    """The measured dispatch rule for an MXFP4 accumulator (profiles/fp4_acc.txt), the one place that
+    encodes it: the calls at which streaming the codes (q4) is faster than the image pass followed by the bf16 skinny forward on
+    the image (d4) by more than the run-to-run spread of the row.  Measured (us, r = 50, T = 4 / 32; +- the larger spread
+    of the two variants): 4096->4096 21.1 / 29.9 against 39.7 / 43.0 (+- 2.5 / 2.6), 4096->11008 24.3 / 38.4 against 62.9 / 90.1
+    (+- 1.8 / 2.8), 11008->4096 26.5 / 37.4 against 62.3 / 81.0 (+- 1.6 / 1.9), 512->512 14.5 / 16.3 against 18.3 / 19.2 (+- 1.5 / 0.3),
+    q + k + v of 4096->4096 33.5 / 52.4 against 70.3 / 84.5 (+- 0.7 / 1.0); q4 / d4 lies between 0.37 and 0.85 in all 48 rows (T = 1,
+    4, 16, 32; r = 8, 50) and the gap exceeds the spread in each: the rule excludes nothing.  q4 is never slower than the E4M3
+    codes (q4 / q8 0.68 ... 1.00); it loses to the bf16 accumulator at 4096->4096, T = 32, r = 8 (29.1 against 25.4) and by up to
+    10 % on 512-wide layers at r = 8, which does not enter the rule: the kind buys memory there.  NOT measured: f16, widths above
+    11008."""
+    return 1 <= T <= SKINNY_MAX_T
+
+
 def skinny_acc(acc_down, acc_up):
     """The accumulator element of a sow_forward_skinny layer tuple: None, the dense tensor, or (codes, exponents)."""
     kind = acc_kind(acc_down, acc_up)
     if kind == _lib.ACC_NONE:
         return None
-    return (acc_down, acc_up) if kind == _lib.ACC_DENSE_FP8 else acc_down
+    return (acc_down, acc_up) if kind in (_lib.ACC_DENSE_FP8, _lib.ACC_DENSE_FP4) else acc_down
 
 
 def skinny_admits(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, acc_up, bias) -> bool:
@@ -501,7 +550,7 @@ def skinny_admits(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, 
         return False
     T, d_in = x2.shape
     r, d_out = B.shape
-    if tuple(A.shape) != (d_in, r) or (kind != _lib.ACC_NONE and tuple(acc_down.shape) != (d_in, d_out)):
+    if tuple(A.shape) != (d_in, r) or (kind != _lib.ACC_NONE and acc_logical_shape(acc_down) != (d_in, d_out)):
         return False
     for t in (A, B, bias, acc_down if kind == _lib.ACC_DENSE else None):
         if t is not None and (t.dtype != x2.dtype or t.device != x2.device):
@@ -509,6 +558,10 @@ def skinny_admits(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, 
     if kind == _lib.ACC_DENSE_FP8:
         if (acc_up is None or acc_up.dtype != torch.int8 or tuple(acc_up.shape) != (d_out,) or acc_down.device != x2.device
                 or acc_up.device != x2.device or not skinny_fp8_pays(T, d_in, d_out)):
+            return False
+    if kind == _lib.ACC_DENSE_FP4:
+        if (acc_up is None or acc_up.dtype != torch.uint8 or d_in % FP4_BLOCK or tuple(acc_up.shape) != (d_in // FP4_BLOCK, d_out)
+                or acc_down.device != x2.device or acc_up.device != x2.device or not skinny_fp4_pays(T, d_in, d_out)):
             return False
     return skinny_pays(T, d_in, d_out) and skinny_workspace_bytes(T, d_in, d_out, r, kind, dt) > 0
 
@@ -531,7 +584,11 @@ def sow_forward_skinny(layers) -> Optional[list]:
         exps = None
         if isinstance(acc_down, tuple):
             acc_down, exps = acc_down
-            if acc_down.dtype != FP8 or exps.dtype != torch.int8 or tuple(exps.shape) != (acc_down.shape[-1],):
+            if acc_down.dtype == FP4:
+                if exps.dtype != torch.uint8 or acc_down.dim() != 2 or tuple(exps.shape) != (acc_down.shape[0] // 16, acc_down.shape[1]):
+                    raise TypeError("sow_amd.sow_forward_skinny: an MXFP4 accumulator is (packed uint8 codes [d_in / 2, d_out], "
+                                    "uint8 block scales [d_in / 32, d_out])")
+            elif acc_down.dtype != FP8 or exps.dtype != torch.int8 or tuple(exps.shape) != (acc_down.shape[-1],):
                 raise TypeError("sow_amd.sow_forward_skinny: an E4M3 accumulator is (float8_e4m3fn codes, int8 exponents)")
         dev = _need_gpu(x2, A, B, acc_down, exps, bias)
         if dev != x0.device or any(t is not None and t.dtype != x0.dtype
@@ -539,10 +596,11 @@ def sow_forward_skinny(layers) -> Optional[list]:
             raise TypeError("sow_amd.sow_forward_skinny: all tensors of a call share one dtype and one device")
         T, d_in = x2.shape
         r, d_out = B.shape
-        if tuple(A.shape) != (d_in, r) or (acc_down is not None and tuple(acc_down.shape) != (d_in, d_out)) or (
+        if tuple(A.shape) != (d_in, r) or (acc_down is not None and acc_logical_shape(acc_down) != (d_in, d_out)) or (
                 bias is not None and tuple(bias.shape) != (d_out,)):
             raise ValueError("sow_amd.sow_forward_skinny: operand shapes do not match")
-        kind = _lib.ACC_NONE if acc_down is None else _lib.ACC_DENSE if exps is None else _lib.ACC_DENSE_FP8
+        kind = (_lib.ACC_NONE if acc_down is None else _lib.ACC_DENSE if exps is None
+                else _lib.ACC_DENSE_FP4 if acc_down.dtype == FP4 else _lib.ACC_DENSE_FP8)
         nws = skinny_workspace_bytes(T, d_in, d_out, r, kind, dt) if T else 0
         if T and not nws:
             return None

@@ -146,7 +146,7 @@ def accumulate(model):
     sow.py:163-165) draws [in, out] per layer -- so a seeded run is reproducible within a path, not across the two."""
     mods = [m for _, m in model.named_modules() if isinstance(m, SoWLinear)]
     if any(m.acc_quantized() for m in mods):      # before any layer is touched
-        raise RuntimeError("sow_amd.accumulate: the model holds quantised (E4M3) accumulators, which are frozen; call "
+        raise RuntimeError("sow_amd.accumulate: the model holds quantised (E4M3 / MXFP4) accumulators, which are frozen; call "
                            "sow_amd.dequantize_accumulators(model) first")
     # layers attached to a FactorBucket (sow_amd/dp.py): pending partial sums belong to the OLD factors -- reduce them
     # first; afterwards the rebound .data tensors are copied back into the flat buffer so the fused optimizer and the
