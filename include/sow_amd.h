@@ -67,7 +67,7 @@ extern "C" {
  * the caller takes the grouped calls); every other entry point, and SOW_DTYPE_F32 | SOW_PARAM_F32 anywhere, returns
  * SOW_ERR_DTYPE (checked on the host before anything is launched or dereferenced).  With the flag:
  *   - the activations are of the compute dtype: x, y, h_save, dy, dx (and the internal dh);
- *   - A, B, bias, acc_down and acc_up are read as fp32, each element rounded once, to nearest even, to the compute dtype
+ *   - A, B, bias, acc_down and acc_up (the accumulator unless SOW_ACC_NATIVE, below, says otherwise) are read as fp32, each element rounded once, to nearest even, to the compute dtype
  *     before use (the cast autocast applies to every F.linear / matmul operand, bias included): one launch packs all of
  *     them (every layer of a group call) into the caller's workspace, and the bf16 / f16 kernels run on the packed copies
  *     -- results equal those of the unflagged call on pre-rounded parameters bit for bit;
@@ -119,6 +119,27 @@ extern "C" {
  * Rounding contract, results (h_save, dh, y, dX) and the weight-gradient phases: those of SOW_FUSE_ACC above -- the bias is
  * added in fp32 before the one rounding of y. */
 #define SOW_FUSE_ACC_DEEP 0x400
+
+/* The accumulator of a SOW_PARAM_F32 call is already of the compute dtype (fp32 master factors over a frozen bf16 / f16 base,
+ * or over the image of a quantised one): OR-ed into the dtype next to SOW_PARAM_F32.  With  cd | SOW_PARAM_F32 | SOW_ACC_NATIVE:
+ *   - A, B and bias are fp32 and are packed exactly as under SOW_PARAM_F32;
+ *   - acc_down / acc_up are tensors OF THE COMPUTE DTYPE, read in place by the kernels that read them in an unflagged call:
+ *     never packed, never copied;
+ *   - the workspace queries return the unflagged plan plus the 256-aligned packs of A, B and bias only (SOW_PARAM_F32's figure
+ *     minus the packs of the accumulator tensors; the same figure for SOW_ACC_NONE);
+ *   - y, h_save, dx and the internal dh are bit-identical to the unflagged call on parameters pre-rounded to the compute dtype,
+ *     and to the SOW_PARAM_F32 call whose fp32 accumulator holds the same values; dA, dB and dbias are fp32 as under
+ *     SOW_PARAM_F32.
+ * Admitted: every entry point that accepts SOW_PARAM_F32 accepts the pair (sow_workspace_bytes, sow_forward_workspace_bytes,
+ * sow_forward, sow_backward, sow_backward_ex, sow_backward_reduce_desc, sow_reduce_batch, sow_forward_group, sow_backward_group,
+ * sow_backward_group_reduce_desc, sow_backward_group_plan), and sow_forward_skinny admits the pair although it refuses
+ * SOW_PARAM_F32 alone (see there).  Without SOW_PARAM_F32 the bit is accepted wherever SOW_PARAM_F32 is accepted and ignored
+ * there: the accumulator is native already.  Wherever SOW_PARAM_F32 is refused or rejected (sow_forward_shared and
+ * sow_backward_shared: SOW_ERR_UNSUPPORTED; the entry points outside the layer surface: SOW_ERR_DTYPE) the bit gets the same
+ * code, with or without SOW_PARAM_F32.  SOW_DTYPE_F32 with either flag stays SOW_ERR_DTYPE; SOW_FUSE_ACC* stay ignored next
+ * to SOW_PARAM_F32.  The weight-gradient phases, plans and reduce descriptors read no accumulator: the bit changes nothing
+ * there. */
+#define SOW_ACC_NATIVE 0x800
 
 #define SOW_OK 0
 #define SOW_ERR_NULL (-1)
@@ -365,8 +386,8 @@ int sow_backward_shared(const sow_layer_args* layers, int n, int dtype, int phas
  * Fields used: x, A, B, acc_down, bias, y, T, d_in, d_out, r_live, acc_kind, scale, workspace, workspace_bytes (h_save and
  * the backward fields are ignored).  Layers may share x or not.
  * Admitted: SOW_DTYPE_BF16 / SOW_DTYPE_F16, T <= 32, SOW_ACC_DENSE, SOW_ACC_DENSE_FP8, SOW_ACC_DENSE_FP4 or SOW_ACC_NONE, r_live <= 64,
- * d_in and d_out multiples of 8 (d_in of 32 with SOW_ACC_DENSE_FP4), 16-byte-aligned x, y, acc_down, A, B and bias, n <= 16.  Anything else -- SOW_ACC_LOWRANK, SOW_PARAM_F32,
- * and everything while the NO_SKINNY switch is on -- returns SOW_ERR_UNSUPPORTED; SOW_DTYPE_F32 returns SOW_ERR_DTYPE and a
+ * d_in and d_out multiples of 8 (d_in of 32 with SOW_ACC_DENSE_FP4), 16-byte-aligned x, y, acc_down, A, B and bias, n <= 16.  Anything else -- SOW_ACC_LOWRANK, SOW_PARAM_F32
+ * without SOW_ACC_NATIVE, and everything while the NO_SKINNY switch is on -- returns SOW_ERR_UNSUPPORTED; SOW_DTYPE_F32 returns SOW_ERR_DTYPE and a
  * workspace below the query SOW_ERR_WORKSPACE.  All of it is decided on the host for every layer before anything is launched
  * or dereferenced (the caller then takes sow_forward / sow_forward_group).  Layers with T = 0 are skipped (SOW_OK).
  * sow_forward_skinny_workspace_bytes: per layer, a pure function of the shape (the switches do not enter); 0 outside the
@@ -381,7 +402,13 @@ int sow_backward_shared(const sow_layer_args* layers, int n, int dtype, int phas
  * quarter of the stream -- 8-byte pieces of 8 columns x 2 rows, and the block's 8 scale bytes once per 32 rows -- and converts a
  * byte and its scale straight into an MFMA operand register (v_cvt_scalef32_pk_{bf16,f16}_fp4: exact); the slab partials
  * hold sum_k x[t,k] W^[k,n] and the second launch is the one of SOW_ACC_DENSE.  128-column ranges as for SOW_ACC_DENSE_FP8;
- * size the workspace with sow_forward_skinny_fp4_workspace_bytes.  Kinds 2, 3 and 4 do not mix in one call. */
+ * size the workspace with sow_forward_skinny_fp4_workspace_bytes.  Kinds 2, 3 and 4 do not mix in one call.
+ * fp32 factors: dtype = cd | SOW_PARAM_F32 | SOW_ACC_NATIVE is admitted for all four kinds, every other condition unchanged (A,
+ * B and bias of every layer are then fp32, 16-byte aligned; the accumulator is of cd, or codes).  No pack launch and no extra
+ * workspace -- the three queries answer for the flagged dtype what they answer for cd (and 0 for SOW_PARAM_F32 alone): the x . A
+ * workgroups of the first launch gather A with 4-byte loads, the second loads its column of B and the bias as fp32, and each
+ * value is rounded once, to nearest even, to cd in registers before use.  y is bit-identical to the unflagged call on factors
+ * pre-rounded to cd.  SOW_ACC_NATIVE alone is ignored (the unflagged call). */
 size_t sow_forward_skinny_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype);
 /* The same query for a layer with SOW_ACC_DENSE_FP8, under the conditions of SOW_ACC_DENSE (0 outside them).  A query of
  * its own: sow_forward_skinny_workspace_bytes answers 0 for acc_kind = 3, as it did while 3 was no kind, so that a caller

@@ -4,7 +4,7 @@ helpers and TT optimizers.  Arithmetic runs in libsow_amd.so (hand-written HIP f
 include/sow_amd.h); this package is the host-side mirror of the reference's Python surface.
 """
 from .layer import SoWLinear, SoWParameter  # noqa: F401
-from .prepare import SoWConfig, accumulate, load_sow, prepare_sow, reset_optimizer  # noqa: F401
+from .prepare import SoWConfig, accumulate, load_sow, master_factors, prepare_sow, reset_optimizer  # noqa: F401
 from .tt import TensorTrain  # noqa: F401
 from .optimizer import TTAdam, TTSGD, FactorAdamW, clip_grad_norm_  # noqa: F401
 from .tensor_linear import TensorTrainLinear  # noqa: F401

@@ -18,6 +18,7 @@ F32, BF16, F16 = 0, 1, 2
 PARAM_F32 = 0x100        # OR-ed into BF16 / F16: fp32 parameters, fp32 weight gradients (mixed precision)
 FUSE_ACC = 0x200         # OR-ed into BF16 / F16: permission to run a low-rank accumulator and the live term in one pass
 FUSE_ACC_DEEP = 0x400    # the same permission for 256 < r_acc + r <= 960 (chain_deep_acc.hip); a call carries one of the two
+ACC_NATIVE = 0x800       # OR-ed in next to PARAM_F32: the accumulator is of the compute dtype, read in place, never packed
 ACC_NONE, ACC_LOWRANK, ACC_DENSE = 0, 1, 2
 ACC_DENSE_FP8 = 3        # a dense accumulator as E4M3 codes (acc_down) with int8 column exponents (acc_up)
 ACC_DENSE_FP4 = 4        # a dense accumulator as packed E2M1 codes (acc_down) with E8M0 block scales (acc_up): MXFP4

@@ -82,7 +82,7 @@ static inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 static inline size_t esize(int dtype) { return dtype == SOW_F32 ? 4 : 2; }
 static inline bool ok_dtype(int d) { return d == SOW_F32 || d == SOW_BF16 || d == SOW_F16; }
 // The dtype argument of an entry point, decoded once.  SOW_FUSE_ACC and SOW_FUSE_ACC_DEEP are permissions and are ignored
-// together with SOW_PARAM_F32.
+// together with SOW_PARAM_F32; SOW_ACC_NATIVE means something next to SOW_PARAM_F32 only.
 // The layer entry points, their plans and descriptors take what layer_ok() admits; sow_*_shared refuses SOW_PARAM_F32 as
 // unsupported after its own checks.  The entry points outside the layer surface (GEMM, QR, accumulate, optimizer, copies)
 // only strip the permission with nofuse() and refuse or reject SOW_PARAM_F32 themselves, each with its own code.
@@ -91,19 +91,23 @@ struct Dtype {
   bool param_f32;   // SOW_PARAM_F32
   bool fuse;        // SOW_FUSE_ACC, without SOW_PARAM_F32
   bool deep;        // SOW_FUSE_ACC_DEEP, without SOW_PARAM_F32
+  bool native;      // SOW_ACC_NATIVE next to SOW_PARAM_F32: the accumulator is of the compute dtype and is not packed
+  bool native_bit;  // SOW_ACC_NATIVE as passed (ignored without SOW_PARAM_F32; refused where SOW_PARAM_F32 is refused)
   // the permission bits a layer call carries on (SOW_FUSE_ACC | SOW_FUSE_ACC_DEEP, or 0)
   int perm() const { return (fuse ? SOW_FUSE_ACC : 0) | (deep ? SOW_FUSE_ACC_DEEP : 0); }
-  bool layer_ok() const { return ok_dtype(cd) && !(param_f32 && cd == SOW_F32); }
+  bool layer_ok() const { return ok_dtype(cd) && !((param_f32 || native_bit) && cd == SOW_F32); }   // fp32 compute takes neither flag
 };
 static inline Dtype decode_dtype(int d) {
   Dtype f;
-  f.cd = d & ~(SOW_FUSE_ACC | SOW_FUSE_ACC_DEEP | SOW_PARAM_F32);
+  f.cd = d & ~(SOW_FUSE_ACC | SOW_FUSE_ACC_DEEP | SOW_PARAM_F32 | SOW_ACC_NATIVE);
   f.param_f32 = (d & SOW_PARAM_F32) != 0;
+  f.native_bit = (d & SOW_ACC_NATIVE) != 0;
+  f.native = f.native_bit && f.param_f32;
   f.fuse = (d & SOW_FUSE_ACC) != 0 && !f.param_f32;
   f.deep = (d & SOW_FUSE_ACC_DEEP) != 0 && !f.param_f32;
   return f;
 }
-static inline bool flagged(int d) { return (d & SOW_PARAM_F32) != 0; }
+static inline bool flagged(int d) { return (d & (SOW_PARAM_F32 | SOW_ACC_NATIVE)) != 0; }
 static inline int nofuse(int d) { return d & ~(SOW_FUSE_ACC | SOW_FUSE_ACC_DEEP); }
 
 // ---- short inputs ---------------------------------------------------------------------------------
@@ -219,7 +223,7 @@ static int gemm_auto(const void* A, int64_t lda, const void* B, int64_t ldb, boo
 
 extern "C" {
 
-int sow_version(void) { return 120; }
+int sow_version(void) { return 121; }
 
 int sow_set_switch(const char* name, int value) {
   if (!name) return SOW_ERR_NULL;
@@ -438,8 +442,10 @@ static int check_layer(const sow_layer_args& L, bool bwd, bool lowrank) {
 // past the compute-dtype plan (pack_params_kernel, misc.hip); the bf16 / f16 kernels then read the packed copies, in the
 // layouts they read from the caller.  Packed again at every call: the factors change at every optimizer step.
 static inline size_t pack_elems_bytes(int64_t n) { return al256((size_t)n * 2); }
-static size_t pack_bytes(int d_in, int d_out, int r_live, int r_acc, int acc_kind) {
+// native (SOW_ACC_NATIVE): the accumulator is of the compute dtype already; the kernels read it where it lies
+static size_t pack_bytes(int d_in, int d_out, int r_live, int r_acc, int acc_kind, bool native) {
   size_t b = pack_elems_bytes((int64_t)d_in * r_live) + pack_elems_bytes((int64_t)r_live * d_out) + pack_elems_bytes(d_out);
+  if (native) return b;
   if (acc_kind == SOW_ACC_DENSE) b += pack_elems_bytes((int64_t)d_in * d_out);
   if (acc_kind == SOW_ACC_LOWRANK) b += pack_elems_bytes((int64_t)d_in * r_acc) + pack_elems_bytes((int64_t)r_acc * d_out);
   return b;
@@ -449,10 +455,10 @@ static size_t pack_bytes(int d_in, int d_out, int r_live, int r_acc, int acc_kin
 // the workspace), except for a forward (fwd) whose kernels need no scratch (sow_forward_workspace_bytes = 0 for the compute
 // dtype) given a workspace sized by the flagged forward query only: there they start the workspace.  Such a forward then runs
 // without workspace, exactly as the unflagged call.
-static int pack_layer(sow_layer_args& L, int cd, bool fwd, std::vector<PackItem>& items) {
+static int pack_layer(sow_layer_args& L, int cd, bool fwd, bool native, std::vector<PackItem>& items) {
   const int r_acc = acc_rank(L);
   const WsPlan w = plan_of(L, cd);
-  const size_t pack = pack_bytes(L.d_in, L.d_out, L.r_live, r_acc, L.acc_kind);
+  const size_t pack = pack_bytes(L.d_in, L.d_out, L.r_live, r_acc, L.acc_kind, native);
   const bool no_scratch = fwd && sow_forward_workspace_bytes(L.T, L.d_in, L.d_out, L.r_live, r_acc, L.acc_kind, cd) == 0;
   const size_t off = (no_scratch && L.workspace_bytes < w.total + pack + 255) ? 0 : w.total;
   if (!L.workspace) return SOW_ERR_NULL;
@@ -468,6 +474,7 @@ static int pack_layer(sow_layer_args& L, int cd, bool fwd, std::vector<PackItem>
   put(L.A, (int64_t)L.d_in * L.r_live);
   put(L.B, (int64_t)L.r_live * L.d_out);
   put(L.bias, L.d_out);
+  if (native) return SOW_OK;
   if (L.acc_kind == SOW_ACC_DENSE) put(L.acc_down, (int64_t)L.d_in * L.d_out);
   if (L.acc_kind == SOW_ACC_LOWRANK) {
     put(L.acc_down, (int64_t)L.d_in * r_acc);
@@ -476,12 +483,12 @@ static int pack_layer(sow_layer_args& L, int cd, bool fwd, std::vector<PackItem>
   return SOW_OK;
 }
 // one layer of a single-layer call: checked as the unflagged call checks it, packed by a launch of its own
-static int pack_single(sow_layer_args& L, int cd, bool fwd, hipStream_t stream) {
+static int pack_single(sow_layer_args& L, int cd, bool fwd, bool native, hipStream_t stream) {
   int rc = check_layer(L, !fwd, true);
   if (rc) return rc;
   normalise_acc(L);
   std::vector<PackItem> items;
-  if ((rc = pack_layer(L, cd, fwd, items))) return rc;
+  if ((rc = pack_layer(L, cd, fwd, native, items))) return rc;
   return launch_pack_params(items.data(), (int)items.size(), cd, stream);
 }
 
@@ -782,7 +789,7 @@ int sow_reduce_batch(const void* descs, const int* starts, int n, int total_bloc
   if (!f.layer_ok()) return SOW_ERR_DTYPE;
   // the slab partials are fp32 whatever the compute dtype: fp32 gradients are their sums, rounded once.  An unflagged dtype
   // goes through as it came: SOW_FUSE_ACC is not stripped here, the launcher refuses it (SOW_ERR_DTYPE)
-  const int gdt = f.param_f32 ? SOW_F32 : dtype;
+  const int gdt = f.param_f32 ? SOW_F32 : (dtype & ~SOW_ACC_NATIVE);
   if (n < 0 || total_blocks < 0) return SOW_ERR_SHAPE;
   if (n == 0) return SOW_OK;
   if (!descs || !starts) return SOW_ERR_NULL;
@@ -795,7 +802,7 @@ size_t sow_forward_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, i
   if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0 || !f.layer_ok()) return 0;
   if (f.param_f32) {   // the forward's own scratch (if any) followed by the packed parameters (pack_layer)
     const size_t own = sow_forward_workspace_bytes(T, d_in, d_out, r_live, r_acc, acc_kind, f.cd);
-    const size_t pack = pack_bytes(d_in, d_out, r_live, acc_kind == SOW_ACC_LOWRANK ? r_acc : 0, acc_kind);
+    const size_t pack = pack_bytes(d_in, d_out, r_live, acc_kind == SOW_ACC_LOWRANK ? r_acc : 0, acc_kind, f.native);
     return own ? own + pack : pack + 256;
   }
   const bool wide_acc = acc_kind == SOW_ACC_LOWRANK && r_acc > 64;
@@ -809,7 +816,7 @@ size_t sow_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int r_acc
   const Dtype f = decode_dtype(dtype);
   if (acc_kind == SOW_ACC_DENSE_FP8 || acc_kind == SOW_ACC_DENSE_FP4) return 0;
   if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0 || !f.layer_ok()) return 0;
-  const size_t pack = f.param_f32 ? pack_bytes(d_in, d_out, r_live, acc_kind == SOW_ACC_LOWRANK ? r_acc : 0, acc_kind) : 0;
+  const size_t pack = f.param_f32 ? pack_bytes(d_in, d_out, r_live, acc_kind == SOW_ACC_LOWRANK ? r_acc : 0, acc_kind, f.native) : 0;
   return plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, f.cd, f.perm()).total + pack + 256;
 }
 
@@ -868,7 +875,7 @@ int sow_forward(const void* x, const void* A, const void* B, const void* acc_dow
   sow_layer_args L = single_layer(x, A, B, acc_down, acc_up, bias, y, h_save, nullptr, nullptr, nullptr, nullptr, nullptr, T, d_in,
                                   d_out, r_live, r_acc, acc_kind, scale, 0.f, workspace, workspace_bytes);
   if (f.param_f32 && T > 0) {   // fp32 parameters: forward_impl's checks before the pack launch reads them
-    const int rc = pack_single(L, f.cd, true, (hipStream_t)stream);
+    const int rc = pack_single(L, f.cd, true, f.native, (hipStream_t)stream);
     if (rc) return rc;
   }
   return forward_impl(L, f.cd, f.perm(), (hipStream_t)stream);
@@ -991,11 +998,12 @@ int sow_backward_ex(const void* dy, const void* x, const void* h_save, const voi
   const Dtype f = decode_dtype(dtype);
   sow_layer_args L = single_layer(x, A, B, acc_down, acc_up, nullptr, nullptr, const_cast<void*>(h_save), dy, dx, dA, dB, dbias, T,
                                   d_in, d_out, r_live, r_acc, acc_kind, scale, grad_beta, workspace, workspace_bytes);
+  if (f.native_bit && !f.layer_ok()) return SOW_ERR_DTYPE;
   if (!f.param_f32) return backward_impl(L, f.cd, f.cd, phases, f.perm(), (hipStream_t)stream);
   if (!f.layer_ok()) return SOW_ERR_DTYPE;
   // fp32 parameters: only the data gradient reads the factors (and the accumulator); they are packed when it runs
   if ((phases & SOW_BWD_DATA) && T > 0) {
-    const int rc = pack_single(L, f.cd, false, (hipStream_t)stream);
+    const int rc = pack_single(L, f.cd, false, f.native, (hipStream_t)stream);
     if (rc) return rc;
   }
   return backward_impl(L, f.cd, SOW_F32, phases, 0, (hipStream_t)stream);
@@ -1058,7 +1066,8 @@ static bool group_rows(const sow_layer_args* layers, int n, int dtype, int phase
 }
 
 // fp32 parameters of a group: a copy of the layer list pointing at the packed operands, every layer packed by ONE launch
-static int pack_group(const sow_layer_args* layers, int n, int cd, bool bwd, std::vector<sow_layer_args>& out, hipStream_t stream) {
+static int pack_group(const sow_layer_args* layers, int n, int cd, bool bwd, bool native, std::vector<sow_layer_args>& out,
+                      hipStream_t stream) {
   out.assign(layers, layers + n);
   std::vector<PackItem> items;
   int rc;
@@ -1067,7 +1076,7 @@ static int pack_group(const sow_layer_args* layers, int n, int cd, bool bwd, std
     if (L.T == 0) continue;
     normalise_acc(L);
     if (bwd) L.bias = nullptr;   // backward reads no bias
-    if ((rc = pack_layer(L, cd, !bwd, items))) return rc;
+    if ((rc = pack_layer(L, cd, !bwd, native, items))) return rc;
   }
   return launch_pack_params(items.data(), (int)items.size(), cd, stream);
 }
@@ -1120,12 +1129,12 @@ int sow_forward_group(const sow_layer_args* layers, int n, int dtype, void* stre
   if (!f.layer_ok()) return SOW_ERR_DTYPE;
   if (!f.param_f32 || n <= 0 || !layers) return forward_group_impl(layers, n, f.cd, f.perm(), (hipStream_t)stream);
   std::vector<sow_layer_args> packed;
-  const int rc = pack_group(layers, n, f.cd, false, packed, (hipStream_t)stream);
+  const int rc = pack_group(layers, n, f.cd, false, f.native, packed, (hipStream_t)stream);
   return rc ? rc : forward_group_impl(packed.data(), n, f.cd, 0, (hipStream_t)stream);
 }
 
 // ---- generation-sized forwards (skinny_fwd.hip) --------------------------------------------------------------
-// The admitted set, decided from the shape alone: 1 <= T <= 32, bf16 / f16 without SOW_PARAM_F32, a dense accumulator (in the
+// The admitted set, decided from the shape alone: 1 <= T <= 32, bf16 / f16 (SOW_PARAM_F32 only with SOW_ACC_NATIVE), a dense accumulator (in the
 // compute dtype, as E4M3 codes or as MXFP4 codes) or none, r_live <= 64, widths multiples of 8 (d_in of 32 for MXFP4: whole blocks).
 static bool skinny_shape_ok(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype) {
   return (dtype == SOW_BF16 || dtype == SOW_F16) && T >= 1 && T <= 32 && d_in > 0 && d_out > 0 && r_live >= 1 && r_live <= 64 &&
@@ -1148,19 +1157,19 @@ static SkWs skinny_ws(int64_t T, int d_in, int d_out, int acc_kind) {
 // (an E4M3 and an MXFP4 accumulator have queries of their own: this one keeps answering 0 for every kind value it answered 0 for before)
 size_t sow_forward_skinny_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype) {
   const Dtype f = decode_dtype(dtype);
-  if (f.param_f32 || acc_kind == SOW_ACC_DENSE_FP8 || acc_kind == SOW_ACC_DENSE_FP4 || !skinny_shape_ok(T, d_in, d_out, r_live, acc_kind, f.cd)) return 0;
+  if ((f.param_f32 && !f.native) || acc_kind == SOW_ACC_DENSE_FP8 || acc_kind == SOW_ACC_DENSE_FP4 || !skinny_shape_ok(T, d_in, d_out, r_live, acc_kind, f.cd)) return 0;
   return skinny_ws(T, d_in, d_out, acc_kind).total;
 }
 
 size_t sow_forward_skinny_fp8_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int dtype) {
   const Dtype f = decode_dtype(dtype);
-  if (f.param_f32 || !skinny_shape_ok(T, d_in, d_out, r_live, SOW_ACC_DENSE_FP8, f.cd)) return 0;
+  if ((f.param_f32 && !f.native) || !skinny_shape_ok(T, d_in, d_out, r_live, SOW_ACC_DENSE_FP8, f.cd)) return 0;
   return skinny_ws(T, d_in, d_out, SOW_ACC_DENSE_FP8).total;
 }
 
 size_t sow_forward_skinny_fp4_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int dtype) {
   const Dtype f = decode_dtype(dtype);
-  if (f.param_f32 || !skinny_shape_ok(T, d_in, d_out, r_live, SOW_ACC_DENSE_FP4, f.cd)) return 0;
+  if ((f.param_f32 && !f.native) || !skinny_shape_ok(T, d_in, d_out, r_live, SOW_ACC_DENSE_FP4, f.cd)) return 0;
   return skinny_ws(T, d_in, d_out, SOW_ACC_DENSE_FP4).total;
 }
 
@@ -1170,7 +1179,8 @@ int sow_forward_skinny(const sow_layer_args* layers, int n, int dtype, void* str
   const Dtype f = decode_dtype(dtype);
   const int cd = f.cd;
   if (!f.layer_ok() || cd == SOW_F32) return SOW_ERR_DTYPE;
-  if (f.param_f32 || sw_on(SW_NO_SKINNY)) return SOW_ERR_UNSUPPORTED;
+  // fp32 factors are admitted over a native accumulator only (SOW_ACC_NATIVE: the kernels round A, B and the bias in registers)
+  if ((f.param_f32 && !f.native) || sw_on(SW_NO_SKINNY)) return SOW_ERR_UNSUPPORTED;
   if (n < 0) return SOW_ERR_SHAPE;
   if (n == 0) return SOW_OK;
   if (!layers) return SOW_ERR_NULL;
@@ -1205,7 +1215,7 @@ int sow_forward_skinny(const sow_layer_args* layers, int n, int dtype, void* str
     K.T = (int)L.T, K.d_in = L.d_in, K.d_out = L.d_out, K.r = L.r_live, K.scale = L.scale;
     K.wexp = fp8 || fp4 ? (const int8_t*)L.acc_up : nullptr;
   }
-  return launch_skinny_fwd(sk, m, cd, n_fp4 ? SOW_ACC_DENSE_FP4 : n_fp8 ? SOW_ACC_DENSE_FP8 : SOW_ACC_DENSE, (hipStream_t)stream);
+  return launch_skinny_fwd(sk, m, cd, n_fp4 ? SOW_ACC_DENSE_FP4 : n_fp8 ? SOW_ACC_DENSE_FP8 : SOW_ACC_DENSE, f.native, (hipStream_t)stream);
 }
 
 static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, int gdt, int phases, int perm, hipStream_t stream) {
@@ -1317,11 +1327,12 @@ int sow_backward_group(const sow_layer_args* layers, int n, int dtype, int phase
   if (any_fp8_acc(layers, n)) return SOW_ERR_UNSUPPORTED;
   hipStream_t stream = (hipStream_t)stream_;
   const Dtype f = decode_dtype(dtype);
+  if (f.native_bit && !f.layer_ok()) return SOW_ERR_DTYPE;
   if (!f.param_f32) return backward_group_impl(layers, n, f.cd, f.cd, phases, f.perm(), stream);
   if (!f.layer_ok()) return SOW_ERR_DTYPE;
   if (n <= 0 || !layers || !(phases & SOW_BWD_DATA)) return backward_group_impl(layers, n, f.cd, SOW_F32, phases, 0, stream);
   std::vector<sow_layer_args> packed;
-  const int rc = pack_group(layers, n, f.cd, true, packed, stream);
+  const int rc = pack_group(layers, n, f.cd, true, f.native, packed, stream);
   return rc ? rc : backward_group_impl(packed.data(), n, f.cd, SOW_F32, phases, 0, stream);
 }
 
@@ -1354,7 +1365,7 @@ int sow_forward_shared(const sow_layer_args* layers, int n, int dtype, void* str
   if ((rc = shared_common(layers, n, false))) return rc;
   for (int i = 0; i < n; ++i)
     if ((rc = check_layer(layers[i], false, false))) return rc;
-  if (sw_on(SW_NO_SHARED_X) || f.param_f32 || n > C2_MAXG || layers[0].T == 0) return SOW_ERR_UNSUPPORTED;
+  if (sw_on(SW_NO_SHARED_X) || f.param_f32 || f.native_bit || n > C2_MAXG || layers[0].T == 0) return SOW_ERR_UNSUPPORTED;
   ChainParams ps[C2_MAXG];
   for (int i = 0; i < n; ++i)
     if (!group_chain_params(layers[i], false, f.cd, WsPlan{}, &ps[i])) return SOW_ERR_UNSUPPORTED;
@@ -1370,7 +1381,7 @@ int sow_backward_shared(const sow_layer_args* layers, int n, int dtype, int phas
   int rc;
   if ((rc = shared_common(layers, n, true))) return rc;
   if (n > C2_MAXG) return SOW_ERR_UNSUPPORTED;
-  if (f.param_f32) return SOW_ERR_UNSUPPORTED;
+  if (f.param_f32 || f.native_bit) return SOW_ERR_UNSUPPORTED;   // (SOW_ACC_NATIVE: the code of SOW_PARAM_F32)
   sow_layer_args filled[C2_MAXG];
   shared_fill_dx(layers, n, filled);
   if (!(phases & SOW_BWD_DATA)) return backward_group_impl(filled, n, cd, cd, phases, 0, stream);

@@ -249,6 +249,7 @@ int launch_tn_wide(const void* x, const void* dh, const void* dy, const void* h,
 constexpr int SK_MAXL = 16;
 struct SkLayer {
   const void *x, *W, *A, *B, *bias;   // W = the dense accumulator [d_in][d_out] (or its E4M3 codes), or nullptr
+                                      // A, B, bias: of the compute dtype, or all fp32 (launch_skinny_fwd's param_f32)
   void* y;
   float *Py, *Ph;                     // slab partials [S][T][d_out] (nullptr without W) and [S][T][64]
   int T, d_in, d_out, r;
@@ -261,7 +262,8 @@ void skinny_plan(int d_in, int d_out, int acc_kind, int* S, int* KS, int* ncr);
 size_t skinny_py_bytes(int64_t T, int d_out, int S);
 size_t skinny_ph_bytes(int64_t T, int S);
 // acc_kind: the kind of the call's dense layers (SOW_ACC_DENSE, SOW_ACC_DENSE_FP8 or SOW_ACC_DENSE_FP4; any of them without one)
-int launch_skinny_fwd(const SkLayer* layers, int n, int dtype, int acc_kind, hipStream_t stream);
+// param_f32: A, B and bias are fp32 (16-byte aligned as before), rounded once to `dtype` in registers by both kernels
+int launch_skinny_fwd(const SkLayer* layers, int n, int dtype, int acc_kind, bool param_f32, hipStream_t stream);
 // gemm.hip
 int launch_gemm(const void* A, int64_t lda, bool transA, const void* B, int64_t ldb, bool transB, void* C, int64_t ldc,
                 const void* bias, int64_t M, int N, int K, float alpha, float beta, int dtype, hipStream_t stream);

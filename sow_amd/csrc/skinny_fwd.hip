@@ -42,6 +42,14 @@
 // instead of eight, plus one 8-byte load of the block's scale bytes.  v_cvt_scalef32_pk_{bf16,f16}_fp4 turns one byte and the
 // scale into a fragment register (two rows of one column): 32 conversions per step, no packs.  The scale is applied in the
 // conversion, so Py holds sum x . W^ and phase B is the plain one.
+//
+// fp32 factors (SOW_PARAM_F32 | SOW_ACC_NATIVE, the PF = true instantiations of both kernels, for every accumulator format): A, B
+// and the bias are fp32 master copies and the accumulator is what it is above.  No pack launch: the x . A workgroups gather A
+// with 4-byte loads into the register the 2-byte load fills (the raw bits wait there while x is staged) and round at first use;
+// phase B loads its column of B and the bias as fp32 and rounds where the fmaf reads them.  One rounding per value, to nearest
+// even (from_f32<T>, the rounding of the parameter pack): y is bit-identical to the PF = false call on pre-rounded factors.
+#include <type_traits>
+
 #include "kernels.hpp"
 
 namespace sow {
@@ -119,9 +127,24 @@ template <> __device__ __forceinline__ uint32_t sk_pack_exact<f16_t>(float lo, f
   return u;
 }
 
+// fp32 factors (PF = true instantiations, SOW_PARAM_F32 | SOW_ACC_NATIVE): one fp32 element, rounded once to nearest even to T,
+// as the 16 bits the kernels would have loaded from a packed copy (the rounding of the parameter pack, misc.hip)
+template <typename T> __device__ __forceinline__ uint32_t sk_rn_bits(float v) {
+  const T t = from_f32<T>(v);
+  uint16_t u;
+  __builtin_memcpy(&u, &t, 2);
+  return u;
+}
+
+// a parameter element as phase B uses it: of T as loaded, or fp32 rounded once to T
+template <typename T, typename TP> __device__ __forceinline__ float sk_param(TP v) {
+  if constexpr (std::is_same<TP, T>::value) return to_f32(v);
+  else return to_f32(from_f32<T>(v));
+}
+
 constexpr int SK_PF = 4;   // k-steps a wave keeps in flight: all of them are requested before the x slab is staged
 
-template <typename T, SkFmt F = SK_PLAIN> __global__ __launch_bounds__(256) void skinny_a_kernel(const SkGroup g) {
+template <typename T, SkFmt F = SK_PLAIN, bool PF = false> __global__ __launch_bounds__(256) void skinny_a_kernel(const SkGroup g) {
   extern __shared__ __align__(16) char sk_smem[];
   constexpr bool FP8 = F == SK_FP8, FP4 = F == SK_FP4;
   constexpr int SK_NCT = SkW<F>::NCT, SK_CN = sk_cn(F != SK_PLAIN), SK_RS = sk_rs(F != SK_PLAIN);
@@ -152,6 +175,7 @@ template <typename T, SkFmt F = SK_PLAIN> __global__ __launch_bounds__(256) void
   const size_t wpitch = (size_t)d_out * (F != SK_PLAIN ? 1 : sizeof(T));   // bytes per row of W (per row pair of MXFP4 codes)
   const int r = L.r, ja = cr * 16 + n16;
   const uint16_t* Ap = (const uint16_t*)L.A + ja;
+  const uint32_t* Apf = (const uint32_t*)L.A + ja;   // PF: A is fp32, a 4-byte gather; the raw bits wait in the register
   auto load_step = [&](int kk, sk_wvec(&o)[8]) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -170,7 +194,9 @@ template <typename T, SkFmt F = SK_PLAIN> __global__ __launch_bounds__(256) void
           }
         } else if (col_ok && kk < klen && k < d_in) v = sk_load_w((const sk_wvec*)(Wp + (size_t)k * wpitch));
       } else {
-        if (ja < r && kk < klen && k < d_in) v[0] = Ap[(size_t)k * r];
+        if constexpr (PF) {
+          if (ja < r && kk < klen && k < d_in) v[0] = Apf[(size_t)k * r];
+        } else if (ja < r && kk < klen && k < d_in) v[0] = Ap[(size_t)k * r];
       }
       o[i] = v;
     }
@@ -209,7 +235,12 @@ template <typename T, SkFmt F = SK_PLAIN> __global__ __launch_bounds__(256) void
         if (is_xa) {
           u32x4 f;
 #pragma unroll
-          for (int m = 0; m < 4; ++m) f[m] = d[p][2 * m][0] | (d[p][2 * m + 1][0] << 16);
+          for (int m = 0; m < 4; ++m) {
+            if constexpr (PF)   // rounded here, at first use: the requests above stay in flight while x is staged
+              f[m] = sk_rn_bits<T>(__uint_as_float(d[p][2 * m][0])) | (sk_rn_bits<T>(__uint_as_float(d[p][2 * m + 1][0])) << 16);
+            else
+              f[m] = d[p][2 * m][0] | (d[p][2 * m + 1][0] << 16);
+          }
           acc[0][0] = sk_mfma<T>(a0, f, acc[0][0]);
           if (rows == 32) acc[0][1] = sk_mfma<T>(a1, f, acc[0][1]);
         } else if constexpr (FP8) {
@@ -306,7 +337,7 @@ template <typename T, SkFmt F = SK_PLAIN> __global__ __launch_bounds__(256) void
 // instead of a chain of r + 2 S + 1, and only the fp32 additions run in order.
 constexpr int SK_BS = 16;   // slab partials requested up front; a layer with more slabs adds the rest in a second loop
 
-template <typename T, bool FP8 = false> __global__ __launch_bounds__(256) void skinny_b_kernel(const SkGroup g) {
+template <typename T, bool FP8 = false, bool PF = false> __global__ __launch_bounds__(256) void skinny_b_kernel(const SkGroup g) {
   __shared__ float hs[4][64];
   int li = 0;
   for (int i = 1; i < g.n; ++i)
@@ -322,13 +353,15 @@ template <typename T, bool FP8 = false> __global__ __launch_bounds__(256) void s
   const int tc = min(t, Tn - 1), nc = min(n, d_out - 1), jc = min(nn, r - 1);
   const bool dense = L.Py != nullptr;
 
-  T bv[64];
+  // PF: B and the bias are fp32; the loads are requested as they are and each value is rounded once to T where it is used
+  typedef typename std::conditional<PF, float, T>::type TP;
+  TP bv[64];
   {
-    const T* B = (const T*)L.B + nc;
+    const TP* B = (const TP*)L.B + nc;
 #pragma unroll
     for (int j = 0; j < 64; ++j) bv[j] = B[(size_t)min(j, r - 1) * d_out];
   }
-  const T bias = L.bias ? ((const T*)L.bias)[nc] : from_f32<T>(0.f);
+  const TP bias = L.bias ? ((const TP*)L.bias)[nc] : from_f32<TP>(0.f);
   int wexp = 0;   // the column's exponent: |e| <= 119, 2^e is a normal fp32 number
   if constexpr (FP8)
     if (dense) wexp = L.wexp[nc];
@@ -363,17 +396,30 @@ template <typename T, bool FP8 = false> __global__ __launch_bounds__(256) void s
   if (!live) return;
 #pragma unroll
   for (int j = 0; j < 64; ++j)
-    if (j < r) acc = fmaf(hs[tl][j], to_f32(bv[j]), acc);
-  if (L.bias) acc += to_f32(bias);
+    if (j < r) acc = fmaf(hs[tl][j], sk_param<T>(bv[j]), acc);
+  if (L.bias) acc += sk_param<T>(bias);
   ((T*)L.y)[(size_t)t * d_out + n] = from_f32<T>(acc);
 }
 
 size_t skinny_py_bytes(int64_t T, int d_out, int S) { return (size_t)S * (size_t)T * (size_t)d_out * sizeof(float); }
 size_t skinny_ph_bytes(int64_t T, int S) { return (size_t)S * (size_t)T * 64 * sizeof(float); }
 
+// the two launches of one (compute dtype, accumulator format, factor dtype): one instantiation of each kernel
+template <typename T, SkFmt F, bool PF> static int sk_launch(const SkGroup& g, int na, int nb, size_t lds, hipStream_t stream) {
+  constexpr int LDS_X = 32 * (SK_KS_MAX + SK_XPAD) * 2;
+  constexpr int LDS_PARK = 4 * 32 * sk_rs(F != SK_PLAIN) * 4;
+  constexpr int LDS_MAX = LDS_PARK > LDS_X ? LDS_PARK : LDS_X;
+  SOW_SET_MAX_LDS_ONCE(LDS_MAX, skinny_a_kernel<T, F, PF>);
+  hipLaunchKernelGGL((skinny_a_kernel<T, F, PF>), dim3(na), dim3(256), lds, stream, g);
+  SOW_CHECK_LAUNCH();
+  hipLaunchKernelGGL((skinny_b_kernel<T, F == SK_FP8, PF>), dim3(nb), dim3(256), 0, stream, g);
+  SOW_CHECK_LAUNCH();
+  return SOW_OK;
+}
+
 // layers: x, W (or nullptr), A, B, bias, y, Py (or nullptr), Ph, T in [1, 32], d_in, d_out, r, scale set by the caller (api.hip
-// has checked the admitted set); the plan and the block offsets are filled in here
-int launch_skinny_fwd(const SkLayer* layers, int n, int dtype, int acc_kind, hipStream_t stream) {
+// has checked the admitted set); the plan and the block offsets are filled in here.  param_f32: A, B and bias are fp32
+int launch_skinny_fwd(const SkLayer* layers, int n, int dtype, int acc_kind, bool param_f32, hipStream_t stream) {
   if (n <= 0) return SOW_OK;
   if (n > SK_MAXL || (dtype != SOW_BF16 && dtype != SOW_F16)) return SOW_ERR_UNSUPPORTED;
   // the dense layers of a call are of one kind: the kernels are instantiated per kind
@@ -402,42 +448,15 @@ int launch_skinny_fwd(const SkLayer* layers, int n, int dtype, int acc_kind, hip
     lds = xb > lds ? xb : lds;
     lds = rb > lds ? rb : lds;
   }
-  constexpr int LDS_X = 32 * (SK_KS_MAX + SK_XPAD) * 2;
-  constexpr int LDS_MAX = 4 * 32 * sk_rs(false) * 4 > LDS_X ? 4 * 32 * sk_rs(false) * 4 : LDS_X;
-  constexpr int LDS_MAX8 = 4 * 32 * sk_rs(true) * 4 > LDS_X ? 4 * 32 * sk_rs(true) * 4 : LDS_X;
-  if (fp4 && dtype == SOW_BF16) {   // the scale went into the conversion: Py holds sum x . W^, phase B is the plain one
-    SOW_SET_MAX_LDS_ONCE(LDS_MAX8, skinny_a_kernel<bf16_t, SK_FP4>);
-    hipLaunchKernelGGL((skinny_a_kernel<bf16_t, SK_FP4>), dim3(na), dim3(256), lds, stream, g);
-    SOW_CHECK_LAUNCH();
-    hipLaunchKernelGGL(skinny_b_kernel<bf16_t>, dim3(nb), dim3(256), 0, stream, g);
-  } else if (fp4) {
-    SOW_SET_MAX_LDS_ONCE(LDS_MAX8, skinny_a_kernel<f16_t, SK_FP4>);
-    hipLaunchKernelGGL((skinny_a_kernel<f16_t, SK_FP4>), dim3(na), dim3(256), lds, stream, g);
-    SOW_CHECK_LAUNCH();
-    hipLaunchKernelGGL(skinny_b_kernel<f16_t>, dim3(nb), dim3(256), 0, stream, g);
-  } else if (fp8 && dtype == SOW_BF16) {
-    SOW_SET_MAX_LDS_ONCE(LDS_MAX8, skinny_a_kernel<bf16_t, SK_FP8>);
-    hipLaunchKernelGGL((skinny_a_kernel<bf16_t, SK_FP8>), dim3(na), dim3(256), lds, stream, g);
-    SOW_CHECK_LAUNCH();
-    hipLaunchKernelGGL((skinny_b_kernel<bf16_t, true>), dim3(nb), dim3(256), 0, stream, g);
-  } else if (fp8) {
-    SOW_SET_MAX_LDS_ONCE(LDS_MAX8, skinny_a_kernel<f16_t, SK_FP8>);
-    hipLaunchKernelGGL((skinny_a_kernel<f16_t, SK_FP8>), dim3(na), dim3(256), lds, stream, g);
-    SOW_CHECK_LAUNCH();
-    hipLaunchKernelGGL((skinny_b_kernel<f16_t, true>), dim3(nb), dim3(256), 0, stream, g);
-  } else if (dtype == SOW_BF16) {
-    SOW_SET_MAX_LDS_ONCE(LDS_MAX, skinny_a_kernel<bf16_t>);
-    hipLaunchKernelGGL(skinny_a_kernel<bf16_t>, dim3(na), dim3(256), lds, stream, g);
-    SOW_CHECK_LAUNCH();
-    hipLaunchKernelGGL(skinny_b_kernel<bf16_t>, dim3(nb), dim3(256), 0, stream, g);
-  } else {
-    SOW_SET_MAX_LDS_ONCE(LDS_MAX, skinny_a_kernel<f16_t>);
-    hipLaunchKernelGGL(skinny_a_kernel<f16_t>, dim3(na), dim3(256), lds, stream, g);
-    SOW_CHECK_LAUNCH();
-    hipLaunchKernelGGL(skinny_b_kernel<f16_t>, dim3(nb), dim3(256), 0, stream, g);
+  // MXFP4: the scale went into the conversion, Py holds sum x . W^ and phase B is the plain one
+  if (param_f32) {
+    if (fp4) return dtype == SOW_BF16 ? sk_launch<bf16_t, SK_FP4, true>(g, na, nb, lds, stream) : sk_launch<f16_t, SK_FP4, true>(g, na, nb, lds, stream);
+    if (fp8) return dtype == SOW_BF16 ? sk_launch<bf16_t, SK_FP8, true>(g, na, nb, lds, stream) : sk_launch<f16_t, SK_FP8, true>(g, na, nb, lds, stream);
+    return dtype == SOW_BF16 ? sk_launch<bf16_t, SK_PLAIN, true>(g, na, nb, lds, stream) : sk_launch<f16_t, SK_PLAIN, true>(g, na, nb, lds, stream);
   }
-  SOW_CHECK_LAUNCH();
-  return SOW_OK;
+  if (fp4) return dtype == SOW_BF16 ? sk_launch<bf16_t, SK_FP4, false>(g, na, nb, lds, stream) : sk_launch<f16_t, SK_FP4, false>(g, na, nb, lds, stream);
+  if (fp8) return dtype == SOW_BF16 ? sk_launch<bf16_t, SK_FP8, false>(g, na, nb, lds, stream) : sk_launch<f16_t, SK_FP8, false>(g, na, nb, lds, stream);
+  return dtype == SOW_BF16 ? sk_launch<bf16_t, SK_PLAIN, false>(g, na, nb, lds, stream) : sk_launch<f16_t, SK_PLAIN, false>(g, na, nb, lds, stream);
 }
 
 }  // namespace sow

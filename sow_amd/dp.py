@@ -106,8 +106,9 @@ class _GradSink:
         # sized for the fused data gradient (SOW_FUSE_ACC / SOW_FUSE_ACC_DEEP) where the layer takes it (the flagged plan also
         # serves the unflagged call)
         self.fuse_acc = ops.acc_permission(T, d_in, d_out, r, r_acc, kind, x2.dtype, _mixed(x2, B))
+        # (fp32 factors over an accumulator of the compute dtype, SOW_ACC_NATIVE: no room for a packed accumulator)
         need = ops.workspace_bytes(T, d_in, d_out, r, r_acc, kind, x2.dtype, param_f32=_mixed(x2, B),
-                                   fuse_acc=self.fuse_acc) + 256
+                                   fuse_acc=self.fuse_acc, native=ops.acc_native(x2, acc_down)) + 256
         if self.ws is None or self.ws.numel() < need or self.ws.device != x2.device:
             self.ws = torch.empty(need, dtype=torch.uint8, device=x2.device)
         return kind, r_acc
@@ -283,9 +284,10 @@ class FactorBucket:
             return
         q, blk["queue"] = blk["queue"], []
         # layers of one dtype / device go together (a model holds one of each; anything else flushes in runs); the
-        # parameter dtype is part of the key: fp32 factors under autocast take the SOW_PARAM_F32 form (fp32 gradients)
+        # parameter dtype is part of the key: fp32 factors under autocast take the SOW_PARAM_F32 form (fp32 gradients), and so
+        # is the form of the accumulator next to them (native or fp32: SOW_ACC_NATIVE rides in the dtype of the call)
         def key(e):
-            return e[1][1].dtype, e[1][4].dtype, e[1][1].device
+            return e[1][1].dtype, e[1][4].dtype, e[1][1].device, _mixed(e[1][1], e[1][4]) and ops.acc_native(e[1][1], e[1][5])
 
         while q:
             k0 = key(q[0])
@@ -296,7 +298,7 @@ class FactorBucket:
             x0, B0 = run[0][1][1], run[0][1][4]
             # the run dtype of a bucket is not fixed by its parameters: an fp32 bucket runs as F32 outside autocast and as
             # BF16 / F16 | PARAM_F32 under autocast, and the reduction descriptors (workspace offsets, slab counts) depend on it
-            dt = ops._dt(x0) | (_lib.PARAM_F32 if _mixed(x0, B0) else 0)
+            dt = ops._dt(x0) | (_lib.PARAM_F32 if _mixed(x0, B0) else 0) | (_lib.ACC_NATIVE if k0[3] else 0)
             stable = [dt]
             for i, (sink, (dy2, x2, h, A, B, acc_down, acc_up, scale, kind, r_acc)) in enumerate(run):
                 T, d_in = x2.shape

@@ -205,6 +205,7 @@ class SiblingGroup:
         if cdt is not None and x.dtype not in (torch.float32, cdt):
             return False
         pdt = torch.float32 if cdt is not None else x.dtype
+        forms = set()          # fp32 factors: the accumulators a grouped call takes are all fp32 or all native (SOW_ACC_NATIVE)
         for m in self.layers:
             if m.n_iter != 1 or m.downscale_weights[0].dtype != pdt or m.upscale_weights[0].dtype != pdt or (
                     m.bias is not None and m.bias.dtype != pdt):
@@ -213,25 +214,30 @@ class SiblingGroup:
             # loaded in another precision, load_sow): the layer runs on its own and raises exactly what the ungrouped
             # call raises
             try:
-                ops.check_accumulator(x, m.in_features, m.out_features, *m._acc_pair(),
-                                      param_dtype=pdt if cdt is not None else None)
+                kind, _ = ops.check_accumulator(x, m.in_features, m.out_features, *m._acc_pair(),
+                                                param_dtype=pdt if cdt is not None else None, compute_dtype=cdt)
             except (TypeError, ValueError, RuntimeError):
                 return False
-        return True
+            if cdt is not None and kind != _lib.ACC_NONE:
+                forms.add(m.acc_downweight.dtype == torch.float32)
+        return len(forms) <= 1
 
-    def _forward_skinny(self, x: torch.Tensor):
+    def _forward_skinny(self, x: torch.Tensor, cdt: Optional[torch.dtype] = None):
         """The siblings' outputs of a generation-sized no-grad call (at most 32 flattened tokens) through ONE
         sow_forward_skinny call -- two launches for q / k / v -- or None: a set the skinny forward does not admit (any
         sibling: low-rank accumulator, wide rank, ragged widths) or that the library refuses runs the grouped path.  _PER_LAYER:
-        every sibling is admitted, but their dense accumulators are of differing kinds."""
+        every sibling is admitted, but their dense accumulators are of differing kinds.  cdt: the compute dtype of fp32 layers
+        under autocast (absent, native and quantised accumulators are admitted there; an fp32 accumulator is not)."""
         x2 = x.reshape(-1, x.shape[-1])
         if not 1 <= x2.shape[0] <= ops.SKINNY_MAX_T:
             return None
+        if cdt is not None:      # fp32 master factors under autocast: the input in the compute dtype, cast once for the set
+            x2 = autocast_input(x2.contiguous(), cdt)
         calls = []
         for m in self.layers:
             A, B = m.downscale_weights._parameters["0"], m.upscale_weights._parameters["0"]
             acc_down, acc_up = m._acc_pair()
-            if not ops.skinny_admits(x2, A, B, acc_down, acc_up, m.bias):
+            if not ops.skinny_admits(x2, A, B, acc_down, acc_up, m.bias, mixed=cdt is not None):
                 return None
             calls.append((x2, A, B, ops.skinny_acc(acc_down, acc_up), m.bias, float(m.scale)))
         if len({c[3][0].dtype if isinstance(c[3], tuple) else None for c in calls if c[3] is not None}) > 1:
@@ -257,8 +263,8 @@ class SiblingGroup:
             return None            # the layer raises on its own
         if not self.usable(x, cdt):
             return None
-        if cdt is None and not torch.is_grad_enabled():
-            ys = self._forward_skinny(x)
+        if not torch.is_grad_enabled():
+            ys = self._forward_skinny(x, cdt)
             if ys is _PER_LAYER:
                 return None
             if ys is not None:

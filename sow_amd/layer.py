@@ -245,15 +245,17 @@ class SoWLinear(nn.Module):
             # no backward will follow (eval / generate, commonsense_evaluate.py:268-287; the first pass of activation
             # checkpointing): the projection h = scale * x A is not written to HBM
             x2 = x.reshape(-1, x.shape[-1])
+            if cdt is not None:
+                x2 = autocast_input(x2.contiguous(), cdt)
             # generation-sized calls (generate(): batch x beams rows per new token): the fused skinny forward, two launches,
-            # the accumulator (or its E4M3 / MXFP4 codes: a half / a quarter of the bytes) streamed once on the whole chip.  Autocast with fp32
-            # parameters, a low-rank accumulator, a wide rank, ragged widths and a refusal from the library keep the path below.
-            if cdt is None and x2.shape[0] <= ops.SKINNY_MAX_T and ops.skinny_admits(x2, A, B, acc_down, acc_up, self.bias):
+            # the accumulator (or its E4M3 / MXFP4 codes: a half / a quarter of the bytes) streamed once on the whole chip.  Under
+            # autocast with fp32 factors it takes an absent, native (compute dtype) or quantised accumulator and rounds the
+            # factors in registers.  An fp32 accumulator under autocast, a low-rank accumulator, a wide rank, ragged widths and a
+            # refusal from the library keep the path below.
+            if x2.shape[0] <= ops.SKINNY_MAX_T and ops.skinny_admits(x2, A, B, acc_down, acc_up, self.bias, mixed=cdt is not None):
                 ys = ops.sow_forward_skinny([(x2, A, B, ops.skinny_acc(acc_down, acc_up), self.bias, float(self.scale))])
                 if ys is not None:
                     return ys[0].reshape(*x.shape[:-1], B.shape[1])
-            if cdt is not None:
-                x2 = autocast_input(x2.contiguous(), cdt)
             # every other call of a quantised layer: the existing dense path on the image
             (acc_down, acc_up), = ops.acc_operands([(acc_down, acc_up)], x2.dtype)
             y, _ = ops.sow_forward(x2, A, B, acc_down, acc_up, self.bias, float(self.scale), save_h=False,
@@ -276,14 +278,22 @@ class SoWLinear(nn.Module):
         has_down = self.acc_downweight.numel() != 0
         has_up = self.acc_upweight.numel() != 0
         scale = float(self.scale)
+        # fp32 master factors over a bf16 / f16 base: the factors fold as the forward reads them, rounded once to the
+        # accumulator's dtype, and the accumulator keeps its dtype
+        mixed = has_down and A.dtype == torch.float32 and self.acc_downweight.dtype in _HALF
+        if mixed:
+            A, B = A.to(self.acc_downweight.dtype), B.to(self.acc_downweight.dtype)
         if has_down and has_up:      # W_acc = Q R, then += scale * A B   (sow.py:137-138)
             acc = ops.gemm(self.acc_downweight.data.to(A.dtype), self.acc_upweight.data.to(A.dtype))
             ops.gemm(A, B, out=acc, alpha=scale, beta=1.0)
         elif has_down:               # dense accumulator updated in place (sow.py:139-140)
             acc = self.acc_downweight.data
-            if acc.dtype != A.dtype:
-                acc = acc.to(A.dtype)
-            ops.gemm(A, B, out=acc, alpha=scale, beta=1.0)
+            if mixed:
+                ops.gemm(A, B, out=acc, alpha=scale, beta=1.0)
+            else:
+                if acc.dtype != A.dtype:
+                    acc = acc.to(A.dtype)
+                ops.gemm(A, B, out=acc, alpha=scale, beta=1.0)
         else:
             acc = ops.gemm(A, B, alpha=scale)
 
@@ -306,7 +316,7 @@ class SoWLinear(nn.Module):
             if self.init_method == "normal_QR":
                 w = self._fresh_gaussian((self.in_features, self.out_features), self.acc_downweight.device,
                                          self.acc_downweight.dtype)
-                q, _ = ops.qr_thin(w, self.rank, need_r=False)
+                q, _ = ops.qr_thin(w, self.rank, need_r=False, out_dtype=new_down[i].dtype)   # (the factor dtype)
                 new_down[i] = q.contiguous()
             else:   # plain Gaussian re-init (sow.py:174), through the same draw hook as the QR branch
                 new_down[i] = self._fresh_gaussian(tuple(new_down[i].shape), new_down[i].device, new_down[i].dtype)

@@ -42,9 +42,17 @@ def _perm(fuse_acc) -> int:
     return int(fuse_acc)
 
 
-def _call_dtype(x2: torch.Tensor, param_f32: bool, who: str = "sow_amd", fuse_acc=False) -> Tuple[int, torch.dtype]:
-    """(C-ABI dtype code, parameter dtype) of a layer call on activations x2.  param_f32: the parameters (factors, bias,
-    accumulator) are fp32 and x2 is of the compute dtype, bf16 or f16 (SOW_PARAM_F32: mixed precision, torch.autocast).
+def acc_native(x2: torch.Tensor, acc_down: Optional[torch.Tensor]) -> bool:
+    """Whether the accumulator of a call with fp32 parameters on activations x2 is NATIVE: held in the compute dtype (x2's), so
+    that the kernels read it in place (SOW_ACC_NATIVE) -- a frozen bf16 / f16 base, or the image of a quantised one."""
+    return acc_down is not None and acc_down.numel() != 0 and acc_down.dtype == x2.dtype and x2.dtype != torch.float32
+
+
+def _call_dtype(x2: torch.Tensor, param_f32: bool, who: str = "sow_amd", fuse_acc=False,
+                acc_down: Optional[torch.Tensor] = None) -> Tuple[int, torch.dtype]:
+    """(C-ABI dtype code, parameter dtype) of a layer call on activations x2.  param_f32: the parameters (factors, bias) are
+    fp32 and x2 is of the compute dtype, bf16 or f16 (SOW_PARAM_F32: mixed precision, torch.autocast); the accumulator
+    `acc_down` is fp32 as well (packed with them) or native (acc_native: SOW_ACC_NATIVE is set, it is read in place).
     fuse_acc: the call's permission (_perm: SOW_FUSE_ACC or SOW_FUSE_ACC_DEEP; bf16 / f16 parameters only: the library
     ignores it next to SOW_PARAM_F32, so it is not passed there)."""
     dt = _dt(x2)
@@ -52,7 +60,7 @@ def _call_dtype(x2: torch.Tensor, param_f32: bool, who: str = "sow_amd", fuse_ac
         return (dt | _perm(fuse_acc) if dt != _lib.F32 else dt), x2.dtype
     if dt == _lib.F32:
         raise TypeError(f"{who}: fp32 parameters need bfloat16 or float16 activations, got {x2.dtype}")
-    return dt | _lib.PARAM_F32, torch.float32
+    return dt | _lib.PARAM_F32 | (_lib.ACC_NATIVE if acc_native(x2, acc_down) else 0), torch.float32
 
 
 def _need_gpu(*ts: Optional[torch.Tensor]) -> torch.device:
@@ -146,19 +154,23 @@ def acc_kind(acc_down: Optional[torch.Tensor], acc_up: Optional[torch.Tensor]) -
 
 
 def check_accumulator(x2: torch.Tensor, d_in: int, d_out: int, acc_down, acc_up, who: str = "sow_amd",
-                      param_dtype: Optional[torch.dtype] = None) -> Tuple[int, int]:
+                      param_dtype: Optional[torch.dtype] = None, compute_dtype: Optional[torch.dtype] = None) -> Tuple[int, int]:
     """(acc_kind, r_acc) after the checks every entry point applies before raw pointers reach the kernels: the
     accumulator has the input's dtype (TypeError), the shapes of its kind (ValueError), lives on the input's device and is
     dense row-major.  A mismatch that got through would be read as the wrong type -- silent garbage for an fp32
     accumulator under bf16 inputs, an out-of-bounds device read the other way round.  `param_dtype`: the parameter dtype
-    of the call when it is not the input's (fp32 under SOW_PARAM_F32)."""
+    of the call when it is not the input's (fp32 under SOW_PARAM_F32).  The accumulator next to fp32 parameters has one of
+    three forms: fp32 (packed with the factors by every call), the compute dtype (native, read in place: SOW_ACC_NATIVE), or
+    E4M3 / MXFP4 codes (run on their image in the compute dtype, or streamed by the skinny forward).  `compute_dtype`: the
+    compute dtype when x2 is not of it yet (an fp32 input under autocast that the call casts first)."""
     kind = acc_kind(acc_down, acc_up)
+    cdt = x2.dtype if compute_dtype is None else compute_dtype
     if kind == _lib.ACC_NONE:
         return kind, 0
     r_acc = 0
     if kind == _lib.ACC_DENSE_FP8:
-        if param_dtype is not None or x2.dtype not in (torch.bfloat16, torch.float16):
-            raise TypeError(f"{who}: an E4M3 accumulator runs with bfloat16 or float16 inputs and parameters, got {x2.dtype}"
+        if param_dtype not in (None, torch.float32) or cdt not in (torch.bfloat16, torch.float16):
+            raise TypeError(f"{who}: an E4M3 accumulator runs with bfloat16 or float16 inputs and parameters, got {cdt}"
                             + ("" if param_dtype is None else f" inputs and {param_dtype} parameters"))
         if acc_up is None or acc_up.dtype != torch.int8:
             raise TypeError(f"{who}: an E4M3 accumulator comes with int8 column exponents")
@@ -170,8 +182,8 @@ def check_accumulator(x2: torch.Tensor, d_in: int, d_out: int, acc_down, acc_up,
                 raise RuntimeError(f"{who}: the accumulator is on {t.device}, the input on {x2.device}")
         return kind, 0
     if kind == _lib.ACC_DENSE_FP4:
-        if param_dtype is not None or x2.dtype not in (torch.bfloat16, torch.float16):
-            raise TypeError(f"{who}: an MXFP4 accumulator runs with bfloat16 or float16 inputs and parameters, got {x2.dtype}"
+        if param_dtype not in (None, torch.float32) or cdt not in (torch.bfloat16, torch.float16):
+            raise TypeError(f"{who}: an MXFP4 accumulator runs with bfloat16 or float16 inputs and parameters, got {cdt}"
                             + ("" if param_dtype is None else f" inputs and {param_dtype} parameters"))
         if acc_up is None or acc_up.dtype != torch.uint8:
             raise TypeError(f"{who}: an MXFP4 accumulator comes with uint8 (E8M0) block scales")
@@ -184,10 +196,13 @@ def check_accumulator(x2: torch.Tensor, d_in: int, d_out: int, acc_down, acc_up,
                 raise RuntimeError(f"{who}: the accumulator is on {t.device}, the input on {x2.device}")
         return kind, 0
     want = x2.dtype if param_dtype is None else param_dtype
+    if param_dtype == torch.float32 and acc_down.dtype == cdt and cdt in (torch.bfloat16, torch.float16):
+        want = cdt      # native: both tensors of the accumulator in the compute dtype
     if acc_down.dtype != want or (kind == _lib.ACC_LOWRANK and acc_up.dtype != want):
         bad = acc_down.dtype if acc_down.dtype != want else acc_up.dtype
         raise TypeError(f"{who}: dtype mismatch, x is {x2.dtype} but the accumulator is {bad}"
-                        + ("" if param_dtype is None else f" (parameters must be {param_dtype})"))
+                        + ("" if param_dtype is None else f" (parameters must be {param_dtype}; the accumulator {param_dtype} "
+                                                           f"or the compute dtype)"))
     if kind == _lib.ACC_DENSE and tuple(acc_down.shape) != (d_in, d_out):
         raise ValueError(f"{who}: dense accumulator must be [in_features, out_features]")
     if kind == _lib.ACC_LOWRANK:
@@ -443,15 +458,16 @@ def sow_forward(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, ac
     e.g. the reload + generate loop of commonsense_evaluate.py:268-287): the projection is not written to HBM and None
     is returned in its place (every rank except r <= 64 with a dense accumulator, whose fused kernels write it as scratch;
     a wide layer off the fused chain keeps its intermediate in the forward workspace).
-    param_f32: A, B, bias and the accumulator are fp32, x2 is bf16 / f16 (the compute dtype); the kernels round the
-    parameters once to x2's dtype (include/sow_amd.h: SOW_PARAM_F32) and y is of x2's dtype.
+    param_f32: A, B and bias are fp32, x2 is bf16 / f16 (the compute dtype); the kernels round the
+    parameters once to x2's dtype (include/sow_amd.h: SOW_PARAM_F32) and y is of x2's dtype.  The accumulator is fp32 too
+    (rounded with them at every call) or of x2's dtype (native: read in place, SOW_ACC_NATIVE).
     fuse_acc: the call's permission (True or _lib.FUSE_ACC: SOW_FUSE_ACC; _lib.FUSE_ACC_DEEP: SOW_FUSE_ACC_DEEP) -- a low-rank
     accumulator and the live term in one pass where the library admits the call; the same result as without it everywhere
     else."""
     lib = _lib.load()
     dev = _need_gpu(x2, A, B, acc_down if acc_down is not None and acc_down.numel() else None,
                     acc_up if acc_up is not None and acc_up.numel() else None, bias)
-    dt, pdt = _call_dtype(x2, param_f32, fuse_acc=fuse_acc)
+    dt, pdt = _call_dtype(x2, param_f32, fuse_acc=fuse_acc, acc_down=acc_down)
     for name, t in (("A", A), ("B", B), ("bias", bias)):
         if t is not None and t.dtype != pdt:
             raise TypeError(f"sow_amd: dtype mismatch, x is {x2.dtype} but {name} is {t.dtype}"
@@ -537,11 +553,12 @@ def skinny_acc(acc_down, acc_up):
     return (acc_down, acc_up) if kind in (_lib.ACC_DENSE_FP8, _lib.ACC_DENSE_FP4) else acc_down
 
 
-def skinny_admits(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, acc_up, bias) -> bool:
+def skinny_admits(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, acc_up, bias, mixed: bool = False) -> bool:
     """Whether a no-grad module call on the flattened input x2 may go to sow_forward_skinny: a bf16 / f16 call of at most 32
-    tokens with parameters of the input's dtype, a dense accumulator (in that dtype or as E4M3 codes) or none, and a shape the
-    library admits and the dispatch rule keeps.  False sends the caller to the existing path, which raises whatever it raises
-    today."""
+    tokens with parameters of the input's dtype -- or fp32 factors and bias (autocast with master factors: SOW_PARAM_F32 |
+    SOW_ACC_NATIVE, the kernels round them in registers) --, a dense accumulator (in the input's dtype or as E4M3 / MXFP4 codes)
+    or none, and a shape the library admits and the dispatch rule keeps.  False sends the caller to the existing path, which
+    raises whatever it raises today.  mixed: the call runs under autocast with fp32 factors and x2 already of the compute dtype."""
     dt = _DT.get(x2.dtype)
     if dt is None or dt == _lib.F32 or not x2.is_cuda or x2.dim() != 2 or not 1 <= x2.shape[0] <= SKINNY_MAX_T:
         return False
@@ -552,9 +569,12 @@ def skinny_admits(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, 
     r, d_out = B.shape
     if tuple(A.shape) != (d_in, r) or (kind != _lib.ACC_NONE and acc_logical_shape(acc_down) != (d_in, d_out)):
         return False
-    for t in (A, B, bias, acc_down if kind == _lib.ACC_DENSE else None):
-        if t is not None and (t.dtype != x2.dtype or t.device != x2.device):
+    pdt = torch.float32 if mixed else x2.dtype      # fp32 master factors (mixed: under autocast), or parameters of the input's dtype
+    for t, want in ((A, pdt), (B, pdt), (bias, pdt), (acc_down if kind == _lib.ACC_DENSE else None, x2.dtype)):
+        if t is not None and (t.dtype != want or t.device != x2.device):
             return False
+    if pdt != x2.dtype:
+        dt |= _lib.PARAM_F32 | _lib.ACC_NATIVE
     if kind == _lib.ACC_DENSE_FP8:
         if (acc_up is None or acc_up.dtype != torch.int8 or tuple(acc_up.shape) != (d_out,) or acc_down.device != x2.device
                 or acc_up.device != x2.device or not skinny_fp8_pays(T, d_in, d_out)):
@@ -569,7 +589,8 @@ def skinny_admits(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, 
 def sow_forward_skinny(layers) -> Optional[list]:
     """y_i of n <= 16 independent generation-sized layer calls (T_i <= 32 tokens) in two launches (include/sow_amd.h:
     sow_forward_skinny).  `layers`: one (x2, A, B, acc_down, bias, scale) per layer -- x2 [T, d_in] bf16 / f16, acc_down the
-    dense accumulator, the (codes, exponents) pair of an E4M3 one, or None.  Returns the list of outputs, or None when the library refuses the set (nothing was launched:
+    dense accumulator, the (codes, exponents) pair of an E4M3 one, or None.  A, B and bias are of x2's dtype, or fp32 in every
+    layer of the call (SOW_PARAM_F32 | SOW_ACC_NATIVE: rounded once in registers, the accumulator stays of x2's dtype).  Returns the list of outputs, or None when the library refuses the set (nothing was launched:
     the caller runs sow_forward / LayerGroup instead)."""
     lib = _lib.load()
     n = len(layers)
@@ -579,6 +600,9 @@ def sow_forward_skinny(layers) -> Optional[list]:
         return None
     x0 = layers[0][0]
     dt = _dt(x0)
+    pdt = x0.dtype
+    if layers[0][1].dtype == torch.float32 and dt != _lib.F32:      # fp32 master factors over a native accumulator
+        pdt, dt = torch.float32, dt | _lib.PARAM_F32 | _lib.ACC_NATIVE
     keep, sizes, total = [], [], 0
     for x2, A, B, acc_down, bias, scale in layers:
         exps = None
@@ -591,9 +615,10 @@ def sow_forward_skinny(layers) -> Optional[list]:
             elif acc_down.dtype != FP8 or exps.dtype != torch.int8 or tuple(exps.shape) != (acc_down.shape[-1],):
                 raise TypeError("sow_amd.sow_forward_skinny: an E4M3 accumulator is (float8_e4m3fn codes, int8 exponents)")
         dev = _need_gpu(x2, A, B, acc_down, exps, bias)
-        if dev != x0.device or any(t is not None and t.dtype != x0.dtype
-                                   for t in (x2, A, B, acc_down if exps is None else None, bias)):
-            raise TypeError("sow_amd.sow_forward_skinny: all tensors of a call share one dtype and one device")
+        if dev != x0.device or any(t is not None and t.dtype != x0.dtype for t in (x2, acc_down if exps is None else None)) or any(
+                t is not None and t.dtype != pdt for t in (A, B, bias)):
+            raise TypeError("sow_amd.sow_forward_skinny: the inputs and dense accumulators of a call share one dtype, its factors "
+                            "and biases one dtype (the inputs', or float32), and all tensors one device")
         T, d_in = x2.shape
         r, d_out = B.shape
         if tuple(A.shape) != (d_in, r) or (acc_down is not None and acc_logical_shape(acc_down) != (d_in, d_out)) or (
@@ -630,8 +655,10 @@ def sow_forward_skinny(layers) -> Optional[list]:
 
 
 def workspace_bytes(T: int, d_in: int, d_out: int, r: int, r_acc: int, kind: int, dtype: torch.dtype,
-                    param_f32: bool = False, fuse_acc=False) -> int:
-    flags = _lib.PARAM_F32 if param_f32 else (_perm(fuse_acc) if dtype != torch.float32 else 0)
+                    param_f32: bool = False, fuse_acc=False, native: bool = False) -> int:
+    """native: the accumulator next to fp32 parameters is of the compute dtype (acc_native): no room for its packed copy."""
+    flags = (_lib.PARAM_F32 | (_lib.ACC_NATIVE if native and kind != _lib.ACC_NONE else 0) if param_f32
+             else (_perm(fuse_acc) if dtype != torch.float32 else 0))
     return _workspace_bytes(_lib.load(), T, d_in, d_out, r, r_acc, kind, _DT[dtype] | flags)
 
 
@@ -649,7 +676,7 @@ def sow_backward(dy2: torch.Tensor, x2: torch.Tensor, h: torch.Tensor, A: torch.
     workspace_bytes(..., fuse_acc=the same value), a smaller one makes the call run the unflagged kernels."""
     lib = _lib.load()
     dev = _need_gpu(dy2, x2, h, A, B)
-    dt, pdt = _call_dtype(x2, param_f32, fuse_acc=fuse_acc)
+    dt, pdt = _call_dtype(x2, param_f32, fuse_acc=fuse_acc, acc_down=acc_down)
     if dy2.dtype != x2.dtype:
         raise TypeError(f"sow_amd: grad dtype {dy2.dtype} differs from input dtype {x2.dtype}")
     if param_f32 and (A.dtype != pdt or B.dtype != pdt):
@@ -693,21 +720,23 @@ class LayerCall:
         dev = _need_gpu(x2, A, B, bias, y, h, dy2, dx, workspace)
         # param_f32: fp32 A, B, bias, accumulator and gradients, activations of the compute dtype (SOW_PARAM_F32)
         # fuse_acc: the call's permission (_perm); it rides in the dtype, so the workspace queries below are the flagged ones
-        self.dtype, pdt = _call_dtype(x2, param_f32, "sow_amd.LayerCall", fuse_acc=fuse_acc)
+        self.dtype, pdt = _call_dtype(x2, param_f32, "sow_amd.LayerCall", fuse_acc=fuse_acc, acc_down=acc_down)
+        adt = x2.dtype if self.dtype & _lib.ACC_NATIVE else pdt      # a native accumulator is of the compute dtype
         T, d_in = x2.shape
         r, d_out = B.shape
         # the same accumulator checks as the single-layer entry point (ops.sow_forward): same exceptions for the same input
         kind, _ = check_accumulator(x2, d_in, d_out, acc_down, acc_up, "sow_amd.LayerCall", param_dtype=pdt if param_f32 else None)
         for name, t, want in (("x", x2, x2.dtype), ("A", A, pdt), ("B", B, pdt), ("bias", bias, pdt), ("y", y, x2.dtype),
                               ("dy", dy2, x2.dtype), ("dx", dx, x2.dtype),
-                              ("acc_down", acc_down if kind != _lib.ACC_NONE else None, pdt),
-                              ("acc_up", acc_up if kind == _lib.ACC_LOWRANK else None, pdt)):
+                              ("acc_down", acc_down if kind != _lib.ACC_NONE else None, adt),
+                              ("acc_up", acc_up if kind == _lib.ACC_LOWRANK else None, adt)):
             if t is not None and (not t.is_contiguous() or t.dtype != want):
                 raise ValueError(f"sow_amd.LayerCall: {name} must be contiguous and of the "
                                  + ("input" if want == x2.dtype else "parameter") + " dtype")
         if A.shape != (d_in, r):
             raise ValueError("sow_amd.LayerCall: factor shapes do not match the input")
         self.device, self.kind = dev, kind
+        self.legacy_acc = bool(param_f32) and kind != _lib.ACC_NONE and not self.dtype & _lib.ACC_NATIVE   # an fp32 accumulator
         self.y = y if y is not None else torch.empty((T, d_out), dtype=x2.dtype, device=dev)
         # save_h = False (forward_only calls that no backward follows): h_save = NULL, the projection stays on chip --
         # except with a dense accumulator, whose single-launch kernels need the buffer (as in sow_forward)
@@ -753,8 +782,14 @@ class LayerGroup:
     def __init__(self, calls: Sequence[LayerCall]):
         if not calls:
             raise ValueError("empty group")
-        if len({c.dtype & ~_PERMS for c in calls}) != 1 or len({c.device for c in calls}) != 1:
+        if len({c.dtype & ~(_PERMS | _lib.ACC_NATIVE) for c in calls}) != 1 or len({c.device for c in calls}) != 1:
             raise ValueError("sow_amd.LayerGroup: all layers must share dtype and device")
+        # SOW_ACC_NATIVE rides in the dtype of the whole C call: layers without accumulator go with either form, but a native
+        # accumulator and an fp32 one cannot share a call
+        native = _lib.ACC_NATIVE if any(c.dtype & _lib.ACC_NATIVE for c in calls) else 0
+        if native and any(c.legacy_acc for c in calls):
+            raise ValueError("sow_amd.LayerGroup: fp32 parameters -- the accumulators of one group are all fp32 or all of the "
+                             "compute dtype")
         self.calls = list(calls)
         self.arr = (_lib.LayerArgs * len(calls))(*[c.args for c in calls])
         # A permission rides in the dtype of the whole C call and belongs to each LayerCall: a group whose layers hold
@@ -764,7 +799,8 @@ class LayerGroup:
         self._perms = [c.dtype & _PERMS for c in calls]
         mixed = len(set(self._perms)) > 1
         self._fused = [p == _lib.FUSE_ACC for p in self._perms] if mixed else None   # None: one value, one C call
-        self.dtype, self.device = calls[0].dtype & ~_PERMS | (0 if mixed else self._perms[0]), calls[0].device
+        self.dtype = calls[0].dtype & ~(_PERMS | _lib.ACC_NATIVE) | native | (0 if mixed else self._perms[0])
+        self.device = calls[0].device
 
     @classmethod
     def from_args(cls, arr, n: int, dtype: int, device, keep=None) -> "LayerGroup":
@@ -888,7 +924,7 @@ class DeferredReduce:
         r, d_out = B.shape
         kind = acc_kind(acc_down, acc_up)
         r_acc = acc_down.shape[1] if kind == _lib.ACC_LOWRANK else 0
-        dt = _call_dtype(x2, param_f32)[0]
+        dt = _call_dtype(x2, param_f32, acc_down=acc_down)[0]
         key = (_ptr(dA), _ptr(dB), _ptr(dbias), T, d_in, d_out, r, r_acc, kind, float(grad_beta), dt, _ptr(workspace))
         i = self._pos
         self._pos += 1

@@ -131,6 +131,28 @@ def load_sow(model, checkpoint_path):
             obj.data.copy_(tensor.data)
 
 
+def master_factors(model, dtype: torch.dtype = torch.float32) -> int:
+    """Cast the trainable part of every SoWLinear -- the factors and the bias -- to `dtype` and leave the frozen part alone:
+    accumulators keep their dtype, quantised ones their codes and scales.  With dtype = float32 on a bf16 / f16 model this is
+    the mixed-precision arrangement (fp32 master factors over a half-precision or 4- / 8-bit base, as PEFT / QLoRA keep it):
+    under torch.autocast the layers then run with SOW_PARAM_F32 | SOW_ACC_NATIVE -- the factors rounded once per call, the
+    accumulator read where it lies.  The step after prepare_sow(config with decompose="keep") on a half-precision model, and
+    after quantize_accumulators; before the optimizer and FactorBucket are built (the Parameter objects stay, their .data is
+    replaced).  Returns the number of layers touched."""
+    n = 0
+    for m in model.modules():
+        if not isinstance(m, SoWLinear):
+            continue
+        params = [*m.downscale_weights, *m.upscale_weights] + ([m.bias] if m.bias is not None else [])
+        for p in params:
+            if p.dtype != dtype:
+                p.data = p.data.to(dtype)
+                if p.grad is not None:
+                    p.grad = None
+        n += 1
+    return n
+
+
 _ACC_STREAMS: dict = {}
 _ACC_WIDTH = 8
 
