@@ -1,0 +1,83 @@
+"""Where a quantised-accumulator format is described: one record per format, read by ops.py (checks, shapes, C entry points,
+dispatch rule) and acc_quant.py (the quantiser).  What adding a format takes is listed in DESIGN.md section 4.5c."""
+from typing import Callable, NamedTuple, Optional, Tuple
+
+import torch
+
+from . import _lib
+
+SKINNY_MAX_T = 32          # include/sow_amd.h: sow_forward_skinny admits at most 32 tokens per layer
+
+
+def skinny_fp8_pays(T: int, d_in: int, d_out: int) -> bool:
+    """The measured dispatch rule for an E4M3 accumulator (profiles/fp8_acc.txt), the one place that
+    encodes it: the calls at which streaming the codes (q) is faster than the image pass followed by the bf16 skinny forward
+    on the image (d).  Measured (us, r = 50, T = 4 / 32): 4096->4096 25.4 / 32.9 against 40.8 / 44.2, 4096->11008 37.6 / 47.4
+    against 67.4 / 92.6, 11008->4096 37.4 / 47.4 against 67.8 / 83.7, 512->512 17.7 / 19.8 against 20.5 / 22.2, q + k + v of
+    4096->4096 39.9 / 59.3 against 73.7 / 88.0; q / d lies between 0.47 and 0.89 in all 48 rows (T = 1, 4, 16, 32; r = 8, 50):
+    the rule excludes nothing.  NOT measured: f16, widths above 11008."""
+    return 1 <= T <= SKINNY_MAX_T
+
+
+def skinny_fp4_pays(T: int, d_in: int, d_out: int) -> bool:
+    """The measured dispatch rule for an MXFP4 accumulator (profiles/fp4_acc.txt), the one place that
+    encodes it: the calls at which streaming the codes (q4) is faster than the image pass followed by the bf16 skinny forward on
+    the image (d4) by more than the run-to-run spread of the row.  Measured (us, r = 50, T = 4 / 32; +- the larger spread
+    of the two variants): 4096->4096 21.1 / 29.9 against 39.7 / 43.0 (+- 2.5 / 2.6), 4096->11008 24.3 / 38.4 against 62.9 / 90.1
+    (+- 1.8 / 2.8), 11008->4096 26.5 / 37.4 against 62.3 / 81.0 (+- 1.6 / 1.9), 512->512 14.5 / 16.3 against 18.3 / 19.2 (+- 1.5 / 0.3),
+    q + k + v of 4096->4096 33.5 / 52.4 against 70.3 / 84.5 (+- 0.7 / 1.0); q4 / d4 lies between 0.37 and 0.85 in all 48 rows (T = 1,
+    4, 16, 32; r = 8, 50) and the gap exceeds the spread in each: the rule excludes nothing.  q4 is never slower than the E4M3
+    codes (q4 / q8 0.68 ... 1.00); it loses to the bf16 accumulator at 4096->4096, T = 32, r = 8 (29.1 against 25.4) and by up to
+    10 % on 512-wide layers at r = 8, which does not enter the rule: the kind buys memory there.  NOT measured: f16, widths above
+    11008."""
+    return 1 <= T <= SKINNY_MAX_T
+
+
+class AccFormat(NamedTuple):
+    name: str                       # the fmt= argument of quantize_accumulators
+    label: str                      # the name used in messages
+    kind: int                       # include/sow_amd.h: SOW_ACC_DENSE_*
+    code_dtype: torch.dtype
+    scale_dtype: torch.dtype
+    rows_per_code: int              # rows of one column packed into a code element
+    block: Optional[int]            # rows of one column per scale; None: one scale per column
+    d_in_multiple: int              # the widths quantize_accumulators converts and the streaming kernels admit
+    d_out_multiple: int
+    workspace_query: str            # C entry (T, d_in, d_out, r, dtype) -> bytes of the skinny forward on the codes
+    dequantize: str                 # C entry that writes the image
+    exp_range: dict                 # compute dtype -> the (lo, hi) clamp of a scale's exponent
+    scale_bias: int                 # a scale is stored as its exponent + this
+    code_max: float                 # the largest code magnitude
+    frexp: Tuple[float, int]        # code_max = threshold * 2^offset with threshold in [0.5, 1)
+    pays: Callable[[int, int, int], bool]      # the measured rule that admits the streaming path
+
+    def code_shape(self, d_in, d_out): return (d_in // self.rows_per_code, d_out)      # (of a [d_in, d_out] matrix, as scale_shape)
+    def scale_shape(self, d_in, d_out): return (d_out,) if self.block is None else (d_in // self.block, d_out)
+    def logical_shape(self, codes): return (codes.shape[0] * self.rows_per_code, codes.shape[1])
+
+    def scales_fit(self, scales, d_in, d_out):
+        """`scales` are this format's scales of a [d_in, d_out] matrix (written out, one .shape read: it runs on every generated token)."""
+        b = self.block
+        return (scales.dtype == self.scale_dtype and (b is None or d_in % b == 0)
+                and tuple(scales.shape) == ((d_out,) if b is None else (d_in // b, d_out)))
+
+    def well_formed(self, codes, scales):
+        """(codes, scales) are a pair of this format: 2-D codes, and the scales of the matrix they stand for."""
+        cs = codes.shape
+        return len(cs) == 2 and self.scales_fit(scales, cs[0] * self.rows_per_code, cs[1])
+
+
+FORMATS = {f.name: f for f in (
+    # W^[k, n] = codes[k, n] * 2^scales[n]
+    AccFormat(name="fp8_e4m3", label="E4M3", kind=_lib.ACC_DENSE_FP8, code_dtype=torch.float8_e4m3fn, scale_dtype=torch.int8,
+              rows_per_code=1, block=None, d_in_multiple=8, d_out_multiple=8, workspace_query="sow_forward_skinny_fp8_workspace_bytes",
+              dequantize="sow_acc_dequantize", exp_range={torch.bfloat16: (-117, 119), torch.float16: (-15, 7)}, scale_bias=0,
+              code_max=448.0, frexp=(0.875, 9), pays=skinny_fp8_pays),
+    # W^[k, n] = e2m1(nibble k % 2 of codes[k / 2, n]) * 2^(scales[k / 32, n] - 127): E8M0 scale bytes
+    AccFormat(name="mxfp4", label="MXFP4", kind=_lib.ACC_DENSE_FP4, code_dtype=torch.uint8, scale_dtype=torch.uint8,
+              rows_per_code=2, block=32, d_in_multiple=32, d_out_multiple=8, workspace_query="sow_forward_skinny_fp4_workspace_bytes",
+              dequantize="sow_acc_dequantize_fp4", exp_range={torch.bfloat16: (-125, 125), torch.float16: (-13, 13)}, scale_bias=127,
+              code_max=6.0, frexp=(0.75, 3), pays=skinny_fp4_pays),
+)}
+BY_CODE_DTYPE = {f.code_dtype: f for f in FORMATS.values()}
+BY_KIND = {f.kind: f for f in FORMATS.values()}

@@ -402,12 +402,12 @@ static void normalise_acc(sow_layer_args& L) {
   if (L.acc_kind != SOW_ACC_LOWRANK) L.r_acc = 0, L.acc_up = nullptr;
   if (L.acc_kind == SOW_ACC_NONE) L.acc_down = nullptr;
 }
-// A quantised accumulator (SOW_ACC_DENSE_FP8, SOW_ACC_DENSE_FP4) is read by sow_forward_skinny only: every other layer entry point asks here first,
-// before any other check, launch or dereference
-static inline bool any_fp8_acc(const sow_layer_args* layers, int n) {
+// A quantised accumulator (codes and scales: acc_is_codes) is read by sow_forward_skinny only: every other layer entry point asks
+// here first, before any other check, launch or dereference
+static inline bool any_codes_acc(const sow_layer_args* layers, int n) {
   if (layers)
     for (int i = 0; i < n; ++i)
-      if (layers[i].acc_kind == SOW_ACC_DENSE_FP8 || layers[i].acc_kind == SOW_ACC_DENSE_FP4) return true;
+      if (acc_is_codes(layers[i].acc_kind)) return true;
   return false;
 }
 static inline WsPlan plan_of(const sow_layer_args& L, int cd, int perm = 0) {
@@ -763,7 +763,7 @@ size_t sow_reduce_desc_bytes(void) { return sizeof(ReduceParams); }
 int sow_backward_reduce_desc(void* dA, void* dB, void* dbias, int64_t T, int d_in, int d_out, int r_live, int r_acc,
                              int acc_kind, float grad_beta, int dtype, void* workspace, size_t workspace_bytes, void* desc_out,
                              int* blocks_out) {
-  if (acc_kind == SOW_ACC_DENSE_FP8 || acc_kind == SOW_ACC_DENSE_FP4) return SOW_ERR_UNSUPPORTED;
+  if (acc_is_codes(acc_kind)) return SOW_ERR_UNSUPPORTED;
   const Dtype f = decode_dtype(dtype);   // the descriptor is the same with fp32 gradients: sow_reduce_batch picks the output type
   if (!f.layer_ok()) return SOW_ERR_DTYPE;
   if (T <= 0 || d_in <= 0 || d_out <= 0 || r_live <= 0) return SOW_ERR_SHAPE;
@@ -798,7 +798,7 @@ int sow_reduce_batch(const void* descs, const int* starts, int n, int total_bloc
 
 size_t sow_forward_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, int dtype) {
   const Dtype f = decode_dtype(dtype);
-  if (acc_kind == SOW_ACC_DENSE_FP8 || acc_kind == SOW_ACC_DENSE_FP4) return 0;
+  if (acc_is_codes(acc_kind)) return 0;
   if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0 || !f.layer_ok()) return 0;
   if (f.param_f32) {   // the forward's own scratch (if any) followed by the packed parameters (pack_layer)
     const size_t own = sow_forward_workspace_bytes(T, d_in, d_out, r_live, r_acc, acc_kind, f.cd);
@@ -814,7 +814,7 @@ size_t sow_forward_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, i
 
 size_t sow_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, int dtype) {
   const Dtype f = decode_dtype(dtype);
-  if (acc_kind == SOW_ACC_DENSE_FP8 || acc_kind == SOW_ACC_DENSE_FP4) return 0;
+  if (acc_is_codes(acc_kind)) return 0;
   if (T < 0 || d_in <= 0 || d_out <= 0 || r_live <= 0 || !f.layer_ok()) return 0;
   const size_t pack = f.param_f32 ? pack_bytes(d_in, d_out, r_live, acc_kind == SOW_ACC_LOWRANK ? r_acc : 0, acc_kind, f.native) : 0;
   return plan_ws(T, d_in, d_out, r_live, r_acc, acc_kind, f.cd, f.perm()).total + pack + 256;
@@ -869,7 +869,7 @@ static int forward_impl(const sow_layer_args& L, int dtype, int perm, hipStream_
 int sow_forward(const void* x, const void* A, const void* B, const void* acc_down, const void* acc_up, const void* bias,
                 void* y, void* h_save, int64_t T, int d_in, int d_out, int r_live, int r_acc, int acc_kind, float scale,
                 int dtype, void* workspace, size_t workspace_bytes, void* stream) {
-  if (acc_kind == SOW_ACC_DENSE_FP8 || acc_kind == SOW_ACC_DENSE_FP4) return SOW_ERR_UNSUPPORTED;
+  if (acc_is_codes(acc_kind)) return SOW_ERR_UNSUPPORTED;
   const Dtype f = decode_dtype(dtype);
   if (!f.layer_ok()) return SOW_ERR_DTYPE;
   sow_layer_args L = single_layer(x, A, B, acc_down, acc_up, bias, y, h_save, nullptr, nullptr, nullptr, nullptr, nullptr, T, d_in,
@@ -994,7 +994,7 @@ int sow_backward_ex(const void* dy, const void* x, const void* h_save, const voi
                     const void* acc_up, void* dx, void* dA, void* dB, void* dbias, int64_t T, int d_in, int d_out,
                     int r_live, int r_acc, int acc_kind, float scale, float grad_beta, int dtype, void* workspace,
                     size_t workspace_bytes, int phases, void* stream) {
-  if (acc_kind == SOW_ACC_DENSE_FP8 || acc_kind == SOW_ACC_DENSE_FP4) return SOW_ERR_UNSUPPORTED;
+  if (acc_is_codes(acc_kind)) return SOW_ERR_UNSUPPORTED;
   const Dtype f = decode_dtype(dtype);
   sow_layer_args L = single_layer(x, A, B, acc_down, acc_up, nullptr, nullptr, const_cast<void*>(h_save), dy, dx, dA, dB, dbias, T,
                                   d_in, d_out, r_live, r_acc, acc_kind, scale, grad_beta, workspace, workspace_bytes);
@@ -1124,7 +1124,7 @@ static int forward_group_impl(const sow_layer_args* layers, int n, int dtype, in
 }
 
 int sow_forward_group(const sow_layer_args* layers, int n, int dtype, void* stream) {
-  if (any_fp8_acc(layers, n)) return SOW_ERR_UNSUPPORTED;
+  if (any_codes_acc(layers, n)) return SOW_ERR_UNSUPPORTED;
   const Dtype f = decode_dtype(dtype);
   if (!f.layer_ok()) return SOW_ERR_DTYPE;
   if (!f.param_f32 || n <= 0 || !layers) return forward_group_impl(layers, n, f.cd, f.perm(), (hipStream_t)stream);
@@ -1138,8 +1138,7 @@ int sow_forward_group(const sow_layer_args* layers, int n, int dtype, void* stre
 // compute dtype, as E4M3 codes or as MXFP4 codes) or none, r_live <= 64, widths multiples of 8 (d_in of 32 for MXFP4: whole blocks).
 static bool skinny_shape_ok(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype) {
   return (dtype == SOW_BF16 || dtype == SOW_F16) && T >= 1 && T <= 32 && d_in > 0 && d_out > 0 && r_live >= 1 && r_live <= 64 &&
-         (acc_kind == SOW_ACC_DENSE || acc_kind == SOW_ACC_DENSE_FP8 || acc_kind == SOW_ACC_DENSE_FP4 || acc_kind == SOW_ACC_NONE) &&
-         d_in % 8 == 0 && d_out % 8 == 0 && (acc_kind != SOW_ACC_DENSE_FP4 || d_in % 32 == 0);
+         acc_kind_known(acc_kind) && acc_kind != SOW_ACC_LOWRANK && d_in % 8 == 0 && d_out % 8 == 0 && (acc_kind != SOW_ACC_DENSE_FP4 || d_in % 32 == 0);
 }
 struct SkWs {
   size_t off_py, off_ph, total;
@@ -1154,23 +1153,21 @@ static SkWs skinny_ws(int64_t T, int d_in, int d_out, int acc_kind) {
   return w;
 }
 
-// (an E4M3 and an MXFP4 accumulator have queries of their own: this one keeps answering 0 for every kind value it answered 0 for before)
-size_t sow_forward_skinny_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype) {
+static size_t skinny_ws_query(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype) {
   const Dtype f = decode_dtype(dtype);
-  if ((f.param_f32 && !f.native) || acc_kind == SOW_ACC_DENSE_FP8 || acc_kind == SOW_ACC_DENSE_FP4 || !skinny_shape_ok(T, d_in, d_out, r_live, acc_kind, f.cd)) return 0;
+  if ((f.param_f32 && !f.native) || !skinny_shape_ok(T, d_in, d_out, r_live, acc_kind, f.cd)) return 0;
   return skinny_ws(T, d_in, d_out, acc_kind).total;
 }
 
-size_t sow_forward_skinny_fp8_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int dtype) {
-  const Dtype f = decode_dtype(dtype);
-  if ((f.param_f32 && !f.native) || !skinny_shape_ok(T, d_in, d_out, r_live, SOW_ACC_DENSE_FP8, f.cd)) return 0;
-  return skinny_ws(T, d_in, d_out, SOW_ACC_DENSE_FP8).total;
+// (a quantised accumulator has the query of its format: this one keeps answering 0 for every kind value it answered 0 for before)
+size_t sow_forward_skinny_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype) {
+  return acc_is_codes(acc_kind) ? 0 : skinny_ws_query(T, d_in, d_out, r_live, acc_kind, dtype);
 }
-
+size_t sow_forward_skinny_fp8_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int dtype) {
+  return skinny_ws_query(T, d_in, d_out, r_live, SOW_ACC_DENSE_FP8, dtype);
+}
 size_t sow_forward_skinny_fp4_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int dtype) {
-  const Dtype f = decode_dtype(dtype);
-  if ((f.param_f32 && !f.native) || !skinny_shape_ok(T, d_in, d_out, r_live, SOW_ACC_DENSE_FP4, f.cd)) return 0;
-  return skinny_ws(T, d_in, d_out, SOW_ACC_DENSE_FP4).total;
+  return skinny_ws_query(T, d_in, d_out, r_live, SOW_ACC_DENSE_FP4, dtype);
 }
 
 // The checks of this entry point are its own (not check_layer): stricter, and every layer is checked before the first
@@ -1186,25 +1183,23 @@ int sow_forward_skinny(const sow_layer_args* layers, int n, int dtype, void* str
   if (!layers) return SOW_ERR_NULL;
   if (n > SK_MAXL) return SOW_ERR_UNSUPPORTED;
   SkLayer sk[SK_MAXL];
-  int m = 0, n_fp8 = 0, n_fp4 = 0, n_plain = 0;
+  int m = 0, call_kind = SOW_ACC_NONE;      // the kind of the call's dense accumulators, once one was seen
   for (int i = 0; i < n; ++i) {
     const sow_layer_args& L = layers[i];
     if (L.T < 0 || L.d_in <= 0 || L.d_out <= 0 || L.r_live <= 0) return SOW_ERR_SHAPE;
-    if (L.acc_kind != SOW_ACC_NONE && L.acc_kind != SOW_ACC_LOWRANK && L.acc_kind != SOW_ACC_DENSE && L.acc_kind != SOW_ACC_DENSE_FP8 &&
-        L.acc_kind != SOW_ACC_DENSE_FP4)
-      return SOW_ERR_SHAPE;
+    if (!acc_kind_known(L.acc_kind)) return SOW_ERR_SHAPE;
     if (L.T == 0) continue;
     if (!skinny_shape_ok(L.T, L.d_in, L.d_out, L.r_live, L.acc_kind, cd)) return SOW_ERR_UNSUPPORTED;
-    const bool fp8 = L.acc_kind == SOW_ACC_DENSE_FP8, fp4 = L.acc_kind == SOW_ACC_DENSE_FP4;
-    const bool dense = L.acc_kind == SOW_ACC_DENSE || fp8 || fp4;
-    if (!L.x || !L.A || !L.B || !L.y || (dense && !L.acc_down) || ((fp8 || fp4) && !L.acc_up)) return SOW_ERR_NULL;
+    const bool codes = acc_is_codes(L.acc_kind), fp4 = L.acc_kind == SOW_ACC_DENSE_FP4;
+    const bool dense = L.acc_kind == SOW_ACC_DENSE || codes;
+    if (!L.x || !L.A || !L.B || !L.y || (dense && !L.acc_down) || (codes && !L.acc_up)) return SOW_ERR_NULL;
     if (!al16p(L.x) || !al16p(L.y) || !al16p(L.A) || !al16p(L.B) || !al16p(L.bias) || (dense && !fp4 && !al16p(L.acc_down)))
       return SOW_ERR_UNSUPPORTED;
     // MXFP4: codes and block scales are read in 8-byte pieces
     if (fp4 && ((reinterpret_cast<uintptr_t>(L.acc_down) | reinterpret_cast<uintptr_t>(L.acc_up)) & 7)) return SOW_ERR_UNSUPPORTED;
     // one kind of dense accumulator per call (the kernels are instantiated per kind)
-    n_fp8 += fp8, n_fp4 += fp4, n_plain += dense && !fp8 && !fp4;
-    if ((n_fp8 != 0) + (n_fp4 != 0) + (n_plain != 0) > 1) return SOW_ERR_UNSUPPORTED;
+    if (dense && call_kind != SOW_ACC_NONE && call_kind != L.acc_kind) return SOW_ERR_UNSUPPORTED;
+    if (dense) call_kind = L.acc_kind;
     const SkWs w = skinny_ws(L.T, L.d_in, L.d_out, L.acc_kind);
     if (!L.workspace || L.workspace_bytes < w.total) return SOW_ERR_WORKSPACE;
     char* ws = ws_base(L.workspace);
@@ -1213,9 +1208,9 @@ int sow_forward_skinny(const sow_layer_args* layers, int n, int dtype, void* str
     K.x = L.x, K.W = dense ? L.acc_down : nullptr, K.A = L.A, K.B = L.B, K.bias = L.bias, K.y = L.y;
     K.Py = dense ? (float*)(ws + w.off_py) : nullptr, K.Ph = (float*)(ws + w.off_ph);
     K.T = (int)L.T, K.d_in = L.d_in, K.d_out = L.d_out, K.r = L.r_live, K.scale = L.scale;
-    K.wexp = fp8 || fp4 ? (const int8_t*)L.acc_up : nullptr;
+    K.wexp = codes ? (const int8_t*)L.acc_up : nullptr;
   }
-  return launch_skinny_fwd(sk, m, cd, n_fp4 ? SOW_ACC_DENSE_FP4 : n_fp8 ? SOW_ACC_DENSE_FP8 : SOW_ACC_DENSE, f.native, (hipStream_t)stream);
+  return launch_skinny_fwd(sk, m, cd, call_kind != SOW_ACC_NONE ? call_kind : SOW_ACC_DENSE, f.native, (hipStream_t)stream);
 }
 
 static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, int gdt, int phases, int perm, hipStream_t stream) {
@@ -1324,7 +1319,7 @@ static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, i
 }
 
 int sow_backward_group(const sow_layer_args* layers, int n, int dtype, int phases, void* stream_) {
-  if (any_fp8_acc(layers, n)) return SOW_ERR_UNSUPPORTED;
+  if (any_codes_acc(layers, n)) return SOW_ERR_UNSUPPORTED;
   hipStream_t stream = (hipStream_t)stream_;
   const Dtype f = decode_dtype(dtype);
   if (f.native_bit && !f.layer_ok()) return SOW_ERR_DTYPE;
@@ -1358,7 +1353,7 @@ static void shared_fill_dx(const sow_layer_args* layers, int n, sow_layer_args* 
 }
 
 int sow_forward_shared(const sow_layer_args* layers, int n, int dtype, void* stream) {
-  if (any_fp8_acc(layers, n)) return SOW_ERR_UNSUPPORTED;
+  if (any_codes_acc(layers, n)) return SOW_ERR_UNSUPPORTED;
   const Dtype f = decode_dtype(dtype);
   if (!ok_dtype(f.cd)) return SOW_ERR_DTYPE;
   int rc;
@@ -1373,7 +1368,7 @@ int sow_forward_shared(const sow_layer_args* layers, int n, int dtype, void* str
 }
 
 int sow_backward_shared(const sow_layer_args* layers, int n, int dtype, int phases, void* stream_) {
-  if (any_fp8_acc(layers, n)) return SOW_ERR_UNSUPPORTED;
+  if (any_codes_acc(layers, n)) return SOW_ERR_UNSUPPORTED;
   hipStream_t stream = (hipStream_t)stream_;
   const Dtype f = decode_dtype(dtype);
   const int cd = f.cd;
@@ -1418,7 +1413,7 @@ static int check_group(const sow_layer_args* layers, int n) {
 }
 
 int sow_backward_group_plan(const sow_layer_args* layers, int n, int dtype, int phases, int* slabs_out) {
-  if (any_fp8_acc(layers, n)) return SOW_ERR_UNSUPPORTED;
+  if (any_codes_acc(layers, n)) return SOW_ERR_UNSUPPORTED;
   const Dtype f = decode_dtype(dtype);   // the plan does not depend on the parameter dtype
   if (!f.layer_ok()) return SOW_ERR_DTYPE;
   if (n < 0) return SOW_ERR_SHAPE;
@@ -1439,7 +1434,7 @@ int sow_backward_group_plan(const sow_layer_args* layers, int n, int dtype, int 
 }
 
 int sow_backward_group_reduce_desc(const sow_layer_args* layers, int n, int dtype, int phases, void* descs_out, int* blocks_out) {
-  if (any_fp8_acc(layers, n)) return SOW_ERR_UNSUPPORTED;
+  if (any_codes_acc(layers, n)) return SOW_ERR_UNSUPPORTED;
   const Dtype f = decode_dtype(dtype);
   if (!f.layer_ok()) return SOW_ERR_DTYPE;
   if (n < 0) return SOW_ERR_SHAPE;

@@ -246,16 +246,19 @@ int launch_tn_wide(const void* x, const void* dh, const void* dy, const void* h,
 // An MXFP4 accumulator (SOW_ACC_DENSE_FP4: W = the packed E2M1 codes [d_in / 2][d_out], wexp = the E8M0 block scales
 // [d_in / 32][d_out]) takes the same geometry with the scale applied in the conversion, and the plain second kernel.
 // The dense layers of one call are all of one kind.
+// A dense accumulator stored as codes, with scales in acc_up's place; and a kind value of include/sow_amd.h (a format is added to both)
+constexpr bool acc_is_codes(int kind) { return kind == SOW_ACC_DENSE_FP8 || kind == SOW_ACC_DENSE_FP4; }
+constexpr bool acc_kind_known(int kind) { return kind == SOW_ACC_NONE || kind == SOW_ACC_LOWRANK || kind == SOW_ACC_DENSE || acc_is_codes(kind); }
 constexpr int SK_MAXL = 16;
 struct SkLayer {
-  const void *x, *W, *A, *B, *bias;   // W = the dense accumulator [d_in][d_out] (or its E4M3 codes), or nullptr
+  const void *x, *W, *A, *B, *bias;   // W = the dense accumulator [d_in][d_out], its codes (E4M3 [d_in][d_out], MXFP4 [d_in / 2][d_out]), or nullptr
                                       // A, B, bias: of the compute dtype, or all fp32 (launch_skinny_fwd's param_f32)
   void* y;
   float *Py, *Ph;                     // slab partials [S][T][d_out] (nullptr without W) and [S][T][64]
   int T, d_in, d_out, r;
   int S, KS, ncr, startA, startB;     // filled in by launch_skinny_fwd (skinny_plan)
   float scale;
-  const int8_t* wexp;                 // column exponents [d_out] of an E4M3 accumulator, the E8M0 block scale bytes of an MXFP4 one, or nullptr
+  const int8_t* wexp;                 // the scales of codes in W (E4M3: int8 column exponents [d_out]; MXFP4: E8M0 bytes [d_in / 32][d_out]), or nullptr
 };
 // K-slabs, slab length and phase-A column ranges of a layer: a pure function of the shape
 void skinny_plan(int d_in, int d_out, int acc_kind, int* S, int* KS, int* ncr);

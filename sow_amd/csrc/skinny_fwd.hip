@@ -82,7 +82,7 @@ template <> struct SkW<SK_PLAIN> {
 };
 constexpr int sk_cn(bool codes) { return 16 * (codes ? SK_NCT8 : SK_NCT); }   // columns per phase-A workgroup
 constexpr int sk_rs(bool codes) { return sk_cn(codes) + 4; }   // row pitch (floats) of the parked tiles: 4 rows apart = 16 banks apart
-constexpr bool sk_codes(int acc_kind) { return acc_kind == SOW_ACC_DENSE_FP8 || acc_kind == SOW_ACC_DENSE_FP4; }
+constexpr SkFmt sk_fmt(int acc_kind) { return acc_kind == SOW_ACC_DENSE_FP8 ? SK_FP8 : acc_kind == SOW_ACC_DENSE_FP4 ? SK_FP4 : SK_PLAIN; }
 
 struct SkGroup {
   SkLayer L[SK_MAXL];
@@ -91,8 +91,9 @@ struct SkGroup {
 static_assert(sizeof(SkGroup) <= 4096, "by-value kernel arguments must stay under 4 KiB");
 
 void skinny_plan(int d_in, int d_out, int acc_kind, int* S, int* KS, int* ncr) {
-  const int nc = acc_kind == SOW_ACC_DENSE ? ceil_div(d_out, sk_cn(false)) : sk_codes(acc_kind) ? ceil_div(d_out, sk_cn(true)) : 0;
-  const int want = nc ? ceil_div(sk_codes(acc_kind) ? SK_WANT_WGS8 : SK_WANT_WGS, nc) : 32;
+  const bool codes = acc_is_codes(acc_kind);
+  const int nc = acc_kind == SOW_ACC_DENSE || codes ? ceil_div(d_out, sk_cn(codes)) : 0;
+  const int want = nc ? ceil_div(codes ? SK_WANT_WGS8 : SK_WANT_WGS, nc) : 32;
   int ks = ceil_div(ceil_div(d_in, want), SK_KQ) * SK_KQ;
   if (ks < SK_KQ) ks = SK_KQ;
   if (ks > SK_KS_MAX) ks = SK_KS_MAX;
@@ -416,6 +417,11 @@ template <typename T, SkFmt F, bool PF> static int sk_launch(const SkGroup& g, i
   SOW_CHECK_LAUNCH();
   return SOW_OK;
 }
+// every instantiation there is, by [dtype is f16][SkFmt][param_f32]
+using SkLaunch = int (*)(const SkGroup&, int, int, size_t, hipStream_t);
+#define SK_FMT_ROW(T, F) {sk_launch<T, F, false>, sk_launch<T, F, true>}
+#define SK_DTYPE_ROWS(T) {SK_FMT_ROW(T, SK_PLAIN), SK_FMT_ROW(T, SK_FP8), SK_FMT_ROW(T, SK_FP4)}
+static constexpr SkLaunch SK_LAUNCH[2][3][2] = {SK_DTYPE_ROWS(bf16_t), SK_DTYPE_ROWS(f16_t)};
 
 // layers: x, W (or nullptr), A, B, bias, y, Py (or nullptr), Ph, T in [1, 32], d_in, d_out, r, scale set by the caller (api.hip
 // has checked the admitted set); the plan and the block offsets are filled in here.  param_f32: A, B and bias are fp32
@@ -423,12 +429,11 @@ int launch_skinny_fwd(const SkLayer* layers, int n, int dtype, int acc_kind, boo
   if (n <= 0) return SOW_OK;
   if (n > SK_MAXL || (dtype != SOW_BF16 && dtype != SOW_F16)) return SOW_ERR_UNSUPPORTED;
   // the dense layers of a call are of one kind: the kernels are instantiated per kind
-  bool fp8 = false, plain = false;
-  for (int i = 0; i < n; ++i) (layers[i].wexp ? fp8 : plain) |= layers[i].W != nullptr;
-  if ((fp8 && plain) || (acc_kind != SOW_ACC_DENSE_FP8 && acc_kind != SOW_ACC_DENSE_FP4 && fp8) || (sk_codes(acc_kind) && plain))
-    return SOW_ERR_UNSUPPORTED;
-  const bool fp4 = fp8 && acc_kind == SOW_ACC_DENSE_FP4;   // (fp8 below: the accumulator is codes, of either format)
-  const int SK_RS = sk_rs(fp8);
+  bool codes = false, plain = false;
+  for (int i = 0; i < n; ++i) (layers[i].wexp ? codes : plain) |= layers[i].W != nullptr;
+  if ((codes && plain) || (!acc_is_codes(acc_kind) && codes) || (acc_is_codes(acc_kind) && plain)) return SOW_ERR_UNSUPPORTED;
+  const SkFmt fmt = codes ? sk_fmt(acc_kind) : SK_PLAIN;
+  const int SK_RS = sk_rs(codes);
   SkGroup g;
   g.n = n;
   int na = 0, nb = 0;
@@ -438,7 +443,7 @@ int launch_skinny_fwd(const SkLayer* layers, int n, int dtype, int acc_kind, boo
     L = layers[i];
     if (!L.W) L.wexp = nullptr;
     int ncr;
-    skinny_plan(L.d_in, L.d_out, !L.W ? SOW_ACC_NONE : fp8 ? acc_kind : SOW_ACC_DENSE, &L.S, &L.KS, &ncr);
+    skinny_plan(L.d_in, L.d_out, !L.W ? SOW_ACC_NONE : codes ? acc_kind : SOW_ACC_DENSE, &L.S, &L.KS, &ncr);
     L.ncr = ncr;
     L.startA = na, L.startB = nb;
     na += L.S * ((L.r + 15) / 16 + ncr);
@@ -449,14 +454,7 @@ int launch_skinny_fwd(const SkLayer* layers, int n, int dtype, int acc_kind, boo
     lds = rb > lds ? rb : lds;
   }
   // MXFP4: the scale went into the conversion, Py holds sum x . W^ and phase B is the plain one
-  if (param_f32) {
-    if (fp4) return dtype == SOW_BF16 ? sk_launch<bf16_t, SK_FP4, true>(g, na, nb, lds, stream) : sk_launch<f16_t, SK_FP4, true>(g, na, nb, lds, stream);
-    if (fp8) return dtype == SOW_BF16 ? sk_launch<bf16_t, SK_FP8, true>(g, na, nb, lds, stream) : sk_launch<f16_t, SK_FP8, true>(g, na, nb, lds, stream);
-    return dtype == SOW_BF16 ? sk_launch<bf16_t, SK_PLAIN, true>(g, na, nb, lds, stream) : sk_launch<f16_t, SK_PLAIN, true>(g, na, nb, lds, stream);
-  }
-  if (fp4) return dtype == SOW_BF16 ? sk_launch<bf16_t, SK_FP4, false>(g, na, nb, lds, stream) : sk_launch<f16_t, SK_FP4, false>(g, na, nb, lds, stream);
-  if (fp8) return dtype == SOW_BF16 ? sk_launch<bf16_t, SK_FP8, false>(g, na, nb, lds, stream) : sk_launch<f16_t, SK_FP8, false>(g, na, nb, lds, stream);
-  return dtype == SOW_BF16 ? sk_launch<bf16_t, SK_PLAIN, false>(g, na, nb, lds, stream) : sk_launch<f16_t, SK_PLAIN, false>(g, na, nb, lds, stream);
+  return SK_LAUNCH[dtype == SOW_F16][fmt][param_f32](g, na, nb, lds, stream);
 }
 
 }  // namespace sow

@@ -233,16 +233,17 @@ class SiblingGroup:
             return None
         if cdt is not None:      # fp32 master factors under autocast: the input in the compute dtype, cast once for the set
             x2 = autocast_input(x2.contiguous(), cdt)
-        calls = []
+        calls, kinds = [], set()
         for m in self.layers:
             A, B = m.downscale_weights._parameters["0"], m.upscale_weights._parameters["0"]
             acc_down, acc_up = m._acc_pair()
             if not ops.skinny_admits(x2, A, B, acc_down, acc_up, m.bias, mixed=cdt is not None):
                 return None
             calls.append((x2, A, B, ops.skinny_acc(acc_down, acc_up), m.bias, float(m.scale)))
-        if len({c[3][0].dtype if isinstance(c[3], tuple) else None for c in calls if c[3] is not None}) > 1:
-            # E4M3, MXFP4 and unquantised dense accumulators in one set: the library takes one kind per call, and every
-            # sibling is admitted on its own -- each streams its own accumulator in a call of its own
+            kinds.add(ops.acc_kind(acc_down, acc_up))
+        if len(kinds - {_lib.ACC_NONE}) > 1:
+            # quantised accumulators of differing formats, or quantised and unquantised ones, in one set: the library takes one
+            # kind per call, and every sibling is admitted on its own -- each streams its own accumulator in a call of its own
             return _PER_LAYER
         ys = ops.sow_forward_skinny(calls)
         if ys is None:

@@ -35,9 +35,6 @@ class SoWParameter(nn.ParameterList):
         return f"{self.n_iter} x ({self.in_features}, {self.out_features})"
 
 
-_HALF = (torch.bfloat16, torch.float16)
-
-
 def autocast_compute_dtype(param_dtype: torch.dtype) -> Optional[torch.dtype]:
     """The compute dtype of a SoW call with parameters of `param_dtype` under torch.autocast("cuda"): bf16 / f16 for fp32
     parameters (fp32 master factors, the mixed-precision path: include/sow_amd.h SOW_PARAM_F32), None outside autocast or
@@ -45,7 +42,7 @@ def autocast_compute_dtype(param_dtype: torch.dtype) -> Optional[torch.dtype]:
     if not torch.is_autocast_enabled("cuda"):
         return None
     ad = torch.get_autocast_dtype("cuda")
-    if ad not in _HALF:
+    if ad not in ops._HALF:
         raise TypeError(f"SoWLinear under torch.autocast: autocast dtype {ad} is not supported (bfloat16 or float16)")
     if param_dtype == ad:
         return None
@@ -192,8 +189,8 @@ class SoWLinear(nn.Module):
     # ------------------------------------------------------------------------------------------
     # A dense accumulator quantised by sow_amd.quantize_accumulators: acc_downweight holds the E4M3 codes (a frozen
     # float8_e4m3fn parameter) and the persistent buffer acc_exponent the int8 column exponents -- or, for fmt="mxfp4", the packed
-    # E2M1 codes (uint8 [d_in / 2, d_out]) and the uint8 E8M0 block scales [d_in / 32, d_out].  An unquantised layer has no
-    # such buffer: its state-dict keys are the reference's.
+    # E2M1 codes (uint8 [d_in / 2, d_out]) and the uint8 E8M0 block scales [d_in / 32, d_out] (the formats: acc_format.py).  An
+    # unquantised layer has no such buffer: its state-dict keys are the reference's.
     def acc_quantized(self) -> bool:
         return self._buffers.get("acc_exponent") is not None
 
@@ -280,7 +277,7 @@ class SoWLinear(nn.Module):
         scale = float(self.scale)
         # fp32 master factors over a bf16 / f16 base: the factors fold as the forward reads them, rounded once to the
         # accumulator's dtype, and the accumulator keeps its dtype
-        mixed = has_down and A.dtype == torch.float32 and self.acc_downweight.dtype in _HALF
+        mixed = has_down and A.dtype == torch.float32 and self.acc_downweight.dtype in ops._HALF
         if mixed:
             A, B = A.to(self.acc_downweight.dtype), B.to(self.acc_downweight.dtype)
         if has_down and has_up:      # W_acc = Q R, then += scale * A B   (sow.py:137-138)

@@ -12,12 +12,13 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from . import _lib
+from .acc_format import BY_CODE_DTYPE, BY_KIND, FORMATS, SKINNY_MAX_T, skinny_fp4_pays, skinny_fp8_pays  # noqa: F401
 
 _DT = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
-FP8 = torch.float8_e4m3fn      # the codes of a quantised dense accumulator (include/sow_amd.h: SOW_ACC_DENSE_FP8)
-FP4 = torch.uint8              # ... of an MXFP4 one (SOW_ACC_DENSE_FP4): two E2M1 codes per byte, rows k and k + 1 of a column
-CODES = (FP8, FP4)
-FP4_BLOCK = 32                 # rows per MXFP4 scale block
+_HALF = (torch.bfloat16, torch.float16)
+FP8, FP4 = FORMATS["fp8_e4m3"].code_dtype, FORMATS["mxfp4"].code_dtype     # the quantised formats are described in acc_format.py:
+CODES, FP4_BLOCK = tuple(BY_CODE_DTYPE), FORMATS["mxfp4"].block            # these are its facts under the names tests and tools read
+_NOT_A_PAIR = f"not the codes and scales of a quantised accumulator ({', '.join(FORMATS)}: their dtypes and shapes are in acc_format.py)"
 
 
 def _dt(t: torch.Tensor) -> int:
@@ -138,19 +139,19 @@ def _workspace_bytes(lib, T: int, d_in: int, d_out: int, r: int, r_acc: int, kin
     return n
 
 
-def acc_kind(acc_down: Optional[torch.Tensor], acc_up: Optional[torch.Tensor]) -> int:
-    """Accumulator kind as SoWLinear.forward decides it (reference sow.py:109-112).  E4M3 codes in acc_down (with their int8
-    column exponents in acc_up) are a quantised dense accumulator, and so are packed uint8 MXFP4 codes (with their uint8 E8M0
-    block scales in acc_up)."""
+def _acc_kind_fmt(acc_down, acc_up):
+    """(kind, format record or None): the ONE place that tells a quantised accumulator from the others, by its codes' dtype."""
     if acc_down is None or acc_down.numel() == 0:
-        return _lib.ACC_NONE
-    if acc_down.dtype == FP8:
-        return _lib.ACC_DENSE_FP8
-    if acc_down.dtype == FP4:
-        return _lib.ACC_DENSE_FP4
-    if acc_up is None or acc_up.numel() == 0:
-        return _lib.ACC_DENSE
-    return _lib.ACC_LOWRANK
+        return _lib.ACC_NONE, None
+    fmt = BY_CODE_DTYPE.get(acc_down.dtype)
+    if fmt is not None:
+        return fmt.kind, fmt
+    return (_lib.ACC_DENSE if acc_up is None or acc_up.numel() == 0 else _lib.ACC_LOWRANK), None
+
+
+def acc_kind(acc_down: Optional[torch.Tensor], acc_up: Optional[torch.Tensor]) -> int:
+    """Accumulator kind as SoWLinear.forward decides it (reference sow.py:109-112); codes of a quantised format: that format's kind."""
+    return _acc_kind_fmt(acc_down, acc_up)[0]
 
 
 def check_accumulator(x2: torch.Tensor, d_in: int, d_out: int, acc_down, acc_up, who: str = "sow_amd",
@@ -163,53 +164,38 @@ def check_accumulator(x2: torch.Tensor, d_in: int, d_out: int, acc_down, acc_up,
     three forms: fp32 (packed with the factors by every call), the compute dtype (native, read in place: SOW_ACC_NATIVE), or
     E4M3 / MXFP4 codes (run on their image in the compute dtype, or streamed by the skinny forward).  `compute_dtype`: the
     compute dtype when x2 is not of it yet (an fp32 input under autocast that the call casts first)."""
-    kind = acc_kind(acc_down, acc_up)
+    kind, fmt = _acc_kind_fmt(acc_down, acc_up)
     cdt = x2.dtype if compute_dtype is None else compute_dtype
     if kind == _lib.ACC_NONE:
         return kind, 0
     r_acc = 0
-    if kind == _lib.ACC_DENSE_FP8:
-        if param_dtype not in (None, torch.float32) or cdt not in (torch.bfloat16, torch.float16):
-            raise TypeError(f"{who}: an E4M3 accumulator runs with bfloat16 or float16 inputs and parameters, got {cdt}"
+    if fmt is not None:
+        if param_dtype not in (None, torch.float32) or cdt not in _HALF:
+            raise TypeError(f"{who}: an {fmt.label} accumulator runs with bfloat16 or float16 inputs and parameters, got {cdt}"
                             + ("" if param_dtype is None else f" inputs and {param_dtype} parameters"))
-        if acc_up is None or acc_up.dtype != torch.int8:
-            raise TypeError(f"{who}: an E4M3 accumulator comes with int8 column exponents")
-        if tuple(acc_down.shape) != (d_in, d_out) or tuple(acc_up.shape) != (d_out,) or d_out % 8:
-            raise ValueError(f"{who}: an E4M3 accumulator is [in_features, out_features] codes and [out_features] exponents, "
-                             "out_features a multiple of 8")
-        for t in (acc_down, acc_up):
-            if not t.is_cuda or t.device != x2.device:
-                raise RuntimeError(f"{who}: the accumulator is on {t.device}, the input on {x2.device}")
-        return kind, 0
-    if kind == _lib.ACC_DENSE_FP4:
-        if param_dtype not in (None, torch.float32) or cdt not in (torch.bfloat16, torch.float16):
-            raise TypeError(f"{who}: an MXFP4 accumulator runs with bfloat16 or float16 inputs and parameters, got {cdt}"
-                            + ("" if param_dtype is None else f" inputs and {param_dtype} parameters"))
-        if acc_up is None or acc_up.dtype != torch.uint8:
-            raise TypeError(f"{who}: an MXFP4 accumulator comes with uint8 (E8M0) block scales")
-        if (d_in % FP4_BLOCK or d_out % 8 or tuple(acc_down.shape) != (d_in // 2, d_out)
-                or tuple(acc_up.shape) != (d_in // FP4_BLOCK, d_out)):
-            raise ValueError(f"{who}: an MXFP4 accumulator is [in_features / 2, out_features] packed codes and [in_features / 32, "
-                             "out_features] block scales, in_features a multiple of 32, out_features of 8")
-        for t in (acc_down, acc_up):
-            if not t.is_cuda or t.device != x2.device:
-                raise RuntimeError(f"{who}: the accumulator is on {t.device}, the input on {x2.device}")
-        return kind, 0
-    want = x2.dtype if param_dtype is None else param_dtype
-    if param_dtype == torch.float32 and acc_down.dtype == cdt and cdt in (torch.bfloat16, torch.float16):
-        want = cdt      # native: both tensors of the accumulator in the compute dtype
-    if acc_down.dtype != want or (kind == _lib.ACC_LOWRANK and acc_up.dtype != want):
-        bad = acc_down.dtype if acc_down.dtype != want else acc_up.dtype
-        raise TypeError(f"{who}: dtype mismatch, x is {x2.dtype} but the accumulator is {bad}"
-                        + ("" if param_dtype is None else f" (parameters must be {param_dtype}; the accumulator {param_dtype} "
-                                                           f"or the compute dtype)"))
-    if kind == _lib.ACC_DENSE and tuple(acc_down.shape) != (d_in, d_out):
-        raise ValueError(f"{who}: dense accumulator must be [in_features, out_features]")
-    if kind == _lib.ACC_LOWRANK:
-        r_acc = acc_down.shape[1] if acc_down.dim() == 2 else -1
-        if acc_down.dim() != 2 or acc_down.shape[0] != d_in or tuple(acc_up.shape) != (r_acc, d_out):
-            raise ValueError(f"{who}: low-rank accumulator shapes do not match")
-    for t in (acc_down, acc_up if kind == _lib.ACC_LOWRANK else None):
+        if acc_up is None or acc_up.dtype != fmt.scale_dtype:
+            raise TypeError(f"{who}: an {fmt.label} accumulator comes with {fmt.scale_dtype} scales")
+        if (d_in % (fmt.block or 1) or d_out % fmt.d_out_multiple or tuple(acc_down.shape) != fmt.code_shape(d_in, d_out)
+                or tuple(acc_up.shape) != fmt.scale_shape(d_in, d_out)):
+            raise ValueError(f"{who}: an {fmt.label} accumulator of [{d_in}, {d_out}] is codes {fmt.code_shape(d_in, d_out)} and scales "
+                             f"{fmt.scale_shape(d_in, d_out)}, out_features a multiple of {fmt.d_out_multiple}"
+                             + (f", in_features whole blocks of {fmt.block}" if fmt.block else ""))
+    else:
+        want = x2.dtype if param_dtype is None else param_dtype
+        if param_dtype == torch.float32 and acc_down.dtype == cdt and cdt in _HALF:
+            want = cdt      # native: both tensors of the accumulator in the compute dtype
+        if acc_down.dtype != want or (kind == _lib.ACC_LOWRANK and acc_up.dtype != want):
+            bad = acc_down.dtype if acc_down.dtype != want else acc_up.dtype
+            raise TypeError(f"{who}: dtype mismatch, x is {x2.dtype} but the accumulator is {bad}"
+                            + ("" if param_dtype is None else f" (parameters must be {param_dtype}; the accumulator {param_dtype} "
+                                                               f"or the compute dtype)"))
+        if kind == _lib.ACC_DENSE and tuple(acc_down.shape) != (d_in, d_out):
+            raise ValueError(f"{who}: dense accumulator must be [in_features, out_features]")
+        if kind == _lib.ACC_LOWRANK:
+            r_acc = acc_down.shape[1] if acc_down.dim() == 2 else -1
+            if acc_down.dim() != 2 or acc_down.shape[0] != d_in or tuple(acc_up.shape) != (r_acc, d_out):
+                raise ValueError(f"{who}: low-rank accumulator shapes do not match")
+    for t in (acc_down, acc_up if kind != _lib.ACC_DENSE else None):      # (a dense accumulator has no second tensor)
         if t is not None and (not t.is_cuda or t.device != x2.device):
             raise RuntimeError(f"{who}: the accumulator is on {t.device}, the input on {x2.device}")
     return kind, r_acc
@@ -371,34 +357,29 @@ def shared_fused_acc_pays(r_tots: Sequence[int]) -> bool:
 
 
 def acc_logical_shape(codes: torch.Tensor) -> Tuple[int, int]:
-    """(d_in, d_out) of the matrix a codes tensor stands for: MXFP4 packs two rows into one byte."""
-    return (2 * codes.shape[0], codes.shape[1]) if codes.dtype == FP4 else (codes.shape[0], codes.shape[1])
+    """(d_in, d_out) of the matrix a codes tensor stands for (a format may pack several rows into one code element)."""
+    fmt = BY_CODE_DTYPE.get(codes.dtype)
+    return fmt.logical_shape(codes) if fmt else (codes.shape[0], codes.shape[1])
 
 
 def acc_dequantize(codes: torch.Tensor, exps: torch.Tensor, dtype: torch.dtype, out: Optional[torch.Tensor] = None):
-    """The image of an E4M3 accumulator, W^[k, n] = codes[k, n] * 2^exps[n], or of an MXFP4 one (packed uint8 codes, uint8 block
-    scales in `exps`: W^[k, n] = e2m1(code(k, n)) * 2^(exps[k // 32, n] - 127)), exactly, in bf16 or f16 (sow_acc_dequantize /
-    sow_acc_dequantize_fp4: one streaming pass).  `out`: a [d_in, d_out] tensor of `dtype` whose rows are contiguous (any row pitch that is a multiple of
-    8), written in place."""
+    """The image W^ of a quantised accumulator (codes and their scales `exps`, of one format of acc_format.py), exactly, in bf16
+    or f16 (the format's image entry, sow_acc_dequantize / sow_acc_dequantize_fp4: one streaming pass).  `out`: a [d_in, d_out]
+    tensor of `dtype` whose rows are contiguous (any row pitch that is a multiple of 8), written in place."""
     dev = _need_gpu(codes, exps, out)
-    fp4 = codes.dtype == FP4
-    if fp4:
-        if exps.dtype != torch.uint8 or codes.dim() != 2 or (2 * codes.shape[0]) % FP4_BLOCK or tuple(exps.shape) != (
-                2 * codes.shape[0] // FP4_BLOCK, codes.shape[1]):
-            raise TypeError("sow_amd.acc_dequantize: packed uint8 MXFP4 codes [d_in / 2, d_out] and uint8 block scales [d_in / 32, d_out]")
-    elif codes.dtype != FP8 or exps.dtype != torch.int8 or codes.dim() != 2 or tuple(exps.shape) != (codes.shape[1],):
-        raise TypeError("sow_amd.acc_dequantize: float8_e4m3fn codes [d_in, d_out] and int8 exponents [d_out]")
-    if dtype not in (torch.bfloat16, torch.float16):
+    fmt = BY_CODE_DTYPE.get(codes.dtype)
+    if fmt is None or not fmt.well_formed(codes, exps):
+        raise TypeError(f"sow_amd.acc_dequantize: {_NOT_A_PAIR}")
+    if dtype not in _HALF:
         raise TypeError(f"sow_amd.acc_dequantize: the image is bfloat16 or float16, not {dtype}")
-    d_in, d_out = acc_logical_shape(codes)
+    d_in, d_out = fmt.logical_shape(codes)
     codes, exps = codes.contiguous(), exps.contiguous()
     if out is None:
         out = torch.empty((d_in, d_out), dtype=dtype, device=dev)
     elif out.dtype != dtype or tuple(out.shape) != (d_in, d_out) or (d_out > 1 and out.stride(1) != 1):
         raise ValueError("sow_amd.acc_dequantize: `out` must be a [d_in, d_out] tensor of the image dtype with contiguous rows")
     if d_in and d_out:
-        name = "sow_acc_dequantize_fp4" if fp4 else "sow_acc_dequantize"
-        _launch(dev, name, getattr(_lib.load(), name), _ptr(codes), _ptr(exps), d_in, d_out, _ptr(out),
+        _launch(dev, fmt.dequantize, getattr(_lib.load(), fmt.dequantize), _ptr(codes), _ptr(exps), d_in, d_out, _ptr(out),
                 out.stride(0) if d_in > 1 else d_out, _DT[dtype])
     return out
 
@@ -443,11 +424,11 @@ def acc_images(pairs, dtype: torch.dtype) -> list:
 def acc_operands(accs, dtype: torch.dtype) -> list:
     """(acc_down, acc_up) of every layer of ONE call as the dense kernels read them: an E4M3 or MXFP4 accumulator (codes, exponents)
     is replaced by (its image in the scratch arena, None), everything else passes through."""
-    fp8 = [i for i, (d, _) in enumerate(accs) if d is not None and d.numel() and d.dtype in CODES]
-    if not fp8:
+    quantised = [i for i, (d, _) in enumerate(accs) if d is not None and d.numel() and d.dtype in BY_CODE_DTYPE]
+    if not quantised:
         return list(accs)
     out = list(accs)
-    for i, img in zip(fp8, acc_images([accs[i] for i in fp8], dtype)):
+    for i, img in zip(quantised, acc_images([accs[i] for i in quantised], dtype)):
         out[i] = (img, None)
     return out
 
@@ -496,78 +477,51 @@ def sow_forward(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, ac
     return y, (h if save_h else None)
 
 
-SKINNY_MAX_T = 32          # include/sow_amd.h: sow_forward_skinny admits at most 32 tokens per layer ...
-SKINNY_MAX_LAYERS = 16     # ... and 16 layers per call
+SKINNY_MAX_LAYERS = 16     # include/sow_amd.h: sow_forward_skinny admits at most 32 tokens per layer (SKINNY_MAX_T) and 16 layers per call
 _SKINNY_WS_BYTES: dict = {}
 
 
 def skinny_workspace_bytes(T: int, d_in: int, d_out: int, r: int, kind: int, dt: int) -> int:
-    """sow_forward_skinny_workspace_bytes (sow_forward_skinny_fp8_workspace_bytes for an E4M3 accumulator,
-    sow_forward_skinny_fp4_workspace_bytes for an MXFP4 one), memoised per shape: 0 = the shape is outside the admitted set.  A pure function
-    of the shape (no switch enters), so the memo is never dropped."""
+    """sow_forward_skinny_workspace_bytes -- for a quantised accumulator the query of its format --, memoised per shape: 0 = the
+    shape is outside the admitted set.  A pure function of the shape (no switch enters), so the memo is never dropped."""
     key = (T, d_in, d_out, r, kind, dt)
     n = _SKINNY_WS_BYTES.get(key)
     if n is None:
-        lib = _lib.load()
-        n = _SKINNY_WS_BYTES[key] = int(lib.sow_forward_skinny_fp8_workspace_bytes(T, d_in, d_out, r, dt) if kind == _lib.ACC_DENSE_FP8
-                                        else lib.sow_forward_skinny_fp4_workspace_bytes(T, d_in, d_out, r, dt) if kind == _lib.ACC_DENSE_FP4
-                                        else lib.sow_forward_skinny_workspace_bytes(T, d_in, d_out, r, kind, dt))
+        lib, fmt = _lib.load(), BY_KIND.get(kind)
+        n = _SKINNY_WS_BYTES[key] = int(lib.sow_forward_skinny_workspace_bytes(T, d_in, d_out, r, kind, dt) if fmt is None
+                                        else getattr(lib, fmt.workspace_query)(T, d_in, d_out, r, dt))
     return n
 
 
 def skinny_pays(T: int, d_in: int, d_out: int) -> bool:
     """The measured dispatch rule of the module surface (profiles/skinny_forward.txt): the token
-    counts and widths at which the fused skinny forward is faster than the path it replaces."""
-    return 1 <= T <= SKINNY_MAX_T
-
-
-def skinny_fp8_pays(T: int, d_in: int, d_out: int) -> bool:
-    """The measured dispatch rule for an E4M3 accumulator (profiles/fp8_acc.txt), the one place that
-    encodes it: the calls at which streaming the codes (q) is faster than the image pass followed by the bf16 skinny forward
-    on the image (d).  Measured (us, r = 50, T = 4 / 32): 4096->4096 25.4 / 32.9 against 40.8 / 44.2, 4096->11008 37.6 / 47.4
-    against 67.4 / 92.6, 11008->4096 37.4 / 47.4 against 67.8 / 83.7, 512->512 17.7 / 19.8 against 20.5 / 22.2, q + k + v of
-    4096->4096 39.9 / 59.3 against 73.7 / 88.0; q / d lies between 0.47 and 0.89 in all 48 rows (T = 1, 4, 16, 32; r = 8, 50):
-    the rule excludes nothing.  NOT measured: f16, widths above 11008."""
-    return 1 <= T <= SKINNY_MAX_T
-
-
-def skinny_fp4_pays(T: int, d_in: int, d_out: int) -> bool:
-    """The measured dispatch rule for an MXFP4 accumulator (profiles/fp4_acc.txt), the one place that
-    encodes it: the calls at which streaming the codes (q4) is faster than the image pass followed by the bf16 skinny forward on
-    the image (d4) by more than the run-to-run spread of the row.  Measured (us, r = 50, T = 4 / 32; +- the larger spread
-    of the two variants): 4096->4096 21.1 / 29.9 against 39.7 / 43.0 (+- 2.5 / 2.6), 4096->11008 24.3 / 38.4 against 62.9 / 90.1
-    (+- 1.8 / 2.8), 11008->4096 26.5 / 37.4 against 62.3 / 81.0 (+- 1.6 / 1.9), 512->512 14.5 / 16.3 against 18.3 / 19.2 (+- 1.5 / 0.3),
-    q + k + v of 4096->4096 33.5 / 52.4 against 70.3 / 84.5 (+- 0.7 / 1.0); q4 / d4 lies between 0.37 and 0.85 in all 48 rows (T = 1,
-    4, 16, 32; r = 8, 50) and the gap exceeds the spread in each: the rule excludes nothing.  q4 is never slower than the E4M3
-    codes (q4 / q8 0.68 ... 1.00); it loses to the bf16 accumulator at 4096->4096, T = 32, r = 8 (29.1 against 25.4) and by up to
-    10 % on 512-wide layers at r = 8, which does not enter the rule: the kind buys memory there.  NOT measured: f16, widths above
-    11008."""
+    counts and widths at which the fused skinny forward is faster than the path it replaces (quantised formats: acc_format.py)."""
     return 1 <= T <= SKINNY_MAX_T
 
 
 def skinny_acc(acc_down, acc_up):
-    """The accumulator element of a sow_forward_skinny layer tuple: None, the dense tensor, or (codes, exponents)."""
-    kind = acc_kind(acc_down, acc_up)
-    if kind == _lib.ACC_NONE:
+    """The accumulator element of a sow_forward_skinny layer tuple: None, the dense tensor, or (codes, scales)."""
+    if acc_down is None or acc_down.numel() == 0:
         return None
-    return (acc_down, acc_up) if kind in (_lib.ACC_DENSE_FP8, _lib.ACC_DENSE_FP4) else acc_down
+    return (acc_down, acc_up) if acc_down.dtype in BY_CODE_DTYPE else acc_down
 
 
 def skinny_admits(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, acc_up, bias, mixed: bool = False) -> bool:
     """Whether a no-grad module call on the flattened input x2 may go to sow_forward_skinny: a bf16 / f16 call of at most 32
     tokens with parameters of the input's dtype -- or fp32 factors and bias (autocast with master factors: SOW_PARAM_F32 |
-    SOW_ACC_NATIVE, the kernels round them in registers) --, a dense accumulator (in the input's dtype or as E4M3 / MXFP4 codes)
+    SOW_ACC_NATIVE, the kernels round them in registers) --, a dense accumulator (in the input's dtype or as codes of a format)
     or none, and a shape the library admits and the dispatch rule keeps.  False sends the caller to the existing path, which
     raises whatever it raises today.  mixed: the call runs under autocast with fp32 factors and x2 already of the compute dtype."""
     dt = _DT.get(x2.dtype)
     if dt is None or dt == _lib.F32 or not x2.is_cuda or x2.dim() != 2 or not 1 <= x2.shape[0] <= SKINNY_MAX_T:
         return False
-    kind = acc_kind(acc_down, acc_up)
+    kind, fmt = _acc_kind_fmt(acc_down, acc_up)
     if kind == _lib.ACC_LOWRANK or A.dim() != 2 or B.dim() != 2:
         return False
     T, d_in = x2.shape
     r, d_out = B.shape
-    if tuple(A.shape) != (d_in, r) or (kind != _lib.ACC_NONE and acc_logical_shape(acc_down) != (d_in, d_out)):
+    if tuple(A.shape) != (d_in, r) or (kind != _lib.ACC_NONE and tuple(acc_down.shape) != (
+            d_in // fmt.rows_per_code if fmt else d_in, d_out)):     # (d_in is whole code rows: scales_fit asks for whole blocks below)
         return False
     pdt = torch.float32 if mixed else x2.dtype      # fp32 master factors (mixed: under autocast), or parameters of the input's dtype
     for t, want in ((A, pdt), (B, pdt), (bias, pdt), (acc_down if kind == _lib.ACC_DENSE else None, x2.dtype)):
@@ -575,21 +529,16 @@ def skinny_admits(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, 
             return False
     if pdt != x2.dtype:
         dt |= _lib.PARAM_F32 | _lib.ACC_NATIVE
-    if kind == _lib.ACC_DENSE_FP8:
-        if (acc_up is None or acc_up.dtype != torch.int8 or tuple(acc_up.shape) != (d_out,) or acc_down.device != x2.device
-                or acc_up.device != x2.device or not skinny_fp8_pays(T, d_in, d_out)):
-            return False
-    if kind == _lib.ACC_DENSE_FP4:
-        if (acc_up is None or acc_up.dtype != torch.uint8 or d_in % FP4_BLOCK or tuple(acc_up.shape) != (d_in // FP4_BLOCK, d_out)
-                or acc_down.device != x2.device or acc_up.device != x2.device or not skinny_fp4_pays(T, d_in, d_out)):
-            return False
+    if fmt is not None and (acc_up is None or not fmt.scales_fit(acc_up, d_in, d_out) or acc_down.device != x2.device
+                            or acc_up.device != x2.device or not fmt.pays(T, d_in, d_out)):
+        return False
     return skinny_pays(T, d_in, d_out) and skinny_workspace_bytes(T, d_in, d_out, r, kind, dt) > 0
 
 
 def sow_forward_skinny(layers) -> Optional[list]:
     """y_i of n <= 16 independent generation-sized layer calls (T_i <= 32 tokens) in two launches (include/sow_amd.h:
     sow_forward_skinny).  `layers`: one (x2, A, B, acc_down, bias, scale) per layer -- x2 [T, d_in] bf16 / f16, acc_down the
-    dense accumulator, the (codes, exponents) pair of an E4M3 one, or None.  A, B and bias are of x2's dtype, or fp32 in every
+    dense accumulator, the (codes, scales) pair of a quantised one (TypeError unless well formed: acc_format.py), or None.  A, B and bias are of x2's dtype, or fp32 in every
     layer of the call (SOW_PARAM_F32 | SOW_ACC_NATIVE: rounded once in registers, the accumulator stays of x2's dtype).  Returns the list of outputs, or None when the library refuses the set (nothing was launched:
     the caller runs sow_forward / LayerGroup instead)."""
     lib = _lib.load()
@@ -605,15 +554,12 @@ def sow_forward_skinny(layers) -> Optional[list]:
         pdt, dt = torch.float32, dt | _lib.PARAM_F32 | _lib.ACC_NATIVE
     keep, sizes, total = [], [], 0
     for x2, A, B, acc_down, bias, scale in layers:
-        exps = None
+        exps = fmt = None
         if isinstance(acc_down, tuple):
             acc_down, exps = acc_down
-            if acc_down.dtype == FP4:
-                if exps.dtype != torch.uint8 or acc_down.dim() != 2 or tuple(exps.shape) != (acc_down.shape[0] // 16, acc_down.shape[1]):
-                    raise TypeError("sow_amd.sow_forward_skinny: an MXFP4 accumulator is (packed uint8 codes [d_in / 2, d_out], "
-                                    "uint8 block scales [d_in / 32, d_out])")
-            elif acc_down.dtype != FP8 or exps.dtype != torch.int8 or tuple(exps.shape) != (acc_down.shape[-1],):
-                raise TypeError("sow_amd.sow_forward_skinny: an E4M3 accumulator is (float8_e4m3fn codes, int8 exponents)")
+            fmt = BY_CODE_DTYPE.get(acc_down.dtype)
+            if fmt is None or not fmt.well_formed(acc_down, exps):
+                raise TypeError(f"sow_amd.sow_forward_skinny: {_NOT_A_PAIR}")
         dev = _need_gpu(x2, A, B, acc_down, exps, bias)
         if dev != x0.device or any(t is not None and t.dtype != x0.dtype for t in (x2, acc_down if exps is None else None)) or any(
                 t is not None and t.dtype != pdt for t in (A, B, bias)):
@@ -621,11 +567,10 @@ def sow_forward_skinny(layers) -> Optional[list]:
                             "and biases one dtype (the inputs', or float32), and all tensors one device")
         T, d_in = x2.shape
         r, d_out = B.shape
-        if tuple(A.shape) != (d_in, r) or (acc_down is not None and acc_logical_shape(acc_down) != (d_in, d_out)) or (
+        if tuple(A.shape) != (d_in, r) or (acc_down is not None and (fmt.logical_shape(acc_down) if fmt else tuple(acc_down.shape[:2])) != (d_in, d_out)) or (
                 bias is not None and tuple(bias.shape) != (d_out,)):
             raise ValueError("sow_amd.sow_forward_skinny: operand shapes do not match")
-        kind = (_lib.ACC_NONE if acc_down is None else _lib.ACC_DENSE if exps is None
-                else _lib.ACC_DENSE_FP4 if acc_down.dtype == FP4 else _lib.ACC_DENSE_FP8)
+        kind = _lib.ACC_NONE if acc_down is None else _lib.ACC_DENSE if fmt is None else fmt.kind
         nws = skinny_workspace_bytes(T, d_in, d_out, r, kind, dt) if T else 0
         if T and not nws:
             return None

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 import fp4_acc_ref as R
-from sow_amd import fp8_acc
+from sow_amd import acc_quant
 
 BF16, F16 = torch.bfloat16, torch.float16
 DTYPES = [BF16, F16]
@@ -32,7 +32,7 @@ def _column(vals, dtype, rows=32):
 def _both(W):
     """The reference's and the package's quantisation of W, asserted bit-identical; returns (codes, scale bytes)."""
     codes, scales = R.quantize(W)
-    q, s = fp8_acc.quantize_tensor_fp4(W)
+    q, s = acc_quant.quantize_tensor(W, "mxfp4")
     assert q.dtype == torch.uint8 and s.dtype == torch.uint8
     assert q.shape == (W.shape[0] // 2, W.shape[1]) and s.shape == (W.shape[0] // 32, W.shape[1])
     assert torch.equal(s, scales), f"scales differ: {s[s != scales][:8].tolist()} vs {scales[s != scales][:8].tolist()}"
@@ -208,20 +208,20 @@ def test_non_finite_is_refused(bad):
     W = torch.zeros(32, 8, dtype=BF16)
     W[2, 5] = bad
     with pytest.raises(ValueError):
-        fp8_acc.quantize_tensor_fp4(W)
+        acc_quant.quantize_tensor(W, "mxfp4")
     with pytest.raises(ValueError):
         R.quantize(W)
 
 
 def test_other_dtypes_shapes_and_formats_are_refused():
     with pytest.raises(TypeError):
-        fp8_acc.quantize_tensor_fp4(torch.zeros(32, 8))
+        acc_quant.quantize_tensor(torch.zeros(32, 8), "mxfp4")
     with pytest.raises(ValueError):
-        fp8_acc.quantize_tensor_fp4(torch.zeros(24, 8, dtype=BF16))
+        acc_quant.quantize_tensor(torch.zeros(24, 8, dtype=BF16), "mxfp4")
     with pytest.raises(ValueError):
-        fp8_acc.quantize_accumulators(torch.nn.Linear(8, 8), fmt="int4")
-    assert "mxfp4" in fp8_acc.FORMATS and "fp8_e4m3" in fp8_acc.FORMATS
-    assert fp8_acc.quantize_accumulators(torch.nn.Linear(8, 8), fmt="mxfp4") == 0
+        acc_quant.quantize_accumulators(torch.nn.Linear(8, 8), fmt="int4")
+    assert "mxfp4" in acc_quant.FORMATS and "fp8_e4m3" in acc_quant.FORMATS
+    assert acc_quant.quantize_accumulators(torch.nn.Linear(8, 8), fmt="mxfp4") == 0
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=_ID)

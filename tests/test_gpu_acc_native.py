@@ -18,7 +18,7 @@ import torch.nn as nn
 
 import graph_replay as GR
 import test_gpu_elementwise as E
-from sow_amd import (FactorBucket, SoWLinear, _lib, dequantize_accumulators, factor_parameters, fp8_acc, group_siblings, ops,
+from sow_amd import (FactorBucket, SoWLinear, _lib, dequantize_accumulators, factor_parameters, acc_quant, group_siblings, ops,
                      quantize_accumulators)
 
 pytestmark = pytest.mark.gpu
@@ -226,9 +226,9 @@ def _skinny_layer(cd, kind, T, d_in, d_out, r, bias, seed=0):
     d = _operands(cd, T, d_in, d_out, r, bias, "dense" if kind != "none" else None, seed=seed)
     acc_down, acc_up = _dev(d["acc_down"]), None
     if kind == "e4m3":
-        acc_down, acc_up = fp8_acc.quantize_tensor(acc_down)
+        acc_down, acc_up = acc_quant.quantize_tensor(acc_down)
     elif kind == "mxfp4":
-        acc_down, acc_up = fp8_acc.quantize_tensor_fp4(acc_down)
+        acc_down, acc_up = acc_quant.quantize_tensor(acc_down, "mxfp4")
     return dict(d, q_down=acc_down, q_up=acc_up, kind=KINDS[kind])
 
 
@@ -484,7 +484,7 @@ def test_check_accumulator_forms():
                               param_dtype=F32)
     with pytest.raises(TypeError, match="dtype mismatch"):      # outside mixed precision nothing changes
         ops.check_accumulator(x, 64, 64, torch.zeros(64, 64, device=DEV, dtype=F32), None)
-    codes, exps = fp8_acc.quantize_tensor(torch.randn(64, 64, device=DEV).to(BF16))
+    codes, exps = acc_quant.quantize_tensor(torch.randn(64, 64, device=DEV).to(BF16))
     assert ops.check_accumulator(x, 64, 64, codes, exps, param_dtype=F32)[0] == _lib.ACC_DENSE_FP8
 
 

@@ -26,7 +26,7 @@ import test_gpu_fp8_acc as F8
 import test_gpu_skinny as S
 import value_plan as VP
 from numerics import bound, fp32_floor, rne, to64, ulp
-from sow_amd import _lib, dequantize_accumulators, fp8_acc, ops, quantize_accumulators
+from sow_amd import _lib, dequantize_accumulators, acc_quant, ops, quantize_accumulators
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -191,7 +191,7 @@ def test_quantiser_matches_the_reference_bit_for_bit(dt):
     W[:, 25] = (torch.randint(-24, 25, (160,), generator=g).double() * 0.25 * 2.0 ** -5).to(dtype)   # exact ties
     W[::32, 25] = 6.0 * 2.0 ** -5
     codes, scales = R.quantize(W)
-    q, e = fp8_acc.quantize_tensor_fp4(W.to(DEV))
+    q, e = acc_quant.quantize_tensor(W.to(DEV), "mxfp4")
     assert q.is_cuda and q.dtype == torch.uint8 and e.dtype == torch.uint8 and q.is_contiguous() and e.is_contiguous()
     assert q.shape == (80, 136) and e.shape == (5, 136)
     assert torch.equal(e.cpu(), scales), "scale bytes"
@@ -202,7 +202,7 @@ def test_quantiser_matches_the_reference_bit_for_bit(dt):
     with pytest.raises(ValueError):
         bad_w = W.to(DEV)
         bad_w[3, 4] = float("inf")
-        fp8_acc.quantize_tensor_fp4(bad_w)
+        acc_quant.quantize_tensor(bad_w, "mxfp4")
 
 
 # ---- 3. one-hot rows: y[t, :] = W^[k_t, :] -------------------------------------------------------------------------------------------
@@ -328,7 +328,7 @@ def test_skinny_ring_refill():
     lib = _lib.load()
     assert lib.sow_forward_skinny_fp4_workspace_bytes(32, 4128, 8200, 8, _lib.BF16) == 256 + 7 * 32 * (8200 + 64) * 4
     d = _clear_of_ties(BF16, 32, 4128, 8200, 8, False, 1.0, seed=41)
-    q, e = fp8_acc.quantize_tensor_fp4(d["W"].to(DEV))          # (tied to the reference by the quantiser tests)
+    q, e = acc_quant.quantize_tensor(d["W"].to(DEV), "mxfp4")          # (tied to the reference by the quantiser tests)
     codes, scales = q.cpu(), e.cpu()
     d = dict(d, W=R.dequantize(codes, scales, BF16), q=codes, e=scales)
     (y,) = _run(BF16, [d], runs=(0xFF, 0x00), what="ring refill")

@@ -22,7 +22,7 @@ import test_gpu_elementwise as E
 import test_gpu_skinny as S
 import value_plan as VP
 from numerics import fp32_floor, rne, to64, ulp
-from sow_amd import _lib, dequantize_accumulators, fp8_acc, ops, quantize_accumulators
+from sow_amd import _lib, dequantize_accumulators, acc_quant, ops, quantize_accumulators
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -41,7 +41,7 @@ def _quant(W):
     if W.numel() <= 1 << 20:
         codes, exps = R.quantize(W)
     else:
-        q, e = fp8_acc.quantize_tensor(W.to(DEV))
+        q, e = acc_quant.quantize_tensor(W.to(DEV))
         codes, exps = q.view(torch.uint8).cpu(), e.cpu()
     img = R.dequantize(codes, exps)
     what = img.to(W.dtype)
@@ -161,7 +161,7 @@ def test_quantiser_matches_the_reference_bit_for_bit(dt, shape):
     W[:, 25] = (torch.randn(shape[0], generator=g) * 2.0 ** -18).to(dtype)          # the f16 lower clamp: e = -15 clamps amax ~ 2^-16
     W[:, 33] = (torch.randn(shape[0], generator=g).clamp(-1, 1) * 448 * 2.0 ** -15).to(dtype)
     codes, exps = R.quantize(W)
-    q, e = fp8_acc.quantize_tensor(W.to(DEV))
+    q, e = acc_quant.quantize_tensor(W.to(DEV))
     assert q.is_cuda and q.dtype == FP8 and e.dtype == torch.int8 and q.is_contiguous()
     assert torch.equal(e.cpu(), exps), "exponents"
     bad = q.view(torch.uint8).cpu() != codes
@@ -176,7 +176,7 @@ def test_quantiser_refuses_non_finite():
     W = torch.zeros(16, 16, dtype=BF16, device=DEV)
     W[3, 4] = float("inf")
     with pytest.raises(ValueError):
-        fp8_acc.quantize_tensor(W)
+        acc_quant.quantize_tensor(W)
 
 
 # ---- the image pass ----------------------------------------------------------------------------------------------------------

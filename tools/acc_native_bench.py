@@ -23,7 +23,7 @@ import sys
 import torch
 
 sys.path.insert(0, __import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__))))
-from sow_amd import _lib, fp8_acc  # noqa: E402
+from sow_amd import _lib, acc_quant  # noqa: E402
 from tools.fp8_acc_bench import TIMED, WARM, measure  # noqa: E402
 from tools.skinny_bench import copy_rate  # noqa: E402
 
@@ -96,8 +96,8 @@ class Skinny:
         self.keep, self.calls = [], {"h": [], "f": []}
         for _ in range(self.copies):
             W = rnd(d_in, d_out, std=0.02).to(BF16)
-            acc_down, acc_up = ((W, None) if kind == "plain" else fp8_acc.quantize_tensor(W) if kind == "e4m3"
-                                else fp8_acc.quantize_tensor_fp4(W))
+            acc_down, acc_up = ((W, None) if kind == "plain" else acc_quant.quantize_tensor(W) if kind == "e4m3"
+                                else acc_quant.quantize_tensor(W, "mxfp4"))
             A32, B32, b32 = rnd(d_in, r, std=0.05), rnd(r, d_out, std=0.05), rnd(d_out, std=0.1)
             y = torch.empty(T, d_out, device=DEV, dtype=BF16)
             ws = torch.empty(nws, device=DEV, dtype=torch.uint8)

@@ -21,7 +21,7 @@ import sys
 import torch
 
 sys.path.insert(0, __import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__))))
-from sow_amd import _lib, fp8_acc  # noqa: E402
+from sow_amd import _lib, acc_quant  # noqa: E402
 from tools import fp8_acc_bench as B8  # noqa: E402
 from tools.skinny_bench import copy_rate  # noqa: E402
 
@@ -50,8 +50,8 @@ class Skinny:
             arrs = {k: (_lib.LayerArgs * n)() for k in self.calls}
             for i in range(n):
                 W = torch.randn(d_in, d_out, device=DEV, dtype=BF16, generator=g) * 0.02
-                q8, e8 = fp8_acc.quantize_tensor(W)
-                q4, e4 = fp8_acc.quantize_tensor_fp4(W)
+                q8, e8 = acc_quant.quantize_tensor(W)
+                q4, e4 = acc_quant.quantize_tensor(W, "mxfp4")
                 A, Bm = rnd(d_in, r, std=0.05), rnd(r, d_out, std=0.05)
                 y = torch.empty(T, d_out, device=DEV, dtype=BF16)
                 ws = torch.empty(nws, device=DEV, dtype=torch.uint8)
@@ -90,7 +90,7 @@ class Long(B8.Long):
 
     def __init__(self, T, d_in, d_out, r=50):
         super().__init__(T, d_in, d_out, r)
-        self.fp4 = [fp8_acc.quantize_tensor_fp4(s[0]) for s in self.sets]
+        self.fp4 = [acc_quant.quantize_tensor(s[0], "mxfp4") for s in self.sets]
 
     def deq(self, j):
         q, e = self.fp4[j % self.copies]

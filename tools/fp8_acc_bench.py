@@ -21,7 +21,7 @@ import sys
 import torch
 
 sys.path.insert(0, __import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__))))
-from sow_amd import _lib, fp8_acc  # noqa: E402
+from sow_amd import _lib, acc_quant  # noqa: E402
 from tools.skinny_bench import copy_rate  # noqa: E402
 
 DEV = torch.device("cuda:0")
@@ -36,7 +36,7 @@ WARM, TIMED = 3, 24
 
 def _weights(d_in, d_out, g):
     W = torch.randn(d_in, d_out, device=DEV, dtype=BF16, generator=g) * 0.02
-    q, e = fp8_acc.quantize_tensor(W)
+    q, e = acc_quant.quantize_tensor(W)
     return W, q, e
 
 
