@@ -7,6 +7,13 @@
 * groups: sets of 2 - 4 layers through sow_forward_group / sow_backward_group, a share with the deferred reduction;
 * shared: sibling sets inside chain2_shared_supported;
 * gemms: sow_gemm_ex in bf16 / f16 / fp32, every transpose combination, strided operands.
+A second stream (seed + 1, drawn after the four lists above, which it leaves what they were) covers the families that landed
+after the first sweep:
+* skinny / skinny_groups: sow_forward_skinny per accumulator kind, every slab length, tail and column class of skinny_plan
+  (mirrored below), odd ranks, grouped calls whose layers differ in T, d_in and slab length;
+* fused / deep: SOW_FUSE_ACC and SOW_FUSE_ACC_DEEP layers over every r_pad; shared_acc: sibling sets of
+  sow_backward_shared | SOW_FUSE_ACC inside the LDS rule, one exactly at it;
+* eight ragged layers with a dense accumulator (gemm_rag_kernel), appended to `layers`.
 
 Every case's id names its shape, so that a failure names its case.  `ref_cost` is the float64 reference work of a case
 (multiply-adds of the CPU products of the checks); the CPU test keeps every case under REF_COST_CAP.
@@ -20,16 +27,21 @@ from typing import List, Optional
 SEED = 20261016
 REF_COST_CAP = 6.0e10          # multiply-adds of one case's float64 reference
 LAYER_SWITCHES = ("NO_GEMM4H", "GEMM4", "GEMM3S", "NO_SPLITK", "NO_WIDE_CHAIN", "NO_RAGGED", "F32_EXACT", "FORCE_CHAIN_V1",
-                  "NO_CHAIN3F", "NO_TN_F32Q", "TN_NARROW")
+                  "NO_CHAIN3F", "NO_TN_F32Q", "TN_NARROW", "NO_RAGGED_GEMM")
 
 # the kernel families the sweep has to reach (test_zz_fuzz_coverage); "chain_wide_kernel" is counted apart for aligned and
-# ragged widths, gemm4_kernel as plain, h-fused and split-K
-FAMILIES = ("chain2_kernel", "chain2_f16_kernel", "h_reduce_kernel", "chain_kernel", "chain_wide_kernel[aligned]",
+# ragged widths, gemm4_kernel as plain, h-fused and split-K.  FAMILIES_FIRST: those of the first stream, which the chosen-value
+# cases of tests/value_plan.py are taken from; FAMILIES adds those of the second (skinny_a_kernel per accumulator format and
+# with fp32 factors)
+FAMILIES_SECOND = ("skinny_a_kernel[plain]", "skinny_a_kernel[e4m3]", "skinny_a_kernel[mxfp4]", "skinny_a_kernel[fp32-factors]",
+                   "skinny_b_kernel", "chain_wide_acc_kernel", "chain_deep_acc_kernel", "chain_shared_acc_kernel", "gemm_rag_kernel")
+FAMILIES_FIRST = ("chain2_kernel", "chain2_f16_kernel", "h_reduce_kernel", "chain_kernel", "chain_wide_kernel[aligned]",
             "chain_wide_kernel[ragged]", "chain3f_kernel", "chain2f_kernel", "chain2_shared_kernel",
             "tn_partial_dma_kernel|tn_partial_dma_wide_kernel", "tn_partial_rows_kernel", "tn_partial_kernel",
             "tnw_partial_kernel", "tn_partial_f32_quad_kernel", "tn_partial_dma_f32_kernel|tn_partial_dma_f32_wide_kernel",
             "colsum_kernel", "gemm4_kernel[plain]", "gemm4_kernel[h]", "gemm4_kernel[splitk]", "gemm4_f16_kernel",
             "gemm2h_kernel", "gemm2_kernel", "gemm3s_kernel", "gemm_x3_kernel", "gemm_kernel")
+FAMILIES = FAMILIES_FIRST + FAMILIES_SECOND
 
 
 @dataclasses.dataclass
@@ -151,6 +163,14 @@ def ref_cost(c) -> float:
         return sum(ref_cost(m) for m in c.layers)
     if isinstance(c, Shared):
         return sum(14.0 * c.T * (c.d_in + sb.d_out) * 64 for sb in c.sibs)
+    if isinstance(c, Skinny):       # x W and its squares once (the tie-clearing step keeps them), x A and h B per pass of it
+        return (2.0 * c.T * c.d_in * c.d_out if c.kind != "none" else 0.0) + 16.0 * c.T * (c.d_in + c.d_out) * 64
+    if isinstance(c, SkinnyGroup):
+        return sum(ref_cost(m) for m in c.layers)
+    if isinstance(c, Fused):        # fused_acc_numerics.check: the products over r_pad columns, forward and backward
+        return 14.0 * c.T * (c.d_in + c.d_out) * (64 + r_pad(c.r + c.r_acc))
+    if isinstance(c, SharedAcc):
+        return sum(6.0 * c.T * (c.d_in + sb.d_out) * r_pad(sb.r + sb.r_acc) for sb in c.sibs)   # shared_fused_acc_numerics.dx_reference
     return 2.0 * c.M * c.N * c.K
 
 
@@ -196,6 +216,21 @@ def _finish(c: Layer, tag):
         c.y_rounds = c.dx_rounds = "twice"
     c.name = _name(c, tag)
     return c
+
+
+def _wide_T(g, d_in, d_out, kind):
+    """T of a wide-rank layer by kind: below 64, below 256, or one past / one short of a slab boundary of tnw_pick_slabs."""
+    if kind == "T<64":
+        return g.randint(1, 63)
+    if kind == "T<256":
+        return g.randint(64, 255)
+    ns_lo = 2
+    for _ in range(10000):
+        T = g.randint(600, 8300)
+        ns, ln = tnw_pick_slabs(T, d_in, d_out)
+        if ns >= ns_lo and ((kind == "slab+1" and T % ln == 1) or (kind == "slab-1" and T % ln == ln - 1)):
+            return T
+    raise AssertionError("no slab boundary found")
 
 
 def _layers(d: _Draw) -> List[Layer]:
@@ -285,17 +320,7 @@ def _layers(d: _Draw) -> List[Layer]:
 
     # ---------------------------------------------------------------- bf16 / f16, even r in (64, 256]
     def wide_T(d_in, d_out, kind):
-        if kind == "T<64":
-            return g.randint(1, 63)
-        if kind == "T<256":
-            return g.randint(64, 255)
-        ns_lo = 2
-        for _ in range(10000):
-            T = g.randint(600, 8300)
-            ns, ln = tnw_pick_slabs(T, d_in, d_out)
-            if ns >= ns_lo and ((kind == "slab+1" and T % ln == 1) or (kind == "slab-1" and T % ln == ln - 1)):
-                return T
-        raise AssertionError("no slab boundary found")
+        return _wide_T(g, d_in, d_out, kind)
 
     kinds = ("T<64", "T<256", "slab+1", "slab-1")
     for i in range(12):   # aligned widths
@@ -518,14 +543,395 @@ def _x3_vec(M, N, K, ta, tb, lda, ldb, ldc):
     return mode(lda, not ta, M) and mode(ldb, tb, N) and ldc % 4 == 0 and N % 4 == 0 and K >= 16
 
 
+# ---- the second stream: the kernel families that landed after the first sweep ------------------------------------------------
+@dataclasses.dataclass
+class Skinny:
+    name: str
+    dtype: str                  # "bf16" | "f16"
+    kind: str                   # SK_KINDS: the accumulator of sow_forward_skinny
+    T: int
+    d_in: int
+    d_out: int
+    r: int
+    bias: bool
+    s: float
+    f32: bool                   # fp32 factors (SOW_PARAM_F32 | SOW_ACC_NATIVE)
+    seed: int
+
+
+@dataclasses.dataclass
+class SkinnyGroup:
+    name: str
+    dtype: str
+    kind: str                   # the kind of the call's dense layers ("none": no layer has an accumulator)
+    layers: List[Skinny]
+    x_shared: bool              # every layer reads the first layer's x buffer (one T and d_in in the call)
+    f32: bool
+
+
+@dataclasses.dataclass
+class Fused:
+    name: str
+    dtype: str
+    T: int
+    d_in: int
+    d_out: int
+    r: int
+    r_acc: int
+    bias: bool
+    s: float
+    save_h: bool
+    group: bool                 # through sow_forward_group / sow_backward_group as a group of one
+    deep: bool                  # SOW_FUSE_ACC_DEEP (r + r_acc > 256)
+    seed: int
+
+
+@dataclasses.dataclass
+class AccSib:
+    d_out: int
+    r: int
+    r_acc: int
+    s: float
+
+
+@dataclasses.dataclass
+class SharedAcc:
+    name: str
+    dtype: str
+    T: int
+    d_in: int
+    sibs: List[AccSib]
+    grad_beta: float
+    seed: int
+
+
+SK_KINDS = ("dense", "e4m3", "mxfp4", "none")
+SK_KS = (128, 256, 384, 512, 640, 768, 896, 1024)
+SK_R_EDGES = (1, 15, 16, 17, 31, 32, 33, 47, 48, 49, 63, 64)   # around the x A tile counts (16 columns each)
+SK_T_EDGES = (1, 15, 16, 17, 31, 32)                           # around the second row tile
+SK_TAILS = ("kgroup", "partial", ">512", "full")
+SK_COLS = ("lt", "8", "cn-8", "0")
+
+
+def al256(n):
+    return (n + 255) // 256 * 256
+
+
+def r_pad(tot):
+    return (tot + 63) // 64 * 64
+
+
+def sk_cn(kind):
+    """Columns per phase-A workgroup of the skinny forward: 128 for the code formats, else 64."""
+    return 128 if kind in ("e4m3", "mxfp4") else 64
+
+
+def sk_step(kind):
+    """What d_in is a multiple of: whole MXFP4 blocks of 32, else one k-group of 8."""
+    return 32 if kind == "mxfp4" else 8
+
+
+def skinny_plan(d_in, d_out, kind):
+    """skinny_fwd.hip skinny_plan: (slab count S, slab length KS, column ranges nc)."""
+    nc = cdiv(d_out, sk_cn(kind)) if kind != "none" else 0
+    want = cdiv(512, nc) if nc else 32
+    ks = min(max(cdiv(cdiv(d_in, want), 128) * 128, 128), 1024)
+    return cdiv(d_in, ks), ks, nc
+
+
+def skinny_ws_bytes(T, d_in, d_out, kind):
+    """api.hip skinny_ws: the answer of the three sow_forward_skinny*_workspace_bytes queries on an admitted shape."""
+    S = skinny_plan(d_in, d_out, kind)[0]
+    return 256 + (al256(S * T * d_out * 4) if kind != "none" else 0) + al256(S * T * 64 * 4)
+
+
+def skinny_tail(d_in, d_out, kind):
+    """Rows of the last K-slab."""
+    S, ks, _ = skinny_plan(d_in, d_out, kind)
+    return d_in - (S - 1) * ks
+
+
+def skinny_tail_classes(d_in, d_out, kind):
+    """SK_TAILS the last slab falls into: one k-group; otherwise no multiple of 128 (a partial round, idle waves); above 512
+    (a fifth k-step refills the request ring); a whole slab."""
+    tail, ks = skinny_tail(d_in, d_out, kind), skinny_plan(d_in, d_out, kind)[1]
+    out = set()
+    if tail == sk_step(kind):
+        out.add("kgroup")
+    elif tail % 128:
+        out.add("partial")
+    if tail > 512:
+        out.add(">512")
+    if tail == ks:
+        out.add("full")
+    return out
+
+
+def skinny_col_class(d_out, kind):
+    """SK_COLS of the last column range ("other": a residue the list does not name)."""
+    cn = sk_cn(kind)
+    if d_out < cn:
+        return "lt"
+    return {8: "8", cn - 8: "cn-8", 0: "0"}.get(d_out % cn, "other")
+
+
+def fused_acc_shape_ok(r, r_acc, d_in, d_out, dtype):
+    """chain_wide_acc.hip fused_acc_shape_ok: the admitted set of SOW_FUSE_ACC."""
+    return (dtype in ("bf16", "f16") and 2 <= r <= 64 and r % 2 == 0 and r_acc >= 2 and r_acc % 2 == 0 and r_acc + r <= 256
+            and d_in > 0 and d_out > 0 and d_in % 8 == 0 and d_out % 8 == 0)
+
+
+def deep_acc_shape_ok(r, r_acc, d_in, d_out, dtype):
+    """chain_deep_acc.hip deep_acc_shape_ok: the admitted set of SOW_FUSE_ACC_DEEP (DEEP_MAX_TOT = 960)."""
+    return (dtype in ("bf16", "f16") and 2 <= r <= 64 and r % 2 == 0 and r_acc >= 2 and r_acc % 2 == 0 and r_acc <= 960
+            and 256 < r_acc + r <= 960 and d_in > 0 and d_out > 0 and d_in % 8 == 0 and d_out % 8 == 0)
+
+
+SHARED_ACC_MAX_LDS = 160 * 1024
+
+
+def shared_acc_lds_bytes(r_tots):
+    """chain_shared_acc.hip shared_acc_lds_bytes of the siblings' r + r_acc: 128 sum r_pad + max(128 max r_pad + 8192, 24576)
+    (include/sow_amd.h); 0 outside 1 .. 4 siblings."""
+    if not 1 <= len(r_tots) <= 4:
+        return 0
+    pads = [r_pad(t) for t in r_tots]
+    return 128 * sum(pads) + max(128 * max(pads) + 8192, 24576)
+
+
+def shared_acc_lds_ok(r_tots):
+    b = shared_acc_lds_bytes(r_tots)
+    return b != 0 and b <= SHARED_ACC_MAX_LDS
+
+
+def sk_w_cap(kind, ks):
+    """The largest d_in x d_out a drawn single-layer case takes at slab length ks: 1.5 x the smallest W that plans ks (an
+    exhaustive search up to 9000 per side: 3.7 M elements per 128 rows of ks past the first for 64-column ranges, twice that
+    for the code formats; 4104 x 8 and 8200 x 8 without an accumulator); at ks = 128 every width plans it, and 2 M (4 M) is taken."""
+    if kind == "none":
+        return {128: 1 << 20, 256: 1.5 * 4104 * 8, 384: 1.5 * 8200 * 8}[ks]
+    return (sk_cn(kind) // 64) * (1.5 * 3.7e6 * (ks - 128) // 128 if ks > 128 else 2 << 20)
+
+
+def _skinny_shape(g, kind, ks, tail, col, big_s):
+    """(d_in, d_out) that plans slab length ks with the last slab in class `tail`, the last column range in class `col` and,
+    for big_s, more than 16 slabs: d_out first (it fixes nc and want), then d_in inside the band of ks and under sk_w_cap."""
+    cn, step, cap = sk_cn(kind), sk_step(kind), sk_w_cap(kind, ks)
+    for _ in range(2000):
+        if kind == "none" and ks > 128:
+            d_out = 8
+        else:
+            if col == "lt":
+                d_out = 8 * g.randint(1, cn // 8 - 1)
+            else:
+                # ranges: few where every width plans 128 rows, else as many as keep both sides under ~9000
+                nc = g.randint(2, 16) if ks == 128 else g.randint(9000 // cn // 2, 9000 // cn)
+                d_out = {"8": (nc - 1) * cn + 8, "cn-8": nc * cn - 8, "0": nc * cn}.get(col) or (nc - 1) * cn + 8 * g.randint(2, cn // 8 - 2)
+        _, _, nc = skinny_plan(step, d_out, kind)
+        want = cdiv(512, nc) if nc else 32
+        lo = want * (ks - 128) + 1 if ks > 128 else step
+        hi = min(want * ks if ks < 1024 else 1 << 30, int(cap // d_out), 8192 if ks == 128 else 1 << 30)
+        cands = []
+        for d_in in range(cdiv(lo, step) * step, hi + 1, step):
+            S, k, _ = skinny_plan(d_in, d_out, kind)
+            if k == ks and tail in skinny_tail_classes(d_in, d_out, kind) and (not big_s or S > 16):
+                cands.append(d_in)
+        if cands:
+            # (the matrices of 12 M elements and more: the lower quarter of the band, for the float64 reference's sake)
+            return g.choice(cands[:max(len(cands) // 4, 1)] if ks >= 512 else cands), d_out
+    raise AssertionError(f"no skinny shape for {kind} KS {ks} tail {tail} col {col}")
+
+
+def _sk_name(c: Skinny, tag):
+    S, ks, _ = skinny_plan(c.d_in, c.d_out, c.kind)
+    return (f"{tag}_{c.kind}_{c.dtype}_T{c.T}_{c.d_in}x{c.d_out}_r{c.r}_KS{ks}x{S}" + ("_bias" if c.bias else "")
+            + ("_f32" if c.f32 else ""))
+
+
+def _sk_settings(d: _Draw, c: Skinny):
+    g = d.g
+    c.bias = g.random() < 0.6
+    c.s = g.choice([1.0, 0.5, 0.25, 1.0 / c.r])
+    c.seed = d.n
+    d.n += 1
+    return c
+
+
+# per dense kind: slab length, tail class, column class and "more than 16 slabs" of its 16 cases.  Every slab length is reached;
+# one case at each length from 512 up (these are the 12 M to 58 M element matrices), the rest at 128, 256 and 384
+_SK_DENSE = ([(128, t, c, b) for t, c, b in (("kgroup", "lt", False), ("partial", "lt", False), ("full", "8", False),
+                                             ("kgroup", "cn-8", False), ("partial", "0", True))]
+             + [(256, "full", "other", False), (256, "kgroup", "8", False), (256, "partial", "cn-8", False),
+                (384, "full", "0", False), (384, "kgroup", "other", False), (384, "partial", "8", False),
+                (512, "full", "cn-8", False), (640, ">512", "0", False), (768, ">512", "other", False), (896, ">512", "8", False),
+                (1024, "partial", "cn-8", False)])
+_SK_NONE = [(128, "kgroup", "8", False), (128, "partial", "cn-8", False), (128, "full", "0", False), (128, "partial", "lt", False),
+            (256, "kgroup", "lt", True), (256, "partial", "lt", True), (384, "full", "lt", True), (384, "partial", "lt", True)]
+
+
+def _skinny(d: _Draw) -> List[Skinny]:
+    g = d.g
+    specs = [(kind,) + sp for kind in SK_KINDS[:3] for sp in _SK_DENSE] + [("none",) + sp for sp in _SK_NONE]
+    n = len(specs)
+    # r uniform over 1 .. 64 and T over 1 .. 32, every edge value once; drawn again until 20 ranks are odd
+    while True:
+        rs, Ts = [g.randint(1, 64) for _ in range(n)], [g.randint(1, 32) for _ in range(n)]
+        for v, i in zip(SK_R_EDGES, g.sample(range(n), len(SK_R_EDGES))):
+            rs[i] = v
+        for v, i in zip(SK_T_EDGES, g.sample(range(n), len(SK_T_EDGES))):
+            Ts[i] = v
+        if sum(r % 2 for r in rs) >= 20:
+            break
+    out = []
+    for j, (kind, ks, tail, col, big_s) in enumerate(specs):
+        d_in, d_out = _skinny_shape(g, kind, ks, tail, col, big_s)
+        c = _sk_settings(d, Skinny("", "bf16" if j % 2 == 0 else "f16", kind, Ts[j], d_in, d_out, rs[j], True, 1.0, j % 3 == 0, 0))
+        c.name = _sk_name(c, "sk")
+        out.append(c)
+    return out
+
+
+def _skinny_groups(d: _Draw) -> List[SkinnyGroup]:
+    g = d.g
+    out = []
+    calls = [(2, "dense"), (3, "e4m3"), (4, "mxfp4"), (7, "none"), (16, "dense"), (3, "e4m3"), (4, "mxfp4"), (2, "dense")]
+    for i, (n, kind) in enumerate(calls):
+        dt = "bf16" if i % 2 == 0 else "f16"
+        x_shared, f32 = i in (2, 5), i in (0, 5)
+        kinds = [kind] * n
+        if kind != "none":   # one or two layers without an accumulator share the call
+            for j in g.sample(range(n), 1 if n == 2 else g.randint(1, 2)):
+                kinds[j] = "none"
+        T0, din0 = g.randint(1, 32), 32 * g.randint(1, 32)
+        layers = []
+        for k in kinds:
+            if x_shared:
+                T, d_in = T0, din0
+                d_out = d.m8(8, 1024)
+            elif k == "none":   # d_in up to 12288: slabs of 256 and 384 rows next to the dense layers' 128
+                T, d_in = g.randint(1, 32), g.choice([d.m8(8, 4096), d.m8(4104, 12288)])
+                d_out = d.m8(8, min(1024, (1 << 20) // d_in))
+            else:               # W <= 1 M elements
+                T, d_out = g.randint(1, 32), d.m8(8, 1024)
+                d_in = sk_step(k) * g.randint(1, min(4096, (1 << 20) // d_out) // sk_step(k))
+            c = _sk_settings(d, Skinny("", dt, k, T, d_in, d_out, g.randint(1, 64), True, 1.0, f32, 0))
+            if f32 and layers:   # (the fp32-factor runner of test_gpu_acc_native takes one scale per call)
+                c.s = layers[0].s
+            c.name = _sk_name(c, f"skg{i}.{len(layers)}")
+            layers.append(c)
+        name = f"skgroup{i}_{kind}_{dt}_n{n}" + ("_xshared" if x_shared else "") + ("_f32" if f32 else "")
+        out.append(SkinnyGroup(name, dt, kind, layers, x_shared, f32))
+    return out
+
+
+def _fused_T(g, i):
+    if i == 5:
+        return g.randint(1000, 4200)
+    if i % 2 == 0:
+        return g.randint(1, 63)
+    return 64 * g.randint(1, 6) + g.choice([-1, 0, 1])
+
+
+def _split(g, tot, r=None):
+    """(r, r_acc) of even parts with r <= 64 and r + r_acc = tot."""
+    r = r or 2 * g.randint(1, min(64, tot - 2) // 2)
+    return r, tot - r
+
+
+def _fused(d: _Draw, deep: bool) -> List[Fused]:
+    """16 layers of the SOW_FUSE_ACC set (deep: of SOW_FUSE_ACC_DEEP): the r_pad values in turn, r + r_acc drawn inside each;
+    h_save = NULL for about an eighth (and for case 7), every fourth case as a group of one."""
+    g = d.g
+    out = []
+    pads = list(range(320, 961, 64)) if deep else [64, 128, 192, 256]
+    for i in range(16):
+        pad = pads[i % len(pads)]
+        tot = 2 * g.randint(max(pad - 62, 258 if deep else 4) // 2, pad // 2)
+        r = None
+        if deep:
+            if i < 11 and pad in (320, 576, 832):   # the live columns [r_acc, r_acc + r) straddle the group boundary at pad - 64
+                tot = pad - 64 + 2 * g.randint(1, 30)
+                r = 2 * g.randint((tot - (pad - 64)) // 2 + 1, 32)
+            elif pad in (384, 960) and i < 11:
+                r = 64
+        elif i < 3:                                 # (r + r_acc) % 64 of 0, 2 and 62
+            tot = pad + (0, -62, -2)[i]
+        r, r_acc = _split(g, tot, r)
+        c = Fused("", "bf16" if i % 2 == 0 else "f16", _fused_T(g, i), d.m8(8, 600), d.m8(8, 600), r, r_acc, g.random() < 0.6,
+                  1.0, i != 7 and g.random() >= 0.12, i % 4 == 3, deep, d.n)
+        c.s = g.choice([1.0, 0.5, 1.0 / c.r, 2.0])
+        d.n += 1
+        assert (deep_acc_shape_ok if deep else fused_acc_shape_ok)(c.r, c.r_acc, c.d_in, c.d_out, c.dtype), c
+        c.name = (f"{'deep' if deep else 'fused'}_{c.dtype}_T{c.T}_{c.d_in}x{c.d_out}_r{c.r}_acc{c.r_acc}" + ("_bias" if c.bias else "")
+                  + ("" if c.save_h else "_noh") + ("_group" if c.group else ""))
+        out.append(c)
+    return out
+
+
+def _shared_acc(d: _Draw) -> List[SharedAcc]:
+    g = d.g
+    out = []
+    for i in range(8):
+        dt = "f16" if i in (3, 6) else "bf16"
+        if i == 0:     # 15 panels: 120 KiB of factors + 40 KiB of stage = exactly 160 KiB
+            pads = [256, 256, 256, 192]
+        else:
+            while True:
+                pads = [64 * g.randint(1, 4) for _ in range(4 if i == 1 else g.randint(1, 4))]
+                if shared_acc_lds_ok(pads):
+                    break
+        sibs = []
+        for pad in pads:
+            r, r_acc = _split(g, 2 * g.randint(max(pad - 62, 4) // 2, pad // 2))
+            sibs.append(AccSib(d.m8(24, 520), r, r_acc, g.choice([1.0, 0.5, 0.75])))
+        T, d_in = g.randint(8193, 8800), d.m8(8, 520)
+        name = f"sharedacc{i}_{dt}_T{T}_in{d_in}_" + "_".join(f"{sb.d_out}r{sb.r}a{sb.r_acc}" for sb in sibs)
+        out.append(SharedAcc(name, dt, T, d_in, sibs, g.choice([0.0, 0.5, 1.0]), d.n))
+        d.n += 1
+    return out
+
+
+def _ragged_dense(d: _Draw) -> List[Layer]:
+    """Ragged widths with a dense accumulator: x W_acc by gemm_rag_kernel, then the ragged chain with beta = 1."""
+    g = d.g
+    out = []
+    kinds = ("T<64", "T<256", "slab+1", "slab-1")
+    for i in range(8):
+        res = g.randint(1, 7)
+        rag, other = 8 * g.randint(8, 70) + res, d.m8(64, 560)
+        d_in, d_out = (rag, other) if i < 4 else (other, rag)
+        kind = kinds[i % 4]
+        c = Layer("", "bf16" if i % 2 == 0 else "f16", _wide_T(g, d_in, d_out, kind), d_in, d_out, d.even(66, 256), acc="dense",
+                  stratum="ragged", family="gemm_rag_kernel", y_rounds="twice", dx_rounds="twice",
+                  edges=(kind, f"rag_{'in' if i < 4 else 'out'}_{res}"))
+        d.settings(c, h_null_ok=False)
+        if i == 6:
+            c.switches, c.family = {"NO_RAGGED_GEMM": 1}, "gemm_kernel"
+        c.name = _name(c, "ragdense")
+        out.append(c)
+    return out
+
+
 @dataclasses.dataclass
 class Plan:
     layers: List[Layer]
     groups: List[Group]
     shared: List[Shared]
     gemms: List[Gemm]
+    skinny: List[Skinny]
+    skinny_groups: List[SkinnyGroup]
+    fused: List[Fused]
+    deep: List[Fused]
+    shared_acc: List[SharedAcc]
+
+
+N_FIRST_LAYERS = 103   # layers of the first stream; the second stream's dense ragged layers follow them in Plan.layers
 
 
 def plan(seed: int = SEED) -> Plan:
     d = _Draw(seed)
-    return Plan(_layers(d), _groups(d), _shared(d), _gemms(d))
+    first = (_layers(d), _groups(d), _shared(d), _gemms(d))
+    d2 = _Draw(seed + 1)     # a stream of its own: the four lists above stay what they were, case for case
+    d2.n = 1000
+    second = (_skinny(d2), _skinny_groups(d2), _fused(d2, False), _fused(d2, True), _shared_acc(d2))
+    return Plan(first[0] + _ragged_dense(d2), *first[1:], *second)

@@ -21,11 +21,12 @@ import torch.nn as nn
 
 import fp4_acc_ref as R
 import graph_replay as GR
+import skinny_sweep as SW
 import test_gpu_elementwise as E
 import test_gpu_fp8_acc as F8
 import test_gpu_skinny as S
 import value_plan as VP
-from numerics import bound, fp32_floor, rne, to64, ulp
+from numerics import rne, to64
 from sow_amd import _lib, dequantize_accumulators, acc_quant, ops, quantize_accumulators
 
 pytestmark = pytest.mark.gpu
@@ -264,25 +265,7 @@ def _off_ties(dtype, d):
     1.02e-5 = ulp(h) B[1, 250] away.  An element (t, j) MATTERS when such a move would exceed an eighth of the comparator's own
     bound somewhere in its row; while one that matters is within the noise of a tie, one more element of column j of A is moved
     by one ulp (each element at most once), which shifts the column's h by about s x[t, k] ulp(A).  Returns (d, elements moved)."""
-    A = d["A"].clone()
-    d = dict(d, A=A)
-    x, B, sc = to64(d["x"]), to64(d["B"]), d["s"]
-    nxt = [0] * A.shape[1]
-    for _ in range(4 * A.shape[0]):
-        y_ref, y_sq, n_y = S._reference(dtype, {k: v for k, v in d.items() if k not in ("q", "e")})
-        bnd = bound(y_ref, dtype, fp32_floor(y_sq, n_y))
-        h = sc * (x @ to64(A))
-        half, noise = ulp(h, dtype) / 2, fp32_floor(sc * sc * (x * x) @ (to64(A) * to64(A)), 64)
-        near = (half - (h - rne(h, dtype)).abs()) <= noise
-        impact = torch.stack([2 * half[t] * (B.abs() / bnd[t]).amax(dim=1) for t in range(h.shape[0])])
-        cols = sorted(set(torch.nonzero(near & (half > noise) & (impact > 0.125))[:, 1].tolist()))
-        if not cols:
-            return d, sum(nxt)
-        for j in cols:
-            assert nxt[j] < A.shape[0], f"column {j} of h stays on a rounding tie"
-            A[nxt[j]:nxt[j] + 1, j].view(torch.int16).add_(1)
-            nxt[j] += 1
-    raise AssertionError("the projections stay on rounding ties")
+    return SW.off_ties(dtype, d)   # (the step itself, shared with the seeded sweep: a plain W or none pass through it too)
 
 
 @pytest.mark.parametrize("T", [1, 4, 17, 32])

@@ -6,6 +6,10 @@ bit-identical.  The third run is traced (torch.profiler):
 * the kernel family the plan targets has to appear -- a case that falls back to another kernel fails;
 * the rounding class of y and of dX is read off the trace (a fused single-accumulator path rounds once; an accumulator
   product followed by the chain with beta = 1 rounds twice) and has to agree with the plan's;
+* the second stream of the plan runs each family through that family's own runner and comparator: the skinny forward
+  (test_gpu_skinny, test_gpu_fp8_acc, test_gpu_fp4_acc, the fp32-factor runner of test_gpu_acc_native) on operands cleared of
+  rounding ties (skinny_sweep.py), the fused accumulator passes (test_gpu_fused_acc, test_gpu_deep_acc), the shared-input data
+  gradient of low-rank siblings (test_gpu_shared_fused_acc); the dense ragged layers are cases of test_fuzz_layer;
 * test_zz_fuzz_coverage (last) asserts that every family of fuzz_plan.FAMILIES was reached by >= 3 cases and prints the
   counts and the worst err / limit of the cases that ran each family.
 """
@@ -14,11 +18,22 @@ import ctypes
 import pytest
 import torch
 
+import fp4_acc_ref as R4
+import fused_acc_numerics as FA
 import fuzz_plan as FP
+import shared_fused_acc_numerics as SN
+import skinny_sweep as SW
+import test_gpu_acc_native as AN
+import test_gpu_deep_acc as DE
 import test_gpu_elementwise as E
+import test_gpu_fp4_acc as F4
+import test_gpu_fp8_acc as F8
+import test_gpu_fused_acc as FU
+import test_gpu_shared_fused_acc as SA
 import test_gpu_shared_input as S
-from numerics import check_bound, check_gaps, fp32_floor, gemm_epilogue, gemm_f32_bound, to64
-from sow_amd import _lib
+import test_gpu_skinny as SK
+from numerics import check_bound, check_gaps, check_h_save, fp32_floor, gemm_epilogue, gemm_f32_bound, to64
+from sow_amd import _lib, acc_quant
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -32,7 +47,7 @@ GEMMS = ("gemm_kernel", "gemm_x3_kernel", "gemm2_kernel", "gemm2h_kernel", "gemm
 KNOWN = CHAINS + GEMMS + ("h_reduce_kernel", "tn_partial_dma_kernel", "tn_partial_dma_wide_kernel", "tn_partial_rows_kernel",
                           "tn_partial_kernel", "tnw_partial_kernel", "tn_partial_f32_quad_kernel", "tn_partial_dma_f32_kernel",
                           "tn_partial_dma_f32_wide_kernel", "colsum_kernel", "gemm4_splitk_reduce_kernel",
-                          "gemm4_f16_splitk_reduce_kernel")
+                          "gemm4_f16_splitk_reduce_kernel", "gemm_rag_kernel")
 SEEN = {}        # family label -> set of case names
 WORST = {}       # family label -> (worst err / limit, case)
 RAN = set()      # cases that reached their checks
@@ -376,11 +391,210 @@ def run_gemm(gm, a, bm, bias, c0):
     return runs[0].cpu(), seq
 
 
+# ---------------------------------------------------------------------------------------------------------------- skinny
+def _quant4(W):
+    """test_gpu_fp4_acc._quant; matrices past 1 M elements through the package's quantiser on the GPU, which
+    test_gpu_fp4_acc.test_quantiser_* tie to the reference bit for bit (as test_gpu_fp8_acc._quant does)."""
+    if W.numel() <= 1 << 20:
+        return F4._quant(W)
+    q, e = acc_quant.quantize_tensor(W.to(DEV), "mxfp4")
+    codes, scales = q.cpu(), e.cpu()
+    return codes, scales, R4.dequantize(codes, scales, W.dtype)
+
+
+# per accumulator kind: (runner, comparator, the prefix under which the comparator files its worst ratio, quantiser, label)
+SKINNY = {"dense": (SK._run, SK._check, "", None, "skinny_a_kernel[plain]"),
+          "none": (SK._run, SK._check, "", None, "skinny_a_kernel[plain]"),
+          "e4m3": (F8._run, F8._check, "fp8_", F8._quant, "skinny_a_kernel[e4m3]"),
+          "mxfp4": (F4._run, F4._check, "fp4_", _quant4, "skinny_a_kernel[mxfp4]")}
+
+
+def _ours(seq):
+    """The library's kernels of a trace (the rest: torch's fills and copies of the buffer protocol)."""
+    return [k for k in seq if "sow::" in k or "3sow" in k]
+
+
+def _skinny_trace(seq, name):
+    """One launch of each skinny kernel and nothing else of the library: nothing else writes y."""
+    ours = _ours(seq)
+    a, b = sum(_is(k, "skinny_a_kernel") for k in ours), sum(_is(k, "skinny_b_kernel") for k in ours)
+    assert a == 1 and b == 1 and len(ours) == 2, f"{name}: the trace holds {ours}"
+
+
+def _skinny_query(c, code):
+    """The workspace query of the case's kind under the dtype code `code`, asserted equal to the plan's mirror."""
+    lib = _lib.load()
+    if c.kind == "e4m3":
+        got = lib.sow_forward_skinny_fp8_workspace_bytes(c.T, c.d_in, c.d_out, c.r, code)
+    elif c.kind == "mxfp4":
+        got = lib.sow_forward_skinny_fp4_workspace_bytes(c.T, c.d_in, c.d_out, c.r, code)
+    else:
+        got = lib.sow_forward_skinny_workspace_bytes(c.T, c.d_in, c.d_out, c.r, AN.KINDS[c.kind], code)
+    want = FP.skinny_ws_bytes(c.T, c.d_in, c.d_out, c.kind)
+    assert got == want, f"{c.name}: the workspace query says {got}, fuzz_plan.skinny_ws_bytes {want}"
+
+
+def _skinny_runs(run, dtype, ds, x_shared, name):
+    """Three runs of one sow_forward_skinny call through the family's runner (poisoned, zeroed: bit-identical, guards intact;
+    poisoned again on fresh buffers, traced: bit-identical to the first).  Returns (the y of the first run, the trace)."""
+    ys = run(dtype, ds, x_shared=x_shared, runs=(0xFF, 0x00), what=name)
+    third = []
+    seq = E._kernel_seq(lambda: third.extend(run(dtype, ds, x_shared=x_shared, runs=(0xFF,), what=name + " (traced)")))
+    for i, (a, b) in enumerate(zip(ys, third)):
+        assert torch.equal(E._bits(a), E._bits(b)), f"{name}: y of layer {i} differs on the traced run"
+    _skinny_trace(seq, name)
+    return ys, seq
+
+
+def _native_layer(c, d):
+    """The case's operands as test_gpu_acc_native._skinny reads them: fp32 masters that round to the factors."""
+    q_down = d.get("q") if c.kind in ("e4m3", "mxfp4") else d["W"]
+    return dict(x=d["x"], A=SW.fp32_master(d["A"]), B=SW.fp32_master(d["B"]), bias=None if d["bias"] is None else SW.fp32_master(d["bias"]),
+                q_down=AN._dev(q_down), q_up=AN._dev(d.get("e")), kind=AN.KINDS[c.kind])
+
+
+def _native_runs(cs, ds, s, x_shared, name):
+    """The call on fp32 factors (SOW_PARAM_F32 | SOW_ACC_NATIVE), traced; returns its y per layer on the CPU."""
+    cd = SW.DT[cs[0].dtype]
+    for c in cs:
+        _skinny_query(c, AN.CODE[cd] | AN.PF | AN.NATIVE)
+    layers = [_native_layer(c, d) for c, d in zip(cs, ds)]
+    got = []
+    seq = E._kernel_seq(lambda: got.extend(AN._skinny(cd, layers, True, s=s, x_shared=x_shared)))
+    _skinny_trace(seq, name + " (fp32 factors)")
+    return [y.cpu() for y in got]
+
+
+@pytest.mark.parametrize("c", PLAN.skinny, ids=lambda c: c.name)
+def test_fuzz_skinny(c):
+    dtype = SW.DT[c.dtype]
+    run, check, prefix, quantise, label = SKINNY[c.kind]
+    d, moved = SW.operands(c, quantise)
+    print(f"{c.name}: {moved} of {d['A'].numel()} elements of A moved by one ulp")
+    _skinny_query(c, E._dt(dtype))
+    (y,), seq = _skinny_runs(run, dtype, [d], False, c.name)
+    labels = {label, "skinny_b_kernel"}
+    if c.f32:   # fp32 factors: the bits of the call on the pre-rounded ones
+        (y32,) = _native_runs([c], [d], c.s, False, c.name)
+        assert torch.equal(E._bits(y32), E._bits(y)), f"{c.name}: fp32 factors differ from the pre-rounded call"
+        labels.add("skinny_a_kernel[fp32-factors]")
+    try:
+        check(c.name, dtype, d, y)
+    finally:
+        _note(c.name, labels, SK.WORST.get(prefix + c.name))
+
+
+@pytest.mark.parametrize("gp", PLAN.skinny_groups, ids=lambda g: g.name)
+def test_fuzz_skinny_group(gp):
+    dtype = SW.DT[gp.dtype]
+    run, check, prefix, quantise, label = SKINNY[gp.kind]
+    x0 = None
+    ds = []
+    for c in gp.layers:
+        d, _ = SW.operands(c, quantise, x=x0)
+        x0 = d["x"] if gp.x_shared else None
+        _skinny_query(c, E._dt(dtype))
+        ds.append(d)
+    grouped, seq = _skinny_runs(run, dtype, ds, gp.x_shared, gp.name)
+    labels = {label, "skinny_b_kernel"}
+    calls = [("grouped", grouped)]
+    if gp.f32:
+        calls.append(("grouped on fp32 factors", _native_runs(gp.layers, ds, gp.layers[0].s, gp.x_shared, gp.name)))
+        labels.add("skinny_a_kernel[fp32-factors]")
+    try:
+        for i, (c, d) in enumerate(zip(gp.layers, ds)):
+            (single,) = run(dtype, [d], runs=(0xFF,), what=c.name)
+            for what, ys in calls:
+                assert torch.equal(E._bits(ys[i]), E._bits(single)), f"{gp.name}: y of layer {i} of the {what} call differs from its call alone"
+            check(c.name, dtype, d, single)
+    finally:
+        ws = [SK.WORST[prefix + c.name] for c in gp.layers if prefix + c.name in SK.WORST]
+        _note(gp.name, labels, max(ws) if ws else None)
+
+
+# ---------------------------------------------------------------------------------------------------------------- fused, deep
+def _fuzz_fused(c, flags, trace_check, label):
+    case = FA.case(c.name, DT[c.dtype], c.T, c.d_in, c.d_out, c.r, c.r_acc, s=c.s, bias=c.bias, seed=c.seed)
+    d = E._inputs(case)
+    trace = {}
+    out = FU._run(case, d, flags=flags, trace=trace, save_h=c.save_h, group=c.group)
+    # h_save = NULL: the forward only -- its trace is held to the rule of both directions
+    trace_check(dict(trace, bwd=trace.get("bwd", trace["fwd"])), c.name)
+    worst = {}
+    try:
+        worst = FA.check(case, d, out)
+        if out.get("dh") is not None:   # dh, which the weight kernels read (test_fused_layer_elementwise)
+            dy, B = to64(d["dy"]), to64(d["B"])
+            st = check_h_save(to64(out["dh"]), c.s * (dy @ B.t()), c.r, case.dtype,
+                              acc=fp32_floor(c.s * c.s * ((dy * dy) @ (B * B).t()), c.d_out), name=f"{c.name}: dh")
+            worst["dh"] = st["worst"]
+        for k in ("y", "h", "dx", "dA", "dB", "dbias"):
+            assert out.get(k) is None or not torch.isnan(out[k].float()).any(), f"{c.name}: poison left in {k}"
+    finally:
+        _note(c.name, {label}, max(worst.values()) if worst else None)
+
+
+@pytest.mark.parametrize("c", PLAN.fused, ids=lambda c: c.name)
+def test_fuzz_fused(c):
+    _fuzz_fused(c, FU.FUSE, FU._fused_trace, "chain_wide_acc_kernel")
+
+
+@pytest.mark.parametrize("c", PLAN.deep, ids=lambda c: c.name)
+def test_fuzz_deep(c):
+    _fuzz_fused(c, DE.DEEP, DE._deep_trace, "chain_deep_acc_kernel")
+
+
+# ---------------------------------------------------------------------------------------------------------------- shared_acc
+@pytest.mark.parametrize("sp", PLAN.shared_acc, ids=lambda s: s.name)
+def test_fuzz_shared_acc(sp):
+    """test_gpu_shared_fused_acc's buffers and calls: the flagged grouped forward and backward, then sow_backward_shared on the
+    grouped call's h -- three times (poisoned, zeroed, poisoned)."""
+    lib = _lib.load()
+    st = SN.Set(sp.name, DT[sp.dtype], sp.T, sp.d_in, [SN.Sib(sb.d_out, sb.r, sb.r_acc, s=sb.s) for sb in sp.sibs],
+                grad_beta=sp.grad_beta, seed=sp.seed)
+    assert FP.shared_acc_lds_ok([sb.r + sb.r_acc for sb in sp.sibs])
+    d = SN.inputs(st)
+    b = SA.Bound(st, d)
+    n, flag = len(st.sibs), SA._flag(st)
+    hs = b.sets["group"]
+    both = SA.DATA | SA.WEIGHTS
+
+    def shared():
+        rc = lib.sow_backward_shared(b.args("shared", h_from=hs), n, flag, both, E._stream())
+        assert rc == 0, f"{sp.name}: sow_backward_shared returned {rc}"
+
+    runs, seq = [], []
+    for byte in (0xFF, 0x00, 0xFF):
+        b.ar.fill(byte)
+        _lib.check(lib.sow_forward_group(b.args("group"), n, flag, E._stream()), "sow_forward_group")
+        _lib.check(lib.sow_backward_group(b.args("group"), n, flag, both, E._stream()), "sow_backward_group")
+        if len(runs) == 2:
+            seq = E._kernel_seq(shared)
+        else:
+            shared()
+        b.ar.check_guards(f"{sp.name} run {len(runs)}")
+        for i, (og, os_) in enumerate(zip(b.sets["group"], b.sets["shared"])):
+            for k in ("dA", "dB", "dbias"):
+                if og[k] is not None:
+                    assert torch.equal(E._bits(og[k]), E._bits(os_[k])), \
+                        f"{sp.name}: {k} of sibling {i} differs from the grouped path (dh is not bit-identical)"
+        runs.append(b.sets["shared"][0]["dx"].clone())
+    assert torch.equal(E._bits(runs[0]), E._bits(runs[1])) and torch.equal(E._bits(runs[0]), E._bits(runs[2])), \
+        f"{sp.name}: dX differs between runs"
+    assert _has(seq, "chain_shared_acc_kernel") and not _has(seq, "chain_wide_acc_kernel"), f"{sp.name}: the trace holds {_ours(seq)}"
+    worst = None
+    try:
+        worst = SN.check_dx(st, d, runs[0].cpu())["worst"]
+    finally:
+        _note(sp.name, {"chain_shared_acc_kernel"}, worst)
+
+
 # ---------------------------------------------------------------------------------------------------------------- coverage
 def test_zz_fuzz_coverage():
     """Every family of fuzz_plan.FAMILIES reached by >= 3 drawn cases; prints the counts and the worst err / limit of the
     cases that ran each family (run with -s)."""
-    planned = len(PLAN.layers) + len(PLAN.groups) + len(PLAN.shared) + len(PLAN.gemms)
+    planned = sum(len(v) for v in (PLAN.layers, PLAN.groups, PLAN.shared, PLAN.gemms, PLAN.skinny, PLAN.skinny_groups, PLAN.fused,
+                                   PLAN.deep, PLAN.shared_acc))
     if len(RAN) < planned:
         pytest.skip(f"the coverage check runs after the whole sweep ({len(RAN)} of {planned} cases ran)")
     for fam in FP.FAMILIES:

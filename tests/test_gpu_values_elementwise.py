@@ -13,7 +13,7 @@ C  one NaN / +Inf / -Inf inside the data: the mask of non-finite output elements
    kernel's is the same Inf (fp32 runs on the 3 x bf16 split, which turns an Inf operand into NaN: mask only).  One stated
    exception (include/sow_amd.h): a non-finite element of A may take the dX columns of the rows of A stored just before it
    along -- the kernels read a row of A with its successors against explicit zeros.
-test_zz_value_coverage (last) asserts from the kernel traces that every family of fuzz_plan.FAMILIES was reached by an
+test_zz_value_coverage (last) asserts from the kernel traces that every family of fuzz_plan.FAMILIES_FIRST was reached by an
 exact case and a scaled case, and the chain / GEMM / weight-gradient families by a poisoned case.
 """
 import dataclasses
@@ -519,20 +519,20 @@ def test_exact_accumulate_and_axpby(dtype):
 
 
 # ------------------------------------------------------------------------------------------------------------- coverage
-C_FAMILIES = tuple(f for f in FP.FAMILIES if f not in ("h_reduce_kernel", "colsum_kernel"))
+C_FAMILIES = tuple(f for f in FP.FAMILIES_FIRST if f not in ("h_reduce_kernel", "colsum_kernel"))
 
 
 def test_zz_value_coverage():
-    """Every family of fuzz_plan.FAMILIES reached by an exact case (A) and a scaled case (B), every chain / GEMM /
+    """Every family of fuzz_plan.FAMILIES_FIRST reached by an exact case (A) and a scaled case (B), every chain / GEMM /
     weight-gradient family by a poisoned case (C); prints the counts per family (run with -s)."""
     if len(RAN) < PLANNED:   # RAN holds every case that started: one that failed leaves its family short below
         pytest.skip(f"the coverage check runs after the whole file ({len(RAN)} of {PLANNED} cases started)")
-    for fam in FP.FAMILIES:
+    for fam in FP.FAMILIES_FIRST:
         w, case = WORST_B.get(fam, (float("nan"), ""))
         print(f"family {fam:58s} exact {len(SEEN['A'].get(fam, ())):3d}  scaled {len(SEEN['B'].get(fam, ())):3d}  poisoned "
               f"{len(SEEN['C'].get(fam, ())):3d}  worst scaled Gaussian err/limit {w:.3f}  ({case})")
     print(f"{COUNT['exact_elements']} elements compared bit for bit, {COUNT.get('f32_gradients', 0)} runs with fp32 gradients, "
           f"{COUNT['B']} scaled runs, {COUNT['C']} poisoned placements")
-    for fam_set, fams in (("A", FP.FAMILIES), ("B", FP.FAMILIES), ("C", C_FAMILIES)):
+    for fam_set, fams in (("A", FP.FAMILIES_FIRST), ("B", FP.FAMILIES_FIRST), ("C", C_FAMILIES)):
         missing = [f for f in fams if not SEEN[fam_set].get(f)]
         assert not missing, f"families without a case of {fam_set}: {missing}"

@@ -71,7 +71,7 @@ def cases() -> Cases:
     p = FP.plan()
     size = lambda c: c.T * (c.d_in + c.d_out) + (c.d_in * c.d_out if c.acc == "dense" else 0)   # noqa: E731
     best = {}
-    for c in p.layers:
+    for c in p.layers[:FP.N_FIRST_LAYERS]:   # (the first stream: the second's families have exact-operand tests of their own)
         key = (c.stratum, c.family, c.dtype, tuple(sorted(c.switches)), c.acc, c.edges if c.stratum == "generic" else ())
         if c.stratum == "generic" and (c.dtype, c.edges[0]) not in GENERIC:
             continue
