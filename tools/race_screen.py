@@ -1,6 +1,8 @@
 """Race screen: the kernels are deterministic by construction (fixed reduction orders, no float atomics), so repeated
 launches on the same inputs must be BIT-identical; a difference means a missing wait / barrier somewhere in the
-LDS-DMA pipelines.  Runs every streaming path (chain2, chain2f, skinny-TN, streaming GEMM with and without the in-kernel projection, short-T split) many times."""
+LDS-DMA pipelines.  Runs every streaming path (chain2, chain2f, skinny-TN, streaming GEMM with and without the in-kernel projection, short-T split) many times.
+A tool for workload sizes on a quiet chip; the suite's check of the same property -- every kernel family at ring-wrap shapes,
+under concurrent load on a second stream, bit for bit -- is tests/test_gpu_under_load.py (plan: tests/race_plan.py)."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sow_amd import ops
