@@ -419,6 +419,22 @@ size_t sow_forward_skinny_fp8_workspace_bytes(int64_t T, int d_in, int d_out, in
 size_t sow_forward_skinny_fp4_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int dtype);
 int sow_forward_skinny(const sow_layer_args* layers, int n, int dtype, void* stream);
 
+/* The same forward for up to SOW_SKINNY_ROWS_MAX tokens per layer (decode steps of batch x beams = 33 ... 64, e.g. 16 prompts
+ * x 4 beams): the same contract, the same two launches, every byte of the accumulator (codes, scales) still read once.  A
+ * layer with 33 <= T <= 64 takes instantiations of the same two kernels that hold three or four 16-row tiles per wave -- each
+ * fragment of W is built or converted once and fed to up to four MFMAs -- and a slab plan of its own (fewer, longer slabs:
+ * the fp32 slab partials grow with T).  A layer with T <= 32 takes the plan and the kernels of sow_forward_skinny and gives
+ * the same bits, also next to a 64-row layer in one call (layers of both ranges are then launched as two groups).
+ * Admitted: 1 <= T <= 64 per layer, every other condition as for sow_forward_skinny: bf16 / f16 (SOW_PARAM_F32 only with
+ * SOW_ACC_NATIVE), SOW_ACC_NONE / _DENSE / _DENSE_FP8 / _DENSE_FP4 (the dense kinds do not mix in a call), r_live <= 64, widths
+ * multiples of 8 (d_in of 32 for _DENSE_FP4), the alignments, n <= 16; the same return codes, decided on the host for every
+ * layer before anything is launched or dereferenced; NO_SKINNY refuses everything; layers with T = 0 are skipped.
+ * sow_forward_skinny_rows_workspace_bytes: ONE query for all four kinds, a pure function of the shape, 0 outside the admitted
+ * set; for T <= 32 it returns what the matching query above returns.  Every scratch byte is written before it is read. */
+#define SOW_SKINNY_ROWS_MAX 64
+size_t sow_forward_skinny_rows_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype);
+int sow_forward_skinny_rows(const sow_layer_args* layers, int n, int dtype, void* stream);
+
 /* General row-major GEMM  C[M,N] = alpha * op(A) op(B) + beta * C + bias[N]  (bias may be NULL).
  * trans_a: A is stored [K,M]; trans_b: B is stored [N,K].  Replaces the plain `@` / einsum call
  * sites: accumulate() sow.py:131-140 (W_acc += scale * A @ B, Q @ R), prepare.py:135, tt.py:213-237. */

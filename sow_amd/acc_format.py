@@ -33,6 +33,34 @@ def skinny_fp4_pays(T: int, d_in: int, d_out: int) -> bool:
     return 1 <= T <= SKINNY_MAX_T
 
 
+SKINNY_ROWS_MAX = 64       # include/sow_amd.h: sow_forward_skinny_rows admits at most 64 (sow_amd.skinny_rows opts in)
+
+
+def skinny_fp8_rows_pays(T: int, d_in: int, d_out: int) -> bool:
+    """The measured dispatch rule for an E4M3 accumulator at 33 ... 64 rows inside sow_amd.skinny_rows (profiles/skinny_rows.txt,
+    DESIGN.md section 4.5d), the one place that encodes it: the calls at which sow_forward_skinny_rows on the codes (n) is
+    faster than the image pass followed by sow_forward / sow_forward_group on the image (a) by more than the larger
+    run-to-run spread of the two.  Measured (us, r = 50, T = 33 / 64; +- the larger spread): 4096->4096 42.8 /
+    51.6 against 237.9 / 134.5 (+- 2.3 / 3.0), 4096->11008 67.4 / 80.8 against 394.4 / 147.0 (+- 1.8 / 1.3), 11008->4096 65.2 / 82.9
+    against 462.2 / 314.6 (+- 0.8 / 0.5), 512->512 21.0 / 23.2 against 44.1 / 42.2 (+- 1.2 / 11.1), q + k + v of 4096->4096 76.5 / 96.5
+    against 692.3 / 381.1 (+- 2.8 / 0.3); a / n lies between 1.63 and 9.05 in all 36 rows and the gap exceeds the spread in each: the
+    rule excludes nothing.  Against two sow_forward_skinny calls on the row halves (b2) n wins or ties except 11008->4096, T = 64,
+    r = 8 (73.5 against 71.5 +- 1.3), which does not enter the rule.  NOT measured: f16, widths above 11008."""
+    return SKINNY_MAX_T < T <= SKINNY_ROWS_MAX
+
+
+def skinny_fp4_rows_pays(T: int, d_in: int, d_out: int) -> bool:
+    """The same rule for an MXFP4 accumulator (profiles/skinny_rows.txt).  Measured
+    (us, r = 50, T = 33 / 64; +- the larger spread): 4096->4096 39.6 / 49.1 against 236.1 / 131.0 (+- 1.4 / 1.8), 4096->11008 59.2 /
+    77.2 against 391.9 / 144.7 (+- 2.6 / 1.8), 11008->4096 58.8 / 78.0 against 458.9 / 306.7 (+- 1.3 / 1.2), 512->512 20.2 / 22.7 against
+    45.4 / 44.2 (+- 0.9 / 6.9), q + k + v of 4096->4096 71.3 / 92.0 against 691.4 / 378.8 (+- 2.6 / 1.5); a / n lies between 1.66 and 9.70
+    in all 36 rows and the gap exceeds the spread in each: the rule excludes nothing.  Two sow_forward_skinny calls on the row halves
+    (b2) are faster than n at T = 64 on 11008->4096 (60.7 against 69.2 at r = 8, 74.7 against 78.0 at r = 50) and on 4096->11008 at
+    r = 8 (70.7 against 73.6): reported in DESIGN with the kernel trace of one
+    of them (phase A 63.3 us against 2 x 28.5), no split routing is built.  NOT measured: f16, widths above 11008."""
+    return SKINNY_MAX_T < T <= SKINNY_ROWS_MAX
+
+
 class AccFormat(NamedTuple):
     name: str                       # the fmt= argument of quantize_accumulators
     label: str                      # the name used in messages
@@ -50,6 +78,7 @@ class AccFormat(NamedTuple):
     code_max: float                 # the largest code magnitude
     frexp: Tuple[float, int]        # code_max = threshold * 2^offset with threshold in [0.5, 1)
     pays: Callable[[int, int, int], bool]      # the measured rule that admits the streaming path
+    pays_rows: Callable[[int, int, int], bool]     # ... at 33 ... 64 rows (sow_forward_skinny_rows inside sow_amd.skinny_rows)
 
     def code_shape(self, d_in, d_out): return (d_in // self.rows_per_code, d_out)      # (of a [d_in, d_out] matrix, as scale_shape)
     def scale_shape(self, d_in, d_out): return (d_out,) if self.block is None else (d_in // self.block, d_out)
@@ -72,12 +101,12 @@ FORMATS = {f.name: f for f in (
     AccFormat(name="fp8_e4m3", label="E4M3", kind=_lib.ACC_DENSE_FP8, code_dtype=torch.float8_e4m3fn, scale_dtype=torch.int8,
               rows_per_code=1, block=None, d_in_multiple=8, d_out_multiple=8, workspace_query="sow_forward_skinny_fp8_workspace_bytes",
               dequantize="sow_acc_dequantize", exp_range={torch.bfloat16: (-117, 119), torch.float16: (-15, 7)}, scale_bias=0,
-              code_max=448.0, frexp=(0.875, 9), pays=skinny_fp8_pays),
+              code_max=448.0, frexp=(0.875, 9), pays=skinny_fp8_pays, pays_rows=skinny_fp8_rows_pays),
     # W^[k, n] = e2m1(nibble k % 2 of codes[k / 2, n]) * 2^(scales[k / 32, n] - 127): E8M0 scale bytes
     AccFormat(name="mxfp4", label="MXFP4", kind=_lib.ACC_DENSE_FP4, code_dtype=torch.uint8, scale_dtype=torch.uint8,
               rows_per_code=2, block=32, d_in_multiple=32, d_out_multiple=8, workspace_query="sow_forward_skinny_fp4_workspace_bytes",
               dequantize="sow_acc_dequantize_fp4", exp_range={torch.bfloat16: (-125, 125), torch.float16: (-13, 13)}, scale_bias=127,
-              code_max=6.0, frexp=(0.75, 3), pays=skinny_fp4_pays),
+              code_max=6.0, frexp=(0.75, 3), pays=skinny_fp4_pays, pays_rows=skinny_fp4_rows_pays),
 )}
 BY_CODE_DTYPE = {f.code_dtype: f for f in FORMATS.values()}
 BY_KIND = {f.kind: f for f in FORMATS.values()}

@@ -223,7 +223,7 @@ static int gemm_auto(const void* A, int64_t lda, const void* B, int64_t ldb, boo
 
 extern "C" {
 
-int sow_version(void) { return 121; }
+int sow_version(void) { return 122; }
 
 int sow_set_switch(const char* name, int value) {
   if (!name) return SOW_ERR_NULL;
@@ -1136,8 +1136,9 @@ int sow_forward_group(const sow_layer_args* layers, int n, int dtype, void* stre
 // ---- generation-sized forwards (skinny_fwd.hip) --------------------------------------------------------------
 // The admitted set, decided from the shape alone: 1 <= T <= 32, bf16 / f16 (SOW_PARAM_F32 only with SOW_ACC_NATIVE), a dense accumulator (in the
 // compute dtype, as E4M3 codes or as MXFP4 codes) or none, r_live <= 64, widths multiples of 8 (d_in of 32 for MXFP4: whole blocks).
-static bool skinny_shape_ok(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype) {
-  return (dtype == SOW_BF16 || dtype == SOW_F16) && T >= 1 && T <= 32 && d_in > 0 && d_out > 0 && r_live >= 1 && r_live <= 64 &&
+// (tmax: 32 for sow_forward_skinny, SOW_SKINNY_ROWS_MAX for sow_forward_skinny_rows)
+static bool skinny_shape_ok(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype, int tmax = 32) {
+  return (dtype == SOW_BF16 || dtype == SOW_F16) && T >= 1 && T <= tmax && d_in > 0 && d_out > 0 && r_live >= 1 && r_live <= 64 &&
          acc_kind_known(acc_kind) && acc_kind != SOW_ACC_LOWRANK && d_in % 8 == 0 && d_out % 8 == 0 && (acc_kind != SOW_ACC_DENSE_FP4 || d_in % 32 == 0);
 }
 struct SkWs {
@@ -1145,7 +1146,7 @@ struct SkWs {
 };
 static SkWs skinny_ws(int64_t T, int d_in, int d_out, int acc_kind) {
   int S, KS, ncr;
-  skinny_plan(d_in, d_out, acc_kind, &S, &KS, &ncr);
+  skinny_rows_plan(T, d_in, d_out, acc_kind, &S, &KS, &ncr);   // skinny_plan itself for T <= 32
   SkWs w;
   w.off_py = 0;
   w.off_ph = acc_kind != SOW_ACC_NONE ? al256(skinny_py_bytes(T, d_out, S)) : 0;
@@ -1153,9 +1154,9 @@ static SkWs skinny_ws(int64_t T, int d_in, int d_out, int acc_kind) {
   return w;
 }
 
-static size_t skinny_ws_query(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype) {
+static size_t skinny_ws_query(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype, int tmax = 32) {
   const Dtype f = decode_dtype(dtype);
-  if ((f.param_f32 && !f.native) || !skinny_shape_ok(T, d_in, d_out, r_live, acc_kind, f.cd)) return 0;
+  if ((f.param_f32 && !f.native) || !skinny_shape_ok(T, d_in, d_out, r_live, acc_kind, f.cd, tmax)) return 0;
   return skinny_ws(T, d_in, d_out, acc_kind).total;
 }
 
@@ -1169,10 +1170,14 @@ size_t sow_forward_skinny_fp8_workspace_bytes(int64_t T, int d_in, int d_out, in
 size_t sow_forward_skinny_fp4_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int dtype) {
   return skinny_ws_query(T, d_in, d_out, r_live, SOW_ACC_DENSE_FP4, dtype);
 }
+// one query for all four kinds and 1 <= T <= SOW_SKINNY_ROWS_MAX; for T <= 32 what the matching query above returns
+size_t sow_forward_skinny_rows_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype) {
+  return skinny_ws_query(T, d_in, d_out, r_live, acc_kind, dtype, SOW_SKINNY_ROWS_MAX);
+}
 
 // The checks of this entry point are its own (not check_layer): stricter, and every layer is checked before the first
 // launch, so that a refusal leaves all outputs and workspaces untouched.
-int sow_forward_skinny(const sow_layer_args* layers, int n, int dtype, void* stream) {
+static int forward_skinny_impl(const sow_layer_args* layers, int n, int dtype, void* stream, int tmax) {
   const Dtype f = decode_dtype(dtype);
   const int cd = f.cd;
   if (!f.layer_ok() || cd == SOW_F32) return SOW_ERR_DTYPE;
@@ -1189,7 +1194,7 @@ int sow_forward_skinny(const sow_layer_args* layers, int n, int dtype, void* str
     if (L.T < 0 || L.d_in <= 0 || L.d_out <= 0 || L.r_live <= 0) return SOW_ERR_SHAPE;
     if (!acc_kind_known(L.acc_kind)) return SOW_ERR_SHAPE;
     if (L.T == 0) continue;
-    if (!skinny_shape_ok(L.T, L.d_in, L.d_out, L.r_live, L.acc_kind, cd)) return SOW_ERR_UNSUPPORTED;
+    if (!skinny_shape_ok(L.T, L.d_in, L.d_out, L.r_live, L.acc_kind, cd, tmax)) return SOW_ERR_UNSUPPORTED;
     const bool codes = acc_is_codes(L.acc_kind), fp4 = L.acc_kind == SOW_ACC_DENSE_FP4;
     const bool dense = L.acc_kind == SOW_ACC_DENSE || codes;
     if (!L.x || !L.A || !L.B || !L.y || (dense && !L.acc_down) || (codes && !L.acc_up)) return SOW_ERR_NULL;
@@ -1210,7 +1215,23 @@ int sow_forward_skinny(const sow_layer_args* layers, int n, int dtype, void* str
     K.T = (int)L.T, K.d_in = L.d_in, K.d_out = L.d_out, K.r = L.r_live, K.scale = L.scale;
     K.wexp = codes ? (const int8_t*)L.acc_up : nullptr;
   }
-  return launch_skinny_fwd(sk, m, cd, call_kind != SOW_ACC_NONE ? call_kind : SOW_ACC_DENSE, f.native, (hipStream_t)stream);
+  // layers of at most 32 rows keep the plan and the kernels of sow_forward_skinny, layers past 32 take the four-row-tile forms:
+  // two launches each (a call of one range launches nothing for the other)
+  SkLayer hi[SK_MAXL];
+  int nlo = 0, nhi = 0;
+  for (int i = 0; i < m; ++i) {
+    if (sk[i].T > 32) hi[nhi++] = sk[i];
+    else sk[nlo++] = sk[i];
+  }
+  const int kind = call_kind != SOW_ACC_NONE ? call_kind : SOW_ACC_DENSE;
+  const int rc = launch_skinny_fwd(sk, nlo, cd, kind, f.native, (hipStream_t)stream);
+  return rc ? rc : launch_skinny_fwd(hi, nhi, cd, kind, f.native, (hipStream_t)stream, true);
+}
+int sow_forward_skinny(const sow_layer_args* layers, int n, int dtype, void* stream) {
+  return forward_skinny_impl(layers, n, dtype, stream, 32);
+}
+int sow_forward_skinny_rows(const sow_layer_args* layers, int n, int dtype, void* stream) {
+  return forward_skinny_impl(layers, n, dtype, stream, SOW_SKINNY_ROWS_MAX);
 }
 
 static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, int gdt, int phases, int perm, hipStream_t stream) {

@@ -238,7 +238,7 @@ size_t tnw_partial_bytes(int64_t T, int d_in, int d_out, int r);
 int launch_tn_wide(const void* x, const void* dh, const void* dy, const void* h, void* dA, void* dB, void* dbias, int64_t T,
                    int d_in, int d_out, int r, float scale, float beta, int dtype, int out_dtype, void* ws, size_t ws_bytes,
                    hipStream_t stream);
-// skinny_fwd.hip: the fused forward of generation-sized calls (T <= 32, bf16 / f16, r <= 64, dense accumulator or none), n <=
+// skinny_fwd.hip: the fused forward of generation-sized calls (T <= 32, or T <= 64 through the four-row-tile forms of phase A: rows64; bf16 / f16, r <= 64, dense accumulator or none), n <=
 // SK_MAXL independent layers in two launches: W streamed once by a grid over (column range) x (K-slab), fp32 slab partials
 // through the workspace, summed in slab order with h . B and the bias and rounded once.  An E4M3 accumulator (SOW_ACC_DENSE_FP8:
 // W = the codes, 1 byte per element, wexp = the column exponents) is streamed as bytes by instantiations of the same two
@@ -262,11 +262,15 @@ struct SkLayer {
 };
 // K-slabs, slab length and phase-A column ranges of a layer: a pure function of the shape
 void skinny_plan(int d_in, int d_out, int acc_kind, int* S, int* KS, int* ncr);
+// ... of sow_forward_skinny_rows: skinny_plan for T <= 32, a plan of fewer, longer slabs (by T) for 33 <= T <= 64
+void skinny_rows_plan(int64_t T, int d_in, int d_out, int acc_kind, int* S, int* KS, int* ncr);
 size_t skinny_py_bytes(int64_t T, int d_out, int S);
 size_t skinny_ph_bytes(int64_t T, int S);
 // acc_kind: the kind of the call's dense layers (SOW_ACC_DENSE, SOW_ACC_DENSE_FP8 or SOW_ACC_DENSE_FP4; any of them without one)
 // param_f32: A, B and bias are fp32 (16-byte aligned as before), rounded once to `dtype` in registers by both kernels
-int launch_skinny_fwd(const SkLayer* layers, int n, int dtype, int acc_kind, bool param_f32, hipStream_t stream);
+// rows64: every layer has 33 <= T <= 64 and takes skinny_rows_plan and the four-row-tile phase A (sow_forward_skinny_rows);
+// otherwise every layer has T <= 32
+int launch_skinny_fwd(const SkLayer* layers, int n, int dtype, int acc_kind, bool param_f32, hipStream_t stream, bool rows64 = false);
 // gemm.hip
 int launch_gemm(const void* A, int64_t lda, bool transA, const void* B, int64_t ldb, bool transB, void* C, int64_t ldc,
                 const void* bias, int64_t M, int N, int K, float alpha, float beta, int dtype, hipStream_t stream);

@@ -48,6 +48,15 @@
 // with 4-byte loads into the register the 2-byte load fills (the raw bits wait there while x is staged) and round at first use;
 // phase B loads its column of B and the bias as fp32 and rounds where the fmaf reads them.  One rounding per value, to nearest
 // even (from_f32<T>, the rounding of the parameter pack): y is bit-identical to the PF = false call on pre-rounded factors.
+//
+// 33 <= T <= 64 (sow_forward_skinny_rows, the RT = 4 instantiations of phase A, for every format and factor dtype): a wave holds
+// three or four 16-row tiles of x (the x slab is 48 or 64 rows) and feeds every fragment of W, built or converted ONCE, to four
+// MFMAs (the fourth tile of a 48-row slab is zeros in a register: no branch around its MFMA).  The four waves' tiles are parked
+// and added in two passes of 32 rows -- 4 x 32 x 132 floats = 66 KiB for a 128-column range -- in the same wave order.  The slab
+// plan is skinny_rows_plan (below): slabs of at most 768 rows at T <= 48 and 512 above keep the x slab under half a CU's LDS.
+// A plain accumulator keeps two workgroups per CU (230 registers); four row tiles of codes hold 128 accumulator registers next
+// to the operand ring and run one workgroup per CU (SOW_SKINNY_ROWS_OCC8).  Phase B is the kernel above on a
+// larger grid.  Layers of at most 32 rows in such a call are launched as a group of their own through the RT = 2 forms.
 #include <type_traits>
 
 #include "kernels.hpp"
@@ -144,8 +153,24 @@ template <typename T, typename TP> __device__ __forceinline__ float sk_param(TP 
 }
 
 constexpr int SK_PF = 4;   // k-steps a wave keeps in flight: all of them are requested before the x slab is staged
+// Four row tiles of codes hold 128 accumulator registers, and the compiler needs about 390 for the whole wave: one wave per
+// SIMD (one workgroup per CU), with the same four k-steps in flight.  Two per SIMD (256 registers) spill, at any depth of the
+// ring: -DSOW_SKINNY_ROWS_OCC8=2 -DSOW_SKINNY_ROWS_PF8=2 builds that form for the A/B of DESIGN 4.5d.
+#ifndef SOW_SKINNY_ROWS_PF8
+#define SOW_SKINNY_ROWS_PF8 SK_PF
+#endif
+#ifndef SOW_SKINNY_ROWS_OCC8
+#define SOW_SKINNY_ROWS_OCC8 1
+#endif
 
-template <typename T, SkFmt F = SK_PLAIN, bool PF = false> __global__ __launch_bounds__(256) void skinny_a_kernel(const SkGroup g) {
+// The second argument of __launch_bounds__: the least number of waves per SIMD the compiler has to leave room for.  With two
+// row tiles it is 1, which asks for nothing -- one wave per SIMD is what __launch_bounds__(256) alone guarantees, and the
+// RT = 2 forms keep the registers and occupancy they had without it.  With four row tiles: two for a plain
+// accumulator, SOW_SKINNY_ROWS_OCC8 for codes.  (A table, because the attribute takes no template-id with a comma.)
+// by [SkFmt][RT / 4]
+constexpr int SK_OCC[3][2] = {{1, 2}, {1, SOW_SKINNY_ROWS_OCC8}, {1, SOW_SKINNY_ROWS_OCC8}};
+// RT = the 16-row tiles of x a wave holds: 2 (T <= 32, one or two live) or 4 (33 <= T <= 64, three or four live)
+template <typename T, SkFmt F = SK_PLAIN, bool PF = false, int RT = 2> __global__ __launch_bounds__(256, SK_OCC[F][RT / 4]) void skinny_a_kernel(const SkGroup g) {
   extern __shared__ __align__(16) char sk_smem[];
   constexpr bool FP8 = F == SK_FP8, FP4 = F == SK_FP4;
   constexpr int SK_NCT = SkW<F>::NCT, SK_CN = sk_cn(F != SK_PLAIN), SK_RS = sk_rs(F != SK_PLAIN);
@@ -161,7 +186,9 @@ template <typename T, SkFmt F = SK_PLAIN, bool PF = false> __global__ __launch_b
   const int s = is_xa ? b / ntj : (b - L.S * ntj) / L.ncr;
   const int cr = is_xa ? b % ntj : (b - L.S * ntj) % L.ncr;   // tile of x . A, or column range of W
   const int Tn = L.T, d_in = L.d_in, d_out = L.d_out, KS = L.KS;
-  const int rows = Tn > 16 ? 32 : 16;
+  const int rows = RT == 2 ? (Tn > 16 ? 32 : 16) : (Tn > 48 ? 64 : 48);
+  // row tile rt holds rows of the call (uniform per layer); tile 0, and with RT = 4 tiles 1 and 2, always do
+  auto live = [&](int rt) { return RT == 2 ? rows == 32 : (rt < 3 || rows == 64); };
   const int kbeg = s * KS;
   const int klen = min(KS, d_in - kbeg);
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, n16 = lane & 15, kg = lane >> 4;
@@ -169,7 +196,8 @@ template <typename T, SkFmt F = SK_PLAIN, bool PF = false> __global__ __launch_b
 
   // ---- requests first: the operand stream does not depend on x ----
   // W: lane = rows k0 + 8 kg + i, columns col0 .. col0 + NCT - 1.  x . A: lane = the same rows, column j of A, one element.
-  sk_wvec d[SK_PF][8];
+  constexpr int NPF = (RT == 4 && F != SK_PLAIN) ? SOW_SKINNY_ROWS_PF8 : SK_PF;
+  sk_wvec d[NPF][8];
   const int col0 = cr * SK_CN + n16 * SK_NCT;
   const bool col_ok = col0 < d_out;   // d_out is a multiple of 8, NCT of 4 (8 for E4M3): a lane's columns are all in or all out
   const char* Wp = (const char*)L.W + (size_t)col0 * (F != SK_PLAIN ? 1 : sizeof(T));
@@ -203,7 +231,7 @@ template <typename T, SkFmt F = SK_PLAIN, bool PF = false> __global__ __launch_b
     }
   };
 #pragma unroll
-  for (int p = 0; p < SK_PF; ++p) load_step(kk0 + p * SK_KQ, d[p]);
+  for (int p = 0; p < NPF; ++p) load_step(kk0 + p * SK_KQ, d[p]);
 
   // ---- the slab of x: [rows][KS + pad], zeros for t >= T and k >= d_in ----
   const int xpitch = (KS + SK_XPAD) * 2;   // bytes
@@ -219,20 +247,31 @@ template <typename T, SkFmt F = SK_PLAIN, bool PF = false> __global__ __launch_b
   }
   __syncthreads();
 
-  f32x4 acc[SK_NCT][2];
+  f32x4 acc[SK_NCT][RT];
 #pragma unroll
-  for (int c = 0; c < SK_NCT; ++c) acc[c][0] = acc[c][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int c = 0; c < SK_NCT; ++c)
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) acc[c][rt] = f32x4{0.f, 0.f, 0.f, 0.f};
   const char* xa0 = sk_smem + n16 * xpitch + kg * 16;
-  const char* xa1 = xa0 + 16 * xpitch;
-
-  for (int kb = kk0; kb < klen; kb += SK_PF * SK_KQ) {
+  u32x4 a[RT];
+  // one W fragment, built once, against every live row tile
+  auto mma = [&](int c, const u32x4& f) {
 #pragma unroll
-    for (int p = 0; p < SK_PF; ++p) {
+    for (int rt = 0; rt < RT; ++rt)
+      if (RT == 4 || rt == 0 || live(rt)) acc[c][rt] = sk_mfma<T>(a[rt], f, acc[c][rt]);   // RT = 4: a dead tile's a[rt] is zeros
+  };
+
+  for (int kb = kk0; kb < klen; kb += NPF * SK_KQ) {
+#pragma unroll
+    for (int p = 0; p < NPF; ++p) {
       const int kk = kb + p * SK_KQ;
       if (kk < klen) {   // uniform per wave
-        const u32x4 a0 = *(const u32x4*)(xa0 + kk * 2);
-        u32x4 a1 = {0u, 0u, 0u, 0u};
-        if (rows == 32) a1 = *(const u32x4*)(xa1 + kk * 2);
+        a[0] = *(const u32x4*)(xa0 + kk * 2);
+#pragma unroll
+        for (int rt = 1; rt < RT; ++rt) {
+          a[rt] = u32x4{0u, 0u, 0u, 0u};
+          if (live(rt)) a[rt] = *(const u32x4*)(xa0 + rt * 16 * xpitch + kk * 2);
+        }
         if (is_xa) {
           u32x4 f;
 #pragma unroll
@@ -242,8 +281,7 @@ template <typename T, SkFmt F = SK_PLAIN, bool PF = false> __global__ __launch_b
             else
               f[m] = d[p][2 * m][0] | (d[p][2 * m + 1][0] << 16);
           }
-          acc[0][0] = sk_mfma<T>(a0, f, acc[0][0]);
-          if (rows == 32) acc[0][1] = sk_mfma<T>(a1, f, acc[0][1]);
+          mma(0, f);
         } else if constexpr (FP8) {
           // dword wd of a row = columns 4 wd .. 4 wd + 3: the conversion yields two columns of one row, a fragment register
           // wants two rows of one column
@@ -261,11 +299,7 @@ template <typename T, SkFmt F = SK_PLAIN, bool PF = false> __global__ __launch_b
               f[3][m] = sk_pack_exact<T>(r0h[1], r1h[1]);
             }
 #pragma unroll
-            for (int cc = 0; cc < 4; ++cc) {
-              const int c = 4 * wd + cc;
-              acc[c][0] = sk_mfma<T>(a0, f[cc], acc[c][0]);
-              if (rows == 32) acc[c][1] = sk_mfma<T>(a1, f[cc], acc[c][1]);
-            }
+            for (int cc = 0; cc < 4; ++cc) mma(4 * wd + cc, f[cc]);
           }
         } else if constexpr (FP4) {
           // byte c of a row pair = column c, rows 2 m and 2 m + 1 of the lane's eight: the scaled conversion IS fragment
@@ -276,8 +310,7 @@ template <typename T, SkFmt F = SK_PLAIN, bool PF = false> __global__ __launch_b
             u32x4 f;
 #pragma unroll
             for (int m = 0; m < 4; ++m) f[m] = cvt_fp4_pair<T>(d[p][m][c >> 2], sc, c & 3);
-            acc[c][0] = sk_mfma<T>(a0, f, acc[c][0]);
-            if (rows == 32) acc[c][1] = sk_mfma<T>(a1, f, acc[c][1]);
+            mma(c, f);
           }
         } else {
 #pragma unroll
@@ -286,48 +319,55 @@ template <typename T, SkFmt F = SK_PLAIN, bool PF = false> __global__ __launch_b
 #pragma unroll
             for (int m = 0; m < 4; ++m)
               f[m] = __builtin_amdgcn_perm(d[p][2 * m + 1][c >> 1], d[p][2 * m][c >> 1], (c & 1) ? 0x07060302u : 0x05040100u);
-            acc[c][0] = sk_mfma<T>(a0, f, acc[c][0]);
-            if (rows == 32) acc[c][1] = sk_mfma<T>(a1, f, acc[c][1]);
+            mma(c, f);
           }
         }
-        load_step(kk + SK_PF * SK_KQ, d[p]);   // (requests nothing past the slab)
+        load_step(kk + NPF * SK_KQ, d[p]);   // (requests nothing past the slab)
       }
     }
   }
 
   // ---- park the four waves' tiles, add them in wave order, store the slab partial ----
+  // RT = 4: in two passes of 32 rows (row tiles 0-1, then 2-3), so that the parked tiles of a 128-column range stay under
+  // half a CU's LDS; the wave order of every sum is the same
   __syncthreads();   // every wave is done with the x slab: the parked tiles take its place
   float* red = (float*)sk_smem;
+  const int prows = RT == 2 ? rows : 32;   // rows a wave parks per pass
 #pragma unroll
-  for (int c = 0; c < SK_NCT; ++c)
+  for (int ps = 0; ps < RT / 2; ++ps) {
+    if (ps) __syncthreads();   // the pass before is read
 #pragma unroll
-    for (int hf = 0; hf < 2; ++hf)
-      if ((hf == 0 || rows == 32) && (c == 0 || !is_xa)) {
+    for (int c = 0; c < SK_NCT; ++c)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) red[(w * rows + hf * 16 + kg * 4 + q) * SK_RS + c * 16 + n16] = acc[c][hf][q];
+      for (int hf = 0; hf < 2; ++hf)
+        if ((2 * ps + hf == 0 || live(2 * ps + hf)) && (c == 0 || !is_xa)) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) red[(w * prows + hf * 16 + kg * 4 + q) * SK_RS + c * 16 + n16] = acc[c][2 * ps + hf][q];
+        }
+    __syncthreads();
+    const int t0 = 32 * ps, tn = RT == 2 ? Tn : min(Tn - t0, 32);   // the pass's rows of the call: t0 .. t0 + tn - 1
+    if (!is_xa) {
+      float* Py = L.Py + ((size_t)s * Tn + t0) * d_out;
+      for (int idx = tid; idx < tn * SK_CN; idx += 256) {
+        const int t = idx / SK_CN, jc = idx - t * SK_CN;
+        const int n = cr * SK_CN + jc;
+        // local column jc = n16 * NCT + c sits in fragment c, tile column n16
+        const int slot = (jc % SK_NCT) * 16 + jc / SK_NCT;
+        float v = red[t * SK_RS + slot];
+#pragma unroll
+        for (int ww = 1; ww < 4; ++ww) v += red[(ww * prows + t) * SK_RS + slot];
+        if (n < d_out) Py[(size_t)t * d_out + n] = v;
       }
-  __syncthreads();
-  if (!is_xa) {
-    float* Py = L.Py + (size_t)s * Tn * d_out;
-    for (int idx = tid; idx < Tn * SK_CN; idx += 256) {
-      const int t = idx / SK_CN, jc = idx - t * SK_CN;
-      const int n = cr * SK_CN + jc;
-      // local column jc = n16 * NCT + c sits in fragment c, tile column n16
-      const int slot = (jc % SK_NCT) * 16 + jc / SK_NCT;
-      float v = red[t * SK_RS + slot];
+    } else {
+      // columns 16 cr .. 16 cr + 15 of Ph[s] (columns >= r hold zeros; those past the last tile are never read)
+      float* Ph = L.Ph + ((size_t)s * Tn + t0) * 64 + cr * 16;
+      for (int idx = tid; idx < tn * 16; idx += 256) {
+        const int t = idx >> 4, jj = idx & 15;
+        float v = red[t * SK_RS + jj];
 #pragma unroll
-      for (int ww = 1; ww < 4; ++ww) v += red[(ww * rows + t) * SK_RS + slot];
-      if (n < d_out) Py[(size_t)t * d_out + n] = v;
-    }
-  } else {
-    // columns 16 cr .. 16 cr + 15 of Ph[s] (columns >= r hold zeros; those past the last tile are never read)
-    float* Ph = L.Ph + (size_t)s * Tn * 64 + cr * 16;
-    for (int idx = tid; idx < Tn * 16; idx += 256) {
-      const int t = idx >> 4, jj = idx & 15;
-      float v = red[t * SK_RS + jj];
-#pragma unroll
-      for (int ww = 1; ww < 4; ++ww) v += red[(ww * rows + t) * SK_RS + jj];
-      Ph[t * 64 + jj] = v;
+        for (int ww = 1; ww < 4; ++ww) v += red[(ww * prows + t) * SK_RS + jj];
+        Ph[t * 64 + jj] = v;
+      }
     }
   }
 }
@@ -405,29 +445,60 @@ template <typename T, bool FP8 = false, bool PF = false> __global__ __launch_bou
 size_t skinny_py_bytes(int64_t T, int d_out, int S) { return (size_t)S * (size_t)T * (size_t)d_out * sizeof(float); }
 size_t skinny_ph_bytes(int64_t T, int S) { return (size_t)S * (size_t)T * 64 * sizeof(float); }
 
-// the two launches of one (compute dtype, accumulator format, factor dtype): one instantiation of each kernel
-template <typename T, SkFmt F, bool PF> static int sk_launch(const SkGroup& g, int na, int nb, size_t lds, hipStream_t stream) {
-  constexpr int LDS_X = 32 * (SK_KS_MAX + SK_XPAD) * 2;
-  constexpr int LDS_PARK = 4 * 32 * sk_rs(F != SK_PLAIN) * 4;
+// ---- 33 <= T <= 64 (sow_forward_skinny_rows): the RT = 4 instantiations of phase A ----
+// The slab plan depends on T here.  The x slab is 48 or 64 rows, and two workgroups share a CU's 160 KiB of LDS: the longest
+// slab is 768 at T <= 48 (48 x 776 x 2 = 74496 bytes) and 512 above (64 x 520 x 2 = 66560).  The Py partials grow with T
+// (S T d_out 4 bytes written and read back), so a layer asks for fewer workgroups than skinny_plan does: DESIGN 4.5d.
+#ifndef SOW_SKINNY_ROWS_WANT
+#define SOW_SKINNY_ROWS_WANT 512
+#endif
+#ifndef SOW_SKINNY_ROWS_WANT8
+#define SOW_SKINNY_ROWS_WANT8 256
+#endif
+constexpr int SK_ROWS_MAX = 64;
+constexpr int SK_KS_MAX48 = 768, SK_KS_MAX64 = 512;
+void skinny_rows_plan(int64_t T, int d_in, int d_out, int acc_kind, int* S, int* KS, int* ncr) {
+  if (T <= 32) return skinny_plan(d_in, d_out, acc_kind, S, KS, ncr);   // the plan of sow_forward_skinny, as it is
+  const bool codes = acc_is_codes(acc_kind);
+  const int nc = acc_kind == SOW_ACC_DENSE || codes ? ceil_div(d_out, sk_cn(codes)) : 0;
+  const int want = nc ? ceil_div(codes ? SOW_SKINNY_ROWS_WANT8 : SOW_SKINNY_ROWS_WANT, nc) : 32;
+  const int ks_max = T > 48 ? SK_KS_MAX64 : SK_KS_MAX48;
+  int ks = ceil_div(ceil_div(d_in, want), SK_KQ) * SK_KQ;
+  if (ks < SK_KQ) ks = SK_KQ;
+  if (ks > ks_max) ks = ks_max;
+  *KS = ks, *S = ceil_div(d_in, ks), *ncr = nc;
+}
+
+// the two launches of one (compute dtype, accumulator format, factor dtype, row tiles): one instantiation of each kernel
+template <typename T, SkFmt F, bool PF, int RT> static int sk_launch(const SkGroup& g, int na, int nb, size_t lds, hipStream_t stream) {
+  constexpr int LDS_X = RT == 2 ? 32 * (SK_KS_MAX + SK_XPAD) * 2 : 48 * (SK_KS_MAX48 + SK_XPAD) * 2;
+  static_assert(RT == 2 || 64 * (SK_KS_MAX64 + SK_XPAD) * 2 <= LDS_X, "the 64-row slab is the shorter one");
+  constexpr int LDS_PARK = 4 * 32 * sk_rs(F != SK_PLAIN) * 4;   // RT = 4 parks 32 rows per pass
   constexpr int LDS_MAX = LDS_PARK > LDS_X ? LDS_PARK : LDS_X;
-  SOW_SET_MAX_LDS_ONCE(LDS_MAX, skinny_a_kernel<T, F, PF>);
-  hipLaunchKernelGGL((skinny_a_kernel<T, F, PF>), dim3(na), dim3(256), lds, stream, g);
+  static_assert(RT == 2 || 2 * LDS_MAX <= 160 * 1024, "two workgroups per CU");
+  if (lds > (size_t)LDS_MAX) return SOW_ERR_UNSUPPORTED;   // (the plans keep below it)
+  SOW_SET_MAX_LDS_ONCE(LDS_MAX, skinny_a_kernel<T, F, PF, RT>);
+  hipLaunchKernelGGL((skinny_a_kernel<T, F, PF, RT>), dim3(na), dim3(256), lds, stream, g);
   SOW_CHECK_LAUNCH();
   hipLaunchKernelGGL((skinny_b_kernel<T, F == SK_FP8, PF>), dim3(nb), dim3(256), 0, stream, g);
   SOW_CHECK_LAUNCH();
   return SOW_OK;
 }
-// every instantiation there is, by [dtype is f16][SkFmt][param_f32]
+// every instantiation there is, by [dtype is f16][SkFmt][param_f32][row tiles are 4]
 using SkLaunch = int (*)(const SkGroup&, int, int, size_t, hipStream_t);
-#define SK_FMT_ROW(T, F) {sk_launch<T, F, false>, sk_launch<T, F, true>}
+#define SK_PF_ROW(T, F, PF) {sk_launch<T, F, PF, 2>, sk_launch<T, F, PF, 4>}
+#define SK_FMT_ROW(T, F) {SK_PF_ROW(T, F, false), SK_PF_ROW(T, F, true)}
 #define SK_DTYPE_ROWS(T) {SK_FMT_ROW(T, SK_PLAIN), SK_FMT_ROW(T, SK_FP8), SK_FMT_ROW(T, SK_FP4)}
-static constexpr SkLaunch SK_LAUNCH[2][3][2] = {SK_DTYPE_ROWS(bf16_t), SK_DTYPE_ROWS(f16_t)};
+static constexpr SkLaunch SK_LAUNCH[2][3][2][2] = {SK_DTYPE_ROWS(bf16_t), SK_DTYPE_ROWS(f16_t)};
 
-// layers: x, W (or nullptr), A, B, bias, y, Py (or nullptr), Ph, T in [1, 32], d_in, d_out, r, scale set by the caller (api.hip
-// has checked the admitted set); the plan and the block offsets are filled in here.  param_f32: A, B and bias are fp32
-int launch_skinny_fwd(const SkLayer* layers, int n, int dtype, int acc_kind, bool param_f32, hipStream_t stream) {
+// layers: x, W (or nullptr), A, B, bias, y, Py (or nullptr), Ph, T, d_in, d_out, r, scale set by the caller (api.hip has checked
+// the admitted set); the plan and the block offsets are filled in here.  param_f32: A, B and bias are fp32.  rows64: every
+// layer has 33 <= T <= 64 (skinny_rows_plan, four row tiles); otherwise every layer has T in [1, 32] (skinny_plan, two)
+int launch_skinny_fwd(const SkLayer* layers, int n, int dtype, int acc_kind, bool param_f32, hipStream_t stream, bool rows64) {
   if (n <= 0) return SOW_OK;
   if (n > SK_MAXL || (dtype != SOW_BF16 && dtype != SOW_F16)) return SOW_ERR_UNSUPPORTED;
+  for (int i = 0; i < n; ++i)
+    if (layers[i].T < (rows64 ? 33 : 1) || layers[i].T > (rows64 ? SK_ROWS_MAX : 32)) return SOW_ERR_UNSUPPORTED;
   // the dense layers of a call are of one kind: the kernels are instantiated per kind
   bool codes = false, plain = false;
   for (int i = 0; i < n; ++i) (layers[i].wexp ? codes : plain) |= layers[i].W != nullptr;
@@ -443,18 +514,18 @@ int launch_skinny_fwd(const SkLayer* layers, int n, int dtype, int acc_kind, boo
     L = layers[i];
     if (!L.W) L.wexp = nullptr;
     int ncr;
-    skinny_plan(L.d_in, L.d_out, !L.W ? SOW_ACC_NONE : codes ? acc_kind : SOW_ACC_DENSE, &L.S, &L.KS, &ncr);
+    skinny_rows_plan(L.T, L.d_in, L.d_out, !L.W ? SOW_ACC_NONE : codes ? acc_kind : SOW_ACC_DENSE, &L.S, &L.KS, &ncr);
     L.ncr = ncr;
     L.startA = na, L.startB = nb;
     na += L.S * ((L.r + 15) / 16 + ncr);
     nb += ceil_div(L.d_out, SK_BN) * ((L.T + 3) / 4);
-    const int rows = L.T > 16 ? 32 : 16;
-    const size_t xb = (size_t)rows * (L.KS + SK_XPAD) * 2, rb = (size_t)4 * rows * SK_RS * sizeof(float);
+    const int rows = rows64 ? (L.T > 48 ? 64 : 48) : (L.T > 16 ? 32 : 16);
+    const size_t xb = (size_t)rows * (L.KS + SK_XPAD) * 2, rb = (size_t)4 * (rows64 ? 32 : rows) * SK_RS * sizeof(float);
     lds = xb > lds ? xb : lds;
     lds = rb > lds ? rb : lds;
   }
   // MXFP4: the scale went into the conversion, Py holds sum x . W^ and phase B is the plain one
-  return SK_LAUNCH[dtype == SOW_F16][fmt][param_f32](g, na, nb, lds, stream);
+  return SK_LAUNCH[dtype == SOW_F16][fmt][param_f32][rows64](g, na, nb, lds, stream);
 }
 
 }  // namespace sow

@@ -229,7 +229,7 @@ class SiblingGroup:
         every sibling is admitted, but their dense accumulators are of differing kinds.  cdt: the compute dtype of fp32 layers
         under autocast (absent, native and quantised accumulators are admitted there; an fp32 accumulator is not)."""
         x2 = x.reshape(-1, x.shape[-1])
-        if not 1 <= x2.shape[0] <= ops.SKINNY_MAX_T:
+        if not 1 <= x2.shape[0] <= ops.skinny_rows_limit():      # (32, or up to 64 inside sow_amd.skinny_rows)
             return None
         if cdt is not None:      # fp32 master factors under autocast: the input in the compute dtype, cast once for the set
             x2 = autocast_input(x2.contiguous(), cdt)
@@ -245,7 +245,7 @@ class SiblingGroup:
             # quantised accumulators of differing formats, or quantised and unquantised ones, in one set: the library takes one
             # kind per call, and every sibling is admitted on its own -- each streams its own accumulator in a call of its own
             return _PER_LAYER
-        ys = ops.sow_forward_skinny(calls)
+        ys = (ops.sow_forward_skinny_rows if x2.shape[0] > ops.SKINNY_MAX_T else ops.sow_forward_skinny)(calls)
         if ys is None:
             return None
         return [y.reshape(*x.shape[:-1], y.shape[1]) for y in ys]

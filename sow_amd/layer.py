@@ -249,8 +249,10 @@ class SoWLinear(nn.Module):
             # autocast with fp32 factors it takes an absent, native (compute dtype) or quantised accumulator and rounds the
             # factors in registers.  An fp32 accumulator under autocast, a low-rank accumulator, a wide rank, ragged widths and a
             # refusal from the library keep the path below.
-            if x2.shape[0] <= ops.SKINNY_MAX_T and ops.skinny_admits(x2, A, B, acc_down, acc_up, self.bias, mixed=cdt is not None):
-                ys = ops.sow_forward_skinny([(x2, A, B, ops.skinny_acc(acc_down, acc_up), self.bias, float(self.scale))])
+            # Inside sow_amd.skinny_rows(n), calls of 33 ... n rows take sow_forward_skinny_rows the same way.
+            if x2.shape[0] <= ops.skinny_rows_limit() and ops.skinny_admits(x2, A, B, acc_down, acc_up, self.bias, mixed=cdt is not None):
+                fwd = ops.sow_forward_skinny_rows if x2.shape[0] > ops.SKINNY_MAX_T else ops.sow_forward_skinny
+                ys = fwd([(x2, A, B, ops.skinny_acc(acc_down, acc_up), self.bias, float(self.scale))])
                 if ys is not None:
                     return ys[0].reshape(*x.shape[:-1], B.shape[1])
             # every other call of a quantised layer: the existing dense path on the image

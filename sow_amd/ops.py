@@ -6,13 +6,14 @@ Every function requires CUDA(=HIP) tensors and raises otherwise.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 from typing import Optional, Sequence, Tuple
 
 import torch
 
 from . import _lib
-from .acc_format import BY_CODE_DTYPE, BY_KIND, FORMATS, SKINNY_MAX_T, skinny_fp4_pays, skinny_fp8_pays  # noqa: F401
+from .acc_format import BY_CODE_DTYPE, BY_KIND, FORMATS, SKINNY_MAX_T, SKINNY_ROWS_MAX, skinny_fp4_pays, skinny_fp8_pays  # noqa: F401
 
 _DT = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
 _HALF = (torch.bfloat16, torch.float16)
@@ -493,6 +494,59 @@ def skinny_workspace_bytes(T: int, d_in: int, d_out: int, r: int, kind: int, dt:
     return n
 
 
+_SKINNY_ROWS_WS_BYTES: dict = {}
+_SKINNY_ROWS = SKINNY_MAX_T       # the most rows a no-grad module call sends to the skinny forward: sow_amd.skinny_rows / set_skinny_rows
+
+
+def set_skinny_rows(n: int) -> int:
+    """The most flattened rows (batch x beams of a decode step) at which no-grad SoWLinear / SiblingGroup calls take the fused
+    skinny forward: 32 (the default: sow_forward_skinny alone) up to 64 (33 ... n rows go to sow_forward_skinny_rows).  Opt-in,
+    because a call of 33 ... 64 rows then rounds y once from one fp32 sum where the default path rounds h B and the dense
+    product as the training forward does: the results differ in the last bit.  Returns the value it replaces."""
+    global _SKINNY_ROWS
+    if isinstance(n, bool) or not isinstance(n, int) or not SKINNY_MAX_T <= n <= SKINNY_ROWS_MAX:
+        raise ValueError(f"sow_amd.set_skinny_rows: {n!r} is not an int in [{SKINNY_MAX_T}, {SKINNY_ROWS_MAX}]")
+    old, _SKINNY_ROWS = _SKINNY_ROWS, n
+    return old
+
+
+@contextlib.contextmanager
+def skinny_rows(n: int):
+    """with sow_amd.skinny_rows(64): ...  -- set_skinny_rows(n) for the block, the earlier value restored after it."""
+    old = set_skinny_rows(n)
+    try:
+        yield
+    finally:
+        set_skinny_rows(old)
+
+
+def skinny_rows_limit() -> int:
+    return _SKINNY_ROWS
+
+
+def skinny_rows_workspace_bytes(T: int, d_in: int, d_out: int, r: int, kind: int, dt: int) -> int:
+    """sow_forward_skinny_rows_workspace_bytes (one query for every kind), memoised per shape: 0 = outside the admitted set."""
+    key = (T, d_in, d_out, r, kind, dt)
+    n = _SKINNY_ROWS_WS_BYTES.get(key)
+    if n is None:
+        n = _SKINNY_ROWS_WS_BYTES[key] = int(_lib.load().sow_forward_skinny_rows_workspace_bytes(T, d_in, d_out, r, kind, dt))
+    return n
+
+
+def skinny_rows_pays(T: int, d_in: int, d_out: int) -> bool:
+    """The measured dispatch rule of the module surface at 33 ... 64 rows inside sow_amd.skinny_rows, for a bf16 / f16 dense
+    accumulator or none (profiles/skinny_rows.txt; quantised formats: acc_format.py): the calls at which
+    sow_forward_skinny_rows (n) is faster than sow_forward / sow_forward_group with a scratch h (a) by more than the larger
+    run-to-run spread of the two.  Measured (us, bf16,
+    r = 50, T = 33 / 64, n against a; +- the larger spread of the two): 4096->4096 38.0 / 43.2 against 234.6 / 129.7 (+- 2.7 / 2.1),
+    4096->11008 64.7 / 73.6 against 378.0 / 130.2 (+- 1.0 / 0.9), 11008->4096 60.0 / 69.2 against 459.8 / 312.2 (+- 0.8 / 3.1),
+    512->512 18.4 / 19.6 against 40.0 / 37.6 (+- 2.2 / 9.1), 512->1376 18.6 / 21.3 against 60.2 / 35.7 (+- 0.6 / 6.9), q + k + v of
+    4096->4096 68.9 / 85.7 against 687.6 / 375.5 (+- 0.7 / 0.9); a / n lies between 1.68 and 9.98 in all 36 rows (T = 33, 48, 64;
+    r = 8, 50) and the gap exceeds the spread in each: the rule excludes nothing.  n is also below two sow_forward_skinny calls on
+    the row halves in every row (b2 / n 1.18 ... 1.94).  NOT measured: f16, widths above 11008."""
+    return SKINNY_MAX_T < T <= SKINNY_ROWS_MAX
+
+
 def skinny_pays(T: int, d_in: int, d_out: int) -> bool:
     """The measured dispatch rule of the module surface (profiles/skinny_forward.txt): the token
     counts and widths at which the fused skinny forward is faster than the path it replaces (quantised formats: acc_format.py)."""
@@ -513,8 +567,9 @@ def skinny_admits(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, 
     or none, and a shape the library admits and the dispatch rule keeps.  False sends the caller to the existing path, which
     raises whatever it raises today.  mixed: the call runs under autocast with fp32 factors and x2 already of the compute dtype."""
     dt = _DT.get(x2.dtype)
-    if dt is None or dt == _lib.F32 or not x2.is_cuda or x2.dim() != 2 or not 1 <= x2.shape[0] <= SKINNY_MAX_T:
+    if dt is None or dt == _lib.F32 or not x2.is_cuda or x2.dim() != 2 or not 1 <= x2.shape[0] <= _SKINNY_ROWS:
         return False
+    rows = x2.shape[0] > SKINNY_MAX_T      # 33 ... sow_amd.skinny_rows: sow_forward_skinny_rows, its query and its rules
     kind, fmt = _acc_kind_fmt(acc_down, acc_up)
     if kind == _lib.ACC_LOWRANK or A.dim() != 2 or B.dim() != 2:
         return False
@@ -530,9 +585,17 @@ def skinny_admits(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, 
     if pdt != x2.dtype:
         dt |= _lib.PARAM_F32 | _lib.ACC_NATIVE
     if fmt is not None and (acc_up is None or not fmt.scales_fit(acc_up, d_in, d_out) or acc_down.device != x2.device
-                            or acc_up.device != x2.device or not fmt.pays(T, d_in, d_out)):
+                            or acc_up.device != x2.device or not (fmt.pays_rows if rows else fmt.pays)(T, d_in, d_out)):
         return False
+    if rows:
+        return skinny_rows_pays(T, d_in, d_out) and skinny_rows_workspace_bytes(T, d_in, d_out, r, kind, dt) > 0
     return skinny_pays(T, d_in, d_out) and skinny_workspace_bytes(T, d_in, d_out, r, kind, dt) > 0
+
+
+def sow_forward_skinny_rows(layers) -> Optional[list]:
+    """sow_forward_skinny for layers of up to 64 rows each (include/sow_amd.h: sow_forward_skinny_rows; layers of at most 32
+    rows compute in it what they compute in sow_forward_skinny, bit for bit).  Same arguments, same result."""
+    return _forward_skinny(layers, True)
 
 
 def sow_forward_skinny(layers) -> Optional[list]:
@@ -541,7 +604,13 @@ def sow_forward_skinny(layers) -> Optional[list]:
     dense accumulator, the (codes, scales) pair of a quantised one (TypeError unless well formed: acc_format.py), or None.  A, B and bias are of x2's dtype, or fp32 in every
     layer of the call (SOW_PARAM_F32 | SOW_ACC_NATIVE: rounded once in registers, the accumulator stays of x2's dtype).  Returns the list of outputs, or None when the library refuses the set (nothing was launched:
     the caller runs sow_forward / LayerGroup instead)."""
+    return _forward_skinny(layers, False)
+
+
+def _forward_skinny(layers, _rows: bool) -> Optional[list]:
+    """sow_forward_skinny (_rows: sow_forward_skinny_rows): the one body of both."""
     lib = _lib.load()
+    name = "sow_amd.sow_forward_skinny_rows" if _rows else "sow_amd.sow_forward_skinny"
     n = len(layers)
     if n == 0:
         return []
@@ -559,19 +628,19 @@ def sow_forward_skinny(layers) -> Optional[list]:
             acc_down, exps = acc_down
             fmt = BY_CODE_DTYPE.get(acc_down.dtype)
             if fmt is None or not fmt.well_formed(acc_down, exps):
-                raise TypeError(f"sow_amd.sow_forward_skinny: {_NOT_A_PAIR}")
+                raise TypeError(f"{name}: {_NOT_A_PAIR}")
         dev = _need_gpu(x2, A, B, acc_down, exps, bias)
         if dev != x0.device or any(t is not None and t.dtype != x0.dtype for t in (x2, acc_down if exps is None else None)) or any(
                 t is not None and t.dtype != pdt for t in (A, B, bias)):
-            raise TypeError("sow_amd.sow_forward_skinny: the inputs and dense accumulators of a call share one dtype, its factors "
+            raise TypeError(f"{name}: the inputs and dense accumulators of a call share one dtype, its factors "
                             "and biases one dtype (the inputs', or float32), and all tensors one device")
         T, d_in = x2.shape
         r, d_out = B.shape
         if tuple(A.shape) != (d_in, r) or (acc_down is not None and (fmt.logical_shape(acc_down) if fmt else tuple(acc_down.shape[:2])) != (d_in, d_out)) or (
                 bias is not None and tuple(bias.shape) != (d_out,)):
-            raise ValueError("sow_amd.sow_forward_skinny: operand shapes do not match")
+            raise ValueError(f"{name}: operand shapes do not match")
         kind = _lib.ACC_NONE if acc_down is None else _lib.ACC_DENSE if fmt is None else fmt.kind
-        nws = skinny_workspace_bytes(T, d_in, d_out, r, kind, dt) if T else 0
+        nws = (skinny_rows_workspace_bytes if _rows else skinny_workspace_bytes)(T, d_in, d_out, r, kind, dt) if T else 0
         if T and not nws:
             return None
         nws = (nws + 255) & ~255
@@ -592,10 +661,10 @@ def sow_forward_skinny(layers) -> Optional[list]:
         a.acc_up, a.acc_kind = _ptr(exps), kind
         a.scale = float(layer[5])
         a.workspace, a.workspace_bytes = base + off, nws
-    rc = _launch_rc(x0.device, lib.sow_forward_skinny, arr, n, dt)
+    rc = _launch_rc(x0.device, lib.sow_forward_skinny_rows if _rows else lib.sow_forward_skinny, arr, n, dt)
     if rc == _lib.ERR_UNSUPPORTED:
         return None
-    _lib.check(rc, "sow_forward_skinny")
+    _lib.check(rc, "sow_forward_skinny_rows" if _rows else "sow_forward_skinny")
     return ys
 
 
