@@ -435,6 +435,36 @@ int sow_forward_skinny(const sow_layer_args* layers, int n, int dtype, void* str
 size_t sow_forward_skinny_rows_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype);
 int sow_forward_skinny_rows(const sow_layer_args* layers, int n, int dtype, void* stream);
 
+/* Short batches of dense-accumulator layers, WITH gradients: n <= 16 independent layers of 1 ... SOW_SHORT_ROWS_MAX rows each on
+ * the two skinny kernels, cut into row blocks of 64 on one W (one launch pair per 16 (layer, row block) entries):
+ *   forward   h   = rn(scale * x A)              fp32 sum, rounded once  -> h_save (the r_live <= 64 layout) when given
+ *             y   = rn(x acc_down + h B + bias)  ONE fp32 sum, rounded once
+ *   data      dh  = rn(scale * dY B^T)           fp32 sum, rounded once  -> the workspace, where the weight phases read it
+ *             dX  = rn(dY acc_down^T + dh A^T)   ONE fp32 sum, rounded once
+ * h_save and dh have the layout the streaming kernels leave: [T][64], zeros past r_live, 1.0 in column 63 when r_live <= 63.
+ * sow_backward_short runs the data phase only; an unchanged sow_backward_ex(..., SOW_BWD_WEIGHTS | _PARTIAL | _REDUCE) on the
+ * same workspace then produces dA, dB and dbias.  acc_down is read in place in both directions (transposed by the loads of
+ * the data phase).  No atomics and a fixed order of every sum: a repeat gives the same bits, a layer computes inside a call what
+ * it computes alone, and a row's result does not depend on its position or on the rows next to it.
+ * Fields used: forward x, A, B, acc_down, bias, y, h_save (may be NULL); data phase dy, A, B, acc_down, dx; both T, d_in,
+ * d_out, r_live, acc_kind, scale, workspace, workspace_bytes.
+ * Admitted: SOW_DTYPE_BF16 / SOW_DTYPE_F16 without flags, SOW_ACC_DENSE only, 1 <= T <= SOW_SHORT_ROWS_MAX, r_live <= 64, d_in and
+ * d_out multiples of 8, 16-byte-aligned x, y, dy, dx, acc_down, A, B, bias and h_save, n <= 16.  SOW_ACC_NONE, SOW_ACC_LOWRANK,
+ * the code kinds, SOW_PARAM_F32 (with or without SOW_ACC_NATIVE) and everything while the NO_SKINNY switch is on return
+ * SOW_ERR_UNSUPPORTED; SOW_DTYPE_F32 returns SOW_ERR_DTYPE; a workspace below the query SOW_ERR_WORKSPACE.  All of it is decided
+ * on the host for every layer before anything is launched or dereferenced.  Layers with T = 0 are skipped (SOW_OK).
+ * sow_forward_short_workspace_bytes: the forward's slab partials (a no-grad call needs no more).
+ * sow_short_workspace_bytes: ONE size for the forward, the data phase and the weight phases -- the plan of sow_workspace_bytes
+ * for the same layer with the 256-aligned slab partials appended, so the buffer passes sow_backward_ex's size check and dh sits
+ * where that plan keeps it.  (The forward writes its partials to the front of the workspace it is given: nothing there is live
+ * before the data phase.)  Both are pure functions of the shape, 0 outside the admitted set; every byte of the partials is
+ * written before it is read. */
+#define SOW_SHORT_ROWS_MAX 1024
+size_t sow_forward_short_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype);
+size_t sow_short_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype);
+int sow_forward_short(const sow_layer_args* layers, int n, int dtype, void* stream);
+int sow_backward_short(const sow_layer_args* layers, int n, int dtype, void* stream);
+
 /* General row-major GEMM  C[M,N] = alpha * op(A) op(B) + beta * C + bias[N]  (bias may be NULL).
  * trans_a: A is stored [K,M]; trans_b: B is stored [N,K].  Replaces the plain `@` / einsum call
  * sites: accumulate() sow.py:131-140 (W_acc += scale * A @ B, Q @ R), prepare.py:135, tt.py:213-237. */

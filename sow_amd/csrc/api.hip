@@ -223,7 +223,7 @@ static int gemm_auto(const void* A, int64_t lda, const void* B, int64_t ldb, boo
 
 extern "C" {
 
-int sow_version(void) { return 122; }
+int sow_version(void) { return 123; }
 
 int sow_set_switch(const char* name, int value) {
   if (!name) return SOW_ERR_NULL;
@@ -1233,6 +1233,91 @@ int sow_forward_skinny(const sow_layer_args* layers, int n, int dtype, void* str
 int sow_forward_skinny_rows(const sow_layer_args* layers, int n, int dtype, void* stream) {
   return forward_skinny_impl(layers, n, dtype, stream, SOW_SKINNY_ROWS_MAX);
 }
+
+// ---- short batches of dense-accumulator layers (skinny_fwd.hip: the row-block forms) ------------------------------------
+// The admitted set, from the shape alone: bf16 / f16 without flags, SOW_ACC_DENSE, 1 <= T <= SOW_SHORT_ROWS_MAX, r_live <= 64,
+// widths multiples of 8.
+static_assert(SOW_SHORT_ROWS_MAX == SK_SHORT_MAX && SOW_SHORT_ROWS_MAX == 64 * SK_MAXL, "a layer's row blocks are one launch group");
+static bool short_shape_ok(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype) {
+  return (dtype == SOW_BF16 || dtype == SOW_F16) && acc_kind == SOW_ACC_DENSE && T >= 1 && T <= SOW_SHORT_ROWS_MAX && d_in > 0 && d_out > 0 &&
+         r_live >= 1 && r_live <= 64 && d_in % 8 == 0 && d_out % 8 == 0;
+}
+// the slab partials of one direction: Py [S][T][N] (row block b at S * 64 b * N floats), then Ph [S][T][64], each 256-aligned
+struct ShortWs {
+  int S, KS, ncr;
+  size_t off_ph, bytes;
+};
+static ShortWs short_ws(int64_t T, int K, int N, bool bwd) {
+  ShortWs w;
+  short_rows_plan(T, K, N, bwd ? SK_SHORT_KQ_BWD : SK_SHORT_KQ_FWD, &w.S, &w.KS, &w.ncr);
+  w.off_ph = al256(skinny_py_bytes(T, N, w.S));
+  w.bytes = w.off_ph + al256(skinny_ph_bytes(T, w.S));
+  return w;
+}
+static bool short_dtype_ok(const Dtype& f) { return !f.param_f32 && !f.native_bit && (f.cd == SOW_BF16 || f.cd == SOW_F16); }
+
+size_t sow_forward_short_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype) {
+  const Dtype f = decode_dtype(dtype);
+  if (!short_dtype_ok(f) || !short_shape_ok(T, d_in, d_out, r_live, acc_kind, f.cd)) return 0;
+  return 256 + short_ws(T, d_in, d_out, false).bytes;
+}
+// the plan of sow_workspace_bytes (dh at off_dh, the weight phases' partials), then the slab partials of the larger direction:
+// the forward puts its own at the front of whichever workspace it is given (nothing there is live before the data phase)
+size_t sow_short_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype) {
+  const Dtype f = decode_dtype(dtype);
+  if (!short_dtype_ok(f) || !short_shape_ok(T, d_in, d_out, r_live, acc_kind, f.cd)) return 0;
+  const size_t fw = short_ws(T, d_in, d_out, false).bytes, bw = short_ws(T, d_out, d_in, true).bytes;
+  return plan_ws(T, d_in, d_out, r_live, 0, SOW_ACC_DENSE, f.cd).total + (fw > bw ? fw : bw) + 256;
+}
+
+// Checks of their own, as sow_forward_skinny: every layer is checked before the first launch.
+static int short_impl(const sow_layer_args* layers, int n, int dtype, void* stream, bool bwd) {
+  const Dtype f = decode_dtype(dtype);
+  const int cd = f.cd;
+  if (!f.layer_ok() || cd == SOW_F32) return SOW_ERR_DTYPE;
+  if (f.param_f32 || f.native_bit || sw_on(SW_NO_SKINNY)) return SOW_ERR_UNSUPPORTED;
+  if (n < 0) return SOW_ERR_SHAPE;
+  if (n == 0) return SOW_OK;
+  if (!layers) return SOW_ERR_NULL;
+  if (n > SK_MAXL) return SOW_ERR_UNSUPPORTED;
+  for (int i = 0; i < n; ++i)
+    if (layers[i].acc_kind != SOW_ACC_DENSE) return acc_kind_known(layers[i].acc_kind) ? SOW_ERR_UNSUPPORTED : SOW_ERR_SHAPE;
+  std::vector<SkLayer> e;
+  for (int i = 0; i < n; ++i) {
+    const sow_layer_args& L = layers[i];
+    if (L.T < 0 || L.d_in <= 0 || L.d_out <= 0 || L.r_live <= 0) return SOW_ERR_SHAPE;
+    if (L.T == 0) continue;
+    if (!short_shape_ok(L.T, L.d_in, L.d_out, L.r_live, L.acc_kind, cd)) return SOW_ERR_UNSUPPORTED;
+    if (!L.A || !L.B || !L.acc_down || (bwd ? (!L.dy || !L.dx) : (!L.x || !L.y))) return SOW_ERR_NULL;
+    if (!al16p(L.A) || !al16p(L.B) || !al16p(L.acc_down)) return SOW_ERR_UNSUPPORTED;
+    if (bwd ? (!al16p(L.dy) || !al16p(L.dx)) : (!al16p(L.x) || !al16p(L.y) || !al16p(L.bias) || !al16p(L.h_save))) return SOW_ERR_UNSUPPORTED;
+    const size_t need = bwd ? sow_short_workspace_bytes(L.T, L.d_in, L.d_out, L.r_live, L.acc_kind, cd)
+                            : sow_forward_short_workspace_bytes(L.T, L.d_in, L.d_out, L.r_live, L.acc_kind, cd);
+    if (!L.workspace || L.workspace_bytes < need) return SOW_ERR_WORKSPACE;
+    char* ws = ws_base(L.workspace);
+    const int K = bwd ? L.d_out : L.d_in, N = bwd ? L.d_in : L.d_out;
+    const ShortWs w = short_ws(L.T, K, N, bwd);
+    // the data phase keeps dh where the weight phases read it and its partials behind the plan they use
+    const WsPlan p = plan_of(L, cd);
+    char* part = bwd ? ws + p.total : ws;
+    char* hout = bwd ? ws + p.off_dh : (char*)L.h_save;
+    const size_t es = esize(cd);
+    for (int64_t t0 = 0; t0 < L.T; t0 += 64) {
+      SkLayer E{};
+      E.x = (const char*)(bwd ? L.dy : L.x) + (size_t)t0 * K * es;
+      E.y = (char*)(bwd ? L.dx : L.y) + (size_t)t0 * N * es;
+      E.W = L.acc_down, E.A = bwd ? L.B : L.A, E.B = bwd ? L.A : L.B, E.bias = bwd ? nullptr : L.bias;
+      E.Py = (float*)part + (size_t)w.S * t0 * N, E.Ph = (float*)(part + w.off_ph) + (size_t)w.S * t0 * 64;
+      E.T = (int)(L.T - t0 < 64 ? L.T - t0 : 64), E.d_in = K, E.d_out = N, E.r = L.r_live, E.scale = L.scale;
+      E.S = w.S, E.KS = w.KS, E.ncr = w.ncr;
+      E.hout = hout ? hout + (size_t)t0 * 64 * es : nullptr;
+      e.push_back(E);
+    }
+  }
+  return launch_skinny_short(e.data(), (int)e.size(), cd, bwd, (hipStream_t)stream);
+}
+int sow_forward_short(const sow_layer_args* layers, int n, int dtype, void* stream) { return short_impl(layers, n, dtype, stream, false); }
+int sow_backward_short(const sow_layer_args* layers, int n, int dtype, void* stream) { return short_impl(layers, n, dtype, stream, true); }
 
 static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, int gdt, int phases, int perm, hipStream_t stream) {
   const Phases ph = decode_phases(phases);

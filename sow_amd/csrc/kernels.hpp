@@ -258,7 +258,10 @@ struct SkLayer {
   int T, d_in, d_out, r;
   int S, KS, ncr, startA, startB;     // filled in by launch_skinny_fwd (skinny_plan)
   float scale;
-  const int8_t* wexp;                 // the scales of codes in W (E4M3: int8 column exponents [d_out]; MXFP4: E8M0 bytes [d_in / 32][d_out]), or nullptr
+  union {                             // (one pointer either way: the existing forms see the struct they saw)
+    const int8_t* wexp;               // the scales of codes in W (E4M3: int8 column exponents [d_out]; MXFP4: E8M0 bytes [d_in / 32][d_out]), or nullptr
+    void* hout;                       // short-row forms (plain accumulator only): where phase B stores h / dh, [T][64], or nullptr
+  };
 };
 // K-slabs, slab length and phase-A column ranges of a layer: a pure function of the shape
 void skinny_plan(int d_in, int d_out, int acc_kind, int* S, int* KS, int* ncr);
@@ -271,6 +274,17 @@ size_t skinny_ph_bytes(int64_t T, int S);
 // rows64: every layer has 33 <= T <= 64 and takes skinny_rows_plan and the four-row-tile phase A (sow_forward_skinny_rows);
 // otherwise every layer has T <= 32
 int launch_skinny_fwd(const SkLayer* layers, int n, int dtype, int acc_kind, bool param_f32, hipStream_t stream, bool rows64 = false);
+// Short batches (sow_forward_short / sow_backward_short: SOW_ACC_DENSE, 1 <= T <= SK_SHORT_MAX): a layer is cut into row blocks
+// of 64, every block one SkLayer entry on the same W.  short_rows_plan: the slab plan ALL blocks of a layer take, counted over
+// blocks x column ranges x slabs; K = the contraction width, N = the output width (forward: d_in, d_out; data gradient: d_out,
+// d_in), kq = the k per round of the four waves (SK_SHORT_KQ_FWD / _BWD).  A pure function of its arguments.
+constexpr int SK_SHORT_MAX = 1024, SK_SHORT_KQ_FWD = 128, SK_SHORT_KQ_BWD = 256;
+void short_rows_plan(int64_t T, int K, int N, int kq, int* S, int* KS, int* ncr);
+// entries: any number of row blocks (1 <= T <= 64 each) with S, KS and ncr set from short_rows_plan, Py / Ph per block, hout = h_save
+// / dh of the block or nullptr; launched 16 at a time, one launch pair each.  bwd: the entries carry the data gradient's
+// operands in the forward's fields -- x = dY, W = W_acc (read transposed in place), A = B [r][d_out], B = A [d_in][r], y = dX,
+// d_in = the layer's d_out (contraction), d_out = the layer's d_in (output), no bias
+int launch_skinny_short(const SkLayer* entries, int n, int dtype, bool bwd, hipStream_t stream);
 // gemm.hip
 int launch_gemm(const void* A, int64_t lda, bool transA, const void* B, int64_t ldb, bool transB, void* C, int64_t ldc,
                 const void* bias, int64_t M, int N, int K, float alpha, float beta, int dtype, hipStream_t stream);

@@ -57,6 +57,12 @@
 // A plain accumulator keeps two workgroups per CU (230 registers); four row tiles of codes hold 128 accumulator registers next
 // to the operand ring and run one workgroup per CU (SOW_SKINNY_ROWS_OCC8).  Phase B is the kernel above on a
 // larger grid.  Layers of at most 32 rows in such a call are launched as a group of their own through the RT = 2 forms.
+//
+// Short batches WITH gradients (sow_forward_short / sow_backward_short, SOW_ACC_DENSE, 1 <= T <= 1024): a layer is
+// cut into row blocks of 64, every block one SkLayer entry on the same W with a slab plan counted over the blocks
+// (short_rows_plan).  The forward is the RT = 4 plain phase A as it is and the SK_SH_FWD form of phase B, which also stores the
+// h rows it has rounded (h_save).  The data gradient is the TR = true form of phase A (skinny_a_tr: dY staged as x, W_acc read
+// transposed in place) and the SK_SH_BWD form of phase B (skinny_b_tr: dh to memory, dX = rn(sum Py + dh . A^T)).
 #include <type_traits>
 
 #include "kernels.hpp"
@@ -169,9 +175,162 @@ constexpr int SK_PF = 4;   // k-steps a wave keeps in flight: all of them are re
 // accumulator, SOW_SKINNY_ROWS_OCC8 for codes.  (A table, because the attribute takes no template-id with a comma.)
 // by [SkFmt][RT / 4]
 constexpr int SK_OCC[3][2] = {{1, 2}, {1, SOW_SKINNY_ROWS_OCC8}, {1, SOW_SKINNY_ROWS_OCC8}};
+// ---- short batches, data gradient (sow_backward_short): the TR = true instantiations of phase A (plain format, RT = 4) ----
+//   dh = rn(scale . dY B^T),  dX = rn(dY W_acc^T + dh A^T)
+// The roles are swapped on the host (launch_skinny_short): L.x = dY [T][K], K = the layer's d_out = the contraction, L.d_out = N =
+// the layer's d_in; a K-slab is a range of the layer's d_out, a column range 64 columns of its d_in.  W_acc is read in place: the B
+// operand of v_mfma_f32_16x16x32 wants eight consecutive contraction elements of one output column per lane, and for W_acc^T
+// those are W_acc[n0 + (l & 15)][k0 + 8 (l >> 4) .. + 7] -- one aligned 16-byte load, no byte permutes.  A wave takes its k-steps
+// in PAIRS (SK_TR_KC = 64 deep per wave and round): the two loads of a tile ask for the 128 contiguous bytes of a W row together,
+// non-temporal, every byte of W read once per row block.  The first S * ceil(r / 16) workgroups compute dY . B^T instead: the
+// fragment of column j is B[j][k .. k + 7], again one 16-byte load (B is [r][d_out]: no 2-byte gather).  x staging, MFMA, the
+// park and the wave-order reduction are those of the forward; an accumulator tile's column IS the local column here.
+constexpr int SK_TR_KC = 2 * SK_KSTEP;   // k per wave and round
+constexpr int SK_TR_KQ = 4 * SK_TR_KC;   // k per round of the four waves (SK_SHORT_KQ_BWD)
+constexpr int SK_TR_PF = 2;              // rounds a wave keeps in flight: all of a slab of at most 512
+static_assert(SK_TR_KQ == SK_SHORT_KQ_BWD, "the data gradient's slabs are whole rounds");
+template <typename T> __device__ __forceinline__ void skinny_a_tr(const SkGroup& g, char* sk_smem) {
+  constexpr int RT = 4, NCT = 4, CN = 64, RS = sk_rs(false);
+  int li = 0;
+  for (int i = 1; i < g.n; ++i)
+    if ((int)blockIdx.x >= g.L[i].startA) li = i;
+  const SkLayer& L = g.L[li];
+  const int b = (int)blockIdx.x - L.startA;
+  const int ntj = (L.r + 15) >> 4;            // 16-column tiles of dY . B^T
+  const bool is_p = b < L.S * ntj;            // the first S * ntj workgroups: (slab, tile) of dY . B^T
+  const int s = is_p ? b / ntj : (b - L.S * ntj) / L.ncr;
+  const int cr = is_p ? b % ntj : (b - L.S * ntj) % L.ncr;
+  const int Tn = L.T, K = L.d_in, N = L.d_out, KS = L.KS, r = L.r;
+  const int rows = Tn > 48 ? 64 : 48;
+  const bool live3 = rows == 64;              // the fourth row tile holds rows of the call
+  const int kbeg = s * KS;
+  const int klen = min(KS, K - kbeg);
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, n16 = lane & 15, kg = lane >> 4;
+  const int kk0 = w * SK_TR_KC;
+
+  // ---- requests first ----
+  // tile c of W: row n = 64 cr + 16 c + n16 of W_acc (clamped: a row past N is not requested); dY . B^T: row j = 16 cr + n16 of B
+  const T* rowp[NCT];
+  bool ok[NCT];
+#pragma unroll
+  for (int c = 0; c < NCT; ++c) {
+    const int n = is_p ? cr * 16 + n16 : cr * CN + c * 16 + n16;
+    const int lim = is_p ? r : N;
+    ok[c] = n < lim && (c == 0 || !is_p);
+    rowp[c] = (const T*)(is_p ? L.A : L.W) + (size_t)min(n, lim - 1) * K;
+  }
+  u32x4 d[SK_TR_PF][NCT][2];
+  auto load_round = [&](int kk, u32x4(&o)[NCT][2]) {
+#pragma unroll
+    for (int c = 0; c < NCT; ++c)
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const int kq = kk + q * SK_KSTEP, k = kbeg + kq + kg * 8;   // K is a multiple of 8: a lane's eight are all in or all out
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (ok[c] && kq < klen && k < K) {
+          if (is_p) v = *(const u32x4*)(rowp[c] + k);               // B is read by every slab's workgroups of every block: cached
+          else v = sk_load_w((const u32x4*)(rowp[c] + k));
+        }
+        o[c][q] = v;
+      }
+  };
+#pragma unroll
+  for (int p = 0; p < SK_TR_PF; ++p) load_round(kk0 + p * SK_TR_KQ, d[p]);
+
+  // ---- the slab of dY: [rows][KS + pad], zeros for t >= T and k >= K ----
+  const int xpitch = (KS + SK_XPAD) * 2;   // bytes
+  {
+    const T* x = (const T*)L.x;
+    const int cpr = KS / 8;
+    for (int idx = tid; idx < rows * cpr; idx += 256) {
+      const int t = idx / cpr, c = idx - t * cpr, k = kbeg + c * 8;
+      u32x4 v = {0u, 0u, 0u, 0u};
+      if (t < Tn && k < K) v = *(const u32x4*)(x + (size_t)t * K + k);
+      *(u32x4*)(sk_smem + t * xpitch + c * 16) = v;
+    }
+  }
+  __syncthreads();
+
+  f32x4 acc[NCT][RT];
+#pragma unroll
+  for (int c = 0; c < NCT; ++c)
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) acc[c][rt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const char* xa0 = sk_smem + n16 * xpitch + kg * 16;
+  for (int kb = kk0; kb < klen; kb += SK_TR_PF * SK_TR_KQ) {
+#pragma unroll
+    for (int p = 0; p < SK_TR_PF; ++p) {
+      const int kk = kb + p * SK_TR_KQ;
+      if (kk < klen) {   // uniform per wave
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          const int kq = kk + q * SK_KSTEP;   // (< KS: slabs are whole rounds; past klen both operands are zeros)
+          u32x4 a[RT];
+#pragma unroll
+          for (int rt = 0; rt < RT; ++rt) {
+            a[rt] = u32x4{0u, 0u, 0u, 0u};
+            if (rt < 3 || live3) a[rt] = *(const u32x4*)(xa0 + rt * 16 * xpitch + kq * 2);
+          }
+#pragma unroll
+          for (int c = 0; c < NCT; ++c)
+            if (c == 0 || !is_p) {
+#pragma unroll
+              for (int rt = 0; rt < RT; ++rt) acc[c][rt] = sk_mfma<T>(a[rt], d[p][c][q], acc[c][rt]);
+            }
+        }
+        load_round(kk + SK_TR_PF * SK_TR_KQ, d[p]);   // (requests nothing past the slab)
+      }
+    }
+  }
+
+  // ---- park the four waves' tiles in two passes of 32 rows, add them in wave order, store the slab partial ----
+  __syncthreads();
+  float* red = (float*)sk_smem;
+#pragma unroll
+  for (int ps = 0; ps < 2; ++ps) {
+    if (ps) __syncthreads();
+#pragma unroll
+    for (int c = 0; c < NCT; ++c)
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf)
+        if ((2 * ps + hf < 3 || live3) && (c == 0 || !is_p)) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) red[(w * 32 + hf * 16 + kg * 4 + q) * RS + c * 16 + n16] = acc[c][2 * ps + hf][q];
+        }
+    __syncthreads();
+    const int t0 = 32 * ps, tn = min(Tn - t0, 32);
+    if (!is_p) {
+      float* Py = L.Py + ((size_t)s * Tn + t0) * N;
+      for (int idx = tid; idx < tn * CN; idx += 256) {
+        const int t = idx / CN, jc = idx - t * CN;
+        const int n = cr * CN + jc;
+        float v = red[t * RS + jc];
+#pragma unroll
+        for (int ww = 1; ww < 4; ++ww) v += red[(ww * 32 + t) * RS + jc];
+        if (n < N) Py[(size_t)t * N + n] = v;
+      }
+    } else {
+      float* Ph = L.Ph + ((size_t)s * Tn + t0) * 64 + cr * 16;
+      for (int idx = tid; idx < tn * 16; idx += 256) {
+        const int t = idx >> 4, jj = idx & 15;
+        float v = red[t * RS + jj];
+#pragma unroll
+        for (int ww = 1; ww < 4; ++ww) v += red[(ww * 32 + t) * RS + jj];
+        Ph[t * 64 + jj] = v;
+      }
+    }
+  }
+}
+
 // RT = the 16-row tiles of x a wave holds: 2 (T <= 32, one or two live) or 4 (33 <= T <= 64, three or four live)
-template <typename T, SkFmt F = SK_PLAIN, bool PF = false, int RT = 2> __global__ __launch_bounds__(256, SK_OCC[F][RT / 4]) void skinny_a_kernel(const SkGroup g) {
+// TR: the data gradient of short batches (skinny_a_tr above; plain format, RT = 4 only)
+template <typename T, SkFmt F = SK_PLAIN, bool PF = false, int RT = 2, bool TR = false> __global__ __launch_bounds__(256, SK_OCC[F][RT / 4]) void skinny_a_kernel(const SkGroup g) {
   extern __shared__ __align__(16) char sk_smem[];
+  static_assert(!TR || (F == SK_PLAIN && !PF && RT == 4), "the transposed form exists for the plain format with four row tiles");
+  if constexpr (TR) {   // (what follows is dead code in these instantiations)
+    skinny_a_tr<T>(g, sk_smem);
+    return;
+  }
   constexpr bool FP8 = F == SK_FP8, FP4 = F == SK_FP4;
   constexpr int SK_NCT = SkW<F>::NCT, SK_CN = sk_cn(F != SK_PLAIN), SK_RS = sk_rs(F != SK_PLAIN);
   typedef typename SkW<F>::vec sk_wvec;
@@ -378,7 +537,74 @@ template <typename T, SkFmt F = SK_PLAIN, bool PF = false, int RT = 2> __global_
 // instead of a chain of r + 2 S + 1, and only the fp32 additions run in order.
 constexpr int SK_BS = 16;   // slab partials requested up front; a layer with more slabs adds the rest in a second loop
 
-template <typename T, bool FP8 = false, bool PF = false> __global__ __launch_bounds__(256) void skinny_b_kernel(const SkGroup g) {
+// Short batches, data gradient (SH = SK_SH_BWD): the same workgroup over dX -- 64 columns of the layer's d_in x 4 token rows.
+// dh = rn(scale * sum_s Ph[s]) goes into LDS and, from the workgroups of the first column block, to memory once per row in the
+// layout the chain kernels leave (pad columns zero, 1.0 in column 63 when r <= 63); then per element the Py slabs in slab
+// order, the r products dh[t][j] . A[n][j] in order of j (the thread's row of A is contiguous), one rounding, one store.  No bias.
+enum SkShort : int { SK_SH_NONE = 0, SK_SH_FWD = 1, SK_SH_BWD = 2 };
+template <typename T> __device__ __forceinline__ void skinny_b_tr(const SkGroup& g) {
+  __shared__ float hs[4][64];
+  int li = 0;
+  for (int i = 1; i < g.n; ++i)
+    if ((int)blockIdx.x >= g.L[i].startB) li = i;
+  const SkLayer& L = g.L[li];
+  const int b = (int)blockIdx.x - L.startB;
+  const int Tn = L.T, N = L.d_out, r = L.r, S = L.S;
+  const int nrg = (Tn + 3) >> 2;
+  const int cb = b / nrg, rg = b - cb * nrg;
+  const int tid = threadIdx.x, nn = tid & 63, tl = tid >> 6;
+  const int t = rg * 4 + tl, n = cb * SK_BN + nn;
+  const bool live = t < Tn && n < N;
+  const int tc = min(t, Tn - 1), nc = min(n, N - 1), jc = min(nn, r - 1);
+
+  // every request before the first use, at clamped addresses: the thread's row of A (L.B here: [N][r]), its slab partials
+  T av[64];
+  {
+    const T* A = (const T*)L.B + (size_t)nc * r;
+#pragma unroll
+    for (int j = 0; j < 64; ++j) av[j] = A[min(j, r - 1)];
+  }
+  float ph[SK_BS], py[SK_BS];
+  const float* Ph = L.Ph + (size_t)tc * 64 + jc;
+  const size_t phs = (size_t)Tn * 64;
+  const float* Py = L.Py + (size_t)tc * N + nc;
+  const size_t pys = (size_t)Tn * N;
+#pragma unroll
+  for (int u = 0; u < SK_BS; ++u) ph[u] = Ph[(size_t)min(u, S - 1) * phs];
+#pragma unroll
+  for (int u = 0; u < SK_BS; ++u) py[u] = Py[(size_t)min(u, S - 1) * pys];
+
+  {
+    float v = 0.f;
+#pragma unroll
+    for (int u = 0; u < SK_BS; ++u)
+      if (u < S) v += ph[u];
+    for (int s = SK_BS; s < S; ++s) v += Ph[(size_t)s * phs];
+    const float hv = (t < Tn && nn < r) ? to_f32(from_f32<T>(L.scale * v)) : 0.f;
+    hs[tl][nn] = hv;
+    if (cb == 0 && t < Tn && L.hout) ((T*)L.hout)[(size_t)t * 64 + nn] = from_f32<T>((nn == 63 && r < 64) ? 1.f : hv);
+  }
+  float acc = 0.f;
+#pragma unroll
+  for (int u = 0; u < SK_BS; ++u)
+    if (u < S) acc += py[u];
+  for (int s = SK_BS; s < S; ++s) acc += Py[(size_t)s * pys];
+  __syncthreads();
+  if (!live) return;
+#pragma unroll
+  for (int j = 0; j < 64; ++j)
+    if (j < r) acc = fmaf(hs[tl][j], to_f32(av[j]), acc);
+  ((T*)L.y)[(size_t)t * N + n] = from_f32<T>(acc);
+}
+
+// SH: the short-batch forms (plain format, factors of T): SK_SH_FWD also stores the h rows it has just rounded, from the workgroups
+// of the first column block, in the h_save layout; SK_SH_BWD is the data gradient above
+template <typename T, bool FP8 = false, bool PF = false, int SH = SK_SH_NONE> __global__ __launch_bounds__(256) void skinny_b_kernel(const SkGroup g) {
+  static_assert(SH == SK_SH_NONE || (!FP8 && !PF), "the short-batch forms read a plain accumulator and factors of T");
+  if constexpr (SH == SK_SH_BWD) {   // (what follows is dead code in these instantiations)
+    skinny_b_tr<T>(g);
+    return;
+  }
   __shared__ float hs[4][64];
   int li = 0;
   for (int i = 1; i < g.n; ++i)
@@ -424,6 +650,8 @@ template <typename T, bool FP8 = false, bool PF = false> __global__ __launch_bou
       if (u < S) v += ph[u];
     for (int s = SK_BS; s < S; ++s) v += Ph[(size_t)s * phs];
     hs[tl][nn] = (t < Tn && nn < r) ? to_f32(from_f32<T>(L.scale * v)) : 0.f;
+    if constexpr (SH == SK_SH_FWD)   // h_save: the rounded row, zeros past r, 1.0 in column 63 when free (the chain kernels' layout)
+      if (cb == 0 && t < Tn && L.hout) ((T*)L.hout)[(size_t)t * 64 + nn] = from_f32<T>((nn == 63 && r < 64) ? 1.f : hs[tl][nn]);
   }
   float acc = 0.f;
   if (dense) {
@@ -526,6 +754,68 @@ int launch_skinny_fwd(const SkLayer* layers, int n, int dtype, int acc_kind, boo
   }
   // MXFP4: the scale went into the conversion, Py holds sum x . W^ and phase B is the plain one
   return SK_LAUNCH[dtype == SOW_F16][fmt][param_f32][rows64](g, na, nb, lds, stream);
+}
+
+// ---- short batches: 1 <= T <= SK_SHORT_MAX rows of a dense-accumulator layer, forward and data gradient ----
+// A layer is ceil(T / 64) row blocks on one W, every block an entry of the group with its own x / y / Py / Ph / hout.  The plan
+// counts the blocks: about SK_SHORT_WANT workgroups over blocks x column ranges x slabs, not per block -- the slab partials are S T N
+// floats written and read back, and sixteen blocks fill the chip without short slabs.  Slabs are at most 512 (the 64-row x slab:
+// two workgroups per CU) and whole rounds of the four waves (kq).  All blocks of a layer take the one plan, and a block of fewer
+// than 49 rows pads with a zero tile: the order of a row's sum does not depend on the block it is in or on its place there.
+#ifndef SOW_SKINNY_SHORT_WANT
+#define SOW_SKINNY_SHORT_WANT 512
+#endif
+void short_rows_plan(int64_t T, int K, int N, int kq, int* S, int* KS, int* ncr) {
+  const int nblk = (int)ceil_div(T, (int64_t)SK_ROWS_MAX), nc = ceil_div(N, sk_cn(false));
+  const int want = ceil_div(SOW_SKINNY_SHORT_WANT, nc * (nblk > 0 ? nblk : 1));
+  int ks = ceil_div(ceil_div(K, want), kq) * kq;
+  if (ks < kq) ks = kq;
+  if (ks > SK_KS_MAX64) ks = SK_KS_MAX64;
+  *KS = ks, *S = ceil_div(K, ks), *ncr = nc;
+}
+
+template <typename T, bool BWD> static int sk_launch_short(const SkGroup& g, int na, int nb, size_t lds, hipStream_t stream) {
+  // (the forward's phase A is the RT = 4 plain form of sow_forward_skinny_rows itself: the same limit as sk_launch sets for it)
+  constexpr int LDS_MAX = 48 * (SK_KS_MAX48 + SK_XPAD) * 2;
+  static_assert(64 * (SK_KS_MAX64 + SK_XPAD) * 2 <= LDS_MAX && 4 * 32 * sk_rs(false) * 4 <= LDS_MAX && 2 * LDS_MAX <= 160 * 1024, "two workgroups per CU");
+  if (lds > (size_t)LDS_MAX) return SOW_ERR_UNSUPPORTED;
+  SOW_SET_MAX_LDS_ONCE(LDS_MAX, skinny_a_kernel<T, SK_PLAIN, false, 4, BWD>);
+  hipLaunchKernelGGL((skinny_a_kernel<T, SK_PLAIN, false, 4, BWD>), dim3(na), dim3(256), lds, stream, g);
+  SOW_CHECK_LAUNCH();
+  hipLaunchKernelGGL((skinny_b_kernel<T, false, false, BWD ? SK_SH_BWD : SK_SH_FWD>), dim3(nb), dim3(256), 0, stream, g);
+  SOW_CHECK_LAUNCH();
+  return SOW_OK;
+}
+
+int launch_skinny_short(const SkLayer* entries, int n, int dtype, bool bwd, hipStream_t stream) {
+  if (n <= 0) return SOW_OK;
+  if (dtype != SOW_BF16 && dtype != SOW_F16) return SOW_ERR_UNSUPPORTED;
+  const int kq = bwd ? SK_SHORT_KQ_BWD : SK_SHORT_KQ_FWD;
+  for (int i = 0; i < n; ++i) {
+    const SkLayer& E = entries[i];
+    if (E.T < 1 || E.T > SK_ROWS_MAX || !E.W || !E.Py || !E.Ph || E.r < 1 || E.r > 64 || E.KS < kq || E.KS > SK_KS_MAX64 || E.KS % kq ||
+        E.S != ceil_div(E.d_in, E.KS) || E.ncr != ceil_div(E.d_out, sk_cn(false)))
+      return SOW_ERR_UNSUPPORTED;
+  }
+  for (int i0 = 0; i0 < n; i0 += SK_MAXL) {
+    SkGroup g;
+    g.n = n - i0 < SK_MAXL ? n - i0 : SK_MAXL;
+    int na = 0, nb = 0;
+    size_t lds = (size_t)4 * 32 * sk_rs(false) * sizeof(float);
+    for (int i = 0; i < g.n; ++i) {
+      SkLayer& L = g.L[i];
+      L = entries[i0 + i];
+      L.startA = na, L.startB = nb;
+      na += L.S * ((L.r + 15) / 16 + L.ncr);
+      nb += ceil_div(L.d_out, SK_BN) * ((L.T + 3) / 4);
+      const size_t xb = (size_t)(L.T > 48 ? 64 : 48) * (L.KS + SK_XPAD) * 2;
+      lds = xb > lds ? xb : lds;
+    }
+    const int rc = dtype == SOW_F16 ? (bwd ? sk_launch_short<f16_t, true>(g, na, nb, lds, stream) : sk_launch_short<f16_t, false>(g, na, nb, lds, stream))
+                                    : (bwd ? sk_launch_short<bf16_t, true>(g, na, nb, lds, stream) : sk_launch_short<bf16_t, false>(g, na, nb, lds, stream));
+    if (rc) return rc;
+  }
+  return SOW_OK;
 }
 
 }  // namespace sow

@@ -64,6 +64,20 @@ class _SoWGroupFunction(torch.autograd.Function):
         # E4M3 accumulators (codes, exponents): the siblings' images side by side in the scratch arena; the codes are what is
         # saved, backward builds the images again
         accs = ops.acc_operands([(t[2], t[3]) for t in per], x2.dtype)
+        # inside sow_amd.short_rows: every sibling admitted (dense accumulators or images, the measured rule) -> one
+        # sow_forward_short call for the set; sinks and autocast keep the grouped path
+        ctx.short = False
+        if not mixed and sinks is None and n <= ops.SKINNY_MAX_LAYERS and all(
+                ops.short_admits(x2, A, B, acc_down, acc_up, bias) for (A, B, _, _, bias), (acc_down, acc_up) in zip(per, accs)):
+            res = ops.sow_forward_short([(x2, A, B, acc_down, bias, s) for (A, B, _, _, bias), (acc_down, _), s in zip(per, accs, scales)],
+                                        save_h=need_bwd)
+            if res is not None:
+                ys, hs = res
+                ctx.short, ctx.shared = True, shared
+                if need_bwd:
+                    ctx.save_for_backward(x2, *hs, *tensors)
+                ctx.scales, ctx.n, ctx.x_shape, ctx.x_dtype, ctx.mixed = scales, n, x.shape, x.dtype, mixed
+                return tuple(y.reshape(*lead, y.shape[1]) for y in ys)
         calls = []
         for (A, B, _, _, bias), (acc_down, acc_up), s in zip(per, accs, scales):
             kind = ops.acc_kind(acc_down, acc_up)
@@ -88,6 +102,22 @@ class _SoWGroupFunction(torch.autograd.Function):
                                                                 x2.dtype)):
             tensors[5 * i + 2], tensors[5 * i + 3] = acc_down, acc_up
         sinks = ctx.sinks
+        if ctx.short:
+            # the siblings' data gradients in one sow_backward_short call, then each layer's weight phases on its workspace
+            layers = []
+            for i in range(n):
+                A, B, acc_down, _, bias = tensors[5 * i:5 * i + 5]
+                dy, d_out = dys[i], B.shape[1]
+                dy2 = torch.zeros(x2.shape[0], d_out, dtype=x2.dtype, device=x2.device) if dy is None else dy.reshape(-1, d_out).contiguous()
+                layers.append((dy2, x2, hs[i], A, B, acc_down, ctx.scales[i], bias is not None))
+            res = ops.sow_backward_short(layers)
+            dx = res[-1][0]        # (summed last sibling first: _input_grad)
+            for g in reversed(res[:-1]):
+                dx = dx + g[0]
+            grads = []
+            for (_, dA, dB, dbias) in res:
+                grads += [dA, dB, None, None, dbias]
+            return (dx.reshape(ctx.x_shape), None, None, None, None, *grads)
         if sinks is not None and x2.shape[0] > 0 and all(
                 s.usable(tensors[5 * i], tensors[5 * i + 1], tensors[5 * i + 4]) for i, s in enumerate(sinks)):
             # FactorBucket.attach(): ONE data-gradient launch for the siblings, weight gradients queued with their decoder

@@ -93,7 +93,16 @@ class _SoWFunction(torch.autograd.Function):
         # an E4M3 accumulator (codes, exponents): the dense kernels run on its image in the scratch arena; what is saved
         # below is the codes, and backward builds the image again
         (img_down, img_up), = ops.acc_operands([(acc_down, acc_up)], x2.dtype)
-        y, h = ops.sow_forward(x2, A, B, img_down, img_up, bias, scale, param_f32=cdt is not None, fuse_acc=fuse)
+        # inside sow_amd.short_rows: a dense accumulator (or the image of a quantised one) at a row count the measured rule keeps
+        # runs forward and data gradient on the skinny kernel pair; FactorBucket sinks and autocast keep the path below
+        res = None
+        if cdt is None and sink is None and ops.short_admits(x2, A, B, img_down, img_up, bias):
+            res = ops.sow_forward_short([(x2, A, B, img_down, bias, scale)])
+        ctx.short = res is not None
+        if res is not None:
+            (y,), (h,) = res
+        else:
+            y, h = ops.sow_forward(x2, A, B, img_down, img_up, bias, scale, param_f32=cdt is not None, fuse_acc=fuse)
         ctx.fuse_acc = fuse
         ctx.save_for_backward(x2, h, A, B, acc_down, acc_up)
         ctx.scale = scale
@@ -110,7 +119,9 @@ class _SoWFunction(torch.autograd.Function):
         (acc_down, acc_up), = ops.acc_operands([(acc_down, acc_up)], x2.dtype)
         dy2 = dy.reshape(-1, dy.shape[-1])
         sink = ctx.sink
-        if sink is not None and x2.shape[0] > 0 and sink.usable(A, B, ctx.bias):
+        if ctx.short:
+            (dx, dA, dB, dbias), = ops.sow_backward_short([(dy2, x2, h, A, B, acc_down, ctx.scale, ctx.has_bias)])
+        elif sink is not None and x2.shape[0] > 0 and sink.usable(A, B, ctx.bias):
             # FactorBucket.attach(): the weight gradients accumulate straight into the flat gradient buffer (p.grad is a
             # view of it), so autograd gets None for A and B (and for a bias that is a bucket member: its gradient comes
             # out of the same partial sums); the slab-partial sums are reduced for all layers in one launch by
@@ -257,6 +268,11 @@ class SoWLinear(nn.Module):
                     return ys[0].reshape(*x.shape[:-1], B.shape[1])
             # every other call of a quantised layer: the existing dense path on the image
             (acc_down, acc_up), = ops.acc_operands([(acc_down, acc_up)], x2.dtype)
+            # inside sow_amd.short_rows: 65 ... 1024 rows of a dense accumulator on the skinny pair, h_save = NULL
+            if cdt is None and ops.short_admits(x2, A, B, acc_down, acc_up, self.bias):
+                res = ops.sow_forward_short([(x2, A, B, acc_down, self.bias, float(self.scale))], save_h=False)
+                if res is not None:
+                    return res[0][0].reshape(*x.shape[:-1], B.shape[1])
             y, _ = ops.sow_forward(x2, A, B, acc_down, acc_up, self.bias, float(self.scale), save_h=False,
                                    param_f32=cdt is not None, fuse_acc=_fuse_acc(x2, B, acc_down, acc_up, cdt is not None))
             return y.reshape(*x.shape[:-1], B.shape[1])

@@ -547,6 +547,85 @@ def skinny_rows_pays(T: int, d_in: int, d_out: int) -> bool:
     return SKINNY_MAX_T < T <= SKINNY_ROWS_MAX
 
 
+SHORT_ROWS_MAX = 1024      # include/sow_amd.h: SOW_SHORT_ROWS_MAX
+_SHORT_ROWS = False        # sow_amd.short_rows / set_short_rows: training calls of short batches on the skinny kernel pair
+_SHORT_WS_BYTES: dict = {}
+
+
+def set_short_rows(on: bool) -> bool:
+    """Whether bf16 / f16 dense-accumulator layers of at most 1024 flattened rows run forward and data gradient on the skinny
+    kernel pair (sow_forward_short / sow_backward_short) where short_rows_pays admits the call.  Off by default: opt-in, because
+    such a call rounds y and dX once from one fp32 sum where the default path's bits are pinned by the module tests.  Returns
+    the value it replaces."""
+    global _SHORT_ROWS
+    if not isinstance(on, bool):
+        raise ValueError(f"sow_amd.set_short_rows: {on!r} is not a bool")
+    old, _SHORT_ROWS = _SHORT_ROWS, on
+    return old
+
+
+@contextlib.contextmanager
+def short_rows(on: bool = True):
+    """with sow_amd.short_rows(): ...  -- set_short_rows(on) for the block, the earlier value restored after it."""
+    old = set_short_rows(on)
+    try:
+        yield
+    finally:
+        set_short_rows(old)
+
+
+def short_rows_enabled() -> bool:
+    return _SHORT_ROWS
+
+
+def short_workspace_bytes(T: int, d_in: int, d_out: int, r: int, dt: int, forward_only: bool = False) -> int:
+    """sow_short_workspace_bytes (forward_only: sow_forward_short_workspace_bytes) of a dense-accumulator layer, memoised per
+    shape: 0 = outside the admitted set.  Pure functions of the shape."""
+    key = (T, d_in, d_out, r, dt, forward_only)
+    n = _SHORT_WS_BYTES.get(key)
+    if n is None:
+        lib = _lib.load()
+        q = lib.sow_forward_short_workspace_bytes if forward_only else lib.sow_short_workspace_bytes
+        n = _SHORT_WS_BYTES[key] = int(q(T, d_in, d_out, r, _lib.ACC_DENSE, dt))
+    return n
+
+
+# (d_in, d_out) -> the most rows at which the new pair won: the table of short_rows_pays' docstring
+SHORT_ROWS_TABLE: dict = {(768, 768): 256, (768, 3072): 256, (3072, 768): 256, (4096, 4096): 128, (4096, 11008): 128,
+                          (11008, 4096): 128, (512, 512): 256, (512, 1376): 256}
+
+
+def short_rows_pays(T: int, d_in: int, d_out: int) -> bool:
+    """The measured dispatch rule of the module surface inside sow_amd.short_rows (profiles/short_rows.txt, DESIGN.md section
+    4.5e): the (rows, shape) classes at which forward + data gradient on sow_forward_short / sow_backward_short (n) beat
+    sow_forward + the data phase of sow_backward_ex (a) by more than the larger run-to-run spread of the two.  One line per
+    measured shape, the most rows up to which n won at EVERY measured row count and rank (bf16, MI355X):
+
+        768->768: T <= 256
+        768->3072: T <= 256
+        3072->768: T <= 256
+        4096->4096: T <= 128
+        4096->11008: T <= 128
+        11008->4096: T <= 128
+        512->512: T <= 256
+        512->1376: T <= 256
+
+    Measured (us, forward + data gradient in one timed region, a against n, +- the larger spread): 768->768 r = 8 at T = 128 /
+    256 / 512 / 1024: 68.3 / 69.0 / 69.3 / 70.8 against 37.9 / 44.7 / 73.1 / 121.1 (+- 2.5 / 2.3 / 2.6 / 2.0); 768->3072: 110.2 /
+    109.0 / 91.5 / 90.4 against 53.6 / 76.4 / 120.5 / 219.7; 3072->768: 125.2 / 124.9 / 115.2 / 114.5 against 58.5 / 93.6 / 167.4
+    / 303.3; 4096->4096 r = 50 at T = 65 / 128 / 256 / 512 / 1024: 205.5 / 203.5 / 203.9 / 137.3 / 138.5 against 106.0 / 145.3 /
+    251.6 / 459.9 / 877.6; 4096->11008 r = 50: 298.3 / 300.0 / 252.8 / 212.9 / 224.1 against 194.8 / 258.0 / 475.2 / 921.0 /
+    1845.3; 11008->4096 r = 50: 348.4 / 348.5 / 331.9 / 213.2 / 219.0 against 217.1 / 301.3 / 560.2 / 1085.4 / 2188.8; 512->512
+    r = 50 at T = 256 / 1024: 64.7 / 66.1 against 41.6 / 97.3; 512->1376: 73.7 / 73.3 against 50.4 / 133.6.  n's time grows with
+    the row blocks -- W is read once per 64 rows -- while a is flat and drops where its product leaves the generic GEMM, so a / n
+    falls from 2.1 to 0.1 along every shape.
+    The rule EXCLUDES: every row count above a shape's line (n lost there, or the count lies between a measured win and a
+    measured loss: 257 ... 511 on the narrow shapes, 129 ... 255 on llama-7b's); every shape that was not measured; and calls
+    of at most 64 rows, which the sweep does not hold.  NOT measured: f16, a full GLUE step, hardware counters."""
+    tmax = SHORT_ROWS_TABLE.get((d_in, d_out), 0)
+    return 64 < T <= tmax
+
+
 def skinny_pays(T: int, d_in: int, d_out: int) -> bool:
     """The measured dispatch rule of the module surface (profiles/skinny_forward.txt): the token
     counts and widths at which the fused skinny forward is faster than the path it replaces (quantised formats: acc_format.py)."""
@@ -666,6 +745,119 @@ def _forward_skinny(layers, _rows: bool) -> Optional[list]:
         return None
     _lib.check(rc, "sow_forward_skinny_rows" if _rows else "sow_forward_skinny")
     return ys
+
+
+def short_admits(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, acc_up, bias) -> bool:
+    """Whether a module call on the flattened input x2 goes to sow_forward_short / sow_backward_short: inside sow_amd.short_rows,
+    a bf16 / f16 call with parameters of the input's dtype, a dense accumulator of that dtype (the image of a quantised one
+    included: pass the image), a shape the library admits and short_rows_pays keeps.  False keeps the existing path."""
+    if not _SHORT_ROWS:
+        return False
+    dt = _DT.get(x2.dtype)
+    if dt is None or dt == _lib.F32 or not x2.is_cuda or x2.dim() != 2 or A.dim() != 2 or B.dim() != 2:
+        return False
+    if acc_down is None or acc_down.numel() == 0 or acc_down.dtype in BY_CODE_DTYPE or (acc_up is not None and acc_up.numel()):
+        return False
+    T, d_in = x2.shape
+    r, d_out = B.shape
+    if tuple(A.shape) != (d_in, r) or tuple(acc_down.shape) != (d_in, d_out) or (bias is not None and tuple(bias.shape) != (d_out,)):
+        return False
+    for t in (A, B, bias, acc_down):
+        if t is not None and (t.dtype != x2.dtype or t.device != x2.device):
+            return False
+    return short_rows_pays(T, d_in, d_out) and short_workspace_bytes(T, d_in, d_out, r, dt) > 0
+
+
+def _short_args(n: int):
+    return (_lib.LayerArgs * n)()
+
+
+def sow_forward_short(layers, save_h: bool = True):
+    """(ys, hs) of n <= 16 dense-accumulator layer calls of at most 1024 rows each through sow_forward_short (include/sow_amd.h):
+    `layers` = one (x2, A, B, acc_down, bias, scale) per layer, everything of x2's dtype.  hs[i] is the h_save the weight phases
+    read, or None with save_h = False (a no-grad call).  None when the library refuses the set: nothing was launched."""
+    lib = _lib.load()
+    n = len(layers)
+    if n == 0:
+        return [], []
+    if n > SKINNY_MAX_LAYERS:
+        return None
+    x0 = layers[0][0]
+    dt = _dt(x0)
+    keep, sizes, total = [], [], 0
+    for x2, A, B, acc_down, bias, scale in layers:
+        dev = _need_gpu(x2, A, B, acc_down, bias)
+        if dev != x0.device or any(t is not None and t.dtype != x0.dtype for t in (x2, A, B, acc_down, bias)):
+            raise TypeError("sow_amd.sow_forward_short: the tensors of a call share one dtype and one device")
+        T, d_in = x2.shape
+        r, d_out = B.shape
+        if tuple(A.shape) != (d_in, r) or tuple(acc_down.shape) != (d_in, d_out) or (bias is not None and tuple(bias.shape) != (d_out,)):
+            raise ValueError("sow_amd.sow_forward_short: operand shapes do not match")
+        nws = short_workspace_bytes(T, d_in, d_out, r, dt, forward_only=True) if T else 0
+        if T and not nws:
+            return None
+        nws = (nws + 255) & ~255
+        keep.append((x2.contiguous(), A.contiguous(), B.contiguous(), acc_down.contiguous(), None if bias is None else bias.contiguous()))
+        sizes.append((total, nws))
+        total += nws
+    ws = _ws(total, x0.device)
+    base = ws.data_ptr()
+    arr = _short_args(n)
+    ys, hs = [], []
+    for i, ((x2, A, B, acc_down, bias), (off, nws), layer) in enumerate(zip(keep, sizes, layers)):
+        T, d_out = x2.shape[0], B.shape[1]
+        y = torch.empty((T, d_out), dtype=x2.dtype, device=x0.device)
+        h = torch.empty(T * 64, dtype=x2.dtype, device=x0.device) if save_h else None
+        ys.append(y)
+        hs.append(h)
+        a = arr[i]
+        a.x, a.A, a.B, a.acc_down, a.bias, a.y, a.h_save = _ptr(x2), _ptr(A), _ptr(B), _ptr(acc_down), _ptr(bias), _ptr(y), _ptr(h)
+        a.T, a.d_in, a.d_out, a.r_live, a.acc_kind, a.scale = T, x2.shape[1], d_out, B.shape[0], _lib.ACC_DENSE, float(layer[5])
+        a.workspace, a.workspace_bytes = base + off, nws
+    rc = _launch_rc(x0.device, lib.sow_forward_short, arr, n, dt)
+    if rc == _lib.ERR_UNSUPPORTED:
+        return None
+    _lib.check(rc, "sow_forward_short")
+    return ys, hs
+
+
+def sow_backward_short(layers):
+    """[(dx, dA, dB, dbias)] of n <= 16 layer calls: the data gradients through sow_backward_short (one call for the set), then the
+    existing weight phases of every layer on the same workspace (sow_backward with SOW_BWD_WEIGHTS), which read the dh the data
+    phase left there.  `layers` = one (dy2, x2, h, A, B, acc_down, scale, need_bias) per layer, h from sow_forward_short."""
+    lib = _lib.load()
+    n = len(layers)
+    if n == 0:
+        return []
+    x0 = layers[0][1]
+    dt = _dt(x0)
+    arr = _short_args(n)
+    keep = []
+    for i, (dy2, x2, h, A, B, acc_down, scale, need_bias) in enumerate(layers):
+        dev = _need_gpu(dy2, x2, h, A, B, acc_down)
+        if any(t.dtype != x0.dtype or t.device != x0.device for t in (dy2, x2, h, A, B, acc_down)):
+            raise TypeError("sow_amd.sow_backward_short: the tensors of a call share one dtype and one device")
+        T, d_in = x2.shape
+        r, d_out = B.shape
+        dy2, A, B, acc_down = dy2.contiguous(), A.contiguous(), B.contiguous(), acc_down.contiguous()
+        nws = short_workspace_bytes(T, d_in, d_out, r, dt)
+        if T and not nws:
+            raise ValueError("sow_amd.sow_backward_short: the library does not admit this layer")
+        ws = _ws(nws, dev)
+        dx = torch.empty((T, d_in), dtype=x2.dtype, device=dev)
+        a = arr[i]
+        a.dy, a.dx, a.A, a.B, a.acc_down = _ptr(dy2), _ptr(dx), _ptr(A), _ptr(B), _ptr(acc_down)
+        a.T, a.d_in, a.d_out, a.r_live, a.acc_kind, a.scale = T, d_in, d_out, r, _lib.ACC_DENSE, float(scale)
+        a.workspace, a.workspace_bytes = _ptr(ws), ws.numel()
+        keep.append((dy2, A, B, acc_down, ws, dx))
+    _launch(x0.device, "sow_backward_short", lib.sow_backward_short, arr, n, dt)
+    out = []
+    for (dy2, A, B, acc_down, ws, dx), (_, x2, h, _, _, _, scale, need_bias) in zip(keep, layers):
+        if x2.shape[0] == 0:
+            out.append(sow_backward(dy2, x2, h, A, B, acc_down, None, scale, need_bias))
+        else:
+            out.append(sow_backward(dy2, x2, h, A, B, acc_down, None, scale, need_bias, phases=_lib.BWD_WEIGHTS, dx=dx, workspace=ws))
+    return out
 
 
 def workspace_bytes(T: int, d_in: int, d_out: int, r: int, r_acc: int, kind: int, dtype: torch.dtype,
