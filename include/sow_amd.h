@@ -187,7 +187,7 @@ const char* sow_error_string(int code);
  * never touches them.  They are the library's ONLY process-wide state: a table of atomics initialised from the
  * environment (SOW_AMD_<NAME>) once, at first use; no launch path calls getenv.  Names: FORCE_CHAIN_V1, NO_SHORT_SPLIT,
  * NO_FUSED_H, FORCE_GEMM_V1, TN_NARROW, NO_GEMM3S, NO_GROUPED, NO_PERSIST, NO_NT_STORE, NT_LOAD, NO_PAIR_FLUSH, F32_EXACT, NO_PARK16, TN_NO_NT_LOAD, NO_TN_ROWS, NO_GEMM4H, NO_CHAIN3F, NO_TN_F32Q, NO_SPLITK,
- * NO_WIDE_CHAIN, NO_SHARED_X, NO_RAGGED, NO_RAGGED_GEMM, NO_BLOCKED_QR, NO_SKINNY, NO_H_ROWS, NO_FUSED_ACC, NO_DEEP_ACC
+ * NO_WIDE_CHAIN, NO_SHARED_X, NO_RAGGED, NO_RAGGED_GEMM, NO_BLOCKED_QR, NO_SKINNY, NO_H_ROWS, NO_X_PAIR, NO_FUSED_ACC, NO_DEEP_ACC
  * (value 1 = on, -1 / 0 = off), NO_ROW_ALIGN (1 = on, 2 = on for the X stages only, 3 = on for the Y slices only; it keeps
  * and returns that value) and GEMM3S, GEMM3, GEMM4
  * (1 = force, 0 = forbid, -1 = automatic).  sow_set_switch returns SOW_ERR_UNSUPPORTED for an unknown name;

@@ -55,7 +55,7 @@ static const char* const kSwitchNames[SW_COUNT] = {"FORCE_CHAIN_V1", "NO_SHORT_S
                                                    "NO_PARK16",      "TN_NO_NT_LOAD",  "NO_TN_ROWS",     "GEMM4",          "NO_GEMM4H",      "NO_CHAIN3F",     "NO_TN_F32Q",     "NO_SPLITK",
                                                    "NO_WIDE_CHAIN",  "NO_SHARED_X",    "NO_RAGGED",      "NO_RAGGED_GEMM", "NO_BLOCKED_QR",
                                                    "NO_SKINNY",      "NO_FUSED_ACC",   "NO_DEEP_ACC",    "NO_F16_TN",
-                                                   "NO_ROW_ALIGN",   "NO_H_ROWS"};
+                                                   "NO_ROW_ALIGN",   "NO_X_PAIR",      "NO_H_ROWS"};
 static std::atomic<int> g_switch[SW_COUNT];
 static std::once_flag g_switch_once;
 static void switches_from_env() {

@@ -84,7 +84,7 @@ constexpr int C2_BM = 32 * C2_NTG;    // tokens per workgroup
 #define C2_NSLOT_X 6
 #define C2_AHEAD_X 5
 #endif
-constexpr int C2_DEPTH = C2_DEPTH_X;   // X stage slots per token group (DEPTH - 1 in flight)
+constexpr int C2_DEPTH = C2_DEPTH_X;   // X stage slots per token group (c2_x_issued: DEPTH - 2 or DEPTH - 1 in flight)
 constexpr int C2_STAGE = 4096;        // [32 tok][64 k] bf16
 constexpr int C2_NSLOT = C2_NSLOT_X;   // factor chunk slots
 constexpr int C2_AHEAD = C2_AHEAD_X;   // chunks the loaders run ahead: the slot of chunk c + AHEAD held chunk c - 1, drained before barrier c
@@ -102,6 +102,19 @@ constexpr int C2_LDS = C2_RING0 + C2_NTG * C2_RING;   // 80 KiB: two workgroups 
 constexpr int C2_THREADS = 64 * (C2_NCW + C2_NLW);
 constexpr int C2_RESIDENT = 512;      // resident workgroups of a persistent grid (2 per CU x 256 CUs)
 
+
+// X issue schedule of a token group's ring: the number of stages issued when a wave reaches the counted wait of stage `st`,
+// that is, by the prologue and after the barriers of stages 0 .. st - 1.  The prologue (st = 0), the loop (what follows barrier
+// st is the difference between st + 1 and st) and the wait count (issued - st - 1 stages are newer than `st`) all read it here.
+//   one by one: depth - 1 stages ahead; stage st + depth - 1 follows barrier st into the slot of stage st - 1.
+//   paired    : depth - 2 stages ahead; stages st + depth - 2 and st + depth - 1 follow the barrier of every EVEN st into the
+//               slots of stages st - 2 and st - 1, odd stages issue nothing: the two 128-byte halves of 256 contiguous bytes of
+//               a row leave the same wave back to back.  An odd count ends with a single stage.  (A prologue that fills the
+//               whole ring -- every slot is free at the start of a block -- was slower in the step: profiles/x_pair_ab.txt.)
+__host__ __device__ constexpr int c2_x_issued(int st, int nst, int depth, bool paired) {
+  const int n = paired ? depth - 2 + 2 * ((st + 1) >> 1) : depth - 1 + st;
+  return n < nst ? n : nst;
+}
 
 template <bool TR> __device__ __forceinline__ int img_chunk(int row, int c) {
   return TR ? (c ^ (((row >> 1) & 1) << 2)) : (c ^ ((row >> 1) & 7));
@@ -341,16 +354,17 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
 #pragma unroll
   for (int i = 0; i < 16; ++i) hacc[i] = 0.f;
 
-  // stage s+DEPTH-1 is issued after barrier(s): by then BOTH waves of the token group are done with stage s-1
-  const int pre = nst < (C2_DEPTH - 1) ? nst : (C2_DEPTH - 1);
-  for (int st = 0; st < pre; ++st) issue_x(st);
+  // a stage is issued after barrier(s) into the slot of stage s-1 or older: by then BOTH waves of the token group are done with it
+  const bool xpair = p.x_pair != 0;
+  int issued = 0;   // X stages issued so far (c2_x_issued)
+  for (const int pre = c2_x_issued(0, nst, C2_DEPTH, xpair); issued < pre; ++issued) issue_x(issued);
 
   // ================================================================== phase 1: H^T = F1^T . X^T (rank tile hh)
   uint64_t tw_x = 0, tw_b1 = 0, tw_b2 = 0;
 #pragma unroll 1
   for (int st = 0; st < nst; ++st) {
-    // stages issued after `st` at this point: st+1 .. st+DEPTH-2
-    const int newer = (nst - 1 - st) < (C2_DEPTH - 2) ? (nst - 1 - st) : (C2_DEPTH - 2);
+    // stages issued after `st` at this point: st+1 .. issued-1
+    const int newer = issued - st - 1;
     const uint64_t tk0 = C2_TICK();
     wait_groups<2>(newer);   // this wave's half of X stage `st` has landed
     C2_ACC(tw_x, tk0);
@@ -358,7 +372,7 @@ __device__ __forceinline__ void chain2_block(const ChainParams& p, const int bid
     raw_barrier();           // ... and so have the partner's half and factor chunk `st`
     C2_ACC(tw_b1, tk1);
     if (st == 0) C2_STAMP(1);
-    if (st + C2_DEPTH - 1 < nst) issue_x(st + C2_DEPTH - 1);   // into the slot of stage st-1
+    for (const int upto = c2_x_issued(st + 1, nst, C2_DEPTH, xpair); issued < upto; ++issued) issue_x(issued);
     const uint32_t xs = ring_a + (uint32_t)((st % C2_DEPTH) * C2_STAGE) + xoff;
     const uint32_t fs = slot_a + (uint32_t)((st % C2_NSLOT) * C2_FSLOT);
     // shifted stage: k-steps 0, 1 from the upper half of chunk st - 1 (stage 0: any resident slot, not multiplied)
@@ -867,6 +881,7 @@ int launch_chain2_group(const ChainParams* ps, int n, bool bwd, int dtype, hipSt
     g.p[i].nt_store = sw_on(SW_NO_NT_STORE) ? 0 : 1;
     g.p[i].nt_load = sw_on(SW_NT_LOAD) ? 1 : 0;
     g.p[i].h_rows = sw_on(SW_NO_H_ROWS) ? 0 : 1;
+    g.p[i].x_pair = sw_on(SW_NO_X_PAIR) ? 0 : 1;
     g.p[i].pair_flush = sw_on(SW_NO_PAIR_FLUSH) ? 0 : 1;
     g.start[i] = (int)total;
     total += chain2_grid(p);
@@ -927,3 +942,10 @@ int launch_chain2_group(const ChainParams* ps, int n, bool bwd, int dtype, hipSt
 int launch_chain2(const ChainParams& p, bool bwd, int dtype, hipStream_t stream) { return launch_chain2_group(&p, 1, bwd, dtype, stream); }
 
 }  // namespace sow
+
+// the X issue schedule of chain2_block and the ring depth of this build, for the host test that walks the ring
+// (tests/test_host_x_pair_cpu.py; not declared in include/sow_amd.h)
+extern "C" int sow_debug_chain2_x_issued(int st, int nst, int depth, int paired) {
+  return sow::c2_x_issued(st, nst, depth, paired != 0);
+}
+extern "C" int sow_debug_chain2_x_depth(void) { return sow::C2_DEPTH; }

@@ -210,6 +210,7 @@ enum Switch : int {
   SW_NO_F16_TN,           // f16 weight gradients on the generic kernel for every shape, never grouped, no row-owner plan
   SW_NO_ROW_ALIGN,        // chain kernel cuts the pieces of 64-bytes-off-a-line row pitches at multiples of 64 columns, as for every other
                           // pitch: 1 = both sides, 2 = the X stages only, 3 = the Y slices only
+  SW_NO_X_PAIR,           // chain kernel issues its X stages one per stage barrier (128-byte pieces per row) instead of two at every other one
   SW_NO_H_ROWS,           // chain kernel writes h_save / dh as 8-byte pieces per lane instead of whole streaming rows
   SW_COUNT
 };

@@ -32,6 +32,7 @@ struct ChainParams {
   int h_rows;     // chain2: write Hsave as whole 128-byte rows with the non-temporal hint (through an LDS image)
   int pair_flush; // chain2: store two output slices at a time (256-byte pieces per row)
   int row_align;  // chain2 (set by launch_chain2_group): bit 0 / bit 1 = X stages / Y slices cut on 128-byte lines of every row
+  int x_pair;     // chain2 (set by launch_chain2_group): X stages are issued two at a time (256 contiguous bytes per row)
   // chain3f (fp32, T >= 8192): scratch for the pre-split factor planes (chain3f_plane_bytes(D1, D2), 16-byte aligned,
   // from the caller's workspace); nullptr = not available, the launch falls back to chain2f
   void* planes;
