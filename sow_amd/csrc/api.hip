@@ -223,7 +223,7 @@ static int gemm_auto(const void* A, int64_t lda, const void* B, int64_t ldb, boo
 
 extern "C" {
 
-int sow_version(void) { return 123; }
+int sow_version(void) { return 124; }
 
 int sow_set_switch(const char* name, int value) {
   if (!name) return SOW_ERR_NULL;
@@ -311,9 +311,7 @@ static WsPlan plan_ws(int64_t T, int d_in, int d_out, int r_live, int r_acc, int
   w.off_hp = off;     // fp32 partial H of the short-T split: splits * T * 64 floats, splits <= 256 / ceil(T / 64)
   off += short_hp_bytes(T, d_in, d_out, r_live, dtype);
   if (r_live <= 64) {
-    const int cg_in = (d_in + 63) / 64, cg_out = (d_out + 63) / 64;
-    const int quads = (dtype == SOW_F32 && tn_f32q_shape_ok(T, d_in, d_out)) ? (cg_in + 3) / 4 + (cg_out + 3) / 4 : 0;
-    w.ns = tn_pick_slabs(T, cg_in + cg_out, (cg_in + 1) / 2 + (cg_out + 1) / 2, quads, dtype, &w.slab_len);
+    w.ns = tn_pick_slabs(T, d_in, d_out, dtype, &w.slab_len);
     w.ns_cap = w.ns;
     // both 16-bit dtypes (a pure function of shape and dtype: NO_F16_TN does not shrink the f16 workspace)
     if ((dtype == SOW_BF16 || dtype == SOW_F16) && T >= 1024) {
@@ -360,7 +358,8 @@ static WsPlan plan_ws(int64_t T, int d_in, int d_out, int r_live, int r_acc, int
     }
     off += al256(w.wide_bytes);
   }
-  // token-slab partials of the wide weight-gradient kernel (skinny_tn_wide.hip)
+  // token-slab partials of the wide weight-gradient kernel (skinny_tn_wide.hip), whatever NO_WIDE_CHAIN / NO_RAGGED say;
+  // pw_bytes != 0 is the shape half of pick_tn_wide_rank
   w.off_pw = off;
   w.pw_bytes = 0;
   if (tnw_shape_ok(r_live, d_in, d_out, dtype) || rag_layer(r_live, r_acc, acc_kind, d_in, d_out, dtype)) {
@@ -730,7 +729,7 @@ static inline Phases decode_phases(int phases) {
 // The two slab-partial jobs of a layer with r_live <= 64: dA = x^T dh ; dB^T = dY^T h ; dbias = colsum(dY) via the all-ones
 // column 63 (the chain kernels write 1.0 into column 63 of h_save / dh whenever r_live <= 63).
 // vec: fp32 reads 16-byte vectors, the 16-bit dtypes 4-byte pairs.  The grouped launch takes 16-bit dtypes only
-// (tn_group_supported refuses fp32), so the one rule serves it as it serves the single layer.
+// (pick_tn never answers TN_DMA_WIDE for fp32), so the one rule serves it as it serves the single layer.
 static TnParams tn_params(const sow_layer_args& L, const WsPlan& w, char* ws, int dtype) {
   TnParams tp{};
   tp.njobs = 2, tp.T = L.T, tp.ns = w.ns, tp.slab_len = w.slab_len;
@@ -744,6 +743,25 @@ static TnParams tn_params(const sow_layer_args& L, const WsPlan& w, char* ws, in
   tp.job[1] = TnJob{L.dy, L.h_save, (float*)(ws + w.off_p1), (int64_t)L.d_out, L.d_out, ones_ok ? 63 : -1, (L.d_out + 63) / 64,
                     vec_ok(L.dy, L.d_out), 1};
   return tp;
+}
+// an operand of the row-owner kernel: job J of tn_params with its group-planned slabs (launch_tn_rows fills in the rest)
+static TnRowsItem tn_rows_item(const TnJob& J, int64_t T, int ns, int slab_len) {
+  return TnRowsItem{J.M, J.S, J.partial, J.ldm, T, J.D, 0, 0, 0, 0, ns, slab_len, 0};
+}
+// The wide-rank arm of the weight-gradient selector (r_live > 64; the rule: skinny_tn.hip).  w.pw_bytes != 0: plan_ws found
+// tnw_shape_ok or an admitted ragged layer and the workspace holds the partials; what is left for launch_tn_wide to refuse is
+// checked here, so the pick is what runs.
+static TnKernel pick_tn_wide_rank(const sow_layer_args& L, const WsPlan& w, char* ws) {
+  const bool rag = L.d_in % 8 != 0 || L.d_out % 8 != 0;
+  if (!w.pw_bytes || sw_on(rag ? SW_NO_RAGGED : SW_NO_WIDE_CHAIN)) return TN_GEMM_PAIR;
+  return tnw_operands_ok(L.x, ws + w.off_dh, L.dy, L.h_save, rag) ? TN_WIDE_RANK : TN_GEMM_PAIR;
+}
+// the kernel of layer L's PARTIAL phase (T > 0, plan w); *tp: its operands when r_live <= 64
+static TnKernel pick_layer_tn(const sow_layer_args& L, const WsPlan& w, int dtype, TnParams* tp) {
+  char* ws = ws_base(L.workspace);
+  if (L.r_live > 64) return pick_tn_wide_rank(L, w, ws);
+  *tp = tn_params(L, w, ws, dtype);
+  return pick_tn(*tp, dtype);
 }
 // the reduction of the slab partials of one layer (shared by sow_backward_ex and the deferred, batched form)
 static ReduceParams make_reduce_params(const WsPlan& w, char* ws, void* dA, void* dB, void* dbias_ones, int d_in, int d_out,
@@ -972,11 +990,9 @@ static int backward_impl(const sow_layer_args& L, int dtype, int gdt, int phases
   // kernel, else the generic GEMM composition
   if (do_data && (rc = wide_live_term(v, beta, c))) return rc;
   if (!ph.partial) return SOW_OK;   // wide ranks: the PARTIAL phase does all of the weight gradients
-  if (w.pw_bytes && (rag_w || (!sw_on(SW_NO_WIDE_CHAIN) && tnw_shape_ok(r_live, d_in, d_out, dtype)))) {
-    rc = launch_tn_wide(L.x, dh, L.dy, L.h_save, L.dA, L.dB, L.dbias, T, d_in, d_out, r_live, L.scale, L.grad_beta, dtype, gdt,
-                        ws + w.off_pw, w.pw_bytes, stream);
-    if (rc != SOW_ERR_UNSUPPORTED) return rc;
-  }
+  if (pick_tn_wide_rank(L, w, ws) == TN_WIDE_RANK)
+    return launch_tn_wide(L.x, dh, L.dy, L.h_save, L.dA, L.dB, L.dbias, T, d_in, d_out, r_live, L.scale, L.grad_beta, dtype, gdt,
+                          ws + w.off_pw, w.pw_bytes, stream);
   rc = launch_gemm_out(L.x, d_in, true, dh, r_live, false, L.dA, r_live, nullptr, d_in, r_live, (int)T, 1.f, L.grad_beta, dtype, gdt,
                        stream);
   if (rc) return rc;
@@ -1041,7 +1057,9 @@ static bool group_chain_params(const sow_layer_args& L, bool bwd, int dtype, con
 // f16 takes the plan only when the caller asks for it (SOW_BWD_GROUP_SLABS: a deferred reduction); a call that runs both
 // weight phases itself keeps the column-owner kernel for f16, whose grouped results are pinned bit-identical to single calls.
 static bool group_rows_plan(const sow_layer_args* layers, int n, int dtype, int phases, int* ns, int* slab_len) {
-  if (!tn_dma_dtype(dtype) || (dtype == SOW_F16 && !(phases & SOW_BWD_GROUP_SLABS)) || n < 1 || n > TN_MAXG) return false;
+  // (the 16-bit dtypes while they take the wide LDS-DMA kernel: not f16 under NO_F16_TN, neither under TN_NARROW)
+  if (tn_shape_kernel(0, 0, 0, dtype) != TN_DMA_WIDE || (dtype == SOW_F16 && !(phases & SOW_BWD_GROUP_SLABS)) || n < 1 || n > TN_MAXG)
+    return false;
   int64_t T[TNR_MAXI];
   int D[TNR_MAXI], cap[TNR_MAXI];
   for (int i = 0; i < n; ++i) {
@@ -1049,7 +1067,8 @@ static bool group_rows_plan(const sow_layer_args* layers, int n, int dtype, int 
     if (L.T <= 0 || L.r_live > 64 || (L.dbias && L.r_live > 63)) return false;
     const WsPlan w = plan_of(L, dtype);
     if (L.workspace_bytes < w.total + 255) return false;
-    if (L.d_in % 8 || L.d_out % 8 || !al16p(L.x) || !al16p(L.dy) || !al16p(L.h_save)) return false;
+    const TnParams tp = tn_params(L, w, ws_base(L.workspace), dtype);
+    if (!tn_operand_ok(tp.job[0], 8) || !tn_operand_ok(tp.job[1], 8)) return false;
     T[2 * i] = T[2 * i + 1] = L.T;
     D[2 * i] = L.d_in, D[2 * i + 1] = L.d_out;
     cap[2 * i] = cap[2 * i + 1] = w.ns_cap;
@@ -1374,12 +1393,8 @@ static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, i
     TnRowsItem items[TNR_MAXI];
     for (int i = 0; i < n; ++i) {
       const sow_layer_args& L = layers[i];
-      const WsPlan w = plan_of(L, dtype);
-      char* ws = ws_base(L.workspace);
-      items[2 * i] = TnRowsItem{L.x, ws + w.off_dh, (float*)(ws + w.off_p0), (int64_t)L.d_in, L.T, L.d_in, 0, 0, 0, 0, rns[2 * i],
-                                rslab[2 * i], 0};
-      items[2 * i + 1] = TnRowsItem{L.dy, L.h_save, (float*)(ws + w.off_p1), (int64_t)L.d_out, L.T, L.d_out, 0, 0, 0, 0,
-                                    rns[2 * i + 1], rslab[2 * i + 1], 0};
+      const TnParams tp = tn_params(L, plan_of(L, dtype), ws_base(L.workspace), dtype);
+      for (int j = 0; j < 2; ++j) items[2 * i + j] = tn_rows_item(tp.job[j], L.T, rns[2 * i + j], rslab[2 * i + j]);
     }
     if ((rc = launch_tn_rows(items, 2 * n, dtype, stream))) return rc;
   } else if (ph.partial) {
@@ -1393,19 +1408,14 @@ static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, i
       }
       const WsPlan w = plan_of(L, dtype);
       if (L.workspace_bytes < w.total + 255) return SOW_ERR_WORKSPACE;
-      bool grouped = false;
-      if (L.r_live <= 64 && !sw_on(SW_NO_GROUPED)) {
-        const TnParams tp = tn_params(L, w, ws_base(L.workspace), dtype);
-        if (tn_group_supported(tp, dtype)) {
-          batch[nb] = tp;
-          grouped = true;
-          if (++nb == TN_MAXG) {
-            if ((rc = launch_tn_group(batch, nb, dtype, stream))) return rc;
-            nb = 0;
-          }
+      // the layers of the wide 16-bit kernel share its grouped launch; every other pick runs on its own
+      if (!sw_on(SW_NO_GROUPED) && pick_layer_tn(L, w, dtype, &batch[nb]) == TN_DMA_WIDE) {
+        if (++nb == TN_MAXG) {
+          if ((rc = launch_tn_group(batch, nb, dtype, stream))) return rc;
+          nb = 0;
         }
-      }
-      if (!grouped && (rc = backward_impl(L, dtype, gdt, SOW_BWD_WEIGHTS_PARTIAL, perm, stream))) return rc;
+      } else if ((rc = backward_impl(L, dtype, gdt, SOW_BWD_WEIGHTS_PARTIAL, perm, stream)))
+        return rc;
     }
     if (nb && (rc = launch_tn_group(batch, nb, dtype, stream))) return rc;
   }
@@ -1537,6 +1547,50 @@ int sow_backward_group_plan(const sow_layer_args* layers, int n, int dtype, int 
       slabs_out[2 * i + 1] = rows ? rns[2 * i + 1] : ns;
     }
   return rows ? 1 : 0;
+}
+
+// Debug export (declared by tests/test_host_tn_pick_cpu.py only): the weight-gradient kernel of n <= TN_MAXG layers [T, d_in[i]]
+// x [T, d_out[i]] of rank r_live without accumulator, as sow_backward_ex (n = 1) or sow_backward_group (n > 1) with `phases`
+// would choose it.  Nothing is launched or dereferenced: the operands are fake pointers through the real plan_ws / tn_params /
+// group_rows path, 16-byte aligned except where `misalign` says one element further (bit 0 x, 1 dY, 2 h_save, 3 workspace).
+// out[9 i ..]: TnKernel, blocks of work (tn_blocks), ns and slab_len of x's operand, of dY's operand, bytes of the two partial
+// regions of the plan (wide rank: of its one region, and 0), 1 when the layer shares a grouped launch.
+int sow_debug_tn_pick(int n, int64_t T, const int* d_in, const int* d_out, int r_live, int has_dbias, int dtype, int phases,
+                      int misalign, int64_t* out) {
+  if (n < 1 || n > TN_MAXG || T < 0 || !d_in || !d_out || !out || !ok_dtype(dtype)) return SOW_ERR_SHAPE;
+  auto fake = [&](int bit) { return (void*)(((uintptr_t)1 << 20) + ((misalign >> bit) & 1) * esize(dtype)); };
+  sow_layer_args Ls[TN_MAXG];
+  for (int i = 0; i < n; ++i) {
+    const size_t bytes = plan_ws(T, d_in[i], d_out[i], r_live, 0, SOW_ACC_NONE, dtype).total + 512;
+    Ls[i] = single_layer(fake(0), fake(4), fake(4), nullptr, nullptr, nullptr, nullptr, fake(2), fake(1), fake(4), fake(4), fake(4),
+                         has_dbias ? fake(4) : nullptr, T, d_in[i], d_out[i], r_live, 0, SOW_ACC_NONE, 1.f, 0.f, fake(3), bytes);
+  }
+  int rns[TNR_MAXI], rslab[TNR_MAXI];
+  const bool rows = n > 1 && T > 0 && group_rows(Ls, n, dtype, phases, rns, rslab);
+  for (int i = 0; i < n; ++i) {
+    const sow_layer_args& L = Ls[i];
+    const WsPlan w = plan_of(L, dtype);
+    int64_t* o = out + 9 * i;
+    for (int j = 0; j < 9; ++j) o[j] = 0;
+    if (T == 0) continue;   // TN_NONE: the gradients are zeroed, no kernel of the family runs
+    TnParams tp{};
+    const TnKernel k = rows ? TN_ROWS : pick_layer_tn(L, w, dtype, &tp);
+    o[0] = k, o[8] = rows || (n > 1 && k == TN_DMA_WIDE && !sw_on(SW_NO_GROUPED));
+    if (L.r_live > 64) {
+      int len = 0;
+      const int ns = k == TN_WIDE_RANK ? tnw_pick_slabs(T, L.d_in, L.d_out, &len) : 0;
+      o[1] = (int64_t)ns * ((L.d_in + 63) / 64 + (L.d_out + 63) / 64), o[2] = o[4] = ns, o[3] = o[5] = len, o[6] = (int64_t)w.pw_bytes;
+      continue;
+    }
+    o[6] = (int64_t)(w.off_p1 - w.off_p0), o[7] = (int64_t)(w.off_planes - w.off_p1);
+    if (rows) {
+      for (int j = 0; j < 2; ++j) o[2 + 2 * j] = rns[2 * i + j], o[3 + 2 * j] = rslab[2 * i + j];
+      o[1] = (int64_t)rns[2 * i] * (((L.d_in + 63) / 64 + 15) / 16) + (int64_t)rns[2 * i + 1] * (((L.d_out + 63) / 64 + 15) / 16);
+    } else {
+      o[1] = tn_blocks(k, tp), o[2] = o[4] = tp.ns, o[3] = o[5] = tp.slab_len;
+    }
+  }
+  return SOW_OK;
 }
 
 int sow_backward_group_reduce_desc(const sow_layer_args* layers, int n, int dtype, int phases, void* descs_out, int* blocks_out) {

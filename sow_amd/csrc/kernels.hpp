@@ -101,23 +101,45 @@ struct ReduceParams {
   int ns;
   int blocks0;
 };
-// total_colgroups = 64-column groups over both jobs; total_colgroup_pairs = the same in pairs, rounded up per job
-// total_colgroup_quads > 0: the caller's shape takes the fp32 quad kernel (skinny_tn_f32q.hip: four column groups per block)
-int tn_pick_slabs(int64_t T, int total_colgroups, int total_colgroup_pairs, int total_colgroup_quads, int dtype, int* slab_len);
-bool tn_f32q_shape_ok(int64_t T, int d_in, int d_out);
+// Every way a layer's weight gradients are computed (the rule: skinny_tn.hip, above tn_shape_kernel).  Per kernel: 64-column
+// groups a workgroup owns (tn_groups_per_block) and what the slab length must be a multiple of (tn_slab_mult).
+enum TnKernel {
+  TN_NONE,        // no blocks: nothing is launched
+  TN_GENERIC,     // tn_partial_kernel<T>: 1 group; any operands, any slab length
+  TN_DMA,         // tn_partial_dma_kernel<T> (bf16 / f16): 1 group; slab_len % 16
+  TN_DMA_WIDE,    // tn_partial_dma_wide_kernel (bf16 / f16; also n layers in one grid, launch_tn_group): 2 groups; slab_len % 16
+  TN_ROWS,        // tn_partial_rows_kernel (bf16 / f16, grouped): all groups of a slab, 16 per column range; slab_len % 32, own plan
+  TN_F32_X3,      // tn_partial_dma_f32_kernel<true> (3 x bf16): 1 group; slab_len % 8
+  TN_F32_EXACT,   // tn_partial_dma_f32_kernel<false> (fp32 MFMAs): 1 group; slab_len % 8
+  TN_F32_WIDE,    // tn_partial_dma_f32_wide_kernel: 2 groups; slab_len % 8
+  TN_F32_QUAD,    // tn_partial_f32_quad_kernel: 4 groups, grid padded to a multiple of 8 slabs per operand; slab_len % 32
+  TN_WIDE_RANK,   // r > 64: tnw_partial_kernel + tnw_reduce_kernel (launch_tn_wide)
+  TN_GEMM_PAIR,   // r > 64: two transposed GEMMs and a column sum
+};
+constexpr int tn_groups_per_block(TnKernel k) { return k == TN_F32_QUAD ? 4 : (k == TN_DMA_WIDE || k == TN_F32_WIDE) ? 2 : 1; }
+constexpr int tn_slab_mult(TnKernel k) {
+  return (k == TN_ROWS || k == TN_F32_QUAD) ? 32 : (k == TN_DMA || k == TN_DMA_WIDE) ? 16 : (k == TN_F32_X3 || k == TN_F32_EXACT || k == TN_F32_WIDE) ? 8 : 1;
+}
+// what every LDS-DMA kernel asks of an operand: D and ldm multiples of 16 bytes' worth of elements, M and S 16-byte aligned
+// (a TnJob: and the ones column already in S)
+bool tn_operand_ok(const void* M, const void* S, int64_t ldm, int D, int elems_per_16B);
+bool tn_operand_ok(const TnJob& J, int elems_per_16B);
+// the kernel a layer of this shape takes when its operands are aligned: a function of shape, dtype and switches
+TnKernel tn_shape_kernel(int64_t T, int d_in, int d_out, int dtype);
+TnKernel pick_tn(const TnParams& p, int dtype);      // reads operands and switches, launches nothing
+int tn_blocks(TnKernel k, const TnParams& p);        // blocks of work = the grid (the persistent kernels run them on <= 256 workgroups)
+int launch_picked_tn(TnKernel k, const TnParams& p, int dtype, hipStream_t stream);
+int tn_pick_slabs(int64_t T, int d_in, int d_out, int dtype, int* slab_len);
 size_t tn_partial_bytes(int ns, int D);
 // skinny_tn_f32q.hip
-bool tn_f32q_ok(const TnParams& p);
 int launch_tn_f32q(const TnParams& p, hipStream_t stream);
-int launch_tn(const TnParams& p, int dtype, hipStream_t stream);
+int launch_tn(const TnParams& p, int dtype, hipStream_t stream);   // pick_tn, then launch_picked_tn
 constexpr int TN_MAXG = 8;   // layers per grouped launch of the wide bf16 kernel (a decoder block has 7)
 struct TnGroup {
   TnParams p[TN_MAXG];
   int start[TN_MAXG + 1];
   int n;
 };
-bool tn_group_supported(const TnParams& p, int dtype);
-bool tn_dma_dtype(int dtype);   // bf16, and f16 unless NO_F16_TN: the dtypes of the LDS-DMA weight-gradient kernels
 // Row-owner weight-gradient kernel (skinny_tn.hip: tn_partial_rows_kernel): one item per (layer, operand); a workgroup
 // owns ALL columns of a token slab (up to 1024 per column range), so S (h / dh) is read once per range instead of once
 // per 128 columns.  The slab counts are planned over the whole group (work per block equal across items).
@@ -232,6 +254,8 @@ struct TnwReduce {
   float scale, beta;
 };
 bool tnw_shape_ok(int r, int d_in, int d_out, int dtype);
+// x, dh, dY, h as launch_tn_wide wants them: 4-byte aligned (ragged widths: x and dY at any 2-byte offset)
+bool tnw_operands_ok(const void* x, const void* dh, const void* dy, const void* h, bool rag);
 int tnw_pick_slabs(int64_t T, int d_in, int d_out, int* slab_len);
 size_t tnw_partial_bytes(int64_t T, int d_in, int d_out, int r);
 // dA = x^T dh, dB = scale h^T dY, dbias = colsum(dY), each g = beta g + new; `ws` 256-byte aligned (tnw_partial_bytes);

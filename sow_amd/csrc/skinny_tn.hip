@@ -1270,39 +1270,99 @@ __global__ __launch_bounds__(256) void tn_reduce_batch_kernel(const ReduceParams
   tn_reduce_body<T>(descs[lo], b - starts[lo]);
 }
 
-// ---------------------------------------------------------------------------------------------
-int tn_pick_slabs(int64_t T, int total_colgroups, int total_colgroup_pairs, int total_colgroup_quads, int dtype, int* slab_len) {
-  const int bt = dtype == SOW_F32 ? TnCfg<float>::BT : TnCfg<bf16_t>::BT;
-  // Two workgroups per CU are resident (64 KiB of LDS each), 512 in all; slabs stay >= 512 tokens so the
-  // partial traffic (ns * D * 64 * 4 bytes) is a small fraction of the streamed operand.
-  //   bf16 (HBM-bound): see below; a multiple of 8 keeps the column groups of one slab on one XCD (S from that L2).
-  //   fp32 (MFMA-bound): AT MOST 512 blocks -- a 13 % overshoot is a second, nearly empty round on a saturated
-  //     matrix pipe (measured: 576 blocks 93 us vs 504 blocks 74 us).
-  int ns;
+// ---- host: which kernel takes a weight gradient, its slab plan and its grid ------------------------------------------
+// The one place where the weight-gradient kernel of a layer is chosen (TnKernel, kernels.hpp).  tn_shape_kernel answers from
+// the shape and the switches alone -- it is what the slab plan is made for -- pick_tn from the operands of a launch, and
+// launch_picked_tn launches what pick_tn said.  The rule, r <= 64:
+//   * fp32: the quad kernel from T >= 4096 with at least 3 column groups per operand (NO_TN_F32Q: never), else the wide 3 x bf16
+//     kernel; under F32_EXACT or TN_NARROW one of the narrow forms (exact MFMAs under F32_EXACT, whatever TN_NARROW says).
+//   * bf16 / f16: the wide LDS-DMA kernel; the narrow one under TN_NARROW; f16 under NO_F16_TN the generic kernel.
+//   * every LDS-DMA kernel wants both operands vector-aligned (tn_operand_ok: widths and pitches multiples of 16 bytes, M and S
+//     16-byte aligned, the ones column already in S) and a slab length that is a multiple of tn_slab_mult(kernel); a launch
+//     whose operands miss either runs tn_partial_kernel, in every dtype.
+//   * a grouped call (api.hip: backward_group_impl) takes the row-owner kernel for ALL its layers when group_rows admits the
+//     group (tn_rows_plan: 160 .. 256 blocks), else every layer pick_tn sends to the wide 16-bit kernel shares its grouped
+//     launch and the others go one by one.
+//   r > 64 (api.hip: pick_tn_wide_rank): tnw_partial_kernel where the plan holds its partial region and the operands are 4-byte
+//   aligned, else two transposed GEMMs and a column sum.
+// Asymmetries, kept as they were measured and tested:
+//   * f16 takes the row-owner kernel only under SOW_BWD_GROUP_SLABS (a deferred reduction); bf16 also when one call runs both
+//     weight phases (the f16 grouped results of such a call are pinned bit-identical to single calls);
+//   * the slab count is rounded down to a multiple of 8 in the 16-bit and the quad plans, never in the fp32 wide plan (every CU
+//     counts there), and in the fp32 narrow plan only where that costs at most 10 %;
+//   * the 16-bit plan is a function of shape and dtype alone: neither TN_NARROW nor NO_F16_TN changes it, so NO_F16_TN does
+//     not shrink the f16 workspace; the fp32 plan follows F32_EXACT, TN_NARROW and NO_TN_F32Q;
+//   * NO_WIDE_CHAIN sends an aligned wide-rank layer to the GEMM pair, a ragged one only NO_RAGGED does; the workspace holds the
+//     partial region either way.
+// Plan and launch.  Every kernel but the row-owner one takes ANY (ns, slab_len) with ns = ceil(T / slab_len): block -> (slab,
+// group) is computed from p.ns in the kernel, a slab writes [ncg * 64][64] floats at partial + slab * that, and a workgroup
+// that owns 2 or 4 groups skips those past ncg.  So the partials of every kernel fill exactly tn_partial_bytes(ns, D) <=
+// tn_partial_bytes(ns_cap, D), which is what plan_ws reserves; the quad kernel pads its GRID to a multiple of 8 slabs per
+// operand, and the surplus blocks (slab >= ns) leave before they touch memory.  tn_pick_slabs plans for tn_shape_kernel; a
+// launch that steps down (a misaligned pointer: generic; a slab length off 32: quad -> wide; TN_NARROW flipped since the
+// plan was made) keeps p.ns and p.slab_len and only changes how many groups a block owns, so it stays inside the same region.
+// The planned slab length is a multiple of 64 tokens (fp32: 32), which every tn_slab_mult divides.  The row-owner kernel needs
+// its own plan (slab counts per operand, up to TNR_MAX_SLABS): plan_ws sizes ns_cap for it from T >= 1024 on, and tn_rows_plan
+// refuses a group whose counts exceed a layer's ns_cap.
+bool tn_operand_ok(const void* M, const void* S, int64_t ldm, int D, int elems_per_16B) {
+  return D % elems_per_16B == 0 && ldm % elems_per_16B == 0 && al16p(M) && al16p(S);
+}
+bool tn_operand_ok(const TnJob& J, int elems_per_16B) { return tn_operand_ok(J.M, J.S, J.ldm, J.D, elems_per_16B) && J.ones_col_in_s; }
+
+TnKernel tn_shape_kernel(int64_t T, int d_in, int d_out, int dtype) {
+  if (dtype == SOW_BF16 || (dtype == SOW_F16 && !sw_on(SW_NO_F16_TN))) return sw_on(SW_TN_NARROW) ? TN_DMA : TN_DMA_WIDE;
+  if (dtype != SOW_F32) return TN_GENERIC;
+  if (sw_on(SW_F32_EXACT)) return TN_F32_EXACT;
+  if (sw_on(SW_TN_NARROW)) return TN_F32_X3;
+  const bool quad = !sw_on(SW_NO_TN_F32Q) && T >= 4096 && (d_in + 63) / 64 >= 3 && (d_out + 63) / 64 >= 3;
+  return quad ? TN_F32_QUAD : TN_F32_WIDE;
+}
+
+int tn_blocks(TnKernel k, const TnParams& p) {
+  const int gpb = tn_groups_per_block(k), ns = k == TN_F32_QUAD ? (p.ns + 7) / 8 * 8 : p.ns;
+  int blocks = 0;
+  for (int j = 0; j < p.njobs; ++j) blocks += (p.job[j].ncg + gpb - 1) / gpb * ns;
+  return blocks;
+}
+
+TnKernel pick_tn(const TnParams& p, int dtype) {
+  if (tn_blocks(TN_GENERIC, p) == 0) return TN_NONE;
+  TnKernel k = tn_shape_kernel(p.T, p.job[0].D, p.job[1].D, dtype);
+  if (k == TN_F32_QUAD && (p.njobs != 2 || p.slab_len % tn_slab_mult(k) || p.ns < 1)) k = TN_F32_WIDE;
+  bool dma = k != TN_GENERIC && p.slab_len % tn_slab_mult(k) == 0;
+  for (int j = 0; j < p.njobs; ++j) dma = dma && tn_operand_ok(p.job[j], dtype == SOW_F32 ? 4 : 8);
+  return dma ? k : TN_GENERIC;
+}
+
+// Slab count and length of a layer with r <= 64, planned for tn_shape_kernel (the 16-bit dtypes always for the wide kernel).
+// Two workgroups per CU are resident (64 KiB of LDS each), 512 in all; slabs stay >= 512 tokens so the partial traffic
+// (ns * D * 64 * 4 bytes) is a small fraction of the streamed operand.
+int tn_pick_slabs(int64_t T, int d_in, int d_out, int dtype, int* slab_len) {
+  const TnKernel k = dtype == SOW_F32 ? tn_shape_kernel(T, d_in, d_out, dtype) : TN_DMA_WIDE;
+  const int bt = dtype == SOW_F32 ? TnCfg<float>::BT : TnCfg<bf16_t>::BT, gpb = tn_groups_per_block(k);
+  int per_slab = ((d_in + 63) / 64 + gpb - 1) / gpb + ((d_out + 63) / 64 + gpb - 1) / gpb;   // blocks of one slab
+  if (per_slab < 1) per_slab = 1;
   int64_t max_ns = (T + 511) / 512;
   if (max_ns < 1) max_ns = 1;
-  if (dtype == SOW_F32 && (sw_on(SW_F32_EXACT) || sw_on(SW_TN_NARROW))) {
-    ns = 512 / total_colgroups;
+  int ns;
+  if (gpb == 1) {
+    // fp32 narrow (MFMA-bound): AT MOST 512 blocks -- a 13 % overshoot is a second, nearly empty round on a saturated matrix
+    // pipe (measured: 576 blocks 93 us vs 504 blocks 74 us)
+    ns = 512 / per_slab;
     if (ns > max_ns) ns = (int)max_ns;
     if (ns < 1) ns = 1;
     if (ns > 8 && (ns & ~7) * 10 >= ns * 9) ns &= ~7;
-  } else {   // bf16, and fp32 on the wide 3 x bf16 kernel
-    // the wide kernel owns two column groups per block and one 8-wave workgroup per CU: the largest multiple of 8
-    // that keeps the grid within ONE round of 256 (measured at d = 768, 12 double groups: 16 slabs / 192 blocks
-    // 22.2 us, 21 / 252 26.9 us, 24 / 288 30.5 us; llama_60m: 32 slabs for 512/512, 16 for the 1376-wide layers)
-    const int cg2 = total_colgroup_pairs > 0 ? total_colgroup_pairs : 1;
-    ns = (256 / cg2) & ~7;
-    if (ns < 8) ns = 256 / cg2;
-    // fp32 wide kernel: latency-bound on the bytes one CU keeps in flight (144 KiB of rings), so every CU counts:
-    // no rounding to a multiple of 8 (d = 768: 21 slabs / 252 blocks instead of 16 / 192)
-    if (dtype == SOW_F32) ns = 256 / cg2;
-    // fp32 quad kernel (skinny_tn_f32q.hip): four column groups per block, one 8-wave workgroup per CU, one round
-    // (slab counts are padded to a multiple of 8 per operand there -- same-slab ranges share an XCD -- so a multiple of 8 it is,
-    // where that still leaves at least 8 slabs: the padded grid must stay within the one round)
-    if (dtype == SOW_F32 && total_colgroup_quads > 0) {
-      ns = 256 / total_colgroup_quads;
-      if (ns >= 8) ns &= ~7;
-    }
+  } else {
+    // one 8-wave workgroup per CU and 2 or 4 column groups per block: the grid stays within ONE round of 256.
+    // 16-bit wide: the largest multiple of 8 that does (a multiple of 8 keeps the column groups of one slab on one XCD, S from
+    // that L2; measured at d = 768, 12 double groups: 16 slabs / 192 blocks 22.2 us, 21 / 252 26.9 us, 24 / 288 30.5 us;
+    // llama_60m: 32 slabs for 512/512, 16 for the 1376-wide layers).
+    // fp32 wide: latency-bound on the bytes one CU keeps in flight (144 KiB of rings), so every CU counts: no rounding
+    // (d = 768: 21 slabs / 252 blocks instead of 16 / 192).
+    // fp32 quad: its grid is padded to a multiple of 8 slabs per operand (same-slab ranges share an XCD), so a multiple of 8 it
+    // is, where that still leaves at least 8 slabs: the padded grid must stay within the one round.
+    ns = 256 / per_slab;
+    if (k != TN_F32_WIDE && ns >= 8) ns &= ~7;
     if (ns > max_ns) ns = (int)max_ns;
     if (ns < 1) ns = 1;
   }
@@ -1317,26 +1377,21 @@ int tn_pick_slabs(int64_t T, int total_colgroups, int total_colgroup_pairs, int 
 
 size_t tn_partial_bytes(int ns, int D) { return (size_t)ns * ((D + 63) / 64 * 64) * 64 * sizeof(float); }
 
-static bool tn_wide_ok(const TnParams& p) {
-  bool dma = p.slab_len % 16 == 0;
-  for (int j = 0; j < p.njobs; ++j) {
-    const TnJob& J = p.job[j];
-    dma = dma && J.D % 8 == 0 && J.ldm % 8 == 0 && (reinterpret_cast<uintptr_t>(J.M) & 15) == 0 &&
-          (reinterpret_cast<uintptr_t>(J.S) & 15) == 0 && J.ones_col_in_s;
-  }
-  return dma;
+// One launch: the dynamic-LDS limit (once per device and kernel), the launch, its error.  K is a kernel symbol; the 16-bit
+// form takes the f16 instantiation and the bf16 symbol, which for the wide and the row-owner kernel is the plain
+// (non-template) one: a function-pointer parameter picks it over the template of the same name.
+template <typename Arg, void (*K)(const Arg)>
+static int launch_tn_kernel(int64_t grid, int threads, int lds, hipStream_t stream, const Arg& arg) {
+  if (lds) SOW_SET_MAX_LDS_ONCE(lds, K);
+  hipLaunchKernelGGL(K, dim3((unsigned)grid), dim3(threads), lds, stream, arg);
+  SOW_CHECK_LAUNCH();
+  return SOW_OK;
 }
-static int tn_wide_blocks(const TnParams& p) {
-  int blocks2 = 0;   // two 64-column groups per block
-  for (int j = 0; j < p.njobs; ++j) blocks2 += (p.job[j].ncg + 1) / 2 * p.ns;
-  return blocks2;
-}
-
-// the 16-bit dtypes whose weight gradients run on the LDS-DMA kernels (NO_F16_TN: f16 on the generic kernel, as before them)
-bool tn_dma_dtype(int dtype) { return dtype == SOW_BF16 || (dtype == SOW_F16 && !sw_on(SW_NO_F16_TN)); }
-
-bool tn_group_supported(const TnParams& p, int dtype) {
-  return tn_dma_dtype(dtype) && tn_wide_ok(p) && !sw_on(SW_TN_NARROW) && tn_wide_blocks(p) > 0;
+template <typename Arg, void (*F16)(const Arg), void (*BF16)(const Arg)>
+static int launch_tn16(int dtype, int64_t grid, int threads, int lds, hipStream_t stream, const Arg& arg) {
+  if (dtype == SOW_F16) return launch_tn_kernel<Arg, F16>(grid, threads, lds, stream, arg);
+  if (dtype == SOW_BF16) return launch_tn_kernel<Arg, BF16>(grid, threads, lds, stream, arg);
+  return SOW_ERR_DTYPE;
 }
 
 int launch_tn_group(const TnParams* ps, int n, int dtype, hipStream_t stream) {
@@ -1349,27 +1404,18 @@ int launch_tn_group(const TnParams* ps, int n, int dtype, hipStream_t stream) {
   for (int i = 0; i < n; ++i) {
     g.p[i] = ps[i];
     g.start[i] = (int)total;
-    total += tn_wide_blocks(ps[i]);
+    total += tn_blocks(TN_DMA_WIDE, ps[i]);
   }
   for (int i = n; i <= TN_MAXG; ++i) g.start[i] = (int)total;
   if (total <= 0) return SOW_OK;
   if (total > 0x7fffffff) return SOW_ERR_SHAPE;
   constexpr int LDS = TNW_WAVES * TNW_DEPTH * TNW_STAGE_BYTES;  // 144 KiB (rings; reused by the cross-wave sum)
   const int64_t grid = (sw_on(SW_NO_PERSIST) || total < 256) ? total : 256;   // one resident workgroup per CU
-  if (dtype == SOW_F16) {
-    SOW_SET_MAX_LDS_ONCE(LDS, tn_partial_dma_wide_kernel<f16_t>);
-    hipLaunchKernelGGL(tn_partial_dma_wide_kernel<f16_t>, dim3((unsigned)grid), dim3(64 * TNW_WAVES), LDS, stream, g);
-  } else {
-    void (*const bf16_kernel)(const TnGroup) = tn_partial_dma_wide_kernel;   // the plain (non-template) symbol
-    SOW_SET_MAX_LDS_ONCE(LDS, bf16_kernel);
-    hipLaunchKernelGGL(bf16_kernel, dim3((unsigned)grid), dim3(64 * TNW_WAVES), LDS, stream, g);
-  }
-  SOW_CHECK_LAUNCH();
-  return SOW_OK;
+  return launch_tn16<TnGroup, tn_partial_dma_wide_kernel<f16_t>, tn_partial_dma_wide_kernel>(dtype, grid, 64 * TNW_WAVES, LDS, stream, g);
 }
 
 bool tn_rows_plan(const int64_t* T, const int* D, const int* cap, int n, int* ns_out, int* slab_len_out) {
-  if (n <= 0 || n > TNR_MAXI || sw_on(SW_NO_TN_ROWS) || sw_on(SW_TN_NARROW) || sw_on(SW_NO_GROUPED)) return false;
+  if (n <= 0 || n > TNR_MAXI || sw_on(SW_NO_TN_ROWS) || sw_on(SW_NO_GROUPED)) return false;   // (TN_NARROW: the caller, tn_shape_kernel)
   double work = 0.0;
   for (int i = 0; i < n; ++i) {
     if (T[i] <= 0 || D[i] <= 0 || D[i] % 8) return false;
@@ -1402,9 +1448,7 @@ int launch_tn_rows(TnRowsItem* items, int n, int dtype, hipStream_t stream) {
   int total = 0;
   for (int i = 0; i < n; ++i) {
     TnRowsItem& it = items[i];
-    if ((reinterpret_cast<uintptr_t>(it.M) & 15) || (reinterpret_cast<uintptr_t>(it.S) & 15) || it.ldm % 8 || it.D % 8 ||
-        it.slab_len % 32 || it.ns < 1)
-      return SOW_ERR_ALIGN;
+    if (!tn_operand_ok(it.M, it.S, it.ldm, it.D, 8) || it.slab_len % tn_slab_mult(TN_ROWS) || it.ns < 1) return SOW_ERR_ALIGN;
     it.ncg = (it.D + 63) / 64;
     it.nr = (it.ncg + 15) / 16;
     it.gpr = (it.ncg + it.nr - 1) / it.nr;
@@ -1417,75 +1461,34 @@ int launch_tn_rows(TnRowsItem* items, int n, int dtype, hipStream_t stream) {
   // M (x, dY) is streamed once: non-temporal loads keep it out of the Infinity Cache, where dh, the slab partials and the next
   // kernels' operands live (the launch itself 135 -> 138 us, the step 3.82 -> 3.78 ms; TN_NO_NT_LOAD switch)
   g.nt_load = sw_on(SW_TN_NO_NT_LOAD) ? 0 : 1;
-  const dim3 grid((unsigned)(total < 256 ? total : 256));
-  if (dtype == SOW_F16) {
-    SOW_SET_MAX_LDS_ONCE(TNR_LDS, tn_partial_rows_kernel<f16_t>);
-    hipLaunchKernelGGL(tn_partial_rows_kernel<f16_t>, grid, dim3(64 * TNR_WAVES), TNR_LDS, stream, g);
-  } else {
-    void (*const bf16_kernel)(const TnRowsGroup) = tn_partial_rows_kernel;   // the plain (non-template) symbol
-    SOW_SET_MAX_LDS_ONCE(TNR_LDS, bf16_kernel);
-    hipLaunchKernelGGL(bf16_kernel, grid, dim3(64 * TNR_WAVES), TNR_LDS, stream, g);
-  }
-  SOW_CHECK_LAUNCH();
-  return SOW_OK;
+  return launch_tn16<TnRowsGroup, tn_partial_rows_kernel<f16_t>, tn_partial_rows_kernel>(dtype, total < 256 ? total : 256, 64 * TNR_WAVES,
+                                                                                          TNR_LDS, stream, g);
 }
 
-int launch_tn(const TnParams& p, int dtype, hipStream_t stream) {
-  int blocks = 0;
-  for (int j = 0; j < p.njobs; ++j) blocks += p.job[j].ncg * p.ns;
-  if (blocks == 0) return SOW_OK;
-  if (dtype == SOW_BF16 || dtype == SOW_F16) {
-    // one ladder for both 16-bit dtypes: wide DMA, narrow DMA under TN_NARROW, the generic kernel for ragged widths,
-    // misaligned views and slab lengths off 16 (and for every f16 shape under NO_F16_TN)
-    const bool f16 = dtype == SOW_F16;
-    const bool dma = tn_dma_dtype(dtype) && tn_wide_ok(p);
-    if (dma && !sw_on(SW_TN_NARROW)) {
-      return launch_tn_group(&p, 1, dtype, stream);
-    } else if (dma) {
-      constexpr int LDS = 4 * TN_DEPTH * TN_STAGE_BYTES;  // 64 KiB (rings; reused by the cross-wave sum)
-      if (f16) {
-        SOW_SET_MAX_LDS_ONCE(LDS, tn_partial_dma_kernel<f16_t>);
-        hipLaunchKernelGGL(tn_partial_dma_kernel<f16_t>, dim3(blocks), dim3(256), LDS, stream, p);
-      } else {
-        SOW_SET_MAX_LDS_ONCE(LDS, tn_partial_dma_kernel<bf16_t>);
-        hipLaunchKernelGGL(tn_partial_dma_kernel<bf16_t>, dim3(blocks), dim3(256), LDS, stream, p);
-      }
-    } else if (f16) {
-      hipLaunchKernelGGL(tn_partial_kernel<f16_t>, dim3(blocks), dim3(256), 0, stream, p);
-    } else {
-      hipLaunchKernelGGL(tn_partial_kernel<bf16_t>, dim3(blocks), dim3(256), 0, stream, p);
-    }
-  } else if (dtype == SOW_F32) {
-    bool dma = p.slab_len % 8 == 0;
-    for (int j = 0; j < p.njobs; ++j) {
-      const TnJob& J = p.job[j];
-      dma = dma && J.D % 4 == 0 && J.ldm % 4 == 0 && (reinterpret_cast<uintptr_t>(J.M) & 15) == 0 &&
-            (reinterpret_cast<uintptr_t>(J.S) & 15) == 0 && J.ones_col_in_s;
-    }
-    if (dma && tn_f32q_ok(p)) return launch_tn_f32q(p, stream);
-    if (dma && !sw_on(SW_F32_EXACT) && !sw_on(SW_TN_NARROW)) {
-      constexpr int LDSW = TNFW_WAVES * TNFW_DEPTH * TNFW_STAGE_BYTES;  // 144 KiB
-      int blocks2 = 0;   // two 64-column groups per block
-      for (int j = 0; j < p.njobs; ++j) blocks2 += (p.job[j].ncg + 1) / 2 * p.ns;
-      SOW_SET_MAX_LDS_ONCE(LDSW, tn_partial_dma_f32_wide_kernel);
-      hipLaunchKernelGGL(tn_partial_dma_f32_wide_kernel, dim3(blocks2), dim3(64 * TNFW_WAVES), LDSW, stream, p);
-    } else if (dma) {
-      constexpr int LDS = 4 * TNF_DEPTH * TNF_STAGE_BYTES;  // 64 KiB
-      if (sw_on(SW_F32_EXACT)) {
-        SOW_SET_MAX_LDS_ONCE(LDS, tn_partial_dma_f32_kernel<false>);
-        hipLaunchKernelGGL(tn_partial_dma_f32_kernel<false>, dim3(blocks), dim3(256), LDS, stream, p);
-      } else {
-        SOW_SET_MAX_LDS_ONCE(LDS, tn_partial_dma_f32_kernel<true>);
-        hipLaunchKernelGGL(tn_partial_dma_f32_kernel<true>, dim3(blocks), dim3(256), LDS, stream, p);
-      }
-    } else {
-      hipLaunchKernelGGL(tn_partial_kernel<float>, dim3(blocks), dim3(256), 0, stream, p);
-    }
-  } else
-    return SOW_ERR_DTYPE;
-  SOW_CHECK_LAUNCH();
-  return SOW_OK;
+// launches kernel k (pick_tn's answer for p) and nothing else.  The row-owner kernel has its own operand list
+// (launch_tn_rows), the wide-rank arms are launched by api.hip.
+int launch_picked_tn(TnKernel k, const TnParams& p, int dtype, hipStream_t stream) {
+  const int blocks = tn_blocks(k, p);
+  switch (k) {
+    case TN_NONE: return SOW_OK;
+    case TN_DMA_WIDE: return launch_tn_group(&p, 1, dtype, stream);
+    case TN_DMA:
+      return launch_tn16<TnParams, tn_partial_dma_kernel<f16_t>, tn_partial_dma_kernel<bf16_t>>(dtype, blocks, 256, 4 * TN_DEPTH * TN_STAGE_BYTES,
+                                                                                                 stream, p);   // 64 KiB of rings
+    case TN_GENERIC:
+      if (dtype != SOW_F32) return launch_tn16<TnParams, tn_partial_kernel<f16_t>, tn_partial_kernel<bf16_t>>(dtype, blocks, 256, 0, stream, p);
+      break;
+    case TN_F32_QUAD: return launch_tn_f32q(p, stream);
+    case TN_F32_WIDE:   // 144 KiB
+      return launch_tn_kernel<TnParams, tn_partial_dma_f32_wide_kernel>(blocks, 64 * TNFW_WAVES, TNFW_WAVES * TNFW_DEPTH * TNFW_STAGE_BYTES, stream, p);
+    case TN_F32_EXACT: return launch_tn_kernel<TnParams, tn_partial_dma_f32_kernel<false>>(blocks, 256, 4 * TNF_DEPTH * TNF_STAGE_BYTES, stream, p);
+    case TN_F32_X3: return launch_tn_kernel<TnParams, tn_partial_dma_f32_kernel<true>>(blocks, 256, 4 * TNF_DEPTH * TNF_STAGE_BYTES, stream, p);
+    default: return SOW_ERR_UNSUPPORTED;
+  }
+  return launch_tn_kernel<TnParams, tn_partial_kernel<float>>(blocks, 256, 0, stream, p);   // TN_GENERIC in fp32
 }
+
+int launch_tn(const TnParams& p, int dtype, hipStream_t stream) { return launch_picked_tn(pick_tn(p, dtype), p, dtype, stream); }
 
 int launch_tn_reduce_batch(const ReduceParams* descs, const int* starts, int n, int total_blocks, int dtype, hipStream_t stream) {
   if (n <= 0 || total_blocks <= 0) return SOW_OK;

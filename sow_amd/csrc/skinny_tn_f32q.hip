@@ -16,7 +16,7 @@
 //     (90 instead of 144 split instructions per wave and stage);
 //   * accumulators as in the wide kernel (lane li owns columns 2 li, 2 li + 1 of both operands' images); the two token halves
 //     are summed through LDS at the end of the slab, in a fixed order (deterministic).
-// Taken for fp32 inputs with T >= 4096 and at least 3 column groups per operand (tn_f32q_shape_ok); tn_pick_slabs then plans
+// Taken for fp32 inputs with T >= 4096 and at least 3 column groups per operand (tn_shape_kernel, skinny_tn.hip); tn_pick_slabs then plans
 // the slab count for one resident round of these workgroups.
 #include "kernels.hpp"
 #include "lds_dma.hpp"
@@ -317,26 +317,9 @@ __global__ __launch_bounds__(64 * TNQ_WAVES, 2) void tn_partial_f32_quad_kernel(
   }
 }
 
-// shapes the quad kernel is planned for (tn_pick_slabs) -- alignment is checked at launch
-bool tn_f32q_shape_ok(int64_t T, int d_in, int d_out) {
-  if (sw_on(SW_F32_EXACT) || sw_on(SW_TN_NARROW) || sw_on(SW_NO_TN_F32Q)) return false;
-  return T >= 4096 && (d_in + 63) / 64 >= 3 && (d_out + 63) / 64 >= 3;
-}
-
-bool tn_f32q_ok(const TnParams& p) {
-  if (p.njobs != 2 || p.slab_len % 32 || p.ns < 1) return false;
-  if (!tn_f32q_shape_ok(p.T, p.job[0].D, p.job[1].D)) return false;
-  for (int j = 0; j < p.njobs; ++j) {
-    const TnJob& J = p.job[j];
-    if (J.D % 4 || J.ldm % 4 || (reinterpret_cast<uintptr_t>(J.M) & 15) || (reinterpret_cast<uintptr_t>(J.S) & 15) || !J.ones_col_in_s)
-      return false;
-  }
-  return true;
-}
-
+// which shapes and operands take this kernel: tn_shape_kernel / pick_tn (skinny_tn.hip)
 int launch_tn_f32q(const TnParams& p, hipStream_t stream) {
-  int blocks = 0;
-  for (int j = 0; j < p.njobs; ++j) blocks += (p.job[j].ncg + 3) / 4 * ((p.ns + 7) / 8 * 8);
+  const int blocks = tn_blocks(TN_F32_QUAD, p);
   if (blocks <= 0) return SOW_OK;
   SOW_SET_MAX_LDS_ONCE(TNQ_LDS, tn_partial_f32_quad_kernel);
   hipLaunchKernelGGL(tn_partial_f32_quad_kernel, dim3(blocks), dim3(64 * TNQ_WAVES), TNQ_LDS, stream, p);

@@ -198,7 +198,9 @@ size_t tnw_partial_bytes(int64_t T, int d_in, int d_out, int r) {
          ((ns * dp1 * 4 + 255) & ~(size_t)255);
 }
 
-static bool al4w(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; }
+bool tnw_operands_ok(const void* x, const void* dh, const void* dy, const void* h, bool rag) {
+  return (rag || (al4p(x) && al4p(dy))) && al4p(h) && al4p(dh);
+}
 
 int launch_tn_wide(const void* x, const void* dh, const void* dy, const void* h, void* dA, void* dB, void* dbias, int64_t T,
                    int d_in, int d_out, int r, float scale, float beta, int dtype, int out_dtype, void* ws, size_t ws_bytes,
@@ -207,7 +209,7 @@ int launch_tn_wide(const void* x, const void* dh, const void* dy, const void* h,
   const bool rag = d_in % 8 != 0 || d_out % 8 != 0;
   if (!(rag ? ragged_shape_ok(r, d_in, d_out, dtype) && r > 64 : tnw_shape_ok(r, d_in, d_out, dtype))) return SOW_ERR_UNSUPPORTED;
   if (out_dtype != dtype && out_dtype != SOW_F32) return SOW_ERR_DTYPE;
-  if ((!rag && (!al4w(x) || !al4w(dy))) || !al4w(h) || !al4w(dh) || !ws || (reinterpret_cast<uintptr_t>(ws) & 255) ||
+  if (!tnw_operands_ok(x, dh, dy, h, rag) || !ws || (reinterpret_cast<uintptr_t>(ws) & 255) ||
       ws_bytes < tnw_partial_bytes(T, d_in, d_out, r))
     return SOW_ERR_UNSUPPORTED;
   if (T <= 0) return SOW_ERR_SHAPE;

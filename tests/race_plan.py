@@ -30,7 +30,7 @@ The rings (the kernels that order LDS by hand: every file that includes lds_dma.
   gemm4.hip:43-44         two K-tile buffers of four half-tiles (G4_LDS = 2 * G4_BUF), K-tiles of 64 k (+ the extension tile);
                           gemm4h's projection pass: three buffers (gemm4_body.hpp:151, tl % 3), one trip per K-tile
 The token-slab rings of the weight-gradient kernels turn once per 16 (8, 32) tokens of a slab; the slab length is the C
-plan's (tn_pick_slabs, skinny_tn.hip:1274, mirrored below), never longer than about T / 16 + 64 at these widths, so they wrap
+plan's (tn_pick_slabs, mirrored below), never longer than about T / 16 + 64 at these widths, so they wrap
 3 x only in the cases with many tokens or few slabs; the per-case rows say where.
 
 Every other kernel keeps ONE LDS image per workgroup between __syncthreads() (compiler-visible LDS accesses, which hipcc
@@ -45,11 +45,11 @@ More than one block per workgroup.  A persistent grid carries LDS state from one
   chain2.hip:879    launch_chain2_group: grid = min(blocks, C2_RESIDENT = 512) unless NO_PERSIST; blocks = ceil(T / 64) per
                     layer; workgroup g runs blocks g, g + 512, ... (chain2.hip:753)
   chain2_shared.hip:615   the same with CS_RESIDENT = 512 over ceil(T / 64) blocks
-  skinny_tn.hip:1358      launch_tn_group: grid = min(blocks, 256); blocks = sum over the layers of a grouped launch of
+  skinny_tn.hip           launch_tn_group: grid = min(blocks, 256); blocks = sum over the layers of a grouped launch of
                     (pairs of 64-column groups) x slabs.  One layer never exceeds 256 (tn_pick_slabs keeps it in one round), a
                     group of three 776-wide layers does.
 The other grids are one workgroup per tile or slab: the GEMM kernels use gridDim only for the XCD remap (there is no resident
-tile loop), tn_partial_rows_kernel's plan (tn_rows_plan, skinny_tn.hip:1393) admits 160 .. 256 blocks against a grid of 256.
+tile loop), tn_partial_rows_kernel's plan (tn_rows_plan, skinny_tn.hip) admits 160 .. 256 blocks against a grid of 256.
 T past 2 * 512 * 64 tokens is what the chain2 case costs; at the ring-wrap widths (776 x 776) its buffers (360 MB) and its
 float64 reference (8e10 multiply-adds) would break both caps below, so the chain2 case takes the widest shape the caps leave
 (712 x 72: the forward X ring wraps, 14 chunks against 6 slots), the shared one 72 -> 72 + 136, and the ring-wrap cases the
@@ -236,7 +236,7 @@ def _layers():
     out.append(_add(GP._layer("chain2f", lay, ("chain2f_kernel", "tn_partial_dma_f32_wide_kernel")),
                     _chain_rows("chain2f.hip", "C3_DEPTH", "C3_NSLOT", W, W)))
     # the wide fp32 weight-gradient kernel past 4096 tokens: an operand with fewer than 3 column groups keeps the layer off the
-    # quad kernel (tn_f32q_shape_ok); 32 slabs of 576 tokens: 72 stages of 8 tokens over 6 waves
+    # quad kernel (tn_shape_kernel); 32 slabs of 576 tokens: 72 stages of 8 tokens over 6 waves
     lay = L("", "f32", 276 * 64 + 1, W, 128, 16, s=0.5)
     out.append(_add(GP._layer("tnf32w", lay, ("chain3f_kernel", "tn_partial_dma_f32_wide_kernel")), (_tn_row(lay, "TNFW_DEPTH", 8, 6),)))
     lay = L("", "f32", 1000, W, W, 16, s=0.5, switches={"TN_NARROW": 1})
