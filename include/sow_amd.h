@@ -465,6 +465,27 @@ size_t sow_short_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int
 int sow_forward_short(const sow_layer_args* layers, int n, int dtype, void* stream);
 int sow_backward_short(const sow_layer_args* layers, int n, int dtype, void* stream);
 
+/* The same on a quantised accumulator READ IN PLACE: acc_down = the codes, acc_up = the scales (as in sow_forward_skinny), no image
+ * and no arena traffic.  The contract is the one above with acc_down := W^, the matrix sow_acc_dequantize / sow_acc_dequantize_fp4
+ * write for the same codes and scales:
+ *   forward   y  = rn(x W^ + h B + bias)          data   dX = rn(dY W^T + dh A^T)
+ * with h, dh, h_save, the workspace layout, the order of every sum and the invariants as above.  The data phase dequantises in
+ * registers to the exact bits of W^ and keeps the geometry of sow_backward_short: dX and dh are bit-identical to sow_backward_short on the
+ * image.  The weight phases are an unchanged sow_backward_ex(..., SOW_BWD_WEIGHTS ...) on the same workspace, called with acc_kind =
+ * SOW_ACC_DENSE (they read no accumulator); the workspace is sized for that plan.
+ * Admitted: acc_kind SOW_ACC_DENSE_FP8 or SOW_ACC_DENSE_FP4 only, all layers of a call of ONE kind; SOW_DTYPE_BF16 / SOW_DTYPE_F16
+ * without flags; 1 <= T <= SOW_SHORT_ROWS_MAX, r_live <= 64, n <= 16; E4M3: d_in and d_out multiples of 8, 16-byte-aligned codes, 8-byte-aligned
+ * exponents (the data phase loads eight at once); MXFP4: d_in a multiple of 32, d_out of 8, 8-byte-aligned codes and scales; the other operands
+ * aligned as above.  SOW_ACC_DENSE, SOW_ACC_NONE, SOW_ACC_LOWRANK, mixed code kinds, more than 16 layers, SOW_PARAM_F32 and everything while NO_SKINNY is
+ * on return SOW_ERR_UNSUPPORTED; the other codes are those of sow_forward_short; all decided on the host for every layer before a launch
+ * or a dereference.  The queries are pure functions of the shape (no switch moves them) and 0 outside the admitted set;
+ * sow_short_codes_workspace_bytes = the plan of sow_workspace_bytes(..., SOW_ACC_DENSE, ...) with the larger direction's slab partials
+ * appended, sow_forward_short_codes_workspace_bytes = the forward's partials alone. */
+size_t sow_forward_short_codes_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype);
+size_t sow_short_codes_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype);
+int sow_forward_short_codes(const sow_layer_args* layers, int n, int dtype, void* stream);
+int sow_backward_short_codes(const sow_layer_args* layers, int n, int dtype, void* stream);
+
 /* General row-major GEMM  C[M,N] = alpha * op(A) op(B) + beta * C + bias[N]  (bias may be NULL).
  * trans_a: A is stored [K,M]; trans_b: B is stored [N,K].  Replaces the plain `@` / einsum call
  * sites: accumulate() sow.py:131-140 (W_acc += scale * A @ B, Q @ R), prepare.py:135, tt.py:213-237. */

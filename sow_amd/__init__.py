@@ -13,6 +13,7 @@ from .group import group_siblings, ungroup_siblings  # noqa: F401
 from .acc_quant import dequantize_accumulators, quantize_accumulators  # noqa: F401
 from .ops import set_skinny_rows, skinny_rows  # noqa: F401
 from .ops import set_short_rows, short_rows  # noqa: F401
+from .ops import set_short_codes, short_codes  # noqa: F401
 from .utils import qr_weight, svd_weight, pad_matrix, unpad_matrix, closest_factorization  # noqa: F401
 
 __version__ = "0.1.0"

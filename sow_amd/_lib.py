@@ -110,6 +110,10 @@ SIGNATURES = {
     "sow_short_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int, c_int, c_int]),
     "sow_forward_short": (c_int, [POINTER(LayerArgs), c_int, c_int, c_void_p]),
     "sow_backward_short": (c_int, [POINTER(LayerArgs), c_int, c_int, c_void_p]),
+    "sow_forward_short_codes_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int, c_int, c_int]),
+    "sow_short_codes_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int, c_int, c_int]),
+    "sow_forward_short_codes": (c_int, [POINTER(LayerArgs), c_int, c_int, c_void_p]),
+    "sow_backward_short_codes": (c_int, [POINTER(LayerArgs), c_int, c_int, c_void_p]),
     "sow_backward_group_reduce_desc": (c_int, [POINTER(LayerArgs), c_int, c_int, c_int, c_void_p, POINTER(c_int)]),
     "sow_backward_group_plan": (c_int, [POINTER(LayerArgs), c_int, c_int, c_int, POINTER(c_int)]),
     "sow_accumulate_batch": (c_int, [POINTER(AccumulateArgs), c_int, c_int, c_void_p]),

@@ -61,6 +61,70 @@ def skinny_fp4_rows_pays(T: int, d_in: int, d_out: int) -> bool:
     return SKINNY_MAX_T < T <= SKINNY_ROWS_MAX
 
 
+# (d_in, d_out) -> the most rows at which the pair on the codes won: the tables of the two docstrings below
+SHORT_CODES_TABLE: dict = {"fp8_e4m3": {(3072, 768): 128, (4096, 4096): 128, (4096, 11008): 128, (11008, 4096): 128},
+                           "mxfp4": {(3072, 768): 128, (4096, 4096): 128, (4096, 11008): 128, (11008, 4096): 128, (512, 512): 512,
+                                     (512, 1376): 512}}
+
+
+def _short_codes_pays(name: str, T: int, d_in: int, d_out: int) -> bool:
+    return 64 < T <= SHORT_CODES_TABLE[name].get((d_in, d_out), 0)
+
+
+def short_fp8_pays(T: int, d_in: int, d_out: int) -> bool:
+    """The measured dispatch rule for an E4M3 accumulator in calls WITH gradients inside sow_amd.short_rows + sow_amd.short_codes
+    (profiles/short_codes.txt), the one place that encodes it: the (rows, shape) classes at which forward +
+    data gradient on the codes read in place (n: sow_forward_short_codes / sow_backward_short_codes) beat what such a layer runs
+    without the opt-in (a: the image pass ahead of the forward and again ahead of the data gradient, and on the image the short pair
+    where short_rows_pays admits the row, else sow_forward / the data phase of sow_backward_ex) by more than the larger run-to-run
+    spread of the two, at r = 8 AND r = 50.  One line per measured shape, the most rows up to which n won at every measured row count
+    (65, 128, 256, 512, 1024) from 65 on; 0 = never (bf16, MI355X):
+
+        768->768: T <= 0
+        768->3072: T <= 0
+        3072->768: T <= 128
+        4096->4096: T <= 128
+        4096->11008: T <= 128
+        11008->4096: T <= 128
+        512->512: T <= 0
+        512->1376: T <= 0
+
+    Measured (us, a against n, +- the larger spread; r = 50 at T = 65 / 128 / 256): 3072->768 66.2 / 76.2 / 113.1 against 58.1 / 70.4 /
+    116.2 (+- 3.1 / 1.8 / 1.1), 4096->4096 128.8 / 168.0 / 227.3 against 112.8 / 154.2 / 270.4 (+- 0.8 / 1.7 / 1.4), 4096->11008 237.5 /
+    306.7 / 302.1 against 206.0 / 273.9 / 512.8 (+- 0.8 / 2.8 / 2.5), 11008->4096 262.7 / 352.2 / 379.1 against 235.4 / 324.4 / 610.6
+    (+- 0.7 / 1.8 / 1.5): a / n is 1.08 ... 1.17 where n wins -- the two image passes, 5 ... 19 us each -- and falls to 0.11 at 1024 rows,
+    where n reads the codes once per 64-row block and a has left the short pair.  On the 768- and 512-wide shapes n's median is below
+    a's at every row count up to 256 (a / n 1.00 ... 1.20) but the gap is inside the spread of a row at one rank or the other (up to
+    20.8 us at 768->768, T = 65), so the rule excludes them; 3072->768 loses at 256 rows and r = 50 (116.2 against 113.1).
+    The rule EXCLUDES: every row count above a shape's line, every shape that was not measured, calls of at most 64 rows.  NOT
+    measured: f16, a full finetune step."""
+    return _short_codes_pays("fp8_e4m3", T, d_in, d_out)
+
+
+def short_fp4_pays(T: int, d_in: int, d_out: int) -> bool:
+    """The same rule for an MXFP4 accumulator (profiles/short_codes.txt; a, n and the criterion as in
+    short_fp8_pays).  One line per measured shape:
+
+        768->768: T <= 0
+        768->3072: T <= 0
+        3072->768: T <= 128
+        4096->4096: T <= 128
+        4096->11008: T <= 128
+        11008->4096: T <= 128
+        512->512: T <= 512
+        512->1376: T <= 512
+
+    Measured (us, a against n, +- the larger spread; r = 50 at T = 65 / 128 / 256): 3072->768 65.0 / 75.3 / 111.9 against 56.0 / 68.2 /
+    113.2 (+- 0.5 / 1.3 / 1.2), 4096->4096 125.4 / 165.3 / 226.5 against 106.4 / 146.7 / 258.1 (+- 0.9 / 0.4 / 1.0), 4096->11008 232.2 /
+    297.2 / 297.5 against 189.4 / 253.4 / 474.0 (+- 1.1 / 1.9 / 11.3), 11008->4096 260.0 / 344.3 / 378.6 against 220.7 / 307.9 / 578.8
+    (+- 3.8 / 3.3 / 2.4); 512->512 at T = 65 / 128 / 256 / 512 / 1024: 42.6 / 42.8 / 50.2 / 73.3 / 74.1 against 40.0 / 40.2 / 47.6 / 61.5 /
+    104.9 (+- 0.5 / 0.7 / 0.5 / 0.7 / 1.0); 512->1376: 44.7 / 47.1 / 59.6 / 84.9 / 84.8 against 41.1 / 42.8 / 55.2 / 78.6 / 141.6.  a / n is
+    1.06 ... 1.23 where n wins and 0.11 at 1024 rows of 11008->4096.  On the 768-wide shapes a row's spread (up to 24.6 us at T = 65)
+    hides the gap at one rank or the other: excluded.  The rule EXCLUDES what short_fp8_pays excludes.  NOT measured: f16, a full
+    finetune step."""
+    return _short_codes_pays("mxfp4", T, d_in, d_out)
+
+
 class AccFormat(NamedTuple):
     name: str                       # the fmt= argument of quantize_accumulators
     label: str                      # the name used in messages
@@ -79,6 +143,9 @@ class AccFormat(NamedTuple):
     frexp: Tuple[float, int]        # code_max = threshold * 2^offset with threshold in [0.5, 1)
     pays: Callable[[int, int, int], bool]      # the measured rule that admits the streaming path
     pays_rows: Callable[[int, int, int], bool]     # ... at 33 ... 64 rows (sow_forward_skinny_rows inside sow_amd.skinny_rows)
+    # ... of calls WITH gradients at 65 ... 1024 rows on the codes read in place (sow_forward_short_codes / sow_backward_short_codes
+    # inside sow_amd.short_rows + sow_amd.short_codes).  Last and with a default: a record built without it routes nothing there
+    pays_short: Callable[[int, int, int], bool] = lambda T, d_in, d_out: False
 
     def code_shape(self, d_in, d_out): return (d_in // self.rows_per_code, d_out)      # (of a [d_in, d_out] matrix, as scale_shape)
     def scale_shape(self, d_in, d_out): return (d_out,) if self.block is None else (d_in // self.block, d_out)
@@ -101,12 +168,12 @@ FORMATS = {f.name: f for f in (
     AccFormat(name="fp8_e4m3", label="E4M3", kind=_lib.ACC_DENSE_FP8, code_dtype=torch.float8_e4m3fn, scale_dtype=torch.int8,
               rows_per_code=1, block=None, d_in_multiple=8, d_out_multiple=8, workspace_query="sow_forward_skinny_fp8_workspace_bytes",
               dequantize="sow_acc_dequantize", exp_range={torch.bfloat16: (-117, 119), torch.float16: (-15, 7)}, scale_bias=0,
-              code_max=448.0, frexp=(0.875, 9), pays=skinny_fp8_pays, pays_rows=skinny_fp8_rows_pays),
+              code_max=448.0, frexp=(0.875, 9), pays=skinny_fp8_pays, pays_rows=skinny_fp8_rows_pays, pays_short=short_fp8_pays),
     # W^[k, n] = e2m1(nibble k % 2 of codes[k / 2, n]) * 2^(scales[k / 32, n] - 127): E8M0 scale bytes
     AccFormat(name="mxfp4", label="MXFP4", kind=_lib.ACC_DENSE_FP4, code_dtype=torch.uint8, scale_dtype=torch.uint8,
               rows_per_code=2, block=32, d_in_multiple=32, d_out_multiple=8, workspace_query="sow_forward_skinny_fp4_workspace_bytes",
               dequantize="sow_acc_dequantize_fp4", exp_range={torch.bfloat16: (-125, 125), torch.float16: (-13, 13)}, scale_bias=127,
-              code_max=6.0, frexp=(0.75, 3), pays=skinny_fp4_pays, pays_rows=skinny_fp4_rows_pays),
+              code_max=6.0, frexp=(0.75, 3), pays=skinny_fp4_pays, pays_rows=skinny_fp4_rows_pays, pays_short=short_fp4_pays),
 )}
 BY_CODE_DTYPE = {f.code_dtype: f for f in FORMATS.values()}
 BY_KIND = {f.kind: f for f in FORMATS.values()}

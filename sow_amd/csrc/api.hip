@@ -223,7 +223,7 @@ static int gemm_auto(const void* A, int64_t lda, const void* B, int64_t ldb, boo
 
 extern "C" {
 
-int sow_version(void) { return 124; }
+int sow_version(void) { return 125; }
 
 int sow_set_switch(const char* name, int value) {
   if (!name) return SOW_ERR_NULL;
@@ -1337,6 +1337,90 @@ static int short_impl(const sow_layer_args* layers, int n, int dtype, void* stre
 }
 int sow_forward_short(const sow_layer_args* layers, int n, int dtype, void* stream) { return short_impl(layers, n, dtype, stream, false); }
 int sow_backward_short(const sow_layer_args* layers, int n, int dtype, void* stream) { return short_impl(layers, n, dtype, stream, true); }
+
+// ---- the same on E4M3 / MXFP4 codes read in place (acc_down = the codes, acc_up = the scales; no image, no arena) ----------------
+// Entry points and queries of their own: the four above keep refusing the code kinds and answering 0 for them.  The admitted set:
+// SOW_ACC_DENSE_FP8 / _FP4 only, one kind per call, bf16 / f16 without flags, 1 <= T <= SOW_SHORT_ROWS_MAX, r_live <= 64, the widths
+// of the format (E4M3 8 / 8, MXFP4 d_in % 32 and d_out % 8).
+static bool short_codes_shape_ok(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype) {
+  return acc_is_codes(acc_kind) && short_shape_ok(T, d_in, d_out, r_live, SOW_ACC_DENSE, dtype) && (acc_kind != SOW_ACC_DENSE_FP4 || d_in % 32 == 0);
+}
+// the forward's partials take the plan of the 128-column code forms; the data gradient keeps the plain geometry (short_ws)
+static ShortWs short_codes_fwd_ws(int64_t T, int d_in, int d_out) {
+  ShortWs w;
+  short_codes_plan(T, d_in, d_out, &w.S, &w.KS, &w.ncr);
+  w.off_ph = al256(skinny_py_bytes(T, d_out, w.S));
+  w.bytes = w.off_ph + al256(skinny_ph_bytes(T, w.S));
+  return w;
+}
+size_t sow_forward_short_codes_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype) {
+  const Dtype f = decode_dtype(dtype);
+  if (!short_dtype_ok(f) || !short_codes_shape_ok(T, d_in, d_out, r_live, acc_kind, f.cd)) return 0;
+  return 256 + short_codes_fwd_ws(T, d_in, d_out).bytes;
+}
+// the plan of sow_workspace_bytes(..., SOW_ACC_DENSE, ...) -- the kind the weight phases are called with -- then the larger direction's partials
+size_t sow_short_codes_workspace_bytes(int64_t T, int d_in, int d_out, int r_live, int acc_kind, int dtype) {
+  const Dtype f = decode_dtype(dtype);
+  if (!short_dtype_ok(f) || !short_codes_shape_ok(T, d_in, d_out, r_live, acc_kind, f.cd)) return 0;
+  const size_t fw = short_codes_fwd_ws(T, d_in, d_out).bytes, bw = short_ws(T, d_out, d_in, true).bytes;
+  return plan_ws(T, d_in, d_out, r_live, 0, SOW_ACC_DENSE, f.cd).total + (fw > bw ? fw : bw) + 256;
+}
+
+// The checks and refusal codes of short_impl, every layer before the first launch or dereference.
+static int short_codes_impl(const sow_layer_args* layers, int n, int dtype, void* stream, bool bwd) {
+  const Dtype f = decode_dtype(dtype);
+  const int cd = f.cd;
+  if (!f.layer_ok() || cd == SOW_F32) return SOW_ERR_DTYPE;
+  if (f.param_f32 || f.native_bit || sw_on(SW_NO_SKINNY)) return SOW_ERR_UNSUPPORTED;
+  if (n < 0) return SOW_ERR_SHAPE;
+  if (n == 0) return SOW_OK;
+  if (!layers) return SOW_ERR_NULL;
+  if (n > SK_MAXL) return SOW_ERR_UNSUPPORTED;
+  const int kind = layers[0].acc_kind;   // one kind per call: the kernels are instantiated per kind
+  for (int i = 0; i < n; ++i) {
+    if (!acc_kind_known(layers[i].acc_kind)) return SOW_ERR_SHAPE;
+    if (!acc_is_codes(layers[i].acc_kind) || layers[i].acc_kind != kind) return SOW_ERR_UNSUPPORTED;
+  }
+  const bool fp4 = kind == SOW_ACC_DENSE_FP4;
+  std::vector<SkLayer> e;
+  for (int i = 0; i < n; ++i) {
+    const sow_layer_args& L = layers[i];
+    if (L.T < 0 || L.d_in <= 0 || L.d_out <= 0 || L.r_live <= 0) return SOW_ERR_SHAPE;
+    if (L.T == 0) continue;
+    if (!short_codes_shape_ok(L.T, L.d_in, L.d_out, L.r_live, kind, cd)) return SOW_ERR_UNSUPPORTED;
+    if (!L.A || !L.B || !L.acc_down || !L.acc_up || (bwd ? (!L.dy || !L.dx) : (!L.x || !L.y))) return SOW_ERR_NULL;
+    if (!al16p(L.A) || !al16p(L.B) || (!fp4 && !al16p(L.acc_down))) return SOW_ERR_UNSUPPORTED;
+    // codes and scales are read in 8-byte pieces: MXFP4 as in sow_forward_skinny; the data gradient reads the E4M3 exponents so too
+    if (((fp4 ? reinterpret_cast<uintptr_t>(L.acc_down) : 0) | reinterpret_cast<uintptr_t>(L.acc_up)) & 7) return SOW_ERR_UNSUPPORTED;
+    if (bwd ? (!al16p(L.dy) || !al16p(L.dx)) : (!al16p(L.x) || !al16p(L.y) || !al16p(L.bias) || !al16p(L.h_save))) return SOW_ERR_UNSUPPORTED;
+    const size_t need = bwd ? sow_short_codes_workspace_bytes(L.T, L.d_in, L.d_out, L.r_live, kind, cd)
+                            : sow_forward_short_codes_workspace_bytes(L.T, L.d_in, L.d_out, L.r_live, kind, cd);
+    if (!L.workspace || L.workspace_bytes < need) return SOW_ERR_WORKSPACE;
+    char* ws = ws_base(L.workspace);
+    const int K = bwd ? L.d_out : L.d_in, N = bwd ? L.d_in : L.d_out;
+    const ShortWs w = bwd ? short_ws(L.T, K, N, true) : short_codes_fwd_ws(L.T, K, N);
+    // dh where the weight phases (called with SOW_ACC_DENSE) read it, the partials behind the plan they use
+    const WsPlan p = plan_ws(L.T, L.d_in, L.d_out, L.r_live, 0, SOW_ACC_DENSE, cd);
+    char* part = bwd ? ws + p.total : ws;
+    char* hout = bwd ? ws + p.off_dh : (char*)L.h_save;
+    const size_t es = esize(cd);
+    for (int64_t t0 = 0; t0 < L.T; t0 += 64) {
+      SkLayer E{};
+      E.x = (const char*)(bwd ? L.dy : L.x) + (size_t)t0 * K * es;
+      E.y = (char*)(bwd ? L.dx : L.y) + (size_t)t0 * N * es;
+      E.W = L.acc_down, E.wexp = (const int8_t*)L.acc_up;
+      E.A = bwd ? L.B : L.A, E.B = bwd ? L.A : L.B, E.bias = bwd ? nullptr : L.bias;
+      E.Py = (float*)part + (size_t)w.S * t0 * N, E.Ph = (float*)(part + w.off_ph) + (size_t)w.S * t0 * 64;
+      E.T = (int)(L.T - t0 < 64 ? L.T - t0 : 64), E.d_in = K, E.d_out = N, E.r = L.r_live, E.scale = L.scale;
+      E.S = w.S, E.KS = w.KS, E.ncr = w.ncr;
+      E.hout = hout ? hout + (size_t)t0 * 64 * es : nullptr;
+      e.push_back(E);
+    }
+  }
+  return launch_skinny_short(e.data(), (int)e.size(), cd, bwd, (hipStream_t)stream, kind);
+}
+int sow_forward_short_codes(const sow_layer_args* layers, int n, int dtype, void* stream) { return short_codes_impl(layers, n, dtype, stream, false); }
+int sow_backward_short_codes(const sow_layer_args* layers, int n, int dtype, void* stream) { return short_codes_impl(layers, n, dtype, stream, true); }
 
 static int backward_group_impl(const sow_layer_args* layers, int n, int dtype, int gdt, int phases, int perm, hipStream_t stream) {
   const Phases ph = decode_phases(phases);

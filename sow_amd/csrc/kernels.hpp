@@ -283,10 +283,8 @@ struct SkLayer {
   int T, d_in, d_out, r;
   int S, KS, ncr, startA, startB;     // filled in by launch_skinny_fwd (skinny_plan)
   float scale;
-  union {                             // (one pointer either way: the existing forms see the struct they saw)
-    const int8_t* wexp;               // the scales of codes in W (E4M3: int8 column exponents [d_out]; MXFP4: E8M0 bytes [d_in / 32][d_out]), or nullptr
-    void* hout;                       // short-row forms (plain accumulator only): where phase B stores h / dh, [T][64], or nullptr
-  };
+  const int8_t* wexp;                 // the scales of codes in W (E4M3: int8 column exponents [d_out]; MXFP4: E8M0 bytes [d_in / 32][d_out]), or nullptr
+  void* hout;                         // short-row forms: where phase B stores h / dh, [T][64], or nullptr (a slot of its own: the code forms need both)
 };
 // K-slabs, slab length and phase-A column ranges of a layer: a pure function of the shape
 void skinny_plan(int d_in, int d_out, int acc_kind, int* S, int* KS, int* ncr);
@@ -309,7 +307,13 @@ void short_rows_plan(int64_t T, int K, int N, int kq, int* S, int* KS, int* ncr)
 // / dh of the block or nullptr; launched 16 at a time, one launch pair each.  bwd: the entries carry the data gradient's
 // operands in the forward's fields -- x = dY, W = W_acc (read transposed in place), A = B [r][d_out], B = A [d_in][r], y = dX,
 // d_in = the layer's d_out (contraction), d_out = the layer's d_in (output), no bias
-int launch_skinny_short(const SkLayer* entries, int n, int dtype, bool bwd, hipStream_t stream);
+// acc_kind: SOW_ACC_DENSE, or the code kind of ALL entries (sow_forward_short_codes / sow_backward_short_codes: W = the codes, wexp = the
+// scales).  On codes the forward's phase A is the RT = 4 code form (128-column ranges: short_codes_plan), the data gradient keeps
+// the plain geometry (short_rows_plan) and dequantises W in registers
+int launch_skinny_short(const SkLayer* entries, int n, int dtype, bool bwd, hipStream_t stream, int acc_kind = SOW_ACC_DENSE);
+// the forward's slab plan on codes, next to short_rows_plan: the row blocks counted with 128-column ranges, slabs of whole MX
+// blocks and whole rounds (SK_SHORT_KQ_FWD), at most 512.  A pure function of its arguments.
+void short_codes_plan(int64_t T, int K, int N, int* S, int* KS, int* ncr);
 // gemm.hip
 int launch_gemm(const void* A, int64_t lda, bool transA, const void* B, int64_t ldb, bool transB, void* C, int64_t ldc,
                 const void* bias, int64_t M, int N, int K, float alpha, float beta, int dtype, hipStream_t stream);

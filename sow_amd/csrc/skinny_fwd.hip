@@ -63,6 +63,12 @@
 // (short_rows_plan).  The forward is the RT = 4 plain phase A as it is and the SK_SH_FWD form of phase B, which also stores the
 // h rows it has rounded (h_save).  The data gradient is the TR = true form of phase A (skinny_a_tr: dY staged as x, W_acc read
 // transposed in place) and the SK_SH_BWD form of phase B (skinny_b_tr: dh to memory, dX = rn(sum Py + dh . A^T)).
+//
+// The same on codes read in place (sow_forward_short_codes / sow_backward_short_codes, SOW_ACC_DENSE_FP8 / _FP4): the
+// forward is the RT = 4 code form of phase A per row block (128-column ranges, short_codes_plan) and SK_SH_FWD of phase B, with the
+// E4M3 column scaling where the format asks for it.  The data gradient keeps the plain geometry and dequantises W in registers to the
+// exact bits of the image (skinny_a_tr_codes: the scale varies along the contraction there), so phase B is the plain SK_SH_BWD and dX,
+// dh are bit-identical to sow_backward_short on the image.
 #include <type_traits>
 
 #include "kernels.hpp"
@@ -189,15 +195,16 @@ constexpr int SK_TR_KC = 2 * SK_KSTEP;   // k per wave and round
 constexpr int SK_TR_KQ = 4 * SK_TR_KC;   // k per round of the four waves (SK_SHORT_KQ_BWD)
 constexpr int SK_TR_PF = 2;              // rounds a wave keeps in flight: all of a slab of at most 512
 static_assert(SK_TR_KQ == SK_SHORT_KQ_BWD, "the data gradient's slabs are whole rounds");
-template <typename T> __device__ __forceinline__ void skinny_a_tr(const SkGroup& g, char* sk_smem) {
-  constexpr int RT = 4, NCT = 4, CN = 64, RS = sk_rs(false);
+// PONLY: the dY . B^T workgroups alone, as the code forms call them (one tile: the W tiles' registers are not held)
+template <typename T, bool PONLY = false> __device__ __forceinline__ void skinny_a_tr(const SkGroup& g, char* sk_smem) {
+  constexpr int RT = 4, NCT = PONLY ? 1 : 4, CN = 64, RS = sk_rs(false);
   int li = 0;
   for (int i = 1; i < g.n; ++i)
     if ((int)blockIdx.x >= g.L[i].startA) li = i;
   const SkLayer& L = g.L[li];
   const int b = (int)blockIdx.x - L.startA;
   const int ntj = (L.r + 15) >> 4;            // 16-column tiles of dY . B^T
-  const bool is_p = b < L.S * ntj;            // the first S * ntj workgroups: (slab, tile) of dY . B^T
+  const bool is_p = PONLY || b < L.S * ntj;   // the first S * ntj workgroups: (slab, tile) of dY . B^T
   const int s = is_p ? b / ntj : (b - L.S * ntj) / L.ncr;
   const int cr = is_p ? b % ntj : (b - L.S * ntj) % L.ncr;
   const int Tn = L.T, K = L.d_in, N = L.d_out, KS = L.KS, r = L.r;
@@ -322,13 +329,217 @@ template <typename T> __device__ __forceinline__ void skinny_a_tr(const SkGroup&
   }
 }
 
+// ---- the same on codes (sow_backward_short_codes): the W workgroups of the TR = true instantiations with F = SK_FP8 / SK_FP4 ----
+// The geometry above is kept -- contraction = the layer's d_out, 64-column ranges of its d_in, the k-to-wave partition with each wave's k
+// pair, the park, the wave-order reduction -- and a fragment is dequantised in registers to the exact bits of the image W^ (the scale
+// varies along the contraction here: it cannot wait for phase B).  The sums therefore see the operands sow_backward_short sees on
+// the image, in the same order: dX and dh are bit-identical to it.  The dY . B^T workgroups are the plain ones (skinny_a_tr<T, true>).
+//   E4M3   a lane's fragment = codes[n][k .. k + 7], one 8-byte non-temporal load per tile; the eight exponents exps[k .. k + 7], one
+//          8-byte load per k-step for the four tiles (cached: every workgroup of the slab reads them).  v_cvt_pk_f32_fp8, v_ldexp_f32
+//          (never a multiply: fused into a conversion it loses the sign of -0) and the pack of the forward, which rounds nothing.
+//   MXFP4  a byte of codes[n / 2][k] = rows n and n + 1 of column k: one 8-byte load gives eight contraction elements of TWO output
+//          columns, their scale bytes are scales[n / 32][k .. k + 7].  The scaled conversion of byte k with ITS scale yields (row n,
+//          row n + 1) of that k; four v_perm_b32 per parity gather the low halves (row n) and the high halves (row n + 1) into two
+//          fragments.  A wave's four tiles are the even and odd rows of two groups of 16 code rows (32 rows of d_in each, one MX
+//          block): tile 2 g + parity, tile column n16 = local column 32 g + 2 n16 + parity, undone where the sum is stored.
+// A row past N is not requested (N is a multiple of 32 for MXFP4: a group is whole or absent).
+#ifndef SOW_SHORT_CODES_NQ
+#define SOW_SHORT_CODES_NQ 2
+#endif
+template <typename T, SkFmt F> __device__ __forceinline__ void skinny_a_tr_codes(const SkGroup& g, char* sk_smem) {
+  static_assert(F == SK_FP8 || F == SK_FP4, "a code format");
+  constexpr bool FP4 = F == SK_FP4;
+  constexpr int RT = 4, NCT = 4, CN = 64, RS = sk_rs(false);
+  constexpr int NLD = FP4 ? 2 : 4;   // code loads per k-step: groups of 16 code rows, or tiles
+  constexpr int NSC = FP4 ? 2 : 1;   // scale loads per k-step: one per group (its MX block), or the step's column exponents
+  // k-steps a wave takes per round: 2 = the plain form's pairs (64-byte pieces of a code row, its summation partition: the bit
+  // identity); 4 = the A/B of DESIGN 4.5f (128-byte pieces, one round in flight, another partition of the sum)
+  constexpr int NQ = SOW_SHORT_CODES_NQ, KC = NQ * SK_KSTEP, KQ = 4 * KC, PF = NQ == 2 ? SK_TR_PF : 1;
+  static_assert(NQ == 2 || NQ == 4, "pairs or fours");
+  typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
+  int li = 0;
+  for (int i = 1; i < g.n; ++i)
+    if ((int)blockIdx.x >= g.L[i].startA) li = i;
+  const SkLayer& L = g.L[li];
+  const int b = (int)blockIdx.x - L.startA - L.S * ((L.r + 15) >> 4);   // (>= 0: the caller took the dY . B^T workgroups)
+  const int s = b / L.ncr, cr = b % L.ncr;
+  const int Tn = L.T, K = L.d_in, N = L.d_out, KS = L.KS;
+  const int rows = Tn > 48 ? 64 : 48;
+  const bool live3 = rows == 64;
+  const int kbeg = s * KS;
+  const int klen = min(KS, K - kbeg);
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, n16 = lane & 15, kg = lane >> 4;
+  const int kk0 = w * KC;
+
+  // ---- requests first ----
+  const char* cp[NLD];   // the lane's row of codes (K bytes per row, per row pair of MXFP4)
+  const char* sp[NSC];
+  bool ok[NLD];
+#pragma unroll
+  for (int u = 0; u < NLD; ++u) {
+    if constexpr (FP4) {
+      const int n0 = cr * CN + u * 32;   // the group's first row of d_in
+      ok[u] = n0 < N;
+      const int nc0 = min(n0, N - 32);
+      cp[u] = (const char*)L.W + (size_t)((nc0 >> 1) + n16) * K;
+      sp[u] = (const char*)L.wexp + (size_t)(nc0 >> 5) * K;
+    } else {
+      const int n = cr * CN + u * 16 + n16;
+      ok[u] = n < N;
+      cp[u] = (const char*)L.W + (size_t)min(n, N - 1) * K;
+    }
+  }
+  if constexpr (!FP4) sp[0] = (const char*)L.wexp;
+  u32x2 d[PF][NQ][NLD + NSC];
+  auto load_round = [&](int kk, u32x2(&o)[NQ][NLD + NSC]) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int kq = kk + q * SK_KSTEP, k = kbeg + kq + kg * 8;   // K is a multiple of 8: a lane's eight are all in or all out
+      const bool in = kq < klen && k < K;
+#pragma unroll
+      for (int u = 0; u < NLD; ++u) {
+        u32x2 v = {0u, 0u};
+        if (ok[u] && in) v = sk_load_w((const u32x2*)(cp[u] + k));
+        o[q][u] = v;
+      }
+#pragma unroll
+      for (int u = 0; u < NSC; ++u) {
+        u32x2 v = {0u, 0u};
+        if (in) v = *(const u32x2*)(sp[u] + k);
+        o[q][NLD + u] = v;
+      }
+    }
+  };
+#pragma unroll
+  for (int p = 0; p < PF; ++p) load_round(kk0 + p * KQ, d[p]);
+
+  // ---- the slab of dY: [rows][KS + pad], zeros for t >= T and k >= K ----
+  const int xpitch = (KS + SK_XPAD) * 2;   // bytes
+  {
+    const T* x = (const T*)L.x;
+    const int cpr = KS / 8;
+    for (int idx = tid; idx < rows * cpr; idx += 256) {
+      const int t = idx / cpr, c = idx - t * cpr, k = kbeg + c * 8;
+      u32x4 v = {0u, 0u, 0u, 0u};
+      if (t < Tn && k < K) v = *(const u32x4*)(x + (size_t)t * K + k);
+      *(u32x4*)(sk_smem + t * xpitch + c * 16) = v;
+    }
+  }
+  __syncthreads();
+
+  f32x4 acc[NCT][RT];
+#pragma unroll
+  for (int c = 0; c < NCT; ++c)
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) acc[c][rt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const char* xa0 = sk_smem + n16 * xpitch + kg * 16;
+  for (int kb = kk0; kb < klen; kb += PF * KQ) {
+#pragma unroll
+    for (int p = 0; p < PF; ++p) {
+      const int kk = kb + p * KQ;
+      if (kk < klen) {   // uniform per wave
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+          const int kq = kk + q * SK_KSTEP;
+          u32x4 a[RT];
+#pragma unroll
+          for (int rt = 0; rt < RT; ++rt) {
+            a[rt] = u32x4{0u, 0u, 0u, 0u};
+            if (rt < 3 || live3) a[rt] = *(const u32x4*)(xa0 + rt * 16 * xpitch + kq * 2);
+          }
+          auto mma = [&](int c, const u32x4& f) {
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt) acc[c][rt] = sk_mfma<T>(a[rt], f, acc[c][rt]);
+          };
+          if constexpr (FP4) {
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+              const u32x2 qv = d[p][q][u], sv = d[p][q][NLD + u];
+              uint32_t pr[8];   // k element j: row n in the low half, row n + 1 in the high half
+#pragma unroll
+              for (int j = 0; j < 8; ++j) {
+                const float sc = __uint_as_float(((sv[j >> 2] >> (8 * (j & 3))) & 0xffu) << 23);   // E8M0 byte -> 2^e
+                pr[j] = cvt_fp4_pair<T>(qv[j >> 2], sc, j & 3);
+              }
+              u32x4 fe, fo;
+#pragma unroll
+              for (int m = 0; m < 4; ++m) {
+                fe[m] = __builtin_amdgcn_perm(pr[2 * m + 1], pr[2 * m], 0x05040100u);
+                fo[m] = __builtin_amdgcn_perm(pr[2 * m + 1], pr[2 * m], 0x07060302u);
+              }
+              mma(2 * u, fe);
+              mma(2 * u + 1, fo);
+            }
+          } else {
+            const u32x2 ev = d[p][q][NLD];
+            int e[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) e[j] = (int)(int8_t)(ev[j >> 2] >> (8 * (j & 3)));
+#pragma unroll
+            for (int c = 0; c < NCT; ++c) {
+              const u32x2 qv = d[p][q][c];
+              u32x4 f;
+#pragma unroll
+              for (int wd = 0; wd < 2; ++wd) {
+                const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8(qv[wd], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(qv[wd], true);
+                f[2 * wd] = sk_pack_exact<T>(__builtin_ldexpf(lo[0], e[4 * wd]), __builtin_ldexpf(lo[1], e[4 * wd + 1]));
+                f[2 * wd + 1] = sk_pack_exact<T>(__builtin_ldexpf(hi[0], e[4 * wd + 2]), __builtin_ldexpf(hi[1], e[4 * wd + 3]));
+              }
+              mma(c, f);
+            }
+          }
+        }
+        load_round(kk + PF * KQ, d[p]);   // (requests nothing past the slab)
+      }
+    }
+  }
+
+  // ---- park the four waves' tiles in two passes of 32 rows, add them in wave order, store the slab partial ----
+  __syncthreads();
+  float* red = (float*)sk_smem;
+#pragma unroll
+  for (int ps = 0; ps < 2; ++ps) {
+    if (ps) __syncthreads();
+#pragma unroll
+    for (int c = 0; c < NCT; ++c)
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf)
+        if (2 * ps + hf < 3 || live3) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) red[(w * 32 + hf * 16 + kg * 4 + q) * RS + c * 16 + n16] = acc[c][2 * ps + hf][q];
+        }
+    __syncthreads();
+    const int t0 = 32 * ps, tn = min(Tn - t0, 32);
+    float* Py = L.Py + ((size_t)s * Tn + t0) * N;
+    for (int idx = tid; idx < tn * CN; idx += 256) {
+      const int t = idx / CN, jc = idx - t * CN;
+      const int n = cr * CN + jc;
+      // MXFP4: local column jc = 32 g + 2 n16 + parity sits in tile 2 g + parity, tile column n16
+      const int slot = FP4 ? (((jc >> 5) * 2 + (jc & 1)) * 16 + ((jc & 31) >> 1)) : jc;
+      float v = red[t * RS + slot];
+#pragma unroll
+      for (int ww = 1; ww < 4; ++ww) v += red[(ww * 32 + t) * RS + slot];
+      if (n < N) Py[(size_t)t * N + n] = v;
+    }
+  }
+}
+
 // RT = the 16-row tiles of x a wave holds: 2 (T <= 32, one or two live) or 4 (33 <= T <= 64, three or four live)
-// TR: the data gradient of short batches (skinny_a_tr above; plain format, RT = 4 only)
-template <typename T, SkFmt F = SK_PLAIN, bool PF = false, int RT = 2, bool TR = false> __global__ __launch_bounds__(256, SK_OCC[F][RT / 4]) void skinny_a_kernel(const SkGroup g) {
+// TR: the data gradient of short batches (skinny_a_tr / skinny_a_tr_codes above; RT = 4 only, every format: two waves per SIMD as the plain form)
+template <typename T, SkFmt F = SK_PLAIN, bool PF = false, int RT = 2, bool TR = false> __global__ __launch_bounds__(256, SK_OCC[TR ? SK_PLAIN : F][RT / 4]) void skinny_a_kernel(const SkGroup g) {
   extern __shared__ __align__(16) char sk_smem[];
-  static_assert(!TR || (F == SK_PLAIN && !PF && RT == 4), "the transposed form exists for the plain format with four row tiles");
+  static_assert(!TR || (!PF && RT == 4), "the transposed form exists with four row tiles and factors of T");
   if constexpr (TR) {   // (what follows is dead code in these instantiations)
-    skinny_a_tr<T>(g, sk_smem);
+    if constexpr (F == SK_PLAIN) {
+      skinny_a_tr<T>(g, sk_smem);
+    } else {
+      int li = 0;
+      for (int i = 1; i < g.n; ++i)
+        if ((int)blockIdx.x >= g.L[i].startA) li = i;
+      const SkLayer& L = g.L[li];
+      if ((int)blockIdx.x - L.startA < L.S * ((L.r + 15) >> 4)) skinny_a_tr<T, true>(g, sk_smem);   // dY . B^T: the plain workgroups
+      else skinny_a_tr_codes<T, F>(g, sk_smem);
+    }
     return;
   }
   constexpr bool FP8 = F == SK_FP8, FP4 = F == SK_FP4;
@@ -597,10 +808,10 @@ template <typename T> __device__ __forceinline__ void skinny_b_tr(const SkGroup&
   ((T*)L.y)[(size_t)t * N + n] = from_f32<T>(acc);
 }
 
-// SH: the short-batch forms (plain format, factors of T): SK_SH_FWD also stores the h rows it has just rounded, from the workgroups
+// SH: the short-batch forms (factors of T; SK_SH_FWD with either column scaling, SK_SH_BWD plain: the data gradient dequantises in phase A): SK_SH_FWD also stores the h rows it has just rounded, from the workgroups
 // of the first column block, in the h_save layout; SK_SH_BWD is the data gradient above
 template <typename T, bool FP8 = false, bool PF = false, int SH = SK_SH_NONE> __global__ __launch_bounds__(256) void skinny_b_kernel(const SkGroup g) {
-  static_assert(SH == SK_SH_NONE || (!FP8 && !PF), "the short-batch forms read a plain accumulator and factors of T");
+  static_assert(SH == SK_SH_NONE || (!PF && (SH == SK_SH_FWD || !FP8)), "the short-batch forms read factors of T; the data gradient's sums are scaled already");
   if constexpr (SH == SK_SH_BWD) {   // (what follows is dead code in these instantiations)
     skinny_b_tr<T>(g);
     return;
@@ -774,34 +985,60 @@ void short_rows_plan(int64_t T, int K, int N, int kq, int* S, int* KS, int* ncr)
   *KS = ks, *S = ceil_div(K, ks), *ncr = nc;
 }
 
-template <typename T, bool BWD> static int sk_launch_short(const SkGroup& g, int na, int nb, size_t lds, hipStream_t stream) {
-  // (the forward's phase A is the RT = 4 plain form of sow_forward_skinny_rows itself: the same limit as sk_launch sets for it)
+// ... of the forward on codes (sow_forward_short_codes): the RT = 4 code forms of phase A have 128-column ranges and run one workgroup per
+// CU, so the count is SOW_SKINNY_SHORT_WANT8 workgroups over blocks x 128-column ranges x slabs.  Slabs are whole rounds of
+// the four waves (128: whole MX blocks too) and at most 512, the 64-row x slab of those forms.
+#ifndef SOW_SKINNY_SHORT_WANT8
+#define SOW_SKINNY_SHORT_WANT8 256
+#endif
+void short_codes_plan(int64_t T, int K, int N, int* S, int* KS, int* ncr) {
+  const int nblk = (int)ceil_div(T, (int64_t)SK_ROWS_MAX), nc = ceil_div(N, sk_cn(true));
+  const int want = ceil_div(SOW_SKINNY_SHORT_WANT8, nc * (nblk > 0 ? nblk : 1));
+  int ks = ceil_div(ceil_div(K, want), SK_SHORT_KQ_FWD) * SK_SHORT_KQ_FWD;
+  if (ks < SK_SHORT_KQ_FWD) ks = SK_SHORT_KQ_FWD;
+  if (ks > SK_KS_MAX64) ks = SK_KS_MAX64;
+  *KS = ks, *S = ceil_div(K, ks), *ncr = nc;
+}
+
+// F: the format W is stored in.  Forward: phase A is the RT = 4 form of F as sow_forward_skinny_rows launches it, phase B SK_SH_FWD with
+// the E4M3 column scaling where F asks for it.  Data gradient: the TR form of F, and the plain SK_SH_BWD (the sums are scaled)
+template <typename T, SkFmt F, bool BWD> static int sk_launch_short(const SkGroup& g, int na, int nb, size_t lds, hipStream_t stream) {
+  // (the forward's phase A is the RT = 4 form of sow_forward_skinny_rows itself: the same limit as sk_launch sets for it)
   constexpr int LDS_MAX = 48 * (SK_KS_MAX48 + SK_XPAD) * 2;
-  static_assert(64 * (SK_KS_MAX64 + SK_XPAD) * 2 <= LDS_MAX && 4 * 32 * sk_rs(false) * 4 <= LDS_MAX && 2 * LDS_MAX <= 160 * 1024, "two workgroups per CU");
+  constexpr int LDS_PARK = 4 * 32 * sk_rs(F != SK_PLAIN && !BWD) * 4;
+  static_assert(64 * (SK_KS_MAX64 + SK_XPAD) * 2 <= LDS_MAX && LDS_PARK <= LDS_MAX && 2 * LDS_MAX <= 160 * 1024, "two workgroups per CU");
   if (lds > (size_t)LDS_MAX) return SOW_ERR_UNSUPPORTED;
-  SOW_SET_MAX_LDS_ONCE(LDS_MAX, skinny_a_kernel<T, SK_PLAIN, false, 4, BWD>);
-  hipLaunchKernelGGL((skinny_a_kernel<T, SK_PLAIN, false, 4, BWD>), dim3(na), dim3(256), lds, stream, g);
+  SOW_SET_MAX_LDS_ONCE(LDS_MAX, skinny_a_kernel<T, F, false, 4, BWD>);
+  hipLaunchKernelGGL((skinny_a_kernel<T, F, false, 4, BWD>), dim3(na), dim3(256), lds, stream, g);
   SOW_CHECK_LAUNCH();
-  hipLaunchKernelGGL((skinny_b_kernel<T, false, false, BWD ? SK_SH_BWD : SK_SH_FWD>), dim3(nb), dim3(256), 0, stream, g);
+  hipLaunchKernelGGL((skinny_b_kernel<T, F == SK_FP8 && !BWD, false, BWD ? SK_SH_BWD : SK_SH_FWD>), dim3(nb), dim3(256), 0, stream, g);
   SOW_CHECK_LAUNCH();
   return SOW_OK;
 }
+// by [dtype is f16][SkFmt][bwd]
+#define SK_SHORT_ROW(T, F) {sk_launch_short<T, F, false>, sk_launch_short<T, F, true>}
+#define SK_SHORT_ROWS(T) {SK_SHORT_ROW(T, SK_PLAIN), SK_SHORT_ROW(T, SK_FP8), SK_SHORT_ROW(T, SK_FP4)}
+static constexpr SkLaunch SK_LAUNCH_SHORT[2][3][2] = {SK_SHORT_ROWS(bf16_t), SK_SHORT_ROWS(f16_t)};
 
-int launch_skinny_short(const SkLayer* entries, int n, int dtype, bool bwd, hipStream_t stream) {
+int launch_skinny_short(const SkLayer* entries, int n, int dtype, bool bwd, hipStream_t stream, int acc_kind) {
   if (n <= 0) return SOW_OK;
-  if (dtype != SOW_BF16 && dtype != SOW_F16) return SOW_ERR_UNSUPPORTED;
+  if ((dtype != SOW_BF16 && dtype != SOW_F16) || (acc_kind != SOW_ACC_DENSE && !acc_is_codes(acc_kind))) return SOW_ERR_UNSUPPORTED;
+  const bool codes = acc_is_codes(acc_kind);
+  const bool wide = codes && !bwd;   // 128-column ranges: the forward on codes alone
   const int kq = bwd ? SK_SHORT_KQ_BWD : SK_SHORT_KQ_FWD;
   for (int i = 0; i < n; ++i) {
     const SkLayer& E = entries[i];
     if (E.T < 1 || E.T > SK_ROWS_MAX || !E.W || !E.Py || !E.Ph || E.r < 1 || E.r > 64 || E.KS < kq || E.KS > SK_KS_MAX64 || E.KS % kq ||
-        E.S != ceil_div(E.d_in, E.KS) || E.ncr != ceil_div(E.d_out, sk_cn(false)))
+        E.S != ceil_div(E.d_in, E.KS) || E.ncr != ceil_div(E.d_out, sk_cn(wide)) || codes != (E.wexp != nullptr))
       return SOW_ERR_UNSUPPORTED;
+    // MXFP4 blocks are whole along the layer's d_in: the forward's contraction, the data gradient's output
+    if (acc_kind == SOW_ACC_DENSE_FP4 && (bwd ? E.d_out : E.d_in) % 32) return SOW_ERR_UNSUPPORTED;
   }
   for (int i0 = 0; i0 < n; i0 += SK_MAXL) {
     SkGroup g;
     g.n = n - i0 < SK_MAXL ? n - i0 : SK_MAXL;
     int na = 0, nb = 0;
-    size_t lds = (size_t)4 * 32 * sk_rs(false) * sizeof(float);
+    size_t lds = (size_t)4 * 32 * sk_rs(wide) * sizeof(float);
     for (int i = 0; i < g.n; ++i) {
       SkLayer& L = g.L[i];
       L = entries[i0 + i];
@@ -811,8 +1048,7 @@ int launch_skinny_short(const SkLayer* entries, int n, int dtype, bool bwd, hipS
       const size_t xb = (size_t)(L.T > 48 ? 64 : 48) * (L.KS + SK_XPAD) * 2;
       lds = xb > lds ? xb : lds;
     }
-    const int rc = dtype == SOW_F16 ? (bwd ? sk_launch_short<f16_t, true>(g, na, nb, lds, stream) : sk_launch_short<f16_t, false>(g, na, nb, lds, stream))
-                                    : (bwd ? sk_launch_short<bf16_t, true>(g, na, nb, lds, stream) : sk_launch_short<bf16_t, false>(g, na, nb, lds, stream));
+    const int rc = SK_LAUNCH_SHORT[dtype == SOW_F16][sk_fmt(acc_kind)][bwd](g, na, nb, lds, stream);
     if (rc) return rc;
   }
   return SOW_OK;

@@ -61,12 +61,25 @@ class _SoWGroupFunction(torch.autograd.Function):
             x2 = autocast_input(x2, cdt)     # an fp32 input is cast once for the whole group
         per = [tensors[5 * i:5 * i + 5] for i in range(n)]
         need_bwd = any(ctx.needs_input_grad)
+        # inside sow_amd.short_rows and sow_amd.short_codes: every sibling quantised in ONE format and admitted by its pays_short
+        # rule -> one sow_forward_short_codes call on the codes read in place, no image and no arena
+        ctx.short = ctx.codes = False
+        if not mixed and sinks is None and n <= ops.SKINNY_MAX_LAYERS and len({getattr(t[2], "dtype", None) for t in per}) == 1 and all(
+                ops.short_codes_admits(x2, A, B, acc_down, acc_up, bias) for A, B, acc_down, acc_up, bias in per):
+            res = ops.sow_forward_short_codes([(x2, A, B, (acc_down, acc_up), bias, s) for (A, B, acc_down, acc_up, bias), s in zip(per, scales)],
+                                              save_h=need_bwd)
+            if res is not None:
+                ys, hs = res
+                ctx.codes, ctx.shared = True, shared
+                if need_bwd:
+                    ctx.save_for_backward(x2, *hs, *tensors)
+                ctx.scales, ctx.n, ctx.x_shape, ctx.x_dtype, ctx.mixed = scales, n, x.shape, x.dtype, mixed
+                return tuple(y.reshape(*lead, y.shape[1]) for y in ys)
         # E4M3 accumulators (codes, exponents): the siblings' images side by side in the scratch arena; the codes are what is
         # saved, backward builds the images again
         accs = ops.acc_operands([(t[2], t[3]) for t in per], x2.dtype)
         # inside sow_amd.short_rows: every sibling admitted (dense accumulators or images, the measured rule) -> one
         # sow_forward_short call for the set; sinks and autocast keep the grouped path
-        ctx.short = False
         if not mixed and sinks is None and n <= ops.SKINNY_MAX_LAYERS and all(
                 ops.short_admits(x2, A, B, acc_down, acc_up, bias) for (A, B, _, _, bias), (acc_down, acc_up) in zip(per, accs)):
             res = ops.sow_forward_short([(x2, A, B, acc_down, bias, s) for (A, B, _, _, bias), (acc_down, _), s in zip(per, accs, scales)],
@@ -94,30 +107,37 @@ class _SoWGroupFunction(torch.autograd.Function):
         return tuple(c.y.reshape(*lead, c.y.shape[1]) for c in calls)
 
     @staticmethod
+    def _short_backward(ctx, x2, hs, tensors, dys, codes: bool):
+        """The siblings' data gradients in one sow_backward_short call (codes: sow_backward_short_codes on the (codes, scales) pairs),
+        then each layer's weight phases on its workspace."""
+        layers = []
+        for i in range(ctx.n):
+            A, B, acc_down, acc_up, bias = tensors[5 * i:5 * i + 5]
+            dy, d_out = dys[i], B.shape[1]
+            dy2 = torch.zeros(x2.shape[0], d_out, dtype=x2.dtype, device=x2.device) if dy is None else dy.reshape(-1, d_out).contiguous()
+            layers.append((dy2, x2, hs[i], A, B, (acc_down, acc_up) if codes else acc_down, ctx.scales[i], bias is not None))
+        res = (ops.sow_backward_short_codes if codes else ops.sow_backward_short)(layers)
+        dx = res[-1][0]        # (summed last sibling first: _input_grad)
+        for g in reversed(res[:-1]):
+            dx = dx + g[0]
+        grads = []
+        for (_, dA, dB, dbias) in res:
+            grads += [dA, dB, None, None, dbias]
+        return (dx.reshape(ctx.x_shape), None, None, None, None, *grads)
+
+    @staticmethod
     def backward(ctx, *dys):
         n = ctx.n
         saved = ctx.saved_tensors
         x2, hs, tensors = saved[0], saved[1:1 + n], list(saved[1 + n:])
+        if ctx.codes:      # (the codes as saved: no image is built)
+            return _SoWGroupFunction._short_backward(ctx, x2, hs, tensors, dys, True)
         for i, (acc_down, acc_up) in enumerate(ops.acc_operands([(tensors[5 * i + 2], tensors[5 * i + 3]) for i in range(n)],
                                                                 x2.dtype)):
             tensors[5 * i + 2], tensors[5 * i + 3] = acc_down, acc_up
         sinks = ctx.sinks
         if ctx.short:
-            # the siblings' data gradients in one sow_backward_short call, then each layer's weight phases on its workspace
-            layers = []
-            for i in range(n):
-                A, B, acc_down, _, bias = tensors[5 * i:5 * i + 5]
-                dy, d_out = dys[i], B.shape[1]
-                dy2 = torch.zeros(x2.shape[0], d_out, dtype=x2.dtype, device=x2.device) if dy is None else dy.reshape(-1, d_out).contiguous()
-                layers.append((dy2, x2, hs[i], A, B, acc_down, ctx.scales[i], bias is not None))
-            res = ops.sow_backward_short(layers)
-            dx = res[-1][0]        # (summed last sibling first: _input_grad)
-            for g in reversed(res[:-1]):
-                dx = dx + g[0]
-            grads = []
-            for (_, dA, dB, dbias) in res:
-                grads += [dA, dB, None, None, dbias]
-            return (dx.reshape(ctx.x_shape), None, None, None, None, *grads)
+            return _SoWGroupFunction._short_backward(ctx, x2, hs, tensors, dys, False)
         if sinks is not None and x2.shape[0] > 0 and all(
                 s.usable(tensors[5 * i], tensors[5 * i + 1], tensors[5 * i + 4]) for i, s in enumerate(sinks)):
             # FactorBucket.attach(): ONE data-gradient launch for the siblings, weight gradients queued with their decoder

@@ -92,13 +92,19 @@ class _SoWFunction(torch.autograd.Function):
         fuse = _fuse_acc(x2, B, acc_down, acc_up, cdt is not None)
         # an E4M3 accumulator (codes, exponents): the dense kernels run on its image in the scratch arena; what is saved
         # below is the codes, and backward builds the image again
-        (img_down, img_up), = ops.acc_operands([(acc_down, acc_up)], x2.dtype)
-        # inside sow_amd.short_rows: a dense accumulator (or the image of a quantised one) at a row count the measured rule keeps
-        # runs forward and data gradient on the skinny kernel pair; FactorBucket sinks and autocast keep the path below
+        # inside sow_amd.short_rows and sow_amd.short_codes: a quantised accumulator the format's pays_short rule keeps is read in
+        # place in both directions -- no image, no arena; FactorBucket sinks and autocast keep the paths below
         res = None
-        if cdt is None and sink is None and ops.short_admits(x2, A, B, img_down, img_up, bias):
-            res = ops.sow_forward_short([(x2, A, B, img_down, bias, scale)])
-        ctx.short = res is not None
+        if cdt is None and sink is None and ops.short_codes_admits(x2, A, B, acc_down, acc_up, bias):
+            res = ops.sow_forward_short_codes([(x2, A, B, (acc_down, acc_up), bias, scale)])
+        ctx.codes = res is not None
+        if res is None:
+            (img_down, img_up), = ops.acc_operands([(acc_down, acc_up)], x2.dtype)
+            # inside sow_amd.short_rows: a dense accumulator (or the image of a quantised one) at a row count the measured rule keeps
+            # runs forward and data gradient on the skinny kernel pair; FactorBucket sinks and autocast keep the path below
+            if cdt is None and sink is None and ops.short_admits(x2, A, B, img_down, img_up, bias):
+                res = ops.sow_forward_short([(x2, A, B, img_down, bias, scale)])
+        ctx.short = res is not None and not ctx.codes
         if res is not None:
             (y,), (h,) = res
         else:
@@ -116,10 +122,13 @@ class _SoWFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x2, h, A, B, acc_down, acc_up = ctx.saved_tensors
-        (acc_down, acc_up), = ops.acc_operands([(acc_down, acc_up)], x2.dtype)
         dy2 = dy.reshape(-1, dy.shape[-1])
         sink = ctx.sink
-        if ctx.short:
+        if not ctx.codes:
+            (acc_down, acc_up), = ops.acc_operands([(acc_down, acc_up)], x2.dtype)
+        if ctx.codes:
+            (dx, dA, dB, dbias), = ops.sow_backward_short_codes([(dy2, x2, h, A, B, (acc_down, acc_up), ctx.scale, ctx.has_bias)])
+        elif ctx.short:
             (dx, dA, dB, dbias), = ops.sow_backward_short([(dy2, x2, h, A, B, acc_down, ctx.scale, ctx.has_bias)])
         elif sink is not None and x2.shape[0] > 0 and sink.usable(A, B, ctx.bias):
             # FactorBucket.attach(): the weight gradients accumulate straight into the flat gradient buffer (p.grad is a
@@ -266,6 +275,11 @@ class SoWLinear(nn.Module):
                 ys = fwd([(x2, A, B, ops.skinny_acc(acc_down, acc_up), self.bias, float(self.scale))])
                 if ys is not None:
                     return ys[0].reshape(*x.shape[:-1], B.shape[1])
+            # inside sow_amd.short_rows and sow_amd.short_codes: the forward on the codes read in place, h_save = NULL
+            if cdt is None and ops.short_codes_admits(x2, A, B, acc_down, acc_up, self.bias):
+                res = ops.sow_forward_short_codes([(x2, A, B, (acc_down, acc_up), self.bias, float(self.scale))], save_h=False)
+                if res is not None:
+                    return res[0][0].reshape(*x.shape[:-1], B.shape[1])
             # every other call of a quantised layer: the existing dense path on the image
             (acc_down, acc_up), = ops.acc_operands([(acc_down, acc_up)], x2.dtype)
             # inside sow_amd.short_rows: 65 ... 1024 rows of a dense accumulator on the skinny pair, h_save = NULL

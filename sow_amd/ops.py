@@ -860,6 +860,182 @@ def sow_backward_short(layers):
     return out
 
 
+_SHORT_CODES = False       # sow_amd.short_codes / set_short_codes: inside short_rows, quantised layers read their codes in place
+_SHORT_CODES_WS_BYTES: dict = {}
+
+
+def set_short_codes(on: bool) -> bool:
+    """Whether, INSIDE sow_amd.short_rows, a layer whose dense accumulator is quantised (E4M3 / MXFP4) runs forward and data gradient
+    on the codes read in place (sow_forward_short_codes / sow_backward_short_codes: no image pass, no arena traffic) where the
+    format's pays_short rule admits the call.  Off by default and inert outside short_rows: with it off, a quantised layer inside
+    short_rows does what it did before (the image, then short_rows_pays).  Returns the value it replaces."""
+    global _SHORT_CODES
+    if not isinstance(on, bool):
+        raise ValueError(f"sow_amd.set_short_codes: {on!r} is not a bool")
+    old, _SHORT_CODES = _SHORT_CODES, on
+    return old
+
+
+@contextlib.contextmanager
+def short_codes(on: bool = True):
+    """with sow_amd.short_rows(), sow_amd.short_codes(): ...  -- set_short_codes(on) for the block, the earlier value restored after it."""
+    old = set_short_codes(on)
+    try:
+        yield
+    finally:
+        set_short_codes(old)
+
+
+def short_codes_enabled() -> bool:
+    """The switch itself; it routes calls only while short_rows_enabled() holds too (short_codes_admits)."""
+    return _SHORT_CODES
+
+
+def short_codes_workspace_bytes(T: int, d_in: int, d_out: int, r: int, kind: int, dt: int, forward_only: bool = False) -> int:
+    """sow_short_codes_workspace_bytes (forward_only: sow_forward_short_codes_workspace_bytes), memoised per shape: 0 = outside the
+    admitted set.  Pure functions of the shape."""
+    key = (T, d_in, d_out, r, kind, dt, forward_only)
+    n = _SHORT_CODES_WS_BYTES.get(key)
+    if n is None:
+        lib = _lib.load()
+        q = lib.sow_forward_short_codes_workspace_bytes if forward_only else lib.sow_short_codes_workspace_bytes
+        n = _SHORT_CODES_WS_BYTES[key] = int(q(T, d_in, d_out, r, kind, dt))
+    return n
+
+
+def short_codes_admits(x2: torch.Tensor, A: torch.Tensor, B: torch.Tensor, acc_down, acc_up, bias) -> bool:
+    """Whether a module call on the flattened input x2 goes to sow_forward_short_codes / sow_backward_short_codes: inside
+    sow_amd.short_rows AND sow_amd.short_codes, a bf16 / f16 call with parameters of the input's dtype, a well-formed (codes,
+    scales) pair of a format, a shape the library admits and the format's pays_short keeps.  False keeps the existing path."""
+    if not (_SHORT_ROWS and _SHORT_CODES):
+        return False
+    dt = _DT.get(x2.dtype)
+    if dt is None or dt == _lib.F32 or not x2.is_cuda or x2.dim() != 2 or A.dim() != 2 or B.dim() != 2:
+        return False
+    fmt = BY_CODE_DTYPE.get(acc_down.dtype) if acc_down is not None and acc_down.numel() else None
+    if fmt is None or acc_up is None or not fmt.well_formed(acc_down, acc_up):
+        return False
+    T, d_in = x2.shape
+    r, d_out = B.shape
+    if tuple(A.shape) != (d_in, r) or fmt.logical_shape(acc_down) != (d_in, d_out) or (bias is not None and tuple(bias.shape) != (d_out,)):
+        return False
+    if any(t is not None and (t.dtype != x2.dtype or t.device != x2.device) for t in (A, B, bias)) or any(
+            t.device != x2.device for t in (acc_down, acc_up)):
+        return False
+    return fmt.pays_short(T, d_in, d_out) and short_codes_workspace_bytes(T, d_in, d_out, r, fmt.kind, dt) > 0
+
+
+def _codes_pair(acc, name: str):
+    """(codes, scales, format) of the accumulator element of a sow_*_short_codes layer tuple."""
+    if not isinstance(acc, tuple) or len(acc) != 2:
+        raise TypeError(f"{name}: {_NOT_A_PAIR}")
+    codes, scales = acc
+    fmt = BY_CODE_DTYPE.get(codes.dtype)
+    if fmt is None or not fmt.well_formed(codes, scales):
+        raise TypeError(f"{name}: {_NOT_A_PAIR}")
+    return codes.contiguous(), scales.contiguous(), fmt
+
+
+def sow_forward_short_codes(layers, save_h: bool = True):
+    """sow_forward_short on codes read in place (include/sow_amd.h: sow_forward_short_codes): `layers` = one (x2, A, B, (codes,
+    scales), bias, scale) per layer, all pairs of ONE format, everything else of x2's dtype.  Returns (ys, hs) as sow_forward_short,
+    None when the library refuses the set: nothing was launched.  No image is built and the arena is not touched."""
+    lib = _lib.load()
+    name = "sow_amd.sow_forward_short_codes"
+    n = len(layers)
+    if n == 0:
+        return [], []
+    if n > SKINNY_MAX_LAYERS:
+        return None
+    x0 = layers[0][0]
+    dt = _dt(x0)
+    keep, sizes, total = [], [], 0
+    for x2, A, B, acc, bias, scale in layers:
+        codes, scales, fmt = _codes_pair(acc, name)
+        dev = _need_gpu(x2, A, B, codes, scales, bias)
+        if dev != x0.device or any(t is not None and t.dtype != x0.dtype for t in (x2, A, B, bias)):
+            raise TypeError(f"{name}: the tensors of a call share one dtype and one device")
+        T, d_in = x2.shape
+        r, d_out = B.shape
+        if tuple(A.shape) != (d_in, r) or fmt.logical_shape(codes) != (d_in, d_out) or (bias is not None and tuple(bias.shape) != (d_out,)):
+            raise ValueError(f"{name}: operand shapes do not match")
+        nws = short_codes_workspace_bytes(T, d_in, d_out, r, fmt.kind, dt, forward_only=True) if T else 0
+        if T and not nws:
+            return None
+        nws = (nws + 255) & ~255
+        keep.append((x2.contiguous(), A.contiguous(), B.contiguous(), codes, scales, None if bias is None else bias.contiguous(), fmt.kind))
+        sizes.append((total, nws))
+        total += nws
+    ws = _ws(total, x0.device)
+    base = ws.data_ptr()
+    arr = _short_args(n)
+    ys, hs = [], []
+    for i, ((x2, A, B, codes, scales, bias, kind), (off, nws), layer) in enumerate(zip(keep, sizes, layers)):
+        T, d_out = x2.shape[0], B.shape[1]
+        y = torch.empty((T, d_out), dtype=x2.dtype, device=x0.device)
+        h = torch.empty(T * 64, dtype=x2.dtype, device=x0.device) if save_h else None
+        ys.append(y)
+        hs.append(h)
+        a = arr[i]
+        a.x, a.A, a.B, a.acc_down, a.acc_up, a.bias, a.y, a.h_save = (_ptr(x2), _ptr(A), _ptr(B), _ptr(codes), _ptr(scales), _ptr(bias),
+                                                                      _ptr(y), _ptr(h))
+        a.T, a.d_in, a.d_out, a.r_live, a.acc_kind, a.scale = T, x2.shape[1], d_out, B.shape[0], kind, float(layer[5])
+        a.workspace, a.workspace_bytes = base + off, nws
+    rc = _launch_rc(x0.device, lib.sow_forward_short_codes, arr, n, dt)
+    if rc == _lib.ERR_UNSUPPORTED:
+        return None
+    _lib.check(rc, "sow_forward_short_codes")
+    return ys, hs
+
+
+def sow_backward_short_codes(layers):
+    """[(dx, dA, dB, dbias)] of n <= 16 layer calls: the data gradients through sow_backward_short_codes on the codes (one call for
+    the set), then the existing weight phases of every layer on the same workspace.  The weight phases read x, h, dY and dh and no
+    accumulator: they are called with kind SOW_ACC_DENSE (the plan the workspace is sized for) and the codes' address in acc_down's
+    place, which is checked against NULL and never read.  `layers` = one (dy2, x2, h, A, B, (codes, scales), scale, need_bias) per
+    layer, h from sow_forward_short_codes."""
+    lib = _lib.load()
+    name = "sow_amd.sow_backward_short_codes"
+    n = len(layers)
+    if n == 0:
+        return []
+    x0 = layers[0][1]
+    dt = _dt(x0)
+    arr = _short_args(n)
+    keep = []
+    for i, (dy2, x2, h, A, B, acc, scale, need_bias) in enumerate(layers):
+        codes, scales, fmt = _codes_pair(acc, name)
+        dev = _need_gpu(dy2, x2, h, A, B, codes, scales)
+        if any(t.dtype != x0.dtype or t.device != x0.device for t in (dy2, x2, h, A, B)):
+            raise TypeError(f"{name}: the tensors of a call share one dtype and one device")
+        T, d_in = x2.shape
+        r, d_out = B.shape
+        dy2, x2, A, B = dy2.contiguous(), x2.contiguous(), A.contiguous(), B.contiguous()
+        nws = short_codes_workspace_bytes(T, d_in, d_out, r, fmt.kind, dt) if T else 0
+        if T and not nws:
+            raise ValueError(f"{name}: the library does not admit this layer")
+        ws = _ws(max(nws, 256), dev)
+        dx = torch.empty((T, d_in), dtype=x2.dtype, device=dev)
+        a = arr[i]
+        a.dy, a.dx, a.A, a.B, a.acc_down, a.acc_up = _ptr(dy2), _ptr(dx), _ptr(A), _ptr(B), _ptr(codes), _ptr(scales)
+        a.T, a.d_in, a.d_out, a.r_live, a.acc_kind, a.scale = T, d_in, d_out, r, fmt.kind, float(scale)
+        a.workspace, a.workspace_bytes = _ptr(ws), ws.numel()
+        keep.append((dy2, x2, A, B, codes, scales, ws, dx))
+    _launch(x0.device, "sow_backward_short_codes", lib.sow_backward_short_codes, arr, n, dt)
+    out = []
+    for (dy2, x2, A, B, codes, scales, ws, dx), (_, _, h, _, _, _, scale, need_bias) in zip(keep, layers):
+        T, d_in = x2.shape
+        r, d_out = B.shape
+        dA = torch.empty((d_in, r), dtype=x2.dtype, device=x2.device)
+        dB = torch.empty((r, d_out), dtype=x2.dtype, device=x2.device)
+        dbias = torch.empty((d_out,), dtype=x2.dtype, device=x2.device) if need_bias else None
+        _launch(x2.device, "sow_backward", lib.sow_backward_ex, _ptr(dy2), _ptr(x2), _ptr(h), _ptr(A), _ptr(B), _ptr(codes), None,
+                _ptr(dx), _ptr(dA), _ptr(dB), _ptr(dbias), T, d_in, d_out, r, 0, _lib.ACC_DENSE, float(scale), 0.0, dt,
+                _ptr(ws), ws.numel(), int(_lib.BWD_WEIGHTS))
+        out.append((dx, dA, dB, dbias))
+    return out
+
+
 def workspace_bytes(T: int, d_in: int, d_out: int, r: int, r_acc: int, kind: int, dtype: torch.dtype,
                     param_f32: bool = False, fuse_acc=False, native: bool = False) -> int:
     """native: the accumulator next to fp32 parameters is of the compute dtype (acc_native): no room for its packed copy."""
