@@ -106,10 +106,11 @@ def _run(layers, runs=(0xFF, 0x00, 0xFF), what="codes", share_w=False, stages=("
                 assert torch.equal(E._bits(img.cpu()), E._bits(d["W"])), "the image is not W^"
                 W, sc = ar.input(img), None
         W0 = W0 if W0 is not None else (W, sc)
-        o = dict(y=ar.output((c.T, c.d_out)), h=ar.output((c.T, 64)), dx=ar.output((c.T, c.d_in)), dA=ar.output((c.d_in, c.r)),
+        rows = c.T or d["rows"]              # (a T = 0 layer: test_gpu_short_rows._run)
+        o = dict(y=ar.output((rows, c.d_out)), h=ar.output((rows, 64)), dx=ar.output((rows, c.d_in)), dA=ar.output((c.d_in, c.r)),
                  dB=ar.output((c.r, c.d_out)), dbias=ar.output((c.d_out,)) if c.bias else None)
-        nws = query(c.T, c.d_in, c.d_out, c.r, kind, dt)
-        assert nws >= lib.sow_workspace_bytes(c.T, c.d_in, c.d_out, c.r, 0, _lib.ACC_DENSE, dt) > 0
+        nws = query(rows, c.d_in, c.d_out, c.r, kind, dt)
+        assert nws >= lib.sow_workspace_bytes(rows, c.d_in, c.d_out, c.r, 0, _lib.ACC_DENSE, dt) > 0
         ws = ar.workspace(nws + 256 * i)
         a = arr[i]
         a.x, a.A, a.B, a.acc_down, a.acc_up, a.bias, a.y, a.h_save, a.dy, a.dx = (E._ptr(t) for t in (x, A, B, W, sc, bias, o["y"], o["h"], dy, o["dx"]))
@@ -127,18 +128,23 @@ def _run(layers, runs=(0xFF, 0x00, 0xFF), what="codes", share_w=False, stages=("
             dhs = [_dh(b[7], c) for (c, _), b in zip(layers, bufs)]
         if "weights" in stages:
             for (c, _), (x, A, B, bias, dy, W, sc, ws, o) in zip(layers, bufs):
+                if c.T == 0:
+                    continue
                 _lib.check(lib.sow_backward_ex(E._ptr(dy), E._ptr(x), E._ptr(o["h"]), E._ptr(A), E._ptr(B), E._ptr(W), None, E._ptr(o["dx"]),
                                                E._ptr(o["dA"]), E._ptr(o["dB"]), E._ptr(o["dbias"]), c.T, c.d_in, c.d_out, c.r, 0,
                                                _lib.ACC_DENSE, c.s, 0.0, dt, ws.data_ptr(), ws.numel(), _lib.BWD_WEIGHTS, E._stream()),
                            "sow_backward_ex")
         ar.check_guards(f"{what} run {len(outs)}")
+        for (c, _), b in zip(layers, bufs):
+            if c.T == 0:
+                P._untouched(byte, b[8], b[7], f"{what} run {len(outs)}")
         outs.append([dict({k: (None if v is None else v.clone()) for k, v in b[8].items()}, dh=dh) for b, dh in zip(bufs, dhs)])
     keys = [k for k, st in (("y", "fwd"), ("h", "fwd"), ("dx", "bwd"), ("dh", "bwd"), ("dA", "weights"), ("dB", "weights"), ("dbias", "weights"))
             if st in stages]
     for k in range(1, len(outs)):
         for i in range(n):
             for key in keys:
-                if outs[0][i][key] is not None:
+                if outs[0][i][key] is not None and layers[i][0].T:
                     assert torch.equal(E._bits(outs[0][i][key]), E._bits(outs[k][i][key])), f"{what}: {key} of layer {i} differs between run 0 and run {k}"
     return [{k: (None if v is None or k not in keys else v.cpu()) for k, v in o.items()} for o in outs[0]]
 

@@ -91,7 +91,9 @@ def _al256(n):
 
 def _run(layers, runs=(0xFF, 0x00, 0xFF), what="short", share_w=False, stages=("fwd", "bwd", "weights")):
     """One sow_forward_short + sow_backward_short call over `layers` ((Case, operands) pairs of one dtype), then the weight
-    phases layer by layer; repeated on re-poisoned memory.  Returns the outputs of the first run (CPU), one dict per layer."""
+    phases layer by layer; repeated on re-poisoned memory.  Returns the outputs of the first run (CPU), one dict per layer.
+    A layer of T = 0 (a Case of no rows over operands of d["rows"] rows; the calls skip it) has its outputs and its workspace
+    allocated for d["rows"] rows: every byte of them must keep what each run fills it with (_untouched)."""
     lib = _lib.load()
     dtype = layers[0][0].dtype
     dt = E._dt(dtype)
@@ -103,10 +105,11 @@ def _run(layers, runs=(0xFF, 0x00, 0xFF), what="short", share_w=False, stages=("
         x, A, B, bias, dy = (ar.input(d[k]) for k in ("x", "A", "B", "bias", "dy"))
         W = W0 if (share_w and W0 is not None) else ar.input(d["W"])
         W0 = W0 if W0 is not None else W
-        o = dict(y=ar.output((c.T, c.d_out)), h=ar.output((c.T, 64)), dx=ar.output((c.T, c.d_in)), dA=ar.output((c.d_in, c.r)),
+        rows = c.T or d["rows"]
+        o = dict(y=ar.output((rows, c.d_out)), h=ar.output((rows, 64)), dx=ar.output((rows, c.d_in)), dA=ar.output((c.d_in, c.r)),
                  dB=ar.output((c.r, c.d_out)), dbias=ar.output((c.d_out,)) if c.bias else None)
-        nws = lib.sow_short_workspace_bytes(c.T, c.d_in, c.d_out, c.r, _lib.ACC_DENSE, dt)
-        assert nws >= lib.sow_workspace_bytes(c.T, c.d_in, c.d_out, c.r, 0, _lib.ACC_DENSE, dt) > 0
+        nws = lib.sow_short_workspace_bytes(rows, c.d_in, c.d_out, c.r, _lib.ACC_DENSE, dt)
+        assert nws >= lib.sow_workspace_bytes(rows, c.d_in, c.d_out, c.r, 0, _lib.ACC_DENSE, dt) > 0
         ws = ar.workspace(nws + 256 * i)         # (workspaces of different sizes)
         a = arr[i]
         a.x, a.A, a.B, a.acc_down, a.bias, a.y, a.h_save, a.dy, a.dx = (E._ptr(t) for t in (x, A, B, W, bias, o["y"], o["h"], dy, o["dx"]))
@@ -122,19 +125,32 @@ def _run(layers, runs=(0xFF, 0x00, 0xFF), what="short", share_w=False, stages=("
             _lib.check(lib.sow_backward_short(arr, n, dt, E._stream()), "sow_backward_short")
         if "weights" in stages:
             for (c, _), (x, A, B, bias, dy, W, ws, o) in zip(layers, bufs):
+                if c.T == 0:
+                    continue
                 _lib.check(lib.sow_backward_ex(E._ptr(dy), E._ptr(x), E._ptr(o["h"]), E._ptr(A), E._ptr(B), E._ptr(W), None, E._ptr(o["dx"]),
                                                E._ptr(o["dA"]), E._ptr(o["dB"]), E._ptr(o["dbias"]), c.T, c.d_in, c.d_out, c.r, 0,
                                                _lib.ACC_DENSE, c.s, 0.0, dt, ws.data_ptr(), ws.numel(), _lib.BWD_WEIGHTS, E._stream()),
                            "sow_backward_ex")
         ar.check_guards(f"{what} run {len(outs)}")
+        for (c, _), b in zip(layers, bufs):
+            if c.T == 0:
+                _untouched(byte, b[7], b[6], f"{what} run {len(outs)}")
         outs.append([{k: (None if v is None else v.clone()) for k, v in b[7].items()} for b in bufs])
     keys = [k for k, st in (("y", "fwd"), ("h", "fwd"), ("dx", "bwd"), ("dA", "weights"), ("dB", "weights"), ("dbias", "weights")) if st in stages]
     for k in range(1, len(outs)):
         for i in range(n):
             for key in keys:
-                if outs[0][i][key] is not None:
+                if outs[0][i][key] is not None and layers[i][0].T:
                     assert torch.equal(E._bits(outs[0][i][key]), E._bits(outs[k][i][key])), f"{what}: {key} of layer {i} differs between run 0 and run {k}"
     return [{k: (None if v is None or k not in keys else v.cpu()) for k, v in o.items()} for o in outs[0]]
+
+
+def _untouched(byte, outs, ws, what):
+    """The outputs and the workspace of a T = 0 layer after a run on memory filled with `byte`: every byte is that byte still."""
+    fill = -1 if byte == 0xFF else 0
+    for k, v in outs.items():
+        assert v is None or bool((E._bits(v) == fill).all()), f"{what}: {k} of a T = 0 layer was stored to"
+    assert bool((ws == byte).all()), f"{what}: the workspace of a T = 0 layer was stored to"
 
 
 def _same(a, b, what):
